@@ -3,6 +3,13 @@
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--workload c3|c2|c4shard] [--aln N_ALN]     (N > 1: one process, one thread per GPU)
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...          (one process per GPU)
+    python bench.py ... --dump-outputs DIR      the last timed step's outputs of GPU 0 as DIR/<name>.npy (float64), for comparing two builds
+    python bench.py ... --full                  also everything beyond the headline figure (see below)
+
+A plain run sets up, warms up, times K steps and prints the line.  --full adds what takes runs of its own: the `sustained` repeat of the
+timed passes, the all-reduce on the second stream (N > 1), RCCL's log summary, the measured copy / read rates of the roofline, the CPU
+baseline with its parity spot check, and the untimed blocks north_star, long_read, hg002_shape, e2e and e2e_north_star (each of those
+can be left out of a --full run with its --no-* option).
 
 A step = one pass of the path over one batch: zero the count vector, classify every alignment of this rank's
 GAF shard (text already resident in HBM), all-reduce the per-SV counts (N > 1), genotype every VCF row — one library call
@@ -166,6 +173,28 @@ def timed_steps(ctxs, steps, warmup, min_support=3, err=0.00005, outer_barrier=N
     return dt, ms, outs[0]
 
 
+DUMP_MAX_BYTES = 64 << 20           # --dump-outputs: at most this many bytes of .npy data in all
+DUMP_SEED = 20260515                # the rows kept when the outputs are larger than that (same rows in every run of the same arguments)
+
+
+def dump_outputs(d, arrays):
+    """--dump-outputs: every array as d/<name>.npy in float64 (exact for the u8 / i32 / u32 results).  Over DUMP_MAX_BYTES in all,
+    the same fixed, seeded sample of rows is kept of every array of that length, and d/<name>_rows.npy names the rows kept."""
+    os.makedirs(d, exist_ok=True)
+    arrays = {k: np.asarray(v, dtype=np.float64) for k, v in arrays.items()}
+    total = sum(a.nbytes for a in arrays.values())
+    keep = {}
+    if total > DUMP_MAX_BYTES:
+        frac = DUMP_MAX_BYTES / 2 / total                      # (half the budget: room for the row indices)
+        for n in sorted({len(a) for a in arrays.values()} - {0}):
+            keep[n] = np.sort(np.random.default_rng(DUMP_SEED).choice(n, max(1, int(n * frac)), replace=False))
+    for k, a in arrays.items():
+        if len(a) in keep:
+            np.save(os.path.join(d, f"{k}_rows.npy"), keep[len(a)].astype(np.float64))
+            a = a[keep[len(a)]]
+        np.save(os.path.join(d, f"{k}.npy"), a)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -182,7 +211,11 @@ def main():
     ap.add_argument("--no-e2e-north-star", action="store_true", help="skip the untimed e2e_north_star block (configs[3] as files through the drop-in scripts; needs ~160 GB of /dev/shm)")
     ap.add_argument("--north-star-aln", type=int, default=NORTH_STAR["aln"], help="alignments of the north_star block (tests)")
     ap.add_argument("--north-star-svs", type=int, default=NORTH_STAR["svs"], help="SVs of the north_star block (tests)")
+    ap.add_argument("--full", action="store_true", help="also the measurements and checks beyond the headline figure (module docstring); off by default")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="write the last timed step's outputs (GPU 0) as DIR/<name>.npy, float64")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     # Two ways to N GPUs: under a launcher (torch.distributed.run: WORLD_SIZE ranks, one GPU each, RCCL communicator from a
     # unique id that travels over the launcher's process group), or — no launcher — this one process with one context and one
@@ -224,22 +257,25 @@ def main():
     # ---- inputs (untimed) --------------------------------------------------------------------------
     t0 = time.time()
     tmp = tempfile.mkdtemp(prefix="svjg_bench_")
+    import atexit
+    import shutil
+    atexit.register(shutil.rmtree, tmp, True)                   # (the generated inputs do not outlive the run)
     pre = os.path.join(tmp, "w")
     inf = synth.generate(pre, 0, n_sv, n_chrom, mix, seed, write_gaf=False)
     gaf = synth.gaf_bytes(inf["tables"], seed, rank * n_local * n_aln, n_aln, threads=min(16, os.cpu_count() or 8))   # this process's first shard
     graph = Graph.from_files(pre + "_svs_edges.json", pre + ".gfa")
     rows = genotype.VcfRows(pre + ".vcf", graph.slot_of)
     t_setup = time.time() - t0
-    cpu = cpu_rates(pre, gaf) if (not args.no_cpu_baseline and n_total_ranks == 1) else None   # (forks workers: before the GPU is touched)
+    cpu = cpu_rates(pre, gaf) if (args.full and not args.no_cpu_baseline and n_total_ranks == 1) else None   # (forks workers: before the GPU is touched)
     lr_in = None
-    if not args.no_long_read and n_total_ranks == 1 and not os.environ.get("SVJG_BENCH_CAPI"):
+    if args.full and not args.no_long_read and n_total_ranks == 1 and not os.environ.get("SVJG_BENCH_CAPI"):
         try:                                                     # its inputs, and (the checker) the C oracle over ALL of its lines on all cores — forks too
             lr_in = long_read_inputs(synth, tmp, check=not args.no_cpu_baseline)
         except Exception as e:                                   # noqa: BLE001
             lr_in = {"failed": f"{type(e).__name__}: {e}"[:300]}
 
     hg_in = None
-    if not args.no_hg002_shape and n_total_ranks == 1 and not os.environ.get("SVJG_BENCH_CAPI"):
+    if args.full and not args.no_hg002_shape and n_total_ranks == 1 and not os.environ.get("SVJG_BENCH_CAPI"):
         try:
             hg_in = hg002_shape_inputs(synth, tmp, check=not args.no_cpu_baseline)
         except Exception as e:                                   # noqa: BLE001
@@ -257,7 +293,7 @@ def main():
         t_h2d = max(t_h2d, time.time() - t1)
         del text
     rccl = None
-    rccl_log = rccl_debug_capture(tmp) if n_total_ranks > 1 else None     # (NCCL_DEBUG must be in the environment before the communicator exists)
+    rccl_log = rccl_debug_capture(tmp) if (args.full and n_total_ranks > 1) else None     # (NCCL_DEBUG must be in the environment before the communicator exists)
     t_comm = time.perf_counter()
     if world > 1:
         import dist_boot
@@ -292,13 +328,19 @@ def main():
     dt, kms, out = timed_steps(ctxs, args.steps, args.warmup, outer_barrier=outer)
     dt = max_over_ranks(dt)
     out = tuple(np.array(x) for x in out)                     # (views of the library's pinned result block: copied before anything else runs)
-    # the same passes again, as many as span MIN_SUSTAINED_S (every rank computes the same number from the timed figure all of them hold)
-    n_sus = max(args.steps, int(MIN_SUSTAINED_S / max(dt / args.steps, 1e-6)) + 1)
-    dt_sus, kms_sus, _ = timed_steps(ctxs, n_sus, 0, outer_barrier=outer)
-    dt_sus = max_over_ranks(dt_sus)
+    counts = ctxs[0].counts()                                 # (the last timed pass's count vector, summed over the ranks when N > 1)
+    if args.dump_outputs and rank == 0:
+        gt, pl, raw, flags = out
+        dump_outputs(args.dump_outputs, {"gt": gt, "pl": pl, "raw": raw, "flags": flags, "counts": counts})
+    n_sus = dt_sus = kms_sus = None
+    if args.full:
+        # the same passes again, as many as span MIN_SUSTAINED_S (every rank computes the same number from the timed figure all of them hold)
+        n_sus = max(args.steps, int(MIN_SUSTAINED_S / max(dt / args.steps, 1e-6)) + 1)
+        dt_sus, kms_sus, _ = timed_steps(ctxs, n_sus, 0, outer_barrier=outer)
+        dt_sus = max_over_ranks(dt_sus)
     # N > 1: the all-reduce of a pass on the compute stream (above, `value`) and on the second stream, both measured
     second = None
-    if n_total_ranks > 1 and hasattr(ctxs[0], "allreduce_on_second_stream"):
+    if args.full and n_total_ranks > 1 and hasattr(ctxs[0], "allreduce_on_second_stream"):
         try:                                                     # (a leg beside the point of the run: its failure is reported in its place)
             for c in ctxs:
                 c.allreduce_on_second_stream(True)
@@ -319,10 +361,9 @@ def main():
 
     ctx = ctxs[0]
     st = ctx.stats()
-    counts = ctx.counts()
     gt, pl, raw, done = out
     copy_gbs = read_gbs = None
-    if rank == 0 and hasattr(ctx, "copy_rate"):
+    if args.full and rank == 0 and hasattr(ctx, "copy_rate"):
         try:
             copy_gbs, read_gbs = ctx.copy_rate(1 << 31)          # 2 GB read + 2 GB written / 2 GB read, in this process, on this GPU
         except Exception as e:                                   # noqa: BLE001 (a measurement beside the point of the run)
@@ -330,7 +371,7 @@ def main():
     # the untimed blocks must never cost the line its `value`: a failure in one of them is reported in its place
     ns = None
     e2e_ns_dir = e2e_ns_skip = None                              # the files of configs[3] for the e2e_north_star leg (rank 0 writes the text as it uploads it), or why there are none
-    if not args.no_north_star:
+    if args.full and not args.no_north_star:
         if (not args.no_e2e_north_star and not args.no_e2e and rank == 0 and n_total_ranks == 1 and not os.environ.get("SVJG_BENCH_CAPI")
                 and args.north_star_aln == NORTH_STAR["aln"] and args.north_star_svs == NORTH_STAR["svs"]):
             e2e_ns_dir, e2e_ns_skip = e2e_scratch(E2E_NS_BYTES)
@@ -388,10 +429,10 @@ def main():
                          "kernel": "k_classify_main", "algorithmic_bytes_per_launch": gaf_bytes_0},
             "setup_s": {"generate_and_tables": round(t_setup, 1), "h2d_upload": round(t_h2d, 3), "settle_passes_untimed": n_settle,
                         "pcie_inclusive_alignments_per_s": n_aln / (t_h2d + ms_per_step * 1e-3)},
-            # the timed passes again, repeated until they span >= MIN_SUSTAINED_S: per-step mean over all of them
-            "sustained": {"steps": n_sus, "seconds": dt_sus, "ms_per_step": dt_sus / n_sus * 1e3, "alignments_per_s": total_aln * n_sus / dt_sus,
-                          "classify_main_ms": float(np.mean([m[0] for per in kms_sus for m in per]))},
         }
+        if n_sus:                                                # the timed passes again, repeated until they span >= MIN_SUSTAINED_S: per-step mean over all of them
+            res["sustained"] = {"steps": n_sus, "seconds": dt_sus, "ms_per_step": dt_sus / n_sus * 1e3, "alignments_per_s": total_aln * n_sus / dt_sus,
+                                "classify_main_ms": float(np.mean([m[0] for per in kms_sus for m in per]))}
         if copy_gbs:
             res["roofline"]["measured_copy_gbs"] = copy_gbs      # bytes read + written per second by a plain copy kernel in this process
             res["roofline"]["frac_of_measured_copy"] = achieved / copy_gbs
@@ -406,7 +447,8 @@ def main():
         if rccl:
             rccl["allreduce_stream"] = {"compute": {"ms_per_step": ms_per_step, "classify_main_ms": k_main}, "second": second,
                                         "value_is": "compute (the all-reduce between this pass's kernels and the next pass's)"}
-            rccl.update(rccl_debug_summary(rccl_log))
+            if rccl_log is not None:
+                rccl.update(rccl_debug_summary(rccl_log))
             res["rccl"] = rccl
         # HBM-side bytes per launch come from separate rocprofv3 --pmc passes of this same command (profiles/<round>/traffic.json,
         # the newest round that has one)
@@ -428,9 +470,9 @@ def main():
                                                      "issue_ms": round(issue_ms, 3), "frac_of_launch": round(issue_ms / k_main, 3)}
         except (OSError, ValueError, KeyError, IndexError):
             pass
-        if not args.no_cpu_baseline and n_total_ranks == 1:    # reported on rank 0 at N = 1 only
+        if cpu is not None:                                     # reported on rank 0 at N = 1 only
             res["cpu_baseline"] = cpu_baseline(pre, graph, counts, cpu)
-        if not args.no_e2e and n_total_ranks == 1 and args.workload in ("c2", "c3") and not args.aln and not args.svs:
+        if args.full and not args.no_e2e and n_total_ranks == 1 and args.workload in ("c2", "c3") and not args.aln and not args.svs:
             for c in ctxs:
                 c.close()                                        # (the scripts open the GPU themselves)
             ctxs = []

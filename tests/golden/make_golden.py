@@ -27,6 +27,7 @@ Fixture groups:
   hg002shape/ G14 (r06) BASELINE configs[4]'s shape: the graph built by the reference's construct-graph.py, 200 k lines and the whole 4.65 M-line
                  block through its filter and genotyper
   contigs/   G10 GRCh38 analysis-set contig names (HLA-DRB1*15:03:01:01, chrUn_JTFH01001998v1_decoy, chr6_GL000250v2_alt, chrEBV)
+  graphlayout/ G15 the graph files construct-graph.py writes for two synthetic VCFs (edges JSON, GFA with ref sequences elided, gzip)
   realshape/ G7  lines shaped like real minigraph output (read names, cg:Z: / ds:Z: tags, paths of up to 300 nodes,
                  UCSC contig names) on a 600-SV graph, with the reference's JSON and VCF
              full  c2_full.json / c3_full.json / c4slice_full.json: sha256 of the reference's JSON and VCF for the
@@ -1290,6 +1291,54 @@ def make_contigs():
 
 
 # ----------------------------------------------------------------------------------------------
+# G15 graph layout: tools/synth.py's graph files against construct-graph.py's (tests/test_synth_vs_reference.py)
+# ----------------------------------------------------------------------------------------------
+
+GRAPHLAYOUT_CASES = [(300, 3, "mixed", 7), (200, 1, "del", 8)]
+
+
+def elide_gfa(lines):
+    """GFA lines with the reference sequences elided (S lines of nodes without a '.' in the last ':' field): what the filter reads"""
+    out = []
+    for ln in lines:
+        if ln.startswith("S"):
+            c = ln.rstrip("\n").split("\t")
+            if "." not in c[1].split(":")[-1]:
+                ln = f"S\t{c[1]}\t*\n"
+        out.append(ln)
+    return out
+
+
+def make_graphlayout():
+    """golden/graphlayout/<n_sv>-<n_chrom>-<mix>-<seed>{_svs_edges.json,.elided.gfa}.gz: the graph files construct-graph.py writes for
+    tools/synth.py's VCF of each case and a random FASTA of its contigs, the GFA with the reference sequences elided (gzip, mtime 0)"""
+    import gzip
+    sys.path.insert(0, f"{ROOT}/tools")
+    import synth
+    out = f"{HERE}/graphlayout"
+    os.makedirs(out, exist_ok=True)
+    for n_sv, n_chrom, mix, seed in GRAPHLAYOUT_CASES:
+        tmp = tempfile.mkdtemp()
+        pre = f"{tmp}/s"
+        inf = synth.generate(pre, 100, n_sv, n_chrom, mix, seed)
+        rng = np.random.default_rng(1)
+        with open(f"{tmp}/ref.fa", "w") as fh:
+            for c, l in zip(inf["chroms"], inf["chrom_len"]):
+                s = "".join(rng.choice(list("ACGT"), size=l))
+                fh.write(f">{c}\n" + "\n".join(s[i:i + 80] for i in range(0, l, 80)) + "\n")
+        os.makedirs(f"{tmp}/r")
+        subprocess.run([sys.executable, f"{REF}/construct-graph.py", "-v", pre + ".vcf", "-r", f"{tmp}/ref.fa", "-o", f"{tmp}/r/s.gfa"],
+                       check=True, capture_output=True)
+        tag = f"{n_sv}-{n_chrom}-{mix}-{seed}"
+        for name, text in ((f"{tag}_svs_edges.json.gz", open(f"{tmp}/r/s_svs_edges.json").read()),
+                           (f"{tag}.elided.gfa.gz", "".join(elide_gfa(open(f"{tmp}/r/s.gfa"))))):
+            with open(f"{out}/{name}", "wb") as fo, gzip.GzipFile(fileobj=fo, mode="wb", mtime=0, compresslevel=9) as gz:
+                gz.write(text.encode())
+        shutil.rmtree(tmp)
+    print("graphlayout:", sorted(os.listdir(out)))
+
+
+# ----------------------------------------------------------------------------------------------
 # G6 medium synthetic (needs tools/svjg_synth built)
 # ----------------------------------------------------------------------------------------------
 
@@ -1565,7 +1614,7 @@ def make_full(which=("c2", "c3", "c4slice")):
 
 if __name__ == "__main__":
     which = sys.argv[1:] or ["testdir", "quirks", "unicode", "lik", "lik_boundary", "vcf", "synth", "realshape", "utf8order", "nosv", "vcffuzz", "graphfuzz", "dover", "longpath", "contigs", "longtail",
-                             "blanks", "fuzz7"]          # (hg002shape: minutes and 7 GB of scratch — by name)
+                             "blanks", "fuzz7", "graphlayout"]          # (hg002shape: minutes and 7 GB of scratch — by name)
     for w in which:
         if w.startswith("full"):                   # full | full:c2,c3,c4slice
             make_full(tuple(w.split(":")[1].split(",")) if ":" in w else ("c2", "c3", "c4slice"))

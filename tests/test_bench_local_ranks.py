@@ -118,7 +118,7 @@ def test_bench_under_the_launcher_two_ranks(tmp_path):
     env = dict(os.environ, SVJG_BENCH_CAPI="tests.standin_capi", PYTHONPATH=ROOT + os.pathsep + os.environ.get("PYTHONPATH", ""))
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
            "--master-port", str(port), os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1",
-           "--aln", "2000", "--svs", "300", "--no-e2e", "--no-cpu-baseline", "--north-star-aln", "3000", "--north-star-svs", "200"]
+           "--aln", "2000", "--svs", "300", "--full", "--no-e2e", "--no-cpu-baseline", "--north-star-aln", "3000", "--north-star-svs", "200"]
     p = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=600, cwd=str(tmp_path))
     assert p.returncode == 0, p.stderr[-3000:]
     lines = [l for l in p.stdout.splitlines() if l.startswith("{")]
@@ -137,3 +137,47 @@ def test_bench_under_the_launcher_two_ranks(tmp_path):
     assert "allreduce_stream" in r["rccl"] and "debug_info" in r["rccl"]
     ars = r["rccl"]["allreduce_stream"]                           # both placements of the pass's all-reduce were timed
     assert ars["compute"]["ms_per_step"] > 0 and ars["second"]["steps"] >= 2 and ars["second"]["ms_per_step"] > 0
+
+
+def _plain_run(tmp_path, *extra):
+    import json
+    import subprocess
+    env = dict(os.environ, SVJG_BENCH_CAPI="tests.standin_capi", PYTHONPATH=ROOT + os.pathsep + os.environ.get("PYTHONPATH", ""))
+    for k in ("RANK", "WORLD_SIZE", "LOCAL_RANK"):
+        env.pop(k, None)
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1", "--aln", "2000", "--svs", "300", *extra]
+    p = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=600, cwd=str(tmp_path))
+    assert p.returncode == 0, p.stderr[-3000:]
+    lines = [l for l in p.stdout.splitlines() if l.startswith("{")]
+    assert len(lines) == 1, p.stdout
+    return json.loads(lines[0])
+
+
+def test_bench_plain_run_is_the_headline_and_dumps_its_outputs(tmp_path):
+    """a plain run: the headline line without the --full legs; --dump-outputs: the last timed step's arrays, float64, the same in two runs"""
+    runs = []
+    for i in range(2):
+        d = tmp_path / f"out{i}"
+        r = _plain_run(tmp_path, "--dump-outputs", str(d))
+        for k in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step"):
+            assert k in r
+        assert r["steps"] == 3 and r["warmup"] == 1 and abs(r["value"] - 2000 * 3 / (r["ms_per_step"] * 3e-3)) < 1e-6 * r["value"]
+        assert not {"sustained", "north_star", "long_read", "hg002_shape", "cpu_baseline", "e2e", "e2e_north_star"} & set(r)
+        runs.append({k: np.load(d / f"{k}.npy") for k in ("gt", "pl", "raw", "flags", "counts")})
+    a, b = runs
+    assert all(x.dtype == np.float64 for x in a.values())
+    assert a["pl"].shape == (300, 3) and a["raw"].shape == (300, 2) and a["counts"].shape[1] == 2 and a["counts"].sum() > 0
+    assert all(np.array_equal(a[k], b[k]) for k in a)
+
+
+def test_dump_outputs_keeps_a_fixed_sample_within_the_cap(tmp_path, monkeypatch):
+    monkeypatch.setattr(bench, "DUMP_MAX_BYTES", 1 << 16)
+    big = {"pl": np.arange(30000, dtype=np.int32).reshape(10000, 3), "gt": np.arange(10000) % 3, "counts": np.arange(4000).reshape(2000, 2)}
+    for d in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / d), big)
+    files = sorted(os.listdir(tmp_path / "a"))
+    assert sum(os.path.getsize(tmp_path / "a" / f) for f in files) <= (1 << 16) + 128 * len(files)      # (+ the .npy headers)
+    rows = np.load(tmp_path / "a" / "pl_rows.npy").astype(np.int64)
+    assert np.array_equal(np.load(tmp_path / "a" / "pl.npy"), big["pl"][rows].astype(np.float64))
+    assert np.array_equal(np.load(tmp_path / "a" / "gt.npy"), big["gt"][rows].astype(np.float64))      # (the same rows of every array of that length)
+    assert all(np.array_equal(np.load(tmp_path / "a" / f), np.load(tmp_path / "b" / f)) for f in files)

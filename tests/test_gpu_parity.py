@@ -2159,7 +2159,7 @@ def test_bench_single_process_two_gpus():
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     have = capi.device_count()
     r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--workload", "c2", "--aln", "200000", "--steps", "2", "--warmup", "1",
-                        "--no-cpu-baseline", "--no-e2e", "--north-star-aln", "400000", "--north-star-svs", "5000"], capture_output=True, text=True, timeout=600)
+                        "--full", "--no-cpu-baseline", "--no-e2e", "--north-star-aln", "400000", "--north-star-svs", "5000"], capture_output=True, text=True, timeout=600)
     if have < 2:
         assert r.returncode != 0 and "needs 2 devices, found" in r.stderr and not r.stdout.strip()
         return

@@ -10,10 +10,10 @@ shift || true
 WL="${*:-c3 c4shard}"
 export TMPDIR=/tmp
 cd $R
-python3 bench.py --workload c3 > $O/bench_c3.json 2> $O/bench.err
-python3 bench.py --workload c2 --no-cpu-baseline --no-north-star --no-long-read --no-hg002-shape > $O/bench_c2.json 2>> $O/bench.err
-python3 bench.py --workload c4shard --no-cpu-baseline --no-north-star --no-long-read --no-hg002-shape > $O/bench_c4shard.json 2>> $O/bench.err
-SVJG_BENCH_SYNC=1 python3 bench.py --workload c3 --no-cpu-baseline --no-e2e --no-north-star --no-long-read --no-hg002-shape > $O/bench_c3_one_pass_at_a_time.json 2>> $O/bench.err
+python3 bench.py --workload c3 --full > $O/bench_c3.json 2> $O/bench.err
+python3 bench.py --workload c2 --full --no-cpu-baseline --no-north-star --no-long-read --no-hg002-shape > $O/bench_c2.json 2>> $O/bench.err
+python3 bench.py --workload c4shard --full --no-cpu-baseline --no-north-star --no-long-read --no-hg002-shape > $O/bench_c4shard.json 2>> $O/bench.err
+SVJG_BENCH_SYNC=1 python3 bench.py --workload c3 --full --no-cpu-baseline --no-e2e --no-north-star --no-long-read --no-hg002-shape > $O/bench_c3_one_pass_at_a_time.json 2>> $O/bench.err
 for W in $WL; do
   # (a workload of bench.py, or one of its untimed blocks alone — tools/block_run.py long_read | hg002_shape — so that no other launch of the kernel sits under its name)
   B="python3 bench.py --workload $W --no-cpu-baseline --no-e2e --no-north-star --no-long-read --no-hg002-shape --steps 10 --warmup 2"
