@@ -893,8 +893,10 @@ extern "C" int svjg_allreduce_counts_all(svjg_ctx *const *ctxs, int n) {
 
 // ---- genotypes -----------------------------------------------------------------------------------------
 
-// table of log10(i!) in double-double for the binomial term, at least `upto` entries (kernels on the context's stream; no host wait)
+// table of log10(i!) in double-double for the binomial term, at least `upto` entries and at most LOGFACT_CAP (svjg_geno.h: rows beyond
+// the cap are recomputed on the host) (kernels on the context's stream; no host wait)
 static int build_logfact(svjg_ctx *c, uint32_t upto) {
+    if (upto > LOGFACT_CAP) upto = LOGFACT_CAP;
     const uint32_t want = (upto + LF_BLOCK - 1) / LF_BLOCK * LF_BLOCK;
     hipFree(c->d_logfact); hipFree(c->d_bsum); c->d_logfact = nullptr; c->d_bsum = nullptr; c->logfact_n = 0;
     HIPCHK(c, hipMalloc((void **)&c->d_logfact, (uint64_t)want * sizeof(dd)));
@@ -956,7 +958,7 @@ static int genotype_rows(svjg_ctx *c, const uint8_t *sv_type, const uint32_t *sl
         const unsigned int max_n = *(const unsigned int *)(hb + maxn_off);
         if (max_n == 0) break;                               // every row found its binomial term
         if (attempt == 1) { c->err = "log10(i!) table could not be sized"; return SVJG_E_HIP; }
-        grow_to = max_n + 1 + 1024;
+        grow_to = max_n < LOGFACT_CAP - 1024 ? max_n + 1 + 1024 : LOGFACT_CAP;     // (the kernel reports only n < LOGFACT_CAP)
         c->logfact_n = 0;                                    // rebuild, sized by max_n
     }
     HIPCHK(c, hipEventElapsedTime(&c->ms_geno, c->ev[4], c->ev[5]));
@@ -1218,7 +1220,7 @@ extern "C" int svjg_run_end(svjg_ctx *c, const uint8_t **gt, const int32_t **pl,
                 // (a pass already enqueued behind this one still uses the old table: it must drain before the table is replaced)
                 HIPCHK(c, hipStreamSynchronize(c->stream));
                 HIPCHK(c, hipStreamSynchronize(c->copy_stream));
-                if ((rc = build_logfact(c, max_n + 1 + 1024))) return rc;
+                if ((rc = build_logfact(c, max_n < LOGFACT_CAP - 1024 ? max_n + 1 + 1024 : LOGFACT_CAP))) return rc;   // (only n < LOGFACT_CAP is reported)
             }
             again = false;
             GenoArgs ga = run_geno_args(c, r, L, r.min_support, r.err, redo_counts);

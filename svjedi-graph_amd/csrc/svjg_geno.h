@@ -1,0 +1,114 @@
+// The per-row arithmetic of k_genotype (svjg_kernels.h): the reference's likelihood() (predict-genotype.py:281-338) in fp64 /
+// double-double.  Plain C++ so that tests/hostsim compiles the same code with g++ and checks it against known answers of the
+// reference on a machine without a GPU (and under -fsanitize=address,undefined, tools/asan.sh).
+#pragma once
+#include <math.h>
+#include <stdint.h>
+
+#ifndef SVJG_HD
+#define SVJG_HD __host__ __device__ inline __attribute__((always_inline))
+#endif
+
+namespace svjg {
+
+struct dd { double hi, lo; };
+
+SVJG_HD dd two_sum(double a, double b) {
+    double s = a + b, bb = s - a;
+    return dd{s, (a - (s - bb)) + (b - bb)};
+}
+SVJG_HD dd dd_add(dd a, dd b) {
+    dd s = two_sum(a.hi, b.hi);
+    dd t = two_sum(a.lo, b.lo);
+    s.lo += t.hi;
+    s = two_sum(s.hi, s.lo);          // quick renormalisation (|lo| << |hi| here)
+    s.lo += t.lo;
+    return two_sum(s.hi, s.lo);
+}
+SVJG_HD dd dd_neg(dd a) { return dd{-a.hi, -a.lo}; }
+SVJG_HD int dd_cmp(dd a, dd b) { return a.hi < b.hi ? -1 : a.hi > b.hi ? 1 : a.lo < b.lo ? -1 : a.lo > b.lo ? 1 : 0; }
+
+SVJG_HD int64_t trunc_dd(dd v) {                         // int(Decimal): toward zero
+    double t = trunc(v.hi);
+    if (t == v.hi) {                                     // hi is integral: the tail decides
+        if (v.hi > 0 && v.lo < 0) t -= 1.0;
+        else if (v.hi < 0 && v.lo > 0) t += 1.0;
+    }
+    return (int64_t)t;
+}
+
+// The log10(i!) table (k_logfact_*) never grows beyond LOGFACT_CAP entries (256 MB).  A row whose binomial term would need more
+// (n = r1 + r2 >= LOGFACT_CAP, both r1 and r2 > 0) is not computed from the table: the kernel flags it like a row next to an
+// integer boundary, and the host recomputes it with the reference's arithmetic (svjg/genotype.py: exact_pl).
+constexpr uint32_t LOGFACT_CAP = 1u << 24;
+
+// A row is flagged for the host when one of its three -10 * (lik + comb) lies within PL_GUARD of an integer.  The budget, for
+// n < LOGFACT_CAP: every table entry is a sum of at most n values log10(i) < 7.3, each within 1 ulp (2^-50) if the device log10
+// is (assumed, not measured), summed in double-double: |table error| <= 2^24 * 2^-50 = 1.5e-8 per entry, and comb takes one
+// entry of n terms and two of n terms together: <= 3e-8.  The reference's log10 of a big integer goes through CPython's frexp
+// path, log10(x) + log10(2) * e: a few ulps of L = log10(comb) <= 5.1e6 (ulp 9.3e-10): <= 4e-9.  Both sides round L to a
+// double (1 ulp each).  The likelihood sums are exact here and at 28 digits in the reference.  Times ten: < 3.6e-7 < 1e-6.
+constexpr double PL_GUARD = 1e-6;
+
+// normalised counts (predict-genotype.py:327-338) and the rounded ones fed to comb()
+SVJG_HD void geno_counts(uint32_t type, uint32_t ref, uint32_t alt, double &c1, double &c2, uint32_t &r1, uint32_t &r2) {
+    c1 = (double)ref; c2 = (double)alt;
+    if (type == 0 && ref) c1 = (double)ref * 0.5;       // round(x/2, 1) is exact for halves
+    if (type == 1 && alt) c2 = (double)alt * 0.5;
+    r1 = (uint32_t)rint(c1); r2 = (uint32_t)rint(c2);   // int(round(c, 0)): half to even
+}
+
+// n = r1 + r2 of a row, computed in 64 bits (ref + alt reaches 2^33 - 2)
+SVJG_HD uint64_t geno_n(uint32_t r1, uint32_t r2) { return (uint64_t)r1 + r2; }
+
+enum : uint32_t { GENO_ROW_OK = 0, GENO_ROW_GROW = 1, GENO_ROW_HOST = 2 };
+
+struct GenoRow {
+    int64_t pl[3];
+    uint8_t gt;
+    bool near;       // one of the three PLs lies within PL_GUARD of an integer, or the row is beyond the table's cap: the host recomputes it
+    uint64_t n;      // r1 + r2
+};
+
+// One genotyped row.  -> GENO_ROW_OK, GENO_ROW_GROW (the table is too short for n < LOGFACT_CAP: the host grows it and runs the rows
+// again; the PLs are without the binomial term) or GENO_ROW_HOST (n >= LOGFACT_CAP: row flagged, PLs without the binomial term).
+SVJG_HD uint32_t geno_row(uint32_t type, uint32_t ref, uint32_t alt, uint32_t min_support, double l_ok, double l_err, double l_half,
+                          const dd *logfact, uint32_t logfact_n, GenoRow &o) {
+    double c1, c2; uint32_t r1, r2;
+    geno_counts(type, ref, alt, c1, c2, r1, r2);
+    // products in double, sums exact (the reference adds Decimal images of the doubles, :295-297)
+    dd l0 = two_sum(c1 * l_ok, c2 * l_err);
+    dd l1 = dd{(c1 + c2) * l_half, 0.0};
+    dd l2 = two_sum(c2 * l_ok, c1 * l_err);
+    int c01 = dd_cmp(l0, l1), c02 = dd_cmp(l0, l2), c12 = dd_cmp(l1, l2);
+    uint8_t g = 3;
+    if (c01 > 0 && c02 > 0) g = 0; else if (c01 < 0 && c12 > 0) g = 1; else if (c02 < 0 && c12 < 0) g = 2;
+    if (!(c1 + c2 >= (double)min_support)) g = 3;
+    o.gt = g;
+    const uint64_t n = geno_n(r1, r2);                  // (never a wrapped sum: no index comes from one)
+    o.n = n;
+    uint32_t st = GENO_ROW_OK;
+    dd comb{0.0, 0.0};                                   // comb(n, 0) = comb(n, n) = 1: no table needed
+    if (r1 && r2) {
+        if (n < logfact_n) comb = dd_add(dd_add(logfact[n], dd_neg(logfact[n - r1])), dd_neg(logfact[r1]));
+        else st = n < LOGFACT_CAP ? GENO_ROW_GROW : GENO_ROW_HOST;
+    }
+    comb = dd{comb.hi, 0.0};                             // the reference rounds log10(comb) to a double first (:313)
+    dd ls[3] = {l0, l1, l2};
+    bool near = false;
+    for (int i = 0; i < 3; ++i) {
+        dd s = dd_add(ls[i], comb);
+        dd p = dd_add(dd_add(dd_add(s, s), dd_add(s, s)), s);             // 5 s
+        p = dd_add(p, p);                                                 // 10 s
+        o.pl[i] = trunc_dd(dd_neg(p));
+        // The reference adds Decimal(math.log10(math.comb(n, k))) (:313): libm's log10 of a big integer rounded to a double, which
+        // need not be the correctly rounded value this kernel uses.  The two can differ in the last places; times ten, next to an
+        // integer, that could turn a PL by one.  Rows that close are flagged and recomputed on the host (svjg/genotype.py).
+        // (the fraction from hi AND lo: above |p| ~ 2^33 hi alone cannot resolve PL_GUARD)
+        { const double fr = fabs((p.hi - rint(p.hi)) + p.lo); if (fr < PL_GUARD && comb.hi != 0.0) near = true; }   // (comb = log10(1) = 0 on both sides: nothing to disagree about)
+    }
+    o.near = near || st == GENO_ROW_HOST;
+    return st;
+}
+
+}  // namespace svjg

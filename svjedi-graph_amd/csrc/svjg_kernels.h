@@ -14,6 +14,7 @@
 #include "svjg_line.h"
 #include "svjg_planes.h"
 #include "svjg_pass.h"
+#include "svjg_geno.h"
 
 namespace svjg {
 
@@ -1855,23 +1856,6 @@ __global__ __launch_bounds__(TPB) void k_counts_guard(unsigned long long *counts
 // genotype likelihoods
 // ---------------------------------------------------------------------------------------------------
 
-struct dd { double hi, lo; };
-
-__device__ inline dd two_sum(double a, double b) {
-    double s = a + b, bb = s - a;
-    return dd{s, (a - (s - bb)) + (b - bb)};
-}
-__device__ inline dd dd_add(dd a, dd b) {
-    dd s = two_sum(a.hi, b.hi);
-    dd t = two_sum(a.lo, b.lo);
-    s.lo += t.hi;
-    s = two_sum(s.hi, s.lo);          // quick renormalisation (|lo| << |hi| here)
-    s.lo += t.lo;
-    return two_sum(s.hi, s.lo);
-}
-__device__ inline dd dd_neg(dd a) { return dd{-a.hi, -a.lo}; }
-__device__ inline int dd_cmp(dd a, dd b) { return a.hi < b.hi ? -1 : a.hi > b.hi ? 1 : a.lo < b.lo ? -1 : a.lo > b.lo ? 1 : 0; }
-
 // table[i] = log10(i!) ; three small kernels: per-block scan, scan of block sums, add offsets
 constexpr uint32_t LF_BLOCK = 1024;
 
@@ -1916,14 +1900,6 @@ struct GenoArgs {
     uint32_t n_slots;
 };
 
-// normalised counts (predict-genotype.py:327-338) and the rounded ones fed to comb()
-__device__ inline void geno_counts(uint32_t type, uint32_t ref, uint32_t alt, double &c1, double &c2, uint32_t &r1, uint32_t &r2) {
-    c1 = (double)ref; c2 = (double)alt;
-    if (type == 0 && ref) c1 = (double)ref * 0.5;       // round(x/2, 1) is exact for halves
-    if (type == 1 && alt) c2 = (double)alt * 0.5;
-    r1 = (uint32_t)rint(c1); r2 = (uint32_t)rint(c2);   // int(round(c, 0)): half to even
-}
-
 __device__ inline bool geno_gate(const GenoArgs &a, uint64_t r, uint32_t &ref, uint32_t &alt) {
     ref = alt = 0;
     const uint32_t ok = a.ok[r], sl = a.slot[r];
@@ -1936,31 +1912,24 @@ __device__ inline bool geno_gate(const GenoArgs &a, uint64_t r, uint32_t &ref, u
     return (ok & 2u) || (ref | alt) != 0;
 }
 
-__global__ __launch_bounds__(TPB) void k_geno_maxn(GenoArgs a) {
+__global__ __launch_bounds__(TPB) void k_geno_maxn(GenoArgs a) {     // (the largest n below the table's cap, for sizing the table)
     uint64_t r = (uint64_t)blockIdx.x * TPB + threadIdx.x;
     uint32_t n = 0;
     if (r < a.n_rows) {
         uint32_t ref, alt;
-        if (geno_gate(a, r, ref, alt)) { double c1, c2; uint32_t r1, r2; geno_counts(a.sv_type[r], ref, alt, c1, c2, r1, r2); n = r1 + r2; }
+        if (geno_gate(a, r, ref, alt)) {
+            double c1, c2; uint32_t r1, r2; geno_counts(a.sv_type[r], ref, alt, c1, c2, r1, r2);
+            const uint64_t n64 = geno_n(r1, r2);
+            if (r1 && r2 && n64 < LOGFACT_CAP) n = (uint32_t)n64;
+        }
     }
     for (int d = 32; d; d >>= 1) { uint32_t y = __shfl_down(n, d); n = n > y ? n : y; }
     if ((threadIdx.x & 63) == 0 && n) atomicMax(a.max_n, n);
 }
 
-constexpr double PL_GUARD = 1e-6;
-
-__device__ inline int64_t trunc_dd(dd v) {               // int(Decimal): toward zero
-    double t = trunc(v.hi);
-    if (t == v.hi) {                                     // hi is integral: the tail decides
-        if (v.hi > 0 && v.lo < 0) t -= 1.0;
-        else if (v.hi < 0 && v.lo > 0) t += 1.0;
-    }
-    return (int64_t)t;
-}
-
 // (any grid and block size up to TPB: rows in strides of the grid.  svjg_run_begin launches one WAVE per CU: there the kernel runs beside the
-//  next pass's classify kernel and is bound by PCIe — its results go straight to pinned host memory.  A single wave of 56 VGPRs fits on a
-//  SIMD that holds three classify workers (3 x 128 + 56 <= 512), so the fourteen workers of a CU keep their places whichever kernel
+//  next pass's classify kernel and is bound by PCIe — its results go straight to pinned host memory.  A single wave of 64 VGPRs fits on a
+//  SIMD that holds three classify workers (3 x 128 + 64 <= 512), so the fourteen workers of a CU keep their places whichever kernel
 //  arrives first; a 256-thread block needs room on all four SIMDs and displaces a worker)
 __global__ __launch_bounds__(TPB) void k_genotype(GenoArgs a) {
   for (uint64_t r = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; r < a.n_rows; r += (uint64_t)gridDim.x * blockDim.x) {
@@ -1970,39 +1939,19 @@ __global__ __launch_bounds__(TPB) void k_genotype(GenoArgs a) {
     a.genotyped[r] = go;
     a.boundary[r] = 0;
     if (!go) { a.gt[r] = 3; a.pl[r * 3] = a.pl[r * 3 + 1] = a.pl[r * 3 + 2] = 0; if (a.pl32) a.pl32[r * 3] = a.pl32[r * 3 + 1] = a.pl32[r * 3 + 2] = 0; continue; }
-    double c1, c2; uint32_t r1, r2;
-    geno_counts(a.sv_type[r], ref, alt, c1, c2, r1, r2);
-    // products in double, sums exact (the reference adds Decimal images of the doubles, :295-297)
-    dd l0 = two_sum(c1 * a.l_ok, c2 * a.l_err);
-    dd l1 = dd{(c1 + c2) * a.l_half, 0.0};
-    dd l2 = two_sum(c2 * a.l_ok, c1 * a.l_err);
-    int c01 = dd_cmp(l0, l1), c02 = dd_cmp(l0, l2), c12 = dd_cmp(l1, l2);
-    uint8_t g = 3;
-    if (c01 > 0 && c02 > 0) g = 0; else if (c01 < 0 && c12 > 0) g = 1; else if (c02 < 0 && c12 < 0) g = 2;
-    if (!(c1 + c2 >= (double)a.min_support)) g = 3;
-    a.gt[r] = g;
-    uint32_t n = r1 + r2;
-    dd comb{0.0, 0.0};
-    if (n < a.logfact_n) comb = dd_add(dd_add(a.logfact[n], dd_neg(a.logfact[n - r1])), dd_neg(a.logfact[r1]));
-    else atomicMax(a.max_n, n);                          // the log10(i!) table is too short: the host grows it and runs the pass again
-    comb = dd{comb.hi, 0.0};                             // the reference rounds log10(comb) to a double first (:313)
-    dd ls[3] = {l0, l1, l2};
-    bool wide = false, near = false;
+    GenoRow o;
+    const uint32_t st = geno_row(a.sv_type[r], ref, alt, a.min_support, a.l_ok, a.l_err, a.l_half, a.logfact, a.logfact_n, o);
+    if (st == GENO_ROW_GROW) atomicMax(a.max_n, (uint32_t)o.n);    // the log10(i!) table is too short: the host grows it and runs the pass again
+    a.gt[r] = o.gt;
+    bool wide = false;
 #pragma unroll
     for (int i = 0; i < 3; ++i) {
-        dd s = dd_add(ls[i], comb);
-        dd p = dd_add(dd_add(dd_add(s, s), dd_add(s, s)), s);             // 5 s
-        p = dd_add(p, p);                                                 // 10 s
-        const int64_t v = trunc_dd(dd_neg(p));
+        const int64_t v = o.pl[i];
         a.pl[r * 3 + i] = v;
-        // The reference adds Decimal(math.log10(math.comb(n, k))) (:313): libm's log10 of a big integer rounded to a double, which
-        // need not be the correctly rounded value this kernel uses.  The two can differ in the last places; times ten, next to an
-        // integer, that could turn a PL by one.  Rows that close are flagged and recomputed on the host (svjg/genotype.py).
-        { const double fr = fabs(p.hi - rint(p.hi)); if (fr < PL_GUARD && comb.hi != 0.0) near = true; }   // (comb = log10(1) = 0 on both sides: nothing to disagree about)
         if (a.pl32) { a.pl32[r * 3 + i] = (int32_t)v; if (v != (int64_t)(int32_t)v) wide = true; }
     }
     if (wide) a.genotyped[r] = 3;
-    if (near) a.boundary[r] = 1;
+    if (o.near) a.boundary[r] = 1;
   }
 }
 

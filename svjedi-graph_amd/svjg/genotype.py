@@ -97,13 +97,61 @@ def _fmt_counts(svtype_code, ref, alt):
     return str(round(sum(c), 3)), "%s,%s" % (c[0], c[1])
 
 
+# ln(z!) by Stirling's series at 60 digits: ln z! = (z + 1/2) ln z - z + ln(2 pi) / 2 + sum B_2j / (2j (2j - 1) z^(2j - 1)).  With
+# z > 2000 and the terms up to B_24 the remainder is below 1e-80.
+_PI = "3.14159265358979323846264338327950288419716939937510582097494459230781640628620899"
+_BERNOULLI = ((1, 6), (-1, 30), (1, 42), (-1, 30), (5, 66), (-691, 2730), (7, 6), (-3617, 510), (43867, 798), (-174611, 330),
+              (854513, 138), (-236364091, 2730))
+_COMB_DIRECT = 2000            # min(k, n - k) up to this (or n up to 10 * this): math.comb itself is fast
+
+
+def _ln_fact(z):
+    from decimal import Decimal
+    z = Decimal(z)
+    s = (z + Decimal("0.5")) * z.ln() - z + (2 * Decimal(_PI)).ln() / 2
+    zz, p = z * z, z
+    for j, (a, b) in enumerate(_BERNOULLI, 1):
+        s += Decimal(a) / (Decimal(b) * (2 * j) * (2 * j - 1) * p)
+        p *= zz
+    return s
+
+
+def _log10_comb(n, k):
+    """math.log10(math.comb(n, k)), the same double, without the big integer where it is slow: CPython's log10 of an int
+    (mathmodule.c: loghelper) takes the int rounded to a double (PyLong_AsDouble) if that is below 2^1024, else x * 2^e with x
+    the int's top 53 bits rounded half to even (_PyLong_Frexp) and returns log10(x) + log10(2.0) * e.  The int's rounding is
+    taken from ln comb(n, k) at 60 digits; where that cannot decide it (the value sits at a rounding point), math.comb does."""
+    import math
+    from decimal import Decimal, localcontext
+    if n <= 10 * _COMB_DIRECT or min(k, n - k) <= _COMB_DIRECT:
+        return math.log10(math.comb(n, k))
+    with localcontext() as ctx:
+        ctx.prec = 60
+        lnc = _ln_fact(n) - _ln_fact(k) - _ln_fact(n - k)
+        ln2 = Decimal(2).ln()
+        t = lnc / ln2
+        e = int(t) + 1                                           # bit length: 2^(e-1) <= comb < 2^e
+        m = (lnc - (e - 53) * ln2).exp()                         # comb / 2^(e-53), in [2^52, 2^53)
+        mi = int(m)
+        fr = m - mi
+        if abs(t - int(t)) < Decimal("1e-30") or abs(t - int(t) - 1) < Decimal("1e-30") or abs(fr - Decimal("0.5")) < Decimal("1e-30"):
+            return math.log10(math.comb(n, k))
+    if fr > Decimal("0.5") or (fr == Decimal("0.5") and mi & 1):
+        mi += 1
+    if mi == 1 << 53:                                            # the rounding carried: 0.5 * 2^(e+1)
+        mi, e = 1 << 52, e + 1
+    if e <= 1024:
+        return math.log10(math.ldexp(float(mi), e - 53))
+    return math.log10(math.ldexp(float(mi), -53)) + math.log10(2.0) * e
+
+
 def exact_pl(svtype_code, ref, alt, err):
     """The three PL integers of one row with the reference's own arithmetic (predict-genotype.py:284-323): double products, Decimal
-    sums at precision 28, log10 of the exact binomial coefficient, truncation.  For the rows the kernel flags as lying within 1e-6 of
-    an integer boundary (svjg_genotype_boundary): there libm's log10 of a big integer — not necessarily the correctly rounded
-    value the kernel uses — could decide the integer."""
+    sums at precision 28, log10 of the binomial coefficient as CPython computes it for the exact integer, truncation.  For the rows
+    the kernel flags as lying within 1e-6 of an integer boundary or beyond its log10(i!) table (svjg_genotype_boundary): there
+    libm's log10 of a big integer — not necessarily the correctly rounded value the kernel uses — could decide the integer."""
     import math
-    from decimal import Decimal
+    from decimal import Decimal, localcontext
     c1, c2 = ref, alt
     if svtype_code == 0 and ref > 0:
         c1 = round(ref / 2, 1)
@@ -111,9 +159,11 @@ def exact_pl(svtype_code, ref, alt, err):
         c2 = round(alt / 2, 1)
     rc1, rc2 = int(round(c1, 0)), int(round(c2, 0))
     l_ok, l_err, l_half = math.log10(1 - err), math.log10(err), math.log10(1 / 2)
-    comb = Decimal(math.log10(math.comb(rc1 + rc2, rc1)))
-    liks = (Decimal(c1 * l_ok) + Decimal(c2 * l_err), Decimal((c1 + c2) * l_half), Decimal(c2 * l_ok) + Decimal(c1 * l_err))
-    return [int(-10 * (x + comb)) for x in liks]
+    with localcontext() as ctx:
+        ctx.prec = 28
+        comb = Decimal(_log10_comb(rc1 + rc2, rc1))
+        liks = (Decimal(c1 * l_ok) + Decimal(c2 * l_err), Decimal((c1 + c2) * l_half), Decimal(c2 * l_ok) + Decimal(c1 * l_err))
+        return [int(-10 * (x + comb)) for x in liks]
 
 
 def apply_boundary_guard(ctx, rows, pl, raw, done, err):

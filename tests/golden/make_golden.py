@@ -15,7 +15,8 @@ Fixture groups:
                  data rows of expected_genotype.vcf byte for byte
   quirks/    G3  hand-made graph + GAF lines exercising the quirks of SURVEY Appendix D,
                  with the reference's JSON (or the exception class it dies with)
-  lik/       G4  known answers of the reference's likelihood()
+  lik/       G4  known answers of the reference's likelihood(); lik_deep_hp.npz: answers of the model tests/lik_model.py at counts
+                 the reference cannot finish
   vcf/       G5  VCF-parsing cases through the reference's decision_vcf()
   synth/     G6  medium synthetic case from tools/svjg_synth (inputs regenerated from the seed):
                  sha256 of the reference JSON/VCF + the full count vector
@@ -692,6 +693,145 @@ def make_lik_boundary():
         rows.append((t, x, y, 3, gtc[gt], int(pl[0]), int(pl[1]), int(pl[2])))
     np.savez_compressed(f"{out}/lik_boundary.npz", cases=np.array(rows, dtype=np.int64), err=np.full(len(rows), e))
     print(f"lik_boundary: {len(rows)} known answers ({len(rows) - 240} next to an integer boundary)")
+
+
+_LIK_TYPES = ("DEL", "INS", "INV", "BND")
+_GTC = {"0/0": 0, "0/1": 1, "1/1": 2, "./.": 3}
+
+
+def _norm_r(t, ref, alt):
+    """(r1, r2): the rounded normalised counts likelihood() feeds to comb()"""
+    c1 = round(ref / 2, 1) if t == 0 and ref > 0 else ref
+    c2 = round(alt / 2, 1) if t == 1 and alt > 0 else alt
+    return int(round(c1, 0)), int(round(c2, 0))
+
+
+def _lik_search(pairs, e, lo, hi, rng, max_rows):
+    """INV/BND rows (t, ref, alt) next to a PL's integer boundary: for each (r1, r2 start) a window of consecutive r2, log10 comb(r1 + r2, r1)
+    stepped in np.longdouble from an 80-digit start (tests/lik_model.py), the PLs' distance to the nearest integer in [lo, hi); then
+    confirmed with the model (which takes the reference's own double of log10 comb)."""
+    import math
+    import mpmath
+    sys.path.insert(0, ROOT)
+    from tests import lik_model as M
+    ld = np.longdouble
+    l_ok, l_err, l_half = math.log10(1 - e), math.log10(e), math.log10(0.5)
+    out = []
+    for r1, s0, w in pairs:
+        with mpmath.workdps(40):
+            base = mpmath.log10(mpmath.binomial(r1 + s0, r1))
+        b_hi = ld(float(base))
+        b_lo = ld(float(base - mpmath.mpf(float(base))))
+        r2 = np.arange(s0, s0 + w, dtype=np.int64)
+        inc = np.log10((r2[1:] + r1).astype(ld)) - np.log10(r2[1:].astype(ld))
+        comb = (b_hi + b_lo) + np.concatenate([[ld(0)], np.cumsum(inc)])
+        c1, c2 = float(r1), r2.astype(np.float64)
+        near = np.zeros(w, dtype=bool)
+        for lik in ((ld(c1 * l_ok) + (c2 * l_err).astype(ld)), ((c1 + c2) * l_half).astype(ld), ((c2 * l_ok).astype(ld) + ld(c1 * l_err))):
+            v = -10 * (lik + comb)
+            d = np.abs(v - np.rint(v))
+            near |= (d >= lo * 0.5) & (d < hi * 2)
+        for j in np.flatnonzero(near):
+            t = int(rng.integers(2, 4))
+            ref, alt = (r1, int(r2[j])) if rng.integers(2) else (int(r2[j]), r1)
+            try:
+                fr = M.pl_fractions(t, ref, alt, e)
+            except M.Undecided:
+                continue
+            if any(lo <= f < hi for f in fr):
+                out.append((t, ref, alt))
+            if len(out) >= max_rows:
+                return out
+    return out
+
+
+def _lik_save(name, rows, e, note):
+    cases = np.array([r[:8] for r in rows], dtype=np.int64)
+    src = np.array([r[8] for r in rows])
+    np.savez_compressed(f"{HERE}/lik/{name}", cases=cases, err=np.full(len(rows), e), src=src, note=np.array(note))
+    print(f"{name}: {len(rows)} rows, {os.path.getsize(f'{HERE}/lik/{name}')} bytes")
+
+
+LIK_GRID = (0, 1, 2, 3, 2**16 - 1, 2**16, 2**24, 2**31 - 1, 2**31, 2**31 + 1, 2**32 - 2, 2**32 - 1)
+LIK_CAP = 2**24                                 # svjg_geno.h: LOGFACT_CAP
+
+
+def make_lik_deep():
+    """lik/lik_deep.npz: known answers of the reference's likelihood() (called in process) at deep counts where math.comb is cheap
+    (min(r1, r2) <= 2000 or n <= 10^5).  src: grid (every cheap pair of LIK_GRID x 4 types x min_support 0 / 3), loguniform (n in
+    [10^5, 2^32) with a small k), table_n (n at 65 535 / 65 536 / 65 537, multiples of 1024 +- 1, the table cap +- 1), near (a PL
+    within 1e-7 of an integer), band (a PL 1e-6 .. 1e-5 from one)."""
+    e = 5e-5
+    rng = np.random.default_rng(33)
+    cases = []
+    for t in range(4):
+        for ms in (0, 3):
+            for a in LIK_GRID:
+                for b in LIK_GRID:
+                    r1, r2 = _norm_r(t, a, b)
+                    if min(r1, r2) <= 2000 or r1 + r2 <= 10**5:
+                        cases.append((t, a, b, ms, "grid"))
+    while sum(c[4] == "loguniform" for c in cases) < 150:
+        t = int(rng.integers(4))
+        big = int(np.exp(rng.uniform(np.log(1e5), np.log(2**32 - 1))))
+        small = int(rng.integers(0, 2001))
+        a, b = (small, big) if rng.integers(2) else (big, small)
+        r1, r2 = _norm_r(t, a, b)
+        if min(r1, r2) <= 2000:
+            cases.append((t, a, b, 3, "loguniform"))
+    ns = [65535, 65536, 65537, LIK_CAP - 1, LIK_CAP, LIK_CAP + 1]
+    ns += [j * 1024 + d for j in (1, 63, 64, 65, 1000, 16383, 16384) for d in (-1, 1)]
+    for n in ns:
+        for k in (1, 2, 7, 1000):
+            for t in (2, 3):
+                cases.append((t, k, n - k, 3, "table_n"))
+                cases.append((t, n - k, k, 3, "table_n"))
+    # the search: r1 small, windows of r2 at log-uniform depths
+    pairs = [(int(rng.integers(1, 400)), int(np.exp(rng.uniform(np.log(1e5), np.log(4e9)))), 100_000) for _ in range(600)]
+    cases += [(t, a, b, 3, "near") for t, a, b in _lik_search(pairs, e, 0.0, 1e-7, rng, 40)]
+    cases += [(t, a, b, 3, "band") for t, a, b in _lik_search(pairs[::7], e, 1e-6, 1e-5, rng, 40)]
+    rows = []
+    for t, a, b, ms, src in cases:
+        cnt = [a, b]
+        gt, pl = ref_geno.likelihood(cnt, _LIK_TYPES[t], ms, e)
+        rows.append((t, a, b, ms, _GTC[gt], int(pl[0]), int(pl[1]), int(pl[2]), src))
+    _lik_save("lik_deep.npz", rows, e, "answers of the reference's likelihood(), called in process (tests/golden/make_golden.py: make_lik_deep)")
+
+
+def make_lik_deep_hp():
+    """lik/lik_deep_hp.npz: answers of the MODEL (tests/lik_model.py), not of the reference, which cannot finish these rows (both r1 and
+    r2 between 10^6 and 2^32 - 1: math.comb takes minutes to hours).  src: wrap (pairs whose 32-bit sum wraps or nearly does), cap
+    (n at the table cap +- 1), loguniform, near (a PL within 1e-7 of an integer), band (1e-6 .. 1e-5 from one)."""
+    sys.path.insert(0, ROOT)
+    from tests import lik_model as M
+    e = 5e-5
+    rng = np.random.default_rng(34)
+    cases = []
+    big = (2**31 - 1, 2**31, 2**31 + 1, 2**32 - 2, 2**32 - 1, 10**6, 3 * 10**9)
+    for t in range(4):
+        for a in big:
+            for b in big:
+                cases.append((t, a, b, 3, "wrap"))
+    for n in (LIK_CAP - 1, LIK_CAP, LIK_CAP + 1):
+        for k in (n // 2, n // 3, 10**6):
+            for t in (2, 3):
+                cases.append((t, k, n - k, 3, "cap"))
+    while sum(c[4] == "loguniform" for c in cases) < 120:
+        t = int(rng.integers(4))
+        a, b = (int(np.exp(rng.uniform(np.log(2e6), np.log(2**32 - 1)))) for _ in range(2))
+        r1, r2 = _norm_r(t, a, b)
+        if min(r1, r2) >= 10**6:
+            cases.append((t, a, b, int(rng.integers(0, 4)), "loguniform"))
+    pairs = [(int(np.exp(rng.uniform(np.log(1e6), np.log(4e9)))), int(np.exp(rng.uniform(np.log(1e6), np.log(4e9)))), 100_000)
+             for _ in range(400)]
+    cases += [(t, a, b, 3, "near") for t, a, b in _lik_search(pairs, e, 0.0, 1e-7, rng, 30)]
+    cases += [(t, a, b, 3, "band") for t, a, b in _lik_search(pairs[::5], e, 1e-6, 1e-5, rng, 30)]
+    rows = []
+    for t, a, b, ms, src in cases:
+        gt, pl = M.likelihood([a, b], _LIK_TYPES[t], ms, e)
+        rows.append((t, a, b, ms, _GTC[gt], int(pl[0]), int(pl[1]), int(pl[2]), src))
+    _lik_save("lik_deep_hp.npz", rows, e, "answers of the high-precision MODEL of likelihood() (tests/lik_model.py), not of the reference: "
+              "math.comb cannot finish these rows (tests/golden/make_golden.py: make_lik_deep_hp)")
 
 
 # ----------------------------------------------------------------------------------------------
@@ -1613,7 +1753,7 @@ def make_full(which=("c2", "c3", "c4slice")):
 
 
 if __name__ == "__main__":
-    which = sys.argv[1:] or ["testdir", "quirks", "unicode", "lik", "lik_boundary", "vcf", "synth", "realshape", "utf8order", "nosv", "vcffuzz", "graphfuzz", "dover", "longpath", "contigs", "longtail",
+    which = sys.argv[1:] or ["testdir", "quirks", "unicode", "lik", "lik_boundary", "lik_deep", "lik_deep_hp", "vcf", "synth", "realshape", "utf8order", "nosv", "vcffuzz", "graphfuzz", "dover", "longpath", "contigs", "longtail",
                              "blanks", "fuzz7", "graphlayout"]          # (hg002shape: minutes and 7 GB of scratch — by name)
     for w in which:
         if w.startswith("full"):                   # full | full:c2,c3,c4slice

@@ -1,5 +1,5 @@
 // TEST HARNESS ONLY (never shipped, never loaded by the product): compiles the exact per-line device routine
-// (svjg::slow_line) and the graph-table lookups of svjedi-graph_amd/csrc/svjg_line.h with g++ and drives them
+// (svjg::slow_line), the graph-table lookups of svjedi-graph_amd/csrc/svjg_line.h and the genotype row arithmetic (svjg_geno.h) with g++ and drives them
 // sequentially, so their logic can be checked against the oracle on a machine without a GPU (and under
 // -fsanitize=address,undefined).  The main kernel (k_classify_main) is wave/block-level code and is covered
 // by the -m gpu tests through the C ABI.
@@ -9,6 +9,8 @@
 #include "../../svjedi-graph_amd/csrc/svjg_host_tables.h"
 #include "../../svjedi-graph_amd/csrc/svjg_planes.h"
 #include "../../svjedi-graph_amd/csrc/svjg_pass.h"
+#include "../../svjedi-graph_amd/csrc/svjg_geno.h"
+#include <math.h>
 #include <cstring>
 #include <string>
 #include <vector>
@@ -273,3 +275,22 @@ extern "C" uint64_t hostsim_pass_repeat_word(uint32_t overflow_bits) { return pa
 extern "C" int hostsim_pass_repeats(int has_comm, uint32_t own_overflow_bits, uint64_t guard_repeat_sum) { return pass_repeats(has_comm != 0, own_overflow_bits, guard_repeat_sum) ? 1 : 0; }
 extern "C" int hostsim_pass_counts_overflowed(uint64_t a, uint64_t b) { return pass_counts_overflowed(a, b) ? 1 : 0; }
 extern "C" uint32_t hostsim_guard_words(void) { return GUARD_WORDS; }
+
+// the log10(i!) table of k_logfact_* with the HOST libm's log10 (not the device's), summed in order in double-double (the kernels
+// sum in blocks: the association differs, both far below the guard's budget)
+extern "C" void hostsim_logfact(dd *tab, uint32_t n) {
+    dd run{0.0, 0.0};
+    for (uint32_t i = 0; i < n; ++i) { if (i >= 2) run = dd_add(run, dd{log10((double)i), 0.0}); tab[i] = run; }
+}
+
+// k_genotype's per-row arithmetic (svjg_geno.h: geno_row) over rows of (type, ref, alt); status: GENO_ROW_*, near: the boundary byte
+extern "C" void hostsim_genotype(const uint8_t *type, const uint32_t *cnt, uint64_t n_rows, uint32_t min_support, double err,
+                                 const dd *tab, uint32_t tab_n, uint8_t *gt, int64_t *pl, uint8_t *near, uint8_t *status) {
+    const double l_ok = log10(1.0 - err), l_err = log10(err), l_half = log10(1.0 / 2.0);       // as svjg_capi.hip: host libm
+    for (uint64_t r = 0; r < n_rows; ++r) {
+        GenoRow o;
+        status[r] = (uint8_t)geno_row(type[r], cnt[r * 2], cnt[r * 2 + 1], min_support, l_ok, l_err, l_half, tab, tab_n, o);
+        gt[r] = o.gt; near[r] = o.near;
+        for (int i = 0; i < 3; ++i) pl[r * 3 + i] = o.pl[i];
+    }
+}

@@ -20,6 +20,7 @@ def build():
            os.path.join(HERE, "..", "..", "svjedi-graph_amd", "csrc", "svjg_host_tables.h"),
            os.path.join(HERE, "..", "..", "svjedi-graph_amd", "csrc", "svjg_planes.h"),
            os.path.join(HERE, "..", "..", "svjedi-graph_amd", "csrc", "svjg_pass.h"),
+           os.path.join(HERE, "..", "..", "svjedi-graph_amd", "csrc", "svjg_geno.h"),
            os.path.join(HERE, "..", "..", "include", "svjg.h")]
     if not os.path.exists(SO) or os.path.getmtime(SO) < max(os.path.getmtime(s) for s in src):
         subprocess.run(["g++", "-O2", "-std=c++17", "-Wall", "-shared", "-fPIC", "-o", SO, src[0]], check=True)
@@ -122,3 +123,29 @@ def pass_logic():
     lib.hostsim_guard_words.restype = ctypes.c_uint32
     return (lambda o: int(lib.hostsim_pass_repeat_word(o)), lambda c, o, s: bool(lib.hostsim_pass_repeats(int(c), o, s)),
             lambda a, b: bool(lib.hostsim_pass_counts_overflowed(a, b)), int(lib.hostsim_guard_words()))
+
+
+def logfact_table(n):
+    """log10(i!) for i < n in double-double (float64[n, 2]), built with the host libm's log10 — not the device's"""
+    lib = ctypes.CDLL(build())
+    tab = np.zeros((n, 2), np.float64)
+    lib.hostsim_logfact.restype = None
+    lib.hostsim_logfact.argtypes = [ctypes.c_void_p, ctypes.c_uint32]
+    lib.hostsim_logfact(tab.ctypes.data, n)
+    return tab
+
+
+def genotype_rows(sv_type, counts, min_support, err, tab):
+    """k_genotype's per-row arithmetic (svjg_geno.h: geno_row) -> (gt, pl[n, 3], near, status: 0 ok, 1 table too short, 2 beyond the cap)"""
+    lib = ctypes.CDLL(build())
+    sv_type = np.ascontiguousarray(sv_type, np.uint8)
+    counts = np.ascontiguousarray(counts, np.uint32)
+    tab = np.ascontiguousarray(tab, np.float64)
+    n = len(sv_type)
+    gt, pl, near, st = np.zeros(n, np.uint8), np.zeros((n, 3), np.int64), np.zeros(n, np.uint8), np.zeros(n, np.uint8)
+    lib.hostsim_genotype.restype = None
+    lib.hostsim_genotype.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_uint32, ctypes.c_double, ctypes.c_void_p,
+                                     ctypes.c_uint32] + [ctypes.c_void_p] * 4
+    lib.hostsim_genotype(sv_type.ctypes.data, counts.ctypes.data, n, int(min_support), float(err), tab.ctypes.data, len(tab),
+                         gt.ctypes.data, pl.ctypes.data, near.ctypes.data, st.ctypes.data)
+    return gt, pl, near, st

@@ -390,9 +390,18 @@ def test_synth_g6(ctx, golden, tag, tmp_path):
     assert open(pre + "_genotype.vcf").read() == open(f"{golden}/synth/{tag}.ref_genotype.vcf").read()
 
 
-def test_likelihood_known_answers(ctx, golden):
-    """All known answers of the reference's likelihood(): GT and the three PL integers, exactly."""
-    z = np.load(f"{golden}/lik/lik_kat.npz")
+class _Rows:
+    def __init__(self, sv_type):
+        self.sv_type = sv_type
+
+
+@pytest.mark.parametrize("name", ["lik_kat.npz", "lik_deep.npz", "lik_deep_hp.npz"])
+def test_likelihood_known_answers(ctx, golden, name):
+    """All known answers of the reference's likelihood() (lik_deep_hp.npz: of the model tests/lik_model.py, where the reference
+    cannot finish): GT and the three PL integers, exactly — lik_kat.npz straight from the kernel, the deep files after the host
+    recomputes the rows the kernel flags (next to an integer boundary, or beyond the log10(i!) table's cap)."""
+    from svjg import genotype
+    z = np.load(f"{golden}/lik/{name}")
     cases, errs = z["cases"], z["err"]
     for ms in np.unique(cases[:, 3]):
         for e in np.unique(errs):
@@ -400,18 +409,27 @@ def test_likelihood_known_answers(ctx, golden):
             if len(sel) == 0:
                 continue
             c = cases[sel]
+            rows = _Rows(c[:, 0].astype(np.uint8))
             ctx.alloc_counts(len(sel))
             ctx.set_counts(c[:, 1:3].astype(np.uint32))
             gt, pl, raw, done = ctx.genotype(c[:, 0].astype(np.uint8), np.arange(len(sel), dtype=np.uint32),
                                              np.full(len(sel), 3, dtype=np.uint8), int(ms), float(e))
             assert done.all()
             assert np.array_equal(raw, c[:, 1:3].astype(np.uint32))
-            bad = np.where((gt != c[:, 4]) | (pl != c[:, 5:8]).any(axis=1))[0]
-            assert len(bad) == 0, (c[bad[:5]], gt[bad[:5]], pl[bad[:5]])
+            if name == "lik_kat.npz":
+                bad = np.where((gt != c[:, 4]) | (pl != c[:, 5:8]).any(axis=1))[0]
+                assert len(bad) == 0, (c[bad[:5]], gt[bad[:5]], pl[bad[:5]])
+            pl_g, _ = genotype.apply_boundary_guard(ctx, rows, pl, raw, done, float(e))
+            bad = np.where((gt != c[:, 4]) | (pl_g != c[:, 5:8]).any(axis=1))[0]
+            assert len(bad) == 0, (c[bad[:5]], gt[bad[:5]], pl_g[bad[:5]])
             # the zero-copy form (svjg_genotype_view): read-only views of the library's pinned block, same contents
             v = ctx.genotype(c[:, 0].astype(np.uint8), np.arange(len(sel), dtype=np.uint32),
                              np.full(len(sel), 3, dtype=np.uint8), int(ms), float(e), reuse_outputs=True)
             assert all(np.array_equal(a, b) and not b.flags.writeable for a, b in zip((gt, pl, raw, done), v))
+            pl_v, _ = genotype.apply_boundary_guard(ctx, rows, v[1], v[2], v[3], float(e))
+            assert np.array_equal(pl_v, c[:, 5:8])
+    if name != "lik_kat.npz":
+        return
     # a row that names a count slot beyond the table is a caller error, with or without the gate bit
     from svjg import capi
     for okv in (3, 0):
@@ -421,30 +439,169 @@ def test_likelihood_known_answers(ctx, golden):
     assert done.tolist() == [1, 0]
 
 
-def test_likelihood_next_to_integer_boundaries(ctx, golden):
+@pytest.mark.parametrize("name", ["lik_boundary.npz", "lik_deep.npz", "lik_deep_hp.npz"])
+def test_likelihood_next_to_integer_boundaries(ctx, golden, name):
     """lik_boundary.npz: known answers of the reference where a PL lies within 4e-7 of an integer (found by search) and for counts
-    up to 10^6.  The kernel flags the near ones (svjg_genotype_boundary), the host recomputes the flagged rows with the reference's
-    own arithmetic (svjg.genotype.exact_pl), and GT / PL equal the reference's on every row."""
+    up to 10^6; lik_deep*.npz: rows whose PL lies within 1e-7 of an integer at counts up to 2^32 - 1 (src "near").  The kernel flags the
+    near ones (svjg_genotype_boundary), the host recomputes the flagged rows with the reference's own arithmetic
+    (svjg.genotype.exact_pl), and GT / PL equal the reference's on every row."""
     from svjg import genotype
+    z = np.load(f"{golden}/lik/{name}")
+    cases = z["cases"]
+    e = float(z["err"][0])
+    assert (z["err"] == e).all()
+    for ms in np.unique(cases[:, 3]):
+        sel = np.flatnonzero(cases[:, 3] == ms)
+        c = cases[sel]
+        n = len(c)
+        rows = _Rows(c[:, 0].astype(np.uint8))
+        ctx.alloc_counts(n)
+        ctx.set_counts(c[:, 1:3].astype(np.uint32))
+        gt, pl, raw, done = ctx.genotype(rows.sv_type, np.arange(n, dtype=np.uint32), np.full(n, 3, dtype=np.uint8), int(ms), e)
+        flags = ctx.boundary_flags(n)
+        assert done.all() and np.array_equal(gt, c[:, 4])
+        if name == "lik_boundary.npz":
+            assert flags[:n - 240].all()                                   # every case the search found is one the kernel flags
+            assert flags[n - 240:].sum() <= 2                              # (random deep samples: a few per million rows are flagged)
+        else:
+            assert flags[z["src"][sel] == "near"].all()                    # every PL within 1e-7 of an integer is flagged
+        unguarded = int((pl != c[:, 5:8]).any(axis=1).sum())
+        pl2, n_flagged = genotype.apply_boundary_guard(ctx, rows, pl, raw, done, e)
+        assert n_flagged == int(flags.sum()) and np.array_equal(pl2, c[:, 5:8]), (unguarded, np.flatnonzero((pl2 != c[:, 5:8]).any(axis=1))[:5])
+        print(f"{name} ms {ms}: rows whose kernel PL differs from the reference without the guard: {unguarded} of {n}, flagged {n_flagged}")
 
-    class _Rows:
-        pass
-    z = np.load(f"{golden}/lik/lik_boundary.npz")
-    c = z["cases"]
+
+def test_likelihood_deep_rows_among_ordinary_ones(golden):
+    """ONE call on a fresh context (log10(i!) table of 65 536 entries): ordinary rows, rows that need a larger table (n up to the cap)
+    and rows beyond the cap (recomputed on the host) side by side — the call regrows the table and hands the rest to the host"""
+    from svjg import capi, genotype
+    parts = []
+    for name in ("lik_kat.npz", "lik_deep.npz", "lik_deep_hp.npz"):
+        z = np.load(f"{golden}/lik/{name}")
+        parts.append(z["cases"][(z["cases"][:, 3] == 3) & (z["err"] == 5e-5)])
+    c = np.concatenate(parts)
+    c = c[np.random.default_rng(5).permutation(len(c))]
     n = len(c)
-    rows = _Rows()
-    rows.sv_type = c[:, 0].astype(np.uint8)
-    ctx.alloc_counts(n)
+    rows = _Rows(c[:, 0].astype(np.uint8))
+    cx = capi.Context(0)
+    try:
+        cx.alloc_counts(n)
+        cx.set_counts(c[:, 1:3].astype(np.uint32))
+        gt, pl, raw, done = cx.genotype(rows.sv_type, np.arange(n, dtype=np.uint32), np.full(n, 3, dtype=np.uint8), 3, 5e-5)
+        assert done.all() and np.array_equal(gt, c[:, 4])
+        flags = cx.boundary_flags(n)
+        pl2, n_flagged = genotype.apply_boundary_guard(cx, rows, pl, raw, done, 5e-5)
+        assert np.array_equal(pl2, c[:, 5:8])
+        assert n_flagged < n // 10 and flags.sum() == n_flagged
+    finally:
+        cx.close()
+
+
+def test_vcf_text_of_deep_rows(ctx, golden, tmp_path):
+    """The DP / AD / PL text that svjg_vcf_write gives the deep rows (both files, every SV type, counts up to 2^32 - 1) equals what the
+    reference's Python formatting gives: str(round(sum(c), 3)), '%s,%s' % (c[0], c[1]) after the normalisation, '%d' of the PLs."""
+    from svjg import genotype
+    cs = [np.load(f"{golden}/lik/{n}") for n in ("lik_deep.npz", "lik_deep_hp.npz")]
+    c = np.concatenate([z["cases"][z["cases"][:, 3] == 3] for z in cs])
+    lines, keys = [], []
+    for i, (t, a, b) in enumerate(c[:, 0:3].tolist()):
+        pos = 1000 + 10 * i
+        if t in (0, 2):
+            ty = "DEL" if t == 0 else "INV"
+            lines.append(f"chr1\t{pos}\tsv{i}\tN\t<{ty}>\t.\tPASS\tSVTYPE={ty};END={pos + 100}\tGT\t0/1")
+            keys.append(f"chr1:{ty}-{pos}-{pos + 100}")
+        elif t == 1:
+            lines.append(f"chr1\t{pos}\tsv{i}\tN\t{'A' * 60}\t.\tPASS\tSVTYPE=INS\tGT\t0/1")
+            keys.append(f"chr1:INS-{pos}-1")
+        else:
+            lines.append(f"chr1\t{pos}\tsv{i}\tN\tN[chr2:{pos}[\t.\tPASS\tSVTYPE=BND\tGT\t0/1")
+            keys.append(f"chr1:BND-{pos}[chr2:{pos}[")
+    vcf = tmp_path / "deep.vcf"
+    vcf.write_text("##fileformat=VCFv4.2\n#CHROM\tPOS\tID\tREF\tALT\tQUAL\tFILTER\tINFO\tFORMAT\tSAMPLE\n" + "\n".join(lines) + "\n")
+    ctx.alloc_counts(len(c))
     ctx.set_counts(c[:, 1:3].astype(np.uint32))
-    gt, pl, raw, done = ctx.genotype(rows.sv_type, np.arange(n, dtype=np.uint32), np.full(n, 3, dtype=np.uint8), 3, 0.00005)
-    flags = ctx.boundary_flags(n)
-    assert done.all() and np.array_equal(gt, c[:, 4])
-    assert flags[:n - 240].all()                                   # every case the search found is one the kernel flags
-    assert flags[n - 240:].sum() <= 2                              # (random deep samples: a few per million rows are flagged)
-    unguarded = int((pl != c[:, 5:8]).any(axis=1).sum())
-    pl2, n_flagged = genotype.apply_boundary_guard(ctx, rows, pl, raw, done, 0.00005)
-    assert n_flagged == int(flags.sum()) and np.array_equal(pl2, c[:, 5:8]), (unguarded, np.flatnonzero((pl2 != c[:, 5:8]).any(axis=1))[:5])
-    print(f"rows whose kernel PL differs from the reference without the guard: {unguarded} of {n}")
+    out = tmp_path / "out.vcf"
+    n = genotype.genotype_with_counts(ctx, str(vcf), keys, str(out), 3, 5e-5, slot_is_presence=True)
+    assert n == len(c)
+    got = [ln.split("\t")[-1] for ln in out.read_text().splitlines() if not ln.startswith("#")]
+    assert len(got) == len(c)
+    for (t, a, b, _, g, p0, p1, p2), text in zip(c.tolist(), got):
+        cnt = [a, b]
+        if t == 0 and a > 0:
+            cnt[0] = round(a / 2, 1)
+        elif t == 1 and b > 0:
+            cnt[1] = round(b / 2, 1)
+        want = "%s:%s:%s:%d,%d,%d" % (genotype.GT_TEXT[g], str(round(sum(cnt), 3)), "%s,%s" % (cnt[0], cnt[1]), p0, p1, p2)
+        assert text == want, (t, a, b)
+
+
+def test_fused_pass_beyond_the_first_table(golden):
+    """The fused pass (svjg_run_resident, svjg_run_begin / svjg_run_end) with one SV past 65 536 informative alignments on both alleles
+    (66 000 copies of a ref line and of an alt line of golden/testdir): the pass regrows the log10(i!) table itself.  Counts equal
+    the C oracle's; GT and PL of every row equal the reference's likelihood() (oracle_py, n <= 10^5 so that math.comb stays cheap)."""
+    from svjg import capi, genotype
+    from svjg.graph import Graph
+    d = f"{golden}/testdir"
+    g = Graph.from_files(f"{d}/test_svs_edges.json", f"{d}/test.gfa")
+    orc = OC.COracle(O.load_edges(f"{d}/test_svs_edges.json"), O.load_alt_node_len(f"{d}/test.gfa"))
+    sv = orc.sv_ids.index("1:DEL-72000-72300")
+    pick = [None, None]
+    for ln in open(f"{d}/test.gaf", "rb").read().split(b"\n"):
+        if not ln:
+            continue
+        cnt, _, _ = orc.filter(np.frombuffer(ln + b"\n", dtype=np.uint8), want_hits=False)
+        for a in (0, 1):
+            if pick[a] is None and cnt[sv, a] and cnt[sv, 1 - a] == 0:
+                pick[a] = ln + b"\n"
+    gaf = np.frombuffer(pick[0] * 66000 + pick[1] * 66000, dtype=np.uint8)
+    want, _, n_lines = orc.filter(gaf, want_hits=False)
+    assert want[sv, 0] > 65536 and want[sv, 1] > 65536
+    rows = genotype.VcfRows(f"{d}/test.vcf", g.slot_of)
+    types = ("DEL", "INS", "INV", "BND")
+    exp = {}
+    for r in range(len(rows.sv_type)):
+        s = int(rows.slot[r])
+        if rows.ok[r] & 1 and s != 0xFFFFFFFF and g.sv_ids[s] in orc.sv_ids:
+            a, b = (int(x) for x in want[orc.sv_ids.index(g.sv_ids[s])])
+            if a or b:
+                gt, pl = O.likelihood([a, b], types[rows.sv_type[r]], 3, 0.00005)
+                exp[r] = (("0/0", "0/1", "1/1", "./.").index(gt), [int(x) for x in pl], a, b)
+    assert any(v[2] > 65536 for v in exp.values())
+
+    def check(c, res):
+        gt, pl, raw, flags = (np.array(x) for x in res)
+        pl = pl.astype(np.int64)
+        for r in np.flatnonzero(c.last_boundary):
+            pl[r] = genotype.exact_pl(int(rows.sv_type[r]), int(raw[r, 0]), int(raw[r, 1]), 0.00005)
+        got = {s: (int(x[0]), int(x[1])) for s, x in zip(g.sv_ids, c.counts()) if x.sum()}
+        assert got == {s: (int(x[0]), int(x[1])) for s, x in zip(orc.sv_ids, want) if x.sum()}
+        for r in range(len(rows.sv_type)):
+            if r in exp:
+                assert flags[r] & 1 and gt[r] == exp[r][0] and pl[r].tolist() == exp[r][1] and raw[r].tolist() == [exp[r][2], exp[r][3]], r
+            else:
+                assert not flags[r] & 1
+
+    c = capi.Context(0)
+    try:
+        c.load_graph(g)
+        c.set_rows(rows.sv_type, rows.slot, rows.ok)
+        c.upload(gaf)
+        check(c, c.run_resident(3, 0.00005))
+        assert c.stats()["n_lines"] == n_lines
+        check(c, c.run_resident(3, 0.00005))
+    finally:
+        c.close()
+    c = capi.Context(0)                                    # a fresh table again: the growth inside svjg_run_end
+    try:
+        c.load_graph(g)
+        c.set_rows(rows.sv_type, rows.slot, rows.ok)
+        c.upload(gaf)
+        c.run_begin(3, 0.00005)
+        c.run_begin(3, 0.00005)
+        check(c, c.run_end())
+        check(c, c.run_end())
+    finally:
+        c.close()
 
 
 @pytest.mark.parametrize("tag,ms,err", [("ms3", 3, None), ("ms1", 1, None), ("ms0", 0, None), ("ms3_e1e-3", 3, 0.001)])
