@@ -117,14 +117,7 @@ def reference_error(data, exc):
     if off is None:
         return exc
     n = int(data.size)
-    e = int(off)
-    while e < n and data[e] not in (10, 13):                # the offending line's terminator
-        blk = np.asarray(data[e:e + 65536])
-        hit = np.flatnonzero((blk == 10) | (blk == 13))
-        if hit.size:
-            e += int(hit[0])
-            break
-        e += blk.size
+    e = shard.next_terminator(data, int(off))               # the offending line's terminator
     bad = first_utf8_error(data, min(n, (e // 8192 + 1) * 8192 + 4))
     if bad is not None and e >= (bad // 8192) * 8192:
         try:
@@ -263,14 +256,7 @@ def resolve_host_lines(ctxs, data, want_hits, error=None):
     for off in offs.tolist():
         if limit is not None and off >= limit:
             break
-        e = off
-        while e < n and data[e] not in (10, 13):
-            blk = np.asarray(data[e:e + 65536])
-            hit = np.flatnonzero((blk == 10) | (blk == 13))
-            if hit.size:
-                e += int(hit[0])
-                break
-            e += blk.size
+        e = shard.next_terminator(data, off)
         raw = bytes(data[off:e])
         try:
             text = raw.decode("utf-8") + ("\n" if e < n else "")
@@ -328,6 +314,26 @@ def remap_hits(recs, remap):
     return recs
 
 
+def settle(ctxs, data, want_hits, error, resolved=None, before_reduce=None):
+    """The host's part once every context has classified its text (`error`: what the first failing one raised, file order), the
+    same behind every way into the filter: the lines set aside for the host and the exception the reference dies with first, UTF-8
+    validity, the count all-reduce.  `resolved()` runs once the lines are decided, `before_reduce()` in front of the all-reduce.
+    -> (counts[n_slots, 2], hit records or None)"""
+    if error is not None and not isinstance(error, capi.LINE_ERRORS):
+        raise error
+    try:
+        remap = resolve_host_lines(ctxs, data, want_hits, error)       # (lines with non-ASCII digits: Python's int() decides)
+    except HOST_LINE_ERRORS as e:
+        raise reference_error(data, e)
+    if resolved is not None:
+        resolved()
+    if any(c.stats()["non_ascii"] for c in ctxs):
+        check_utf8(data)
+    if before_reduce is not None:
+        before_reduce()
+    capi.allreduce_counts_all(ctxs)              # (one GPU: only the overflow guard of the 32-bit count fields)
+    return ctxs[0].counts(), (remap_hits(gather_hits(ctxs), remap) if want_hits else None)
+
 
 def _stamp(t, what):
     """stage timers on stderr when SVJG_VERBOSE is set (measurement only)"""
@@ -374,8 +380,8 @@ def _classify_on_device(ctx, graph, data, ranges, want_hits, out, r, path=None):
 class _CommInit(threading.Thread):
     """RCCL communicators for the contexts of this process (ncclCommInitAll), created in a thread of its own WHILE the GPUs upload and
     classify: over eight ranks that call takes seconds — the order of the whole run at BASELINE configs[2] — and nothing it does needs
-    the contexts to be idle (it sets ctx->comm, which only the all-reduce behind the classification reads).  join_or_raise() before that
-    all-reduce; `seconds` = how long the call took."""
+    the contexts to be idle (it sets ctx->comm, which only the all-reduce behind the classification reads).  finish() before that
+    all-reduce."""
 
     def __init__(self, ctxs):
         super().__init__(daemon=True)
@@ -385,39 +391,31 @@ class _CommInit(threading.Thread):
         t = time.perf_counter()
         try:
             capi.comm_init_all(self.ctxs)
-        except BaseException as e:                # noqa: BLE001 (re-raised by join_or_raise)
+        except BaseException as e:                # noqa: BLE001 (re-raised by finish)
             self.error = e
         self.seconds = time.perf_counter() - t
 
-    def join_or_raise(self, started=True):
+    def finish(self, started=True):
+        """join the thread (`started`; else run() was called in this one), raise its error, else leave what the call took for
+        rccl_init_s and report it under SVJG_VERBOSE"""
+        t_wait = time.perf_counter()
         if started:
             self.join()
         if self.error is not None:
             raise self.error
-        return self.seconds
+        note_rccl_init_s(self.seconds, len(self.ctxs))
+        if os.environ.get("SVJG_VERBOSE"):
+            how = (f" beside upload + classify, {time.perf_counter() - t_wait:.2f} s of it waited for here" if started else
+                   ", in front of upload + classify")
+            sys.stderr.write(f"[svjg] RCCL communicators for {len(self.ctxs)} GPUs (ncclCommInitAll): {self.seconds:.2f} s{how}\n")
 
 
 def classify_file(ctx, graph, gaf_path, want_hits=True):
     """One GPU, one context that keeps the counts (fused driver, tests): -> (counts[n_slots, 2], hit records, the file's bytes)."""
     data = read_gaf(gaf_path)
-    ctx.load_graph(graph)
-    n = int(data.size)
-    cuts = shard.cut_points(data, max(1, -(-n // CHUNK_BYTES)))
-    err = None
-    try:
-        for a, b in zip(cuts[:-1], cuts[1:]):
-            if b > a:
-                ctx.classify(data[a:b], base_offset=a, want_hits=want_hits)
-    except capi.LINE_ERRORS as e:
-        err = e
-    try:
-        remap = resolve_host_lines([ctx], data, want_hits, err)
-    except HOST_LINE_ERRORS as e:
-        raise reference_error(data, e)
-    if ctx.stats()["non_ascii"]:
-        check_utf8(data)
-    capi.allreduce_counts_all([ctx])              # one GPU: only the overflow guard of the 32-bit count fields
-    return ctx.counts(), (remap_hits(ctx.hits(), remap) if want_hits else None), data
+    err = [None]
+    _classify_on_device(ctx, graph, data, [(0, int(data.size))], want_hits, err, 0)
+    return (*settle([ctx], data, want_hits, err[0]), data)
 
 
 def classify_sharded(graph, gaf_path, want_hits=True, devices=None, _t=None):
@@ -447,10 +445,7 @@ def classify_sharded(graph, gaf_path, want_hits=True, devices=None, _t=None):
                 comm.start()
             else:
                 comm.run()
-                t_init = comm.join_or_raise(started=False)
-                note_rccl_init_s(t_init, len(ctxs))
-                if os.environ.get("SVJG_VERBOSE"):
-                    sys.stderr.write(f"[svjg] RCCL communicators for {len(ctxs)} GPUs (ncclCommInitAll): {t_init:.2f} s, in front of upload + classify\n")
+                comm.finish(started=False)
                 comm = None
         errs = [None] * len(distinct)
         if len(distinct) == 1:
@@ -465,29 +460,11 @@ def classify_sharded(graph, gaf_path, want_hits=True, devices=None, _t=None):
         # the first failing shard (file order) holds the first bad line
         first_bad = [(ranges[d][0][0], errs[i]) for i, d in enumerate(distinct) if errs[i] is not None]
         err = min(first_bad, key=lambda x: x[0])[1] if first_bad else None
-        if err is not None and not isinstance(err, capi.LINE_ERRORS):
-            raise err
-        try:
-            remap = resolve_host_lines(ctxs, data, want_hits, err)       # (lines with non-ASCII digits: Python's int() decides)
-        except HOST_LINE_ERRORS as e:
-            raise reference_error(data, e)
-        capi.release_host_tables()                 # (every context has the graph: the shared host copy of the kernels' tables can go)
-        _stamp(t, f"tables -> device, upload + classify on {len(distinct)} GPU(s)")
-        if any(c.stats()["non_ascii"] for c in ctxs):
-            check_utf8(data)
-        if comm is not None:
-            t_wait = time.perf_counter()
-            t_init = comm.join_or_raise()
-            note_rccl_init_s(t_init, len(ctxs))
-            if os.environ.get("SVJG_VERBOSE"):
-                sys.stderr.write(f"[svjg] RCCL communicators for {len(ctxs)} GPUs (ncclCommInitAll): {t_init:.2f} s beside upload + classify, "
-                                 f"{time.perf_counter() - t_wait:.2f} s of it waited for here\n")
-            comm = None
-        capi.allreduce_counts_all(ctxs)           # (one GPU: only the overflow guard)
-        total = ctxs[0].counts()
-        recs = None
-        if want_hits:
-            recs = remap_hits(gather_hits(ctxs), remap)
+
+        def resolved():
+            capi.release_host_tables()             # (every context has the graph: the shared host copy of the kernels' tables can go)
+            _stamp(t, f"tables -> device, upload + classify on {len(distinct)} GPU(s)")
+        total, recs = settle(ctxs, data, want_hits, err, resolved, comm.finish if comm else None)
         _stamp(t, "count all-reduce, counts + hit records -> host")
         return total, recs, data
     finally:
@@ -653,15 +630,7 @@ def classify_stream(graph, stream, want_hits=True, device=0, _t=None):
                 buf += b
             err = e
         data = np.frombuffer(bytes(buf), dtype=np.uint8) if err is not None else np.frombuffer(buf, dtype=np.uint8)
-        try:
-            remap = resolve_host_lines([ctx], data, want_hits, err)
-        except HOST_LINE_ERRORS as e:
-            raise reference_error(data, e)
-        _stamp(t, "stream -> device, classified while it arrived")
-        if ctx.stats()["non_ascii"]:
-            check_utf8(data)
-        capi.allreduce_counts_all([ctx])          # one GPU: the overflow guard
-        return ctx.counts(), (remap_hits(ctx.hits(), remap) if want_hits else None), data
+        return (*settle([ctx], data, want_hits, err, lambda: _stamp(t, "stream -> device, classified while it arrived")), data)
     finally:
         ctx.close()
 
@@ -692,11 +661,8 @@ def run(gaf_path, gfa_path, prefix, output_dir=None, device=None, dover_given=Fa
         finally:
             if stream is not sys.stdin.buffer:
                 stream.close()
-        capi.write_informative_json(out_json, data, recs, graph.sv_ids)
-        _stamp(t, "write _informative_aln.json")
-        write_handoff(out_json, graph.sv_ids, counts)
-        return counts, graph
-    counts, recs, data = classify_sharded(graph, gaf_path, want_hits=True, devices=None if device is None else [device], _t=t)
+    else:
+        counts, recs, data = classify_sharded(graph, gaf_path, want_hits=True, devices=None if device is None else [device], _t=t)
     capi.write_informative_json(out_json, data, recs, graph.sv_ids)
     _stamp(t, "write _informative_aln.json")
     write_handoff(out_json, graph.sv_ids, counts)

@@ -7,7 +7,18 @@ SURVEY.md §8(e).  Integer sums make the result independent of the reduction ord
 """
 import numpy as np
 
-_TERM = (10, 13)
+
+def next_terminator(data, off):
+    """Index of the first line terminator (byte 10 or 13) at or after `off` in `data` (uint8 array), or data.size if there is none.
+    Scans in 64 KB blocks: `data` may be a memory-mapped file."""
+    n = int(data.size)
+    while off < n:
+        blk = np.asarray(data[off:off + 65536])
+        hit = np.flatnonzero((blk == 10) | (blk == 13))
+        if hit.size:
+            return off + int(hit[0])
+        off += blk.size
+    return n
 
 
 def cut_points(data, n_ranks):
@@ -18,20 +29,10 @@ def cut_points(data, n_ranks):
     n = int(data.size)
     cuts = [0]
     for r in range(1, n_ranks):
-        p = max(cuts[-1], (n * r) // n_ranks)
-        while p < n and data[p] not in _TERM:
-            # scan forward in blocks
-            blk = data[p:p + 65536]
-            hit = np.flatnonzero((blk == 10) | (blk == 13))
-            if hit.size:
-                p += int(hit[0])
-                break
-            p += blk.size
+        p = next_terminator(data, max(cuts[-1], (n * r) // n_ranks))
         if p < n:
-            if data[p] == 13 and p + 1 < n and data[p + 1] == 10:
-                p += 1
-            p += 1
-        cuts.append(min(p, n))
+            p += 2 if data[p] == 13 and p + 1 < n and data[p + 1] == 10 else 1
+        cuts.append(p)
     cuts.append(n)
     return cuts
 

@@ -1725,17 +1725,15 @@ def test_fuzz_cases(ctx, golden):
         return False                                   # (r03: lines with Unicode digits in decimal columns are decided by the host, no longer left out)
 
     def classify(raw):
-        """ctx.classify + the host's part of the filter (svjg/filter.py): lines set aside for Python's int(), which error comes first"""
+        """ctx.classify + the host's part of the filter (svjg/filter.py: settle): lines set aside for Python's int(), which error comes
+        first, UTF-8 validity as the reference's text-mode read"""
         data = np.frombuffer(raw, dtype=np.uint8)
         err = None
         try:
             ctx.classify(data)
         except (ValueError, IndexError, KeyError, ZeroDivisionError) as e:
             err = e
-        try:
-            flt.resolve_host_lines([ctx], data, False, err)
-        except (ValueError, IndexError, KeyError, ZeroDivisionError) as e:
-            raise flt.reference_error(data, e)
+        flt.settle([ctx], data, False, err)
 
     for i, c in enumerate(cases):
         raw = base64.b64decode(c["gaf"])
@@ -1743,12 +1741,7 @@ def test_fuzz_cases(ctx, golden):
             continue
         ctx.reset_counts()
         try:
-            try:
-                classify(raw)
-            except Exception as e:
-                raise e
-            if ctx.stats()["non_ascii"]:
-                raw.decode("utf-8")                    # the host's check (svjg/filter.py), as the reference's text-mode read
+            classify(raw)
             got = ("ok", _counts_dict(g, ctx.counts()))
         except Exception as e:
             got = ("died", type(e).__name__)
@@ -1799,10 +1792,7 @@ def test_full_alphabet_cases_by_the_reference(ctx, golden, group, all_slow):
             ctx.classify(data)
         except (ValueError, IndexError, KeyError, ZeroDivisionError) as e:
             err = e
-        try:
-            flt.resolve_host_lines([ctx], data, False, err)
-        except flt.HOST_LINE_ERRORS as e:
-            raise flt.reference_error(data, e)
+        flt.settle([ctx], data, False, err)
 
     total, good, refused, n_host = {}, [], 0, 0
     for i, (raw, want) in enumerate(cases):
