@@ -279,8 +279,12 @@ int  svjg_vcf_write(const svjg_vcf *v, const char *out_path, const uint8_t *gt, 
                     const uint8_t *genotyped, uint64_t *n_genotyped);
 void svjg_vcf_free(svjg_vcf *v);
 
-/* ---- measurement hooks (bench.py): HIP-event time of the kernels of the last classify / genotype ---- */
+/* ---- measurement hooks (bench.py): time of the kernels of the last classify / genotype.  HIP events, except in a fused pass
+ * (svjg_run_begin): there the classify kernels leave time stamps of the device's constant-rate clock in the pass's status block — no
+ * event record stands between two passes' kernels —; SVJG_KERNEL_MS=events in the environment puts the event pair back, and
+ * svjg_last_main_ms then gives both readings of the same launch (by_events = 0 without it). ---- */
 int svjg_last_kernel_ms(svjg_ctx *ctx, float *classify_main_ms, float *classify_slow_ms, float *genotype_ms);
+int svjg_last_main_ms(svjg_ctx *ctx, float *by_stamps, float *by_events);
 int svjg_sync(svjg_ctx *ctx);
 /* what plain streams of n_bytes reach on this GPU right now (16 B per lane, non-temporal, four in flight per lane; best of three), in
  * GB/s: copy = a device-to-device copy, bytes read + bytes written per second; read = a kernel that only reads (and folds what it read

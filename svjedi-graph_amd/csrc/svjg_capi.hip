@@ -76,8 +76,12 @@ extern "C" void svjg_release_host_tables(void) {
 constexpr int STAGE_THREADS = 4;
 constexpr uint64_t STAGE_PIECE = 8ull << 20;
 
+// slots the passes of svjg_run_begin rotate through: two may be in flight, and the one the NEXT pass will use is zeroed while the newest computes
+constexpr int RUN_SLOTS = 3;
+
 struct svjg_ctx {
     int device = 0;
+    int wall_khz = 0;                    // rate of wall_clock64(), the clock of the kernels' time stamps
     int n_cu = 256;
     int occ_main = 0;                    // workgroups of k_classify_main one CU holds
     hipStream_t stream = nullptr, copy_stream = nullptr;
@@ -117,13 +121,15 @@ struct svjg_ctx {
         void *d = nullptr;  uint64_t d_cap = 0;  void *h = nullptr;  uint64_t h_cap = 0;  void *h_dev = nullptr;   // h_dev: the pinned block as the device sees it
         unsigned long long *counts = nullptr;  uint64_t counts_cap = 0;   // the pass's own count vector (+ guard words): the next pass may zero its own while this one is genotyped
         hipEvent_t ev[6] = {};  hipEvent_t computed = nullptr, copied = nullptr;
-        uint64_t base_offset = 0;  uint32_t min_support = 0;  double err = 0;  bool had_text = false, slow_end_own = false;
-    } run[2];
+        uint64_t base_offset = 0;  uint32_t min_support = 0;  double err = 0;  bool had_text = false, slow_end_own = false, timed_by_events = false;
+        bool clean = false;              // the pass before has already zeroed this slot's vector, status block and max_n (k_classify_exact)
+    } run[RUN_SLOTS];
     int run_head = 0, run_tail = 0, run_inflight = 0;
     int counts_in_slot = -1;                             // >= 0: the newest counts live in that slot's vector, not yet in d_counts (fetch_slot_counts)
     void *d_run_in = nullptr;  uint64_t d_run_in_cap = 0;  uint64_t run_rows = 0;  bool have_rows = false;
     // timing of the last calls
     float ms_main = 0, ms_slow = 0, ms_geno = 0;
+    float ms_main_stamps = 0, ms_main_events = 0;   // the last fused pass's k_classify_main by the device's clock / by the event pair (svjg_last_main_ms)
     // rccl
     ncclComm_t comm = nullptr;
     bool allreduce_second = false;       // svjg_comm_set_stream
@@ -168,6 +174,7 @@ extern "C" int svjg_init(int device, svjg_ctx **out) {
     }
     hipDeviceProp_t prop;
     if (hipGetDeviceProperties(&prop, device) == hipSuccess) c->n_cu = prop.multiProcessorCount;
+    if (hipDeviceGetAttribute(&c->wall_khz, hipDeviceAttributeWallClockRate, device) != hipSuccess || c->wall_khz < 1) c->wall_khz = 0;
     for (auto &ev : c->ev) hipEventCreate(&ev);
     if (hipMalloc(&c->d_dbg, 32 * 8) != hipSuccess || hipMalloc(&c->d_st, sizeof(DevStatus)) != hipSuccess || hipMalloc(&c->d_maxn, sizeof(unsigned int)) != hipSuccess ||
         hipHostMalloc((void **)&c->h_stp, 2 * sizeof(DevStatus), hipHostMallocDefault) != hipSuccess) {
@@ -189,6 +196,7 @@ static void free_graph(svjg_ctx *c) {
     c->d_nodes = nullptr; c->d_edges = nullptr; c->d_hits = nullptr; c->d_cnames = nullptr; c->d_coff = nullptr;
     c->d_clo = nullptr; c->d_chash = nullptr; c->d_counts = nullptr; c->d_snap = nullptr;
     c->have_graph = false; c->have_counts = false;
+    for (auto &r : c->run) r.clean = false;                   // (the next graph's vector may be longer than what was zeroed)
 }
 
 extern "C" void svjg_destroy(svjg_ctx *c) {
@@ -362,18 +370,6 @@ static int staged_upload(svjg_ctx *c, int fd, uint64_t offset, uint64_t n, uint6
     for (int t = 0; t < STAGE_THREADS; ++t)
         if (rcs[t]) { c->err = errs[t]; return rcs[t]; }
     return 0;
-}
-
-// blocks of k_classify_slow a CU holds at a time (LDS and registers decide; asked of the runtime once, 5 on gfx950 today)
-static uint32_t lane_blocks_per_cu(svjg_ctx *c) {
-    static int per_cu = 0;
-    if (!per_cu) {
-        int n = 0;
-        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, k_classify_slow, (int)SLOW_TPB, 0) != hipSuccess || n < 1) n = 4;
-        per_cu = n;
-    }
-    (void)c;
-    return (uint32_t)per_cu;
 }
 
 static int gaf_finish(svjg_ctx *c, uint64_t n, uint64_t need) {
@@ -1003,7 +999,9 @@ extern "C" int svjg_genotype_view(svjg_ctx *c, const uint8_t *sv_type, const uin
 // host memory.  svjg_run_end waits for the OLDEST pass in flight, checks what the host used to decide between the kernels
 // (a list that overflowed, more deferred lines than one wave per line is good for, a log10(i!) table too short: the pass is then
 // repeated the slow way) and hands out its results.  Up to two passes may be in flight: the results of pass k travel over PCIe
-// while pass k + 1 computes.  svjg_run_resident = begin + end.
+// while pass k + 1 computes.  The passes rotate through RUN_SLOTS = 3 slots (count vector, status block, result blocks): the slot
+// behind the newest pass is used by no pass in flight, and the newest pass's exact-path kernel zeroes it for the pass to come.
+// svjg_run_resident = begin + end.
 // host block (pinned, mapped into the device: the genotype kernel writes its results straight into it — they cross PCIe as they
 // are produced, no copy kernel competes with the next pass —): pl32, raw, gt, flags, boundary, then the tail; device block: the
 // tail (max_n, the pass's status block, the guard words: written by atomics, copied to the host block's tail in one small copy), pl64
@@ -1018,6 +1016,12 @@ static RunLayout run_layout(uint64_t n) {
     return L;
 }
 
+// SVJG_KERNEL_MS=events (read once): the fused pass's kernels timed by HIP events around them, as before r07
+static bool kernel_ms_by_events(const svjg_ctx *c) {
+    static const bool env_events = [] { const char *e = getenv("SVJG_KERNEL_MS"); return e && !strcmp(e, "events"); }();
+    return env_events || c->wall_khz == 0;
+}
+
 extern "C" int svjg_set_rows(svjg_ctx *c, const uint8_t *sv_type, const uint32_t *slot, const uint8_t *ok, uint64_t n_rows) {
     if (!c || (n_rows && (!sv_type || !slot || !ok))) return SVJG_E_ARG;
     if (c->run_inflight) { c->err = "svjg_set_rows with a pass in flight"; return SVJG_E_ARG; }
@@ -1027,8 +1031,9 @@ extern "C" int svjg_set_rows(svjg_ctx *c, const uint8_t *sv_type, const uint32_t
     const RunLayout L = run_layout(n_rows);
     int rc;
     if ((rc = ensure(c, &c->d_run_in, &c->d_run_in_cap, n_rows * 6 + 64, 1, false))) return rc;
-    for (int k = 0; k < 2; ++k) {
+    for (int k = 0; k < RUN_SLOTS; ++k) {
         svjg_ctx::RunSlot &r = c->run[k];
+        r.clean = false;                                      // (the blocks may move)
         if ((rc = ensure(c, &r.d, &r.d_cap, L.total, 1, false))) return rc;
         if (L.out_bytes > r.h_cap) {
             if (r.h) hipHostFree(r.h);
@@ -1039,7 +1044,7 @@ extern "C" int svjg_set_rows(svjg_ctx *c, const uint8_t *sv_type, const uint32_t
         }
         if ((rc = ensure(c, (void **)&r.counts, &r.counts_cap, (uint64_t)c->n_slots + GUARD_WORDS, sizeof(unsigned long long), false))) return rc;
         for (auto &e : r.ev) if (!e) HIPCHK(c, hipEventCreate(&e));
-        if (!r.computed) HIPCHK(c, hipEventCreate(&r.computed));          // (with a time stamp: it also ends the exact-path kernels' interval, below)
+        if (!r.computed) HIPCHK(c, hipEventCreate(&r.computed));          // (with a time stamp: under SVJG_KERNEL_MS=events it also ends the exact-path kernel's interval)
         if (!r.copied) HIPCHK(c, hipEventCreateWithFlags(&r.copied, hipEventDisableTiming));
     }
     if (!c->copy_stream) {                                    // (the lowest priority there is: what runs on it must not take issue slots from the classify kernel)
@@ -1089,12 +1094,16 @@ extern "C" int svjg_run_begin(svjg_ctx *c, uint64_t base_offset, uint32_t min_su
     DevStatus *d_st = (DevStatus *)(base + L.status);             // (the pass's own status block: its tail goes to the host in one small copy)
     if (r.counts_cap < (uint64_t)c->n_slots + GUARD_WORDS) { c->err = "svjg_set_rows must follow svjg_load_graph"; return SVJG_E_ARG; }
     GenoArgs ga = run_geno_args(c, r, L, min_support, err, r.counts);
-    {
-        const uint64_t words = (uint64_t)c->n_slots + GUARD_WORDS;
+    const uint64_t words = (uint64_t)c->n_slots + GUARD_WORDS;
+    if (!r.clean) {                                           // the first pass behind svjg_set_rows / svjg_load_graph, or behind a pass without text
         uint32_t rg = (uint32_t)((words + TPB - 1) / TPB);
         if (rg > 1024) rg = 1024;
         hipLaunchKernelGGL(k_step_reset, dim3(rg), dim3(TPB), 0, c->stream, r.counts, words, d_st, ga.max_n);
     }
+    r.clean = false;
+    // SVJG_KERNEL_MS=events: k_classify_main's time from an event pair around it, as before r07 (two barrier packets a pass; for
+    // comparing the two clocks: svjg_last_main_ms).  Otherwise from the time stamps the kernel leaves in the pass's status block.
+    r.timed_by_events = kernel_ms_by_events(c);
     const uint64_t max_blocks = (uint64_t)c->n_cu * 4, wave_limit = 16 * max_blocks;
     if (n) {
         ClassifyArgs a{};
@@ -1103,20 +1112,26 @@ extern "C" int svjg_run_begin(svjg_ctx *c, uint64_t base_offset, uint32_t min_su
         main_launch_setup(c, 0, n, base_offset, 0, a, grid, lds);
         if (!a.long_pre) { c->err = "no memory for the workers' scratch words"; return SVJG_E_NOMEM; }
         a.st = d_st; a.counts = r.counts;
-        HIPCHK(c, hipEventRecord(r.ev[0], c->stream));
+        if (r.timed_by_events) HIPCHK(c, hipEventRecord(r.ev[0], c->stream));
         hipLaunchKernelGGL(k_classify_main, dim3(grid), dim3(WG), lds, c->stream, a);
-        HIPCHK(c, hipEventRecord(r.ev[1], c->stream));
-        // the exact path, the number of deferred lines read on the device: one wave per line for up to wave_limit lines, one lane per
-        // line beyond it (each kernel works only when the number lies in its range: a few microseconds otherwise).  So whatever a shard
-        // defers is counted before the pass's all-reduce; only a LIST that overflowed makes the pass repeat (svjg_pass.h).  (One block per CU
-        // for the wave kernel: three would triple its rate and cost every pass that defers nothing 4 us; the lane kernel's 2 304 idle blocks
-        // cost such a pass 10 us, 0.85 % of the headline step — the price of never repeating a pass for deferred lines: gpurun j32 / j33.)
-        hipLaunchKernelGGL(k_classify_slow_wave, dim3((uint32_t)c->n_cu), dim3(SLOW_TPB), 0, c->stream, a, SLOW_ASK_DEVICE, 0ull, wave_limit);
-        const uint64_t lane_blocks = (uint64_t)c->n_cu * lane_blocks_per_cu(c);   // (here as many as the CUs hold at a time: idle blocks cost every pass)
-        hipLaunchKernelGGL(k_classify_slow, dim3((uint32_t)lane_blocks), dim3(SLOW_TPB), 0, c->stream, a, SLOW_ASK_DEVICE, wave_limit, ~0ull - 1);
+        if (r.timed_by_events) HIPCHK(c, hipEventRecord(r.ev[1], c->stream));
+        // Between this k_classify_main and the next pass's the compute stream carries ONE launch and ONE event record (`computed`):
+        //   k_classify_exact  the exact path, the number of deferred lines read on the device: every block picks its role from it (none / one
+        //                     wave per line up to wave_limit lines / one lane per line beyond: svjg_kernels.h).  So whatever a shard defers is
+        //                     counted before the pass's all-reduce; only a LIST that overflowed makes the pass repeat (svjg_pass.h).  The same
+        //                     blocks zero what the NEXT pass starts from — the count vector, status block and max_n of the slot behind this
+        //                     one, which no pass in flight uses: two are in flight at most, the slots are three — so the next pass launches no
+        //                     k_step_reset.
+        // Before r07 there were three launches (k_classify_slow_wave, k_classify_slow, k_step_reset) and three event records; the
+        // timeline of both: profiles/r07/experiments/pass_tail.txt.
+        svjg_ctx::RunSlot &nxt = c->run[(c->run_head + 1) % RUN_SLOTS];
+        NextPass nx{};
+        if (nxt.d && nxt.counts && nxt.counts_cap >= words) {
+            nx.counts = nxt.counts; nx.n_words = words; nx.st = (DevStatus *)((uint8_t *)nxt.d + L.status); nx.max_n = (unsigned int *)((uint8_t *)nxt.d + L.maxn);
+        }
+        hipLaunchKernelGGL(k_classify_exact, dim3((uint32_t)c->n_cu * EXACT_BLOCKS_PER_CU), dim3(EXACT_TPB), 0, c->stream, a, wave_limit, nx);
         HIPCHK(c, hipGetLastError());
-        // (no event of their own behind the two: `computed`, a few lines down, ends their interval — an event record is a barrier packet,
-        //  6 us of every pass: profiles/r05/experiments/pass_overhead.txt)
+        nxt.clean = nx.counts != nullptr;
     }
     // The count all-reduce of this pass — every rank issues its collectives in the same order, one per pass — runs on the compute
     // stream, between this pass's kernels and the next pass's: the classify kernel fills every CU (fourteen workers take 126 of a
@@ -1141,7 +1156,7 @@ extern "C" int svjg_run_begin(svjg_ctx *c, uint64_t base_offset, uint32_t min_su
     if (c->comm && !allreduce_second) {
         // (the exact-path kernels' interval must not hold the collective: under a communicator it gets an end event of its own — 6 us of a
         //  multi-GPU pass, none of a one-GPU pass, whose interval `computed` ends)
-        if (r.had_text) { HIPCHK(c, hipEventRecord(r.ev[2], c->stream)); r.slow_end_own = true; }
+        if (n && r.timed_by_events) { HIPCHK(c, hipEventRecord(r.ev[2], c->stream)); r.slow_end_own = true; }
         if ((rc = reduce_on(c->stream))) return rc;
     }
     HIPCHK(c, hipEventRecord(r.computed, c->stream));
@@ -1164,7 +1179,7 @@ extern "C" int svjg_run_begin(svjg_ctx *c, uint64_t base_offset, uint32_t min_su
     HIPCHK(c, hipEventRecord(r.copied, c->copy_stream));
     c->counts_in_slot = c->run_head;
     r.had_text = n != 0;
-    c->run_head ^= 1; ++c->run_inflight;
+    c->run_head = (c->run_head + 1) % RUN_SLOTS; ++c->run_inflight;
     return 0;
 }
 
@@ -1174,7 +1189,7 @@ extern "C" int svjg_run_end(svjg_ctx *c, const uint8_t **gt, const int32_t **pl,
     if (!c->run_inflight) { c->err = "no pass in flight"; return SVJG_E_ARG; }
     HIPCHK(c, hipSetDevice(c->device));
     svjg_ctx::RunSlot &r = c->run[c->run_tail];
-    c->run_tail ^= 1; --c->run_inflight;
+    c->run_tail = (c->run_tail + 1) % RUN_SLOTS; --c->run_inflight;
     const uint64_t n = c->gaf_bytes, n_rows = c->run_rows;
     const RunLayout L = run_layout(n_rows);
     uint8_t *hb = (uint8_t *)r.h;
@@ -1185,8 +1200,19 @@ extern "C" int svjg_run_end(svjg_ctx *c, const uint8_t **gt, const int32_t **pl,
     // ---- what the host would have decided in between ----
     c->ms_slow = 0;
     if (r.had_text) {
-        HIPCHK(c, hipEventElapsedTime(&c->ms_main, r.ev[0], r.ev[1]));
-        if (c->hs().n_deferred) HIPCHK(c, hipEventElapsedTime(&c->ms_slow, r.ev[1], r.slow_end_own ? r.ev[2] : r.computed));   // (the exact-path kernels alone: never the all-reduce)
+        // the device's clock: first worker's start to last worker's end, and from there to the end of the last block of the exact path
+        // that had work (never the all-reduce).  wall_clock64() counts at wall_khz.
+        const DevStatus &t = c->hs();
+        const float per_tick = c->wall_khz ? 1.0f / (float)c->wall_khz : 0.0f;
+        c->ms_main_stamps = t.t_last > t.t_first ? (float)(t.t_last - t.t_first) * per_tick : 0.0f;
+        c->ms_main_events = 0;
+        c->ms_main = c->ms_main_stamps;
+        if (t.n_deferred && t.t_exact > t.t_last) c->ms_slow = (float)(t.t_exact - t.t_last) * per_tick;
+        if (r.timed_by_events) {
+            HIPCHK(c, hipEventElapsedTime(&c->ms_main_events, r.ev[0], r.ev[1]));
+            c->ms_main = c->ms_main_events;
+            if (t.n_deferred) HIPCHK(c, hipEventElapsedTime(&c->ms_slow, r.ev[1], r.slow_end_own ? r.ev[2] : r.computed));   // (the exact-path kernel alone: never the all-reduce)
+        }
     }
     if (n_rows) HIPCHK(c, hipEventElapsedTime(&c->ms_geno, r.ev[4], r.ev[5]));
     bool again = false;
@@ -1257,6 +1283,13 @@ extern "C" int svjg_last_kernel_ms(svjg_ctx *c, float *m, float *s, float *g) {
     if (m) *m = c->ms_main;
     if (s) *s = c->ms_slow;
     if (g) *g = c->ms_geno;
+    return 0;
+}
+
+extern "C" int svjg_last_main_ms(svjg_ctx *c, float *by_stamps, float *by_events) {
+    if (!c) return SVJG_E_ARG;
+    if (by_stamps) *by_stamps = c->ms_main_stamps;
+    if (by_events) *by_events = c->ms_main_events;
     return 0;
 }
 

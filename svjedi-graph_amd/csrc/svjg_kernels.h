@@ -99,6 +99,8 @@ struct DevStatus {
     unsigned long long next_chunk;       // k_classify_main: small chunks handed out so far (zero at launch)
     unsigned long long n_host;           // lines set aside for the host (SVJG_EXC_ASK_HOST)
     unsigned long long cause[8];         // deferred lines by cause (DC_*)
+    unsigned long long t_first, t_last;  // k_classify_main: wall_clock64() when its first worker started / its last worker ended (zero at launch)
+    unsigned long long t_exact;          // k_classify_exact: when the last block that had lines to work off ended
 };
 
 struct ClassifyArgs {
@@ -464,6 +466,7 @@ __device__ inline uint32_t clamp64(uint32_t hi, uint32_t lo) { return hi > lo ? 
 // question is asked again with another modulus (B, then 15/16, 14/16 ... 9/16 of it: the stretches then lie differently) — a line that really
 // comes back to a node is caught by every one of them, a line that does not is let go by the first that tells its stretches apart — and only
 // what all eight flag takes the caller's full search, which is exact.  One call per long line, ~30 instructions a try, two tries on average.
+static_assert(KLONG <= 224, "ids + bitmap share the 256 tab-bitmap words");
 __device__ inline bool long_line_may_repeat(uint32_t *ids, uint32_t K, uint32_t lane) {
     const uint32_t nb = K <= 128u ? 128u : K <= 192u ? 64u : 32u, B = nb * 32u;
     uint32_t *bm = ids + 256u - nb;
@@ -513,6 +516,10 @@ __global__ __launch_bounds__(WG, SVJG_MINW) void k_classify_main(ClassifyArgs a)
     // sit four, four, three and three on its SIMDs and those that share an issue port with three others are a quarter slower
     // (even shares: the last worker ended 15 % behind the average one).
     unsigned long long pos = a.begin + (unsigned long long)blockIdx.x * a.region;   // first byte not worked off yet (wave-uniform)
+    // the kernel's interval without an event record around it (svjg_run_begin): workgroups are handed out in the order of their
+    // numbers, so worker 0 is the first to start — a plain store, no 3 584 atomics on one word at the same moment —; every worker
+    // leaves the time it ended (atomicMax without a result: nobody waits for it)
+    if (blockIdx.x == 0 && lane == 0) a.st->t_first = wall_clock64();
     if (pos >= a.n_bytes) return;
     unsigned long long rend = pos + a.region < a.n_bytes ? pos + a.region : a.n_bytes;   // lines starting before it belong to this chunk
 
@@ -1416,6 +1423,7 @@ __global__ __launch_bounds__(WG, SVJG_MINW) void k_classify_main(ClassifyArgs a)
     rend = pos + a.small < a.n_bytes ? pos + a.small : a.n_bytes;
   }
     if (lane == 0 && wave_lines) atomicAdd(&a.st->n_lines, wave_lines);
+    if (lane == 0) atomicMax(&a.st->t_last, (unsigned long long)wall_clock64());
 #ifdef SVJG_TIMING
     if ((a.diag & 16u) && lane == 0)
         for (int i = 0; i < 16; ++i) atomicAdd(&a.dbg[i], acc[i]);
@@ -1509,13 +1517,18 @@ __device__ inline uint64_t slow_n_def(const ClassifyArgs &a, uint64_t n_def, uin
 // one-wave-per-line kernel does (svjg_line.h: slow_wave_phase1 / phase2 with one lane): O(k) name resolutions a line instead of O(k^2).
 // A path of more nodes runs through slow_line as before.
 constexpr uint32_t SLOW_LANE_NODES = 12;
-__global__ __launch_bounds__(SLOW_TPB) void k_classify_slow(ClassifyArgs a, uint64_t n_def_arg, uint64_t lo, uint64_t hi) {
-    const uint64_t n_def = slow_n_def(a, n_def_arg, lo, hi);
-    __shared__ __attribute__((aligned(16))) uint8_t stage[SLOW_LANE_LDS];
-    __shared__ int64_t c_len[SLOW_LANE_NODES * SLOW_TPB];
-    __shared__ uint32_t c_id[SLOW_LANE_NODES * SLOW_TPB];
-    __shared__ uint8_t c_rc[SLOW_LANE_NODES * SLOW_TPB], c_strand[SLOW_LANE_NODES * SLOW_TPB];
-    const uint32_t lane = threadIdx.x;
+// The kernel's body works on LDS handed to it: WAVES waves of a block run it side by side, each on SLOW_LANE_BYTES(STAGE) bytes of its
+// own (k_classify_slow: one wave, k_classify_exact: two).  Every wave of a block makes the same number of rounds (the barriers).
+constexpr uint32_t SLOW_LANE_SCRATCH = SLOW_LANE_NODES * SLOW_TPB * 14;   // c_len 8, c_id 4, c_rc 1, c_strand 1 bytes a node
+template <uint32_t WAVES, uint32_t STAGE>
+__device__ __forceinline__ void slow_lane_role(const ClassifyArgs &a, const uint64_t n_def, uint8_t *pool) {
+    static_assert(STAGE % 16 == 0, "LDS alignment");
+    const uint32_t lane = threadIdx.x & 63u, wave = WAVES > 1 ? threadIdx.x >> 6 : 0u;
+    uint8_t *stage = pool + wave * (STAGE + SLOW_LANE_SCRATCH);
+    int64_t *c_len = (int64_t *)(stage + STAGE);
+    uint32_t *c_id = (uint32_t *)(c_len + SLOW_LANE_NODES * SLOW_TPB);
+    uint8_t *c_rc = (uint8_t *)(c_id + SLOW_LANE_NODES * SLOW_TPB), *c_strand = c_rc + SLOW_LANE_NODES * SLOW_TPB;
+    constexpr uint32_t SLOW_LANE_LDS = STAGE;
 #ifdef SVJG_TIMING
     // measurement only (SVJG_DIAG & 16): the longest any block of 64 lines took per step (a.dbg[24 ..]: terminators + staging, per-line part, nodes, links)
     unsigned long long lstamp = __builtin_readcyclecounter();
@@ -1523,7 +1536,8 @@ __global__ __launch_bounds__(SLOW_TPB) void k_classify_slow(ClassifyArgs a, uint
 #else
 #define ltick(i) do { } while (0)
 #endif
-    for (uint64_t b0 = (uint64_t)blockIdx.x * SLOW_TPB; b0 < n_def; b0 += (uint64_t)gridDim.x * SLOW_TPB) {
+    for (uint64_t g0 = (uint64_t)blockIdx.x * WAVES; g0 * SLOW_TPB < n_def; g0 += (uint64_t)gridDim.x * WAVES) {
+        const uint64_t b0 = (g0 + wave) * SLOW_TPB;                       // this wave's 64 lines
         const bool have = b0 + lane < n_def;
         ltick(4);
         uint64_t s = 0, e = 0;
@@ -1574,6 +1588,10 @@ __global__ __launch_bounds__(SLOW_TPB) void k_classify_slow(ClassifyArgs a, uint
         }
         __syncthreads();
     }
+}
+__global__ __launch_bounds__(SLOW_TPB) void k_classify_slow(ClassifyArgs a, uint64_t n_def_arg, uint64_t lo, uint64_t hi) {
+    __shared__ __attribute__((aligned(16))) uint8_t pool[SLOW_LANE_LDS + SLOW_LANE_SCRATCH];
+    slow_lane_role<1, SLOW_LANE_LDS>(a, slow_n_def(a, n_def_arg, lo, hi), pool);
 }
 
 // The exact path for a few lines: one WAVE per deferred line.  Every lane runs the per-line part (same control flow in
@@ -1683,16 +1701,20 @@ __device__ inline int slow_prologue_wave(slow_lds_text t, uint64_t s, uint64_t e
     o.Tlen = v6; o.Ts = v7; o.Te = v8;
     return 0;
 }
-__global__ __launch_bounds__(SLOW_TPB) void k_classify_slow_wave(ClassifyArgs a, uint64_t n_def_arg, uint64_t lo, uint64_t hi) {
-    const uint64_t n_def = slow_n_def(a, n_def_arg, lo, hi);
-    __shared__ __attribute__((aligned(16))) uint8_t stage[SLOW_LDS];
-    __shared__ int64_t n_len[SLOW_NODES];
-    __shared__ uint32_t n_id[SLOW_NODES];
-    __shared__ uint8_t n_rc[SLOW_NODES], n_strand[SLOW_NODES];
-    __shared__ uint32_t n_piece[SLOW_NODES];                           // the path's pieces: start | length << 16 (svjg_line.h: strand_of_pieces)
-    __shared__ uint16_t n_colon[SLOW_NODES];                           // ... where each has its ':' (piece_colons)
-    __shared__ uint64_t n_key[SLOW_NODES];                             // ... and what stands around it (piece_key)
-    const uint32_t lane = threadIdx.x;
+// The kernel's body, run by ONE wave on SLOW_WAVE_BYTES of LDS handed to it.  SOLO: the wave is not the only one of its block
+// (k_classify_exact), so the places where it waits for its own LDS writes must not be block barriers.
+constexpr uint32_t SLOW_WAVE_BYTES = SLOW_LDS + SLOW_NODES * 28;       // stage, then n_len 8, n_key 8, n_id 4, n_piece 4, n_colon 2, n_rc 1, n_strand 1 bytes a node
+template <bool SOLO> __device__ __forceinline__ void slow_role_sync() { if (SOLO) wave_sync(); else __syncthreads(); }
+template <bool SOLO>
+__device__ __forceinline__ void slow_wave_role(const ClassifyArgs &a, const uint64_t n_def, uint8_t *pool) {
+    uint8_t *stage = pool;
+    int64_t *n_len = (int64_t *)(pool + SLOW_LDS);
+    uint64_t *n_key = (uint64_t *)(n_len + SLOW_NODES);                // what stands around a piece's ':' (piece_key)
+    uint32_t *n_id = (uint32_t *)(n_key + SLOW_NODES);
+    uint32_t *n_piece = n_id + SLOW_NODES;                             // the path's pieces: start | length << 16 (svjg_line.h: strand_of_pieces)
+    uint16_t *n_colon = (uint16_t *)(n_piece + SLOW_NODES);            // ... where each has its ':' (piece_colons)
+    uint8_t *n_rc = (uint8_t *)(n_colon + SLOW_NODES), *n_strand = n_rc + SLOW_NODES;
+    const uint32_t lane = threadIdx.x & 63u;
 #ifdef SVJG_TIMING
     // measurement only (SVJG_DIAG & 16): the longest any line took per step of this kernel (a.dbg[16 ..]: terminator + staging, per-line part,
     // piece table, nodes, links)
@@ -1722,7 +1744,7 @@ __global__ __launch_bounds__(SLOW_TPB) void k_classify_slow_wave(ClassifyArgs a,
         const uint64_t span = (e - a0 + 15) & ~15ull;                     // bytes of the aligned blocks that hold the line
         const bool staged = span <= SLOW_LDS;
         if (staged) for (uint64_t o = (uint64_t)lane * 16; o < span; o += 1024) *(uint4 *)(stage + o) = *(const uint4 *)(a.gaf + a0 + o);
-        __syncthreads();
+        slow_role_sync<SOLO>();
         wtick(0);
         SlowEmit em{&a, a.base_offset + s};
         uint64_t order = 0;
@@ -1756,7 +1778,7 @@ __global__ __launch_bounds__(SLOW_TPB) void k_classify_slow_wave(ClassifyArgs a,
                     run += (uint32_t)__popcll(m);
                 }
                 ln.k = run;
-                __syncthreads();
+                slow_role_sync<SOLO>();
             }
             if (!rc && ln.k >= 2) {
                 if (ln.k <= SLOW_NODES) {
@@ -1770,14 +1792,14 @@ __global__ __launch_bounds__(SLOW_TPB) void k_classify_slow_wave(ClassifyArgs a,
                             while (e0 > s0 && ((uint8_t)t[e0 - 1] == sep1 || (uint8_t)t[e0 - 1] == sep2)) --e0;
                             n_len[i] = (int64_t)(e0 - s0);                   // (kept aside: the starts are still being read by the neighbours)
                         }
-                        __syncthreads();
+                        slow_role_sync<SOLO>();
                         for (uint32_t i = lane; i < ln.k; i += 64) { const uint16_t cw = piece_colons(t, n_piece[i], (uint64_t)n_len[i]); n_colon[i] = cw; n_key[i] = piece_key(t, n_piece[i], cw); n_piece[i] |= (uint32_t)n_len[i] << 16; }
-                        __syncthreads();
+                        slow_role_sync<SOLO>();
                     }
                     wtick(2);
                     // every node's id and length first, then the strands: by id where the line allows it (svjg_line.h: slow_wave_strands)
                     slow_wave_resolve(a.g, t, ln, ns, lane, 64u, (const SVJG_TAB_AS uint32_t *)n_piece);
-                    __syncthreads();
+                    slow_role_sync<SOLO>();
                     bool clean = ln.oriented, rises = true;
                     for (uint32_t i = lane; i < ln.k; i += 64) {
                         const uint32_t x = n_id[i];
@@ -1789,7 +1811,7 @@ __global__ __launch_bounds__(SLOW_TPB) void k_classify_slow_wave(ClassifyArgs a,
                     // (the call fills `order`: result and order are separate statements, not two arguments of one call)
                     const int r1 = slow_wave_strands(t, ln, ns, lane, 64u, &order, (const SVJG_TAB_AS uint32_t *)n_piece, (const SVJG_TAB_AS uint16_t *)n_colon, (const SVJG_TAB_AS uint64_t *)n_key, clean, rises);
                     rc = wave_min(r1, order);
-                    __syncthreads();
+                    slow_role_sync<SOLO>();
                     wtick(3);
                     if (!rc) {
                         // has every node a length?  Then the links need no walks over the node list: a running sum in place, and a table of
@@ -1802,7 +1824,7 @@ __global__ __launch_bounds__(SLOW_TPB) void k_classify_slow_wave(ClassifyArgs a,
                         }
                         if (__ballot(!good) == 0ull) {
                             oneway = __ballot(!oneway) == 0ull;
-                            __syncthreads();
+                            slow_role_sync<SOLO>();
                             for (uint32_t j = lane; j < ln.k; j += 64) {
                                 uint32_t f = j;
                                 if (!oneway) { const uint32_t x = n_id[j]; if (x != NONE32) { f = 0; while (n_id[f] != x) ++f; } }
@@ -1817,7 +1839,7 @@ __global__ __launch_bounds__(SLOW_TPB) void k_classify_slow_wave(ClassifyArgs a,
                             for (int d = 1; d < 64; d <<= 1) { const unsigned long long y = __shfl_up(inc, d); if ((int)lane >= d) inc += y; }
                             unsigned long long run = inc - sum;
                             for (uint32_t j = j0; j < j1; ++j) { run += (unsigned long long)n_len[j]; n_len[j] = (int64_t)run; }
-                            __syncthreads();
+                            slow_role_sync<SOLO>();
                             const int r2 = slow_wave_links_summed(a.g, ln, (const SVJG_TAB_AS uint32_t *)n_id, (const SVJG_TAB_AS int64_t *)n_len, (const SVJG_TAB_AS uint8_t *)n_strand,
                                                                   (const SVJG_TAB_AS uint32_t *)n_piece, em, lane, &order);
                             rc = wave_min(r2, order);
@@ -1828,8 +1850,47 @@ __global__ __launch_bounds__(SLOW_TPB) void k_classify_slow_wave(ClassifyArgs a,
             }
         } else { const int r4 = slow_line(a.g, a.gaf, s, e, em, lane, 64u, &order); rc = wave_min(r4, order); }
         if (lane == 0 && rc) report_line(a, a.base_offset + s, rc);
-        __syncthreads();
+        slow_role_sync<SOLO>();
     }
+}
+__global__ __launch_bounds__(SLOW_TPB) void k_classify_slow_wave(ClassifyArgs a, uint64_t n_def_arg, uint64_t lo, uint64_t hi) {
+    __shared__ __attribute__((aligned(16))) uint8_t pool[SLOW_WAVE_BYTES];
+    slow_wave_role<false>(a, slow_n_def(a, n_def_arg, lo, hi), pool);
+}
+
+// svjg_run_begin: the whole exact path behind k_classify_main in ONE launch, and the next pass's reset with it.  The number of deferred
+// lines is what the main kernel left in the status block (SLOW_ASK_DEVICE above); every block reads it and picks its role: none (no
+// line deferred, or the list overflowed: the host repeats the pass), one wave per line up to wave_limit lines (the block's second
+// wave leaves at once; the first one never meets a block barrier: slow_wave_role<true>), one lane per line beyond it, both waves
+// working.  A block is two waves so that the LDS the wave role needs (SLOW_WAVE_BYTES) is not lost on the lane role: two lane
+// stages fit in it, three blocks a CU are six lane waves where k_classify_slow alone has five (the stage is 256 bytes shorter than
+// there for that: 42 granules a block).  Before anything else the blocks zero what the pass AFTER this one starts from — its count
+// vector, status block and max_n (k_step_reset; `nx` names a slot no pass in flight uses) —, so that no launch stands between this
+// kernel and the next k_classify_main.
+constexpr uint32_t EXACT_TPB = 2 * SLOW_TPB;
+constexpr uint32_t EXACT_LANE_STAGE = 16128;
+constexpr uint32_t EXACT_LANE_BYTES = 2 * (EXACT_LANE_STAGE + SLOW_LANE_SCRATCH);
+constexpr uint32_t EXACT_LDS = SLOW_WAVE_BYTES > EXACT_LANE_BYTES ? SLOW_WAVE_BYTES : EXACT_LANE_BYTES;
+constexpr uint32_t EXACT_BLOCKS_PER_CU = 3;
+static_assert(EXACT_LDS <= (128 / EXACT_BLOCKS_PER_CU) * LDS_GRANULE, "three blocks of k_classify_exact per CU");
+struct NextPass { unsigned long long *counts; uint64_t n_words; DevStatus *st; unsigned int *max_n; };   // counts = nullptr: nothing to reset
+__global__ __launch_bounds__(EXACT_TPB) void k_classify_exact(ClassifyArgs a, uint64_t wave_limit, NextPass nx) {
+    __shared__ __attribute__((aligned(16))) uint8_t pool[EXACT_LDS];
+    if (nx.counts) {
+        for (uint64_t i = (uint64_t)blockIdx.x * EXACT_TPB + threadIdx.x; i < nx.n_words; i += (uint64_t)gridDim.x * EXACT_TPB) nx.counts[i] = 0ull;
+        if (blockIdx.x == 0 && threadIdx.x == 0) {
+            DevStatus z{}; z.err = ~0ull;
+            *nx.st = z;
+            nx.max_n[0] = 0u; nx.max_n[1] = 0u;
+        }
+    }
+    const uint64_t n_def = slow_n_def(a, SLOW_ASK_DEVICE, 0ull, ~0ull - 1);      // (the same in every block: neither role writes what it reads)
+    if (!n_def) return;
+    if (n_def <= wave_limit) {
+        if (threadIdx.x >= SLOW_TPB) return;
+        slow_wave_role<true>(a, n_def, pool);
+    } else slow_lane_role<2, EXACT_LANE_STAGE>(a, n_def, pool);
+    if ((threadIdx.x & 63u) == 0) atomicMax(&a.st->t_exact, (unsigned long long)wall_clock64());
 }
 
 // Overflow guard of the packed count vector (ref | alt << 32, summed as one 64-bit integer by the kernels' atomics and by the

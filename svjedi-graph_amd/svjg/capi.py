@@ -90,6 +90,7 @@ _SIGS = {
     "svjg_genotype_boundary": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64]),
     "svjg_last_kernel_ms": (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(ctypes.c_float), ctypes.POINTER(ctypes.c_float),
                                            ctypes.POINTER(ctypes.c_float)]),
+    "svjg_last_main_ms": (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(ctypes.c_float), ctypes.POINTER(ctypes.c_float)]),
     "svjg_sync": (ctypes.c_int, [ctypes.c_void_p]),
 }
 
@@ -518,6 +519,12 @@ class Context:
         a, b, c = ctypes.c_float(0), ctypes.c_float(0), ctypes.c_float(0)
         self._chk(self.lib.svjg_last_kernel_ms(self.h, ctypes.byref(a), ctypes.byref(b), ctypes.byref(c)))
         return a.value, b.value, c.value
+
+    def main_ms_both(self):
+        """k_classify_main of the last fused pass -> (ms by the device's clock, ms by the event pair or 0.0 without SVJG_KERNEL_MS=events)"""
+        a, b = ctypes.c_float(0), ctypes.c_float(0)
+        self._chk(self.lib.svjg_last_main_ms(self.h, ctypes.byref(a), ctypes.byref(b)))
+        return a.value, b.value
 
     def sync(self):
         self._chk(self.lib.svjg_sync(self.h))
