@@ -499,6 +499,19 @@ static void main_launch_setup(svjg_ctx *c, uint64_t begin, uint64_t end, uint64_
     grid = (uint32_t)(want_grid < full ? want_grid : full);
 }
 
+// The exact path's one launch, k_classify_exact behind a k_classify_main with the same arguments: its blocks take the wave role up to
+// `wave_rounds` rounds of deferred lines, the lane role beyond, and zero `nx` for the fused pass after this one (NextPass{}: nothing).
+// The two callers' limits were measured apart; making them one needs a crossover measurement and is not part of unifying the kernels.
+constexpr uint64_t EXACT_ROUND_PER_CU = 4;      // lines a CU in a round: the grid of the former one-wave-per-line kernel, now only the limits' unit
+constexpr uint64_t STEP_WAVE_ROUNDS = 30;       // classify_range: the roles met at ~31 k lines on 256 CUs (profiles/r04/experiments/exact_path.txt)
+constexpr uint64_t FUSED_WAVE_ROUNDS = 16;      // svjg_run_begin: r07 (profiles/r07/experiments/pass_tail.txt)
+static int launch_exact(svjg_ctx *c, const ClassifyArgs &a, uint64_t wave_rounds, const NextPass &nx) {
+    const uint64_t wave_limit = wave_rounds * EXACT_ROUND_PER_CU * (uint64_t)c->n_cu;
+    hipLaunchKernelGGL(k_classify_exact, dim3((uint32_t)c->n_cu * EXACT_BLOCKS_PER_CU), dim3(EXACT_TPB), 0, c->stream, a, wave_limit, nx);
+    HIPCHK(c, hipGetLastError());
+    return 0;
+}
+
 // the lines of the resident text that lie in [begin, end): begin is a line start, end the byte behind a terminator (or the text's end)
 static int classify_range(svjg_ctx *c, uint64_t begin, uint64_t end, uint64_t base_offset, int want_hits) {
     HIPCHK(c, hipSetDevice(c->device));
@@ -544,18 +557,7 @@ static int classify_range(svjg_ctx *c, uint64_t begin, uint64_t end, uint64_t ba
         c->ms_slow = 0;
         if (n_def && !(c->hs().overflow & 1u)) {
             HIPCHK(c, hipEventRecord(c->ev[2], c->stream));
-            const uint64_t max_blocks = (uint64_t)c->n_cu * 4;              // (53 KB of LDS each: three at a time per CU)
-            const uint64_t lane_blocks = (uint64_t)c->n_cu * 9;           // the lane-per-line kernel: more blocks than the CUs hold at a time (5 each): the queue evens out the blocks' different times
-            if (n_def <= 30 * max_blocks) {
-                // one wave per line: ~52 ns a line with every CU busy (10 k ordinary lines 0.53 ms); the lane-per-line kernel needs ~1.6 ms
-                // for any number of lines (sixty-four lines with sixty-four control flows share a wave) and ~4 ns for every further one:
-                // they meet at ~31 k lines (profiles/r04/experiments/exact_path.txt)
-                hipLaunchKernelGGL(k_classify_slow_wave, dim3((uint32_t)(n_def < max_blocks ? n_def : max_blocks)), dim3(SLOW_TPB), 0, c->stream, a, n_def, 0ull, 0ull);
-            } else {
-                const uint64_t want_blocks = (n_def + SLOW_TPB - 1) / SLOW_TPB;
-                hipLaunchKernelGGL(k_classify_slow, dim3((uint32_t)(want_blocks < lane_blocks ? want_blocks : lane_blocks)), dim3(SLOW_TPB), 0, c->stream, a, n_def, 0ull, 0ull);
-            }
-            HIPCHK(c, hipGetLastError());
+            if ((rc = launch_exact(c, a, STEP_WAVE_ROUNDS, NextPass{}))) return rc;
             HIPCHK(c, hipEventRecord(c->ev[3], c->stream));
             HIPCHK(c, hipMemcpyAsync(&c->hs(), c->d_st, sizeof(DevStatus), hipMemcpyDeviceToHost, c->stream));
             HIPCHK(c, hipStreamSynchronize(c->stream));
@@ -1098,13 +1100,12 @@ extern "C" int svjg_run_begin(svjg_ctx *c, uint64_t base_offset, uint32_t min_su
     if (!r.clean) {                                           // the first pass behind svjg_set_rows / svjg_load_graph, or behind a pass without text
         uint32_t rg = (uint32_t)((words + TPB - 1) / TPB);
         if (rg > 1024) rg = 1024;
-        hipLaunchKernelGGL(k_step_reset, dim3(rg), dim3(TPB), 0, c->stream, r.counts, words, d_st, ga.max_n);
+        hipLaunchKernelGGL(k_step_reset, dim3(rg), dim3(TPB), 0, c->stream, NextPass{r.counts, words, d_st, ga.max_n});
     }
     r.clean = false;
     // SVJG_KERNEL_MS=events: k_classify_main's time from an event pair around it, as before r07 (two barrier packets a pass; for
     // comparing the two clocks: svjg_last_main_ms).  Otherwise from the time stamps the kernel leaves in the pass's status block.
     r.timed_by_events = kernel_ms_by_events(c);
-    const uint64_t max_blocks = (uint64_t)c->n_cu * 4, wave_limit = 16 * max_blocks;
     if (n) {
         ClassifyArgs a{};
         uint32_t grid = 0;
@@ -1116,21 +1117,19 @@ extern "C" int svjg_run_begin(svjg_ctx *c, uint64_t base_offset, uint32_t min_su
         hipLaunchKernelGGL(k_classify_main, dim3(grid), dim3(WG), lds, c->stream, a);
         if (r.timed_by_events) HIPCHK(c, hipEventRecord(r.ev[1], c->stream));
         // Between this k_classify_main and the next pass's the compute stream carries ONE launch and ONE event record (`computed`):
-        //   k_classify_exact  the exact path, the number of deferred lines read on the device: every block picks its role from it (none / one
-        //                     wave per line up to wave_limit lines / one lane per line beyond: svjg_kernels.h).  So whatever a shard defers is
-        //                     counted before the pass's all-reduce; only a LIST that overflowed makes the pass repeat (svjg_pass.h).  The same
+        //   k_classify_exact  the exact path, the number of deferred lines read on the device (launch_exact above).  So whatever a shard defers
+        //                     is counted before the pass's all-reduce; only a LIST that overflowed makes the pass repeat (svjg_pass.h).  The same
         //                     blocks zero what the NEXT pass starts from — the count vector, status block and max_n of the slot behind this
         //                     one, which no pass in flight uses: two are in flight at most, the slots are three — so the next pass launches no
         //                     k_step_reset.
-        // Before r07 there were three launches (k_classify_slow_wave, k_classify_slow, k_step_reset) and three event records; the
-        // timeline of both: profiles/r07/experiments/pass_tail.txt.
+        // Before r07 there were three launches (two exact-path kernels, k_step_reset) and three event records; the timeline of both:
+        // profiles/r07/experiments/pass_tail.txt.
         svjg_ctx::RunSlot &nxt = c->run[(c->run_head + 1) % RUN_SLOTS];
         NextPass nx{};
         if (nxt.d && nxt.counts && nxt.counts_cap >= words) {
             nx.counts = nxt.counts; nx.n_words = words; nx.st = (DevStatus *)((uint8_t *)nxt.d + L.status); nx.max_n = (unsigned int *)((uint8_t *)nxt.d + L.maxn);
         }
-        hipLaunchKernelGGL(k_classify_exact, dim3((uint32_t)c->n_cu * EXACT_BLOCKS_PER_CU), dim3(EXACT_TPB), 0, c->stream, a, wave_limit, nx);
-        HIPCHK(c, hipGetLastError());
+        if ((rc = launch_exact(c, a, FUSED_WAVE_ROUNDS, nx))) return rc;
         nxt.clean = nx.counts != nullptr;
     }
     // The count all-reduce of this pass — every rank issues its collectives in the same order, one per pass — runs on the compute
@@ -1154,7 +1153,7 @@ extern "C" int svjg_run_begin(svjg_ctx *c, uint64_t base_offset, uint32_t min_su
     };
     r.slow_end_own = false;
     if (c->comm && !allreduce_second) {
-        // (the exact-path kernels' interval must not hold the collective: under a communicator it gets an end event of its own — 6 us of a
+        // (the exact-path kernel's interval must not hold the collective: under a communicator it gets an end event of its own — 6 us of a
         //  multi-GPU pass, none of a one-GPU pass, whose interval `computed` ends)
         if (n && r.timed_by_events) { HIPCHK(c, hipEventRecord(r.ev[2], c->stream)); r.slow_end_own = true; }
         if ((rc = reduce_on(c->stream))) return rc;
@@ -1220,9 +1219,9 @@ extern "C" int svjg_run_end(svjg_ctx *c, const uint8_t **gt, const int32_t **pl,
     const unsigned long long *gd = (const unsigned long long *)(tail + L.guard);   // (meaningful under a communicator: the sums over the ranks)
     if (pass_repeats(c->comm != nullptr, c->hs().overflow, gd[GUARD_REPEAT])) {
         // a list of this rank — or, under a communicator, of ANY rank (svjg_pass.h: the ranks decide together, so all of them issue the
-        // one more all-reduce below) — was too short: the pass again, step by step (classify_range sizes the lists, picks the exact-path
-        // kernel and retries), behind whatever is enqueued already.  The all-reduce is issued even when this rank's text turns out to be
-        // malformed: its peers are waiting in theirs.
+        // one more all-reduce below) — was too short: the pass again, step by step (classify_range sizes the lists and
+        // retries), behind whatever is enqueued already.  The all-reduce is issued even when this rank's text turns out to be malformed:
+        // its peers are waiting in theirs.
         if ((rc = svjg_reset_counts(c))) return rc;
         rc = classify_range(c, 0, n, r.base_offset, 0);
         if (rc && rc != SVJG_E_INPUT) return rc;

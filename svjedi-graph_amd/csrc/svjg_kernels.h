@@ -5,7 +5,10 @@
 //                      coalesced HBM -> register -> LDS staging, byte classes by bit planes (svjg_planes.h), rank-indexed
 //                      lists of line starts / orientation marks, then loop-free per-line, per-node and per-link phases with
 //                      a perfect-hash node-record table, packed 64-bit (ref | alt << 32) atomics into the per-SV count vector
-//   k_classify_slow  one lane per deferred line, exact string path (svjg::slow_line) on an LDS copy of the line
+//   k_classify_exact the exact string path (svjg_line.h, the reference's semantics) for the lines the main kernel defers, on LDS
+//                      copies of the lines; every block picks its role from the number of deferred lines: one wave per line up to
+//                      a limit, one lane per line beyond it.  It also zeroes what the next fused pass starts from
+//   k_step_reset     that reset alone, for a fused pass with no pass in front of it
 //   k_logfact_*      log10(i!) table in double-double for the binomial term
 //   k_genotype       one VCF row per lane, fp64 / double-double likelihoods (predict-genotype.py:281-325)
 #pragma once
@@ -1457,15 +1460,20 @@ __global__ __launch_bounds__(TPB) void k_read16(uint4 *sink, const uint4 *src, u
     if (acc == 0x12345677u) sink[0].x = acc;
 }
 
-// svjg_run_resident: the three things a pass starts from — zero counts (and guard words), a fresh status block, "no row lacked its
-// binomial term" — in one launch instead of two memsets and a copy
-__global__ __launch_bounds__(TPB) void k_step_reset(unsigned long long *counts, uint64_t n_words, DevStatus *st, unsigned int *max_n) {
-    for (uint64_t i = (uint64_t)blockIdx.x * TPB + threadIdx.x; i < n_words; i += (uint64_t)gridDim.x * TPB) counts[i] = 0ull;
-    if (blockIdx.x == 0 && threadIdx.x == 0) {
+// svjg_run_begin: the three things a fused pass starts from — zero counts (and guard words), a fresh status block, "no row lacked its
+// binomial term" — zeroed by the threads of a grid, thread `first` of `stride`: by k_step_reset for a pass with none in front of it,
+// by the k_classify_exact of the pass before otherwise
+struct NextPass { unsigned long long *counts; uint64_t n_words; DevStatus *st; unsigned int *max_n; };   // counts = nullptr: nothing to reset
+__device__ __forceinline__ void reset_next_pass(const NextPass &nx, uint64_t first, uint64_t stride) {
+    for (uint64_t i = first; i < nx.n_words; i += stride) nx.counts[i] = 0ull;
+    if (first == 0) {
         DevStatus z{}; z.err = ~0ull;
-        *st = z;
-        max_n[0] = 0u; max_n[1] = 0u;
+        *nx.st = z;
+        nx.max_n[0] = 0u; nx.max_n[1] = 0u;
     }
+}
+__global__ __launch_bounds__(TPB) void k_step_reset(NextPass nx) {
+    reset_next_pass(nx, (uint64_t)blockIdx.x * TPB + threadIdx.x, (uint64_t)gridDim.x * TPB);
 }
 
 // what the exact routine returned for the line at file offset `off`: the exception the reference would die with (the first of
@@ -1495,40 +1503,31 @@ struct SlowEmit {
 // The exact path: one lane per deferred line (svjg::slow_line, the reference's string semantics).  slow_line indexes
 // the text byte by byte, so every wave first packs its 64 lines into LDS (each lane finds its line's terminator and
 // copies the line, 16 bytes per step) and the string logic then pays LDS latency per byte, not HBM latency.  A line
-// that does not fit (longer than SLOW_MAXLINE, or the 64 lines together exceed the buffer) is read in place.
-#ifndef SVJG_SLOW_LANE_LDS
-#define SVJG_SLOW_LANE_LDS (16 * 1024)   /* measured (tools/slowpath_bench.py, 1 M lines): 32 KB 61 ms, 16 KB 30 ms (eight blocks per CU: the register limit), 8 KB 41 ms (lines no longer fit) */
-#endif
+// that does not fit (longer than SLOW_MAXLINE, or the 64 lines together exceed the stage) is read in place.
 constexpr uint32_t SLOW_TPB = 64, SLOW_LDS = 32 * 1024, SLOW_MAXLINE = 16 * 1024;
-constexpr uint32_t SLOW_LANE_LDS = SVJG_SLOW_LANE_LDS;      // staging buffer of the one-lane-per-line kernel (64 lines: 16 KB holds lines of 256 bytes on average)
-// n_def = SLOW_ASK_DEVICE: the launch was enqueued right behind the main kernel without a host round trip (svjg_run_resident); the
-// number of deferred lines is what the main kernel left in the status block, and the kernel works only if it lies in (lo, hi]
-// (two launches share the range: one wave per line up to a limit, one lane per line beyond it).  A list that overflowed is not
-// touched: the host sees the flag and repeats the pass with a larger one.
-constexpr uint64_t SLOW_ASK_DEVICE = ~0ull;
-__device__ inline uint64_t slow_n_def(const ClassifyArgs &a, uint64_t n_def, uint64_t lo, uint64_t hi) {
-    if (n_def != SLOW_ASK_DEVICE) return n_def;
-    if (a.st->overflow & 1u) return 0;
-    const uint64_t n = a.st->n_deferred;
-    return (n > lo && n <= hi) ? n : 0;
-}
+// The stage of one wave's 64 lines: lines of ~250 bytes on average.  Measured (tools/slowpath_bench.py, 1 M lines, one 64-thread block
+// per stage): 32 KB 61 ms, 16 KB 30 ms (eight blocks per CU: the register limit), 8 KB 41 ms (lines no longer fit).  256 bytes short
+// of 16 KB so that two stages and their scratch fit the LDS the wave role needs anyway (EXACT_LDS below).
+constexpr uint32_t EXACT_LANE_STAGE = 16128;
+static_assert(EXACT_LANE_STAGE % 16 == 0, "LDS alignment");
+// The number of deferred lines is what the main kernel left in the status block: k_classify_exact runs behind it with no host round
+// trip (svjg_run_begin).  A list that overflowed is not touched: the host sees the flag and repeats the pass with a larger one.
+__device__ inline uint64_t exact_n_def(const ClassifyArgs &a) { return (a.st->overflow & 1u) ? 0 : a.st->n_deferred; }
 // (r04) The per-node results — strand of the name's first occurrence, id, get_node_len or the exception it raises — are kept per lane in
 // LDS (SLOW_LANE_NODES nodes a line, the lanes of the wave interleaved: no bank conflicts) and every link adds up what is there, as the
 // one-wave-per-line kernel does (svjg_line.h: slow_wave_phase1 / phase2 with one lane): O(k) name resolutions a line instead of O(k^2).
 // A path of more nodes runs through slow_line as before.
 constexpr uint32_t SLOW_LANE_NODES = 12;
-// The kernel's body works on LDS handed to it: WAVES waves of a block run it side by side, each on SLOW_LANE_BYTES(STAGE) bytes of its
-// own (k_classify_slow: one wave, k_classify_exact: two).  Every wave of a block makes the same number of rounds (the barriers).
+// The role works on LDS handed to it: the two waves of a block run it side by side, each on EXACT_LANE_STAGE + SLOW_LANE_SCRATCH bytes
+// of its own.  Both waves make the same number of rounds (the barriers).
 constexpr uint32_t SLOW_LANE_SCRATCH = SLOW_LANE_NODES * SLOW_TPB * 14;   // c_len 8, c_id 4, c_rc 1, c_strand 1 bytes a node
-template <uint32_t WAVES, uint32_t STAGE>
 __device__ __forceinline__ void slow_lane_role(const ClassifyArgs &a, const uint64_t n_def, uint8_t *pool) {
-    static_assert(STAGE % 16 == 0, "LDS alignment");
-    const uint32_t lane = threadIdx.x & 63u, wave = WAVES > 1 ? threadIdx.x >> 6 : 0u;
-    uint8_t *stage = pool + wave * (STAGE + SLOW_LANE_SCRATCH);
-    int64_t *c_len = (int64_t *)(stage + STAGE);
+    constexpr uint32_t WAVES = 2;
+    const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
+    uint8_t *stage = pool + wave * (EXACT_LANE_STAGE + SLOW_LANE_SCRATCH);
+    int64_t *c_len = (int64_t *)(stage + EXACT_LANE_STAGE);
     uint32_t *c_id = (uint32_t *)(c_len + SLOW_LANE_NODES * SLOW_TPB);
     uint8_t *c_rc = (uint8_t *)(c_id + SLOW_LANE_NODES * SLOW_TPB), *c_strand = c_rc + SLOW_LANE_NODES * SLOW_TPB;
-    constexpr uint32_t SLOW_LANE_LDS = STAGE;
 #ifdef SVJG_TIMING
     // measurement only (SVJG_DIAG & 16): the longest any block of 64 lines took per step (a.dbg[24 ..]: terminators + staging, per-line part, nodes, links)
     unsigned long long lstamp = __builtin_readcyclecounter();
@@ -1554,10 +1553,10 @@ __device__ __forceinline__ void slow_lane_role(const ClassifyArgs &a, const uint
         }
         const uint64_t a0 = s & ~15ull;
         const uint64_t span = have ? ((e - a0 + 15) & ~15ull) : 0;        // bytes of the aligned blocks that hold the line
-        const uint32_t want = span <= (SLOW_MAXLINE < SLOW_LANE_LDS ? SLOW_MAXLINE : SLOW_LANE_LDS) ? (uint32_t)span : 0u;
+        const uint32_t want = span <= (SLOW_MAXLINE < EXACT_LANE_STAGE ? SLOW_MAXLINE : EXACT_LANE_STAGE) ? (uint32_t)span : 0u;
         uint32_t tot;
         const uint32_t off = wave_excl_scan(want, tot);
-        const bool staged = have && want && off + want <= SLOW_LANE_LDS;
+        const bool staged = have && want && off + want <= EXACT_LANE_STAGE;
         if (staged)
             for (uint32_t o = 0; o < want; o += 16) *(uint4 *)(stage + off + o) = *(const uint4 *)(a.gaf + a0 + o);
         __syncthreads();
@@ -1588,10 +1587,6 @@ __device__ __forceinline__ void slow_lane_role(const ClassifyArgs &a, const uint
         }
         __syncthreads();
     }
-}
-__global__ __launch_bounds__(SLOW_TPB) void k_classify_slow(ClassifyArgs a, uint64_t n_def_arg, uint64_t lo, uint64_t hi) {
-    __shared__ __attribute__((aligned(16))) uint8_t pool[SLOW_LANE_LDS + SLOW_LANE_SCRATCH];
-    slow_lane_role<1, SLOW_LANE_LDS>(a, slow_n_def(a, n_def_arg, lo, hi), pool);
 }
 
 // The exact path for a few lines: one WAVE per deferred line.  Every lane runs the per-line part (same control flow in
@@ -1701,11 +1696,9 @@ __device__ inline int slow_prologue_wave(slow_lds_text t, uint64_t s, uint64_t e
     o.Tlen = v6; o.Ts = v7; o.Te = v8;
     return 0;
 }
-// The kernel's body, run by ONE wave on SLOW_WAVE_BYTES of LDS handed to it.  SOLO: the wave is not the only one of its block
-// (k_classify_exact), so the places where it waits for its own LDS writes must not be block barriers.
+// The role's body, run by ONE wave on SLOW_WAVE_BYTES of LDS handed to it.  The wave is not the only one of its block (the second
+// one of k_classify_exact has left), so the places where it waits for its own LDS writes must not be block barriers: wave_sync().
 constexpr uint32_t SLOW_WAVE_BYTES = SLOW_LDS + SLOW_NODES * 28;       // stage, then n_len 8, n_key 8, n_id 4, n_piece 4, n_colon 2, n_rc 1, n_strand 1 bytes a node
-template <bool SOLO> __device__ __forceinline__ void slow_role_sync() { if (SOLO) wave_sync(); else __syncthreads(); }
-template <bool SOLO>
 __device__ __forceinline__ void slow_wave_role(const ClassifyArgs &a, const uint64_t n_def, uint8_t *pool) {
     uint8_t *stage = pool;
     int64_t *n_len = (int64_t *)(pool + SLOW_LDS);
@@ -1744,7 +1737,7 @@ __device__ __forceinline__ void slow_wave_role(const ClassifyArgs &a, const uint
         const uint64_t span = (e - a0 + 15) & ~15ull;                     // bytes of the aligned blocks that hold the line
         const bool staged = span <= SLOW_LDS;
         if (staged) for (uint64_t o = (uint64_t)lane * 16; o < span; o += 1024) *(uint4 *)(stage + o) = *(const uint4 *)(a.gaf + a0 + o);
-        slow_role_sync<SOLO>();
+        wave_sync();
         wtick(0);
         SlowEmit em{&a, a.base_offset + s};
         uint64_t order = 0;
@@ -1778,7 +1771,7 @@ __device__ __forceinline__ void slow_wave_role(const ClassifyArgs &a, const uint
                     run += (uint32_t)__popcll(m);
                 }
                 ln.k = run;
-                slow_role_sync<SOLO>();
+                wave_sync();
             }
             if (!rc && ln.k >= 2) {
                 if (ln.k <= SLOW_NODES) {
@@ -1792,14 +1785,14 @@ __device__ __forceinline__ void slow_wave_role(const ClassifyArgs &a, const uint
                             while (e0 > s0 && ((uint8_t)t[e0 - 1] == sep1 || (uint8_t)t[e0 - 1] == sep2)) --e0;
                             n_len[i] = (int64_t)(e0 - s0);                   // (kept aside: the starts are still being read by the neighbours)
                         }
-                        slow_role_sync<SOLO>();
+                        wave_sync();
                         for (uint32_t i = lane; i < ln.k; i += 64) { const uint16_t cw = piece_colons(t, n_piece[i], (uint64_t)n_len[i]); n_colon[i] = cw; n_key[i] = piece_key(t, n_piece[i], cw); n_piece[i] |= (uint32_t)n_len[i] << 16; }
-                        slow_role_sync<SOLO>();
+                        wave_sync();
                     }
                     wtick(2);
                     // every node's id and length first, then the strands: by id where the line allows it (svjg_line.h: slow_wave_strands)
                     slow_wave_resolve(a.g, t, ln, ns, lane, 64u, (const SVJG_TAB_AS uint32_t *)n_piece);
-                    slow_role_sync<SOLO>();
+                    wave_sync();
                     bool clean = ln.oriented, rises = true;
                     for (uint32_t i = lane; i < ln.k; i += 64) {
                         const uint32_t x = n_id[i];
@@ -1811,7 +1804,7 @@ __device__ __forceinline__ void slow_wave_role(const ClassifyArgs &a, const uint
                     // (the call fills `order`: result and order are separate statements, not two arguments of one call)
                     const int r1 = slow_wave_strands(t, ln, ns, lane, 64u, &order, (const SVJG_TAB_AS uint32_t *)n_piece, (const SVJG_TAB_AS uint16_t *)n_colon, (const SVJG_TAB_AS uint64_t *)n_key, clean, rises);
                     rc = wave_min(r1, order);
-                    slow_role_sync<SOLO>();
+                    wave_sync();
                     wtick(3);
                     if (!rc) {
                         // has every node a length?  Then the links need no walks over the node list: a running sum in place, and a table of
@@ -1824,7 +1817,7 @@ __device__ __forceinline__ void slow_wave_role(const ClassifyArgs &a, const uint
                         }
                         if (__ballot(!good) == 0ull) {
                             oneway = __ballot(!oneway) == 0ull;
-                            slow_role_sync<SOLO>();
+                            wave_sync();
                             for (uint32_t j = lane; j < ln.k; j += 64) {
                                 uint32_t f = j;
                                 if (!oneway) { const uint32_t x = n_id[j]; if (x != NONE32) { f = 0; while (n_id[f] != x) ++f; } }
@@ -1839,7 +1832,7 @@ __device__ __forceinline__ void slow_wave_role(const ClassifyArgs &a, const uint
                             for (int d = 1; d < 64; d <<= 1) { const unsigned long long y = __shfl_up(inc, d); if ((int)lane >= d) inc += y; }
                             unsigned long long run = inc - sum;
                             for (uint32_t j = j0; j < j1; ++j) { run += (unsigned long long)n_len[j]; n_len[j] = (int64_t)run; }
-                            slow_role_sync<SOLO>();
+                            wave_sync();
                             const int r2 = slow_wave_links_summed(a.g, ln, (const SVJG_TAB_AS uint32_t *)n_id, (const SVJG_TAB_AS int64_t *)n_len, (const SVJG_TAB_AS uint8_t *)n_strand,
                                                                   (const SVJG_TAB_AS uint32_t *)n_piece, em, lane, &order);
                             rc = wave_min(r2, order);
@@ -1850,46 +1843,32 @@ __device__ __forceinline__ void slow_wave_role(const ClassifyArgs &a, const uint
             }
         } else { const int r4 = slow_line(a.g, a.gaf, s, e, em, lane, 64u, &order); rc = wave_min(r4, order); }
         if (lane == 0 && rc) report_line(a, a.base_offset + s, rc);
-        slow_role_sync<SOLO>();
+        wave_sync();
     }
 }
-__global__ __launch_bounds__(SLOW_TPB) void k_classify_slow_wave(ClassifyArgs a, uint64_t n_def_arg, uint64_t lo, uint64_t hi) {
-    __shared__ __attribute__((aligned(16))) uint8_t pool[SLOW_WAVE_BYTES];
-    slow_wave_role<false>(a, slow_n_def(a, n_def_arg, lo, hi), pool);
-}
 
-// svjg_run_begin: the whole exact path behind k_classify_main in ONE launch, and the next pass's reset with it.  The number of deferred
-// lines is what the main kernel left in the status block (SLOW_ASK_DEVICE above); every block reads it and picks its role: none (no
-// line deferred, or the list overflowed: the host repeats the pass), one wave per line up to wave_limit lines (the block's second
-// wave leaves at once; the first one never meets a block barrier: slow_wave_role<true>), one lane per line beyond it, both waves
-// working.  A block is two waves so that the LDS the wave role needs (SLOW_WAVE_BYTES) is not lost on the lane role: two lane
-// stages fit in it, three blocks a CU are six lane waves where k_classify_slow alone has five (the stage is 256 bytes shorter than
-// there for that: 42 granules a block).  Before anything else the blocks zero what the pass AFTER this one starts from — its count
-// vector, status block and max_n (k_step_reset; `nx` names a slot no pass in flight uses) —, so that no launch stands between this
-// kernel and the next k_classify_main.
+// The whole exact path behind k_classify_main in ONE launch, and the next fused pass's reset with it.  The number of deferred lines
+// is what the main kernel left in the status block (exact_n_def above); every block reads it and picks its role: none (no line
+// deferred, or the list overflowed: the host repeats the pass), one wave per line up to wave_limit lines (the block's second wave
+// leaves at once; the first one never meets a block barrier), one lane per line beyond it, both waves working.  A block is two
+// waves so that the LDS the wave role needs (SLOW_WAVE_BYTES) is not lost on the lane role: two lane stages fit in it, three blocks
+// a CU are six lane waves (42 granules a block).  Before anything else the blocks zero what the pass AFTER this one starts from —
+// its count vector, status block and max_n (reset_next_pass; `nx` names a slot no pass in flight uses, or nothing) —, so that no
+// launch stands between this kernel and the next k_classify_main.
 constexpr uint32_t EXACT_TPB = 2 * SLOW_TPB;
-constexpr uint32_t EXACT_LANE_STAGE = 16128;
 constexpr uint32_t EXACT_LANE_BYTES = 2 * (EXACT_LANE_STAGE + SLOW_LANE_SCRATCH);
 constexpr uint32_t EXACT_LDS = SLOW_WAVE_BYTES > EXACT_LANE_BYTES ? SLOW_WAVE_BYTES : EXACT_LANE_BYTES;
 constexpr uint32_t EXACT_BLOCKS_PER_CU = 3;
 static_assert(EXACT_LDS <= (128 / EXACT_BLOCKS_PER_CU) * LDS_GRANULE, "three blocks of k_classify_exact per CU");
-struct NextPass { unsigned long long *counts; uint64_t n_words; DevStatus *st; unsigned int *max_n; };   // counts = nullptr: nothing to reset
 __global__ __launch_bounds__(EXACT_TPB) void k_classify_exact(ClassifyArgs a, uint64_t wave_limit, NextPass nx) {
     __shared__ __attribute__((aligned(16))) uint8_t pool[EXACT_LDS];
-    if (nx.counts) {
-        for (uint64_t i = (uint64_t)blockIdx.x * EXACT_TPB + threadIdx.x; i < nx.n_words; i += (uint64_t)gridDim.x * EXACT_TPB) nx.counts[i] = 0ull;
-        if (blockIdx.x == 0 && threadIdx.x == 0) {
-            DevStatus z{}; z.err = ~0ull;
-            *nx.st = z;
-            nx.max_n[0] = 0u; nx.max_n[1] = 0u;
-        }
-    }
-    const uint64_t n_def = slow_n_def(a, SLOW_ASK_DEVICE, 0ull, ~0ull - 1);      // (the same in every block: neither role writes what it reads)
+    if (nx.counts) reset_next_pass(nx, (uint64_t)blockIdx.x * EXACT_TPB + threadIdx.x, (uint64_t)gridDim.x * EXACT_TPB);
+    const uint64_t n_def = exact_n_def(a);                              // (the same in every block: neither role writes what it reads)
     if (!n_def) return;
     if (n_def <= wave_limit) {
         if (threadIdx.x >= SLOW_TPB) return;
-        slow_wave_role<true>(a, n_def, pool);
-    } else slow_lane_role<2, EXACT_LANE_STAGE>(a, n_def, pool);
+        slow_wave_role(a, n_def, pool);
+    } else slow_lane_role(a, n_def, pool);
     if ((threadIdx.x & 63u) == 0) atomicMax(&a.st->t_exact, (unsigned long long)wall_clock64());
 }
 

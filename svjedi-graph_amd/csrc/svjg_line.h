@@ -614,7 +614,7 @@ SVJG_FN int slow_prologue(P t, uint64_t s, uint64_t e, SlowLine &o) {
 }
 
 // ---- the exact routine shared out over the lanes of a wave, node lengths computed ONCE per line ------------------------
-// Per-node scratch (LDS in k_classify_slow_wave, plain arrays in tests/hostsim): what the reference recomputes for every
+// Per-node scratch (LDS in the wave role of k_classify_exact, plain arrays in tests/hostsim): what the reference recomputes for every
 // link is kept per node.  phase 1: lane l takes the nodes l (mod nlanes): strand of the name (str.split quirk), node id,
 // get_node_len or the exception it raises.  phase 2 (after a barrier): lane l takes the links l (mod nlanes).
 // stride: node j's entries sit at index j * stride (1: one line per array; 64: the lanes of a wave interleaved, one line per lane)
@@ -648,7 +648,7 @@ SVJG_HD int slow_wave_phase1(const GraphView &g, P t, const SlowLine &ln, NodeSc
         return 0;
     }
     if (nlanes == 1u && ln.oriented) {
-        // one lane, the whole line (k_classify_slow; r05): every node is resolved in ONE walk, which also notes the node's own orientation
+        // one lane, the whole line (the lane role of k_classify_exact; r05): every node is resolved in ONE walk, which also notes the node's own orientation
         // mark; if the line is clean (every name a graph node that stands inside no other node's name: slow_wave_strands has the
         // argument) a node's strand is the mark of the first node with the same id — filled in place, front to back — and the search
         // through the path's text is not needed; else a second walk searches as before.

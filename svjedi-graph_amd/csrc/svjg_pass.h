@@ -1,9 +1,9 @@
 // What a finished fused pass (svjg_run_begin / svjg_run_end) means for the ranks of a job — host logic shared by libsvjg_hip.so
 // and the CPU harness (tests/hostsim), so that the decision the ranks must take TOGETHER is tested where there is no GPU.
 //
-// A pass enqueues, with no host round trip: reset, k_classify_main, both exact-path kernels (one wave per line for up to
-// `wave_limit` deferred lines, one lane per line beyond it; each reads the number on the device and works only in its range),
-// the guard kernel, the all-reduce of [ counts | guard words ], the genotypes.  The only thing the device cannot repair by itself
+// A pass enqueues, with no host round trip: k_classify_main, k_classify_exact (the exact path: it reads the number of deferred
+// lines on the device and takes its wave role, one wave per line, up to `wave_limit` lines, its lane role, one lane per line,
+// beyond it; the same launch resets what the next pass starts from), the guard kernel, the all-reduce of [ counts | guard words ], the genotypes.  The only thing the device cannot repair by itself
 // is a list that overflowed (deferred lines, lines for the host): such a pass has to be repeated with larger lists.  Under a
 // communicator that decision is COLLECTIVE: every rank puts "I must repeat" into guard word 2, the words travel through the
 // pass's own all-reduce, and every rank repeats (classify step by step + ONE more all-reduce) iff the sum is not zero — so all

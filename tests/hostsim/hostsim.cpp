@@ -47,13 +47,13 @@ static int classify_view(const GraphView &v, const svjg_graph *g, const char *ga
         while (e < n && t[e] != '\n' && t[e] != '\r') ++e;
         CountEmit em{counts};
         int rc = 0;
-        if (g->flags & 8u) {                                               // harness only: the two-phase wave routine of k_classify_slow_wave, 64 lanes
+        if (g->flags & 8u) {                                               // harness only: the two-phase routine of the wave role of k_classify_exact, 64 lanes
             SlowLine ln;
             rc = slow_prologue(t, pos, e, ln);
             if (!rc && ln.k >= 2) {
                 std::vector<uint32_t> id(ln.k); std::vector<int64_t> len(ln.k); std::vector<uint8_t> nrc(ln.k), strand(ln.k);
                 NodeScratch ns{id.data(), len.data(), nrc.data(), strand.data(), ln.k};
-                // the table of the path's pieces, as k_classify_slow_wave builds it (there 64 bytes per step); offsets relative to the line
+                // the table of the path's pieces, as the wave role of k_classify_exact builds it (there 64 bytes per step); offsets relative to the line
                 // start like the kernel's staged copy (below 65536 for the lines the harness is given; longer ones: byte-by-byte search)
                 std::vector<uint32_t> pieces; std::vector<uint16_t> colons; std::vector<uint64_t> keys;
                 const uint8_t *tl = t + pos;
@@ -78,7 +78,7 @@ static int classify_view(const GraphView &v, const svjg_graph *g, const char *ga
                 }
                 uint64_t best = ~0ull;
                 if ((g->flags & 128u) && !pieces.empty()) {
-                    // flag 128, harness only: phase 1 as k_classify_slow_wave runs it since r05 — every node resolved first, then the strands,
+                    // flag 128, harness only: phase 1 as the wave role of k_classify_exact runs it since r05 — every node resolved first, then the strands,
                     // by id where the line is clean (svjg_line.h: slow_wave_strands)
                     for (uint32_t lane = 0; lane < 64; ++lane) slow_wave_resolve(v, tl, ll, ns, lane, 64u, pieces.data());
                     bool clean = ll.oriented, rises = true;
@@ -105,7 +105,7 @@ static int classify_view(const GraphView &v, const svjg_graph *g, const char *ga
                     }
                 if (best != ~0ull) rc = (int)(best & 7);
             }
-        } else if (g->flags & 32u) {                                       // harness only: one lane with its per-node results kept (k_classify_slow since r04), the lanes' entries interleaved
+        } else if (g->flags & 32u) {                                       // harness only: one lane with its per-node results kept (the lane role of k_classify_exact, since r04), the lanes' entries interleaved
             SlowLine ln;
             rc = slow_prologue(t, pos, e, ln);
             if (!rc && ln.k >= 2) {
@@ -116,7 +116,7 @@ static int classify_view(const GraphView &v, const svjg_graph *g, const char *ga
                 rc = slow_wave_phase1(v, t, ln, ns, 0u, 1u, &order);
                 if (!rc) rc = slow_wave_phase2(v, ln, ns, em, 0u, 1u, &order);
             }
-        } else if (g->flags & 4u) {                                        // harness only: 64 cooperating lanes, as k_classify_slow_wave runs a line with too many nodes
+        } else if (g->flags & 4u) {                                        // harness only: 64 cooperating lanes, as the wave role of k_classify_exact runs a line with too many nodes
             uint64_t best = ~0ull;
             for (uint32_t lane = 0; lane < 64; ++lane) {
                 uint64_t order = 0;

@@ -1,7 +1,8 @@
 """The tail of the fused pass (svjg_run_begin / svjg_run_end): ONE launch between two k_classify_main — k_classify_exact, whose blocks
 pick their role (none / one wave per line / one lane per line) from the number of deferred lines they read on the device and zero
 the NEXT pass's count vector and status block — three slots rotating under two passes in flight, and k_classify_main's time taken
-from the device's clock instead of an event pair.  Everything against classify + genotype done step by step on the same context.
+from the device's clock instead of an event pair.  Everything against classify + genotype done step by step on the same context —
+which launches the same k_classify_exact, so the counts of the texts that run its two roles are also pinned to the Python oracle.
 Needs an MI355X: run with -m gpu."""
 import json
 import os
@@ -41,6 +42,16 @@ def _step_by_step(c, gaf, rows):
     return {"counts": c.counts(), "stats": c.stats(), "causes": c.defer_causes(), "gt": gt, "pl": pl, "raw": raw, "done": done}
 
 
+def _oracle_counts(pre, g, gaf):
+    """the count vector of the text by oracle.oracle_py (the checker that shares no code with the library), in the graph's slot order"""
+    from oracle import oracle_py
+    d = oracle_py.classify([ln + "\n" for ln in bytes(gaf).decode().split("\n")[:-1]], oracle_py.load_edges(pre + "_svs_edges.json"), oracle_py.load_alt_node_len(pre + ".gfa"))
+    out = np.zeros((g.n_slots, 2), dtype=np.uint32)
+    for sv, n in oracle_py.counts_of(d).items():
+        out[g.slot_of[sv]] = n
+    return out
+
+
 def _same_results(got, want):
     gt, pl, raw, flags = got
     assert np.array_equal(gt, want["gt"]) and np.array_equal(pl, want["pl"]) and np.array_equal(raw, want["raw"])
@@ -61,13 +72,14 @@ def case(tmp_path_factory):
     # (an id:f: value in exponent form: float() takes it, the main kernel leaves the line to the exact path)
     few = np.frombuffer(bytes(gaf).replace(b"\tdv:f:", b"\tid:f:9e-1\tdv:f:", 7), dtype=np.uint8)      # a handful: the wave role
     many = np.frombuffer(bytes(gaf).replace(b"\tdv:f:", b"\tid:f:5e-1\tdv:f:"), dtype=np.uint8)        # 40 000 > 64 x n_cu: the lane role
-    return g, rows, {"none": gaf, "few": few, "many": many}
+    texts = {"none": gaf, "few": few, "many": many}
+    return g, rows, texts, {k: _oracle_counts(pre, g, texts[k]) for k in ("few", "many")}
 
 
 @pytest.fixture()
 def ctx(case):
     from svjg import capi
-    g, rows, _ = case
+    g, rows, _, _ = case
     c = capi.Context(0)
     c.load_graph(g)
     c.set_rows(rows.sv_type, rows.slot, rows.ok)
@@ -79,10 +91,12 @@ def ctx(case):
 def test_roles_of_the_exact_launch(ctx, case, which, least, most):
     """a pass that defers a handful of lines (one wave per line) and one that defers more than wave_limit = 64 x n_cu lines (one lane
     per line): counts, n_deferred, defer_causes and genotypes equal the step-by-step calls; the pass is not repeated for them (the
-    list did not overflow), twice in a row and with two in flight"""
-    _, rows, texts = case
+    list did not overflow), twice in a row and with two in flight.  Both sides run k_classify_exact, so the counts must also be
+    the Python oracle's over the same text and graph"""
+    _, rows, texts, oracle = case
     want = _step_by_step(ctx, texts[which], rows)
     assert least <= want["stats"]["n_deferred"] <= most and want["counts"].sum() > 0
+    assert np.array_equal(want["counts"], oracle[which])
     for _ in range(2):
         got = [np.array(x) for x in ctx.run_resident(MS, ERR)]
         _same_results(got, want)
@@ -100,7 +114,7 @@ def test_five_passes_alternating_texts(ctx, case):
     """driven as bench.py drives them (begin, begin, end, begin, end, ...), the text changing between a deferring one and one that
     defers nothing whenever no pass is in flight: every pass equals its step-by-step twin — a vector zeroed too late or too early, or
     a status block shared by two passes, shows here"""
-    _, rows, texts = case
+    _, rows, texts, _ = case
     want = {k: _step_by_step(ctx, texts[k], rows) for k in ("none", "few", "many")}
     assert want["none"]["stats"]["n_deferred"] < want["few"]["stats"]["n_deferred"] < want["many"]["stats"]["n_deferred"]
     for order in (("few", "none", "many", "none", "few"), ("none", "many", "none", "few", "none")):
@@ -126,7 +140,7 @@ def test_counts_after_the_last_pass(ctx, case):
     """counts() after the last run_end is the last pass's vector; reset_counts / classify_resident behind fused passes work on a
     vector of their own and the next fused pass starts from zero again; the uploads still refuse while a pass is in flight"""
     from svjg import capi
-    _, rows, texts = case
+    _, rows, texts, _ = case
     want = _step_by_step(ctx, texts["few"], rows)
     ctx.run_begin(MS, ERR); ctx.run_begin(MS, ERR)
     with pytest.raises(capi.SvjgError):

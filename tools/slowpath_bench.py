@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""measurement only: cost of the exact path (k_classify_slow) as a function of the number of deferred lines.
+"""measurement only: cost of the exact path (the wave role / lane role of k_classify_exact, launched step by step) as a function of the number of deferred lines.
 A C2-like batch (1 M alignments, 10 k DEL SVs) with N extra alignments whose paths exceed the main kernel's node cap."""
 import os, sys, tempfile, time
 import numpy as np
