@@ -92,7 +92,7 @@ struct svjg_ctx {
     svjg_node *d_nodes = nullptr;  svjg_edge *d_edges = nullptr;  uint32_t *d_hits = nullptr;
     uint8_t *d_cnames = nullptr;   uint32_t *d_coff = nullptr, *d_clo = nullptr, *d_chash = nullptr, *d_names = nullptr, *d_links = nullptr, *d_nok = nullptr;  uint16_t *d_disp = nullptr;  uint32_t *d_ihits = nullptr, *d_pfx = nullptr;
     GraphView gv{};
-    uint32_t names_len = 0, gflags = 0, n_slots = 0;
+    uint32_t gflags = 0, n_slots = 0;
     unsigned long long *d_counts = nullptr, *d_snap = nullptr;
     // text
     uint8_t *d_gaf = nullptr;  uint64_t gaf_cap = 0, gaf_bytes = 0;  bool have_gaf = false;
@@ -112,7 +112,6 @@ struct svjg_ctx {
     uint64_t total_deferred = 0;
     // genotype scratch
     dd *d_logfact = nullptr;  uint32_t logfact_n = 0;  dd *d_bsum = nullptr;
-    unsigned int *d_maxn = nullptr;
     void *d_rows = nullptr;  uint64_t rows_cap = 0;
     void *h_rows = nullptr;  uint64_t h_rows_cap = 0;   // pinned twin of d_rows
     uint64_t geno_rows = 0;                              // rows of the last svjg_genotype / svjg_genotype_view (svjg_genotype_boundary)
@@ -176,7 +175,7 @@ extern "C" int svjg_init(int device, svjg_ctx **out) {
     if (hipGetDeviceProperties(&prop, device) == hipSuccess) c->n_cu = prop.multiProcessorCount;
     if (hipDeviceGetAttribute(&c->wall_khz, hipDeviceAttributeWallClockRate, device) != hipSuccess || c->wall_khz < 1) c->wall_khz = 0;
     for (auto &ev : c->ev) hipEventCreate(&ev);
-    if (hipMalloc(&c->d_dbg, 32 * 8) != hipSuccess || hipMalloc(&c->d_st, sizeof(DevStatus)) != hipSuccess || hipMalloc(&c->d_maxn, sizeof(unsigned int)) != hipSuccess ||
+    if (hipMalloc(&c->d_dbg, 32 * 8) != hipSuccess || hipMalloc(&c->d_st, sizeof(DevStatus)) != hipSuccess ||
         hipHostMalloc((void **)&c->h_stp, 2 * sizeof(DevStatus), hipHostMallocDefault) != hipSuccess) {
         g_init_error = "hipMalloc failed";
         delete c;
@@ -208,7 +207,7 @@ extern "C" void svjg_destroy(svjg_ctx *c) {
     free_graph(c);
     hipFree(c->d_long);
     hipFree(c->d_gaf); hipFree(c->d_deferred); hipFree(c->d_recs); hipFree(c->d_host); hipFree(c->d_st); hipFree(c->d_logfact);
-    hipFree(c->d_bsum); hipFree(c->d_maxn); hipFree(c->d_rows); hipFree(c->d_run_in);
+    hipFree(c->d_bsum); hipFree(c->d_rows); hipFree(c->d_run_in);
     for (auto &r : c->run) {
         hipFree(r.d); hipFree(r.counts);
         if (r.h) hipHostFree(r.h);
@@ -243,6 +242,19 @@ static int upload(svjg_ctx *c, T **dst, const T *src, uint64_t n, uint64_t extra
 constexpr uint64_t SMALL_CHUNK = SVJG_SMALL_CHUNK;            // bytes (multiple of 16)
 constexpr double FIRST_CHUNK_SHARE = SVJG_FIRST_SHARE;       // of an even share of the text
 
+// the count vector and its guard words (svjg_pass.h), in bytes
+static uint64_t counts_bytes(const svjg_ctx *c) { return ((uint64_t)c->n_slots + GUARD_WORDS) * 8; }
+// d_counts and the snapshot an overflowed classify attempt is rolled back to
+static int alloc_count_vectors(svjg_ctx *c, uint32_t n_slots) {
+    c->n_slots = n_slots;
+    HIPCHK(c, hipMalloc((void **)&c->d_counts, counts_bytes(c)));
+    HIPCHK(c, hipMalloc((void **)&c->d_snap, counts_bytes(c)));
+    c->have_counts = true;
+    return 0;
+}
+// blocks of TPB over n items, 1 to 1024 (the kernels stride)
+static uint32_t capped_grid(uint64_t n) { const uint64_t g = (n + TPB - 1) / TPB; return g > 1024 ? 1024u : g < 1 ? 1u : (uint32_t)g; }
+
 static int reset_status(svjg_ctx *c, bool all) {
     if (all) {                                                // from the constant copy: the host's own status may be written again at once
         c->hs() = c->h_stp[1]; c->total_deferred = 0;
@@ -266,8 +278,7 @@ extern "C" int svjg_load_graph(svjg_ctx *c, const svjg_graph *g) {
     if ((rc = upload(c, &c->d_nodes, g->nodes, g->n_nodes + 1))) return rc;
     if ((rc = upload(c, &c->d_edges, g->edges, g->n_edges))) return rc;
     if ((rc = upload(c, &c->d_hits, g->hits, g->n_hits))) return rc;
-    c->names_len = g->chrom_off[g->n_chrom];
-    if ((rc = upload(c, &c->d_cnames, (const uint8_t *)g->chrom_names, c->names_len, 8))) return rc;
+    if ((rc = upload(c, &c->d_cnames, (const uint8_t *)g->chrom_names, g->chrom_off[g->n_chrom], 8))) return rc;
     if ((rc = upload(c, &c->d_coff, g->chrom_off, g->n_chrom + 1))) return rc;
     if ((rc = upload(c, &c->d_clo, g->chrom_node_lo, g->n_chrom + 1))) return rc;
     std::vector<uint32_t> hash = build_chrom_hash(*g);
@@ -292,10 +303,8 @@ extern "C" int svjg_load_graph(svjg_ctx *c, const svjg_graph *g) {
     c->gflags = g->flags;
     if (g->flags & SVJG_GRAPH_DOVER_LIST) c->gflags |= SVJG_GRAPH_ALL_SLOW;   // (the exact routine knows where the reference's TypeError sits)
     if (kt.links_left_out) c->gflags |= SVJG_GRAPH_ALL_SLOW;   // a link the main kernel could not find would be a silent miss
-    c->n_slots = g->n_slots;
-    HIPCHK(c, hipMalloc((void **)&c->d_counts, ((uint64_t)g->n_slots + GUARD_WORDS) * 8));
-    HIPCHK(c, hipMalloc((void **)&c->d_snap, ((uint64_t)g->n_slots + GUARD_WORDS) * 8));
-    c->have_graph = true; c->have_counts = true;
+    if ((rc = alloc_count_vectors(c, g->n_slots))) return rc;
+    c->have_graph = true;
     undo.armed = false;
     return svjg_reset_counts(c);
 }
@@ -304,18 +313,15 @@ extern "C" int svjg_alloc_counts(svjg_ctx *c, uint32_t n_slots) {
     if (!c) return SVJG_E_ARG;
     HIPCHK(c, hipSetDevice(c->device));
     free_graph(c);
-    c->n_slots = n_slots;
-    HIPCHK(c, hipMalloc((void **)&c->d_counts, ((uint64_t)n_slots + GUARD_WORDS) * 8));
-    HIPCHK(c, hipMalloc((void **)&c->d_snap, ((uint64_t)n_slots + GUARD_WORDS) * 8));
-    c->have_counts = true;
-    return svjg_reset_counts(c);
+    const int rc = alloc_count_vectors(c, n_slots);
+    return rc ? rc : svjg_reset_counts(c);
 }
 
 extern "C" int svjg_reset_counts(svjg_ctx *c) {
     if (!c || !c->have_counts) return SVJG_E_ARG;
     c->counts_in_slot = -1;
     HIPCHK(c, hipSetDevice(c->device));
-    HIPCHK(c, hipMemsetAsync(c->d_counts, 0, ((uint64_t)c->n_slots + GUARD_WORDS) * 8, c->stream));
+    HIPCHK(c, hipMemsetAsync(c->d_counts, 0, counts_bytes(c), c->stream));
     return reset_status(c, true);                             // (nothing to wait for: the next call on the stream comes behind both)
 }
 
@@ -443,6 +449,16 @@ static int ensure(svjg_ctx *c, void **p, uint64_t *cap, uint64_t want, size_t el
     return 0;
 }
 
+// the same for a pinned host block (contents not kept)
+static int ensure_pinned(svjg_ctx *c, void **p, uint64_t *cap, uint64_t want, unsigned int flags) {
+    if (want <= *cap) return 0;
+    if (*p) hipHostFree(*p);
+    *p = nullptr; *cap = 0;
+    HIPCHK(c, hipHostMalloc(p, want, flags));
+    *cap = want;
+    return 0;
+}
+
 // arguments and geometry of one k_classify_main launch over the lines of the resident text that lie in [begin, end)
 // The passes of svjg_run_begin keep their counts in vectors of their own; the rest of the API works on d_counts: the newest pass's
 // vector is copied there when someone asks for it (svjg_get_counts, svjg_genotype, svjg_classify adding to it, ...).
@@ -452,7 +468,7 @@ static int fetch_slot_counts(svjg_ctx *c) {
     c->counts_in_slot = -1;
     HIPCHK(c, hipSetDevice(c->device));
     if (c->run[k].copied) HIPCHK(c, hipStreamWaitEvent(c->stream, c->run[k].copied, 0));   // (the pass's all-reduce runs on the second stream)
-    HIPCHK(c, hipMemcpyAsync(c->d_counts, c->run[k].counts, ((uint64_t)c->n_slots + GUARD_WORDS) * 8, hipMemcpyDeviceToDevice, c->stream));
+    HIPCHK(c, hipMemcpyAsync(c->d_counts, c->run[k].counts, counts_bytes(c), hipMemcpyDeviceToDevice, c->stream));
     return 0;
 }
 
@@ -527,7 +543,7 @@ static int classify_range(svjg_ctx *c, uint64_t begin, uint64_t end, uint64_t ba
         if ((rc = ensure(c, (void **)&c->d_host, &c->host_cap, host_want, sizeof(uint64_t), true))) return rc;
         if (want_hits && (rc = ensure(c, (void **)&c->d_recs, &c->rec_cap, rec_want, sizeof(svjg_hitrec), true))) return rc;
         // snapshot so that an overflowed attempt can be rolled back
-        HIPCHK(c, hipMemcpyAsync(c->d_snap, c->d_counts, ((uint64_t)c->n_slots + GUARD_WORDS) * 8, hipMemcpyDeviceToDevice, c->stream));
+        HIPCHK(c, hipMemcpyAsync(c->d_snap, c->d_counts, counts_bytes(c), hipMemcpyDeviceToDevice, c->stream));
         DevStatus before = c->hs();
         if ((rc = reset_status(c, false))) return rc;
         ClassifyArgs a{};
@@ -585,7 +601,7 @@ static int classify_range(svjg_ctx *c, uint64_t begin, uint64_t end, uint64_t ba
         if (c->hs().overflow & 1u) def_want = n / 24 + 64;
         if (c->hs().overflow & 2u) rec_want = before.n_recs + (c->hs().n_recs - before.n_recs) * 2 + n / 24 + 64;
         if (c->hs().overflow & 4u) host_want = before.n_host + n / 24 + 64;
-        HIPCHK(c, hipMemcpyAsync(c->d_counts, c->d_snap, ((uint64_t)c->n_slots + GUARD_WORDS) * 8, hipMemcpyDeviceToDevice, c->stream));
+        HIPCHK(c, hipMemcpyAsync(c->d_counts, c->d_snap, counts_bytes(c), hipMemcpyDeviceToDevice, c->stream));
         uint64_t keep_err = before.err;
         c->hs() = before; c->hs().err = keep_err;
     }
@@ -803,10 +819,7 @@ static int launch_guard(svjg_ctx *c, unsigned long long *counts = nullptr, hipSt
     HIPCHK(c, hipSetDevice(c->device));
     HIPCHK(c, hipMemsetAsync(counts + c->n_slots, 0, GUARD_WORDS * 8, stream));
     if (c->n_slots || st) {
-        uint32_t grid = (c->n_slots + TPB - 1) / TPB;
-        if (grid > 1024) grid = 1024;
-        if (grid < 1) grid = 1;
-        hipLaunchKernelGGL(k_counts_guard, dim3(grid), dim3(TPB), 0, stream, counts, c->n_slots, st);
+        hipLaunchKernelGGL(k_counts_guard, dim3(capped_grid(c->n_slots)), dim3(TPB), 0, stream, counts, c->n_slots, st);
         HIPCHK(c, hipGetLastError());
     }
     return 0;
@@ -907,76 +920,72 @@ static int build_logfact(svjg_ctx *c, uint32_t upto) {
     return 0;
 }
 
-// results of all rows -> the pinned host block of the context: [ pl 24 | raw 8 | gt 1 | done 1 | boundary 1 ] x n_rows
-static int genotype_rows(svjg_ctx *c, const uint8_t *sv_type, const uint32_t *slot, const uint8_t *ok, uint64_t n_rows,
-                         uint32_t min_support, double err) {
+// ---- one genotype leg, for the step-by-step calls (genotype_rows) and the fused pass alike ----
+// k_genotype's arguments but where the results go (the callers' layouts, svjg_geno.h); p: device block with the rows' inputs at I
+static GenoArgs geno_args(const svjg_ctx *c, const unsigned long long *counts, const uint8_t *p, const RowsIn &I, uint64_t n_rows, uint32_t min_support, double err) {
+    GenoArgs a{};
+    a.counts = counts; a.slot = (const uint32_t *)(p + I.slot); a.sv_type = p + I.type; a.ok = p + I.ok; a.n_rows = n_rows; a.n_slots = c->n_slots;
+    a.min_support = min_support; a.logfact = c->d_logfact; a.logfact_n = c->logfact_n;
+    a.l_ok = log10(1.0 - err); a.l_err = log10(err); a.l_half = log10(1.0 / 2.0);     // host libm, as CPython's math.log10
+    return a;
+}
+
+// all rows with the table at hand, blocks of TPB on the compute stream (a fused pass's FIRST launch is svjg_run_begin's own)
+static int launch_genotype(svjg_ctx *c, GenoArgs &a) {
+    a.logfact = c->d_logfact; a.logfact_n = c->logfact_n;
+    HIPCHK(c, hipMemsetAsync(a.max_n, 0, 8, c->stream));
+    hipLaunchKernelGGL(k_genotype, dim3((uint32_t)((a.n_rows + TPB - 1) / TPB)), dim3(TPB), 0, c->stream, a);
+    HIPCHK(c, hipGetLastError());
+    return 0;
+}
+
+// Behind a launch of `a`, its max_n pair on the host (h_maxn): [1] a row names a slot out of range, [0] the largest n = ref + alt beyond
+// the log10(i!) table.  Only then (first call, or a deeper sample than ever before) the table is rebuilt, the rows run again, `bytes` from
+// d_back come back to h_back (what the caller reads, the pair included) and the check repeats.  relaunch_first: the launch itself is still
+// owed (svjg_run_end behind a repeated pass).  max_n is the maximum over ALL rows, so one growth is enough; the second only guards this reasoning.
+static int settle_genotype(svjg_ctx *c, GenoArgs &a, const unsigned int *h_maxn, void *h_back, const void *d_back, uint64_t bytes, bool relaunch_first) {
+    for (int growths = 0;; relaunch_first = false) {
+        if (!relaunch_first) {
+            if (h_maxn[1]) { c->err = "slot out of range"; return SVJG_E_ARG; }   // (checked by the kernel, row by row)
+            if (h_maxn[0] == 0) return 0;                        // every row found its binomial term
+            if (growths++ == 2) { c->err = "log10(i!) table could not be sized"; return SVJG_E_HIP; }
+            HIPCHK(c, hipStreamSynchronize(c->stream));          // (a pass already enqueued still uses the old table: it drains first)
+            if (c->copy_stream) HIPCHK(c, hipStreamSynchronize(c->copy_stream));
+            if (const int rc = build_logfact(c, logfact_grow_to(h_maxn[0]))) return rc;
+        }
+        if (const int rc = launch_genotype(c, a)) return rc;
+        HIPCHK(c, hipMemcpyAsync(h_back, d_back, bytes, hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(c, hipStreamSynchronize(c->stream));
+    }
+}
+
+// results of all rows -> the pinned host block of the context (rows_layout)
+static int genotype_rows(svjg_ctx *c, const uint8_t *sv_type, const uint32_t *slot, const uint8_t *ok, uint64_t n_rows, uint32_t min_support, double err) {
     HIPCHK(c, hipSetDevice(c->device));
     { const int rc0 = fetch_slot_counts(c); if (rc0) return rc0; }
-    // one device block and its pinned host twin: [ pl 24 | raw 8 | gt 1 | done 1 | boundary 1 ] n rows of output, max_n, then
-    // [ slot 4 | type 1 | ok 1 ] n rows of input -> ONE copy in and ONE copy out per call whatever the number of arrays
-    const uint64_t out_bytes = n_rows * 35, maxn_off = (out_bytes + 7) & ~7ull, in_off = maxn_off + 8, in_bytes = n_rows * 6;
-    const uint64_t total = in_off + in_bytes + 64;
-    int rc = ensure(c, &c->d_rows, &c->rows_cap, total, 1, false);
-    if (rc) return rc;
-    if (total > c->h_rows_cap) {
-        if (c->h_rows) hipHostFree(c->h_rows);
-        c->h_rows = nullptr; c->h_rows_cap = 0;
-        HIPCHK(c, hipHostMalloc(&c->h_rows, total, hipHostMallocDefault));
-        c->h_rows_cap = total;
-    }
+    const RowsLayout L = rows_layout(n_rows);
+    int rc;
+    if ((rc = ensure(c, &c->d_rows, &c->rows_cap, L.total, 1, false))) return rc;
+    if ((rc = ensure_pinned(c, &c->h_rows, &c->h_rows_cap, L.total, hipHostMallocDefault))) return rc;
     uint8_t *base = (uint8_t *)c->d_rows, *hb = (uint8_t *)c->h_rows;
-    int64_t *d_pl = (int64_t *)base;
-    uint32_t *d_raw = (uint32_t *)(base + n_rows * 24);
-    uint8_t *d_gt = base + n_rows * 32, *d_done = base + n_rows * 33;
-    unsigned int *d_maxn = (unsigned int *)(base + maxn_off);
-    uint32_t *d_slot = (uint32_t *)(base + in_off);
-    uint8_t *d_type = base + in_off + n_rows * 4, *d_ok = base + in_off + n_rows * 5;
-    memcpy(hb + in_off, slot, n_rows * 4); memcpy(hb + in_off + n_rows * 4, sv_type, n_rows); memcpy(hb + in_off + n_rows * 5, ok, n_rows);
-    HIPCHK(c, hipMemcpyAsync(base + in_off, hb + in_off, in_bytes, hipMemcpyHostToDevice, c->stream));
-    GenoArgs a{};
-    a.counts = c->d_counts; a.sv_type = d_type; a.slot = d_slot; a.ok = d_ok; a.n_rows = n_rows; a.min_support = min_support;
-    a.l_ok = log10(1.0 - err); a.l_err = log10(err); a.l_half = log10(1.0 / 2.0);     // host libm, as CPython's math.log10
-    a.gt = d_gt; a.pl = d_pl; a.raw = d_raw; a.genotyped = d_done; a.boundary = base + n_rows * 34; a.max_n = d_maxn; a.n_slots = c->n_slots;
+    memcpy(hb + L.in.slot, slot, n_rows * 4); memcpy(hb + L.in.type, sv_type, n_rows); memcpy(hb + L.in.ok, ok, n_rows);
+    HIPCHK(c, hipMemcpyAsync(base + L.in.slot, hb + L.in.slot, L.in.bytes, hipMemcpyHostToDevice, c->stream));
+    GenoArgs a = geno_args(c, c->d_counts, base, L.in, n_rows, min_support, err);
+    a.pl = (int64_t *)(base + L.pl); a.raw = (uint32_t *)(base + L.raw); a.gt = base + L.gt; a.genotyped = base + L.flags;
+    a.boundary = base + L.boundary; a.max_n = (unsigned int *)(base + L.maxn);
     c->geno_rows = n_rows;
-    const uint32_t grid = (uint32_t)((n_rows + TPB - 1) / TPB);
     HIPCHK(c, hipEventRecord(c->ev[4], c->stream));
-    // One pass with the log10(i!) table at hand; the kernel reports the largest n = ref + alt it met beyond the table, and
-    // only then (first call, or a deeper sample than ever before) the table is rebuilt and the pass repeated.
-    uint32_t grow_to = 65536;
-    for (int attempt = 0; attempt < 2; ++attempt) {
-        if (c->logfact_n == 0 && (rc = build_logfact(c, grow_to))) return rc;
-        a.logfact = c->d_logfact; a.logfact_n = c->logfact_n;
-        HIPCHK(c, hipMemsetAsync(d_maxn, 0, 8, c->stream));
-        hipLaunchKernelGGL(k_genotype, dim3(grid), dim3(TPB), 0, c->stream, a);
-        HIPCHK(c, hipGetLastError());
-        if (attempt == 0) HIPCHK(c, hipEventRecord(c->ev[5], c->stream));
-        HIPCHK(c, hipMemcpyAsync(hb, base, maxn_off + 8, hipMemcpyDeviceToHost, c->stream));
-        HIPCHK(c, hipStreamSynchronize(c->stream));
-        if (*(const unsigned int *)(hb + maxn_off + 4)) { c->err = "slot out of range"; return SVJG_E_ARG; }   // (checked by the kernel, row by row)
-        const unsigned int max_n = *(const unsigned int *)(hb + maxn_off);
-        if (max_n == 0) break;                               // every row found its binomial term
-        if (attempt == 1) { c->err = "log10(i!) table could not be sized"; return SVJG_E_HIP; }
-        grow_to = max_n < LOGFACT_CAP - 1024 ? max_n + 1 + 1024 : LOGFACT_CAP;     // (the kernel reports only n < LOGFACT_CAP)
-        c->logfact_n = 0;                                    // rebuild, sized by max_n
-    }
+    if (c->logfact_n == 0 && (rc = build_logfact(c, logfact_first()))) return rc;
+    if ((rc = launch_genotype(c, a))) return rc;
+    HIPCHK(c, hipEventRecord(c->ev[5], c->stream));
+    HIPCHK(c, hipMemcpyAsync(hb, base, L.maxn + 8, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    if ((rc = settle_genotype(c, a, (const unsigned int *)(hb + L.maxn), hb, base, L.maxn + 8, false))) return rc;
     HIPCHK(c, hipEventElapsedTime(&c->ms_geno, c->ev[4], c->ev[5]));
     return 0;
 }
 
-extern "C" int svjg_genotype(svjg_ctx *c, const uint8_t *sv_type, const uint32_t *slot, const uint8_t *ok, uint64_t n_rows,
-                             uint32_t min_support, double err, uint8_t *gt, int64_t *pl, uint32_t *raw, uint8_t *genotyped) {
-    if (!c || !c->have_counts) return SVJG_E_ARG;
-    if (n_rows == 0) return 0;
-    if (!sv_type || !slot || !ok || !gt || !pl || !raw || !genotyped) return SVJG_E_ARG;
-    const int rc = genotype_rows(c, sv_type, slot, ok, n_rows, min_support, err);
-    if (rc) return rc;
-    const uint8_t *hb = (const uint8_t *)c->h_rows;
-    memcpy(pl, hb, n_rows * 24); memcpy(raw, hb + n_rows * 24, n_rows * 8);
-    memcpy(gt, hb + n_rows * 32, n_rows); memcpy(genotyped, hb + n_rows * 33, n_rows);
-    return 0;
-}
-
-// The same, results left where the device wrote them: the four pointers look into the context's pinned host block and stay
+// The results where the device's copy left them: the four pointers look into the context's pinned host block and stay
 // valid until the next svjg_genotype / svjg_genotype_view / svjg_destroy on this context.
 extern "C" int svjg_genotype_view(svjg_ctx *c, const uint8_t *sv_type, const uint32_t *slot, const uint8_t *ok, uint64_t n_rows,
                                   uint32_t min_support, double err, const uint8_t **gt, const int64_t **pl, const uint32_t **raw,
@@ -988,8 +997,19 @@ extern "C" int svjg_genotype_view(svjg_ctx *c, const uint8_t *sv_type, const uin
     const int rc = genotype_rows(c, sv_type, slot, ok, n_rows, min_support, err);
     if (rc) return rc;
     const uint8_t *hb = (const uint8_t *)c->h_rows;
-    *pl = (const int64_t *)hb; *raw = (const uint32_t *)(hb + n_rows * 24);
-    *gt = hb + n_rows * 32; *genotyped = hb + n_rows * 33;
+    const RowsLayout L = rows_layout(n_rows);
+    *pl = (const int64_t *)(hb + L.pl); *raw = (const uint32_t *)(hb + L.raw); *gt = hb + L.gt; *genotyped = hb + L.flags;
+    return 0;
+}
+
+// The same, copied into the caller's arrays.
+extern "C" int svjg_genotype(svjg_ctx *c, const uint8_t *sv_type, const uint32_t *slot, const uint8_t *ok, uint64_t n_rows,
+                             uint32_t min_support, double err, uint8_t *gt, int64_t *pl, uint32_t *raw, uint8_t *genotyped) {
+    if (n_rows && (!gt || !pl || !raw || !genotyped)) return SVJG_E_ARG;
+    const uint8_t *v_gt, *v_done; const int64_t *v_pl; const uint32_t *v_raw;
+    const int rc = svjg_genotype_view(c, sv_type, slot, ok, n_rows, min_support, err, &v_gt, &v_pl, &v_raw, &v_done);   // (checks the rest)
+    if (rc || !n_rows) return rc;
+    memcpy(pl, v_pl, n_rows * 3 * sizeof *pl); memcpy(raw, v_raw, n_rows * 2 * sizeof *raw); memcpy(gt, v_gt, n_rows); memcpy(genotyped, v_done, n_rows);
     return 0;
 }
 
@@ -1003,20 +1023,7 @@ extern "C" int svjg_genotype_view(svjg_ctx *c, const uint8_t *sv_type, const uin
 // repeated the slow way) and hands out its results.  Up to two passes may be in flight: the results of pass k travel over PCIe
 // while pass k + 1 computes.  The passes rotate through RUN_SLOTS = 3 slots (count vector, status block, result blocks): the slot
 // behind the newest pass is used by no pass in flight, and the newest pass's exact-path kernel zeroes it for the pass to come.
-// svjg_run_resident = begin + end.
-// host block (pinned, mapped into the device: the genotype kernel writes its results straight into it — they cross PCIe as they
-// are produced, no copy kernel competes with the next pass —): pl32, raw, gt, flags, boundary, then the tail; device block: the
-// tail (max_n, the pass's status block, the guard words: written by atomics, copied to the host block's tail in one small copy), pl64
-struct RunLayout { uint64_t pl32, raw, gt, flags, boundary, h_tail, out_bytes;  uint64_t maxn, status, guard, tail_bytes, pl64, total; };
-static RunLayout run_layout(uint64_t n) {
-    RunLayout L; uint64_t o = 0;
-    L.pl32 = o; o += n * 12; L.raw = o; o += n * 8; L.gt = o; o += n; L.flags = o; o += n; L.boundary = o; o += n; o = (o + 63) & ~63ull; L.h_tail = o;
-    uint64_t d = 0;
-    L.maxn = d; d += 8; L.status = d; d += (sizeof(DevStatus) + 7) & ~7ull; L.guard = d; d += GUARD_WORDS * 8; L.tail_bytes = d;
-    L.out_bytes = L.h_tail + L.tail_bytes;
-    d = (d + 63) & ~63ull; L.pl64 = d; d += n * 24; L.total = d + 64;
-    return L;
-}
+// svjg_run_resident = begin + end.  Where a slot's results, its tail and the 64-bit PLs lie: run_layout (svjg_geno.h).
 
 // SVJG_KERNEL_MS=events (read once): the fused pass's kernels timed by HIP events around them, as before r07
 static bool kernel_ms_by_events(const svjg_ctx *c) {
@@ -1031,19 +1038,15 @@ extern "C" int svjg_set_rows(svjg_ctx *c, const uint8_t *sv_type, const uint32_t
     { const int rc0 = fetch_slot_counts(c); if (rc0) return rc0; }
     HIPCHK(c, hipSetDevice(c->device));
     const RunLayout L = run_layout(n_rows);
+    const RowsIn I = rows_in(n_rows);
     int rc;
-    if ((rc = ensure(c, &c->d_run_in, &c->d_run_in_cap, n_rows * 6 + 64, 1, false))) return rc;
+    if ((rc = ensure(c, &c->d_run_in, &c->d_run_in_cap, I.bytes + 64, 1, false))) return rc;
     for (int k = 0; k < RUN_SLOTS; ++k) {
         svjg_ctx::RunSlot &r = c->run[k];
         r.clean = false;                                      // (the blocks may move)
         if ((rc = ensure(c, &r.d, &r.d_cap, L.total, 1, false))) return rc;
-        if (L.out_bytes > r.h_cap) {
-            if (r.h) hipHostFree(r.h);
-            r.h = nullptr; r.h_cap = 0;
-            HIPCHK(c, hipHostMalloc(&r.h, L.out_bytes, hipHostMallocMapped));
-            r.h_cap = L.out_bytes;
-            HIPCHK(c, hipHostGetDevicePointer(&r.h_dev, r.h, 0));
-        }
+        if ((rc = ensure_pinned(c, &r.h, &r.h_cap, L.out_bytes, hipHostMallocMapped))) return rc;
+        HIPCHK(c, hipHostGetDevicePointer(&r.h_dev, r.h, 0));
         if ((rc = ensure(c, (void **)&r.counts, &r.counts_cap, (uint64_t)c->n_slots + GUARD_WORDS, sizeof(unsigned long long), false))) return rc;
         for (auto &e : r.ev) if (!e) HIPCHK(c, hipEventCreate(&e));
         if (!r.computed) HIPCHK(c, hipEventCreate(&r.computed));          // (with a time stamp: under SVJG_KERNEL_MS=events it also ends the exact-path kernel's interval)
@@ -1056,9 +1059,9 @@ extern "C" int svjg_set_rows(svjg_ctx *c, const uint8_t *sv_type, const uint32_t
     }
     uint8_t *in = (uint8_t *)c->d_run_in;
     if (n_rows) {
-        HIPCHK(c, hipMemcpyAsync(in, slot, n_rows * 4, hipMemcpyHostToDevice, c->stream));
-        HIPCHK(c, hipMemcpyAsync(in + n_rows * 4, sv_type, n_rows, hipMemcpyHostToDevice, c->stream));
-        HIPCHK(c, hipMemcpyAsync(in + n_rows * 5, ok, n_rows, hipMemcpyHostToDevice, c->stream));
+        HIPCHK(c, hipMemcpyAsync(in + I.slot, slot, n_rows * 4, hipMemcpyHostToDevice, c->stream));
+        HIPCHK(c, hipMemcpyAsync(in + I.type, sv_type, n_rows, hipMemcpyHostToDevice, c->stream));
+        HIPCHK(c, hipMemcpyAsync(in + I.ok, ok, n_rows, hipMemcpyHostToDevice, c->stream));
     }
     HIPCHK(c, hipStreamSynchronize(c->stream));               // (the caller's arrays may go away)
     c->run_rows = n_rows; c->have_rows = true;
@@ -1067,14 +1070,9 @@ extern "C" int svjg_set_rows(svjg_ctx *c, const uint8_t *sv_type, const uint32_t
 
 static GenoArgs run_geno_args(svjg_ctx *c, const svjg_ctx::RunSlot &r, const RunLayout &L, uint32_t min_support, double err, const unsigned long long *counts) {
     uint8_t *base = (uint8_t *)r.d, *hostb = (uint8_t *)r.h_dev;
-    const uint8_t *in = (const uint8_t *)c->d_run_in;
-    GenoArgs a{};
-    a.counts = counts; a.slot = (const uint32_t *)in; a.sv_type = in + c->run_rows * 4; a.ok = in + c->run_rows * 5; a.n_rows = c->run_rows;
-    a.min_support = min_support;
-    a.l_ok = log10(1.0 - err); a.l_err = log10(err); a.l_half = log10(1.0 / 2.0);     // host libm, as CPython's math.log10
+    GenoArgs a = geno_args(c, counts, (const uint8_t *)c->d_run_in, rows_in(c->run_rows), c->run_rows, min_support, err);
     a.gt = hostb + L.gt; a.pl = (int64_t *)(base + L.pl64); a.raw = (uint32_t *)(hostb + L.raw); a.genotyped = hostb + L.flags;
-    a.pl32 = (int32_t *)(hostb + L.pl32); a.boundary = hostb + L.boundary; a.max_n = (unsigned int *)(base + L.maxn); a.n_slots = c->n_slots;
-    a.logfact = c->d_logfact; a.logfact_n = c->logfact_n;
+    a.pl32 = (int32_t *)(hostb + L.pl32); a.boundary = hostb + L.boundary; a.max_n = (unsigned int *)(base + L.maxn);
     return a;
 }
 
@@ -1090,7 +1088,7 @@ extern "C" int svjg_run_begin(svjg_ctx *c, uint64_t base_offset, uint32_t min_su
     int rc;
     if ((rc = ensure(c, (void **)&c->d_deferred, &c->deferred_cap, deferred_want(c, n), sizeof(uint64_t), false))) return rc;
     if ((rc = ensure(c, (void **)&c->d_host, &c->host_cap, 4096, sizeof(uint64_t), false))) return rc;
-    if (c->logfact_n == 0 && (rc = build_logfact(c, 65536))) return rc;
+    if (c->logfact_n == 0 && (rc = build_logfact(c, logfact_first()))) return rc;
     r.base_offset = base_offset; r.min_support = min_support; r.err = err;
     uint8_t *base = (uint8_t *)r.d;
     DevStatus *d_st = (DevStatus *)(base + L.status);             // (the pass's own status block: its tail goes to the host in one small copy)
@@ -1098,9 +1096,7 @@ extern "C" int svjg_run_begin(svjg_ctx *c, uint64_t base_offset, uint32_t min_su
     GenoArgs ga = run_geno_args(c, r, L, min_support, err, r.counts);
     const uint64_t words = (uint64_t)c->n_slots + GUARD_WORDS;
     if (!r.clean) {                                           // the first pass behind svjg_set_rows / svjg_load_graph, or behind a pass without text
-        uint32_t rg = (uint32_t)((words + TPB - 1) / TPB);
-        if (rg > 1024) rg = 1024;
-        hipLaunchKernelGGL(k_step_reset, dim3(rg), dim3(TPB), 0, c->stream, NextPass{r.counts, words, d_st, ga.max_n});
+        hipLaunchKernelGGL(k_step_reset, dim3(capped_grid(words)), dim3(TPB), 0, c->stream, NextPass{r.counts, words, d_st, ga.max_n});
     }
     r.clean = false;
     // SVJG_KERNEL_MS=events: k_classify_main's time from an event pair around it, as before r07 (two barrier packets a pass; for
@@ -1214,8 +1210,7 @@ extern "C" int svjg_run_end(svjg_ctx *c, const uint8_t **gt, const int32_t **pl,
         }
     }
     if (n_rows) HIPCHK(c, hipEventElapsedTime(&c->ms_geno, r.ev[4], r.ev[5]));
-    bool again = false;
-    const unsigned long long *redo_counts = r.counts;             // (a repeated genotype pass reads the slot's vector, or d_counts after the step-by-step fallback)
+    bool again = false;                                           // the pass was repeated step by step: the genotypes again, from d_counts
     const unsigned long long *gd = (const unsigned long long *)(tail + L.guard);   // (meaningful under a communicator: the sums over the ranks)
     if (pass_repeats(c->comm != nullptr, c->hs().overflow, gd[GUARD_REPEAT])) {
         // a list of this rank — or, under a communicator, of ANY rank (svjg_pass.h: the ranks decide together, so all of them issue the
@@ -1227,7 +1222,7 @@ extern "C" int svjg_run_end(svjg_ctx *c, const uint8_t **gt, const int32_t **pl,
         if (rc && rc != SVJG_E_INPUT) return rc;
         if (c->comm) { const std::string keep = c->err; const int rc2 = svjg_allreduce_counts(c); if (rc2 && !rc) return rc2; if (rc) c->err = keep; }
         if (rc) return rc;
-        again = true; redo_counts = c->d_counts;
+        again = true;
     } else {
         c->total_deferred = c->hs().n_deferred;
         if (c->hs().err != ~0ull) return SVJG_E_INPUT;
@@ -1236,25 +1231,9 @@ extern "C" int svjg_run_end(svjg_ctx *c, const uint8_t **gt, const int32_t **pl,
     // (either way: lines the kernels set aside for the host are neither counted nor fatal — the caller has to know)
     if (c->hs().n_host) { c->err = "the text holds lines only the host can decide (non-ASCII digits in a decimal column: svjg_get_host_lines); classify it with svjg_classify"; return SVJG_E_ARG; }
     if (n_rows) {
-        for (int attempt = 0;; ++attempt) {
-            if (!again) {
-                if (*(const unsigned int *)(tail + L.maxn + 4)) { c->err = "slot out of range"; return SVJG_E_ARG; }
-                const unsigned int max_n = *(const unsigned int *)(tail + L.maxn);
-                if (max_n == 0) break;                           // every row found its binomial term
-                if (attempt == 2) { c->err = "log10(i!) table could not be sized"; return SVJG_E_HIP; }
-                // (a pass already enqueued behind this one still uses the old table: it must drain before the table is replaced)
-                HIPCHK(c, hipStreamSynchronize(c->stream));
-                HIPCHK(c, hipStreamSynchronize(c->copy_stream));
-                if ((rc = build_logfact(c, max_n < LOGFACT_CAP - 1024 ? max_n + 1 + 1024 : LOGFACT_CAP))) return rc;   // (only n < LOGFACT_CAP is reported)
-            }
-            again = false;
-            GenoArgs ga = run_geno_args(c, r, L, r.min_support, r.err, redo_counts);
-            HIPCHK(c, hipMemsetAsync(ga.max_n, 0, 8, c->stream));
-            hipLaunchKernelGGL(k_genotype, dim3((uint32_t)((n_rows + TPB - 1) / TPB)), dim3(TPB), 0, c->stream, ga);
-            HIPCHK(c, hipGetLastError());
-            HIPCHK(c, hipMemcpyAsync(hb + L.h_tail + L.maxn, (uint8_t *)r.d + L.maxn, 8, hipMemcpyDeviceToHost, c->stream));
-            HIPCHK(c, hipStreamSynchronize(c->stream));
-        }
+        GenoArgs ga = run_geno_args(c, r, L, r.min_support, r.err, again ? c->d_counts : r.counts);
+        uint8_t *h_maxn = hb + L.h_tail + L.maxn;                 // (the results are already in the mapped host block: only the pair comes back)
+        if ((rc = settle_genotype(c, ga, (const unsigned int *)h_maxn, h_maxn, (const uint8_t *)r.d + L.maxn, 8, again))) return rc;
     }
     *pl = (const int32_t *)(hb + L.pl32); *raw = (const uint32_t *)(hb + L.raw); *gt = hb + L.gt; *flags = hb + L.flags; *boundary = hb + L.boundary;
     return 0;
@@ -1273,7 +1252,7 @@ extern "C" int svjg_run_resident(svjg_ctx *c, uint64_t base_offset, uint32_t min
 // recompute them with the reference's own arithmetic (predict-genotype.py:313: log10 of an exact big integer)
 extern "C" int svjg_genotype_boundary(svjg_ctx *c, uint8_t *out, uint64_t n_rows) {
     if (!c || (n_rows && !out) || n_rows != c->geno_rows || !c->h_rows) return SVJG_E_ARG;
-    memcpy(out, (const uint8_t *)c->h_rows + n_rows * 34, n_rows);
+    memcpy(out, (const uint8_t *)c->h_rows + rows_layout(n_rows).boundary, n_rows);
     return 0;
 }
 

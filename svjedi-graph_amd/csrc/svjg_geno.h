@@ -4,6 +4,7 @@
 #pragma once
 #include <math.h>
 #include <stdint.h>
+#include "svjg_pass.h"
 
 #ifndef SVJG_HD
 #define SVJG_HD __host__ __device__ inline __attribute__((always_inline))
@@ -109,6 +110,41 @@ SVJG_HD uint32_t geno_row(uint32_t type, uint32_t ref, uint32_t alt, uint32_t mi
     }
     o.near = near || st == GENO_ROW_HOST;
     return st;
+}
+
+// ---- host side of a k_genotype launch: the table's size and where a call's rows lie, in plain integers (pinned without a GPU: tests/test_rows_layout.py) ----
+
+// entries of the log10(i!) table: the first one built; the one that holds max_n (the largest n the kernel met beyond the table, < LOGFACT_CAP) with room to spare
+constexpr uint32_t logfact_first() { return 65536; }
+constexpr uint32_t logfact_grow_to(uint32_t max_n) { return max_n < LOGFACT_CAP - 1024 ? max_n + 1 + 1024 : LOGFACT_CAP; }
+
+// the three input arrays of n rows, back to back from byte `at` of a block: [ slot 4 | type 1 | ok 1 ] x n
+struct RowsIn { uint64_t slot, type, ok, bytes; };
+inline RowsIn rows_in(uint64_t n, uint64_t at = 0) { return RowsIn{at, at + n * 4, at + n * 5, n * 6}; }
+
+// step-by-step leg (svjg_genotype, svjg_genotype_view, svjg_genotype_boundary): one device block and its pinned host twin, [ pl 24 | raw 8 |
+// gt 1 | flags 1 | boundary 1 ] x n of output (flags: a row's `genotyped` byte), the max_n pair, then the inputs -> ONE copy in, ONE copy out
+struct RowsLayout { uint64_t pl, raw, gt, flags, boundary, maxn;  RowsIn in;  uint64_t total; };
+inline RowsLayout rows_layout(uint64_t n) {
+    RowsLayout L; uint64_t o = 0;
+    L.pl = o; o += n * 24; L.raw = o; o += n * 8; L.gt = o; o += n; L.flags = o; o += n; L.boundary = o; o += n;
+    L.maxn = (o + 7) & ~7ull; L.in = rows_in(n, L.maxn + 8); L.total = L.in.slot + L.in.bytes + 64;
+    return L;
+}
+
+// fused pass (svjg_set_rows, svjg_run_begin, svjg_run_end), per slot.  Host block (pinned, mapped into the device: the genotype kernel
+// writes its results straight into it — they cross PCIe as they are produced, no copy kernel competes with the next pass —): pl32, raw,
+// gt, flags, boundary, then the tail; device block: the tail (max_n, the pass's status block, the guard words: written by atomics, copied
+// to the host block's tail in one small copy), pl64.  The inputs: one rows_in(n) at offset 0 of a block all slots share.
+struct RunLayout { uint64_t pl32, raw, gt, flags, boundary, h_tail, out_bytes;  uint64_t maxn, status, guard, tail_bytes, pl64, total; };
+inline RunLayout run_layout(uint64_t n) {
+    RunLayout L; uint64_t o = 0;
+    L.pl32 = o; o += n * 12; L.raw = o; o += n * 8; L.gt = o; o += n; L.flags = o; o += n; L.boundary = o; o += n; o = (o + 63) & ~63ull; L.h_tail = o;
+    uint64_t d = 0;
+    L.maxn = d; d += 8; L.status = d; d += (sizeof(DevStatus) + 7) & ~7ull; L.guard = d; d += GUARD_WORDS * 8; L.tail_bytes = d;
+    L.out_bytes = L.h_tail + L.tail_bytes;
+    d = (d + 63) & ~63ull; L.pl64 = d; d += n * 24; L.total = d + 64;
+    return L;
 }
 
 }  // namespace svjg

@@ -91,21 +91,6 @@ static_assert(LDS_MAIN <= 9 * LDS_GRANULE, "fourteen workers per CU");
 static_assert(L_NDBM % 16 == 0 && L_TBM % 16 == 0 && L_OPL % 16 == 0 && L_LINE % 16 == 0 && L_RL % 16 == 0, "LDS alignment");
 #endif
 
-// status words (device)
-struct DevStatus {
-    unsigned long long n_lines;
-    unsigned long long n_deferred;       // entries appended to the deferred list
-    unsigned long long n_recs;           // hit records appended
-    unsigned long long err;              // min over (file offset << 3 | exception class); ~0 = none
-    unsigned int non_ascii;
-    unsigned int overflow;               // bit 0: deferred list, bit 1: hit-record buffer, bit 2: list of lines for the host
-    unsigned long long next_chunk;       // k_classify_main: small chunks handed out so far (zero at launch)
-    unsigned long long n_host;           // lines set aside for the host (SVJG_EXC_ASK_HOST)
-    unsigned long long cause[8];         // deferred lines by cause (DC_*)
-    unsigned long long t_first, t_last;  // k_classify_main: wall_clock64() when its first worker started / its last worker ended (zero at launch)
-    unsigned long long t_exact;          // k_classify_exact: when the last block that had lines to work off ended
-};
-
 struct ClassifyArgs {
     const uint8_t *gaf;                  // resident text, allocation padded with >= TEXT + 64 zero bytes
     uint64_t begin;                      // first byte to classify (a line start); what lies in front of it belongs to another launch
@@ -1950,21 +1935,6 @@ __device__ inline bool geno_gate(const GenoArgs &a, uint64_t r, uint32_t &ref, u
     // sv_id is a key of the informative dict (:216): a key exists iff it has >= 1 informative alignment,
     // unless the caller says the slot itself proves presence (stand-alone run from a JSON, ok bit 1)
     return (ok & 2u) || (ref | alt) != 0;
-}
-
-__global__ __launch_bounds__(TPB) void k_geno_maxn(GenoArgs a) {     // (the largest n below the table's cap, for sizing the table)
-    uint64_t r = (uint64_t)blockIdx.x * TPB + threadIdx.x;
-    uint32_t n = 0;
-    if (r < a.n_rows) {
-        uint32_t ref, alt;
-        if (geno_gate(a, r, ref, alt)) {
-            double c1, c2; uint32_t r1, r2; geno_counts(a.sv_type[r], ref, alt, c1, c2, r1, r2);
-            const uint64_t n64 = geno_n(r1, r2);
-            if (r1 && r2 && n64 < LOGFACT_CAP) n = (uint32_t)n64;
-        }
-    }
-    for (int d = 32; d; d >>= 1) { uint32_t y = __shfl_down(n, d); n = n > y ? n : y; }
-    if ((threadIdx.x & 63) == 0 && n) atomicMax(a.max_n, n);
 }
 
 // (any grid and block size up to TPB: rows in strides of the grid.  svjg_run_begin launches one WAVE per CU: there the kernel runs beside the

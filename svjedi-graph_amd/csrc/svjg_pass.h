@@ -16,6 +16,21 @@ namespace svjg {
 constexpr uint32_t GUARD_WORDS = 3;          // behind the count vector: largest ref field, largest alt field, ranks that must repeat the pass
 constexpr uint32_t GUARD_MAX_REF = 0, GUARD_MAX_ALT = 1, GUARD_REPEAT = 2;
 
+// status words (device); here because a fused pass's row block holds one (svjg_geno.h: run_layout)
+struct DevStatus {
+    unsigned long long n_lines;
+    unsigned long long n_deferred;       // entries appended to the deferred list
+    unsigned long long n_recs;           // hit records appended
+    unsigned long long err;              // min over (file offset << 3 | exception class); ~0 = none
+    unsigned int non_ascii;
+    unsigned int overflow;               // bit 0: deferred list, bit 1: hit-record buffer, bit 2: list of lines for the host
+    unsigned long long next_chunk;       // k_classify_main: small chunks handed out so far (zero at launch)
+    unsigned long long n_host;           // lines set aside for the host (SVJG_EXC_ASK_HOST)
+    unsigned long long cause[8];         // deferred lines by cause (DC_*)
+    unsigned long long t_first, t_last;  // k_classify_main: wall_clock64() when its first worker started / its last worker ended (zero at launch)
+    unsigned long long t_exact;          // k_classify_exact: when the last block that had lines to work off ended
+};
+
 // what this rank contributes to guard word 2 (computed on the device by k_counts_guard from the pass's status block)
 inline
 #ifdef __HIPCC__

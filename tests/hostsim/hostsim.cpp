@@ -276,6 +276,27 @@ extern "C" int hostsim_pass_repeats(int has_comm, uint32_t own_overflow_bits, ui
 extern "C" int hostsim_pass_counts_overflowed(uint64_t a, uint64_t b) { return pass_counts_overflowed(a, b) ? 1 : 0; }
 extern "C" uint32_t hostsim_guard_words(void) { return GUARD_WORDS; }
 
+// where the rows of a genotype call lie (svjg_geno.h), as libsvjg_hip.so lays them out.  which 0: the step-by-step block -> pl, raw, gt, flags,
+// boundary, maxn, slot, type, ok, total; which 1: a fused pass's blocks -> pl32, raw, gt, flags, boundary, h_tail, out_bytes, maxn, status, guard,
+// tail_bytes, pl64, total, then slot, type, ok, bytes of the shared input block.  Returns the number of values written.
+extern "C" int hostsim_rows_layout(uint64_t n, int which, uint64_t *out) {
+    if (which == 0) {
+        const RowsLayout L = rows_layout(n);
+        const uint64_t v[] = {L.pl, L.raw, L.gt, L.flags, L.boundary, L.maxn, L.in.slot, L.in.type, L.in.ok, L.total};
+        memcpy(out, v, sizeof v);
+        return (int)(sizeof v / 8);
+    }
+    const RunLayout L = run_layout(n);
+    const RowsIn I = rows_in(n);
+    const uint64_t v[] = {L.pl32, L.raw, L.gt, L.flags, L.boundary, L.h_tail, L.out_bytes, L.maxn, L.status, L.guard, L.tail_bytes, L.pl64, L.total, I.slot, I.type, I.ok, I.bytes};
+    memcpy(out, v, sizeof v);
+    return (int)(sizeof v / 8);
+}
+extern "C" uint64_t hostsim_sizeof_devstatus(void) { return sizeof(DevStatus); }
+extern "C" uint32_t hostsim_logfact_first(void) { return logfact_first(); }
+extern "C" uint32_t hostsim_logfact_grow_to(uint32_t max_n) { return logfact_grow_to(max_n); }
+extern "C" uint32_t hostsim_logfact_cap(void) { return LOGFACT_CAP; }
+
 // the log10(i!) table of k_logfact_* with the HOST libm's log10 (not the device's), summed in order in double-double (the kernels
 // sum in blocks: the association differs, both far below the guard's budget)
 extern "C" void hostsim_logfact(dd *tab, uint32_t n) {

@@ -125,6 +125,33 @@ def pass_logic():
             lambda a, b: bool(lib.hostsim_pass_counts_overflowed(a, b)), int(lib.hostsim_guard_words()))
 
 
+STEP_FIELDS = ("pl", "raw", "gt", "flags", "boundary", "maxn", "slot", "type", "ok", "total")
+FUSED_FIELDS = ("pl32", "raw", "gt", "flags", "boundary", "h_tail", "out_bytes", "maxn", "status", "guard", "tail_bytes", "pl64", "total",
+                "slot", "type", "ok", "in_bytes")
+
+
+def rows_layout(n, fused=False):
+    """byte offsets of the row block(s) of a genotype call over n rows (svjg_geno.h: rows_layout / run_layout + rows_in), by field name"""
+    lib = ctypes.CDLL(build())
+    lib.hostsim_rows_layout.restype = ctypes.c_int
+    lib.hostsim_rows_layout.argtypes = [ctypes.c_uint64, ctypes.c_int, ctypes.c_void_p]
+    out = (ctypes.c_uint64 * 32)()
+    names = FUSED_FIELDS if fused else STEP_FIELDS
+    assert lib.hostsim_rows_layout(n, int(fused), out) == len(names)
+    return {k: int(out[i]) for i, k in enumerate(names)}
+
+
+def geno_constants():
+    """(sizeof(DevStatus), logfact_first(), LOGFACT_CAP, logfact_grow_to) of the library's headers"""
+    lib = ctypes.CDLL(build())
+    lib.hostsim_sizeof_devstatus.restype = ctypes.c_uint64
+    for f in (lib.hostsim_logfact_first, lib.hostsim_logfact_grow_to, lib.hostsim_logfact_cap):
+        f.restype = ctypes.c_uint32
+    lib.hostsim_logfact_grow_to.argtypes = [ctypes.c_uint32]
+    return (int(lib.hostsim_sizeof_devstatus()), int(lib.hostsim_logfact_first()), int(lib.hostsim_logfact_cap()),
+            lambda m: int(lib.hostsim_logfact_grow_to(m)))
+
+
 def logfact_table(n):
     """log10(i!) for i < n in double-double (float64[n, 2]), built with the host libm's log10 — not the device's"""
     lib = ctypes.CDLL(build())

@@ -535,11 +535,11 @@ def test_vcf_text_of_deep_rows(ctx, golden, tmp_path):
         assert text == want, (t, a, b)
 
 
-def test_fused_pass_beyond_the_first_table(golden):
-    """The fused pass (svjg_run_resident, svjg_run_begin / svjg_run_end) with one SV past 65 536 informative alignments on both alleles
-    (66 000 copies of a ref line and of an alt line of golden/testdir): the pass regrows the log10(i!) table itself.  Counts equal
-    the C oracle's; GT and PL of every row equal the reference's likelihood() (oracle_py, n <= 10^5 so that math.comb stays cheap)."""
-    from svjg import capi, genotype
+def _deep_sv_case(golden, tag=b""):
+    """66 000 copies of a ref line and of an alt line of golden/testdir for one SV, `tag` put in front of every line's dv:f: tag ->
+    (graph, text, number of lines, VCF rows, check(context, results)).  check: counts equal the C oracle's on the same text; GT and PL of
+    every row equal the reference's likelihood() (oracle_py, n <= 10^5 so that math.comb stays cheap)."""
+    from svjg import genotype
     from svjg.graph import Graph
     d = f"{golden}/testdir"
     g = Graph.from_files(f"{d}/test_svs_edges.json", f"{d}/test.gfa")
@@ -552,7 +552,8 @@ def test_fused_pass_beyond_the_first_table(golden):
         cnt, _, _ = orc.filter(np.frombuffer(ln + b"\n", dtype=np.uint8), want_hits=False)
         for a in (0, 1):
             if pick[a] is None and cnt[sv, a] and cnt[sv, 1 - a] == 0:
-                pick[a] = ln + b"\n"
+                pick[a] = (ln + b"\n").replace(b"\tdv:f:", tag + b"\tdv:f:")
+    assert all(tag in p for p in pick)
     gaf = np.frombuffer(pick[0] * 66000 + pick[1] * 66000, dtype=np.uint8)
     want, _, n_lines = orc.filter(gaf, want_hits=False)
     assert want[sv, 0] > 65536 and want[sv, 1] > 65536
@@ -581,6 +582,15 @@ def test_fused_pass_beyond_the_first_table(golden):
             else:
                 assert not flags[r] & 1
 
+    return g, gaf, n_lines, rows, check
+
+
+def test_fused_pass_beyond_the_first_table(golden):
+    """The fused pass (svjg_run_resident, svjg_run_begin / svjg_run_end) with one SV past 65 536 informative alignments on both alleles
+    (66 000 copies of a ref line and of an alt line of golden/testdir): the pass regrows the log10(i!) table itself.  Counts equal
+    the C oracle's; GT and PL of every row equal the reference's likelihood() (oracle_py, n <= 10^5 so that math.comb stays cheap)."""
+    from svjg import capi
+    g, gaf, n_lines, rows, check = _deep_sv_case(golden)
     c = capi.Context(0)
     try:
         c.load_graph(g)
@@ -600,6 +610,37 @@ def test_fused_pass_beyond_the_first_table(golden):
         c.run_begin(3, 0.00005)
         check(c, c.run_end())
         check(c, c.run_end())
+    finally:
+        c.close()
+
+
+def test_repeated_fused_pass_beyond_the_first_table(golden):
+    """Both ways into the loop behind k_genotype at once: the same text with an id:f:5e-1 tag on every line, so that all 132 000 lines
+    are deferred — more than the list of deferred lines holds (n_bytes / 4096 + 65 536 entries) — and the fused pass is repeated step by
+    step; the genotypes launched behind that repeat then find the first log10(i!) table too short.  Fresh contexts, so that the table
+    is the first one: once through svjg_run_resident, once with two passes in flight."""
+    from svjg import capi
+    g, gaf, n_lines, rows, check = _deep_sv_case(golden, b"\tid:f:5e-1")
+    assert gaf.size // 4096 + 65536 < n_lines == 132000     # (svjg_capi.hip: deferred_want)
+    c = capi.Context(0)
+    try:
+        c.load_graph(g)
+        c.set_rows(rows.sv_type, rows.slot, rows.ok)
+        c.upload(gaf)
+        check(c, c.run_resident(3, 0.00005))
+        assert c.stats()["n_deferred"] == n_lines and c.stats()["n_lines"] == n_lines
+    finally:
+        c.close()
+    c = capi.Context(0)
+    try:
+        c.load_graph(g)
+        c.set_rows(rows.sv_type, rows.slot, rows.ok)
+        c.upload(gaf)
+        c.run_begin(3, 0.00005)
+        c.run_begin(3, 0.00005)
+        for _ in range(2):
+            check(c, c.run_end())
+            assert c.stats()["n_deferred"] == n_lines
     finally:
         c.close()
 
