@@ -220,6 +220,19 @@ int svjg_genotype_view(svjg_ctx *ctx, const uint8_t *sv_type, const uint32_t *sl
                        uint64_t n_rows, uint32_t min_support, double err,
                        const uint8_t **gt, const int64_t **pl, const uint32_t **raw, const uint8_t **genotyped);
 
+/* Any ploidy from 1 to SVJG_MAX_PLOIDY, row by row: ploidy[r] in 0..SVJG_MAX_PLOIDY beside the three inputs of svjg_genotype.  A row of
+ * ploidy P has P + 1 genotypes, g = 0..P alt copies; a read shows the alt allele with probability (g (1 - e) + (P - g) e) / P, which at
+ * P = 2 is the reference's likelihood() term for term.  Outputs: gt[r] = alt copies of the call (0xFF = no call), pl[r*9..] = PL_0..PL_P in
+ * that order (entries beyond a row's ploidy = 0), raw and genotyped as svjg_genotype; boundary[r] = 1 where one of the P + 1 values lies within
+ * 1e-6 of an integer (what svjg_genotype_boundary reports for svjg_genotype; this call neither reads nor changes that state, nor the views of
+ * svjg_genotype_view): recompute such rows with svjedi-graph_amd/svjg/genotype.py: exact_pl_ploidy.  A row with ploidy 0 is never genotyped
+ * (genotyped = 0, raw = 0,0).  SVJG_E_ARG: a ploidy above SVJG_MAX_PLOIDY (found before any launch), a null array, no counts yet, a slot out
+ * of range. */
+#define SVJG_MAX_PLOIDY 8
+int svjg_genotype_ploidy(svjg_ctx *ctx, const uint8_t *sv_type, const uint32_t *slot, const uint8_t *ok, const uint8_t *ploidy,
+                         uint64_t n_rows, uint32_t min_support, double err,
+                         uint8_t *gt, int64_t *pl, uint32_t *raw, uint8_t *genotyped, uint8_t *boundary);
+
 /* ---- the whole pass in one call (what a fused svjedi-graph run and bench.py do per batch) -----------------------------------
  * svjg_set_rows copies the three per-row input arrays of svjg_genotype to the device once (they stay until the next
  * svjg_set_rows / svjg_destroy).  svjg_run_resident then does, for the resident text of svjg_gaf_upload and those rows:

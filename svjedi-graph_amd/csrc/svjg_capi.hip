@@ -115,6 +115,8 @@ struct svjg_ctx {
     void *d_rows = nullptr;  uint64_t rows_cap = 0;
     void *h_rows = nullptr;  uint64_t h_rows_cap = 0;   // pinned twin of d_rows
     uint64_t geno_rows = 0;                              // rows of the last svjg_genotype / svjg_genotype_view (svjg_genotype_boundary)
+    void *d_prows = nullptr;  uint64_t prows_cap = 0;    // svjg_genotype_ploidy's own block and pinned twin (ploidy_layout): the views and the
+    void *h_prows = nullptr;  uint64_t h_prows_cap = 0;  // boundary bytes of the calls above stay as they are
     // resident VCF rows of svjg_set_rows / svjg_run_resident: device block (results, row inputs) and the pinned host block the results land in
     struct RunSlot {
         void *d = nullptr;  uint64_t d_cap = 0;  void *h = nullptr;  uint64_t h_cap = 0;  void *h_dev = nullptr;   // h_dev: the pinned block as the device sees it
@@ -207,7 +209,7 @@ extern "C" void svjg_destroy(svjg_ctx *c) {
     free_graph(c);
     hipFree(c->d_long);
     hipFree(c->d_gaf); hipFree(c->d_deferred); hipFree(c->d_recs); hipFree(c->d_host); hipFree(c->d_st); hipFree(c->d_logfact);
-    hipFree(c->d_bsum); hipFree(c->d_rows); hipFree(c->d_run_in);
+    hipFree(c->d_bsum); hipFree(c->d_rows); hipFree(c->d_prows); hipFree(c->d_run_in);
     for (auto &r : c->run) {
         hipFree(r.d); hipFree(r.counts);
         if (r.h) hipHostFree(r.h);
@@ -216,6 +218,7 @@ extern "C" void svjg_destroy(svjg_ctx *c) {
         if (r.copied) hipEventDestroy(r.copied);
     }
     if (c->h_rows) hipHostFree(c->h_rows);
+    if (c->h_prows) hipHostFree(c->h_prows);
     if (c->h_stp) hipHostFree(c->h_stp);
     for (auto &b : c->h_stage) if (b) hipHostFree(b);
     for (auto &ev : c->stage_ev) if (ev) hipEventDestroy(ev);
@@ -931,10 +934,13 @@ static GenoArgs geno_args(const svjg_ctx *c, const unsigned long long *counts, c
 }
 
 // all rows with the table at hand, blocks of TPB on the compute stream (a fused pass's FIRST launch is svjg_run_begin's own)
-static int launch_genotype(svjg_ctx *c, GenoArgs &a) {
+// ploidy != nullptr: k_genotype_ploidy with the rows' ploidies and the call's logarithms (svjg_genotype_ploidy), else k_genotype
+static int launch_genotype(svjg_ctx *c, GenoArgs &a, const uint8_t *ploidy = nullptr, const double *logtab = nullptr) {
     a.logfact = c->d_logfact; a.logfact_n = c->logfact_n;
     HIPCHK(c, hipMemsetAsync(a.max_n, 0, 8, c->stream));
-    hipLaunchKernelGGL(k_genotype, dim3((uint32_t)((a.n_rows + TPB - 1) / TPB)), dim3(TPB), 0, c->stream, a);
+    const dim3 grid((uint32_t)((a.n_rows + TPB - 1) / TPB));
+    if (ploidy) hipLaunchKernelGGL(k_genotype_ploidy, grid, dim3(TPB), 0, c->stream, GenoPloidyArgs{a, ploidy, logtab});
+    else hipLaunchKernelGGL(k_genotype, grid, dim3(TPB), 0, c->stream, a);
     HIPCHK(c, hipGetLastError());
     return 0;
 }
@@ -943,7 +949,8 @@ static int launch_genotype(svjg_ctx *c, GenoArgs &a) {
 // the log10(i!) table.  Only then (first call, or a deeper sample than ever before) the table is rebuilt, the rows run again, `bytes` from
 // d_back come back to h_back (what the caller reads, the pair included) and the check repeats.  relaunch_first: the launch itself is still
 // owed (svjg_run_end behind a repeated pass).  max_n is the maximum over ALL rows, so one growth is enough; the second only guards this reasoning.
-static int settle_genotype(svjg_ctx *c, GenoArgs &a, const unsigned int *h_maxn, void *h_back, const void *d_back, uint64_t bytes, bool relaunch_first) {
+static int settle_genotype(svjg_ctx *c, GenoArgs &a, const unsigned int *h_maxn, void *h_back, const void *d_back, uint64_t bytes, bool relaunch_first,
+                           const uint8_t *ploidy = nullptr, const double *logtab = nullptr) {
     for (int growths = 0;; relaunch_first = false) {
         if (!relaunch_first) {
             if (h_maxn[1]) { c->err = "slot out of range"; return SVJG_E_ARG; }   // (checked by the kernel, row by row)
@@ -953,7 +960,7 @@ static int settle_genotype(svjg_ctx *c, GenoArgs &a, const unsigned int *h_maxn,
             if (c->copy_stream) HIPCHK(c, hipStreamSynchronize(c->copy_stream));
             if (const int rc = build_logfact(c, logfact_grow_to(h_maxn[0]))) return rc;
         }
-        if (const int rc = launch_genotype(c, a)) return rc;
+        if (const int rc = launch_genotype(c, a, ploidy, logtab)) return rc;
         HIPCHK(c, hipMemcpyAsync(h_back, d_back, bytes, hipMemcpyDeviceToHost, c->stream));
         HIPCHK(c, hipStreamSynchronize(c->stream));
     }
@@ -1010,6 +1017,45 @@ extern "C" int svjg_genotype(svjg_ctx *c, const uint8_t *sv_type, const uint32_t
     const int rc = svjg_genotype_view(c, sv_type, slot, ok, n_rows, min_support, err, &v_gt, &v_pl, &v_raw, &v_done);   // (checks the rest)
     if (rc || !n_rows) return rc;
     memcpy(pl, v_pl, n_rows * 3 * sizeof *pl); memcpy(raw, v_raw, n_rows * 2 * sizeof *raw); memcpy(gt, v_gt, n_rows); memcpy(genotyped, v_done, n_rows);
+    return 0;
+}
+
+// Any ploidy from 1 to SVJG_MAX_PLOIDY per row (k_genotype_ploidy): the same leg — one copy in (the call's logarithms and the four input
+// arrays), one kernel, one copy out, settled by settle_genotype — in a block of its own, so that what svjg_genotype_view and
+// svjg_genotype_boundary hand out stays untouched.
+extern "C" int svjg_genotype_ploidy(svjg_ctx *c, const uint8_t *sv_type, const uint32_t *slot, const uint8_t *ok, const uint8_t *ploidy,
+                                    uint64_t n_rows, uint32_t min_support, double err, uint8_t *gt, int64_t *pl, uint32_t *raw,
+                                    uint8_t *genotyped, uint8_t *boundary) {
+    if (!c || !c->have_counts) return SVJG_E_ARG;
+    if (n_rows == 0) return 0;
+    if (!sv_type || !slot || !ok || !ploidy || !gt || !pl || !raw || !genotyped || !boundary) return SVJG_E_ARG;
+    for (uint64_t r = 0; r < n_rows; ++r)
+        if (ploidy[r] > SVJG_MAX_PLOIDY) { c->err = "ploidy above SVJG_MAX_PLOIDY"; return SVJG_E_ARG; }
+    static_assert(SVJG_MAX_PLOIDY == MAX_PLOIDY, "svjg.h and svjg_geno.h disagree");
+    HIPCHK(c, hipSetDevice(c->device));
+    { const int rc0 = fetch_slot_counts(c); if (rc0) return rc0; }
+    const PloidyLayout L = ploidy_layout(n_rows);
+    int rc;
+    if ((rc = ensure(c, &c->d_prows, &c->prows_cap, L.total, 1, false))) return rc;
+    if ((rc = ensure_pinned(c, &c->h_prows, &c->h_prows_cap, L.total, hipHostMallocDefault))) return rc;
+    uint8_t *base = (uint8_t *)c->d_prows, *hb = (uint8_t *)c->h_prows;
+    ploidy_log_table(err, (double *)(hb + L.logtab));            // host libm, as geno_args' three
+    memcpy(hb + L.in.slot, slot, n_rows * 4); memcpy(hb + L.in.type, sv_type, n_rows); memcpy(hb + L.in.ok, ok, n_rows); memcpy(hb + L.ploidy, ploidy, n_rows);
+    HIPCHK(c, hipMemcpyAsync(base + L.logtab, hb + L.logtab, L.in_bytes, hipMemcpyHostToDevice, c->stream));
+    GenoArgs a = geno_args(c, c->d_counts, base, L.in, n_rows, min_support, err);
+    a.pl = (int64_t *)(base + L.pl); a.raw = (uint32_t *)(base + L.raw); a.gt = base + L.gt; a.genotyped = base + L.flags;
+    a.boundary = base + L.boundary; a.max_n = (unsigned int *)(base + L.maxn);
+    const uint8_t *d_ploidy = base + L.ploidy; const double *d_logtab = (const double *)(base + L.logtab);
+    HIPCHK(c, hipEventRecord(c->ev[4], c->stream));
+    if (c->logfact_n == 0 && (rc = build_logfact(c, logfact_first()))) return rc;
+    if ((rc = launch_genotype(c, a, d_ploidy, d_logtab))) return rc;
+    HIPCHK(c, hipEventRecord(c->ev[5], c->stream));
+    HIPCHK(c, hipMemcpyAsync(hb, base, L.maxn + 8, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    if ((rc = settle_genotype(c, a, (const unsigned int *)(hb + L.maxn), hb, base, L.maxn + 8, false, d_ploidy, d_logtab))) return rc;
+    HIPCHK(c, hipEventElapsedTime(&c->ms_geno, c->ev[4], c->ev[5]));
+    memcpy(pl, hb + L.pl, n_rows * (MAX_PLOIDY + 1) * sizeof *pl); memcpy(raw, hb + L.raw, n_rows * 2 * sizeof *raw);
+    memcpy(gt, hb + L.gt, n_rows); memcpy(genotyped, hb + L.flags, n_rows); memcpy(boundary, hb + L.boundary, n_rows);
     return 0;
 }
 

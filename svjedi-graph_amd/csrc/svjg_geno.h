@@ -112,6 +112,86 @@ SVJG_HD uint32_t geno_row(uint32_t type, uint32_t ref, uint32_t alt, uint32_t mi
     return st;
 }
 
+// ---- any ploidy from 1 to MAX_PLOIDY (k_genotype_ploidy) ----
+// A row of ploidy P has P + 1 genotypes, g = 0..P alt copies.  A read shows the alt allele with probability (g (1 - e) + (P - g) e) / P,
+// the ref allele with ((P - g) (1 - e) + g e) / P: lik_g = c1 * Lr[P][g] + c2 * La[P][g].  g = 0 and g = P are the reference's lik0 and
+// lik2 (log10(1 - e), log10(e)), 2 g = P its lik1, ONE product (c1 + c2) * log10(1/2): at P = 2 this is geno_row term for term.
+constexpr uint32_t MAX_PLOIDY = 8;
+#ifdef __clang__
+#define SVJG_UNROLL _Pragma("unroll")
+#else
+#define SVJG_UNROLL
+#endif
+constexpr uint32_t PLOIDY_TAB = 45;                      // entries of Lr (and of La): [P (P + 1) / 2 + g], P = 1..8, g = 0..P; entry 0 unused
+SVJG_HD uint32_t ploidy_tab_at(uint32_t P, uint32_t g) { return P * (P + 1) / 2 + g; }
+
+// The logarithms of a call, by the host's libm like geno_args' three (the kernel computes none): tab[0..44] = Lr, tab[45..89] = La.
+// The quotients are formed in doubles in exactly the order the model is written in.
+inline void ploidy_log_table(double err, double *tab) {
+    const double l_ok = log10(1.0 - err), l_err = log10(err), l_half = log10(1.0 / 2.0);
+    tab[0] = tab[PLOIDY_TAB] = 0.0;
+    for (uint32_t P = 1; P <= MAX_PLOIDY; ++P)
+        for (uint32_t g = 0; g <= P; ++g) {
+            double lr, la;
+            if (g == 0) { lr = l_ok; la = l_err; }
+            else if (g == P) { lr = l_err; la = l_ok; }
+            else if (2 * g == P) lr = la = l_half;
+            else {
+                const double pg = (double)(P - g), gg = (double)g, pp = (double)P, ok = 1.0 - err;
+                const double a = pg * ok, b = gg * err, c = gg * ok, d = pg * err;       // (each product rounded on its own: no fused multiply-add)
+                lr = log10((a + b) / pp); la = log10((c + d) / pp);
+            }
+            tab[ploidy_tab_at(P, g)] = lr; tab[PLOIDY_TAB + ploidy_tab_at(P, g)] = la;
+        }
+}
+
+struct GenoRowPloidy {
+    int64_t pl[MAX_PLOIDY + 1];   // PL_g for g = 0..P, 0 beyond
+    uint8_t gt;                   // alt copies of the call, 0xFF: no call
+    bool near;                    // as GenoRow::near, over the P + 1 values
+    uint64_t n;                   // r1 + r2
+};
+
+// One genotyped row of ploidy P in 1..MAX_PLOIDY; lr / la: the two halves of ploidy_log_table.  Status and flag as geno_row.  The loop
+// over g is unrolled with a predicate so that pl[] is only ever indexed by constants (registers on the device, no scratch).
+SVJG_HD uint32_t geno_row_ploidy(uint32_t type, uint32_t ref, uint32_t alt, uint32_t P, uint32_t min_support, const double *lr, const double *la,
+                                 const dd *logfact, uint32_t logfact_n, GenoRowPloidy &o) {
+#ifdef __clang__
+#pragma clang fp contract(off)                           // the products are rounded to doubles before the exact sums
+#endif
+    double c1, c2; uint32_t r1, r2;
+    geno_counts(type, ref, alt, c1, c2, r1, r2);
+    const uint64_t n = geno_n(r1, r2);
+    o.n = n;
+    uint32_t st = GENO_ROW_OK;
+    dd comb{0.0, 0.0};
+    if (r1 && r2) {
+        if (n < logfact_n) comb = dd_add(dd_add(logfact[n], dd_neg(logfact[n - r1])), dd_neg(logfact[r1]));
+        else st = n < LOGFACT_CAP ? GENO_ROW_GROW : GENO_ROW_HOST;
+    }
+    comb = dd{comb.hi, 0.0};                             // rounded to a double first, like the reference (:313)
+    const uint32_t base = ploidy_tab_at(P, 0);
+    dd best{0.0, 0.0}; uint8_t g_best = 0xFF; bool tie = false, near = false;
+    SVJG_UNROLL
+    for (uint32_t g = 0; g <= MAX_PLOIDY; ++g) {
+        o.pl[g] = 0;
+        if (g > P) continue;
+        const double a = c1 * lr[base + g], b = c2 * la[base + g], h = (c1 + c2) * lr[base + g];
+        const dd l = (g != 0 && 2 * g == P) ? dd{h, 0.0} : two_sum(a, b);
+        const int c = g ? dd_cmp(l, best) : 1;
+        if (c > 0) { best = l; g_best = (uint8_t)g; tie = false; } else if (c == 0) tie = true;
+        dd s = dd_add(l, comb);
+        dd p = dd_add(dd_add(dd_add(s, s), dd_add(s, s)), s);             // 5 s
+        p = dd_add(p, p);                                                 // 10 s
+        o.pl[g] = trunc_dd(dd_neg(p));
+        { const double fr = fabs((p.hi - rint(p.hi)) + p.lo); if (fr < PL_GUARD && comb.hi != 0.0) near = true; }   // (as geno_row)
+    }
+    if (tie || !(c1 + c2 >= (double)min_support)) g_best = 0xFF;
+    o.gt = g_best;
+    o.near = near || st == GENO_ROW_HOST;
+    return st;
+}
+
 // ---- host side of a k_genotype launch: the table's size and where a call's rows lie, in plain integers (pinned without a GPU: tests/test_rows_layout.py) ----
 
 // entries of the log10(i!) table: the first one built; the one that holds max_n (the largest n the kernel met beyond the table, < LOGFACT_CAP) with room to spare
@@ -129,6 +209,17 @@ inline RowsLayout rows_layout(uint64_t n) {
     RowsLayout L; uint64_t o = 0;
     L.pl = o; o += n * 24; L.raw = o; o += n * 8; L.gt = o; o += n; L.flags = o; o += n; L.boundary = o; o += n;
     L.maxn = (o + 7) & ~7ull; L.in = rows_in(n, L.maxn + 8); L.total = L.in.slot + L.in.bytes + 64;
+    return L;
+}
+
+// any-ploidy leg (svjg_genotype_ploidy): the same in a block of its own, [ pl 72 | raw 8 | gt 1 | flags 1 | boundary 1 ] x n, the max_n pair, then
+// ONE copy in: the call's logarithms (ploidy_log_table), rows_in(n) and the ploidy bytes
+struct PloidyLayout { uint64_t pl, raw, gt, flags, boundary, maxn, logtab;  RowsIn in;  uint64_t ploidy, in_bytes, total; };
+inline PloidyLayout ploidy_layout(uint64_t n) {
+    PloidyLayout L; uint64_t o = 0;
+    L.pl = o; o += n * 8 * (MAX_PLOIDY + 1); L.raw = o; o += n * 8; L.gt = o; o += n; L.flags = o; o += n; L.boundary = o; o += n;
+    L.maxn = (o + 7) & ~7ull; L.logtab = L.maxn + 8; L.in = rows_in(n, L.logtab + 2 * PLOIDY_TAB * 8);
+    L.ploidy = L.in.slot + L.in.bytes; L.in_bytes = 2 * PLOIDY_TAB * 8 + L.in.bytes + n; L.total = L.logtab + L.in_bytes + 64;
     return L;
 }
 

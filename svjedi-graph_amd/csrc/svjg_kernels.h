@@ -1965,4 +1965,43 @@ __global__ __launch_bounds__(TPB) void k_genotype(GenoArgs a) {
   }
 }
 
+// k_genotype at any ploidy from 1 to MAX_PLOIDY (svjg_geno.h: geno_row_ploidy).  g: as for k_genotype, but g.pl holds MAX_PLOIDY + 1 integers
+// per row (entries beyond a row's ploidy: 0) and g.pl32 / the three logarithms are unused.  ploidy[r] = 0: the row is never genotyped.
+struct GenoPloidyArgs {
+    GenoArgs g;
+    const uint8_t *ploidy;
+    const double *logtab;              // ploidy_log_table of the call's err: 2 x PLOIDY_TAB doubles
+};
+
+// The ploidy differs from lane to lane, so the logarithms are looked up per lane: the block stages the table in LDS (720 bytes) and each
+// lane reads its P + 1 pairs from there.
+__global__ __launch_bounds__(TPB) void k_genotype_ploidy(GenoPloidyArgs p) {
+  __shared__ double tab[2 * PLOIDY_TAB];
+  for (uint32_t i = threadIdx.x; i < 2 * PLOIDY_TAB; i += blockDim.x) tab[i] = p.logtab[i];
+  __syncthreads();
+  const GenoArgs &a = p.g;
+  constexpr uint32_t NPL = MAX_PLOIDY + 1;
+  for (uint64_t r = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; r < a.n_rows; r += (uint64_t)gridDim.x * blockDim.x) {
+    uint32_t ref, alt;
+    const uint32_t P = p.ploidy[r];
+    bool go = geno_gate(a, r, ref, alt) && P >= 1 && P <= MAX_PLOIDY;
+    a.raw[r * 2] = go ? ref : 0; a.raw[r * 2 + 1] = go ? alt : 0;
+    a.genotyped[r] = go;
+    a.boundary[r] = 0;
+    if (!go) {
+        a.gt[r] = 0xFF;
+#pragma unroll
+        for (uint32_t i = 0; i < NPL; ++i) a.pl[r * NPL + i] = 0;
+        continue;
+    }
+    GenoRowPloidy o;
+    const uint32_t st = geno_row_ploidy(a.sv_type[r], ref, alt, P, a.min_support, tab, tab + PLOIDY_TAB, a.logfact, a.logfact_n, o);
+    if (st == GENO_ROW_GROW) atomicMax(a.max_n, (uint32_t)o.n);
+    a.gt[r] = o.gt;
+#pragma unroll
+    for (uint32_t i = 0; i < NPL; ++i) a.pl[r * NPL + i] = o.pl[i];
+    if (o.near) a.boundary[r] = 1;
+  }
+}
+
 }  // namespace svjg

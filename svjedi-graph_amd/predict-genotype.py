@@ -18,11 +18,15 @@ def main():
     ap.add_argument("-e", "--err", nargs=1, type=float, help="allele error probability")
     ap.add_argument("-ms", "--minsupport", metavar="<minNbAln>", type=int, default=3,
                     help="Minimum number of alignments to genotype a SV (default: 3>=)")
+    ap.add_argument("--ploidy", metavar="<ploidy>", type=int, choices=range(1, 9),
+                    help="ploidy of every SV, 1..8 (extension; default: the reference's diploid model)")
+    ap.add_argument("--ploidy-file", metavar="<ploidyfile>",
+                    help="per-contig or per-region ploidy, 0..8: lines `CHROM PLOIDY` or `CHROM FROM TO PLOIDY` (extension)")
     args = ap.parse_args()
     out = "genotype_results.txt" if args.output is None else args.output[0]
     err = args.err[0] if args.err is not None else 0.00005
     from svjg import genotype
-    genotype.run(args.aln[0], args.vcf, out, args.minsupport, err)
+    genotype.run(args.aln[0], args.vcf, out, args.minsupport, err, ploidy=args.ploidy, ploidy_file=args.ploidy_file)
 
 
 if __name__ == "__main__":

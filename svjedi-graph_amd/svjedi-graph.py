@@ -38,6 +38,10 @@ def main():
                     help="Minimum number of alignments to genotype a SV (default: 3>=)")
     ap.add_argument("--fused", action="store_true", help="filter + genotype in one GPU context (extension)")
     ap.add_argument("--no-json", action="store_true", help="with --fused: skip writing _informative_aln.json (extension)")
+    ap.add_argument("--ploidy", metavar="<ploidy>", type=int, choices=range(1, 9),
+                    help="ploidy of every SV, 1..8 (extension; default: the reference's diploid model)")
+    ap.add_argument("--ploidy-file", metavar="<ploidyfile>",
+                    help="per-contig or per-region ploidy, 0..8: lines `CHROM PLOIDY` or `CHROM FROM TO PLOIDY` (extension)")
     args = ap.parse_args()
     pre = args.prefix
 
@@ -73,7 +77,7 @@ def main():
             sys.exit("Failed to filter the alignments.\nExiting SVJedi-graph.")
         print("Genotyping SVs...")
         try:
-            n = genotype.genotype_with_counts(ctx, args.vcf, graph.slot_of, out_vcf, args.minsupport)
+            n = genotype.genotype_with_counts(ctx, args.vcf, graph.slot_of, out_vcf, args.minsupport, ploidy=args.ploidy, ploidy_file=args.ploidy_file)
             print("Genotyped svs: " + str(n))
         except Exception:
             import traceback
@@ -87,8 +91,10 @@ def main():
         sys.exit("Failed to filter the alignments.\nExiting SVJedi-graph.")
 
     print("Genotyping SVs...")
-    p = subprocess.run("python3 {}/predict-genotype.py -d {} -v {} --minsupport {} -o {}".format(
-        HERE, out_json, args.vcf, str(args.minsupport), out_vcf), shell=True)
+    ploidy_opts = ("" if args.ploidy is None else " --ploidy {}".format(args.ploidy)) + \
+                  ("" if args.ploidy_file is None else " --ploidy-file {}".format(args.ploidy_file))
+    p = subprocess.run("python3 {}/predict-genotype.py -d {} -v {} --minsupport {} -o {}{}".format(
+        HERE, out_json, args.vcf, str(args.minsupport), out_vcf, ploidy_opts), shell=True)
     if p.returncode == 1:
         sys.exit("Failed to predict the genotypes.\nExiting SVJedi-graph.")
 

@@ -83,6 +83,7 @@ _SIGS = {
                                      ctypes.c_void_p]),
     "svjg_genotype_view": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64,
                                           ctypes.c_uint32, ctypes.c_double] + [ctypes.POINTER(ctypes.c_void_p)] * 4),
+    "svjg_genotype_ploidy": (ctypes.c_int, [ctypes.c_void_p] * 5 + [ctypes.c_uint64, ctypes.c_uint32, ctypes.c_double] + [ctypes.c_void_p] * 5),
     "svjg_set_rows": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64]),
     "svjg_run_resident": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_uint64, ctypes.c_uint32, ctypes.c_double] + [ctypes.POINTER(ctypes.c_void_p)] * 5),
     "svjg_run_begin": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_uint64, ctypes.c_uint32, ctypes.c_double]),
@@ -97,6 +98,7 @@ _SIGS = {
 EXPORTS = tuple(_SIGS) + ("svjg_write_informative_json", "svjg_count_informative_json", "svjg_host_free",
                           "svjg_graph_load", "svjg_graph_view", "svjg_graph_info", "svjg_graph_free",
                           "svjg_vcf_load", "svjg_vcf_arrays", "svjg_vcf_write", "svjg_vcf_free")
+MAX_PLOIDY = 8                      # svjg.h: SVJG_MAX_PLOIDY
 _lib = None
 _host_lib = None
 
@@ -465,6 +467,28 @@ class Context:
         self._chk(self.lib.svjg_genotype(self.h, sv_type.ctypes.data, slot.ctypes.data, ok.ctypes.data, n, min_support,
                                          float(err), gt.ctypes.data, pl.ctypes.data, raw.ctypes.data, done.ctypes.data))
         return gt, pl, raw, done
+
+    def genotype_ploidy(self, sv_type, slot, ok, ploidy, min_support, err):
+        """Any ploidy from 1 to MAX_PLOIDY per row (svjg_genotype_ploidy; ploidy 0: the row is never genotyped).
+        -> (gt = alt copies or 0xFF, pl[n, 9] = PL_0..PL_P then zeros, raw[n, 2], genotyped, boundary = the rows to recompute with
+        svjg.genotype.exact_pl_ploidy)"""
+        n = len(sv_type)
+        sv_type = np.ascontiguousarray(sv_type, dtype=np.uint8)
+        slot = np.ascontiguousarray(slot, dtype=np.uint32)
+        ok = np.ascontiguousarray(ok, dtype=np.uint8)
+        ploidy = np.asarray(ploidy)
+        if n and (len(ploidy) != n or int(ploidy.min()) < 0 or int(ploidy.max()) > 255):
+            raise SvjgError("ploidy: one value in 0..%d per row" % MAX_PLOIDY)
+        ploidy = np.ascontiguousarray(ploidy, dtype=np.uint8)
+        gt = np.empty(n, dtype=np.uint8)
+        pl = np.empty((n, MAX_PLOIDY + 1), dtype=np.int64)
+        raw = np.empty((n, 2), dtype=np.uint32)
+        done = np.empty(n, dtype=np.uint8)
+        boundary = np.empty(n, dtype=np.uint8)
+        self._chk(self.lib.svjg_genotype_ploidy(self.h, sv_type.ctypes.data, slot.ctypes.data, ok.ctypes.data, ploidy.ctypes.data, n,
+                                                min_support, float(err), gt.ctypes.data, pl.ctypes.data, raw.ctypes.data,
+                                                done.ctypes.data, boundary.ctypes.data))
+        return gt, pl, raw, done, boundary
 
     def set_rows(self, sv_type, slot, ok):
         """the VCF rows' input arrays of genotype(), left on the device for run_resident()"""

@@ -58,6 +58,7 @@ class VcfRows:
     def __init__(self, vcf_path, slot_of, slot_is_presence=False):
         self.items = []          # ("h", text) or ("r", row index)
         self.prefix = []         # text before "\tGT:DP:AD:PL" for each data row
+        self.chrom, self.pos = [], []   # CHROM and POS text of each data row (the ploidy file is matched against them)
         types, slots, oks = [], [], []
         ins_seen = {}
         with open(vcf_path) as fh:
@@ -81,6 +82,8 @@ class VcfRows:
                 # the first eight columns as they stand (columns 1..8 cannot hold the terminator, so the split of the
                 # stripped line has the same first eight as the reference's split of the raw one)
                 self.prefix.append(text if len(cols) <= 8 else "\t".join(cols[:8]))
+                self.chrom.append(chrom)
+                self.pos.append(pos)
                 self.items.append(("r", len(types) - 1))
         self.sv_type = np.array(types, dtype=np.uint8)
         self.slot = np.array(slots, dtype=np.uint32)
@@ -178,6 +181,158 @@ def apply_boundary_guard(ctx, rows, pl, raw, done, err):
     return pl, len(idx)
 
 
+# ---- any ploidy from 1 to 8 (--ploidy / --ploidy-file): svjg_genotype_ploidy, Python rows and the writer below ----
+
+MAX_PLOIDY = 8
+NO_CALL = 0xFF
+_PL_3 = "##FORMAT=<ID=PL,Number=3,"
+_PL_G = "##FORMAT=<ID=PL,Number=G,"
+
+
+def exact_pl_ploidy(svtype_code, ref, alt, ploidy, err):
+    """The ploidy + 1 PL integers of one row, PL_g for g = 0..ploidy alt copies, with the reference's arithmetic generalised: a read
+    shows the alt allele with probability (g (1 - e) + (P - g) e) / P.  g = 0 and g = P are the reference's lik0 and lik2, 2 g = P its
+    lik1 (one product); at ploidy 2 this is exact_pl.  For the rows svjg_genotype_ploidy flags."""
+    import math
+    from decimal import Decimal, localcontext
+    P = int(ploidy)
+    if not 1 <= P <= MAX_PLOIDY:
+        raise ValueError("ploidy %r is not in 1..%d" % (ploidy, MAX_PLOIDY))
+    c1, c2 = ref, alt
+    if svtype_code == 0 and ref > 0:
+        c1 = round(ref / 2, 1)
+    elif svtype_code == 1 and alt > 0:
+        c2 = round(alt / 2, 1)
+    rc1, rc2 = int(round(c1, 0)), int(round(c2, 0))
+    with localcontext() as ctx:
+        ctx.prec = 28
+        comb = Decimal(_log10_comb(rc1 + rc2, rc1))
+        out = []
+        for g in range(P + 1):
+            if g == 0:
+                lik = Decimal(c1 * math.log10(1 - err)) + Decimal(c2 * math.log10(err))
+            elif g == P:
+                lik = Decimal(c2 * math.log10(1 - err)) + Decimal(c1 * math.log10(err))
+            elif 2 * g == P:
+                lik = Decimal((c1 + c2) * math.log10(1 / 2))
+            else:
+                l_ref = math.log10(((P - g) * (1 - err) + g * err) / P)
+                l_alt = math.log10((g * (1 - err) + (P - g) * err) / P)
+                lik = Decimal(c1 * l_ref) + Decimal(c2 * l_alt)
+            out.append(int(-10 * (lik + comb)))
+        return out
+
+
+def _plain_int(text):
+    if not (text.isascii() and text.isdigit()):
+        raise ValueError
+    return int(text)
+
+
+def load_ploidy_file(path):
+    """-> [(chrom, from, to, ploidy)] in file order; from = to = None for a whole-chromosome line.  Lines: `CHROM PLOIDY` or
+    `CHROM FROM TO PLOIDY`, separated by tabs or blanks, coordinates 1-based and inclusive; `#` lines and empty lines are skipped.
+    ValueError for anything else, and for a ploidy outside 0..8."""
+    regions = []
+    with open(path) as fh:
+        for no, line in enumerate(fh, 1):
+            f = line.split()
+            if not f or f[0].startswith("#"):
+                continue
+            try:
+                if len(f) == 2:
+                    lo = hi = None
+                elif len(f) == 4:
+                    lo, hi = _plain_int(f[1]), _plain_int(f[2])
+                    if lo < 1 or hi < lo:
+                        raise ValueError
+                else:
+                    raise ValueError
+                p = _plain_int(f[-1])
+            except ValueError:
+                raise ValueError("%s:%d: expected `CHROM PLOIDY` or `CHROM FROM TO PLOIDY`: %r" % (path, no, line.rstrip("\n"))) from None
+            if p > MAX_PLOIDY:
+                raise ValueError("%s:%d: ploidy %d is not in 0..%d" % (path, no, p, MAX_PLOIDY))
+            regions.append((f[0], lo, hi, p))
+    return regions
+
+
+def rows_ploidy(rows, ploidy=None, regions=()):
+    """the ploidy of every data row of a VcfRows: the first line of the ploidy file that matches its CHROM (and, for a region line, its POS when
+    that is a plain decimal), else `ploidy`, else 2"""
+    default = 2 if ploidy is None else int(ploidy)
+    if not 1 <= default <= MAX_PLOIDY:
+        raise ValueError("ploidy %r is not in 1..%d" % (ploidy, MAX_PLOIDY))
+    by_chrom = {}
+    for chrom, lo, hi, p in regions:
+        by_chrom.setdefault(chrom, []).append((lo, hi, p))
+    out = np.full(len(rows.chrom), default, dtype=np.uint8)
+    if by_chrom:
+        for r, (chrom, pos) in enumerate(zip(rows.chrom, rows.pos)):
+            lines = by_chrom.get(chrom)
+            if not lines:
+                continue
+            at = int(pos) if pos.isascii() and pos.isdigit() else None
+            for lo, hi, p in lines:
+                if lo is None or (at is not None and lo <= at <= hi):
+                    out[r] = p
+                    break
+    return out
+
+
+def gt_text_ploidy(P, g):
+    """GT of g alt copies out of P: (P - g) zeros then g ones joined by `/`; a no-call: P dots"""
+    if g == NO_CALL:
+        return "/".join("." * P)
+    return "/".join("0" * (P - g) + "1" * g)
+
+
+def write_vcf_ploidy(out_path, rows, ploidy, gt, pl, raw, done):
+    """write_vcf for rows of any ploidy: P + 1 PLs per row, `Number=G` in the PL header line; a ploidy-0 row prints `.:0:0,0:.`"""
+    n_done = 0
+    with open(out_path, "w") as out:
+        for kind, v in rows.items:
+            if kind == "h":
+                out.write(v.replace(_PL_3, _PL_G) if v is FORMAT_HEADER else v)
+                continue
+            P = int(ploidy[v])
+            if P == 0:
+                tail = ".:0:0,0:."
+            elif done[v]:
+                n_done += 1
+                dp, ad = _fmt_counts(int(rows.sv_type[v]), int(raw[v, 0]), int(raw[v, 1]))
+                tail = "%s:%s:%s:%s" % (gt_text_ploidy(P, int(gt[v])), dp, ad, ",".join(str(int(x)) for x in pl[v, :P + 1]))
+            else:
+                tail = "%s:0:0,0:%s" % ("/".join("." * P), ",".join("." * (P + 1)))
+            out.write(rows.prefix[v] + "\tGT:DP:AD:PL\t" + tail + "\n")
+    return n_done
+
+
+def apply_boundary_guard_ploidy(rows, ploidy, pl, raw, done, boundary, err):
+    """-> pl with the flagged rows recomputed by exact_pl_ploidy, number of flagged rows"""
+    idx = np.flatnonzero((np.asarray(boundary) != 0) & (np.asarray(done) != 0))
+    for r in idx:
+        P = int(ploidy[r])
+        pl[r, :P + 1] = exact_pl_ploidy(int(rows.sv_type[r]), int(raw[r, 0]), int(raw[r, 1]), P, err)
+    return pl, len(idx)
+
+
+def genotype_with_counts_ploidy(ctx, vcf_path, slot_of, out_path, min_support, err, slot_is_presence, ploidy, ploidy_file):
+    """genotype_with_counts with --ploidy and / or --ploidy-file: the Python rows, svjg_genotype_ploidy, the writer above"""
+    regions = load_ploidy_file(ploidy_file) if ploidy_file is not None else ()       # (raises before any output exists)
+    if not isinstance(slot_of, dict):
+        slot_of = {k: i for i, k in enumerate(slot_of)}
+    rows = VcfRows(vcf_path, slot_of, slot_is_presence)
+    pld = rows_ploidy(rows, ploidy, regions)
+    min_support = max(0, int(min_support))
+    bad_err = not (0.0 < float(err) < 1.0)
+    gt, pl, raw, done, boundary = ctx.genotype_ploidy(rows.sv_type, rows.slot, rows.ok, pld, min_support, 0.5 if bad_err else err)
+    if bad_err and done.any():
+        raise ValueError("math domain error")
+    pl, _ = apply_boundary_guard_ploidy(rows, pld, pl, raw, done, boundary, err)
+    return write_vcf_ploidy(out_path, rows, pld, gt, pl, raw, done)
+
+
 def write_vcf(out_path, rows, gt, pl, raw, done):
     n_done = 0
     with open(out_path, "w") as out:
@@ -214,8 +369,11 @@ def open_rows(vcf_path, slot_of, slot_is_presence=False):
     return VcfRows(vcf_path, slot_of, slot_is_presence)
 
 
-def genotype_with_counts(ctx, vcf_path, slot_of, out_path, min_support=3, err=0.00005, slot_is_presence=False):
-    """Counts already live in the context (fused path, or set_counts): parse, run the kernel, write."""
+def genotype_with_counts(ctx, vcf_path, slot_of, out_path, min_support=3, err=0.00005, slot_is_presence=False, ploidy=None, ploidy_file=None):
+    """Counts already live in the context (fused path, or set_counts): parse, run the kernel, write.  ploidy (1..8, every row) and / or
+    ploidy_file (per contig or region, load_ploidy_file): genotype_with_counts_ploidy; with neither, the diploid path below."""
+    if ploidy is not None or ploidy_file is not None:
+        return genotype_with_counts_ploidy(ctx, vcf_path, slot_of, out_path, min_support, err, slot_is_presence, ploidy, ploidy_file)
     rows = open_rows(vcf_path, slot_of, slot_is_presence)
     min_support = max(0, int(min_support))                       # (a negative threshold: `sum(nbAln) >= minNbAln` always holds, predict-genotype.py:310)
     bad_err = not (0.0 < float(err) < 1.0)                       # math.log10(e) / math.log10(1 - e) raise in likelihood(), i.e. only once a row gets there
@@ -231,7 +389,7 @@ def genotype_with_counts(ctx, vcf_path, slot_of, out_path, min_support=3, err=0.
         rows.close()
 
 
-def run(json_path, vcf_path, out_path, min_support=3, err=0.00005, device=0):
+def run(json_path, vcf_path, out_path, min_support=3, err=0.00005, device=0, ploidy=None, ploidy_file=None):
     """predict-genotype.py main(): counts come from the informative-alignment JSON."""
     from . import capi, filter as flt
     got = flt.read_handoff(json_path)                            # left by our filter-alignments.py for exactly this file, else None
@@ -242,7 +400,7 @@ def run(json_path, vcf_path, out_path, min_support=3, err=0.00005, device=0):
     try:
         ctx.alloc_counts(len(keys))
         ctx.set_counts(counts)
-        n = genotype_with_counts(ctx, vcf_path, list(keys), out_path, min_support, err, slot_is_presence=True)
+        n = genotype_with_counts(ctx, vcf_path, list(keys), out_path, min_support, err, slot_is_presence=True, ploidy=ploidy, ploidy_file=ploidy_file)
     finally:
         ctx.close()
     print("Genotyped svs: " + str(n))
