@@ -233,6 +233,24 @@ int svjg_genotype_ploidy(svjg_ctx *ctx, const uint8_t *sv_type, const uint32_t *
                          uint64_t n_rows, uint32_t min_support, double err,
                          uint8_t *gt, int64_t *pl, uint32_t *raw, uint8_t *genotyped, uint8_t *boundary);
 
+/* Insertions that share a CHROM and POS, genotyped together (diploid; --joint-ins).  A site has K = 2..SVJG_MAX_SITE_ALTS members; slots holds
+ * SVJG_MAX_SITE_ALTS count slots per site, the members first, 0xFFFFFFFF behind them.  Allele 0 is the reference, allele j the j-th member;
+ * c_0 = the largest raw ref count of the members, c_j = alt_j / 2, N their sum.  The genotypes {a, b}, 0 <= a <= b <= K, in VCF order
+ * b (b + 1) / 2 + a: a read shows an allele with probability q(.|a) / 2 + q(.|b) / 2, q = 1 - e for the haplotype's own allele and e / K for each
+ * other one, i.e. lik = c_a log10(1 - e) + (N - c_a) log10(e / K) for a = b and (c_a + c_b) log10(((1 - e) + e / K) / 2) + (N - c_a - c_b) log10(e / K)
+ * for a < b; the coefficient term is the chain of binomial terms log10 comb(s_j, r_j) over the rounded counts, s_j = r_0 + .. + r_j.  At K = 1
+ * this is the reference's likelihood().  Outputs per site: gt[2] = the pair (a, b) that alone attains the maximum, 0xFF, 0xFF on a tie or when
+ * N is below min_support; pl[SVJG_SITE_GENOTYPES] = the PLs in that order, 0 beyond the site's (K + 1)(K + 2) / 2; raw[7] = the ref maximum and
+ * alt_1..alt_6; boundary = 1 where one of the values lies within 2.5e-6 of an integer or s_K >= 2^24: recompute such sites with
+ * svjedi-graph_amd/svjg/genotype.py: exact_pl_site.  The call neither reads nor changes what svjg_genotype_view and svjg_genotype_boundary hand
+ * out.  n_sites = 0 returns 0.  SVJG_E_ARG, all found before any launch: a site with fewer than two members, a hole in front of a member, a slot
+ * out of range, a slot twice in one site, a null array, no counts yet.  svjg_last_kernel_ms reports the kernel's time as genotype_ms; no timing
+ * of this kernel has been measured beyond the first reading recorded with the change that added it. */
+#define SVJG_MAX_SITE_ALTS 6
+#define SVJG_SITE_GENOTYPES 28
+int svjg_genotype_sites(svjg_ctx *ctx, const uint32_t *slots, uint64_t n_sites, uint32_t min_support, double err,
+                        uint8_t *gt, int64_t *pl, uint32_t *raw, uint8_t *boundary);
+
 /* ---- the whole pass in one call (what a fused svjedi-graph run and bench.py do per batch) -----------------------------------
  * svjg_set_rows copies the three per-row input arrays of svjg_genotype to the device once (they stay until the next
  * svjg_set_rows / svjg_destroy).  svjg_run_resident then does, for the resident text of svjg_gaf_upload and those rows:

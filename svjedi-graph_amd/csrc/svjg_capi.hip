@@ -117,6 +117,8 @@ struct svjg_ctx {
     uint64_t geno_rows = 0;                              // rows of the last svjg_genotype / svjg_genotype_view (svjg_genotype_boundary)
     void *d_prows = nullptr;  uint64_t prows_cap = 0;    // svjg_genotype_ploidy's own block and pinned twin (ploidy_layout): the views and the
     void *h_prows = nullptr;  uint64_t h_prows_cap = 0;  // boundary bytes of the calls above stay as they are
+    void *d_srows = nullptr;  uint64_t srows_cap = 0;    // svjg_genotype_sites' own block and pinned twin (sites_layout), for the same reason
+    void *h_srows = nullptr;  uint64_t h_srows_cap = 0;
     // resident VCF rows of svjg_set_rows / svjg_run_resident: device block (results, row inputs) and the pinned host block the results land in
     struct RunSlot {
         void *d = nullptr;  uint64_t d_cap = 0;  void *h = nullptr;  uint64_t h_cap = 0;  void *h_dev = nullptr;   // h_dev: the pinned block as the device sees it
@@ -209,7 +211,7 @@ extern "C" void svjg_destroy(svjg_ctx *c) {
     free_graph(c);
     hipFree(c->d_long);
     hipFree(c->d_gaf); hipFree(c->d_deferred); hipFree(c->d_recs); hipFree(c->d_host); hipFree(c->d_st); hipFree(c->d_logfact);
-    hipFree(c->d_bsum); hipFree(c->d_rows); hipFree(c->d_prows); hipFree(c->d_run_in);
+    hipFree(c->d_bsum); hipFree(c->d_rows); hipFree(c->d_prows); hipFree(c->d_srows); hipFree(c->d_run_in);
     for (auto &r : c->run) {
         hipFree(r.d); hipFree(r.counts);
         if (r.h) hipHostFree(r.h);
@@ -219,6 +221,7 @@ extern "C" void svjg_destroy(svjg_ctx *c) {
     }
     if (c->h_rows) hipHostFree(c->h_rows);
     if (c->h_prows) hipHostFree(c->h_prows);
+    if (c->h_srows) hipHostFree(c->h_srows);
     if (c->h_stp) hipHostFree(c->h_stp);
     for (auto &b : c->h_stage) if (b) hipHostFree(b);
     for (auto &ev : c->stage_ev) if (ev) hipEventDestroy(ev);
@@ -949,8 +952,9 @@ static int launch_genotype(svjg_ctx *c, GenoArgs &a, const uint8_t *ploidy = nul
 // the log10(i!) table.  Only then (first call, or a deeper sample than ever before) the table is rebuilt, the rows run again, `bytes` from
 // d_back come back to h_back (what the caller reads, the pair included) and the check repeats.  relaunch_first: the launch itself is still
 // owed (svjg_run_end behind a repeated pass).  max_n is the maximum over ALL rows, so one growth is enough; the second only guards this reasoning.
-static int settle_genotype(svjg_ctx *c, GenoArgs &a, const unsigned int *h_maxn, void *h_back, const void *d_back, uint64_t bytes, bool relaunch_first,
-                           const uint8_t *ploidy = nullptr, const double *logtab = nullptr) {
+// launch(): the kernel over all its items again with the table at hand (launch_genotype for the rows, launch_sites for svjg_genotype_sites).
+template <class Launch>
+static int settle_launch(svjg_ctx *c, const unsigned int *h_maxn, void *h_back, const void *d_back, uint64_t bytes, bool relaunch_first, Launch launch) {
     for (int growths = 0;; relaunch_first = false) {
         if (!relaunch_first) {
             if (h_maxn[1]) { c->err = "slot out of range"; return SVJG_E_ARG; }   // (checked by the kernel, row by row)
@@ -960,10 +964,14 @@ static int settle_genotype(svjg_ctx *c, GenoArgs &a, const unsigned int *h_maxn,
             if (c->copy_stream) HIPCHK(c, hipStreamSynchronize(c->copy_stream));
             if (const int rc = build_logfact(c, logfact_grow_to(h_maxn[0]))) return rc;
         }
-        if (const int rc = launch_genotype(c, a, ploidy, logtab)) return rc;
+        if (const int rc = launch()) return rc;
         HIPCHK(c, hipMemcpyAsync(h_back, d_back, bytes, hipMemcpyDeviceToHost, c->stream));
         HIPCHK(c, hipStreamSynchronize(c->stream));
     }
+}
+static int settle_genotype(svjg_ctx *c, GenoArgs &a, const unsigned int *h_maxn, void *h_back, const void *d_back, uint64_t bytes, bool relaunch_first,
+                           const uint8_t *ploidy = nullptr, const double *logtab = nullptr) {
+    return settle_launch(c, h_maxn, h_back, d_back, bytes, relaunch_first, [&] { return launch_genotype(c, a, ploidy, logtab); });
 }
 
 // results of all rows -> the pinned host block of the context (rows_layout)
@@ -1056,6 +1064,63 @@ extern "C" int svjg_genotype_ploidy(svjg_ctx *c, const uint8_t *sv_type, const u
     HIPCHK(c, hipEventElapsedTime(&c->ms_geno, c->ev[4], c->ev[5]));
     memcpy(pl, hb + L.pl, n_rows * (MAX_PLOIDY + 1) * sizeof *pl); memcpy(raw, hb + L.raw, n_rows * 2 * sizeof *raw);
     memcpy(gt, hb + L.gt, n_rows); memcpy(genotyped, hb + L.flags, n_rows); memcpy(boundary, hb + L.boundary, n_rows);
+    return 0;
+}
+
+// Insertions that share a position, genotyped together (k_genotype_sites; svjg.h): the same leg once more — one copy in (the call's logarithms
+// and the sites' slots), one kernel, one copy out, settled like the rows — in a block of its own, so that the views and the boundary bytes of
+// the calls above stay as they are.  Everything a caller can get wrong is found here, before any launch.
+static int launch_sites(svjg_ctx *c, GenoSitesArgs &a) {
+    a.logfact = c->d_logfact; a.logfact_n = c->logfact_n;
+    HIPCHK(c, hipMemsetAsync(a.max_n, 0, 8, c->stream));
+    hipLaunchKernelGGL(k_genotype_sites, dim3(capped_grid(a.n_sites)), dim3(TPB), 0, c->stream, a);
+    HIPCHK(c, hipGetLastError());
+    return 0;
+}
+
+extern "C" int svjg_genotype_sites(svjg_ctx *c, const uint32_t *slots, uint64_t n_sites, uint32_t min_support, double err,
+                                   uint8_t *gt, int64_t *pl, uint32_t *raw, uint8_t *boundary) {
+    static_assert(SVJG_MAX_SITE_ALTS == MAX_SITE_ALTS && SVJG_SITE_GENOTYPES == SITE_GENOTYPES, "svjg.h and svjg_geno.h disagree");
+    if (!c || !c->have_counts) return SVJG_E_ARG;
+    if (n_sites == 0) return 0;
+    if (!slots || !gt || !pl || !raw || !boundary) return SVJG_E_ARG;
+    for (uint64_t s = 0; s < n_sites; ++s) {
+        const uint32_t *m = slots + s * MAX_SITE_ALTS;
+        uint32_t K = 0;
+        for (uint32_t j = 0; j < MAX_SITE_ALTS; ++j) {
+            if (m[j] == NONE32) continue;
+            if (j != K) { c->err = "site with a hole in front of a member"; return SVJG_E_ARG; }
+            if (m[j] >= c->n_slots) { c->err = "slot out of range"; return SVJG_E_ARG; }
+            for (uint32_t i = 0; i < j; ++i) if (m[i] == m[j]) { c->err = "slot twice in one site"; return SVJG_E_ARG; }
+            ++K;
+        }
+        if (K < 2) { c->err = "site with fewer than two members"; return SVJG_E_ARG; }
+    }
+    HIPCHK(c, hipSetDevice(c->device));
+    { const int rc0 = fetch_slot_counts(c); if (rc0) return rc0; }
+    const SitesLayout L = sites_layout(n_sites);
+    int rc;
+    if ((rc = ensure(c, &c->d_srows, &c->srows_cap, L.total, 1, false))) return rc;
+    if ((rc = ensure_pinned(c, &c->h_srows, &c->h_srows_cap, L.total, hipHostMallocDefault))) return rc;
+    uint8_t *base = (uint8_t *)c->d_srows, *hb = (uint8_t *)c->h_srows;
+    site_log_table(err, (double *)(hb + L.logs));                // host libm, as geno_args' three
+    memcpy(hb + L.slots, slots, n_sites * MAX_SITE_ALTS * 4);
+    HIPCHK(c, hipMemcpyAsync(base + L.logs, hb + L.logs, L.in_bytes, hipMemcpyHostToDevice, c->stream));
+    GenoSitesArgs a{};
+    a.counts = c->d_counts; a.n_slots = c->n_slots; a.slots = (const uint32_t *)(base + L.slots); a.n_sites = n_sites; a.min_support = min_support;
+    a.logs = (const double *)(base + L.logs);
+    a.pl = (int64_t *)(base + L.pl); a.raw = (uint32_t *)(base + L.raw); a.gt = base + L.gt; a.boundary = base + L.boundary;
+    a.max_n = (unsigned int *)(base + L.maxn);
+    HIPCHK(c, hipEventRecord(c->ev[4], c->stream));
+    if (c->logfact_n == 0 && (rc = build_logfact(c, logfact_first()))) return rc;
+    if ((rc = launch_sites(c, a))) return rc;
+    HIPCHK(c, hipEventRecord(c->ev[5], c->stream));
+    HIPCHK(c, hipMemcpyAsync(hb, base, L.maxn + 8, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    if ((rc = settle_launch(c, (const unsigned int *)(hb + L.maxn), hb, base, L.maxn + 8, false, [&] { return launch_sites(c, a); }))) return rc;
+    HIPCHK(c, hipEventElapsedTime(&c->ms_geno, c->ev[4], c->ev[5]));
+    memcpy(pl, hb + L.pl, n_sites * SITE_GENOTYPES * sizeof *pl); memcpy(raw, hb + L.raw, n_sites * (MAX_SITE_ALTS + 1) * sizeof *raw);
+    memcpy(gt, hb + L.gt, n_sites * 2); memcpy(boundary, hb + L.boundary, n_sites);
     return 0;
 }
 

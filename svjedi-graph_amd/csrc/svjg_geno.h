@@ -192,6 +192,113 @@ SVJG_HD uint32_t geno_row_ploidy(uint32_t type, uint32_t ref, uint32_t alt, uint
     return st;
 }
 
+// ---- insertions that share a position, genotyped together (k_genotype_sites; diploid) ----
+// A site has K = 2..MAX_SITE_ALTS insertions at one CHROM and POS; allele 0 is the reference, allele j the j-th insertion.  Counts: c_0 = the
+// largest raw ref count of the members (they share the one reference link), c_j = alt_j / 2 (the reference's INS normalisation), N their sum.
+// Genotypes {a, b}, 0 <= a <= b <= K, in VCF order b (b + 1) / 2 + a.  A read shows an allele with probability q(.|a) / 2 + q(.|b) / 2, q = 1 - e
+// for the haplotype's own allele and e / K for every other one:
+//     a == b   lik = c_a * L_ok + (N - c_a) * L_x                      L_ok = log10(1 - e), L_x = log10(e / K)
+//     a <  b   lik = (c_a + c_b) * L_he + (N - c_a - c_b) * L_x        L_he = log10(((1 - e) + e / K) / 2)
+// two double products and one exact sum each, like lik0 / lik2.  The coefficient term is a chain of the reference's binomial terms over the
+// rounded counts r_j: s_0 = r_0, s_j = s_(j-1) + r_j, T = sum of log10 comb(s_j, r_j), each term rounded to a double before it is added (the
+// host model adds Decimal(math.log10(math.comb(s_j, r_j)))).  PL_ab = int(-10 (lik_ab + T)).
+constexpr uint32_t MAX_SITE_ALTS = 6;
+constexpr uint32_t SITE_GENOTYPES = (MAX_SITE_ALTS + 1) * (MAX_SITE_ALTS + 2) / 2;       // 28
+constexpr uint8_t SITE_NO_CALL = 0xFF;
+
+// A site is flagged when one of its -10 (lik + T) lies within SITE_PL_GUARD of an integer.  PL_GUARD's budget above bounds what ONE binomial
+// term can disagree by between the table and the reference's log10 of the big integer, times ten: 3.6e-7.  T has up to MAX_SITE_ALTS such terms
+// (every index is at most s_K < LOGFACT_CAP, so each term is within that budget), their roundings to doubles are part of it, and the sums are
+// exact on both sides: 6 x 3.6e-7 = 2.16e-6 < 2.5e-6.
+constexpr double SITE_PL_GUARD = 2.5e-6;
+
+// The logarithms of a call by the host's libm, in exactly the written order: tab[0] = L_ok, tab[K] = L_x[K], tab[8 + K] = L_he[K], K = 1..6
+constexpr uint32_t SITE_LOGS = 16;
+inline void site_log_table(double err, double *tab) {
+    for (uint32_t i = 0; i < SITE_LOGS; ++i) tab[i] = 0.0;
+    tab[0] = log10(1.0 - err);
+    for (uint32_t K = 1; K <= MAX_SITE_ALTS; ++K) {
+        const double k = (double)K, x = err / k, ok = 1.0 - err;
+        tab[K] = log10(x);
+        tab[8 + K] = log10((ok + x) / 2.0);
+    }
+}
+
+struct GenoSite {
+    uint8_t a, b;    // the call, a <= b; SITE_NO_CALL, SITE_NO_CALL: a tie or below min_support
+    bool near;       // one of the site's values lies within SITE_PL_GUARD of an integer, or the site is beyond the table's cap: the host recomputes it
+    uint64_t n;      // s_K
+};
+
+// One site of K in 2..MAX_SITE_ALTS members: ref = the raw ref maximum, alt[0..K) the raw alt counts (entries beyond K are not read).  pl:
+// SITE_GENOTYPES integers, written as they are produced (the kernel hands in the site's place in global memory), 0 beyond the site's
+// (K + 1)(K + 2) / 2.  Status and flag as geno_row.  Both loops are unrolled under a predicate: c[] and r[] are only ever indexed by constants.
+SVJG_HD uint32_t geno_site(uint32_t K, uint32_t ref, const uint32_t *alt, uint32_t min_support, double l_ok, double l_x, double l_he,
+                           const dd *logfact, uint32_t logfact_n, int64_t *pl, GenoSite &o) {
+#ifdef __clang__
+#pragma clang fp contract(off)                           // the products are rounded to doubles before the exact sums
+#endif
+    double c[MAX_SITE_ALTS + 1]; uint32_t r[MAX_SITE_ALTS + 1];
+    c[0] = (double)ref; r[0] = ref;
+    double N = c[0];
+    uint64_t s_K = ref;
+    bool table = false;                                  // a chain term is not log10(1)
+    SVJG_UNROLL
+    for (uint32_t j = 1; j <= MAX_SITE_ALTS; ++j) {
+        c[j] = 0.0; r[j] = 0;
+        if (j > K) continue;
+        const uint32_t v = alt[j - 1];
+        c[j] = (double)v * 0.5;                          // round(x / 2, 1) is exact for halves (0 stays 0)
+        r[j] = (uint32_t)rint(c[j]);                     // int(round(c, 0)): half to even
+        N += c[j];                                       // (halves below 2^36: exact)
+        if (r[j] && s_K) table = true;
+        s_K += r[j];
+    }
+    o.n = s_K;
+    uint32_t st = GENO_ROW_OK;
+    dd T{0.0, 0.0};
+    if (table) {
+        if (s_K < logfact_n) {
+            uint32_t s = r[0];
+            SVJG_UNROLL
+            for (uint32_t j = 1; j <= MAX_SITE_ALTS; ++j) {
+                if (j > K) continue;
+                const uint32_t t = s + r[j];             // <= s_K < logfact_n: every index below is inside the table
+                if (r[j] && s) {
+                    const dd term = dd_add(dd_add(logfact[t], dd_neg(logfact[s])), dd_neg(logfact[r[j]]));
+                    T = dd_add(T, dd{term.hi, 0.0});     // each term rounded to a double first, like the model's Decimal(math.log10(...))
+                }
+                s = t;
+            }
+        } else st = s_K < LOGFACT_CAP ? GENO_ROW_GROW : GENO_ROW_HOST;
+    }
+    const bool guard = T.hi != 0.0;                      // (T = 0 on both sides: nothing to disagree about)
+    dd best{0.0, 0.0}; uint8_t best_a = SITE_NO_CALL, best_b = SITE_NO_CALL; bool tie = false, near = false;
+    SVJG_UNROLL
+    for (uint32_t b = 0; b <= MAX_SITE_ALTS; ++b) {
+        SVJG_UNROLL
+        for (uint32_t a = 0; a <= b; ++a) {
+            const uint32_t at = b * (b + 1) / 2 + a;
+            if (b > K) { pl[at] = 0; continue; }
+            const double own = a == b ? c[a] : c[a] + c[b];
+            const double rest = a == b ? N - c[a] : N - c[a] - c[b];
+            const double p1 = own * (a == b ? l_ok : l_he), p2 = rest * l_x;
+            const dd l = two_sum(p1, p2);
+            const int cmp = at ? dd_cmp(l, best) : 1;
+            if (cmp > 0) { best = l; best_a = (uint8_t)a; best_b = (uint8_t)b; tie = false; } else if (cmp == 0) tie = true;
+            dd s = dd_add(l, T);
+            dd p = dd_add(dd_add(dd_add(s, s), dd_add(s, s)), s);             // 5 s
+            p = dd_add(p, p);                                                 // 10 s
+            pl[at] = trunc_dd(dd_neg(p));
+            { const double fr = fabs((p.hi - rint(p.hi)) + p.lo); if (fr < SITE_PL_GUARD && guard) near = true; }   // (as geno_row)
+        }
+    }
+    if (tie || !(N >= (double)min_support)) best_a = best_b = SITE_NO_CALL;
+    o.a = best_a; o.b = best_b;
+    o.near = near || st == GENO_ROW_HOST;
+    return st;
+}
+
 // ---- host side of a k_genotype launch: the table's size and where a call's rows lie, in plain integers (pinned without a GPU: tests/test_rows_layout.py) ----
 
 // entries of the log10(i!) table: the first one built; the one that holds max_n (the largest n the kernel met beyond the table, < LOGFACT_CAP) with room to spare
@@ -220,6 +327,17 @@ inline PloidyLayout ploidy_layout(uint64_t n) {
     L.pl = o; o += n * 8 * (MAX_PLOIDY + 1); L.raw = o; o += n * 8; L.gt = o; o += n; L.flags = o; o += n; L.boundary = o; o += n;
     L.maxn = (o + 7) & ~7ull; L.logtab = L.maxn + 8; L.in = rows_in(n, L.logtab + 2 * PLOIDY_TAB * 8);
     L.ploidy = L.in.slot + L.in.bytes; L.in_bytes = 2 * PLOIDY_TAB * 8 + L.in.bytes + n; L.total = L.logtab + L.in_bytes + 64;
+    return L;
+}
+
+// joint-insertion leg (svjg_genotype_sites): a block of its own again, [ pl 224 | raw 28 | gt 2 | boundary 1 ] x n, the max_n pair, then ONE copy
+// in: the call's logarithms (site_log_table) and the sites' slots
+struct SitesLayout { uint64_t pl, raw, gt, boundary, maxn, logs, slots, in_bytes, total; };
+inline SitesLayout sites_layout(uint64_t n) {
+    SitesLayout L; uint64_t o = 0;
+    L.pl = o; o += n * 8 * SITE_GENOTYPES; L.raw = o; o += n * 4 * (MAX_SITE_ALTS + 1); L.gt = o; o += n * 2; L.boundary = o; o += n;
+    L.maxn = (o + 7) & ~7ull; L.logs = L.maxn + 8; L.slots = L.logs + SITE_LOGS * 8;
+    L.in_bytes = SITE_LOGS * 8 + n * 4 * MAX_SITE_ALTS; L.total = L.logs + L.in_bytes + 64;
     return L;
 }
 

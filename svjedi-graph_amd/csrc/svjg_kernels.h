@@ -11,6 +11,7 @@
 //   k_step_reset     that reset alone, for a fused pass with no pass in front of it
 //   k_logfact_*      log10(i!) table in double-double for the binomial term
 //   k_genotype       one VCF row per lane, fp64 / double-double likelihoods (predict-genotype.py:281-325)
+//   k_genotype_sites one site of insertions that share a position per lane, the same arithmetic over (K + 1)(K + 2) / 2 genotypes
 #pragma once
 #include <hip/hip_runtime.h>
 #define SVJG_TAB_AS __attribute__((address_space(3)))      // the exact routine's per-node scratch and piece tables are LDS arrays here (svjg_line.h)
@@ -2001,6 +2002,61 @@ __global__ __launch_bounds__(TPB) void k_genotype_ploidy(GenoPloidyArgs p) {
 #pragma unroll
     for (uint32_t i = 0; i < NPL; ++i) a.pl[r * NPL + i] = o.pl[i];
     if (o.near) a.boundary[r] = 1;
+  }
+}
+
+// Insertions that share a position, genotyped together (svjg_geno.h: geno_site).  slots: MAX_SITE_ALTS count slots per site, the members
+// first, NONE32 behind them (the host has checked them: 2..6 members, no hole, in range, none twice).  Outputs per site: gt[2] = the pair
+// (a, b) or 0xFF, 0xFF; pl[SITE_GENOTYPES]; raw[1 + MAX_SITE_ALTS] = the ref maximum and the members' alt counts; boundary as k_genotype.
+struct GenoSitesArgs {
+    const unsigned long long *counts; uint32_t n_slots;
+    const uint32_t *slots; uint64_t n_sites; uint32_t min_support;
+    const double *logs;                // site_log_table of the call's err: SITE_LOGS doubles
+    const dd *logfact; uint32_t logfact_n;
+    uint8_t *gt; int64_t *pl; uint32_t *raw; uint8_t *boundary;
+    unsigned int *max_n;               // as GenoArgs::max_n
+};
+
+// One site per lane, sites in strides of the grid.  K differs from lane to lane, so the block stages the call's logarithms in LDS (128 bytes)
+// and each lane reads its three from there; the members' counts are gathered under a predicate into registers, and geno_site writes the PLs
+// straight to the site's place in global memory.
+__global__ __launch_bounds__(TPB) void k_genotype_sites(GenoSitesArgs a) {
+  __shared__ double logs[SITE_LOGS];
+  for (uint32_t i = threadIdx.x; i < SITE_LOGS; i += blockDim.x) logs[i] = a.logs[i];
+  __syncthreads();
+  constexpr uint32_t NRAW = MAX_SITE_ALTS + 1;
+  for (uint64_t s = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; s < a.n_sites; s += (uint64_t)gridDim.x * blockDim.x) {
+    uint32_t K = 0, ref = 0, alt[MAX_SITE_ALTS];
+    bool open = true, bad = false;
+#pragma unroll
+    for (uint32_t j = 0; j < MAX_SITE_ALTS; ++j) {
+        const uint32_t sl = a.slots[s * MAX_SITE_ALTS + j];
+        alt[j] = 0;
+        if (sl == NONE32) open = false;
+        else if (!open || sl >= a.n_slots) bad = true;           // (never, behind the host's checks; no count is read through such a slot)
+        else {
+            const unsigned long long c = a.counts[sl];
+            const uint32_t rf = (uint32_t)c;
+            alt[j] = (uint32_t)(c >> 32); ref = rf > ref ? rf : ref; ++K;
+        }
+    }
+    if (K < 2) bad = true;
+    a.raw[s * NRAW] = bad ? 0 : ref;
+#pragma unroll
+    for (uint32_t j = 0; j < MAX_SITE_ALTS; ++j) a.raw[s * NRAW + 1 + j] = bad ? 0 : alt[j];
+    a.boundary[s] = 0;
+    if (bad) {
+        atomicOr(a.max_n + 1, 1u);
+        a.gt[s * 2] = a.gt[s * 2 + 1] = SITE_NO_CALL;
+#pragma unroll
+        for (uint32_t i = 0; i < SITE_GENOTYPES; ++i) a.pl[s * SITE_GENOTYPES + i] = 0;
+        continue;
+    }
+    GenoSite o;
+    const uint32_t st = geno_site(K, ref, alt, a.min_support, logs[0], logs[K], logs[8 + K], a.logfact, a.logfact_n, a.pl + s * SITE_GENOTYPES, o);
+    if (st == GENO_ROW_GROW) atomicMax(a.max_n, (uint32_t)o.n);    // the log10(i!) table is too short: the host grows it and runs the sites again
+    a.gt[s * 2] = o.a; a.gt[s * 2 + 1] = o.b;
+    if (o.near) a.boundary[s] = 1;
   }
 }
 

@@ -22,11 +22,15 @@ def main():
                     help="ploidy of every SV, 1..8 (extension; default: the reference's diploid model)")
     ap.add_argument("--ploidy-file", metavar="<ploidyfile>",
                     help="per-contig or per-region ploidy, 0..8: lines `CHROM PLOIDY` or `CHROM FROM TO PLOIDY` (extension)")
+    ap.add_argument("--joint-ins", action="store_true",
+                    help="genotype insertions that share a CHROM and POS together, 2..6 per site, diploid only (extension)")
     args = ap.parse_args()
+    if args.joint_ins and (args.ploidy is not None or args.ploidy_file is not None):
+        ap.error("--joint-ins is diploid only: it cannot be combined with --ploidy or --ploidy-file")
     out = "genotype_results.txt" if args.output is None else args.output[0]
     err = args.err[0] if args.err is not None else 0.00005
     from svjg import genotype
-    genotype.run(args.aln[0], args.vcf, out, args.minsupport, err, ploidy=args.ploidy, ploidy_file=args.ploidy_file)
+    genotype.run(args.aln[0], args.vcf, out, args.minsupport, err, ploidy=args.ploidy, ploidy_file=args.ploidy_file, joint_ins=args.joint_ins)
 
 
 if __name__ == "__main__":

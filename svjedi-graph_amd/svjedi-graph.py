@@ -42,7 +42,11 @@ def main():
                     help="ploidy of every SV, 1..8 (extension; default: the reference's diploid model)")
     ap.add_argument("--ploidy-file", metavar="<ploidyfile>",
                     help="per-contig or per-region ploidy, 0..8: lines `CHROM PLOIDY` or `CHROM FROM TO PLOIDY` (extension)")
+    ap.add_argument("--joint-ins", action="store_true",
+                    help="genotype insertions that share a CHROM and POS together, 2..6 per site, diploid only (extension)")
     args = ap.parse_args()
+    if args.joint_ins and (args.ploidy is not None or args.ploidy_file is not None):
+        ap.error("--joint-ins is diploid only: it cannot be combined with --ploidy or --ploidy-file")
     pre = args.prefix
 
     print("Constructing variation graph...")
@@ -77,7 +81,8 @@ def main():
             sys.exit("Failed to filter the alignments.\nExiting SVJedi-graph.")
         print("Genotyping SVs...")
         try:
-            n = genotype.genotype_with_counts(ctx, args.vcf, graph.slot_of, out_vcf, args.minsupport, ploidy=args.ploidy, ploidy_file=args.ploidy_file)
+            n = genotype.genotype_with_counts(ctx, args.vcf, graph.slot_of, out_vcf, args.minsupport, ploidy=args.ploidy, ploidy_file=args.ploidy_file,
+                                              joint_ins=args.joint_ins)
             print("Genotyped svs: " + str(n))
         except Exception:
             import traceback
@@ -93,8 +98,9 @@ def main():
     print("Genotyping SVs...")
     ploidy_opts = ("" if args.ploidy is None else " --ploidy {}".format(args.ploidy)) + \
                   ("" if args.ploidy_file is None else " --ploidy-file {}".format(args.ploidy_file))
-    p = subprocess.run("python3 {}/predict-genotype.py -d {} -v {} --minsupport {} -o {}{}".format(
-        HERE, out_json, args.vcf, str(args.minsupport), out_vcf, ploidy_opts), shell=True)
+    joint_opt = " --joint-ins" if args.joint_ins else ""
+    p = subprocess.run("python3 {}/predict-genotype.py -d {} -v {} --minsupport {} -o {}{}{}".format(
+        HERE, out_json, args.vcf, str(args.minsupport), out_vcf, ploidy_opts, joint_opt), shell=True)
     if p.returncode == 1:
         sys.exit("Failed to predict the genotypes.\nExiting SVJedi-graph.")
 

@@ -84,6 +84,7 @@ _SIGS = {
     "svjg_genotype_view": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64,
                                           ctypes.c_uint32, ctypes.c_double] + [ctypes.POINTER(ctypes.c_void_p)] * 4),
     "svjg_genotype_ploidy": (ctypes.c_int, [ctypes.c_void_p] * 5 + [ctypes.c_uint64, ctypes.c_uint32, ctypes.c_double] + [ctypes.c_void_p] * 5),
+    "svjg_genotype_sites": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_uint32, ctypes.c_double] + [ctypes.c_void_p] * 4),
     "svjg_set_rows": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64]),
     "svjg_run_resident": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_uint64, ctypes.c_uint32, ctypes.c_double] + [ctypes.POINTER(ctypes.c_void_p)] * 5),
     "svjg_run_begin": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_uint64, ctypes.c_uint32, ctypes.c_double]),
@@ -99,6 +100,8 @@ EXPORTS = tuple(_SIGS) + ("svjg_write_informative_json", "svjg_count_informative
                           "svjg_graph_load", "svjg_graph_view", "svjg_graph_info", "svjg_graph_free",
                           "svjg_vcf_load", "svjg_vcf_arrays", "svjg_vcf_write", "svjg_vcf_free")
 MAX_PLOIDY = 8                      # svjg.h: SVJG_MAX_PLOIDY
+MAX_SITE_ALTS = 6                   # svjg.h: SVJG_MAX_SITE_ALTS
+SITE_GENOTYPES = 28                 # svjg.h: SVJG_SITE_GENOTYPES
 _lib = None
 _host_lib = None
 
@@ -489,6 +492,22 @@ class Context:
                                                 min_support, float(err), gt.ctypes.data, pl.ctypes.data, raw.ctypes.data,
                                                 done.ctypes.data, boundary.ctypes.data))
         return gt, pl, raw, done, boundary
+
+    def genotype_sites(self, slots, min_support, err):
+        """Insertions that share a position, genotyped together (svjg_genotype_sites).  slots[n, 6]: the members' count slots first, 0xFFFFFFFF
+        behind them.  -> (gt[n, 2] = the pair (a, b) or 0xFF, 0xFF, pl[n, 28] in VCF order then zeros, raw[n, 7] = ref maximum and alt_1..alt_6,
+        boundary = the sites to recompute with svjg.genotype.exact_pl_site)"""
+        slots = np.ascontiguousarray(slots, dtype=np.uint32)
+        if slots.ndim != 2 or slots.shape[1] != MAX_SITE_ALTS:
+            raise SvjgError("slots: %d per site" % MAX_SITE_ALTS)
+        n = len(slots)
+        gt = np.empty((n, 2), dtype=np.uint8)
+        pl = np.empty((n, SITE_GENOTYPES), dtype=np.int64)
+        raw = np.empty((n, MAX_SITE_ALTS + 1), dtype=np.uint32)
+        boundary = np.empty(n, dtype=np.uint8)
+        self._chk(self.lib.svjg_genotype_sites(self.h, slots.ctypes.data, n, min_support, float(err), gt.ctypes.data, pl.ctypes.data,
+                                               raw.ctypes.data, boundary.ctypes.data))
+        return gt, pl, raw, boundary
 
     def set_rows(self, sv_type, slot, ok):
         """the VCF rows' input arrays of genotype(), left on the device for run_resident()"""

@@ -333,6 +333,135 @@ def genotype_with_counts_ploidy(ctx, vcf_path, slot_of, out_path, min_support, e
     return write_vcf_ploidy(out_path, rows, pld, gt, pl, raw, done)
 
 
+# ---- insertions that share a position, genotyped together (--joint-ins): svjg_genotype_sites, Python rows and the writer below ----
+
+MAX_SITE_ALTS = 6
+JOINT_INS_PLOIDY = "--joint-ins is diploid only: it cannot be combined with --ploidy or --ploidy-file"
+_PL_LINE = '##FORMAT=<ID=PL,Number=3,Type=Integer,Description="Phred-scaled likelihood for each genotype">\n'
+SITE_FORMAT_LINES = (
+    '##FORMAT=<ID=SGT,Number=1,Type=String,Description="Joint genotype of the insertions sharing this position: allele 0 is the reference, allele i the insertion with SAL=i">\n'
+    '##FORMAT=<ID=SAL,Number=1,Type=Integer,Description="Allele number of this insertion in SGT">\n'
+)
+
+
+def site_genotypes(K):
+    """the genotypes {a, b} of a site of K members in VCF order: index b (b + 1) / 2 + a"""
+    return [(a, b) for b in range(K + 1) for a in range(b + 1)]
+
+
+def exact_pl_site(ref, alts, err):
+    """The (K + 1)(K + 2) / 2 PL integers of one site (ref: the members' largest raw ref count, alts: their K raw alt counts) in VCF order,
+    with the reference's arithmetic written for K alt alleles: double products, Decimal sums at precision 28, every chain term
+    log10 comb(s_j, r_j) as CPython computes it for the exact integer, truncation.  For the sites svjg_genotype_sites flags."""
+    import math
+    from decimal import Decimal, localcontext
+    K = len(alts)
+    if not 2 <= K <= MAX_SITE_ALTS:
+        raise ValueError("a site has 2..%d insertions, not %d" % (MAX_SITE_ALTS, K))
+    c = [ref] + [round(x / 2, 1) if x > 0 else 0 for x in alts]
+    r = [int(round(x, 0)) for x in c]
+    N = sum(c)
+    l_ok, l_x, l_he = math.log10(1 - err), math.log10(err / K), math.log10(((1 - err) + err / K) / 2)
+    with localcontext() as ctx:
+        ctx.prec = 28
+        T, s = Decimal(0), r[0]
+        for j in range(1, K + 1):
+            s += r[j]
+            T += Decimal(_log10_comb(s, r[j]))
+        out = []
+        for a, b in site_genotypes(K):
+            if a == b:
+                lik = Decimal(c[a] * l_ok) + Decimal((N - c[a]) * l_x)
+            else:
+                lik = Decimal((c[a] + c[b]) * l_he) + Decimal((N - c[a] - c[b]) * l_x)
+            out.append(int(-10 * (lik + T)))
+        return out
+
+
+def form_sites(rows, done):
+    """-> (sites, skipped): sites = lists of row indices, the INS rows the ordinary call genotyped that share CHROM and POS text, 2..6 of them in
+    file order (they need not be adjacent); skipped = [(chrom, pos, count)] for the positions with more than six, which keep their own calls"""
+    by_pos = {}
+    for r in range(len(rows.chrom)):
+        if done[r] and rows.sv_type[r] == TYPE_CODE["INS"]:
+            by_pos.setdefault((rows.chrom[r], rows.pos[r]), []).append(r)
+    sites = [m for m in by_pos.values() if 2 <= len(m) <= MAX_SITE_ALTS]
+    skipped = [(k[0], k[1], len(m)) for k, m in by_pos.items() if len(m) > MAX_SITE_ALTS]
+    return sites, skipped
+
+
+def project_site(K, i, gt_pair, site_pl):
+    """member i (1..K) of a site called gt_pair = (a, b) or (0xFF, 0xFF) -> (its copies g = 0..2, or 3 for a no-call; [PL_0, PL_1, PL_2]: the
+    smallest site PL over the genotypes with exactly that many copies of allele i)"""
+    a, b = int(gt_pair[0]), int(gt_pair[1])
+    g = 3 if a == NO_CALL else (a == i) + (b == i)
+    pl = [None, None, None]
+    for k, (x, y) in enumerate(site_genotypes(K)):
+        n = (x == i) + (y == i)
+        v = int(site_pl[k])
+        pl[n] = v if pl[n] is None else min(pl[n], v)
+    return g, pl
+
+
+def write_vcf_joint(out_path, rows, gt, pl, raw, done, member):
+    """write_vcf with the members of a site printed as GT:DP:AD:PL:SGT:SAL; member: row -> (g, [three PLs], site call text, allele number)"""
+    n_done = 0
+    with open(out_path, "w") as out:
+        for kind, v in rows.items:
+            if kind == "h":
+                out.write(v.replace(_PL_LINE, _PL_LINE + SITE_FORMAT_LINES) if v is FORMAT_HEADER else v)
+                continue
+            fmt = "GT:DP:AD:PL"
+            if done[v]:
+                n_done += 1
+                dp, ad = _fmt_counts(int(rows.sv_type[v]), int(raw[v, 0]), int(raw[v, 1]))
+                if v in member:
+                    g, p, sgt, sal = member[v]
+                    fmt = "GT:DP:AD:PL:SGT:SAL"
+                    tail = "%s:%s:%s:%d,%d,%d:%s:%d" % (GT_TEXT[g], dp, ad, p[0], p[1], p[2], sgt, sal)
+                else:
+                    tail = "%s:%s:%s:%d,%d,%d" % (GT_TEXT[gt[v]], dp, ad, pl[v, 0], pl[v, 1], pl[v, 2])
+            else:
+                tail = "./.:0:0,0:.,.,."
+            out.write(rows.prefix[v] + "\t" + fmt + "\t" + tail + "\n")
+    return n_done
+
+
+def genotype_with_counts_joint(ctx, vcf_path, slot_of, out_path, min_support, err, slot_is_presence):
+    """genotype_with_counts with --joint-ins: the Python rows, the ordinary diploid call on all of them, then ONE svjg_genotype_sites call
+    over the sites of form_sites; the members' GT and PL become the site call's projection (project_site), DP and AD stay the row's own"""
+    import sys
+    if not isinstance(slot_of, dict):
+        slot_of = {k: i for i, k in enumerate(slot_of)}
+    rows = VcfRows(vcf_path, slot_of, slot_is_presence)
+    min_support = max(0, int(min_support))
+    bad_err = not (0.0 < float(err) < 1.0)
+    gt, pl, raw, done = ctx.genotype(rows.sv_type, rows.slot, rows.ok, min_support, 0.5 if bad_err else err)
+    if bad_err and np.asarray(done).any():
+        raise ValueError("math domain error")
+    pl, _ = apply_boundary_guard(ctx, rows, pl, raw, done, err)
+    sites, skipped = form_sites(rows, done)
+    for chrom, pos, count in skipped:
+        print("--joint-ins: %s:%s has %d insertions, more than %d: they keep their independent calls" % (chrom, pos, count, MAX_SITE_ALTS), file=sys.stderr)
+    member = {}
+    if sites:
+        slots = np.full((len(sites), MAX_SITE_ALTS), NONE, dtype=np.uint32)
+        for k, m in enumerate(sites):
+            slots[k, :len(m)] = rows.slot[m]
+        s_gt, s_pl, s_raw, s_boundary = ctx.genotype_sites(slots, min_support, err)
+        for k, m in enumerate(sites):
+            K = len(m)
+            spl = s_pl[k, :(K + 1) * (K + 2) // 2]
+            if s_boundary[k]:
+                spl = exact_pl_site(int(s_raw[k, 0]), [int(x) for x in s_raw[k, 1:K + 1]], err)
+            a, b = int(s_gt[k, 0]), int(s_gt[k, 1])
+            sgt = "./." if a == NO_CALL else "%d/%d" % (a, b)
+            for i, r in enumerate(m, 1):
+                g, p = project_site(K, i, (a, b), spl)
+                member[r] = (g, p, sgt, i)
+    return write_vcf_joint(out_path, rows, gt, pl, raw, done, member)
+
+
 def write_vcf(out_path, rows, gt, pl, raw, done):
     n_done = 0
     with open(out_path, "w") as out:
@@ -369,9 +498,15 @@ def open_rows(vcf_path, slot_of, slot_is_presence=False):
     return VcfRows(vcf_path, slot_of, slot_is_presence)
 
 
-def genotype_with_counts(ctx, vcf_path, slot_of, out_path, min_support=3, err=0.00005, slot_is_presence=False, ploidy=None, ploidy_file=None):
+def genotype_with_counts(ctx, vcf_path, slot_of, out_path, min_support=3, err=0.00005, slot_is_presence=False, ploidy=None, ploidy_file=None,
+                         joint_ins=False):
     """Counts already live in the context (fused path, or set_counts): parse, run the kernel, write.  ploidy (1..8, every row) and / or
-    ploidy_file (per contig or region, load_ploidy_file): genotype_with_counts_ploidy; with neither, the diploid path below."""
+    ploidy_file (per contig or region, load_ploidy_file): genotype_with_counts_ploidy; joint_ins (insertions that share a position are
+    genotyped together, diploid only): genotype_with_counts_joint; with none of them, the diploid path below."""
+    if joint_ins and (ploidy is not None or ploidy_file is not None):
+        raise ValueError(JOINT_INS_PLOIDY)                       # (before anything is asked of the device or written)
+    if joint_ins:
+        return genotype_with_counts_joint(ctx, vcf_path, slot_of, out_path, min_support, err, slot_is_presence)
     if ploidy is not None or ploidy_file is not None:
         return genotype_with_counts_ploidy(ctx, vcf_path, slot_of, out_path, min_support, err, slot_is_presence, ploidy, ploidy_file)
     rows = open_rows(vcf_path, slot_of, slot_is_presence)
@@ -389,9 +524,11 @@ def genotype_with_counts(ctx, vcf_path, slot_of, out_path, min_support=3, err=0.
         rows.close()
 
 
-def run(json_path, vcf_path, out_path, min_support=3, err=0.00005, device=0, ploidy=None, ploidy_file=None):
+def run(json_path, vcf_path, out_path, min_support=3, err=0.00005, device=0, ploidy=None, ploidy_file=None, joint_ins=False):
     """predict-genotype.py main(): counts come from the informative-alignment JSON."""
     from . import capi, filter as flt
+    if joint_ins and (ploidy is not None or ploidy_file is not None):
+        raise ValueError(JOINT_INS_PLOIDY)
     got = flt.read_handoff(json_path)                            # left by our filter-alignments.py for exactly this file, else None
     if got is None:
         got = capi.count_informative_json(json_path)             # len() of the two lists of every key (:219-226)
@@ -400,7 +537,8 @@ def run(json_path, vcf_path, out_path, min_support=3, err=0.00005, device=0, plo
     try:
         ctx.alloc_counts(len(keys))
         ctx.set_counts(counts)
-        n = genotype_with_counts(ctx, vcf_path, list(keys), out_path, min_support, err, slot_is_presence=True, ploidy=ploidy, ploidy_file=ploidy_file)
+        n = genotype_with_counts(ctx, vcf_path, list(keys), out_path, min_support, err, slot_is_presence=True, ploidy=ploidy, ploidy_file=ploidy_file,
+                                 joint_ins=joint_ins)
     finally:
         ctx.close()
     print("Genotyped svs: " + str(n))
