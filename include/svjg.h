@@ -251,6 +251,42 @@ int svjg_genotype_ploidy(svjg_ctx *ctx, const uint8_t *sv_type, const uint32_t *
 int svjg_genotype_sites(svjg_ctx *ctx, const uint32_t *slots, uint64_t n_sites, uint32_t min_support, double err,
                         uint8_t *gt, int64_t *pl, uint32_t *raw, uint8_t *boundary);
 
+/* ---- cohort: many samples' counts, one row set, one multi-sample call (--cohort) -----------------------------------------
+ * A count matrix of n_samples x n_slots lives in the context, slot-major: cm[slot * n_samples + s], packed ref | alt << 32 like the count
+ * vector, with a presence byte beside each entry.  Slot-major because the genotype kernel's neighbouring lanes are neighbouring samples of one
+ * row: they read the counts and write their results coalesced.  The presence byte says that the slot's sv_id is a key of THAT sample's JSON
+ * (predict-genotype.py:216): a key with two empty lists is genotyped, an absent key is not.
+ *   svjg_cohort_alloc        a zeroed matrix (counts and presence); a second call replaces it.  SVJG_E_ARG: n_samples = 0; SVJG_E_NOMEM: the
+ *                            n_samples x n_slots x 9 bytes cannot be had.
+ *   svjg_cohort_set_counts   sparse: the n slots the sample has as keys, counts[k*2..] = (ref, alt) of slots[k]; their presence is set, every
+ *                            other slot of the sample is cleared and absent.  SVJG_E_ARG, found before any launch: no matrix, sample or slot
+ *                            out of range, a slot named twice, null arrays with n > 0.
+ *   svjg_cohort_store_counts the context's current count vector (what the classify kernels have just accumulated) -> column `sample`, device
+ *                            to device by a small transposing kernel; presence = (ref | alt) != 0, the rule of svjg_genotype's gate when ok
+ *                            bit 1 is clear.  Classify S GAFs in a loop on one graph and genotype them without any JSON.  SVJG_E_ARG: no
+ *                            matrix, sample out of range, the count vector's length is not the matrix's n_slots.
+ *   svjg_cohort_get_counts   one sample back (out[slot*2..] as svjg_get_counts, present[slot]); n_slots must be the matrix's.
+ *
+ * svjg_genotype_cohort: per item (r, s) what svjg_genotype does per row, gate included, with the presence test in place of the count test: the
+ * item is genotyped iff ok[r] & 1, slot[r] != 0xFFFFFFFF and present[slot[r]][s].  ok bit 1 is IGNORED here (the presence byte says it per
+ * sample).  An item that is not genotyped has gt = 3, zero PLs, raw = 0,0.  Outputs, [n_rows][n_samples] row-major: gt, pl (3 x int64), raw
+ * (2 x uint32), genotyped, boundary (as svjg_genotype_boundary: recompute such items with svjedi-graph_amd/svjg/genotype.py: exact_pl); and
+ * site[r*2..] = NS (the samples with gt != 3) and AC (the sum of their alt copies) of row r, summed in integers in the same launch (wave
+ * ballots, one 64-bit atomic per row and wave), so they are equal from run to run; AN = 2 NS.  The call works in a block of its own: it
+ * neither reads nor changes what svjg_genotype_view and svjg_genotype_boundary hand out, nor the count vector.  The caller bounds memory by
+ * calling with row chunks (37 bytes per item on the device and on the host).  n_rows = 0 returns 0.  SVJG_E_ARG: no matrix, a null array; a
+ * row naming a slot >= the matrix's n_slots is reported after the pass, as svjg_genotype reports it.  svjg_last_kernel_ms reports the kernel
+ * as genotype_ms.  Measured once, with the change that added it (one MI355X, 100 000 rows x 64 samples, counts 0..60, e = 5e-5, median of 30
+ * calls behind 5, alternated twice with the loop in one process): 0.165 / 0.165 ms for the one launch, against 0.956 / 0.951 ms of kernels summed
+ * and 21.4 / 21.4 ms of wall time for 64 x (svjg_set_counts + svjg_genotype); nothing else about this kernel has been measured. */
+int svjg_cohort_alloc(svjg_ctx *ctx, uint32_t n_samples, uint32_t n_slots);
+int svjg_cohort_set_counts(svjg_ctx *ctx, uint32_t sample, const uint32_t *slots, const uint32_t *counts, uint64_t n);
+int svjg_cohort_store_counts(svjg_ctx *ctx, uint32_t sample);
+int svjg_cohort_get_counts(svjg_ctx *ctx, uint32_t sample, uint32_t *out, uint8_t *present, uint32_t n_slots);
+int svjg_genotype_cohort(svjg_ctx *ctx, const uint8_t *sv_type, const uint32_t *slot, const uint8_t *ok,
+                         uint64_t n_rows, uint32_t min_support, double err,
+                         uint8_t *gt, int64_t *pl, uint32_t *raw, uint8_t *genotyped, uint8_t *boundary, uint32_t *site);
+
 /* ---- the whole pass in one call (what a fused svjedi-graph run and bench.py do per batch) -----------------------------------
  * svjg_set_rows copies the three per-row input arrays of svjg_genotype to the device once (they stay until the next
  * svjg_set_rows / svjg_destroy).  svjg_run_resident then does, for the resident text of svjg_gaf_upload and those rows:

@@ -119,6 +119,12 @@ struct svjg_ctx {
     void *h_prows = nullptr;  uint64_t h_prows_cap = 0;  // boundary bytes of the calls above stay as they are
     void *d_srows = nullptr;  uint64_t srows_cap = 0;    // svjg_genotype_sites' own block and pinned twin (sites_layout), for the same reason
     void *h_srows = nullptr;  uint64_t h_srows_cap = 0;
+    // cohort: the slot-major count matrix (svjg_cohort_alloc: counts, then the presence bytes, ONE allocation), the dense vector a sample's
+    // column is staged in, and svjg_genotype_cohort's own block and pinned twin (cohort_layout), for the same reason
+    unsigned long long *d_cm = nullptr;  uint8_t *d_cpresent = nullptr;  uint32_t cohort_samples = 0, cohort_slots = 0;
+    void *d_cstage = nullptr;  uint64_t cstage_cap = 0;
+    void *d_crows = nullptr;  uint64_t crows_cap = 0;
+    void *h_crows = nullptr;  uint64_t h_crows_cap = 0;
     // resident VCF rows of svjg_set_rows / svjg_run_resident: device block (results, row inputs) and the pinned host block the results land in
     struct RunSlot {
         void *d = nullptr;  uint64_t d_cap = 0;  void *h = nullptr;  uint64_t h_cap = 0;  void *h_dev = nullptr;   // h_dev: the pinned block as the device sees it
@@ -212,6 +218,8 @@ extern "C" void svjg_destroy(svjg_ctx *c) {
     hipFree(c->d_long);
     hipFree(c->d_gaf); hipFree(c->d_deferred); hipFree(c->d_recs); hipFree(c->d_host); hipFree(c->d_st); hipFree(c->d_logfact);
     hipFree(c->d_bsum); hipFree(c->d_rows); hipFree(c->d_prows); hipFree(c->d_srows); hipFree(c->d_run_in);
+    hipFree(c->d_cm); hipFree(c->d_cstage); hipFree(c->d_crows);
+    if (c->h_crows) hipHostFree(c->h_crows);
     for (auto &r : c->run) {
         hipFree(r.d); hipFree(r.counts);
         if (r.h) hipHostFree(r.h);
@@ -1121,6 +1129,137 @@ extern "C" int svjg_genotype_sites(svjg_ctx *c, const uint32_t *slots, uint64_t 
     HIPCHK(c, hipEventElapsedTime(&c->ms_geno, c->ev[4], c->ev[5]));
     memcpy(pl, hb + L.pl, n_sites * SITE_GENOTYPES * sizeof *pl); memcpy(raw, hb + L.raw, n_sites * (MAX_SITE_ALTS + 1) * sizeof *raw);
     memcpy(gt, hb + L.gt, n_sites * 2); memcpy(boundary, hb + L.boundary, n_sites);
+    return 0;
+}
+
+// ---- cohort: many samples' counts against one row set (svjg.h) -------------------------------------------------------------
+// The matrix is slot-major (cm[slot * S + s]) so that k_genotype_cohort, whose neighbouring lanes are neighbouring samples of one row, reads
+// the counts and the presence bytes coalesced.  A sample's column goes in and out through a dense vector and a small transposing kernel.
+extern "C" int svjg_cohort_alloc(svjg_ctx *c, uint32_t n_samples, uint32_t n_slots) {
+    if (!c) return SVJG_E_ARG;
+    if (n_samples == 0) { c->err = "a cohort has at least one sample"; return SVJG_E_ARG; }
+    HIPCHK(c, hipSetDevice(c->device));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    hipFree(c->d_cm); c->d_cm = nullptr; c->d_cpresent = nullptr; c->cohort_samples = c->cohort_slots = 0;
+    const uint64_t n = (uint64_t)n_samples * n_slots;             // (< 2^64; times nine it is below 2^68: checked)
+    void *q = nullptr;
+    if (n > (1ull << 60) || hipMalloc(&q, n * 9 + 8) != hipSuccess) { (void)hipGetLastError(); c->err = "no memory for the cohort matrix"; return SVJG_E_NOMEM; }
+    c->d_cm = (unsigned long long *)q; c->d_cpresent = (uint8_t *)q + n * 8;
+    c->cohort_samples = n_samples; c->cohort_slots = n_slots;
+    HIPCHK(c, hipMemsetAsync(q, 0, n * 9 + 8, c->stream));
+    return 0;
+}
+
+// the staging vector of one column: [ counts 8 | present 1 ] x n_slots
+static int cohort_stage(svjg_ctx *c) { return ensure(c, &c->d_cstage, &c->cstage_cap, (uint64_t)c->cohort_slots * 9 + 16, 1, false); }
+
+extern "C" int svjg_cohort_set_counts(svjg_ctx *c, uint32_t sample, const uint32_t *slots, const uint32_t *counts, uint64_t n) {
+    if (!c) return SVJG_E_ARG;
+    if (!c->d_cm) { c->err = "no cohort matrix"; return SVJG_E_ARG; }
+    if (sample >= c->cohort_samples) { c->err = "sample out of range"; return SVJG_E_ARG; }
+    if (n && (!slots || !counts)) return SVJG_E_ARG;
+    const uint32_t ns = c->cohort_slots;
+    std::vector<unsigned long long> col((size_t)ns + 1, 0ull);
+    std::vector<uint8_t> pres((size_t)ns + 1, 0);
+    for (uint64_t k = 0; k < n; ++k) {
+        const uint32_t sl = slots[k];
+        if (sl >= ns) { c->err = "slot out of range"; return SVJG_E_ARG; }
+        if (pres[sl]) { c->err = "slot named twice"; return SVJG_E_ARG; }
+        pres[sl] = 1;
+        col[sl] = (unsigned long long)counts[2 * k] | ((unsigned long long)counts[2 * k + 1] << 32);
+    }
+    HIPCHK(c, hipSetDevice(c->device));
+    if (ns == 0) return 0;
+    if (const int rc = cohort_stage(c)) return rc;
+    unsigned long long *d_col = (unsigned long long *)c->d_cstage; uint8_t *d_pres = (uint8_t *)c->d_cstage + (uint64_t)ns * 8;
+    HIPCHK(c, hipMemcpyAsync(d_col, col.data(), (uint64_t)ns * 8, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipMemcpyAsync(d_pres, pres.data(), ns, hipMemcpyHostToDevice, c->stream));
+    hipLaunchKernelGGL(k_cohort_store, dim3(capped_grid(ns)), dim3(TPB), 0, c->stream, c->d_cm, c->d_cpresent, c->cohort_samples, sample, d_col, d_pres, ns);
+    HIPCHK(c, hipGetLastError());
+    HIPCHK(c, hipStreamSynchronize(c->stream));                   // `col` and `pres` are locals
+    return 0;
+}
+
+extern "C" int svjg_cohort_store_counts(svjg_ctx *c, uint32_t sample) {
+    if (!c) return SVJG_E_ARG;
+    if (!c->d_cm) { c->err = "no cohort matrix"; return SVJG_E_ARG; }
+    if (sample >= c->cohort_samples) { c->err = "sample out of range"; return SVJG_E_ARG; }
+    if (!c->have_counts || c->n_slots != c->cohort_slots) { c->err = "the count vector and the cohort matrix differ in their slots"; return SVJG_E_ARG; }
+    HIPCHK(c, hipSetDevice(c->device));
+    { const int rc0 = fetch_slot_counts(c); if (rc0) return rc0; }
+    if (c->n_slots == 0) return 0;
+    hipLaunchKernelGGL(k_cohort_store, dim3(capped_grid(c->n_slots)), dim3(TPB), 0, c->stream, c->d_cm, c->d_cpresent, c->cohort_samples, sample,
+                       (const unsigned long long *)c->d_counts, (const uint8_t *)nullptr, c->n_slots);
+    HIPCHK(c, hipGetLastError());
+    return 0;
+}
+
+extern "C" int svjg_cohort_get_counts(svjg_ctx *c, uint32_t sample, uint32_t *out, uint8_t *present, uint32_t n_slots) {
+    if (!c) return SVJG_E_ARG;
+    if (!c->d_cm) { c->err = "no cohort matrix"; return SVJG_E_ARG; }
+    if (sample >= c->cohort_samples) { c->err = "sample out of range"; return SVJG_E_ARG; }
+    if (n_slots != c->cohort_slots || (n_slots && (!out || !present))) return SVJG_E_ARG;
+    HIPCHK(c, hipSetDevice(c->device));
+    if (n_slots == 0) return 0;
+    if (const int rc = cohort_stage(c)) return rc;
+    unsigned long long *d_col = (unsigned long long *)c->d_cstage; uint8_t *d_pres = (uint8_t *)c->d_cstage + (uint64_t)n_slots * 8;
+    hipLaunchKernelGGL(k_cohort_load, dim3(capped_grid(n_slots)), dim3(TPB), 0, c->stream, (const unsigned long long *)c->d_cm, (const uint8_t *)c->d_cpresent,
+                       c->cohort_samples, sample, d_col, d_pres, n_slots);
+    HIPCHK(c, hipGetLastError());
+    std::vector<unsigned long long> tmp(n_slots);
+    HIPCHK(c, hipMemcpyAsync(tmp.data(), d_col, (uint64_t)n_slots * 8, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipMemcpyAsync(present, d_pres, n_slots, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    for (uint32_t i = 0; i < n_slots; ++i) { out[2 * i] = (uint32_t)tmp[i]; out[2 * i + 1] = (uint32_t)(tmp[i] >> 32); }
+    return 0;
+}
+
+// all items with the table at hand.  The site words lie right in front of the max_n pair (cohort_layout): both are zeroed in front of EVERY
+// launch — settle_launch runs the kernel over all items again after the table grew, and the atomics would add to the first launch's sums.
+// Blocks: enough for eight waves on every SIMD (the kernel holds 64 VGPRs or fewer: svjg.h), the rest in strides of the grid.
+static int launch_cohort(svjg_ctx *c, GenoCohortArgs &p) {
+    p.g.logfact = c->d_logfact; p.g.logfact_n = c->logfact_n;
+    HIPCHK(c, hipMemsetAsync(p.site, 0, p.g.n_rows * 8 + 8, c->stream));
+    const uint64_t n_items = p.g.n_rows * p.n_samples, blocks = (n_items + TPB - 1) / TPB, cap = (uint64_t)c->n_cu * 8;
+    hipLaunchKernelGGL(k_genotype_cohort, dim3((uint32_t)(blocks < cap ? blocks : cap)), dim3(TPB), 0, c->stream, p);
+    HIPCHK(c, hipGetLastError());
+    return 0;
+}
+
+extern "C" int svjg_genotype_cohort(svjg_ctx *c, const uint8_t *sv_type, const uint32_t *slot, const uint8_t *ok, uint64_t n_rows,
+                                    uint32_t min_support, double err, uint8_t *gt, int64_t *pl, uint32_t *raw, uint8_t *genotyped,
+                                    uint8_t *boundary, uint32_t *site) {
+    if (!c) return SVJG_E_ARG;
+    if (!c->d_cm) { c->err = "no cohort matrix"; return SVJG_E_ARG; }
+    if (n_rows == 0) return 0;
+    if (!sv_type || !slot || !ok || !gt || !pl || !raw || !genotyped || !boundary || !site) return SVJG_E_ARG;
+    const uint64_t S = c->cohort_samples;
+    if (n_rows > (1ull << 40) / S) { c->err = "too many items for one call: genotype the rows in chunks"; return SVJG_E_ARG; }
+    HIPCHK(c, hipSetDevice(c->device));
+    const CohortLayout L = cohort_layout(n_rows, S);
+    const uint64_t n = n_rows * S;
+    int rc;
+    if ((rc = ensure(c, &c->d_crows, &c->crows_cap, L.total, 1, false))) return rc;
+    if ((rc = ensure_pinned(c, &c->h_crows, &c->h_crows_cap, L.total, hipHostMallocDefault))) return rc;
+    uint8_t *base = (uint8_t *)c->d_crows, *hb = (uint8_t *)c->h_crows;
+    memcpy(hb + L.in.slot, slot, n_rows * 4); memcpy(hb + L.in.type, sv_type, n_rows); memcpy(hb + L.in.ok, ok, n_rows);
+    HIPCHK(c, hipMemcpyAsync(base + L.in.slot, hb + L.in.slot, L.in.bytes, hipMemcpyHostToDevice, c->stream));
+    GenoCohortArgs p{};
+    p.g = geno_args(c, c->d_cm, base, L.in, n_rows, min_support, err);
+    p.g.n_slots = c->cohort_slots;                                // (the matrix's slots, not the count vector's)
+    p.g.pl = (int64_t *)(base + L.pl); p.g.raw = (uint32_t *)(base + L.raw); p.g.gt = base + L.gt; p.g.genotyped = base + L.flags;
+    p.g.boundary = base + L.boundary; p.g.max_n = (unsigned int *)(base + L.maxn);
+    p.present = c->d_cpresent; p.n_samples = c->cohort_samples; p.site = (unsigned long long *)(base + L.site);
+    HIPCHK(c, hipEventRecord(c->ev[4], c->stream));
+    if (c->logfact_n == 0 && (rc = build_logfact(c, logfact_first()))) return rc;
+    if ((rc = launch_cohort(c, p))) return rc;
+    HIPCHK(c, hipEventRecord(c->ev[5], c->stream));
+    HIPCHK(c, hipMemcpyAsync(hb, base, L.maxn + 8, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    if ((rc = settle_launch(c, (const unsigned int *)(hb + L.maxn), hb, base, L.maxn + 8, false, [&] { return launch_cohort(c, p); }))) return rc;
+    HIPCHK(c, hipEventElapsedTime(&c->ms_geno, c->ev[4], c->ev[5]));
+    memcpy(pl, hb + L.pl, n * 3 * sizeof *pl); memcpy(raw, hb + L.raw, n * 2 * sizeof *raw);
+    memcpy(gt, hb + L.gt, n); memcpy(genotyped, hb + L.flags, n); memcpy(boundary, hb + L.boundary, n); memcpy(site, hb + L.site, n_rows * 8);
     return 0;
 }
 

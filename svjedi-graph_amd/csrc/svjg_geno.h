@@ -299,6 +299,23 @@ SVJG_HD uint32_t geno_site(uint32_t K, uint32_t ref, const uint32_t *alt, uint32
     return st;
 }
 
+// ---- many samples, one row set (k_genotype_cohort; diploid) ----
+// Items are flattened as i = r * S + s (row r, sample s) and walked a wave of 64 consecutive items at a time, so the samples of one row are
+// consecutive lanes.  The lanes of a wave that hold the SAME row as lane `lane` (item i, sample s = i % S of S) form one segment:
+// it starts s lanes below (cut at lane 0) and ends S - 1 - s lanes above (cut at lane 63).  A row of R x S items ends at an item below
+// R * S, so no segment reaches beyond the last item; a lane whose item is at or beyond n_items belongs to no segment (mask 0, no leader).
+// The leader is the segment's first lane: it alone adds the segment's sums to the row's site word, so a row that straddles two waves
+// receives two additions.
+struct CohortSeg { uint64_t mask; bool leader; };
+SVJG_HD CohortSeg cohort_segment(uint64_t i, uint64_t s, uint64_t S, uint32_t lane, uint64_t n_items) {
+    if (i >= n_items) return CohortSeg{0, false};
+    const uint32_t lo = s > lane ? 0u : lane - (uint32_t)s;
+    const uint64_t above = S - 1 - s;
+    const uint32_t hi = above > 63u - lane ? 63u : lane + (uint32_t)above;
+    const uint64_t upto = hi == 63u ? ~0ull : (1ull << (hi + 1)) - 1;          // lanes 0..hi
+    return CohortSeg{upto & ~((1ull << lo) - 1), lane == lo};
+}
+
 // ---- host side of a k_genotype launch: the table's size and where a call's rows lie, in plain integers (pinned without a GPU: tests/test_rows_layout.py) ----
 
 // entries of the log10(i!) table: the first one built; the one that holds max_n (the largest n the kernel met beyond the table, < LOGFACT_CAP) with room to spare
@@ -338,6 +355,17 @@ inline SitesLayout sites_layout(uint64_t n) {
     L.pl = o; o += n * 8 * SITE_GENOTYPES; L.raw = o; o += n * 4 * (MAX_SITE_ALTS + 1); L.gt = o; o += n * 2; L.boundary = o; o += n;
     L.maxn = (o + 7) & ~7ull; L.logs = L.maxn + 8; L.slots = L.logs + SITE_LOGS * 8;
     L.in_bytes = SITE_LOGS * 8 + n * 4 * MAX_SITE_ALTS; L.total = L.logs + L.in_bytes + 64;
+    return L;
+}
+
+// cohort leg (svjg_genotype_cohort): a block of its own once more, [ pl 24 | raw 8 | gt 1 | flags 1 | boundary 1 ] x (n_rows * S items, row-major),
+// the rows' site words (NS | AC << 32) with the max_n pair right behind them (ONE memset zeroes both in front of every launch), then ONE copy
+// in: rows_in(n_rows)
+struct CohortLayout { uint64_t pl, raw, gt, flags, boundary, site, maxn;  RowsIn in;  uint64_t total; };
+inline CohortLayout cohort_layout(uint64_t n_rows, uint64_t S) {
+    CohortLayout L; uint64_t o = 0; const uint64_t n = n_rows * S;
+    L.pl = o; o += n * 24; L.raw = o; o += n * 8; L.gt = o; o += n; L.flags = o; o += n; L.boundary = o; o += n;
+    L.site = (o + 7) & ~7ull; L.maxn = L.site + n_rows * 8; L.in = rows_in(n_rows, L.maxn + 8); L.total = L.in.slot + L.in.bytes + 64;
     return L;
 }
 

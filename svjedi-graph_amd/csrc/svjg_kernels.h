@@ -12,6 +12,8 @@
 //   k_logfact_*      log10(i!) table in double-double for the binomial term
 //   k_genotype       one VCF row per lane, fp64 / double-double likelihoods (predict-genotype.py:281-325)
 //   k_genotype_sites one site of insertions that share a position per lane, the same arithmetic over (K + 1)(K + 2) / 2 genotypes
+//   k_genotype_cohort one (row, sample) item per lane over a slot-major count matrix, k_genotype's arithmetic; NS / AC per row by wave ballots
+//   k_cohort_store / k_cohort_load  one sample's column of that matrix from / to a dense count vector
 #pragma once
 #include <hip/hip_runtime.h>
 #define SVJG_TAB_AS __attribute__((address_space(3)))      // the exact routine's per-node scratch and piece tables are LDS arrays here (svjg_line.h)
@@ -2002,6 +2004,86 @@ __global__ __launch_bounds__(TPB) void k_genotype_ploidy(GenoPloidyArgs p) {
 #pragma unroll
     for (uint32_t i = 0; i < NPL; ++i) a.pl[r * NPL + i] = o.pl[i];
     if (o.near) a.boundary[r] = 1;
+  }
+}
+
+// ---- cohort: S samples' counts against one row set (svjg_genotype_cohort) ----
+// The count matrix is slot-major, cm[slot * S + s] packed like the count vector, with a presence byte present[slot * S + s] beside it: the
+// genotype kernel's neighbouring lanes are neighbouring samples of one row, so they read neighbouring words and bytes.
+
+// One count vector -> column `sample` of the matrix (svjg_cohort_store_counts, svjg_cohort_set_counts): reads run along the vector, writes
+// are S words apart.  src_present == nullptr: presence = (ref | alt) != 0, geno_gate's rule when ok bit 1 is clear.
+__global__ __launch_bounds__(TPB) void k_cohort_store(unsigned long long *cm, uint8_t *present, uint32_t S, uint32_t sample,
+                                                      const unsigned long long *src, const uint8_t *src_present, uint32_t n_slots) {
+    for (uint64_t i = (uint64_t)blockIdx.x * TPB + threadIdx.x; i < n_slots; i += (uint64_t)gridDim.x * TPB) {
+        const unsigned long long c = src[i];
+        cm[i * S + sample] = c;
+        present[i * S + sample] = src_present ? src_present[i] : (uint8_t)(c != 0);
+    }
+}
+
+// column `sample` -> a dense vector and its presence bytes (svjg_cohort_get_counts)
+__global__ __launch_bounds__(TPB) void k_cohort_load(const unsigned long long *cm, const uint8_t *present, uint32_t S, uint32_t sample,
+                                                     unsigned long long *dst, uint8_t *dst_present, uint32_t n_slots) {
+    for (uint64_t i = (uint64_t)blockIdx.x * TPB + threadIdx.x; i < n_slots; i += (uint64_t)gridDim.x * TPB) {
+        dst[i] = cm[i * S + sample];
+        dst_present[i] = present[i * S + sample];
+    }
+}
+
+// g: as for k_genotype with counts = the matrix, n_slots = its slots, n_rows = the ROWS, and gt / pl / raw / genotyped / boundary holding
+// n_rows * n_samples items, row-major; g.pl32 is unused.  site[r] = NS | AC << 32, zeroed by the host in front of every launch.
+struct GenoCohortArgs {
+    GenoArgs g;
+    const uint8_t *present;
+    uint32_t n_samples;
+    unsigned long long *site;
+};
+
+// Item i = r * S + s per lane, items in strides of the grid.  What k_genotype does per row, gate included, but the presence test: the item is
+// genotyped iff ok[r] & 1, the row has a slot and present[slot][s] (ok bit 1 is not looked at).  The site tags come from the same pass in
+// integers: the lanes of one row are a segment of the wave (svjg_geno.h: cohort_segment), its NS and AC are popcounts of ballots under the
+// segment's mask, and the segment's first lane adds them to site[r] with one 64-bit atomic.  Every ballot is executed by all 64 lanes on
+// every trip: the loop's bound is the WAVE's first item, and lanes beyond the last item take part with "not called".  (blocks of a multiple
+// of 64 threads)
+__global__ __launch_bounds__(TPB) void k_genotype_cohort(GenoCohortArgs p) {
+  const GenoArgs &a = p.g;
+  const uint64_t S = p.n_samples, n_items = a.n_rows * S;
+  const uint32_t lane = threadIdx.x & 63u;
+  for (uint64_t w0 = (uint64_t)blockIdx.x * blockDim.x + (threadIdx.x - lane); w0 < n_items; w0 += (uint64_t)gridDim.x * blockDim.x) {
+    const uint64_t i = w0 + lane;
+    uint64_t r = 0, s = 0;
+    uint8_t gt = 3;
+    if (i < n_items) {
+        r = i / S; s = i - r * S;
+        uint32_t ref = 0, alt = 0;
+        bool go = false;
+        const uint32_t ok = a.ok[r], sl = a.slot[r];
+        if (sl != NONE32 && sl >= a.n_slots) atomicOr(a.max_n + 1, 1u);       // a caller error, reported after the pass
+        else if ((ok & 1u) && sl != NONE32) {
+            const uint64_t at = (uint64_t)sl * S + s;
+            if (p.present[at]) { const unsigned long long c = a.counts[at]; ref = (uint32_t)c; alt = (uint32_t)(c >> 32); go = true; }
+        }
+        a.raw[i * 2] = ref; a.raw[i * 2 + 1] = alt;
+        a.genotyped[i] = go;
+        uint8_t near = 0;
+        int64_t pl0 = 0, pl1 = 0, pl2 = 0;
+        if (go) {
+            GenoRow o;
+            const uint32_t st = geno_row(a.sv_type[r], ref, alt, a.min_support, a.l_ok, a.l_err, a.l_half, a.logfact, a.logfact_n, o);
+            if (st == GENO_ROW_GROW) atomicMax(a.max_n, (uint32_t)o.n);        // the table is too short: the host grows it and runs the items again
+            gt = o.gt; near = o.near; pl0 = o.pl[0]; pl1 = o.pl[1]; pl2 = o.pl[2];
+        }
+        a.gt[i] = gt; a.boundary[i] = near;
+        a.pl[i * 3] = pl0; a.pl[i * 3 + 1] = pl1; a.pl[i * 3 + 2] = pl2;
+    }
+    const uint64_t called = __ballot(gt != 3), het = __ballot(gt == 1), hom = __ballot(gt == 2);
+    const CohortSeg seg = cohort_segment(i, s, S, lane, n_items);
+    if (seg.leader) {
+        const unsigned long long ns = (unsigned long long)__popcll(called & seg.mask);
+        const unsigned long long ac = (unsigned long long)__popcll(het & seg.mask) + 2ull * (unsigned long long)__popcll(hom & seg.mask);
+        if (ns) atomicAdd(p.site + r, ns | (ac << 32));
+    }
   }
 }
 

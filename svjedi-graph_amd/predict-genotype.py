@@ -2,6 +2,7 @@
 """Drop-in for SVJedi-graph's predict-genotype.py (same flags, same files) running on an MI355X.
 
     predict-genotype.py -d P_informative_aln.json -v VCF --minsupport N -o P_genotype.vcf   (svjedi-graph.py:124)
+    predict-genotype.py --cohort LIST -v VCF --minsupport N -o COHORT_genotype.vcf          (extension: one column per sample)
 """
 import argparse
 import os
@@ -12,7 +13,8 @@ sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 
 def main():
     ap = argparse.ArgumentParser(description="Structural variations genotyping using long reads")
-    ap.add_argument("-d", "--aln", metavar="<alndict>", nargs=1, required=True)
+    # -d stays required when --cohort is absent: every command line of the reference parses, and fails, as before
+    ap.add_argument("-d", "--aln", metavar="<alndict>", nargs=1, required=not any(a == "--cohort" or a.startswith("--cohort=") for a in sys.argv[1:]))
     ap.add_argument("-v", "--vcf", metavar="<vcffile>", help="vcf format", required=True)
     ap.add_argument("-o", "--output", metavar="<output>", nargs=1, help="output file")
     ap.add_argument("-e", "--err", nargs=1, type=float, help="allele error probability")
@@ -24,12 +26,22 @@ def main():
                     help="per-contig or per-region ploidy, 0..8: lines `CHROM PLOIDY` or `CHROM FROM TO PLOIDY` (extension)")
     ap.add_argument("--joint-ins", action="store_true",
                     help="genotype insertions that share a CHROM and POS together, 2..6 per site, diploid only (extension)")
+    ap.add_argument("--cohort", metavar="<samplelist>",
+                    help="many samples, one multi-sample VCF with NS / AN / AC / AF in INFO: lines `NAME<TAB>PATH_TO_informative_aln.json` "
+                         "(extension; takes the place of -d; diploid, row by row)")
     args = ap.parse_args()
+    if args.cohort is not None and args.aln is not None:
+        ap.error("exactly one of -d and --cohort")
+    if args.cohort is not None and (args.ploidy is not None or args.ploidy_file is not None or args.joint_ins):
+        ap.error("--cohort is diploid, row by row: it cannot be combined with --ploidy, --ploidy-file or --joint-ins")
     if args.joint_ins and (args.ploidy is not None or args.ploidy_file is not None):
         ap.error("--joint-ins is diploid only: it cannot be combined with --ploidy or --ploidy-file")
     out = "genotype_results.txt" if args.output is None else args.output[0]
     err = args.err[0] if args.err is not None else 0.00005
     from svjg import genotype
+    if args.cohort is not None:
+        genotype.run_cohort(args.cohort, args.vcf, out, args.minsupport, err)
+        return
     genotype.run(args.aln[0], args.vcf, out, args.minsupport, err, ploidy=args.ploidy, ploidy_file=args.ploidy_file, joint_ins=args.joint_ins)
 
 

@@ -85,6 +85,11 @@ _SIGS = {
                                           ctypes.c_uint32, ctypes.c_double] + [ctypes.POINTER(ctypes.c_void_p)] * 4),
     "svjg_genotype_ploidy": (ctypes.c_int, [ctypes.c_void_p] * 5 + [ctypes.c_uint64, ctypes.c_uint32, ctypes.c_double] + [ctypes.c_void_p] * 5),
     "svjg_genotype_sites": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_uint32, ctypes.c_double] + [ctypes.c_void_p] * 4),
+    "svjg_cohort_alloc": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_uint32, ctypes.c_uint32]),
+    "svjg_cohort_set_counts": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_uint32, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64]),
+    "svjg_cohort_store_counts": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_uint32]),
+    "svjg_cohort_get_counts": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_uint32, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint32]),
+    "svjg_genotype_cohort": (ctypes.c_int, [ctypes.c_void_p] * 4 + [ctypes.c_uint64, ctypes.c_uint32, ctypes.c_double] + [ctypes.c_void_p] * 6),
     "svjg_set_rows": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64]),
     "svjg_run_resident": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_uint64, ctypes.c_uint32, ctypes.c_double] + [ctypes.POINTER(ctypes.c_void_p)] * 5),
     "svjg_run_begin": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_uint64, ctypes.c_uint32, ctypes.c_double]),
@@ -508,6 +513,52 @@ class Context:
         self._chk(self.lib.svjg_genotype_sites(self.h, slots.ctypes.data, n, min_support, float(err), gt.ctypes.data, pl.ctypes.data,
                                                raw.ctypes.data, boundary.ctypes.data))
         return gt, pl, raw, boundary
+
+    def cohort_alloc(self, n_samples, n_slots):
+        """a zeroed count matrix of n_samples x n_slots with its presence bytes (svjg_cohort_alloc); a second call replaces it"""
+        self._chk(self.lib.svjg_cohort_alloc(self.h, int(n_samples), int(n_slots)))
+        self._cohort = (int(n_samples), int(n_slots))
+
+    def cohort_set_counts(self, sample, slots, counts):
+        """the slots `sample` has as keys with their (ref, alt) counts[k]; every other slot of the sample becomes absent (svjg_cohort_set_counts)"""
+        slots = np.ascontiguousarray(slots, dtype=np.uint32)
+        counts = np.ascontiguousarray(counts, dtype=np.uint32).reshape(-1, 2)
+        if len(slots) != len(counts) or slots.ndim != 1:
+            raise SvjgError("cohort_set_counts: one (ref, alt) pair per slot")
+        n = len(slots)
+        self._chk(self.lib.svjg_cohort_set_counts(self.h, int(sample), slots.ctypes.data if n else None, counts.ctypes.data if n else None, n))
+
+    def cohort_store_counts(self, sample):
+        """the context's current count vector -> column `sample`, on the device; presence = a non-zero count (svjg_cohort_store_counts)"""
+        self._chk(self.lib.svjg_cohort_store_counts(self.h, int(sample)))
+
+    def cohort_get_counts(self, sample):
+        """-> (counts[n_slots, 2], present[n_slots]) of one sample (svjg_cohort_get_counts)"""
+        n_slots = getattr(self, "_cohort", (0, 0))[1]
+        out = np.zeros((n_slots, 2), dtype=np.uint32)
+        present = np.zeros(n_slots, dtype=np.uint8)
+        self._chk(self.lib.svjg_cohort_get_counts(self.h, int(sample), out.ctypes.data, present.ctypes.data, n_slots))
+        return out, present
+
+    def genotype_cohort(self, sv_type, slot, ok, min_support, err):
+        """Every row against every sample of the cohort matrix (svjg_genotype_cohort; ok bit 1 is ignored: the presence bytes decide).
+        -> (gt[n, S], pl[n, S, 3], raw[n, S, 2], genotyped[n, S], boundary[n, S] = the items to recompute with svjg.genotype.exact_pl,
+        site[n, 2] = NS and AC of each row)"""
+        n = len(sv_type)
+        S = getattr(self, "_cohort", (0, 0))[0]
+        sv_type = np.ascontiguousarray(sv_type, dtype=np.uint8)
+        slot = np.ascontiguousarray(slot, dtype=np.uint32)
+        ok = np.ascontiguousarray(ok, dtype=np.uint8)
+        gt = np.empty((n, S), dtype=np.uint8)
+        pl = np.empty((n, S, 3), dtype=np.int64)
+        raw = np.empty((n, S, 2), dtype=np.uint32)
+        done = np.empty((n, S), dtype=np.uint8)
+        boundary = np.empty((n, S), dtype=np.uint8)
+        site = np.empty((n, 2), dtype=np.uint32)
+        self._chk(self.lib.svjg_genotype_cohort(self.h, sv_type.ctypes.data, slot.ctypes.data, ok.ctypes.data, n, min_support, float(err),
+                                                gt.ctypes.data, pl.ctypes.data, raw.ctypes.data, done.ctypes.data, boundary.ctypes.data,
+                                                site.ctypes.data))
+        return gt, pl, raw, done, boundary, site
 
     def set_rows(self, sv_type, slot, ok):
         """the VCF rows' input arrays of genotype(), left on the device for run_resident()"""

@@ -462,6 +462,151 @@ def genotype_with_counts_joint(ctx, vcf_path, slot_of, out_path, min_support, er
     return write_vcf_joint(out_path, rows, gt, pl, raw, done, member)
 
 
+# ---- cohort (--cohort): many samples' counts, one multi-sample VCF: svjg_genotype_cohort, Python rows and the writer below ----
+
+COHORT_INFO_LINES = (
+    '##INFO=<ID=NS,Number=1,Type=Integer,Description="Number of samples with a called genotype">\n'
+    '##INFO=<ID=AN,Number=1,Type=Integer,Description="Total number of alleles in called genotypes">\n'
+    '##INFO=<ID=AC,Number=A,Type=Integer,Description="Allele count in called genotypes">\n'
+    '##INFO=<ID=AF,Number=A,Type=Float,Description="Allele frequency in called genotypes: AC / AN">\n'
+)
+_SITE_TAGS = ("NS=", "AN=", "AC=", "AF=")
+COHORT_ITEM_BYTES = 37             # svjg.h: what one (row, sample) item takes in a svjg_genotype_cohort call
+COHORT_CALL_BYTES = 1 << 30
+
+
+def load_cohort_list(path):
+    """-> [(name, json_path)] in file order.  One sample per line, `NAME<TAB>PATH_TO_informative_aln.json`; `#` lines and empty lines are
+    skipped; a relative path is relative to the list's directory.  ValueError naming file and line for anything else: a line without exactly
+    two fields, an empty name or path, a name given twice."""
+    import os
+    here = os.path.dirname(os.path.abspath(path))
+    out, seen = [], set()
+    with open(path) as fh:
+        for no, line in enumerate(fh, 1):
+            text = line.rstrip("\n").rstrip("\r")
+            if not text or text.startswith("#"):
+                continue
+            f = text.split("\t")
+            if len(f) != 2 or not f[0] or not f[1]:
+                raise ValueError("%s:%d: expected `NAME<TAB>PATH`: %r" % (path, no, text))
+            if f[0] in seen:
+                raise ValueError("%s:%d: sample name %r is given twice" % (path, no, f[0]))
+            seen.add(f[0])
+            out.append((f[0], f[1] if os.path.isabs(f[1]) else os.path.join(here, f[1])))
+    if not out:
+        raise ValueError("%s: no sample" % path)
+    return out
+
+
+def cohort_union(samples):
+    """samples: [(keys, counts[n, 2])], one per sample -> (union of the keys in first-seen order, [(slots, counts)] per sample: the slots the
+    sample has as keys, each once; a key repeated within one sample: the last one wins, like json.load)"""
+    slot_of, per = {}, []
+    for keys, counts in samples:
+        last = {}
+        for i, k in enumerate(keys):
+            if k not in slot_of:
+                slot_of[k] = len(slot_of)
+            last[slot_of[k]] = i
+        slots = np.fromiter(last.keys(), dtype=np.uint32, count=len(last))
+        at = np.fromiter(last.values(), dtype=np.int64, count=len(last))
+        per.append((slots, np.asarray(counts, dtype=np.uint32).reshape(-1, 2)[at]))
+    return list(slot_of), per
+
+
+def cohort_info(info, ns, ac):
+    """the INFO column of a cohort row: the input's without any NS= / AN= / AC= / AF= field (whole fields, exact key), a lone `.` replaced,
+    then NS, AN = 2 NS, AC and, when AN > 0, AF = "%.6g" % (AC / AN)"""
+    keep = [f for f in info.split(";") if not f.startswith(_SITE_TAGS)]
+    if keep == ["."]:
+        keep = []
+    an = 2 * ns
+    keep += ["NS=%d" % ns, "AN=%d" % an, "AC=%d" % ac]
+    if an > 0:
+        keep.append("AF=%s" % ("%.6g" % (ac / an)))
+    return ";".join(keep)
+
+
+def write_vcf_cohort(out_path, rows, names, gt, pl, raw, done, site):
+    """write_vcf with one column per sample (gt, done: [n, S]; pl: [n, S, 3]; raw: [n, S, 2]; site: [n, 2] = NS, AC) and the site tags in
+    INFO -> the number of genotyped rows of every sample"""
+    S = len(names)
+    n_done = [0] * S
+    with open(out_path, "w") as out:
+        for kind, v in rows.items:
+            if kind == "h":
+                if v is FORMAT_HEADER:
+                    v = COHORT_INFO_LINES + v.replace("\tFORMAT\tSAMPLE\n", "\tFORMAT\t" + "\t".join(names) + "\n")
+                out.write(v)
+                continue
+            first7, info = rows.prefix[v].rsplit("\t", 1)
+            cols = []
+            t = int(rows.sv_type[v])
+            for s in range(S):
+                if done[v, s]:
+                    n_done[s] += 1
+                    dp, ad = _fmt_counts(t, int(raw[v, s, 0]), int(raw[v, s, 1]))
+                    cols.append("%s:%s:%s:%d,%d,%d" % (GT_TEXT[gt[v, s]], dp, ad, pl[v, s, 0], pl[v, s, 1], pl[v, s, 2]))
+                else:
+                    cols.append("./.:0:0,0:.,.,.")
+            out.write(first7 + "\t" + cohort_info(info, int(site[v, 0]), int(site[v, 1])) + "\tGT:DP:AD:PL\t" + "\t".join(cols) + "\n")
+    return n_done
+
+
+def cohort_chunk_rows(n_samples):
+    """rows per svjg_genotype_cohort call: n_rows x S x 37 bytes stays under 1 GiB"""
+    return max(1, COHORT_CALL_BYTES // (COHORT_ITEM_BYTES * max(1, int(n_samples))))
+
+
+def genotype_cohort_rows(ctx, rows, n_samples, min_support, err):
+    """the rows of a VcfRows against the context's cohort matrix, in row chunks -> (gt, pl, raw, done, site) over all rows, the flagged items
+    recomputed by exact_pl (the GT does not depend on the PL integers: NS and AC stay as the kernel gave them)"""
+    n, S = len(rows.sv_type), int(n_samples)
+    min_support = max(0, int(min_support))
+    bad_err = not (0.0 < float(err) < 1.0)
+    step = cohort_chunk_rows(S)
+    parts = []
+    for at in range(0, n, step):
+        gt, pl, raw, done, boundary, site = ctx.genotype_cohort(rows.sv_type[at:at + step], rows.slot[at:at + step], rows.ok[at:at + step],
+                                                                min_support, 0.5 if bad_err else err)
+        if bad_err and done.any():
+            raise ValueError("math domain error")               # (as genotype_with_counts: the reference dies at the first genotyped row)
+        for r, s in zip(*np.nonzero((boundary != 0) & (done != 0))):
+            pl[r, s] = exact_pl(int(rows.sv_type[at + r]), int(raw[r, s, 0]), int(raw[r, s, 1]), err)
+        parts.append((gt, pl, raw, done, site))
+    if not parts:
+        return (np.zeros((0, S), np.uint8), np.zeros((0, S, 3), np.int64), np.zeros((0, S, 2), np.uint32), np.zeros((0, S), np.uint8),
+                np.zeros((0, 2), np.uint32))
+    return tuple(np.concatenate([p[k] for p in parts]) for k in range(5))
+
+
+def run_cohort(list_path, vcf_path, out_path, min_support=3, err=0.00005, device=0):
+    """predict-genotype.py --cohort: the samples of a cohort list (load_cohort_list), one multi-sample VCF.  Sample column s is what the
+    reference writes as SAMPLE for sample s alone; INFO gains NS, AN, AC and AF.  -> the number of genotyped rows of every sample"""
+    from . import capi, filter as flt
+    samples = load_cohort_list(list_path)                        # (raises before any output exists)
+    loaded = []
+    for _, path in samples:
+        got = flt.read_handoff(path)                             # left by our filter-alignments.py for exactly this file, else None
+        loaded.append(got if got is not None else capi.count_informative_json(path))
+    keys, per = cohort_union(loaded)
+    rows = VcfRows(vcf_path, {k: i for i, k in enumerate(keys)})
+    names = [name for name, _ in samples]
+    ctx = capi.Context(device)
+    try:
+        ctx.cohort_alloc(len(samples), len(keys))
+        for s, (slots, counts) in enumerate(per):
+            ctx.cohort_set_counts(s, slots, counts)
+        gt, pl, raw, done, site = genotype_cohort_rows(ctx, rows, len(samples), min_support, err)
+    finally:
+        ctx.close()
+    n_done = write_vcf_cohort(out_path, rows, names, gt, pl, raw, done, site)
+    for name, n in zip(names, n_done):
+        print("Genotyped svs (%s): %d" % (name, n))
+    return n_done
+
+
 def write_vcf(out_path, rows, gt, pl, raw, done):
     n_done = 0
     with open(out_path, "w") as out:
