@@ -219,6 +219,19 @@ int svjg_genotype_boundary(svjg_ctx *ctx, uint8_t *out, uint64_t n_rows);
 int svjg_genotype_view(svjg_ctx *ctx, const uint8_t *sv_type, const uint32_t *slot, const uint8_t *ok,
                        uint64_t n_rows, uint32_t min_support, double err,
                        const uint8_t **gt, const int64_t **pl, const uint32_t **raw, const uint8_t **genotyped);
+/* The table the binomial term of every genotype call comes from: log10(i!) in double-double, entry i = (hi, lo), built on the device
+ * with the device's log10 (k_logfact_*), 65 536 entries at a context's first genotype call, rebuilt larger inside a call that meets
+ * n = r1 + r2 beyond it, never more than 2^24 entries (256 MB).
+ *   svjg_logfact_reserve  afterwards the table holds at least `entries` (capped at 2^24, rounded up to a multiple of 1024).  It never
+ *                         shrinks the table and does nothing when it is large enough already.  Before a rebuild the context's streams
+ *                         drain: a pass in flight still reads the old table.  Called once behind svjg_init it takes the build (and a
+ *                         later growth) out of the first genotype call, e.g. one that is timed.
+ *   svjg_logfact_read     out[k*2], out[k*2+1] = hi, lo of entry first + k, k < n, copied synchronously; *entries (may be NULL) = the
+ *                         table's size, 0 while none has been built.  n = 0 with out = NULL asks for the size alone.  SVJG_E_ARG with a
+ *                         message in svjg_last_error: first + n beyond the size, out = NULL with n > 0.
+ * Read-only access for tests and diagnostics (tests/test_logfact_gpu.py pins every entry): nothing in the product reads the table back. */
+int svjg_logfact_reserve(svjg_ctx *ctx, uint32_t entries);
+int svjg_logfact_read(svjg_ctx *ctx, uint32_t first, uint32_t n, double *out, uint32_t *entries);
 
 /* Any ploidy from 1 to SVJG_MAX_PLOIDY, row by row: ploidy[r] in 0..SVJG_MAX_PLOIDY beside the three inputs of svjg_genotype.  A row of
  * ploidy P has P + 1 genotypes, g = 0..P alt copies; a read shows the alt allele with probability (g (1 - e) + (P - g) e) / P, which at

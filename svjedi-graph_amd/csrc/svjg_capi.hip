@@ -921,8 +921,8 @@ extern "C" int svjg_allreduce_counts_all(svjg_ctx *const *ctxs, int n) {
 // table of log10(i!) in double-double for the binomial term, at least `upto` entries and at most LOGFACT_CAP (svjg_geno.h: rows beyond
 // the cap are recomputed on the host) (kernels on the context's stream; no host wait)
 static int build_logfact(svjg_ctx *c, uint32_t upto) {
-    if (upto > LOGFACT_CAP) upto = LOGFACT_CAP;
-    const uint32_t want = (upto + LF_BLOCK - 1) / LF_BLOCK * LF_BLOCK;
+    static_assert(LF_BLOCK == LOGFACT_BLOCK, "svjg_kernels.h and svjg_geno.h disagree");
+    const uint32_t want = logfact_built(upto);
     hipFree(c->d_logfact); hipFree(c->d_bsum); c->d_logfact = nullptr; c->d_bsum = nullptr; c->logfact_n = 0;
     HIPCHK(c, hipMalloc((void **)&c->d_logfact, (uint64_t)want * sizeof(dd)));
     HIPCHK(c, hipMalloc((void **)&c->d_bsum, (uint64_t)(want / LF_BLOCK) * sizeof(dd)));
@@ -1503,6 +1503,34 @@ extern "C" int svjg_run_resident(svjg_ctx *c, uint64_t base_offset, uint32_t min
 extern "C" int svjg_genotype_boundary(svjg_ctx *c, uint8_t *out, uint64_t n_rows) {
     if (!c || (n_rows && !out) || n_rows != c->geno_rows || !c->h_rows) return SVJG_E_ARG;
     memcpy(out, (const uint8_t *)c->h_rows + rows_layout(n_rows).boundary, n_rows);
+    return 0;
+}
+
+// ---- the log10(i!) table from outside: build it ahead of a first call, read it back (svjg.h) ----
+
+extern "C" int svjg_logfact_reserve(svjg_ctx *c, uint32_t entries) {
+    if (!c) return SVJG_E_ARG;
+    const uint32_t want = logfact_reserve_to(c->logfact_n, entries);
+    if (!want) return 0;
+    HIPCHK(c, hipSetDevice(c->device));
+    HIPCHK(c, hipStreamSynchronize(c->stream));                  // (as settle_launch: a pass already enqueued still uses the old table)
+    if (c->copy_stream) HIPCHK(c, hipStreamSynchronize(c->copy_stream));
+    return build_logfact(c, want);
+}
+
+extern "C" int svjg_logfact_read(svjg_ctx *c, uint32_t first, uint32_t n, double *out, uint32_t *entries) {
+    if (!c) return SVJG_E_ARG;
+    if (entries) *entries = c->logfact_n;
+    if ((uint64_t)first + n > c->logfact_n) {
+        c->err = "svjg_logfact_read: entries " + std::to_string(first) + " .. " + std::to_string((uint64_t)first + n) + " of a table of " + std::to_string(c->logfact_n);
+        return SVJG_E_ARG;
+    }
+    if (n == 0) return 0;
+    if (!out) { c->err = "svjg_logfact_read: no buffer"; return SVJG_E_ARG; }
+    static_assert(sizeof(dd) == 2 * sizeof(double), "an entry is a (hi, lo) pair");
+    HIPCHK(c, hipSetDevice(c->device));
+    HIPCHK(c, hipMemcpyAsync(out, c->d_logfact + first, (uint64_t)n * sizeof(dd), hipMemcpyDeviceToHost, c->stream));   // (behind the build, on its stream)
+    HIPCHK(c, hipStreamSynchronize(c->stream));
     return 0;
 }
 

@@ -44,11 +44,18 @@ SVJG_HD int64_t trunc_dd(dd v) {                         // int(Decimal): toward
 constexpr uint32_t LOGFACT_CAP = 1u << 24;
 
 // A row is flagged for the host when one of its three -10 * (lik + comb) lies within PL_GUARD of an integer.  The budget, for
-// n < LOGFACT_CAP: every table entry is a sum of at most n values log10(i) < 7.3, each within 1 ulp (2^-50) if the device log10
-// is (assumed, not measured), summed in double-double: |table error| <= 2^24 * 2^-50 = 1.5e-8 per entry, and comb takes one
+// n < LOGFACT_CAP: every table entry is a sum of at most n values log10(i) < 7.3, each within 1 ulp (2^-50) of the true value,
+// summed in double-double: |table error| <= 2^24 * 2^-50 = 1.5e-8 per entry, and comb takes one
 // entry of n terms and two of n terms together: <= 3e-8.  The reference's log10 of a big integer goes through CPython's frexp
 // path, log10(x) + log10(2) * e: a few ulps of L = log10(comb) <= 5.1e6 (ulp 9.3e-10): <= 4e-9.  Both sides round L to a
 // double (1 ulp each).  The likelihood sums are exact here and at 28 digits in the reference.  Times ten: < 3.6e-7 < 1e-6.
+// The "1 ulp" of the device's log10 is measured, not assumed (2026-10-18, one MI355X, ROCm 7.2.0; the table at the cap read back through
+// svjg_logfact_read and held against 60-digit values, tests/test_logfact_gpu.py asserts each bound on every run): all 2^24 - 2 increments
+// table[i] - table[i-1] lie within 0.504 * 2^-50 of log10(i) (worst at i = 5 638 997: the device's log10 is correctly rounded or next to
+// it), the worst entry of 5 450 sampled is 7.6e-12 off (i = 16 344 492; the roundings cancel, they do not add up: 1/2000 of the 1.5e-8),
+// and 10 * |comb from the table - the reference's double| is at most 4.7e-9 over 8 846 pairs (n, k) = (13 266 267, 1 927 482): one ulp of
+// L, against the 3.6e-7 above.  The table the CPU stand-ins build with the host's libm (tests/hostsim) differs from the device's in
+// 16 777 051 of 2^24 entries, by at most 2.2e-11 (i = 11 186 418).
 constexpr double PL_GUARD = 1e-6;
 
 // normalised counts (predict-genotype.py:327-338) and the rounded ones fed to comb()
@@ -321,6 +328,11 @@ SVJG_HD CohortSeg cohort_segment(uint64_t i, uint64_t s, uint64_t S, uint32_t la
 // entries of the log10(i!) table: the first one built; the one that holds max_n (the largest n the kernel met beyond the table, < LOGFACT_CAP) with room to spare
 constexpr uint32_t logfact_first() { return 65536; }
 constexpr uint32_t logfact_grow_to(uint32_t max_n) { return max_n < LOGFACT_CAP - 1024 ? max_n + 1 + 1024 : LOGFACT_CAP; }
+// entries a build for `upto` makes: capped, then whole blocks of the table kernels (LOGFACT_BLOCK = LF_BLOCK of svjg_kernels.h)
+constexpr uint32_t LOGFACT_BLOCK = 1024;
+constexpr uint32_t logfact_built(uint32_t upto) { return ((upto > LOGFACT_CAP ? LOGFACT_CAP : upto) + LOGFACT_BLOCK - 1) / LOGFACT_BLOCK * LOGFACT_BLOCK; }
+// svjg_logfact_reserve: the table has `have` entries (0: none yet) and `entries` are asked for -> the size to build, 0: nothing to do (never a smaller table)
+constexpr uint32_t logfact_reserve_to(uint32_t have, uint32_t entries) { return logfact_built(entries) > have ? logfact_built(entries) : 0; }
 
 // the three input arrays of n rows, back to back from byte `at` of a block: [ slot 4 | type 1 | ok 1 ] x n
 struct RowsIn { uint64_t slot, type, ok, bytes; };

@@ -95,6 +95,8 @@ _SIGS = {
     "svjg_run_begin": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_uint64, ctypes.c_uint32, ctypes.c_double]),
     "svjg_run_end": (ctypes.c_int, [ctypes.c_void_p] + [ctypes.POINTER(ctypes.c_void_p)] * 5),
     "svjg_genotype_boundary": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64]),
+    "svjg_logfact_reserve": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_uint32]),
+    "svjg_logfact_read": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_void_p, ctypes.POINTER(ctypes.c_uint32)]),
     "svjg_last_kernel_ms": (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(ctypes.c_float), ctypes.POINTER(ctypes.c_float),
                                            ctypes.POINTER(ctypes.c_float)]),
     "svjg_last_main_ms": (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(ctypes.c_float), ctypes.POINTER(ctypes.c_float)]),
@@ -607,6 +609,32 @@ class Context:
         out = np.zeros(n_rows, dtype=np.uint8)
         if n_rows:
             self._chk(self.lib.svjg_genotype_boundary(self.h, out.ctypes.data, n_rows))
+        return out
+
+    def logfact_reserve(self, n):
+        """the log10(i!) table holds at least n entries afterwards (capped at 2^24, whole blocks of 1024; never smaller than it was): the table
+        build taken out of a first genotype call (svjg_logfact_reserve)"""
+        if not 0 <= int(n) < 2 ** 32:
+            raise SvjgError("logfact_reserve: 0 <= n < 2^32")
+        self._chk(self.lib.svjg_logfact_reserve(self.h, int(n)))
+
+    def logfact_entries(self):
+        """entries of the log10(i!) table right now, 0 before the context's first genotype call or reserve (svjg_logfact_read)"""
+        n = ctypes.c_uint32(0)
+        self._chk(self.lib.svjg_logfact_read(self.h, 0, 0, None, ctypes.byref(n)))
+        return n.value
+
+    def logfact_table(self, first=0, n=None):
+        """entries first .. first + n of the device's log10(i!) table (n = None: all from `first`) -> float64[n, 2] = (hi, lo)
+        (svjg_logfact_read); SvjgError beyond the table's end"""
+        first = int(first)
+        if n is None:
+            n = self.logfact_entries() - first
+        n = int(n)
+        if first < 0 or n < 0 or first + n >= 2 ** 32:
+            raise SvjgError("logfact_table: entries %d .. %d" % (first, first + n))
+        out = np.empty((n, 2), dtype=np.float64)
+        self._chk(self.lib.svjg_logfact_read(self.h, first, n, out.ctypes.data if n else None, None))
         return out
 
     def kernel_ms(self):

@@ -296,6 +296,8 @@ extern "C" uint64_t hostsim_sizeof_devstatus(void) { return sizeof(DevStatus); }
 extern "C" uint32_t hostsim_logfact_first(void) { return logfact_first(); }
 extern "C" uint32_t hostsim_logfact_grow_to(uint32_t max_n) { return logfact_grow_to(max_n); }
 extern "C" uint32_t hostsim_logfact_cap(void) { return LOGFACT_CAP; }
+extern "C" uint32_t hostsim_logfact_built(uint32_t upto) { return logfact_built(upto); }
+extern "C" uint32_t hostsim_logfact_reserve_to(uint32_t have, uint32_t entries) { return logfact_reserve_to(have, entries); }
 
 // the log10(i!) table of k_logfact_* with the HOST libm's log10 (not the device's), summed in order in double-double (the kernels
 // sum in blocks: the association differs, both far below the guard's budget)

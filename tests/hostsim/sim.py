@@ -152,6 +152,16 @@ def geno_constants():
             lambda m: int(lib.hostsim_logfact_grow_to(m)))
 
 
+def logfact_sizes():
+    """(logfact_built(upto): the entries a build for `upto` makes, logfact_reserve_to(have, entries): the size svjg_logfact_reserve builds or 0)
+    of svjg_geno.h"""
+    lib = ctypes.CDLL(build())
+    lib.hostsim_logfact_built.restype = lib.hostsim_logfact_reserve_to.restype = ctypes.c_uint32
+    lib.hostsim_logfact_built.argtypes = [ctypes.c_uint32]
+    lib.hostsim_logfact_reserve_to.argtypes = [ctypes.c_uint32, ctypes.c_uint32]
+    return (lambda u: int(lib.hostsim_logfact_built(u))), (lambda h, e: int(lib.hostsim_logfact_reserve_to(h, e)))
+
+
 def logfact_table(n):
     """log10(i!) for i < n in double-double (float64[n, 2]), built with the host libm's log10 — not the device's"""
     lib = ctypes.CDLL(build())
