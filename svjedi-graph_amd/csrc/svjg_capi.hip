@@ -76,6 +76,11 @@ extern "C" void svjg_release_host_tables(void) {
 constexpr int STAGE_THREADS = 4;
 constexpr uint64_t STAGE_PIECE = 8ull << 20;
 
+// The device block of a step-by-step genotype call and its pinned host twin (genotype_leg).  Every call has a block of its own: svjg_genotype_view
+// hands out pointers into BLOCK_ROWS' twin and svjg_genotype_boundary reads it later, and both must survive calls of the other three.
+struct LegBlock { void *d = nullptr;  uint64_t d_cap = 0;  void *h = nullptr;  uint64_t h_cap = 0; };
+enum { BLOCK_ROWS, BLOCK_PLOIDY, BLOCK_SITES, BLOCK_COHORT, LEG_BLOCKS };   // rows_layout, ploidy_layout, sites_layout, cohort_layout (svjg_geno.h)
+
 // slots the passes of svjg_run_begin rotate through: two may be in flight, and the one the NEXT pass will use is zeroed while the newest computes
 constexpr int RUN_SLOTS = 3;
 
@@ -112,19 +117,12 @@ struct svjg_ctx {
     uint64_t total_deferred = 0;
     // genotype scratch
     dd *d_logfact = nullptr;  uint32_t logfact_n = 0;  dd *d_bsum = nullptr;
-    void *d_rows = nullptr;  uint64_t rows_cap = 0;
-    void *h_rows = nullptr;  uint64_t h_rows_cap = 0;   // pinned twin of d_rows
+    LegBlock leg[LEG_BLOCKS];
     uint64_t geno_rows = 0;                              // rows of the last svjg_genotype / svjg_genotype_view (svjg_genotype_boundary)
-    void *d_prows = nullptr;  uint64_t prows_cap = 0;    // svjg_genotype_ploidy's own block and pinned twin (ploidy_layout): the views and the
-    void *h_prows = nullptr;  uint64_t h_prows_cap = 0;  // boundary bytes of the calls above stay as they are
-    void *d_srows = nullptr;  uint64_t srows_cap = 0;    // svjg_genotype_sites' own block and pinned twin (sites_layout), for the same reason
-    void *h_srows = nullptr;  uint64_t h_srows_cap = 0;
-    // cohort: the slot-major count matrix (svjg_cohort_alloc: counts, then the presence bytes, ONE allocation), the dense vector a sample's
-    // column is staged in, and svjg_genotype_cohort's own block and pinned twin (cohort_layout), for the same reason
+    // cohort: the slot-major count matrix (svjg_cohort_alloc: counts, then the presence bytes, ONE allocation) and the dense vector a sample's
+    // column is staged in
     unsigned long long *d_cm = nullptr;  uint8_t *d_cpresent = nullptr;  uint32_t cohort_samples = 0, cohort_slots = 0;
     void *d_cstage = nullptr;  uint64_t cstage_cap = 0;
-    void *d_crows = nullptr;  uint64_t crows_cap = 0;
-    void *h_crows = nullptr;  uint64_t h_crows_cap = 0;
     // resident VCF rows of svjg_set_rows / svjg_run_resident: device block (results, row inputs) and the pinned host block the results land in
     struct RunSlot {
         void *d = nullptr;  uint64_t d_cap = 0;  void *h = nullptr;  uint64_t h_cap = 0;  void *h_dev = nullptr;   // h_dev: the pinned block as the device sees it
@@ -217,9 +215,9 @@ extern "C" void svjg_destroy(svjg_ctx *c) {
     free_graph(c);
     hipFree(c->d_long);
     hipFree(c->d_gaf); hipFree(c->d_deferred); hipFree(c->d_recs); hipFree(c->d_host); hipFree(c->d_st); hipFree(c->d_logfact);
-    hipFree(c->d_bsum); hipFree(c->d_rows); hipFree(c->d_prows); hipFree(c->d_srows); hipFree(c->d_run_in);
-    hipFree(c->d_cm); hipFree(c->d_cstage); hipFree(c->d_crows);
-    if (c->h_crows) hipHostFree(c->h_crows);
+    hipFree(c->d_bsum); hipFree(c->d_run_in);
+    hipFree(c->d_cm); hipFree(c->d_cstage);
+    for (auto &b : c->leg) { hipFree(b.d); if (b.h) hipHostFree(b.h); }
     for (auto &r : c->run) {
         hipFree(r.d); hipFree(r.counts);
         if (r.h) hipHostFree(r.h);
@@ -227,9 +225,6 @@ extern "C" void svjg_destroy(svjg_ctx *c) {
         if (r.computed) hipEventDestroy(r.computed);
         if (r.copied) hipEventDestroy(r.copied);
     }
-    if (c->h_rows) hipHostFree(c->h_rows);
-    if (c->h_prows) hipHostFree(c->h_prows);
-    if (c->h_srows) hipHostFree(c->h_srows);
     if (c->h_stp) hipHostFree(c->h_stp);
     for (auto &b : c->h_stage) if (b) hipHostFree(b);
     for (auto &ev : c->stage_ev) if (ev) hipEventDestroy(ev);
@@ -934,7 +929,7 @@ static int build_logfact(svjg_ctx *c, uint32_t upto) {
     return 0;
 }
 
-// ---- one genotype leg, for the step-by-step calls (genotype_rows) and the fused pass alike ----
+// ---- one genotype leg, for the four step-by-step calls (genotype_leg) and the fused pass alike ----
 // k_genotype's arguments but where the results go (the callers' layouts, svjg_geno.h); p: device block with the rows' inputs at I
 static GenoArgs geno_args(const svjg_ctx *c, const unsigned long long *counts, const uint8_t *p, const RowsIn &I, uint64_t n_rows, uint32_t min_support, double err) {
     GenoArgs a{};
@@ -943,24 +938,30 @@ static GenoArgs geno_args(const svjg_ctx *c, const unsigned long long *counts, c
     a.l_ok = log10(1.0 - err); a.l_err = log10(err); a.l_half = log10(1.0 / 2.0);     // host libm, as CPython's math.log10
     return a;
 }
+// the same with the results in the block too: L is a RowsLayout, a PloidyLayout or a CohortLayout (the same five outputs and the pair)
+template <class Layout>
+static GenoArgs block_geno_args(const svjg_ctx *c, const unsigned long long *counts, uint8_t *base, const Layout &L, uint64_t n_rows, uint32_t min_support, double err) {
+    GenoArgs a = geno_args(c, counts, base, L.in, n_rows, min_support, err);
+    a.pl = (int64_t *)(base + L.pl); a.raw = (uint32_t *)(base + L.raw); a.gt = base + L.gt; a.genotyped = base + L.flags;
+    a.boundary = base + L.boundary; a.max_n = (unsigned int *)(base + L.maxn);
+    return a;
+}
 
 // all rows with the table at hand, blocks of TPB on the compute stream (a fused pass's FIRST launch is svjg_run_begin's own)
-// ploidy != nullptr: k_genotype_ploidy with the rows' ploidies and the call's logarithms (svjg_genotype_ploidy), else k_genotype
-static int launch_genotype(svjg_ctx *c, GenoArgs &a, const uint8_t *ploidy = nullptr, const double *logtab = nullptr) {
+static int launch_genotype(svjg_ctx *c, GenoArgs &a) {
     a.logfact = c->d_logfact; a.logfact_n = c->logfact_n;
     HIPCHK(c, hipMemsetAsync(a.max_n, 0, 8, c->stream));
-    const dim3 grid((uint32_t)((a.n_rows + TPB - 1) / TPB));
-    if (ploidy) hipLaunchKernelGGL(k_genotype_ploidy, grid, dim3(TPB), 0, c->stream, GenoPloidyArgs{a, ploidy, logtab});
-    else hipLaunchKernelGGL(k_genotype, grid, dim3(TPB), 0, c->stream, a);
+    hipLaunchKernelGGL(k_genotype, dim3((uint32_t)((a.n_rows + TPB - 1) / TPB)), dim3(TPB), 0, c->stream, a);
     HIPCHK(c, hipGetLastError());
     return 0;
 }
 
-// Behind a launch of `a`, its max_n pair on the host (h_maxn): [1] a row names a slot out of range, [0] the largest n = ref + alt beyond
+// Behind a launch, its max_n pair on the host (h_maxn): [1] a row names a slot out of range, [0] the largest n = ref + alt beyond
 // the log10(i!) table.  Only then (first call, or a deeper sample than ever before) the table is rebuilt, the rows run again, `bytes` from
 // d_back come back to h_back (what the caller reads, the pair included) and the check repeats.  relaunch_first: the launch itself is still
 // owed (svjg_run_end behind a repeated pass).  max_n is the maximum over ALL rows, so one growth is enough; the second only guards this reasoning.
-// launch(): the kernel over all its items again with the table at hand (launch_genotype for the rows, launch_sites for svjg_genotype_sites).
+// launch(): the kernel over all its items again with the table at hand; it zeroes again whatever the kernel adds to (launch_genotype,
+// launch_ploidy, launch_sites, launch_cohort).
 template <class Launch>
 static int settle_launch(svjg_ctx *c, const unsigned int *h_maxn, void *h_back, const void *d_back, uint64_t bytes, bool relaunch_first, Launch launch) {
     for (int growths = 0;; relaunch_first = false) {
@@ -977,35 +978,42 @@ static int settle_launch(svjg_ctx *c, const unsigned int *h_maxn, void *h_back, 
         HIPCHK(c, hipStreamSynchronize(c->stream));
     }
 }
-static int settle_genotype(svjg_ctx *c, GenoArgs &a, const unsigned int *h_maxn, void *h_back, const void *d_back, uint64_t bytes, bool relaunch_first,
-                           const uint8_t *ploidy = nullptr, const double *logtab = nullptr) {
-    return settle_launch(c, h_maxn, h_back, d_back, bytes, relaunch_first, [&] { return launch_genotype(c, a, ploidy, logtab); });
+
+// The host leg of a step-by-step call, on the compute stream: the call's block b and its pinned twin sized for S; fill(hb) stages the inputs into the
+// twin's input region; ONE copy in; the first table, if the context has none; launch(base) runs the call's kernel over all items of the device block
+// `base` with the table at hand; ONE copy out of the outputs and the max_n pair, which then lie in the twin; settle_launch (launch(base) again behind
+// every growth of the table).  ms_geno: the event pair around the FIRST launch (and the table's build, if any), read once the results are settled.
+template <class Fill, class Launch>
+static int genotype_leg(svjg_ctx *c, LegBlock &b, const LegSpan &S, Fill fill, Launch launch) {
+    int rc;
+    if ((rc = ensure(c, &b.d, &b.d_cap, S.total, 1, false))) return rc;
+    if ((rc = ensure_pinned(c, &b.h, &b.h_cap, S.total, hipHostMallocDefault))) return rc;
+    uint8_t *base = (uint8_t *)b.d, *hb = (uint8_t *)b.h;
+    fill(hb);
+    HIPCHK(c, hipMemcpyAsync(base + S.in_at, hb + S.in_at, S.in_bytes, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipEventRecord(c->ev[4], c->stream));
+    if (c->logfact_n == 0 && (rc = build_logfact(c, logfact_first()))) return rc;
+    if ((rc = launch(base))) return rc;
+    HIPCHK(c, hipEventRecord(c->ev[5], c->stream));
+    HIPCHK(c, hipMemcpyAsync(hb, base, S.maxn + 8, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    if ((rc = settle_launch(c, (const unsigned int *)(hb + S.maxn), hb, base, S.maxn + 8, false, [&] { return launch(base); }))) return rc;
+    HIPCHK(c, hipEventElapsedTime(&c->ms_geno, c->ev[4], c->ev[5]));
+    return 0;
 }
 
-// results of all rows -> the pinned host block of the context (rows_layout)
+static void stage_rows(uint8_t *hb, const RowsIn &I, const uint8_t *sv_type, const uint32_t *slot, const uint8_t *ok, uint64_t n_rows) {   // a call's three input arrays into the pinned block
+    memcpy(hb + I.slot, slot, n_rows * 4); memcpy(hb + I.type, sv_type, n_rows); memcpy(hb + I.ok, ok, n_rows);
+}
+
+// results of all rows -> the pinned host block BLOCK_ROWS (rows_layout)
 static int genotype_rows(svjg_ctx *c, const uint8_t *sv_type, const uint32_t *slot, const uint8_t *ok, uint64_t n_rows, uint32_t min_support, double err) {
     HIPCHK(c, hipSetDevice(c->device));
     { const int rc0 = fetch_slot_counts(c); if (rc0) return rc0; }
     const RowsLayout L = rows_layout(n_rows);
-    int rc;
-    if ((rc = ensure(c, &c->d_rows, &c->rows_cap, L.total, 1, false))) return rc;
-    if ((rc = ensure_pinned(c, &c->h_rows, &c->h_rows_cap, L.total, hipHostMallocDefault))) return rc;
-    uint8_t *base = (uint8_t *)c->d_rows, *hb = (uint8_t *)c->h_rows;
-    memcpy(hb + L.in.slot, slot, n_rows * 4); memcpy(hb + L.in.type, sv_type, n_rows); memcpy(hb + L.in.ok, ok, n_rows);
-    HIPCHK(c, hipMemcpyAsync(base + L.in.slot, hb + L.in.slot, L.in.bytes, hipMemcpyHostToDevice, c->stream));
-    GenoArgs a = geno_args(c, c->d_counts, base, L.in, n_rows, min_support, err);
-    a.pl = (int64_t *)(base + L.pl); a.raw = (uint32_t *)(base + L.raw); a.gt = base + L.gt; a.genotyped = base + L.flags;
-    a.boundary = base + L.boundary; a.max_n = (unsigned int *)(base + L.maxn);
-    c->geno_rows = n_rows;
-    HIPCHK(c, hipEventRecord(c->ev[4], c->stream));
-    if (c->logfact_n == 0 && (rc = build_logfact(c, logfact_first()))) return rc;
-    if ((rc = launch_genotype(c, a))) return rc;
-    HIPCHK(c, hipEventRecord(c->ev[5], c->stream));
-    HIPCHK(c, hipMemcpyAsync(hb, base, L.maxn + 8, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    if ((rc = settle_genotype(c, a, (const unsigned int *)(hb + L.maxn), hb, base, L.maxn + 8, false))) return rc;
-    HIPCHK(c, hipEventElapsedTime(&c->ms_geno, c->ev[4], c->ev[5]));
-    return 0;
+    return genotype_leg(c, c->leg[BLOCK_ROWS], L,
+        [&](uint8_t *hb) { stage_rows(hb, L.in, sv_type, slot, ok, n_rows); c->geno_rows = n_rows; },   // (from here on the block is this call's)
+        [&](uint8_t *base) { GenoArgs a = block_geno_args(c, c->d_counts, base, L, n_rows, min_support, err); return launch_genotype(c, a); });
 }
 
 // The results where the device's copy left them: the four pointers look into the context's pinned host block and stay
@@ -1019,7 +1027,7 @@ extern "C" int svjg_genotype_view(svjg_ctx *c, const uint8_t *sv_type, const uin
     if (!sv_type || !slot || !ok) return SVJG_E_ARG;
     const int rc = genotype_rows(c, sv_type, slot, ok, n_rows, min_support, err);
     if (rc) return rc;
-    const uint8_t *hb = (const uint8_t *)c->h_rows;
+    const uint8_t *hb = (const uint8_t *)c->leg[BLOCK_ROWS].h;
     const RowsLayout L = rows_layout(n_rows);
     *pl = (const int64_t *)(hb + L.pl); *raw = (const uint32_t *)(hb + L.raw); *gt = hb + L.gt; *genotyped = hb + L.flags;
     return 0;
@@ -1036,9 +1044,16 @@ extern "C" int svjg_genotype(svjg_ctx *c, const uint8_t *sv_type, const uint32_t
     return 0;
 }
 
-// Any ploidy from 1 to SVJG_MAX_PLOIDY per row (k_genotype_ploidy): the same leg — one copy in (the call's logarithms and the four input
-// arrays), one kernel, one copy out, settled by settle_genotype — in a block of its own, so that what svjg_genotype_view and
-// svjg_genotype_boundary hand out stays untouched.
+// Any ploidy from 1 to SVJG_MAX_PLOIDY per row (k_genotype_ploidy; svjg.h), through genotype_leg in BLOCK_PLOIDY: the call's logarithms and the
+// rows' ploidies go in with the three input arrays.
+static int launch_ploidy(svjg_ctx *c, GenoPloidyArgs &p) {
+    p.g.logfact = c->d_logfact; p.g.logfact_n = c->logfact_n;
+    HIPCHK(c, hipMemsetAsync(p.g.max_n, 0, 8, c->stream));
+    hipLaunchKernelGGL(k_genotype_ploidy, dim3((uint32_t)((p.g.n_rows + TPB - 1) / TPB)), dim3(TPB), 0, c->stream, p);
+    HIPCHK(c, hipGetLastError());
+    return 0;
+}
+
 extern "C" int svjg_genotype_ploidy(svjg_ctx *c, const uint8_t *sv_type, const uint32_t *slot, const uint8_t *ok, const uint8_t *ploidy,
                                     uint64_t n_rows, uint32_t min_support, double err, uint8_t *gt, int64_t *pl, uint32_t *raw,
                                     uint8_t *genotyped, uint8_t *boundary) {
@@ -1051,33 +1066,21 @@ extern "C" int svjg_genotype_ploidy(svjg_ctx *c, const uint8_t *sv_type, const u
     HIPCHK(c, hipSetDevice(c->device));
     { const int rc0 = fetch_slot_counts(c); if (rc0) return rc0; }
     const PloidyLayout L = ploidy_layout(n_rows);
-    int rc;
-    if ((rc = ensure(c, &c->d_prows, &c->prows_cap, L.total, 1, false))) return rc;
-    if ((rc = ensure_pinned(c, &c->h_prows, &c->h_prows_cap, L.total, hipHostMallocDefault))) return rc;
-    uint8_t *base = (uint8_t *)c->d_prows, *hb = (uint8_t *)c->h_prows;
-    ploidy_log_table(err, (double *)(hb + L.logtab));            // host libm, as geno_args' three
-    memcpy(hb + L.in.slot, slot, n_rows * 4); memcpy(hb + L.in.type, sv_type, n_rows); memcpy(hb + L.in.ok, ok, n_rows); memcpy(hb + L.ploidy, ploidy, n_rows);
-    HIPCHK(c, hipMemcpyAsync(base + L.logtab, hb + L.logtab, L.in_bytes, hipMemcpyHostToDevice, c->stream));
-    GenoArgs a = geno_args(c, c->d_counts, base, L.in, n_rows, min_support, err);
-    a.pl = (int64_t *)(base + L.pl); a.raw = (uint32_t *)(base + L.raw); a.gt = base + L.gt; a.genotyped = base + L.flags;
-    a.boundary = base + L.boundary; a.max_n = (unsigned int *)(base + L.maxn);
-    const uint8_t *d_ploidy = base + L.ploidy; const double *d_logtab = (const double *)(base + L.logtab);
-    HIPCHK(c, hipEventRecord(c->ev[4], c->stream));
-    if (c->logfact_n == 0 && (rc = build_logfact(c, logfact_first()))) return rc;
-    if ((rc = launch_genotype(c, a, d_ploidy, d_logtab))) return rc;
-    HIPCHK(c, hipEventRecord(c->ev[5], c->stream));
-    HIPCHK(c, hipMemcpyAsync(hb, base, L.maxn + 8, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    if ((rc = settle_genotype(c, a, (const unsigned int *)(hb + L.maxn), hb, base, L.maxn + 8, false, d_ploidy, d_logtab))) return rc;
-    HIPCHK(c, hipEventElapsedTime(&c->ms_geno, c->ev[4], c->ev[5]));
+    const int rc = genotype_leg(c, c->leg[BLOCK_PLOIDY], L,
+        [&](uint8_t *hb) { ploidy_log_table(err, (double *)(hb + L.logtab)); stage_rows(hb, L.in, sv_type, slot, ok, n_rows); memcpy(hb + L.ploidy, ploidy, n_rows); },   // (the logarithms by the host's libm, as geno_args' three)
+        [&](uint8_t *base) {
+            GenoPloidyArgs p{block_geno_args(c, c->d_counts, base, L, n_rows, min_support, err), base + L.ploidy, (const double *)(base + L.logtab)};
+            return launch_ploidy(c, p);
+        });
+    if (rc) return rc;
+    const uint8_t *hb = (const uint8_t *)c->leg[BLOCK_PLOIDY].h;
     memcpy(pl, hb + L.pl, n_rows * (MAX_PLOIDY + 1) * sizeof *pl); memcpy(raw, hb + L.raw, n_rows * 2 * sizeof *raw);
     memcpy(gt, hb + L.gt, n_rows); memcpy(genotyped, hb + L.flags, n_rows); memcpy(boundary, hb + L.boundary, n_rows);
     return 0;
 }
 
-// Insertions that share a position, genotyped together (k_genotype_sites; svjg.h): the same leg once more — one copy in (the call's logarithms
-// and the sites' slots), one kernel, one copy out, settled like the rows — in a block of its own, so that the views and the boundary bytes of
-// the calls above stay as they are.  Everything a caller can get wrong is found here, before any launch.
+// Insertions that share a position, genotyped together (k_genotype_sites; svjg.h), through genotype_leg in BLOCK_SITES: the call's logarithms
+// and the sites' slots go in.  Everything a caller can get wrong is found here, before any launch.
 static int launch_sites(svjg_ctx *c, GenoSitesArgs &a) {
     a.logfact = c->d_logfact; a.logfact_n = c->logfact_n;
     HIPCHK(c, hipMemsetAsync(a.max_n, 0, 8, c->stream));
@@ -1107,26 +1110,18 @@ extern "C" int svjg_genotype_sites(svjg_ctx *c, const uint32_t *slots, uint64_t 
     HIPCHK(c, hipSetDevice(c->device));
     { const int rc0 = fetch_slot_counts(c); if (rc0) return rc0; }
     const SitesLayout L = sites_layout(n_sites);
-    int rc;
-    if ((rc = ensure(c, &c->d_srows, &c->srows_cap, L.total, 1, false))) return rc;
-    if ((rc = ensure_pinned(c, &c->h_srows, &c->h_srows_cap, L.total, hipHostMallocDefault))) return rc;
-    uint8_t *base = (uint8_t *)c->d_srows, *hb = (uint8_t *)c->h_srows;
-    site_log_table(err, (double *)(hb + L.logs));                // host libm, as geno_args' three
-    memcpy(hb + L.slots, slots, n_sites * MAX_SITE_ALTS * 4);
-    HIPCHK(c, hipMemcpyAsync(base + L.logs, hb + L.logs, L.in_bytes, hipMemcpyHostToDevice, c->stream));
-    GenoSitesArgs a{};
-    a.counts = c->d_counts; a.n_slots = c->n_slots; a.slots = (const uint32_t *)(base + L.slots); a.n_sites = n_sites; a.min_support = min_support;
-    a.logs = (const double *)(base + L.logs);
-    a.pl = (int64_t *)(base + L.pl); a.raw = (uint32_t *)(base + L.raw); a.gt = base + L.gt; a.boundary = base + L.boundary;
-    a.max_n = (unsigned int *)(base + L.maxn);
-    HIPCHK(c, hipEventRecord(c->ev[4], c->stream));
-    if (c->logfact_n == 0 && (rc = build_logfact(c, logfact_first()))) return rc;
-    if ((rc = launch_sites(c, a))) return rc;
-    HIPCHK(c, hipEventRecord(c->ev[5], c->stream));
-    HIPCHK(c, hipMemcpyAsync(hb, base, L.maxn + 8, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    if ((rc = settle_launch(c, (const unsigned int *)(hb + L.maxn), hb, base, L.maxn + 8, false, [&] { return launch_sites(c, a); }))) return rc;
-    HIPCHK(c, hipEventElapsedTime(&c->ms_geno, c->ev[4], c->ev[5]));
+    const int rc = genotype_leg(c, c->leg[BLOCK_SITES], L,
+        [&](uint8_t *hb) { site_log_table(err, (double *)(hb + L.logs)); memcpy(hb + L.slots, slots, n_sites * MAX_SITE_ALTS * 4); },   // (host libm, as geno_args' three)
+        [&](uint8_t *base) {
+            GenoSitesArgs a{};
+            a.counts = c->d_counts; a.n_slots = c->n_slots; a.slots = (const uint32_t *)(base + L.slots); a.n_sites = n_sites; a.min_support = min_support;
+            a.logs = (const double *)(base + L.logs);
+            a.pl = (int64_t *)(base + L.pl); a.raw = (uint32_t *)(base + L.raw); a.gt = base + L.gt; a.boundary = base + L.boundary;
+            a.max_n = (unsigned int *)(base + L.maxn);
+            return launch_sites(c, a);
+        });
+    if (rc) return rc;
+    const uint8_t *hb = (const uint8_t *)c->leg[BLOCK_SITES].h;
     memcpy(pl, hb + L.pl, n_sites * SITE_GENOTYPES * sizeof *pl); memcpy(raw, hb + L.raw, n_sites * (MAX_SITE_ALTS + 1) * sizeof *raw);
     memcpy(gt, hb + L.gt, n_sites * 2); memcpy(boundary, hb + L.boundary, n_sites);
     return 0;
@@ -1214,8 +1209,9 @@ extern "C" int svjg_cohort_get_counts(svjg_ctx *c, uint32_t sample, uint32_t *ou
     return 0;
 }
 
-// all items with the table at hand.  The site words lie right in front of the max_n pair (cohort_layout): both are zeroed in front of EVERY
-// launch — settle_launch runs the kernel over all items again after the table grew, and the atomics would add to the first launch's sums.
+// svjg_genotype_cohort goes through genotype_leg in BLOCK_COHORT.  launch_cohort: all items with the table at hand.  The site words lie right in
+// front of the max_n pair (cohort_layout): both are zeroed in front of EVERY launch — settle_launch runs the kernel over all items again after
+// the table grew, and the atomics would add to the first launch's sums.
 // Blocks: enough for eight waves on every SIMD (the kernel holds 64 VGPRs or fewer: svjg.h), the rest in strides of the grid.
 static int launch_cohort(svjg_ctx *c, GenoCohortArgs &p) {
     p.g.logfact = c->d_logfact; p.g.logfact_n = c->logfact_n;
@@ -1238,26 +1234,15 @@ extern "C" int svjg_genotype_cohort(svjg_ctx *c, const uint8_t *sv_type, const u
     HIPCHK(c, hipSetDevice(c->device));
     const CohortLayout L = cohort_layout(n_rows, S);
     const uint64_t n = n_rows * S;
-    int rc;
-    if ((rc = ensure(c, &c->d_crows, &c->crows_cap, L.total, 1, false))) return rc;
-    if ((rc = ensure_pinned(c, &c->h_crows, &c->h_crows_cap, L.total, hipHostMallocDefault))) return rc;
-    uint8_t *base = (uint8_t *)c->d_crows, *hb = (uint8_t *)c->h_crows;
-    memcpy(hb + L.in.slot, slot, n_rows * 4); memcpy(hb + L.in.type, sv_type, n_rows); memcpy(hb + L.in.ok, ok, n_rows);
-    HIPCHK(c, hipMemcpyAsync(base + L.in.slot, hb + L.in.slot, L.in.bytes, hipMemcpyHostToDevice, c->stream));
-    GenoCohortArgs p{};
-    p.g = geno_args(c, c->d_cm, base, L.in, n_rows, min_support, err);
-    p.g.n_slots = c->cohort_slots;                                // (the matrix's slots, not the count vector's)
-    p.g.pl = (int64_t *)(base + L.pl); p.g.raw = (uint32_t *)(base + L.raw); p.g.gt = base + L.gt; p.g.genotyped = base + L.flags;
-    p.g.boundary = base + L.boundary; p.g.max_n = (unsigned int *)(base + L.maxn);
-    p.present = c->d_cpresent; p.n_samples = c->cohort_samples; p.site = (unsigned long long *)(base + L.site);
-    HIPCHK(c, hipEventRecord(c->ev[4], c->stream));
-    if (c->logfact_n == 0 && (rc = build_logfact(c, logfact_first()))) return rc;
-    if ((rc = launch_cohort(c, p))) return rc;
-    HIPCHK(c, hipEventRecord(c->ev[5], c->stream));
-    HIPCHK(c, hipMemcpyAsync(hb, base, L.maxn + 8, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    if ((rc = settle_launch(c, (const unsigned int *)(hb + L.maxn), hb, base, L.maxn + 8, false, [&] { return launch_cohort(c, p); }))) return rc;
-    HIPCHK(c, hipEventElapsedTime(&c->ms_geno, c->ev[4], c->ev[5]));
+    const int rc = genotype_leg(c, c->leg[BLOCK_COHORT], L,
+        [&](uint8_t *hb) { stage_rows(hb, L.in, sv_type, slot, ok, n_rows); },
+        [&](uint8_t *base) {
+            GenoCohortArgs p{block_geno_args(c, c->d_cm, base, L, n_rows, min_support, err), c->d_cpresent, c->cohort_samples, (unsigned long long *)(base + L.site)};
+            p.g.n_slots = c->cohort_slots;                        // (the matrix's slots, not the count vector's)
+            return launch_cohort(c, p);
+        });
+    if (rc) return rc;
+    const uint8_t *hb = (const uint8_t *)c->leg[BLOCK_COHORT].h;
     memcpy(pl, hb + L.pl, n * 3 * sizeof *pl); memcpy(raw, hb + L.raw, n * 2 * sizeof *raw);
     memcpy(gt, hb + L.gt, n); memcpy(genotyped, hb + L.flags, n); memcpy(boundary, hb + L.boundary, n); memcpy(site, hb + L.site, n_rows * 8);
     return 0;
@@ -1483,7 +1468,7 @@ extern "C" int svjg_run_end(svjg_ctx *c, const uint8_t **gt, const int32_t **pl,
     if (n_rows) {
         GenoArgs ga = run_geno_args(c, r, L, r.min_support, r.err, again ? c->d_counts : r.counts);
         uint8_t *h_maxn = hb + L.h_tail + L.maxn;                 // (the results are already in the mapped host block: only the pair comes back)
-        if ((rc = settle_genotype(c, ga, (const unsigned int *)h_maxn, h_maxn, (const uint8_t *)r.d + L.maxn, 8, again))) return rc;
+        if ((rc = settle_launch(c, (const unsigned int *)h_maxn, h_maxn, (const uint8_t *)r.d + L.maxn, 8, again, [&] { return launch_genotype(c, ga); }))) return rc;
     }
     *pl = (const int32_t *)(hb + L.pl32); *raw = (const uint32_t *)(hb + L.raw); *gt = hb + L.gt; *flags = hb + L.flags; *boundary = hb + L.boundary;
     return 0;
@@ -1501,8 +1486,9 @@ extern "C" int svjg_run_resident(svjg_ctx *c, uint64_t base_offset, uint32_t min
 // which rows of the last svjg_genotype / svjg_genotype_view call lie so close to a PL's integer boundary that the caller should
 // recompute them with the reference's own arithmetic (predict-genotype.py:313: log10 of an exact big integer)
 extern "C" int svjg_genotype_boundary(svjg_ctx *c, uint8_t *out, uint64_t n_rows) {
-    if (!c || (n_rows && !out) || n_rows != c->geno_rows || !c->h_rows) return SVJG_E_ARG;
-    memcpy(out, (const uint8_t *)c->h_rows + rows_layout(n_rows).boundary, n_rows);
+    const void *hb = c ? c->leg[BLOCK_ROWS].h : nullptr;
+    if (!hb || (n_rows && !out) || n_rows != c->geno_rows) return SVJG_E_ARG;
+    memcpy(out, (const uint8_t *)hb + rows_layout(n_rows).boundary, n_rows);
     return 0;
 }
 

@@ -338,46 +338,54 @@ constexpr uint32_t logfact_reserve_to(uint32_t have, uint32_t entries) { return 
 struct RowsIn { uint64_t slot, type, ok, bytes; };
 inline RowsIn rows_in(uint64_t n, uint64_t at = 0) { return RowsIn{at, at + n * 4, at + n * 5, n * 6}; }
 
-// step-by-step leg (svjg_genotype, svjg_genotype_view, svjg_genotype_boundary): one device block and its pinned host twin, [ pl 24 | raw 8 |
-// gt 1 | flags 1 | boundary 1 ] x n of output (flags: a row's `genotyped` byte), the max_n pair, then the inputs -> ONE copy in, ONE copy out
-struct RowsLayout { uint64_t pl, raw, gt, flags, boundary, maxn;  RowsIn in;  uint64_t total; };
+// The four step-by-step calls (svjg_genotype / _view, _ploidy, _sites, _cohort) each own one device block and its pinned host twin, all of ONE
+// shape: the outputs (they end at out_end), the max_n pair 8-aligned, ONE contiguous input region right behind the pair, 64 spare bytes -> ONE copy
+// in (in_bytes from in_at), ONE copy out (maxn + 8 bytes from 0).  A layout below IS a LegSpan and adds only what is its own: its outputs and where its inputs lie.
+struct LegSpan { uint64_t maxn, in_at, in_bytes, total; };
+inline void leg_span(LegSpan &S, uint64_t out_end, uint64_t in_bytes) {
+    S.maxn = (out_end + 7) & ~7ull; S.in_at = S.maxn + 8; S.in_bytes = in_bytes; S.total = S.in_at + in_bytes + 64;
+}
+
+// svjg_genotype, svjg_genotype_view, svjg_genotype_boundary: [ pl 24 | raw 8 | gt 1 | flags 1 | boundary 1 ] x n of output (flags: a row's
+// `genotyped` byte); in: rows_in(n)
+struct RowsLayout : LegSpan { uint64_t pl, raw, gt, flags, boundary;  RowsIn in; };
 inline RowsLayout rows_layout(uint64_t n) {
     RowsLayout L; uint64_t o = 0;
     L.pl = o; o += n * 24; L.raw = o; o += n * 8; L.gt = o; o += n; L.flags = o; o += n; L.boundary = o; o += n;
-    L.maxn = (o + 7) & ~7ull; L.in = rows_in(n, L.maxn + 8); L.total = L.in.slot + L.in.bytes + 64;
+    leg_span(L, o, n * 6); L.in = rows_in(n, L.in_at);
     return L;
 }
 
-// any-ploidy leg (svjg_genotype_ploidy): the same in a block of its own, [ pl 72 | raw 8 | gt 1 | flags 1 | boundary 1 ] x n, the max_n pair, then
-// ONE copy in: the call's logarithms (ploidy_log_table), rows_in(n) and the ploidy bytes
-struct PloidyLayout { uint64_t pl, raw, gt, flags, boundary, maxn, logtab;  RowsIn in;  uint64_t ploidy, in_bytes, total; };
+// svjg_genotype_ploidy: [ pl 72 | raw 8 | gt 1 | flags 1 | boundary 1 ] x n; in: the call's logarithms (ploidy_log_table), rows_in(n) and the
+// ploidy bytes
+struct PloidyLayout : LegSpan { uint64_t pl, raw, gt, flags, boundary, logtab;  RowsIn in;  uint64_t ploidy; };
 inline PloidyLayout ploidy_layout(uint64_t n) {
     PloidyLayout L; uint64_t o = 0;
     L.pl = o; o += n * 8 * (MAX_PLOIDY + 1); L.raw = o; o += n * 8; L.gt = o; o += n; L.flags = o; o += n; L.boundary = o; o += n;
-    L.maxn = (o + 7) & ~7ull; L.logtab = L.maxn + 8; L.in = rows_in(n, L.logtab + 2 * PLOIDY_TAB * 8);
-    L.ploidy = L.in.slot + L.in.bytes; L.in_bytes = 2 * PLOIDY_TAB * 8 + L.in.bytes + n; L.total = L.logtab + L.in_bytes + 64;
+    leg_span(L, o, 2 * PLOIDY_TAB * 8 + n * 7);
+    L.logtab = L.in_at; L.in = rows_in(n, L.logtab + 2 * PLOIDY_TAB * 8); L.ploidy = L.in.slot + L.in.bytes;
     return L;
 }
 
-// joint-insertion leg (svjg_genotype_sites): a block of its own again, [ pl 224 | raw 28 | gt 2 | boundary 1 ] x n, the max_n pair, then ONE copy
-// in: the call's logarithms (site_log_table) and the sites' slots
-struct SitesLayout { uint64_t pl, raw, gt, boundary, maxn, logs, slots, in_bytes, total; };
+// svjg_genotype_sites: [ pl 224 | raw 28 | gt 2 | boundary 1 ] x n; in: the call's logarithms (site_log_table) and the sites' slots
+struct SitesLayout : LegSpan { uint64_t pl, raw, gt, boundary, logs, slots; };
 inline SitesLayout sites_layout(uint64_t n) {
     SitesLayout L; uint64_t o = 0;
     L.pl = o; o += n * 8 * SITE_GENOTYPES; L.raw = o; o += n * 4 * (MAX_SITE_ALTS + 1); L.gt = o; o += n * 2; L.boundary = o; o += n;
-    L.maxn = (o + 7) & ~7ull; L.logs = L.maxn + 8; L.slots = L.logs + SITE_LOGS * 8;
-    L.in_bytes = SITE_LOGS * 8 + n * 4 * MAX_SITE_ALTS; L.total = L.logs + L.in_bytes + 64;
+    leg_span(L, o, SITE_LOGS * 8 + n * 4 * MAX_SITE_ALTS);
+    L.logs = L.in_at; L.slots = L.logs + SITE_LOGS * 8;
     return L;
 }
 
-// cohort leg (svjg_genotype_cohort): a block of its own once more, [ pl 24 | raw 8 | gt 1 | flags 1 | boundary 1 ] x (n_rows * S items, row-major),
-// the rows' site words (NS | AC << 32) with the max_n pair right behind them (ONE memset zeroes both in front of every launch), then ONE copy
-// in: rows_in(n_rows)
-struct CohortLayout { uint64_t pl, raw, gt, flags, boundary, site, maxn;  RowsIn in;  uint64_t total; };
+// svjg_genotype_cohort: [ pl 24 | raw 8 | gt 1 | flags 1 | boundary 1 ] x (n_rows * S items, row-major), then the rows' site words (NS | AC << 32),
+// 8-aligned, as the LAST output: the max_n pair lies right behind them (8 n_rows is a multiple of 8, so leg_span pads nothing), and ONE memset
+// zeroes both in front of every launch; in: rows_in(n_rows)
+struct CohortLayout : LegSpan { uint64_t pl, raw, gt, flags, boundary, site;  RowsIn in; };
 inline CohortLayout cohort_layout(uint64_t n_rows, uint64_t S) {
     CohortLayout L; uint64_t o = 0; const uint64_t n = n_rows * S;
     L.pl = o; o += n * 24; L.raw = o; o += n * 8; L.gt = o; o += n; L.flags = o; o += n; L.boundary = o; o += n;
-    L.site = (o + 7) & ~7ull; L.maxn = L.site + n_rows * 8; L.in = rows_in(n_rows, L.maxn + 8); L.total = L.in.slot + L.in.bytes + 64;
+    o = (o + 7) & ~7ull; L.site = o; o += n_rows * 8;
+    leg_span(L, o, n_rows * 6); L.in = rows_in(n_rows, L.in_at);
     return L;
 }
 

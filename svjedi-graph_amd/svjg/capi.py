@@ -311,6 +311,11 @@ def load_library(path=None):
     return lib
 
 
+def _row_inputs(sv_type, slot, ok):
+    """the three per-row input arrays of a genotype call in the element types the library reads"""
+    return np.ascontiguousarray(sv_type, dtype=np.uint8), np.ascontiguousarray(slot, dtype=np.uint32), np.ascontiguousarray(ok, dtype=np.uint8)
+
+
 class Context:
     """One GPU.  Thin, stateful wrapper over the C ABI."""
 
@@ -457,9 +462,7 @@ class Context:
         result block (svjg_genotype_view: no copy); they are overwritten by the next call and die with the context, so copy
         what has to outlive either."""
         n = len(sv_type)
-        sv_type = np.ascontiguousarray(sv_type, dtype=np.uint8)
-        slot = np.ascontiguousarray(slot, dtype=np.uint32)
-        ok = np.ascontiguousarray(ok, dtype=np.uint8)
+        sv_type, slot, ok = _row_inputs(sv_type, slot, ok)
         if reuse_outputs and n:
             p = [ctypes.c_void_p() for _ in range(4)]
             self._chk(self.lib.svjg_genotype_view(self.h, sv_type.ctypes.data, slot.ctypes.data, ok.ctypes.data, n, min_support,
@@ -483,9 +486,7 @@ class Context:
         -> (gt = alt copies or 0xFF, pl[n, 9] = PL_0..PL_P then zeros, raw[n, 2], genotyped, boundary = the rows to recompute with
         svjg.genotype.exact_pl_ploidy)"""
         n = len(sv_type)
-        sv_type = np.ascontiguousarray(sv_type, dtype=np.uint8)
-        slot = np.ascontiguousarray(slot, dtype=np.uint32)
-        ok = np.ascontiguousarray(ok, dtype=np.uint8)
+        sv_type, slot, ok = _row_inputs(sv_type, slot, ok)
         ploidy = np.asarray(ploidy)
         if n and (len(ploidy) != n or int(ploidy.min()) < 0 or int(ploidy.max()) > 255):
             raise SvjgError("ploidy: one value in 0..%d per row" % MAX_PLOIDY)
@@ -548,9 +549,7 @@ class Context:
         site[n, 2] = NS and AC of each row)"""
         n = len(sv_type)
         S = getattr(self, "_cohort", (0, 0))[0]
-        sv_type = np.ascontiguousarray(sv_type, dtype=np.uint8)
-        slot = np.ascontiguousarray(slot, dtype=np.uint32)
-        ok = np.ascontiguousarray(ok, dtype=np.uint8)
+        sv_type, slot, ok = _row_inputs(sv_type, slot, ok)
         gt = np.empty((n, S), dtype=np.uint8)
         pl = np.empty((n, S, 3), dtype=np.int64)
         raw = np.empty((n, S, 2), dtype=np.uint32)

@@ -278,11 +278,25 @@ extern "C" uint32_t hostsim_guard_words(void) { return GUARD_WORDS; }
 
 // where the rows of a genotype call lie (svjg_geno.h), as libsvjg_hip.so lays them out.  which 0: the step-by-step block -> pl, raw, gt, flags,
 // boundary, maxn, slot, type, ok, total; which 1: a fused pass's blocks -> pl32, raw, gt, flags, boundary, h_tail, out_bytes, maxn, status, guard,
-// tail_bytes, pl64, total, then slot, type, ok, bytes of the shared input block.  Returns the number of values written.
+// tail_bytes, pl64, total, then slot, type, ok, bytes of the shared input block; which 2: svjg_genotype_ploidy's block -> pl, raw, gt, flags,
+// boundary, maxn, logtab, slot, type, ok, ploidy, in_bytes, total; which 3: svjg_genotype_sites' block -> pl, raw, gt, boundary, maxn, logs,
+// slots, in_bytes, total.  Returns the number of values written.
 extern "C" int hostsim_rows_layout(uint64_t n, int which, uint64_t *out) {
     if (which == 0) {
         const RowsLayout L = rows_layout(n);
         const uint64_t v[] = {L.pl, L.raw, L.gt, L.flags, L.boundary, L.maxn, L.in.slot, L.in.type, L.in.ok, L.total};
+        memcpy(out, v, sizeof v);
+        return (int)(sizeof v / 8);
+    }
+    if (which == 2) {
+        const PloidyLayout L = ploidy_layout(n);
+        const uint64_t v[] = {L.pl, L.raw, L.gt, L.flags, L.boundary, L.maxn, L.logtab, L.in.slot, L.in.type, L.in.ok, L.ploidy, L.in_bytes, L.total};
+        memcpy(out, v, sizeof v);
+        return (int)(sizeof v / 8);
+    }
+    if (which == 3) {
+        const SitesLayout L = sites_layout(n);
+        const uint64_t v[] = {L.pl, L.raw, L.gt, L.boundary, L.maxn, L.logs, L.slots, L.in_bytes, L.total};
         memcpy(out, v, sizeof v);
         return (int)(sizeof v / 8);
     }

@@ -128,16 +128,20 @@ def pass_logic():
 STEP_FIELDS = ("pl", "raw", "gt", "flags", "boundary", "maxn", "slot", "type", "ok", "total")
 FUSED_FIELDS = ("pl32", "raw", "gt", "flags", "boundary", "h_tail", "out_bytes", "maxn", "status", "guard", "tail_bytes", "pl64", "total",
                 "slot", "type", "ok", "in_bytes")
+PLOIDY_FIELDS = ("pl", "raw", "gt", "flags", "boundary", "maxn", "logtab", "slot", "type", "ok", "ploidy", "in_bytes", "total")
+SITES_FIELDS = ("pl", "raw", "gt", "boundary", "maxn", "logs", "slots", "in_bytes", "total")
 
 
-def rows_layout(n, fused=False):
-    """byte offsets of the row block(s) of a genotype call over n rows (svjg_geno.h: rows_layout / run_layout + rows_in), by field name"""
+def rows_layout(n, fused=False, which=None):
+    """byte offsets of the row block(s) of a genotype call over n rows (svjg_geno.h: rows_layout / run_layout + rows_in), by field name;
+    which = 2: the block of svjg_genotype_ploidy (ploidy_layout), 3: of svjg_genotype_sites over n sites (sites_layout)"""
     lib = ctypes.CDLL(build())
     lib.hostsim_rows_layout.restype = ctypes.c_int
     lib.hostsim_rows_layout.argtypes = [ctypes.c_uint64, ctypes.c_int, ctypes.c_void_p]
     out = (ctypes.c_uint64 * 32)()
-    names = FUSED_FIELDS if fused else STEP_FIELDS
-    assert lib.hostsim_rows_layout(n, int(fused), out) == len(names)
+    which = int(fused) if which is None else which
+    names = (STEP_FIELDS, FUSED_FIELDS, PLOIDY_FIELDS, SITES_FIELDS)[which]
+    assert lib.hostsim_rows_layout(n, which, out) == len(names)
     return {k: int(out[i]) for i, k in enumerate(names)}
 
 

@@ -1,0 +1,111 @@
+"""The four step-by-step genotype calls share one host leg (svjg_capi.hip: genotype_leg) and keep a block each (svjg_ctx::leg[]): run on ONE
+context in either order, every call returns the bytes it returns on a context of its own, whichever calls ran in between, and a view of
+the diploid call's pinned block outlives the other three.  Needs an MI355X: run with -m gpu."""
+import numpy as np
+import pytest
+
+pytestmark = pytest.mark.gpu
+
+NONE = 0xFFFFFFFF
+R, S, N_SLOTS = 65, 3, 90              # two waves of rows with a ragged end; three samples; the sites' members lie behind the rows' slots
+MS, ERR = 3, 5e-5
+CALLS = ("rows", "ploidy", "sites", "cohort")
+
+
+def _case():
+    rng = np.random.default_rng(2610)
+    c = {}
+    c["counts"] = rng.integers(0, 61, size=(N_SLOTS, 2)).astype(np.uint32)        # the count vector: no row beyond the first table
+    c["t"] = rng.integers(0, 4, size=R).astype(np.uint8)
+    c["slot"] = rng.permutation(R).astype(np.uint32)
+    c["slot"][7] = NONE
+    c["ok"] = np.full(R, 3, np.uint8)
+    c["ok"][11] = 0
+    c["ploidy"] = np.resize(np.array([1, 2, 3, 8], np.uint8), R)
+    sites = np.full((5, 6), NONE, np.uint32)
+    at = R
+    for i, K in enumerate((2, 3, 6, 2, 3)):
+        sites[i, :K] = np.arange(at, at + K)
+        at += K
+    assert at <= N_SLOTS
+    c["sites"] = sites
+    # the matrix: its own counts, a fifth of the entries absent, and ONE item with ref + alt = 80 000 > 65 536 (sv_type 2: nothing is halved):
+    # only the cohort call meets it, so the table grows inside that leg, whichever legs ran in front of it
+    cm = rng.integers(0, 61, size=(N_SLOTS, S, 2)).astype(np.uint32)
+    present = (rng.random((N_SLOTS, S)) >= 0.2).astype(np.uint8)
+    deep = 20
+    assert c["slot"][deep] != NONE and c["ok"][deep] & 1
+    c["t"][deep] = 2
+    cm[c["slot"][deep], 1] = (40_000, 40_000)
+    present[c["slot"][deep], 1] = 1
+    c["cm"], c["present"], c["deep"] = cm, present, deep
+    return c
+
+
+def _load(ctx, c):
+    ctx.alloc_counts(N_SLOTS)
+    ctx.set_counts(c["counts"])
+    ctx.cohort_alloc(S, N_SLOTS)
+    for s in range(S):
+        keys = np.flatnonzero(c["present"][:, s]).astype(np.uint32)
+        ctx.cohort_set_counts(s, keys, c["cm"][keys, s])
+
+
+def _call(ctx, c, which, view=False):
+    """-> the call's arrays (rows: with the boundary flags behind them); view: the diploid call's arrays as views of the pinned block"""
+    if which == "rows":
+        out = ctx.genotype(c["t"], c["slot"], c["ok"], MS, ERR, reuse_outputs=view)
+        return (*out, ctx.boundary_flags(R))
+    if which == "ploidy":
+        return ctx.genotype_ploidy(c["t"], c["slot"], c["ok"], c["ploidy"], MS, ERR)
+    if which == "sites":
+        return ctx.genotype_sites(c["sites"], MS, ERR)
+    return ctx.genotype_cohort(c["t"], c["slot"], c["ok"], MS, ERR)
+
+
+def _bytes(arrays):
+    return [np.array(a).tobytes() for a in arrays]
+
+
+@pytest.fixture(scope="module")
+def case():
+    return _case()
+
+
+@pytest.fixture(scope="module")
+def alone(case):
+    """every call on a fresh context of its own with the same counts -> {call: bytes of its arrays}"""
+    from svjg import capi
+    want = {}
+    for which in CALLS:
+        ctx = capi.Context(0)
+        try:
+            _load(ctx, case)
+            assert ctx.logfact_entries() == 0
+            want[which] = _bytes(_call(ctx, case, which))
+            assert (ctx.logfact_entries() > 65536) == (which == "cohort")     # the deep item is the cohort call's alone
+        finally:
+            ctx.close()
+    gt, pl, raw, done, boundary, site = (np.frombuffer(b, dt) for b, dt in zip(want["cohort"], (np.uint8, np.int64, np.uint32, np.uint8, np.uint8, np.uint32)))
+    item = case["deep"] * S + 1
+    assert done[item] == 1 and raw[2 * item: 2 * item + 2].tolist() == [40_000, 40_000] and pl[3 * item: 3 * item + 3].any()
+    assert any(want["rows"][0]) and any(want["ploidy"][1]) and any(want["sites"][1])
+    return want
+
+
+@pytest.mark.parametrize("order", [("rows", "ploidy", "sites", "cohort", "rows"), ("rows", "cohort", "sites", "ploidy", "rows")])
+def test_every_call_in_a_block_of_its_own(case, alone, order):
+    from svjg import capi
+    ctx = capi.Context(0)
+    try:
+        _load(ctx, case)
+        view = _call(ctx, case, order[0], view=True)[:4]             # gt, pl, raw, genotyped: pointers into the pinned block
+        assert _bytes(view) == alone["rows"][:4] and ctx.logfact_entries() == 65536
+        for which in order[1:4]:
+            assert _bytes(_call(ctx, case, which)) == alone[which], which
+            assert _bytes(view) == alone["rows"][:4], f"the view after {which}"
+            assert ctx.boundary_flags(R).tobytes() == alone["rows"][4], f"the boundary bytes after {which}"
+        assert ctx.logfact_entries() > 65536                         # the table grew inside a leg that was not the first
+        assert _bytes(_call(ctx, case, order[4])) == alone["rows"]
+    finally:
+        ctx.close()

@@ -1,5 +1,5 @@
-"""Where the rows of a genotype call lie, and how the log10(i!) table grows (svjedi-graph_amd/csrc/svjg_geno.h: rows_layout, run_layout,
-rows_in, logfact_grow_to), on the CPU through tests/hostsim.  svjg_genotype_view and svjg_run_end hand out pointers into these blocks and
+"""Where the rows of a genotype call lie, and how the log10(i!) table grows (svjedi-graph_amd/csrc/svjg_geno.h: rows_layout, ploidy_layout,
+sites_layout, run_layout, rows_in, logfact_grow_to), on the CPU through tests/hostsim.  svjg_genotype_view and svjg_run_end hand out pointers into these blocks and
 callers keep them, so every offset is pinned to the formula the library used before the layouts had one description: the formulas are
 written out HERE, as the expectation.  Besides: no two fields overlap, the last one ends inside the block, and every field is aligned
 for its element type."""
@@ -35,6 +35,33 @@ def test_step_by_step_block(n):
     _check_block([("pl", L["pl"], 24 * n, 8), ("raw", L["raw"], 8 * n, 4), ("gt", L["gt"], n, 1), ("flags", L["flags"], n, 1),
                   ("boundary", L["boundary"], n, 1), ("maxn", L["maxn"], 8, 8), ("slot", L["slot"], 4 * n, 4), ("type", L["type"], n, 1),
                   ("ok", L["ok"], n, 1)], L["total"])
+
+
+@pytest.mark.parametrize("n", NS)
+def test_ploidy_block(n):
+    L = sim.rows_layout(n, which=2)
+    maxn = (83 * n + 7) & ~7
+    logtab = maxn + 8                                            # the call's logarithms: 2 x 45 doubles
+    slot = logtab + 720
+    assert L == {"pl": 0, "raw": 72 * n, "gt": 80 * n, "flags": 81 * n, "boundary": 82 * n, "maxn": maxn, "logtab": logtab,
+                 "slot": slot, "type": slot + 4 * n, "ok": slot + 5 * n, "ploidy": slot + 6 * n, "in_bytes": 720 + 7 * n,
+                 "total": logtab + 720 + 7 * n + 64}
+    _check_block([("pl", L["pl"], 72 * n, 8), ("raw", L["raw"], 8 * n, 4), ("gt", L["gt"], n, 1), ("flags", L["flags"], n, 1),
+                  ("boundary", L["boundary"], n, 1), ("maxn", L["maxn"], 8, 8), ("logtab", L["logtab"], 720, 8), ("slot", L["slot"], 4 * n, 4),
+                  ("type", L["type"], n, 1), ("ok", L["ok"], n, 1), ("ploidy", L["ploidy"], n, 1)], L["total"])
+    assert L["ploidy"] + n == L["logtab"] + L["in_bytes"]        # ONE copy in covers the logarithms and the four arrays, and nothing else
+
+
+@pytest.mark.parametrize("n", NS)
+def test_sites_block(n):
+    L = sim.rows_layout(n, which=3)
+    maxn = (255 * n + 7) & ~7
+    logs = maxn + 8                                              # the call's logarithms: 16 doubles
+    assert L == {"pl": 0, "raw": 224 * n, "gt": 252 * n, "boundary": 254 * n, "maxn": maxn, "logs": logs, "slots": logs + 128,
+                 "in_bytes": 128 + 24 * n, "total": logs + 128 + 24 * n + 64}
+    _check_block([("pl", L["pl"], 224 * n, 8), ("raw", L["raw"], 28 * n, 4), ("gt", L["gt"], 2 * n, 1), ("boundary", L["boundary"], n, 1),
+                  ("maxn", L["maxn"], 8, 8), ("logs", L["logs"], 128, 8), ("slots", L["slots"], 24 * n, 4)], L["total"])
+    assert L["slots"] + 24 * n == L["logs"] + L["in_bytes"]      # ONE copy in covers the logarithms and the slots, and nothing else
 
 
 @pytest.mark.parametrize("n", NS)
