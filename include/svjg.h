@@ -313,10 +313,12 @@ int svjg_genotype_cohort(svjg_ctx *ctx, const uint8_t *sv_type, const uint32_t *
 int svjg_set_rows(svjg_ctx *ctx, const uint8_t *sv_type, const uint32_t *slot, const uint8_t *ok, uint64_t n_rows);
 int svjg_run_resident(svjg_ctx *ctx, uint64_t base_offset, uint32_t min_support, double err,
                       const uint8_t **gt, const int32_t **pl, const uint32_t **raw, const uint8_t **flags, const uint8_t **boundary);
-/* The same in two halves, for a loop over batches: svjg_run_begin enqueues a pass (kernels on the context's stream, the copy of
- * its results to pinned host memory on a second stream) and returns; svjg_run_end waits for the OLDEST pass in flight and hands
- * out its results (valid until the second svjg_run_begin after it).  At most two passes are in flight, so the results of pass k
- * cross PCIe while pass k + 1 computes: begin(0); for k: begin(k + 1); end() -> results of k; ...; end(). */
+/* The same in two halves, for a loop over batches: svjg_run_begin enqueues a pass (kernels on a compute stream of the context, its
+ * genotypes and the hand-over of its results to pinned host memory on a low-priority stream) and returns; svjg_run_end waits for the
+ * OLDEST pass in flight and hands out its results (valid until the second svjg_run_begin after it).  At most two passes are in flight,
+ * so the results of pass k cross PCIe while pass k + 1 computes: begin(0); for k: begin(k + 1); end() -> results of k; ...; end().
+ * A context without a communicator alternates its passes between two compute streams: the classify kernel of pass k + 1 starts in the
+ * slots that of pass k vacates; lines such a pass defers are classified by svjg_run_end (same results; svjg_pass.h). */
 int svjg_run_begin(svjg_ctx *ctx, uint64_t base_offset, uint32_t min_support, double err);
 int svjg_run_end(svjg_ctx *ctx, const uint8_t **gt, const int32_t **pl, const uint32_t **raw, const uint8_t **flags, const uint8_t **boundary);
 
@@ -362,7 +364,9 @@ void svjg_vcf_free(svjg_vcf *v);
 /* ---- measurement hooks (bench.py): time of the kernels of the last classify / genotype.  HIP events, except in a fused pass
  * (svjg_run_begin): there the classify kernels leave time stamps of the device's constant-rate clock in the pass's status block — no
  * event record stands between two passes' kernels —; SVJG_KERNEL_MS=events in the environment puts the event pair back, and
- * svjg_last_main_ms then gives both readings of the same launch (by_events = 0 without it). ---- */
+ * svjg_last_main_ms then gives both readings of the same launch (by_events = 0 without it).  classify_main_ms of a fused pass k is
+ * t_last(k) - max(t_first(k), t_last(k - 1)) when pass k was enqueued with pass k - 1 still in flight: the interval two overlapped
+ * launches share is counted once, so the passes' figures add up to the time the device spent on them. ---- */
 int svjg_last_kernel_ms(svjg_ctx *ctx, float *classify_main_ms, float *classify_slow_ms, float *genotype_ms);
 int svjg_last_main_ms(svjg_ctx *ctx, float *by_stamps, float *by_events);
 int svjg_sync(svjg_ctx *ctx);

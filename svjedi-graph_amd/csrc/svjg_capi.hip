@@ -1,5 +1,6 @@
 // libsvjg_hip.so — host side of the C ABI declared in include/svjg.h.
-// One context = one MI355X, one HIP stream; kernels live in svjg_kernels.h.
+// One context = one MI355X; two compute streams (the second only carries every other overlapped fused pass: svjg_pass.h) and a low-priority one
+// for a pass's genotypes and tail; kernels live in svjg_kernels.h.
 #include "svjg_kernels.h"
 #include "svjg_host_tables.h"
 #include "svjg_pass.h"
@@ -90,6 +91,12 @@ struct svjg_ctx {
     int n_cu = 256;
     int occ_main = 0;                    // workgroups of k_classify_main one CU holds
     hipStream_t stream = nullptr, copy_stream = nullptr;
+    // The second compute stream: overlapped fused passes alternate between `stream` and it, everything else runs on `stream`.
+    // second_busy: stream2 holds work `stream` is not ordered behind; first_dirty: `stream` holds work other than overlapped passes that
+    // stream2 is not ordered behind (serial_enter / svjg_run_begin order them, ev_join[i] recorded on stream i).
+    hipStream_t stream2 = nullptr;
+    hipEvent_t ev_join[2] = {};
+    bool second_busy = false, first_dirty = false;
     hipEvent_t ev[6] = {};
     std::string err;
     // graph
@@ -111,7 +118,9 @@ struct svjg_ctx {
     uint64_t *d_host = nullptr;      uint64_t host_cap = 0;     // offsets of the lines set aside for the host (SVJG_EXC_ASK_HOST)
     DevStatus *d_st = nullptr;
     unsigned long long *d_dbg = nullptr;
-    uint32_t *d_long = nullptr;          // LONG_WORDS words per worker of k_classify_main (ClassifyArgs::long_pre)
+    uint32_t *d_long = nullptr;          // LONG_WORDS words per worker of k_classify_main (ClassifyArgs::long_pre): of the launches on `stream`
+    uint32_t *d_long2 = nullptr;         // the same for the launches on stream2: two main kernels may be alive at once, worker numbers are per launch
+    const uint64_t *host_lines_src = nullptr;  uint64_t host_lines_cap = 0;   // the list hs().n_host counts (svjg_get_host_lines): d_host (nullptr), or the last finished pass's own
     DevStatus *h_stp = nullptr;          // host twin of d_st in pinned memory: the status copies are asynchronous in both directions
     DevStatus &hs() { return *h_stp; }
     uint64_t total_deferred = 0;
@@ -129,9 +138,21 @@ struct svjg_ctx {
         unsigned long long *counts = nullptr;  uint64_t counts_cap = 0;   // the pass's own count vector (+ guard words): the next pass may zero its own while this one is genotyped
         hipEvent_t ev[6] = {};  hipEvent_t computed = nullptr, copied = nullptr;
         uint64_t base_offset = 0;  uint32_t min_support = 0;  double err = 0;  bool had_text = false, slow_end_own = false, timed_by_events = false;
+        // the pass's own lists (two main kernels may be alive at once): deferred lines, lines for the host; sized in svjg_run_begin, while no pass uses the slot
+        uint64_t *deferred = nullptr;  uint64_t deferred_cap = 0;  uint64_t *host = nullptr;  uint64_t host_cap = 0;
+        bool overlapped = false;         // the pass's form (svjg_pass.h: pass_overlaps): no exact-path launch on its stream, svjg_run_end settles it
+        bool inflight = false;           // begun, not yet ended
+        bool settled = false;            // settle_pass has looked at it; geno_owed: it ran the exact path, the genotypes are owed once more
+        bool geno_owed = false;  float ms_settle = 0;
+        bool chained = false;            // another pass was in flight when this one was enqueued: its main kernel may have started under that one's drain
+        hipStream_t on = nullptr;        // the compute stream of its kernels
+        ClassifyArgs cargs{};            // its k_classify_main's arguments (the settle step's k_classify_exact takes the same)
         bool clean = false;              // the pass before has already zeroed this slot's vector, status block and max_n (k_classify_exact)
     } run[RUN_SLOTS];
     int run_head = 0, run_tail = 0, run_inflight = 0;
+    uint64_t pass_seq = 0;                               // passes begun: an overlapped pass k runs on compute stream k mod 2
+    bool last_pass_deferred = false;                     // the last pass that finished deferred lines (pass_overlaps)
+    uint64_t prev_t_last = 0;                            // t_last of the last finished pass's main kernel (pass_main_ticks); 0: none since the last host sync
     int counts_in_slot = -1;                             // >= 0: the newest counts live in that slot's vector, not yet in d_counts (fetch_slot_counts)
     void *d_run_in = nullptr;  uint64_t d_run_in_cap = 0;  uint64_t run_rows = 0;  bool have_rows = false;
     // timing of the last calls
@@ -174,7 +195,8 @@ extern "C" int svjg_init(int device, svjg_ctx **out) {
     if (device < 0 || device >= n) { g_init_error = "device index out of range"; return SVJG_E_ARG; }
     svjg_ctx *c = new svjg_ctx();
     c->device = device;
-    if (hipSetDevice(device) != hipSuccess || hipStreamCreate(&c->stream) != hipSuccess) {
+    if (hipSetDevice(device) != hipSuccess || hipStreamCreate(&c->stream) != hipSuccess || hipStreamCreate(&c->stream2) != hipSuccess ||
+        hipEventCreateWithFlags(&c->ev_join[0], hipEventDisableTiming) != hipSuccess || hipEventCreateWithFlags(&c->ev_join[1], hipEventDisableTiming) != hipSuccess) {
         g_init_error = "hipSetDevice / hipStreamCreate failed";
         delete c;
         return SVJG_E_HIP;
@@ -183,7 +205,7 @@ extern "C" int svjg_init(int device, svjg_ctx **out) {
     if (hipGetDeviceProperties(&prop, device) == hipSuccess) c->n_cu = prop.multiProcessorCount;
     if (hipDeviceGetAttribute(&c->wall_khz, hipDeviceAttributeWallClockRate, device) != hipSuccess || c->wall_khz < 1) c->wall_khz = 0;
     for (auto &ev : c->ev) hipEventCreate(&ev);
-    if (hipMalloc(&c->d_dbg, 32 * 8) != hipSuccess || hipMalloc(&c->d_st, sizeof(DevStatus)) != hipSuccess ||
+    if (hipMalloc(&c->d_dbg, DBG_WORDS * 8) != hipSuccess || hipMalloc(&c->d_st, sizeof(DevStatus)) != hipSuccess ||
         hipHostMalloc((void **)&c->h_stp, 2 * sizeof(DevStatus), hipHostMallocDefault) != hipSuccess) {
         g_init_error = "hipMalloc failed";
         delete c;
@@ -210,16 +232,17 @@ extern "C" void svjg_destroy(svjg_ctx *c) {
     if (!c) return;
     hipSetDevice(c->device);
     if (c->stream) hipStreamSynchronize(c->stream);
+    if (c->stream2) hipStreamSynchronize(c->stream2);
     if (c->copy_stream) hipStreamSynchronize(c->copy_stream);
     if (c->comm) ncclCommDestroy(c->comm);
     free_graph(c);
-    hipFree(c->d_long);
+    hipFree(c->d_long); hipFree(c->d_long2);
     hipFree(c->d_gaf); hipFree(c->d_deferred); hipFree(c->d_recs); hipFree(c->d_host); hipFree(c->d_st); hipFree(c->d_logfact);
     hipFree(c->d_bsum); hipFree(c->d_run_in);
     hipFree(c->d_cm); hipFree(c->d_cstage);
     for (auto &b : c->leg) { hipFree(b.d); if (b.h) hipHostFree(b.h); }
     for (auto &r : c->run) {
-        hipFree(r.d); hipFree(r.counts);
+        hipFree(r.d); hipFree(r.counts); hipFree(r.deferred); hipFree(r.host);
         if (r.h) hipHostFree(r.h);
         for (auto &e : r.ev) if (e) hipEventDestroy(e);
         if (r.computed) hipEventDestroy(r.computed);
@@ -230,9 +253,31 @@ extern "C" void svjg_destroy(svjg_ctx *c) {
     for (auto &ev : c->stage_ev) if (ev) hipEventDestroy(ev);
     for (auto &st : c->stage_stream) if (st) hipStreamDestroy(st);
     for (auto &ev : c->ev) if (ev) hipEventDestroy(ev);
+    for (auto &ev : c->ev_join) if (ev) hipEventDestroy(ev);
     if (c->copy_stream) hipStreamDestroy(c->copy_stream);
+    if (c->stream2) hipStreamDestroy(c->stream2);
     if (c->stream) hipStreamDestroy(c->stream);
     delete c;
+}
+
+// ---- the two compute streams ----
+// Everything but an overlapped fused pass runs on c->stream and begins with serial_enter: c->stream then comes behind whatever stream2 holds
+// (a pass's main kernel, a settle step), and the next pass that goes to stream2 will come behind this work (svjg_run_begin).
+static int serial_enter(svjg_ctx *c) {
+    if (c->second_busy) {
+        HIPCHK(c, hipEventRecord(c->ev_join[1], c->stream2));
+        HIPCHK(c, hipStreamWaitEvent(c->stream, c->ev_join[1], 0));
+        c->second_busy = false;
+    }
+    c->first_dirty = true;
+    return 0;
+}
+// the host waits for both (a buffer is about to be freed, the caller wants everything done)
+static int sync_compute(svjg_ctx *c) {
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    if (c->stream2) HIPCHK(c, hipStreamSynchronize(c->stream2));
+    c->second_busy = false; c->first_dirty = false; c->prev_t_last = 0;
+    return 0;
 }
 
 template <class T>
@@ -330,6 +375,7 @@ extern "C" int svjg_reset_counts(svjg_ctx *c) {
     if (!c || !c->have_counts) return SVJG_E_ARG;
     c->counts_in_slot = -1;
     HIPCHK(c, hipSetDevice(c->device));
+    { const int rc0 = serial_enter(c); if (rc0) return rc0; }
     HIPCHK(c, hipMemsetAsync(c->d_counts, 0, counts_bytes(c), c->stream));
     return reset_status(c, true);                             // (nothing to wait for: the next call on the stream comes behind both)
 }
@@ -338,7 +384,7 @@ extern "C" int svjg_reset_counts(svjg_ctx *c) {
 static int gaf_reserve(svjg_ctx *c, uint64_t n, uint64_t *need_out) {
     const uint64_t need = ((n + 15) & ~15ull) + TEXT + 64;
     if (need > c->gaf_cap) {
-        HIPCHK(c, hipStreamSynchronize(c->stream));
+        { const int rc0 = sync_compute(c); if (rc0) return rc0; }     // (both compute streams read the text)
         hipFree(c->d_gaf); c->d_gaf = nullptr; c->gaf_cap = 0;
         HIPCHK(c, hipMalloc((void **)&c->d_gaf, need));
         c->gaf_cap = need;
@@ -453,6 +499,7 @@ static int ensure(svjg_ctx *c, void **p, uint64_t *cap, uint64_t want, size_t el
     if (!q) HIPCHK(c, hipMalloc(&q, want * elem));
     if (keep && *p && *cap) HIPCHK(c, hipMemcpyAsync(q, *p, *cap * elem, hipMemcpyDeviceToDevice, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
+    if (c->second_busy) HIPCHK(c, hipStreamSynchronize(c->stream2));      // (nothing enqueued anywhere still uses the old block)
     hipFree(*p);
     *p = q; *cap = want;
     return 0;
@@ -471,11 +518,16 @@ static int ensure_pinned(svjg_ctx *c, void **p, uint64_t *cap, uint64_t want, un
 // arguments and geometry of one k_classify_main launch over the lines of the resident text that lie in [begin, end)
 // The passes of svjg_run_begin keep their counts in vectors of their own; the rest of the API works on d_counts: the newest pass's
 // vector is copied there when someone asks for it (svjg_get_counts, svjg_genotype, svjg_classify adding to it, ...).
+static int settle_pass(svjg_ctx *c, svjg_ctx::RunSlot &r);
 static int fetch_slot_counts(svjg_ctx *c) {
     if (c->counts_in_slot < 0) return 0;
     const int k = c->counts_in_slot;
     c->counts_in_slot = -1;
     HIPCHK(c, hipSetDevice(c->device));
+    // an overlapped pass still in flight has no exact-path hits in its vector until it is settled: do that now (a host wait for the pass; svjg_run_end
+    // then finds it settled), so that the counts handed out are the whole pass's, as they were when the exact path ran on the stream
+    if (c->run[k].inflight && c->run[k].overlapped) { const int rc0 = settle_pass(c, c->run[k]); if (rc0) return rc0; }
+    { const int rc0 = serial_enter(c); if (rc0) return rc0; }      // (the pass that uses this slot next may run on stream2: it comes behind the copy)
     if (c->run[k].copied) HIPCHK(c, hipStreamWaitEvent(c->stream, c->run[k].copied, 0));   // (the pass's all-reduce runs on the second stream)
     HIPCHK(c, hipMemcpyAsync(c->d_counts, c->run[k].counts, counts_bytes(c), hipMemcpyDeviceToDevice, c->stream));
     return 0;
@@ -502,7 +554,7 @@ static void main_launch_setup(svjg_ctx *c, uint64_t begin, uint64_t end, uint64_
         const int by_lds = (int)((160u * 1024u) / ((lds + LDS_GRANULE - 1) / LDS_GRANULE * LDS_GRANULE));
         if (by_lds >= 1 && occ > by_lds) occ = by_lds;
         c->occ_main = occ;
-        hipFree(c->d_long); c->d_long = nullptr;
+        hipFree(c->d_long); hipFree(c->d_long2); c->d_long = nullptr; c->d_long2 = nullptr;
 #ifdef SVJG_ABLATE
         { const char *oc = getenv("SVJG_OCC"); fprintf(stderr, "[svjg diag] occupancy API: %d workgroups of %u threads per CU (LDS %zu)\n", occ, WG, lds); if (oc && atoi(oc) > 0) c->occ_main = atoi(oc); }
 #endif
@@ -530,9 +582,9 @@ static void main_launch_setup(svjg_ctx *c, uint64_t begin, uint64_t end, uint64_
 constexpr uint64_t EXACT_ROUND_PER_CU = 4;      // lines a CU in a round: the grid of the former one-wave-per-line kernel, now only the limits' unit
 constexpr uint64_t STEP_WAVE_ROUNDS = 30;       // classify_range: the roles met at ~31 k lines on 256 CUs (profiles/r04/experiments/exact_path.txt)
 constexpr uint64_t FUSED_WAVE_ROUNDS = 16;      // svjg_run_begin: r07 (profiles/r07/experiments/pass_tail.txt)
-static int launch_exact(svjg_ctx *c, const ClassifyArgs &a, uint64_t wave_rounds, const NextPass &nx) {
+static int launch_exact(svjg_ctx *c, const ClassifyArgs &a, uint64_t wave_rounds, const NextPass &nx, hipStream_t on = nullptr, unsigned long long *t_begin = nullptr) {
     const uint64_t wave_limit = wave_rounds * EXACT_ROUND_PER_CU * (uint64_t)c->n_cu;
-    hipLaunchKernelGGL(k_classify_exact, dim3((uint32_t)c->n_cu * EXACT_BLOCKS_PER_CU), dim3(EXACT_TPB), 0, c->stream, a, wave_limit, nx);
+    hipLaunchKernelGGL(k_classify_exact, dim3((uint32_t)c->n_cu * EXACT_BLOCKS_PER_CU), dim3(EXACT_TPB), 0, on ? on : c->stream, a, wave_limit, nx, t_begin);
     HIPCHK(c, hipGetLastError());
     return 0;
 }
@@ -541,6 +593,8 @@ static int launch_exact(svjg_ctx *c, const ClassifyArgs &a, uint64_t wave_rounds
 static int classify_range(svjg_ctx *c, uint64_t begin, uint64_t end, uint64_t base_offset, int want_hits) {
     HIPCHK(c, hipSetDevice(c->device));
     { const int rc0 = fetch_slot_counts(c); if (rc0) return rc0; }
+    { const int rc0 = serial_enter(c); if (rc0) return rc0; }
+    c->host_lines_src = nullptr;                                  // (d_host, wherever ensure() puts it)
     if (end <= begin) return 0;
     const uint64_t n = end - begin;
     uint64_t def_want = deferred_want(c, n);
@@ -774,9 +828,11 @@ extern "C" int svjg_get_host_lines(svjg_ctx *c, uint64_t *out, uint64_t cap, uin
     if (!c || !n) return SVJG_E_ARG;
     HIPCHK(c, hipSetDevice(c->device));
     *n = c->hs().n_host;
-    const uint64_t have = c->hs().n_host < cap ? c->hs().n_host : cap;
+    const uint64_t held = c->host_lines_src ? c->host_lines_cap : c->host_cap;       // (never beyond the list itself)
+    uint64_t have = c->hs().n_host < cap ? c->hs().n_host : cap;
+    if (have > held) have = held;
     if (have && !out) return SVJG_E_ARG;
-    if (have) HIPCHK(c, hipMemcpyAsync(out, c->d_host, have * sizeof(uint64_t), hipMemcpyDeviceToHost, c->stream));
+    if (have) HIPCHK(c, hipMemcpyAsync(out, c->host_lines_src ? c->host_lines_src : c->d_host, have * sizeof(uint64_t), hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
     return 0;
 }
@@ -918,6 +974,7 @@ extern "C" int svjg_allreduce_counts_all(svjg_ctx *const *ctxs, int n) {
 static int build_logfact(svjg_ctx *c, uint32_t upto) {
     static_assert(LF_BLOCK == LOGFACT_BLOCK, "svjg_kernels.h and svjg_geno.h disagree");
     const uint32_t want = logfact_built(upto);
+    { const int rc0 = serial_enter(c); if (rc0) return rc0; }
     hipFree(c->d_logfact); hipFree(c->d_bsum); c->d_logfact = nullptr; c->d_bsum = nullptr; c->logfact_n = 0;
     HIPCHK(c, hipMalloc((void **)&c->d_logfact, (uint64_t)want * sizeof(dd)));
     HIPCHK(c, hipMalloc((void **)&c->d_bsum, (uint64_t)(want / LF_BLOCK) * sizeof(dd)));
@@ -969,7 +1026,7 @@ static int settle_launch(svjg_ctx *c, const unsigned int *h_maxn, void *h_back, 
             if (h_maxn[1]) { c->err = "slot out of range"; return SVJG_E_ARG; }   // (checked by the kernel, row by row)
             if (h_maxn[0] == 0) return 0;                        // every row found its binomial term
             if (growths++ == 2) { c->err = "log10(i!) table could not be sized"; return SVJG_E_HIP; }
-            HIPCHK(c, hipStreamSynchronize(c->stream));          // (a pass already enqueued still uses the old table: it drains first)
+            { const int rc0 = sync_compute(c); if (rc0) return rc0; }   // (a pass already enqueued still uses the old table: it drains first)
             if (c->copy_stream) HIPCHK(c, hipStreamSynchronize(c->copy_stream));
             if (const int rc = build_logfact(c, logfact_grow_to(h_maxn[0]))) return rc;
         }
@@ -1321,17 +1378,38 @@ extern "C" int svjg_run_begin(svjg_ctx *c, uint64_t base_offset, uint32_t min_su
     const RunLayout L = run_layout(n_rows);
     svjg_ctx::RunSlot &r = c->run[c->run_head];
     int rc;
-    if ((rc = ensure(c, (void **)&c->d_deferred, &c->deferred_cap, deferred_want(c, n), sizeof(uint64_t), false))) return rc;
-    if ((rc = ensure(c, (void **)&c->d_host, &c->host_cap, 4096, sizeof(uint64_t), false))) return rc;
+    // the slot's own lists (no pass in flight uses this slot: the host has ended the pass that last did)
+    if ((rc = ensure(c, (void **)&r.deferred, &r.deferred_cap, deferred_want(c, n), sizeof(uint64_t), false))) return rc;
+    if ((rc = ensure(c, (void **)&r.host, &r.host_cap, 4096, sizeof(uint64_t), false))) return rc;
     if (c->logfact_n == 0 && (rc = build_logfact(c, logfact_first()))) return rc;
+    // The pass's form and compute stream (svjg_pass.h).  Overlapped: pass k on stream k mod 2 — k_step_reset of its OWN slot in one-wave blocks
+    // (early: behind the main kernel of pass k - 2, beside that of pass k - 1), k_classify_main, the `computed` record, and nothing else: what
+    // was deferred is settled by svjg_run_end.  Otherwise, as before r11: on c->stream, k_classify_exact behind the main kernel.
+    const bool all_slow = (c->gflags & SVJG_GRAPH_ALL_SLOW) != 0;
+    r.overlapped = pass_overlaps(c->comm != nullptr, all_slow, kernel_ms_by_events(c), c->last_pass_deferred);
+    r.on = (r.overlapped && (c->pass_seq & 1)) ? c->stream2 : c->stream;
+    ++c->pass_seq;
+    r.chained = c->run_inflight > 0;
+    r.inflight = false; r.settled = false; r.geno_owed = false; r.ms_settle = 0;
+    if (r.overlapped) {
+        if (c->first_dirty) {                                     // stream2 behind what c->stream holds beside overlapped passes (a pass in the other form, a step-by-step call)
+            HIPCHK(c, hipEventRecord(c->ev_join[0], c->stream));
+            HIPCHK(c, hipStreamWaitEvent(c->stream2, c->ev_join[0], 0));
+            c->first_dirty = false;
+        }
+        if (r.on == c->stream2) c->second_busy = true;
+    } else if ((rc = serial_enter(c))) return rc;                 // (behind an overlapped pass on stream2: its `computed` is that stream's tail)
+    const hipStream_t on = r.on;
     r.base_offset = base_offset; r.min_support = min_support; r.err = err;
     uint8_t *base = (uint8_t *)r.d;
     DevStatus *d_st = (DevStatus *)(base + L.status);             // (the pass's own status block: its tail goes to the host in one small copy)
     if (r.counts_cap < (uint64_t)c->n_slots + GUARD_WORDS) { c->err = "svjg_set_rows must follow svjg_load_graph"; return SVJG_E_ARG; }
     GenoArgs ga = run_geno_args(c, r, L, min_support, err, r.counts);
     const uint64_t words = (uint64_t)c->n_slots + GUARD_WORDS;
-    if (!r.clean) {                                           // the first pass behind svjg_set_rows / svjg_load_graph, or behind a pass without text
-        hipLaunchKernelGGL(k_step_reset, dim3(capped_grid(words)), dim3(TPB), 0, c->stream, NextPass{r.counts, words, d_st, ga.max_n});
+    if (!r.clean) {                                           // an overlapped pass; the first pass behind svjg_set_rows / svjg_load_graph, or behind a pass without text
+        const uint32_t rb = r.overlapped ? 64u : TPB;            // (one-wave blocks find room beside fourteen classify workers a CU)
+        const uint64_t rg = (words + rb - 1) / rb;
+        hipLaunchKernelGGL(k_step_reset, dim3(rg > 1024 ? 1024u : rg < 1 ? 1u : (uint32_t)rg), dim3(rb), 0, on, NextPass{r.counts, words, d_st, ga.max_n});
     }
     r.clean = false;
     // SVJG_KERNEL_MS=events: k_classify_main's time from an event pair around it, as before r07 (two barrier packets a pass; for
@@ -1343,10 +1421,23 @@ extern "C" int svjg_run_begin(svjg_ctx *c, uint64_t base_offset, uint32_t min_su
         size_t lds = 0;
         main_launch_setup(c, 0, n, base_offset, 0, a, grid, lds);
         if (!a.long_pre) { c->err = "no memory for the workers' scratch words"; return SVJG_E_NOMEM; }
+        // what this launch may NOT share with the main kernel of the pass beside it: count vector and status block (the slot's), the two lists
+        // (the slot's), the workers' scratch words (the stream's).  Text and graph tables are read-only; hit records are not written (want_hits 0).
         a.st = d_st; a.counts = r.counts;
-        if (r.timed_by_events) HIPCHK(c, hipEventRecord(r.ev[0], c->stream));
-        hipLaunchKernelGGL(k_classify_main, dim3(grid), dim3(WG), lds, c->stream, a);
-        if (r.timed_by_events) HIPCHK(c, hipEventRecord(r.ev[1], c->stream));
+        a.deferred = r.deferred; a.deferred_cap = r.deferred_cap; a.host_lines = r.host; a.host_cap = r.host_cap;
+        if (on == c->stream2) {                                   // (the second block of scratch words: only a context that overlaps passes has one)
+            if (!c->d_long2 && hipMalloc((void **)&c->d_long2, (uint64_t)c->n_cu * (uint64_t)c->occ_main * LONG_WORDS * sizeof(uint32_t)) != hipSuccess) c->d_long2 = nullptr;
+            if (!c->d_long2) { (void)hipGetLastError(); c->err = "no memory for the workers' scratch words"; return SVJG_E_NOMEM; }
+            a.long_pre = c->d_long2;
+        }
+        r.cargs = a;
+#ifdef SVJG_ENDTIMES
+        HIPCHK(c, hipMemsetAsync(c->d_dbg + ENDT_SUM, 0, (DBG_WORDS - ENDT_SUM) * 8, on));   // (one launch at a time: svjg_run_resident)
+#endif
+        if (r.timed_by_events) HIPCHK(c, hipEventRecord(r.ev[0], on));
+        hipLaunchKernelGGL(k_classify_main, dim3(grid), dim3(WG), lds, on, a);
+        HIPCHK(c, hipGetLastError());
+        if (r.timed_by_events) HIPCHK(c, hipEventRecord(r.ev[1], on));
         // Between this k_classify_main and the next pass's the compute stream carries ONE launch and ONE event record (`computed`):
         //   k_classify_exact  the exact path, the number of deferred lines read on the device (launch_exact above).  So whatever a shard defers
         //                     is counted before the pass's all-reduce; only a LIST that overflowed makes the pass repeat (svjg_pass.h).  The same
@@ -1355,13 +1446,17 @@ extern "C" int svjg_run_begin(svjg_ctx *c, uint64_t base_offset, uint32_t min_su
         //                     k_step_reset.
         // Before r07 there were three launches (two exact-path kernels, k_step_reset) and three event records; the timeline of both:
         // profiles/r07/experiments/pass_tail.txt.
-        svjg_ctx::RunSlot &nxt = c->run[(c->run_head + 1) % RUN_SLOTS];
-        NextPass nx{};
-        if (nxt.d && nxt.counts && nxt.counts_cap >= words) {
-            nx.counts = nxt.counts; nx.n_words = words; nx.st = (DevStatus *)((uint8_t *)nxt.d + L.status); nx.max_n = (unsigned int *)((uint8_t *)nxt.d + L.maxn);
+        // An OVERLAPPED pass has none of this: its stream carries k_step_reset, k_classify_main and `computed`, so that the next pass's workers —
+        // on the other stream — move into the slots this one's vacate; 53 760 B of LDS a block would only be there when THAT pass drains.
+        if (!r.overlapped) {
+            svjg_ctx::RunSlot &nxt = c->run[(c->run_head + 1) % RUN_SLOTS];
+            NextPass nx{};
+            if (nxt.d && nxt.counts && nxt.counts_cap >= words) {
+                nx.counts = nxt.counts; nx.n_words = words; nx.st = (DevStatus *)((uint8_t *)nxt.d + L.status); nx.max_n = (unsigned int *)((uint8_t *)nxt.d + L.maxn);
+            }
+            if ((rc = launch_exact(c, a, FUSED_WAVE_ROUNDS, nx))) return rc;
+            nxt.clean = nx.counts != nullptr;
         }
-        if ((rc = launch_exact(c, a, FUSED_WAVE_ROUNDS, nx))) return rc;
-        nxt.clean = nx.counts != nullptr;
     }
     // The count all-reduce of this pass — every rank issues its collectives in the same order, one per pass — runs on the compute
     // stream, between this pass's kernels and the next pass's: the classify kernel fills every CU (fourteen workers take 126 of a
@@ -1389,7 +1484,7 @@ extern "C" int svjg_run_begin(svjg_ctx *c, uint64_t base_offset, uint32_t min_su
         if (n && r.timed_by_events) { HIPCHK(c, hipEventRecord(r.ev[2], c->stream)); r.slow_end_own = true; }
         if ((rc = reduce_on(c->stream))) return rc;
     }
-    HIPCHK(c, hipEventRecord(r.computed, c->stream));
+    HIPCHK(c, hipEventRecord(r.computed, on));
     HIPCHK(c, hipStreamWaitEvent(c->copy_stream, r.computed, 0));
     if (c->comm && allreduce_second && (rc = reduce_on(c->copy_stream))) return rc;
     if (n_rows) {
@@ -1404,12 +1499,39 @@ extern "C" int svjg_run_begin(svjg_ctx *c, uint64_t base_offset, uint32_t min_su
         HIPCHK(c, hipGetLastError());
         HIPCHK(c, hipEventRecord(r.ev[5], c->copy_stream));
     }
-    // the pass's tail: max_n, status, guard words
-    HIPCHK(c, hipMemcpyAsync((uint8_t *)r.h + L.h_tail, r.d, L.tail_bytes, hipMemcpyDeviceToHost, c->copy_stream));
+    // the pass's tail: max_n, status, guard words — one wave that writes them into the mapped host block, as k_genotype does its results (a
+    // hipMemcpyAsync here is the runtime's copy kernel, whose 256-thread blocks wait for the next pass's classify kernel to drain)
+    static_assert(sizeof(DevStatus) % 8 == 0, "the tail is copied in 8-byte words");
+    hipLaunchKernelGGL(k_pass_tail, dim3(1), dim3(64), 0, c->copy_stream, (unsigned long long *)((uint8_t *)r.h_dev + L.h_tail), (const unsigned long long *)r.d, (uint32_t)(L.tail_bytes / 8));
+    HIPCHK(c, hipGetLastError());
     HIPCHK(c, hipEventRecord(r.copied, c->copy_stream));
     c->counts_in_slot = c->run_head;
-    r.had_text = n != 0;
+    r.had_text = n != 0; r.inflight = true;
     c->run_head = (c->run_head + 1) % RUN_SLOTS; ++c->run_inflight;
+    return 0;
+}
+
+// The settle step of an overlapped pass (svjg_pass.h: pass_settles_exact), once per pass: wait for the pass's tail; if it deferred lines and its lists
+// held, k_classify_exact on the pass's own deferred list into the pass's own count vector, behind its main kernel's stream (the blocks find their LDS
+// when the NEXT pass's classify kernel drains), and the status block once more into the pass's pinned tail — overflow bits the exact path set (the
+// list of lines for the host) included: svjg_run_end reads them there and repeats the pass.  t_first, which is kept, gives way to the launch's own
+// start for the copy: ms_settle is first block in to last block out.  Called by svjg_run_end, and ahead of it by whoever asks for the pass's counts.
+static int settle_pass(svjg_ctx *c, svjg_ctx::RunSlot &r) {
+    if (r.settled) return 0;
+    HIPCHK(c, hipEventSynchronize(r.copied));
+    r.settled = true;
+    const RunLayout L = run_layout(c->run_rows);
+    DevStatus *d_st = (DevStatus *)((uint8_t *)r.d + L.status);
+    DevStatus *h_st = (DevStatus *)((uint8_t *)r.h + L.h_tail + L.status);
+    if (!r.had_text || !pass_settles_exact(c->comm != nullptr, (c->gflags & SVJG_GRAPH_ALL_SLOW) != 0, r.overlapped, h_st->overflow, h_st->n_deferred)) return 0;
+    const unsigned long long t_main_first = h_st->t_first;
+    HIPCHK(c, hipMemsetAsync(&d_st->t_first, 0xFF, 8, r.on));
+    if (const int rc = launch_exact(c, r.cargs, FUSED_WAVE_ROUNDS, NextPass{}, r.on, &d_st->t_first)) return rc;
+    HIPCHK(c, hipMemcpyAsync(h_st, d_st, sizeof(DevStatus), hipMemcpyDeviceToHost, r.on));
+    HIPCHK(c, hipStreamSynchronize(r.on));
+    if (c->wall_khz && h_st->t_exact > h_st->t_first) r.ms_settle = (float)(h_st->t_exact - h_st->t_first) / (float)c->wall_khz;
+    h_st->t_first = t_main_first;
+    r.geno_owed = true;
     return 0;
 }
 
@@ -1425,6 +1547,8 @@ extern "C" int svjg_run_end(svjg_ctx *c, const uint8_t **gt, const int32_t **pl,
     uint8_t *hb = (uint8_t *)r.h;
     int rc;
     HIPCHK(c, hipEventSynchronize(r.copied));                              // the pass's one host wait
+    r.inflight = false;
+    if ((rc = settle_pass(c, r))) return rc;                               // (an overlapped pass that deferred lines: one more; nothing if somebody asked for its counts before)
     const uint8_t *tail = hb + L.h_tail;
     c->hs() = *(const DevStatus *)(tail + L.status);
     // ---- what the host would have decided in between ----
@@ -1434,18 +1558,44 @@ extern "C" int svjg_run_end(svjg_ctx *c, const uint8_t **gt, const int32_t **pl,
         // that had work (never the all-reduce).  wall_clock64() counts at wall_khz.
         const DevStatus &t = c->hs();
         const float per_tick = c->wall_khz ? 1.0f / (float)c->wall_khz : 0.0f;
-        c->ms_main_stamps = t.t_last > t.t_first ? (float)(t.t_last - t.t_first) * per_tick : 0.0f;
+        // (overlapped launches: the interval this one shares with the pass in front of it counts once — pass_main_ticks)
+        c->ms_main_stamps = (float)pass_main_ticks(t.t_first, t.t_last, r.chained ? c->prev_t_last : 0) * per_tick;
+        c->prev_t_last = t.t_last;
         c->ms_main_events = 0;
         c->ms_main = c->ms_main_stamps;
-        if (t.n_deferred && t.t_exact > t.t_last) c->ms_slow = (float)(t.t_exact - t.t_last) * per_tick;
+        if (r.geno_owed) c->ms_slow = r.ms_settle;            // (the settle step's launch, long behind t_last)
+        else if (t.n_deferred && t.t_exact > t.t_last) c->ms_slow = (float)(t.t_exact - t.t_last) * per_tick;
         if (r.timed_by_events) {
             HIPCHK(c, hipEventElapsedTime(&c->ms_main_events, r.ev[0], r.ev[1]));
             c->ms_main = c->ms_main_events;
             if (t.n_deferred) HIPCHK(c, hipEventElapsedTime(&c->ms_slow, r.ev[1], r.slow_end_own ? r.ev[2] : r.computed));   // (the exact-path kernel alone: never the all-reduce)
         }
     }
+#ifdef SVJG_ENDTIMES
+    if (r.had_text) {                                             // measurement only: how long before the launch's last worker the others ended
+        static unsigned long long d[DBG_WORDS];
+        HIPCHK(c, hipMemcpy(d, c->d_dbg, sizeof d, hipMemcpyDeviceToHost));
+        const unsigned long long nw = d[ENDT_N], span = c->hs().t_last - c->hs().t_first;
+        const double us = c->wall_khz ? 1e3 / c->wall_khz : 0.0;
+        double q[3] = {0, 0, 0};                                  // quartiles of (t_last - end), from the histogram (bucket centres)
+        unsigned long long seen = 0;
+        for (uint32_t b = 0, k = 0; b < ENDT_BUCKETS && k < 3; ++b)
+            for (seen += d[ENDT_HIST + b]; k < 3 && seen * 4 >= nw * (k + 1) && nw; ++k) q[2 - k] = ((double)span - (b + 0.5) * ENDT_TICKS) * us;
+        fprintf(stderr, "[svjg endtimes] %llu workers, launch %.1f us; a worker ended before the last one: mean %.1f us, quartiles %.1f / %.1f / %.1f us; ended in the last 20/50/100/200 us:",
+                nw, span * us, nw ? ((double)span - (double)d[ENDT_SUM] / nw) * us : 0.0, q[0], q[1], q[2]);
+        for (const double w : {20.0, 50.0, 100.0, 200.0}) {
+            unsigned long long in = 0;
+            for (uint32_t b = 0; b < ENDT_BUCKETS; ++b) if (((double)span - (b + 1.0) * ENDT_TICKS) * us < w) in += d[ENDT_HIST + b];
+            fprintf(stderr, " %llu", in);
+        }
+        fprintf(stderr, "\n");
+    }
+#endif
     if (n_rows) HIPCHK(c, hipEventElapsedTime(&c->ms_geno, r.ev[4], r.ev[5]));
-    bool again = false;                                           // the pass was repeated step by step: the genotypes again, from d_counts
+    c->last_pass_deferred = r.had_text && c->hs().n_deferred != 0;
+    c->host_lines_src = r.host; c->host_lines_cap = r.host_cap;
+    bool repeated = false;                                        // the pass was repeated step by step: its counts are in d_counts
+    bool again = false;                                           // the genotypes are owed once more (a repeated pass, a settle step)
     const unsigned long long *gd = (const unsigned long long *)(tail + L.guard);   // (meaningful under a communicator: the sums over the ranks)
     if (pass_repeats(c->comm != nullptr, c->hs().overflow, gd[GUARD_REPEAT])) {
         // a list of this rank — or, under a communicator, of ANY rank (svjg_pass.h: the ranks decide together, so all of them issue the
@@ -1457,8 +1607,9 @@ extern "C" int svjg_run_end(svjg_ctx *c, const uint8_t **gt, const int32_t **pl,
         if (rc && rc != SVJG_E_INPUT) return rc;
         if (c->comm) { const std::string keep = c->err; const int rc2 = svjg_allreduce_counts(c); if (rc2 && !rc) return rc2; if (rc) c->err = keep; }
         if (rc) return rc;
-        again = true;
+        again = true; repeated = true;
     } else {
+        again = r.geno_owed;
         c->total_deferred = c->hs().n_deferred;
         if (c->hs().err != ~0ull) return SVJG_E_INPUT;
         if (c->comm && pass_counts_overflowed(gd[GUARD_MAX_REF], gd[GUARD_MAX_ALT])) { c->err = "more than 2^32 informative alignments for one SV"; return SVJG_E_OVERFLOW; }
@@ -1466,7 +1617,7 @@ extern "C" int svjg_run_end(svjg_ctx *c, const uint8_t **gt, const int32_t **pl,
     // (either way: lines the kernels set aside for the host are neither counted nor fatal — the caller has to know)
     if (c->hs().n_host) { c->err = "the text holds lines only the host can decide (non-ASCII digits in a decimal column: svjg_get_host_lines); classify it with svjg_classify"; return SVJG_E_ARG; }
     if (n_rows) {
-        GenoArgs ga = run_geno_args(c, r, L, r.min_support, r.err, again ? c->d_counts : r.counts);
+        GenoArgs ga = run_geno_args(c, r, L, r.min_support, r.err, repeated ? c->d_counts : r.counts);
         uint8_t *h_maxn = hb + L.h_tail + L.maxn;                 // (the results are already in the mapped host block: only the pair comes back)
         if ((rc = settle_launch(c, (const unsigned int *)h_maxn, h_maxn, (const uint8_t *)r.d + L.maxn, 8, again, [&] { return launch_genotype(c, ga); }))) return rc;
     }
@@ -1499,7 +1650,7 @@ extern "C" int svjg_logfact_reserve(svjg_ctx *c, uint32_t entries) {
     const uint32_t want = logfact_reserve_to(c->logfact_n, entries);
     if (!want) return 0;
     HIPCHK(c, hipSetDevice(c->device));
-    HIPCHK(c, hipStreamSynchronize(c->stream));                  // (as settle_launch: a pass already enqueued still uses the old table)
+    { const int rc0 = sync_compute(c); if (rc0) return rc0; }      // (as settle_launch: a pass already enqueued still uses the old table)
     if (c->copy_stream) HIPCHK(c, hipStreamSynchronize(c->copy_stream));
     return build_logfact(c, want);
 }
@@ -1568,6 +1719,5 @@ extern "C" int svjg_copy_rate(svjg_ctx *c, uint64_t n_bytes, double *copy_gb_per
 extern "C" int svjg_sync(svjg_ctx *c) {
     if (!c) return SVJG_E_ARG;
     HIPCHK(c, hipSetDevice(c->device));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    return 0;
+    return sync_compute(c);                                       // (both compute streams)
 }

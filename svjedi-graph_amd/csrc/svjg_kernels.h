@@ -94,6 +94,14 @@ static_assert(LDS_MAIN <= 9 * LDS_GRANULE, "fourteen workers per CU");
 static_assert(L_NDBM % 16 == 0 && L_TBM % 16 == 0 && L_OPL % 16 == 0 && L_LINE % 16 == 0 && L_RL % 16 == 0, "LDS alignment");
 #endif
 
+// ClassifyArgs::dbg: 32 words of the -DSVJG_TIMING builds; a -DSVJG_ENDTIMES build keeps the workers' end times behind them
+constexpr uint32_t ENDT_SUM = 32, ENDT_N = 33, ENDT_HIST = 34, ENDT_BUCKETS = 256, ENDT_TICKS = 1024;
+#ifdef SVJG_ENDTIMES
+constexpr uint32_t DBG_WORDS = ENDT_HIST + ENDT_BUCKETS;
+#else
+constexpr uint32_t DBG_WORDS = 32;
+#endif
+
 struct ClassifyArgs {
     const uint8_t *gaf;                  // resident text, allocation padded with >= TEXT + 64 zero bytes
     uint64_t begin;                      // first byte to classify (a line start); what lies in front of it belongs to another launch
@@ -1415,6 +1423,15 @@ __global__ __launch_bounds__(WG, SVJG_MINW) void k_classify_main(ClassifyArgs a)
   }
     if (lane == 0 && wave_lines) atomicAdd(&a.st->n_lines, wave_lines);
     if (lane == 0) atomicMax(&a.st->t_last, (unsigned long long)wall_clock64());
+#ifdef SVJG_ENDTIMES
+    // measurement only (tools/end_times.py): when this worker ended, counted from the launch's t_first — the sum of all workers (a.dbg[ENDT_SUM]), how
+    // many they were, and a histogram in buckets of ENDT_TICKS ticks — for the host to set against t_last (svjg_run_end prints the drain)
+    if (lane == 0) {
+        const unsigned long long dt = (unsigned long long)wall_clock64() - atomicAdd(&a.st->t_first, 0ull);
+        atomicAdd(&a.dbg[ENDT_SUM], dt); atomicAdd(&a.dbg[ENDT_N], 1ull);
+        atomicAdd(&a.dbg[ENDT_HIST + (dt / ENDT_TICKS < ENDT_BUCKETS - 1 ? dt / ENDT_TICKS : ENDT_BUCKETS - 1)], 1ull);
+    }
+#endif
 #ifdef SVJG_TIMING
     if ((a.diag & 16u) && lane == 0)
         for (int i = 0; i < 16; ++i) atomicAdd(&a.dbg[i], acc[i]);
@@ -1460,8 +1477,16 @@ __device__ __forceinline__ void reset_next_pass(const NextPass &nx, uint64_t fir
         nx.max_n[0] = 0u; nx.max_n[1] = 0u;
     }
 }
+// (blocks of any size up to TPB: an overlapped pass launches one-wave blocks, which find room beside a running k_classify_main)
 __global__ __launch_bounds__(TPB) void k_step_reset(NextPass nx) {
-    reset_next_pass(nx, (uint64_t)blockIdx.x * TPB + threadIdx.x, (uint64_t)gridDim.x * TPB);
+    reset_next_pass(nx, (uint64_t)blockIdx.x * blockDim.x + threadIdx.x, (uint64_t)gridDim.x * blockDim.x);
+}
+
+// The tail of a fused pass's device block (max_n, status block, guard words: run_layout) -> the pass's mapped pinned block, by ONE wave behind
+// k_genotype, which delivers its results the same way.  (The runtime's copy kernel for these few hundred bytes is 256-thread blocks that find
+// no room beside fourteen classify workers a CU: the tail reached the host only when the next pass's classify kernel drained.)
+__global__ __launch_bounds__(64) void k_pass_tail(unsigned long long *dst, const unsigned long long *src, uint32_t n_words) {
+    for (uint32_t i = threadIdx.x; i < n_words; i += 64) dst[i] = src[i];
 }
 
 // what the exact routine returned for the line at file offset `off`: the exception the reference would die with (the first of
@@ -1848,8 +1873,11 @@ constexpr uint32_t EXACT_LANE_BYTES = 2 * (EXACT_LANE_STAGE + SLOW_LANE_SCRATCH)
 constexpr uint32_t EXACT_LDS = SLOW_WAVE_BYTES > EXACT_LANE_BYTES ? SLOW_WAVE_BYTES : EXACT_LANE_BYTES;
 constexpr uint32_t EXACT_BLOCKS_PER_CU = 3;
 static_assert(EXACT_LDS <= (128 / EXACT_BLOCKS_PER_CU) * LDS_GRANULE, "three blocks of k_classify_exact per CU");
-__global__ __launch_bounds__(EXACT_TPB) void k_classify_exact(ClassifyArgs a, uint64_t wave_limit, NextPass nx) {
+// t_begin (or nullptr): where the first block to start leaves its time — the settle step of an overlapped pass (svjg_run_end), whose launch
+// comes long after the main kernel's t_last.
+__global__ __launch_bounds__(EXACT_TPB) void k_classify_exact(ClassifyArgs a, uint64_t wave_limit, NextPass nx, unsigned long long *t_begin) {
     __shared__ __attribute__((aligned(16))) uint8_t pool[EXACT_LDS];
+    if (t_begin && threadIdx.x == 0) atomicMin(t_begin, (unsigned long long)wall_clock64());
     if (nx.counts) reset_next_pass(nx, (uint64_t)blockIdx.x * EXACT_TPB + threadIdx.x, (uint64_t)gridDim.x * EXACT_TPB);
     const uint64_t n_def = exact_n_def(a);                              // (the same in every block: neither role writes what it reads)
     if (!n_def) return;

@@ -8,6 +8,15 @@
 // communicator that decision is COLLECTIVE: every rank puts "I must repeat" into guard word 2, the words travel through the
 // pass's own all-reduce, and every rank repeats (classify step by step + ONE more all-reduce) iff the sum is not zero — so all
 // ranks issue the same number of collectives in the same order and none hands out a sum that lacks a rank's deferred lines.
+//
+// A ONE-GPU pass (no communicator, a graph whose lines are not all the exact path's, the kernels timed by their stamps) runs in the
+// OVERLAPPED form: consecutive passes alternate between two compute streams, so that the workers of pass k + 1 move into the slots
+// those of pass k vacate, and nothing sits on a compute stream between two k_classify_main — no k_classify_exact either.  Such a
+// pass has a SECOND thing the host settles at svjg_run_end: lines that were deferred.  n_deferred comes back in the pass's status
+// block; if it is not zero the host launches k_classify_exact on the pass's own deferred list into the pass's own count vector,
+// runs the genotypes again and waits once more (pass_settles_exact; the pass is not repeated; whoever asks for the pass's counts before
+// svjg_run_end settles it there and then; overflow bits the exact path sets repeat the pass like the main kernel's: pass_repeats).  A context whose last finished pass
+// deferred lines runs its next pass in the former form, exact path on the stream (pass_overlaps), until a pass defers nothing.
 #pragma once
 #include <stdint.h>
 
@@ -42,6 +51,28 @@ uint64_t pass_repeat_word(uint32_t overflow_bits) { return overflow_bits ? 1u : 
 // otherwise the rank is alone and its own status decides.
 inline bool pass_repeats(bool has_comm, uint32_t own_overflow_bits, uint64_t guard_repeat_sum) {
     return has_comm ? guard_repeat_sum != 0 : own_overflow_bits != 0;
+}
+
+// the form of the next pass (svjg_run_begin).  Overlapped — two compute streams, no exact-path launch on them — unless the pass's
+// all-reduce needs the exact path's hits first (has_comm), every line is the exact path's (all_slow), the kernels are timed by event
+// pairs on the stream (timed_by_events), or the last pass that finished on this context deferred lines: a settle step waits for the
+// NEXT pass's main kernel to drain, which a stream of deferring passes would pay every time.
+inline bool pass_overlaps(bool has_comm, bool all_slow, bool timed_by_events, bool last_pass_deferred) {
+    return !has_comm && !all_slow && !timed_by_events && !last_pass_deferred;
+}
+
+// does svjg_run_end owe the pass its exact path (the settle step)?  Only a pass in the overlapped form, which has none on its stream
+// (has_comm / all_slow: never overlapped; given so that the rule stands by itself); a list that overflowed repeats the pass instead.
+inline bool pass_settles_exact(bool has_comm, bool all_slow, bool overlapped, uint32_t own_overflow_bits, uint64_t n_deferred) {
+    return overlapped && !has_comm && !all_slow && !own_overflow_bits && n_deferred != 0;
+}
+
+// kernel_ms()[0] of a fused pass, in ticks of the stamps' clock: its first worker's start to its last worker's end — but where the
+// pass before (prev_t_last != 0: it ran on this context with no host synchronisation in between) was still running when this one's
+// first worker started, only from that pass's end: the interval two overlapped launches share is counted once, in the earlier one.
+inline uint64_t pass_main_ticks(uint64_t t_first, uint64_t t_last, uint64_t prev_t_last) {
+    const uint64_t from = prev_t_last > t_first ? prev_t_last : t_first;
+    return t_last > from ? t_last - from : 0;
 }
 
 // 32-bit halves of the packed ref | alt << 32 counters cannot have carried into each other iff the SUMS of the ranks' maxima fit
