@@ -38,6 +38,36 @@ SVJG_HD int64_t trunc_dd(dd v) {                         // int(Decimal): toward
     return (int64_t)t;
 }
 
+// The reference's lik0 and lik2 are SUMS of two Decimals, rounded to the context's 28 significant digits (half to even); its lik1 is ONE
+// Decimal, the exact image of a double, which no operation ever rounds.  Where the exact sum of the two products IS the double h of lik1
+// (every row at e = 0.5, where log10(1 - e) = log10(e) = log10(1 / 2), whenever the two roundings cancel), the reference therefore compares
+// round28(h) with h itself, and the 29th digit of h decides its GT.  -> the sign of round28(h) - h, 0: h has at most 28 digits.
+// h = (c1 + c2) * log10(1 / 2) with c1 + c2 in [0.5, 2^33]: 0.15 <= |h| < 2^32, so 10^s |h| with s = 27 - floor(log10 |h|) in 18..28 is
+// m * 5^s / 2^r (m: the 53 bits of |h| = m * 2^(ex - 53), r = 53 - ex - s in 1..27; r < 1: an integer): the fraction and the parity of the
+// 28th digit are the low r + 1 bits of m * 5^s, and a 64-bit product that wraps holds them.  (Differences of less than one unit of the 28th digit that are not zero cannot occur: they are
+// multiples of an ulp of the smallest product, > 2^-86 of the largest.)
+#ifdef __clang__
+#define SVJG_NOUNROLL _Pragma("nounroll")
+#else
+#define SVJG_NOUNROLL
+#endif
+SVJG_HD int dec28_round_dir(double h) {
+    const double x = fabs(h);
+    const bool inside = x >= 0.125 && x < 4294967296.0;  // (outside: 0, the row without reads; nothing else)
+    int ex; const double f = frexp(inside ? x : 1.0, &ex);
+    int p10 = -1; double ten = 1.0;
+    SVJG_NOUNROLL                                        // (unrolled, the ten powers would sit in twenty scalar registers of every kernel that inlines this)
+    for (int k = 0; k < 10; ++k) { if (x >= ten) p10 = k; ten *= 10.0; }      // (powers of ten up to 10^9: exact doubles)
+    const int s = 27 - p10, r = 53 - ex - s;             // |h| 10^s = m 5^s / 2^r, s in 18..28
+    uint64_t N = (uint64_t)ldexp(f, 53) * 3814697265625ull;                   // m * 5^18 mod 2^64
+    for (int i = 18; i < 28; ++i) N *= i < s ? 5u : 1u;                       // m * 5^s mod 2^64 (no branch: the lanes of a wave differ in s)
+    const int rr = r < 1 ? 1 : r;
+    const uint64_t frac = N & ((1ull << rr) - 1), half = 1ull << (rr - 1);
+    const bool up = frac > half || (frac == half && ((N >> rr) & 1));         // the magnitude grows (half to even)
+    if (!inside || r < 1 || frac == 0) return 0;         // (r < 1: an integer of 28 digits)
+    return (up == (h > 0)) ? 1 : -1;
+}
+
 // The log10(i!) table (k_logfact_*) never grows beyond LOGFACT_CAP entries (256 MB).  A row whose binomial term would need more
 // (n = r1 + r2 >= LOGFACT_CAP, both r1 and r2 > 0) is not computed from the table: the kernel flags it like a row next to an
 // integer boundary, and the host recomputes it with the reference's arithmetic (svjg/genotype.py: exact_pl).
@@ -48,7 +78,11 @@ constexpr uint32_t LOGFACT_CAP = 1u << 24;
 // summed in double-double: |table error| <= 2^24 * 2^-50 = 1.5e-8 per entry, and comb takes one
 // entry of n terms and two of n terms together: <= 3e-8.  The reference's log10 of a big integer goes through CPython's frexp
 // path, log10(x) + log10(2) * e: a few ulps of L = log10(comb) <= 5.1e6 (ulp 9.3e-10): <= 4e-9.  Both sides round L to a
-// double (1 ulp each).  The likelihood sums are exact here and at 28 digits in the reference.  Times ten: < 3.6e-7 < 1e-6.
+// double (1 ulp each).  The likelihood sums are exact here and at 28 digits in the reference BECAUSE each product c * L is rounded to a double
+// before it is added, as the reference's Decimal(c * L) is: geno_row, geno_row_ploidy and geno_site form them under `fp contract(off)`.  (Until
+// r12 geno_row did not, and hipcc fused the first product of each pair into two_sum: the sum then held the exact products, and the budget would
+// have had to gain two half-ulps of a product, times ten — 1e-5 at c = 2^27 —, on rows with comb = 0 that are never flagged.  Measured on the
+// device: tests/test_genotype_products_gpu.py)  Times ten: < 3.6e-7 < 1e-6.
 // The "1 ulp" of the device's log10 is measured, not assumed (2026-10-18, one MI355X, ROCm 7.2.0; the table at the cap read back through
 // svjg_logfact_read and held against 60-digit values, tests/test_logfact_gpu.py asserts each bound on every run): all 2^24 - 2 increments
 // table[i] - table[i-1] lie within 0.504 * 2^-50 of log10(i) (worst at i = 5 638 997: the device's log10 is correctly rounded or next to
@@ -82,13 +116,22 @@ struct GenoRow {
 // again; the PLs are without the binomial term) or GENO_ROW_HOST (n >= LOGFACT_CAP: row flagged, PLs without the binomial term).
 SVJG_HD uint32_t geno_row(uint32_t type, uint32_t ref, uint32_t alt, uint32_t min_support, double l_ok, double l_err, double l_half,
                           const dd *logfact, uint32_t logfact_n, GenoRow &o) {
+#ifdef __clang__
+#pragma clang fp contract(off)                           // the products are rounded to doubles before the exact sums
+#endif
     double c1, c2; uint32_t r1, r2;
     geno_counts(type, ref, alt, c1, c2, r1, r2);
-    // products in double, sums exact (the reference adds Decimal images of the doubles, :295-297)
+    // products in double, sums exact (the reference adds Decimal images of the doubles, :295-297): each product is ROUNDED before two_sum
+    // sees it.  Fused into the sum (hipcc's default contraction), the first product of each pair entered all five operations unrounded.
     dd l0 = two_sum(c1 * l_ok, c2 * l_err);
     dd l1 = dd{(c1 + c2) * l_half, 0.0};
     dd l2 = two_sum(c2 * l_ok, c1 * l_err);
     int c01 = dd_cmp(l0, l1), c02 = dd_cmp(l0, l2), c12 = dd_cmp(l1, l2);
+    if (c01 == 0 || c12 == 0) {                          // a rounded sum against the one unrounded product of the same value
+        const int d = dec28_round_dir(l1.hi);
+        if (c01 == 0) c01 = d;
+        if (c12 == 0) c12 = -d;
+    }
     uint8_t g = 3;
     if (c01 > 0 && c02 > 0) g = 0; else if (c01 < 0 && c12 > 0) g = 1; else if (c02 < 0 && c12 < 0) g = 2;
     if (!(c1 + c2 >= (double)min_support)) g = 3;
@@ -178,15 +221,31 @@ SVJG_HD uint32_t geno_row_ploidy(uint32_t type, uint32_t ref, uint32_t alt, uint
     }
     comb = dd{comb.hi, 0.0};                             // rounded to a double first, like the reference (:313)
     const uint32_t base = ploidy_tab_at(P, 0);
-    dd best{0.0, 0.0}; uint8_t g_best = 0xFF; bool tie = false, near = false;
+    // (as geno_row) the one product of an even ploidy, g = P / 2, is never rounded to 28 digits, the sums are: where a sum IS that double, the
+    // 29th digit decides.  Looked for ahead of the loop, so that the digits are worked out at one place and only for such a row.
+    int dir = 0;
+    if ((P & 1) == 0) {
+        const double h = (c1 + c2) * lr[base + P / 2];
+        bool same = false;
+        SVJG_UNROLL
+        for (uint32_t g = 0; g <= MAX_PLOIDY; ++g) {
+            if (g > P || 2 * g == P) continue;
+            const dd l = two_sum(c1 * lr[base + g], c2 * la[base + g]);
+            if (l.hi == h && l.lo == 0.0) same = true;
+        }
+        if (same) dir = dec28_round_dir(h);
+    }
+    dd best{0.0, 0.0}; uint8_t g_best = 0xFF; bool tie = false, near = false, best_single = false;
     SVJG_UNROLL
     for (uint32_t g = 0; g <= MAX_PLOIDY; ++g) {
         o.pl[g] = 0;
         if (g > P) continue;
         const double a = c1 * lr[base + g], b = c2 * la[base + g], h = (c1 + c2) * lr[base + g];
-        const dd l = (g != 0 && 2 * g == P) ? dd{h, 0.0} : two_sum(a, b);
-        const int c = g ? dd_cmp(l, best) : 1;
-        if (c > 0) { best = l; g_best = (uint8_t)g; tie = false; } else if (c == 0) tie = true;
+        const bool single = g != 0 && 2 * g == P;
+        const dd l = single ? dd{h, 0.0} : two_sum(a, b);
+        int c = g ? dd_cmp(l, best) : 1;
+        if (c == 0 && single != best_single) c = single ? -dir : dir;      // sign of (the rounded sum - the product) seen from l
+        if (c > 0) { best = l; g_best = (uint8_t)g; best_single = single; tie = false; } else if (c == 0) tie = true;
         dd s = dd_add(l, comb);
         dd p = dd_add(dd_add(dd_add(s, s), dd_add(s, s)), s);             // 5 s
         p = dd_add(p, p);                                                 // 10 s

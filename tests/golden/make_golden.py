@@ -16,7 +16,7 @@ Fixture groups:
   quirks/    G3  hand-made graph + GAF lines exercising the quirks of SURVEY Appendix D,
                  with the reference's JSON (or the exception class it dies with)
   lik/       G4  known answers of the reference's likelihood(); lik_deep_hp.npz: answers of the model tests/lik_model.py at counts
-                 the reference cannot finish
+                 the reference cannot finish; lik_products.npz: rows on which the rounding of each product c * L decides a PL or GT
   vcf/       G5  VCF-parsing cases through the reference's decision_vcf()
   synth/     G6  medium synthetic case from tools/svjg_synth (inputs regenerated from the seed):
                  sha256 of the reference JSON/VCF + the full count vector
@@ -832,6 +832,161 @@ def make_lik_deep_hp():
         rows.append((t, a, b, ms, _GTC[gt], int(pl[0]), int(pl[1]), int(pl[2]), src))
     _lik_save("lik_deep_hp.npz", rows, e, "answers of the high-precision MODEL of likelihood() (tests/lik_model.py), not of the reference: "
               "math.comb cannot finish these rows (tests/golden/make_golden.py: make_lik_deep_hp)")
+
+
+def _products_exact_pl(t, ref, alt, e):
+    """the three int(-10 * (sum of the EXACT products)) of a row whose binomial term is log10(1) = 0: products as Fraction(c) * Fraction(L)"""
+    import math
+    from fractions import Fraction as F
+    c1 = round(ref / 2, 1) if t == 0 and ref > 0 else ref
+    c2 = round(alt / 2, 1) if t == 1 and alt > 0 else alt
+    c1, c2 = F(c1), F(c2)
+    l_ok, l_err, l_half = F(math.log10(1 - e)), F(math.log10(e)), F(math.log10(1 / 2))
+    return [int(-10 * x) for x in (c1 * l_ok + c2 * l_err, F(float(c1 + c2) * float(l_half)), c2 * l_ok + c1 * l_err)]      # (lik1 is ONE rounded product everywhere)
+
+
+def _fused_row(t, ref, alt, ms, e):
+    """(GT, [PL0, PL1, PL2] without the binomial term) as geno_row gave them on the device while its products were fused (tests/lik_model.py:
+    fused_two_sum); the double-double steps behind the two sums are taken as exact"""
+    import math
+    from fractions import Fraction as F
+    from tests import lik_model as M
+    c1 = round(ref / 2, 1) if t == 0 and ref > 0 else ref
+    c2 = round(alt / 2, 1) if t == 1 and alt > 0 else alt
+    c1, c2 = float(c1), float(c2)
+    l_ok, l_err, l_half = math.log10(1 - e), math.log10(e), math.log10(1 / 2)
+    l0, l1, l2 = M.fused_two_sum(c1, l_ok, c2, l_err), ((c1 + c2) * l_half, 0.0), M.fused_two_sum(c2, l_ok, c1, l_err)
+
+    def cmp(a, b):                                       # svjg_geno.h: dd_cmp
+        return -1 if a[0] < b[0] else 1 if a[0] > b[0] else -1 if a[1] < b[1] else 1 if a[1] > b[1] else 0
+    c01, c02, c12 = cmp(l0, l1), cmp(l0, l2), cmp(l1, l2)
+    g = 0 if c01 > 0 and c02 > 0 else 1 if c01 < 0 and c12 > 0 else 2 if c02 < 0 and c12 < 0 else 3
+    if not (c1 + c2 >= ms):
+        g = 3
+    return g, [int(-10 * (F(x[0]) + F(x[1]))) for x in (l0, l1, l2)]
+
+
+def make_lik_products():
+    """lik/lik_products.npz: known answers of the reference's likelihood() (called in process) on rows where it matters that each product
+    c * L is rounded to a double BEFORE the exact sum (geno_row's two_sum; a compiler that fuses the product into the sum gives another
+    answer).  err is per row.  src:
+      fused     one-sided rows (r1 or r2 is 0, the other raw count in [2^27, 2^32), e = 5e-5) on which a PL of the reference differs from
+                int(-10 * sum of the exact products); found by search: 10 * fl(c * L) within twice ten half-ulps of an integer, then decided in Fraction
+      onesided  200 random rows of the same shape (2^27 and 2^32 - 1 among them): the control
+      half      e = 0.5, where the three likelihoods coincide mathematically and the products' roundings decide GT: every pair (c1, c2) of
+                {0, 0.5, .., 30}^2 a type can reach on which the fused sequence (tests/lik_model.py: fused_two_sum) calls another GT than
+                the reference, a quarter of the other pairs; min_support 0 and 3
+      equal     c1 == c2 = 0..60 at e = 5e-5, 1e-2, 0.3: l0 == l2 exactly, a tie a fused pair breaks without changing GT
+      halfdeep  240 one-sided rows at e = 0.5 with the other count up to 2^32 - 1: the sum of lik0 / lik2 IS the one product of lik1, so the
+                reference's rounding of its sums to 28 digits decides GT on every row, at every magnitude"""
+    import math
+    sys.path.insert(0, ROOT)
+    from tests import lik_model as M
+    ld = np.longdouble
+    assert np.finfo(ld).nmant >= 63                      # 10 * a double is exact in it
+    rng = np.random.default_rng(35)
+    e = 5e-5
+    l_err = math.log10(e)
+    cases = []                                           # (t, ref, alt, ms, e, src)
+
+    # ---- fused: the big product is c * log10(e), c the normalised deep count; windows of consecutive raw counts ----
+    def search(t, ref_side, other, start, width):
+        """rows (t, deep count in [start, start + width) on the ref or the alt side, `other` on the other side) with a PL that differs"""
+        raw = np.arange(start, start + width, dtype=np.int64)
+        halved = (t == 0 and ref_side) or (t == 1 and not ref_side)
+        c = raw.astype(np.float64) * (0.5 if halved else 1.0)
+        p = c * l_err                                    # fl(c * L), as the reference forms it
+        v = ld(10) * (p.astype(ld) + ld(0.5 * math.log10(1 - e) if other else 0.0))        # (exact where other is 0)
+        hit = np.flatnonzero(np.abs(v - np.rint(v)) <= 2 * 10 * (np.spacing(np.abs(p)) / 2).astype(ld))
+        out = []
+        for a in raw[hit].tolist():
+            ref, alt = (a, other) if ref_side else (other, a)
+            _, pl = ref_geno.likelihood([ref, alt], _LIK_TYPES[t], 3, e)
+            if [int(x) for x in pl] != _products_exact_pl(t, ref, alt, e):
+                out.append((t, ref, alt, 3, e, "fused"))
+        return out
+    fused = [(2, 0, 3000280009, 3, e, "fused")]
+    assert [int(x) for x in ref_geno.likelihood([0, 3000280009], "INV", 3, e)[1]] != _products_exact_pl(2, 0, 3000280009, e)
+    assert search(2, False, 0, 3_000_000_000, 400_000) == fused          # (the only such row of that window)
+    per_cell = {}
+    while min((per_cell.get((t, s), 0) for t in range(4) for s in (False, True))) < 4:
+        t, side = int(rng.integers(4)), bool(rng.integers(2))
+        if per_cell.get((t, side), 0) >= 4:
+            continue
+        start = int(np.exp(rng.uniform(np.log(2**27), np.log(2**32 - 400_000))))
+        other = int(rng.integers(2)) if (t == 0 and not side) or (t == 1 and side) else 0      # (the half that rounds to 0: DEL ref = 1, INS alt = 1)
+        got = [r for r in search(t, side, other, start, 400_000) if r not in fused]
+        fused += got
+        per_cell[(t, side)] = per_cell.get((t, side), 0) + len(got)
+    assert len(fused) >= 24 and {r[0] for r in fused} == {0, 1, 2, 3}
+    assert any(r[1] <= 1 for r in fused) and any(r[2] <= 1 for r in fused)
+    cases += fused
+
+    # ---- onesided: the control ----
+    ones = [(2, 0, 2**32 - 1), (3, 2**32 - 1, 0), (0, 2**32 - 1, 0), (1, 0, 2**32 - 1), (2, 2**27, 0), (3, 0, 2**27), (0, 1, 2**27), (1, 2**27, 1),
+            (0, 2**27, 0), (1, 0, 2**27)]
+    while len(ones) < 200:
+        t = int(rng.integers(4))
+        a = int(np.exp(rng.uniform(np.log(2**27), np.log(2**32 - 1))))
+        ref_side = bool(rng.integers(2))
+        other = int(rng.integers(2)) if (t == 0 and not ref_side) or (t == 1 and ref_side) else 0
+        ones.append((t, a, other) if ref_side else (t, other, a))
+    cases += [(t, a, b, int(rng.integers(2)) * 3, e, "onesided") for t, a, b in ones]
+
+    # ---- half: e = 0.5 ----
+    n_diff = 0
+    for t in range(4):
+        for ref in range(0, 61 if t == 0 else 31):
+            for alt in range(0, 61 if t == 1 else 31):
+                differs = False
+                for ms in (0, 3):
+                    gt, _ = ref_geno.likelihood([ref, alt], _LIK_TYPES[t], ms, 0.5)
+                    differs |= _fused_row(t, ref, alt, ms, 0.5)[0] != _GTC[gt]
+                n_diff += differs
+                if differs or rng.random() < 0.25:
+                    cases += [(t, ref, alt, ms, 0.5, "half") for ms in (0, 3)]
+    n_half = sum(c[5] == "half" for c in cases)
+
+    # ---- equal: c1 == c2 ----
+    for ee in (5e-5, 1e-2, 0.3):
+        for c in range(61):
+            for t in range(4):
+                cases.append((t, 2 * c if t == 0 else c, 2 * c if t == 1 else c, 3, ee, "equal"))
+
+    # ---- halfdeep: one-sided rows at e = 0.5, the deep count log-uniform in [61, 2^32) (a generator of its own: the rows above stay as they were) ----
+    rng2 = np.random.default_rng(36)
+    for _ in range(240):
+        t, ref_side = int(rng2.integers(4)), bool(rng2.integers(2))
+        a = int(np.exp(rng2.uniform(np.log(61), np.log(2**32 - 1))))
+        other = int(rng2.integers(2)) if (t == 0 and not ref_side) or (t == 1 and ref_side) else 0
+        cases.append((t, a, other, 3, 0.5, "halfdeep") if ref_side else (t, other, a, 3, 0.5, "halfdeep"))
+
+    rows, n_fused_pl, n_fused_gt, n_near = [], 0, 0, 0
+    for t, a, b, ms, ee, src in cases:
+        gt, pl = ref_geno.likelihood([a, b], _LIK_TYPES[t], ms, ee)
+        row = (t, a, b, ms, _GTC[gt], int(pl[0]), int(pl[1]), int(pl[2]))
+        m_gt, m_pl = M.likelihood([a, b], _LIK_TYPES[t], ms, ee)
+        assert (_GTC[m_gt], [int(x) for x in m_pl]) == (row[4], list(row[5:8])), (row, m_gt, m_pl)      # the model reproduces the reference
+        r1, r2 = _norm_r(t, a, b)
+        if src in ("fused", "onesided"):
+            assert r1 == 0 or r2 == 0, row                                                               # comb = 0: the kernel never flags the row
+            f_gt, f_pl = _fused_row(t, a, b, ms, ee)
+            n_fused_pl += f_pl != list(row[5:8])
+            assert f_gt == row[4], row
+        else:
+            n_fused_gt += _fused_row(t, a, b, ms, ee)[0] != row[4]
+            n_near += bool(r1 and r2 and min(M.pl_fractions(t, a, b, ee)) < 1e-6)
+        rows.append(row + (src, ee))
+    assert len(rows) <= 16_500
+    n_he = sum(r[8] in ("half", "equal") for r in rows)
+    print(f"lik_products: {len(fused)} fused rows, {n_fused_pl} fused + onesided rows whose PLs the fused sequence changes; half: {n_half} rows of "
+          f"{n_diff} pairs on which the fused GT differs; {n_fused_gt} half, equal and halfdeep rows with another fused GT; "
+          f"{n_near} of {n_he} half + equal rows within 1e-6 of an integer ({n_near / n_he:.4%})")
+    assert n_near / n_he < 0.01
+    np.savez_compressed(f"{HERE}/lik/lik_products.npz", cases=np.array([r[:8] for r in rows], dtype=np.int64),
+                        err=np.array([r[9] for r in rows], dtype=np.float64), src=np.array([r[8] for r in rows]),
+                        note=np.array("answers of the reference's likelihood(), called in process (tests/golden/make_golden.py: make_lik_products)"))
+    print(f"lik_products.npz: {len(rows)} rows, {os.path.getsize(f'{HERE}/lik/lik_products.npz')} bytes")
 
 
 # ----------------------------------------------------------------------------------------------
@@ -1753,7 +1908,7 @@ def make_full(which=("c2", "c3", "c4slice")):
 
 
 if __name__ == "__main__":
-    which = sys.argv[1:] or ["testdir", "quirks", "unicode", "lik", "lik_boundary", "lik_deep", "lik_deep_hp", "vcf", "synth", "realshape", "utf8order", "nosv", "vcffuzz", "graphfuzz", "dover", "longpath", "contigs", "longtail",
+    which = sys.argv[1:] or ["testdir", "quirks", "unicode", "lik", "lik_boundary", "lik_deep", "lik_deep_hp", "lik_products", "vcf", "synth", "realshape", "utf8order", "nosv", "vcffuzz", "graphfuzz", "dover", "longpath", "contigs", "longtail",
                              "blanks", "fuzz7", "graphlayout"]          # (hg002shape: minutes and 7 GB of scratch — by name)
     for w in which:
         if w.startswith("full"):                   # full | full:c2,c3,c4slice

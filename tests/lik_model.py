@@ -104,6 +104,22 @@ def likelihood(all_count, svtype, min_support, e):
         return geno, prob
 
 
+def fused_two_sum(x1, y1, x2, y2):
+    """What k_genotype's device code computed for two_sum(x1 * y1, x2 * y2) while geno_row was compiled with fused multiply-adds (before
+    it carried `fp contract(off)`): only the SECOND product is rounded to a double, the first one enters every operation exactly.
+    The five instructions in Fraction, float() for each rounding, then the add of the two tail halves -> (hi, lo).  Used by the
+    generator of lik_products.npz (tests/golden/make_golden.py) to find rows on which that differs from the plain C++; no test calls it."""
+    from fractions import Fraction
+    p1 = Fraction(x1) * Fraction(y1)
+    p2 = Fraction(x2) * Fraction(y2)
+    b = float(p2)                                        # v_mul_f64   b  = fl(x2 * y2)
+    s = float(p1 + Fraction(b))                          # v_fmac_f64  s  = fl(x1 * y1 + b)
+    bb = float(Fraction(s) - p1)                         # v_fma_f64   bb = fl(s - x1 * y1)
+    t2 = float(p2 - Fraction(bb))                        # v_fma_f64   fl(x2 * y2 - bb)
+    t1 = float(p1 - Fraction(s - bb))                    # v_fma_f64   fl(x1 * y1 - fl(s - bb))
+    return s, t1 + t2
+
+
 def pl_fractions(svtype_code, ref, alt, e):
     """distance of each -10 * (lik + comb) from the nearest integer, at 80 digits (for the boundary searches)"""
     types = ("DEL", "INS", "INV", "BND")

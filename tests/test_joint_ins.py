@@ -64,6 +64,20 @@ def test_site_arithmetic_against_the_model():
     print("flagged sites:", n_flagged, "of", n)
 
 
+@pytest.mark.parametrize("kind", ["one_sided", "half"])
+def test_site_arithmetic_where_the_products_roundings_decide(kind):
+    """geno_site on the sites formed from lik_products.npz (tests/products_items.py): one deep count beside zeros at K = 2 and 6 — the chain
+    term T is 0, so none may be flagged and every PL is the routine's own — and K = 2 sites at err = 0.5 over the half pairs"""
+    from tests import products_items as PI
+    from tests.site_sim import sim
+    for ms, e, sites, want in PI.site_items(kind):
+        assert len(sites) > 500
+        gt, pl, near, st, s_k = sim.genotype_sites(sites, ms, e, host_table())
+        assert not st.any() and s_k.tolist() == [sum(SM.counts(*s)[1]) for s in sites]
+        n_flagged = SM.check_against_model(sites, want, lambda s: (e, ms), gt, pl, near)
+        assert kind == "half" or n_flagged == 0
+
+
 def test_flagged_sites_of_a_large_set():
     """the random set flags about one site in 6 000: the harness alone runs 240 000 more, and the few dozen it flags are held to the model — one
     value within 2 x SITE_PL_GUARD of an integer, the call equal, exact_pl_site equal"""

@@ -53,7 +53,7 @@ def test_model_comb_against_math_comb():
         assert M.log10_comb(n, k) == math.log10(math.comb(n, k)), (n, k)
 
 
-@pytest.mark.parametrize("name", ["lik_kat.npz", "lik_boundary.npz", "lik_deep.npz"])
+@pytest.mark.parametrize("name", ["lik_kat.npz", "lik_boundary.npz", "lik_deep.npz", "lik_products.npz"])
 def test_model_reproduces_the_reference(golden, name):
     """the model against every known answer of the reference: GT and the three PLs, no difference"""
     cases, errs = _load(golden, name)
@@ -93,15 +93,18 @@ def host_table():
     return sim.logfact_table(LOGFACT_CAP)
 
 
-@pytest.mark.parametrize("name", ["lik_kat.npz", "lik_boundary.npz", "lik_deep.npz", "lik_deep_hp.npz"])
+@pytest.mark.parametrize("name", ["lik_kat.npz", "lik_boundary.npz", "lik_deep.npz", "lik_deep_hp.npz", "lik_products.npz"])
 def test_kernel_row_arithmetic_on_the_host(golden, host_table, name):
     """k_genotype's per-row arithmetic (svjg_geno.h: geno_row, compiled with g++) with a log10(i!) table of LOGFACT_CAP entries built
     with the HOST libm's log10 — not the device's (the -m gpu tests check that one).  Every row: GT equals the fixture; a row the
     routine does not flag has the fixture's PLs; a flagged row gets them from exact_pl; a row with n >= LOGFACT_CAP (both counts > 0)
-    is flagged for the host and never asks for a larger table; a row whose PL lies within 1e-7 of an integer is flagged."""
+    is flagged for the host and never asks for a larger table; a row whose PL lies within 1e-7 of an integer is flagged; a one-sided
+    row (lik_products.npz: fused, onesided — its binomial term is log10(1)) is never flagged, so its PLs are the routine's own."""
     from svjg import genotype
     from tests.hostsim import sim
     cases, errs = _load(golden, name)
+    z = np.load(f"{golden}/lik/{name}")
+    one_sided = np.isin(z["src"], ("fused", "onesided")) if "src" in z.files else np.zeros(len(cases), bool)
     for e in np.unique(errs):
         for ms in np.unique(cases[:, 3]):
             sel = np.flatnonzero((errs == e) & (cases[:, 3] == ms))
@@ -116,6 +119,7 @@ def test_kernel_row_arithmetic_on_the_host(golden, host_table, name):
             beyond = (r >= LOGFACT_CAP) & (k > 0)
             assert np.array_equal(st == 2, beyond)
             assert near[beyond].all()
+            assert not near[one_sided[sel]].any(), c[one_sided[sel] & (near != 0)][:5]
             ok = near == 0
             bad = np.flatnonzero(ok & (pl != c[:, 5:8]).any(axis=1))
             assert len(bad) == 0, (c[bad[:5]], pl[bad[:5]])

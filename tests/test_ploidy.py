@@ -7,6 +7,7 @@ import numpy as np
 import pytest
 
 from tests import ploidy_model as PM
+from tests import products_items as PI
 
 NO_CALL = 0xFF
 N_RANDOM = 24_000                             # 4 000 rows under each of the six (err, min_support) settings
@@ -95,6 +96,22 @@ def test_ploidy_2_equals_the_diploid_routine(golden):
             assert np.array_equal(n, n2) and np.array_equal(s, s2)
             seen += len(sel)
     assert seen == len(cases)
+
+
+@pytest.mark.parametrize("kind,P", PI.PLOIDY_CASES)
+def test_row_arithmetic_where_the_products_roundings_decide(kind, P):
+    """geno_row_ploidy on the rows of lik_products.npz (tests/products_items.py): deep one-sided rows at P = 1, 2, 3, 8 — their binomial
+    term is log10(1), so none may be flagged and every PL is the routine's own — and the rows at err = 0.5, where all P + 1 likelihoods
+    coincide mathematically and the roundings of the products (and of the reference's 28-digit sums) decide GT, at P = 1, 2, 4, 8"""
+    from tests.ploidy_sim import sim
+    seen = 0
+    for ms, e, rows, want in PI.ploidy_items(kind, P):
+        gt, pl, near, st = sim.genotype_rows(rows[:, 0], rows[:, 1:3], rows[:, 3], ms, e, host_table())
+        assert not st.any()
+        n_flagged = PM.check_against_model(rows, want, lambda r: (e, ms), gt, pl, near)
+        assert kind == "half" or n_flagged == 0
+        seen += len(rows)
+    assert seen == int((PI.one_sided() if kind == "one_sided" else PI.fixture()[2] == "half").sum())
 
 
 def test_ties_are_no_calls():
