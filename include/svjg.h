@@ -300,6 +300,32 @@ int svjg_genotype_cohort(svjg_ctx *ctx, const uint8_t *sv_type, const uint32_t *
                          uint64_t n_rows, uint32_t min_support, double err,
                          uint8_t *gt, int64_t *pl, uint32_t *raw, uint8_t *genotyped, uint8_t *boundary, uint32_t *site);
 
+/* svjg_genotype_cohort_ploidy: the cohort call at a ploidy per (row, sample) item (--cohort-ploidy): ploidy[r*n_samples + s] in 0..max_ploidy,
+ * max_ploidy in 1..SVJG_MAX_PLOIDY.  Per item what svjg_genotype_ploidy does per row, with svjg_genotype_cohort's gate plus the ploidy byte: the
+ * item is genotyped iff ok[r] & 1, slot[r] != 0xFFFFFFFF, present[slot[r]][s] and 1 <= ploidy <= max_ploidy (ok bit 1 is IGNORED; ploidy 0: never
+ * genotyped).  An item that is not genotyped has gt = 0xFF, zero PLs, raw = 0,0, boundary = 0.  Outputs, [n_rows][n_samples] row-major: gt = alt
+ * copies of the call (0xFF = no call); pl = max_ploidy + 1 int64 per item, PL_0..PL_P then zeros — the stride is the CALL's, so a human cohort
+ * (max_ploidy 2) moves 24 bytes of PLs per item like the diploid call, not 72 —; raw, genotyped as svjg_genotype_cohort; boundary as
+ * svjg_genotype_ploidy's: recompute flagged items with svjedi-graph_amd/svjg/genotype.py: exact_pl_ploidy.  site[r*3..] = NS (the items with
+ * gt != 0xFF), AN (the sum of their ploidies) and AC (the sum of their alt copies) of row r, summed in integers in the same launch (nine wave ballots,
+ * at most two 64-bit atomics per row and wave), so they are equal from run to run.  The call works in a block of its own: it neither reads nor
+ * changes the count vector, what svjg_genotype_view and svjg_genotype_boundary hand out, or the block of svjg_genotype_cohort.  The caller bounds
+ * memory by calling with row chunks (8 (max_ploidy + 1) + 12 bytes per item).  n_rows = 0 returns 0.  SVJG_E_ARG with a message in
+ * svjg_last_error, all found before any launch: no matrix, a null array, max_ploidy outside 1..SVJG_MAX_PLOIDY, a ploidy byte above max_ploidy,
+ * n_rows x n_samples beyond 2^40, a matrix of 2^28 samples or more (AN must fit 32 bits); a row naming a slot >= the matrix's n_slots is reported
+ * after the pass, as svjg_genotype reports it.  svjg_last_kernel_ms reports the kernel as genotype_ms.
+ * Measured once, with the change that added it (one MI355X, 2026-10-19, tools/cohort_ploidy_timing.py: 100 000 rows x 64 samples, counts 0..60,
+ * e = 5e-5, median of 30 calls behind 5, the legs alternated twice in one process): 0.191 / 0.191 ms for the one launch with ploidies 0 / 1 / 2 by
+ * row class and sex at max_ploidy 2, 0.451 / 0.452 ms with ploidies 1..8 at max_ploidy 8; svjg_genotype_cohort on the same matrix 0.166 / 0.165 ms;
+ * the loop 64 x (svjg_set_counts + svjg_genotype_ploidy) with the same ploidies 1.267 / 1.266 ms and 1.563 / 1.572 ms of kernels summed, 118 / 120 ms
+ * and 134 / 135 ms of wall time.  One call from Python took 35.5 / 37.0 ms (226 MB to the host) and 77.2 / 78.3 ms (533 MB).  Nothing else about
+ * this kernel has been measured. */
+int svjg_genotype_cohort_ploidy(svjg_ctx *ctx, const uint8_t *sv_type, const uint32_t *slot, const uint8_t *ok,
+                                const uint8_t *ploidy /* [n_rows][n_samples] */, uint32_t max_ploidy, uint64_t n_rows,
+                                uint32_t min_support, double err,
+                                uint8_t *gt, int64_t *pl /* [n_rows][n_samples][max_ploidy+1] */, uint32_t *raw,
+                                uint8_t *genotyped, uint8_t *boundary, uint32_t *site /* [n_rows][3] = NS, AN, AC */);
+
 /* ---- the whole pass in one call (what a fused svjedi-graph run and bench.py do per batch) -----------------------------------
  * svjg_set_rows copies the three per-row input arrays of svjg_genotype to the device once (they stay until the next
  * svjg_set_rows / svjg_destroy).  svjg_run_resident then does, for the resident text of svjg_gaf_upload and those rows:

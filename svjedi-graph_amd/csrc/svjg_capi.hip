@@ -78,9 +78,9 @@ constexpr int STAGE_THREADS = 4;
 constexpr uint64_t STAGE_PIECE = 8ull << 20;
 
 // The device block of a step-by-step genotype call and its pinned host twin (genotype_leg).  Every call has a block of its own: svjg_genotype_view
-// hands out pointers into BLOCK_ROWS' twin and svjg_genotype_boundary reads it later, and both must survive calls of the other three.
+// hands out pointers into BLOCK_ROWS' twin and svjg_genotype_boundary reads it later, and both must survive calls of the other four.
 struct LegBlock { void *d = nullptr;  uint64_t d_cap = 0;  void *h = nullptr;  uint64_t h_cap = 0; };
-enum { BLOCK_ROWS, BLOCK_PLOIDY, BLOCK_SITES, BLOCK_COHORT, LEG_BLOCKS };   // rows_layout, ploidy_layout, sites_layout, cohort_layout (svjg_geno.h)
+enum { BLOCK_ROWS, BLOCK_PLOIDY, BLOCK_SITES, BLOCK_COHORT, BLOCK_COHORT_PLOIDY, LEG_BLOCKS };   // rows_layout, ploidy_layout, sites_layout, cohort_layout, cohort_ploidy_layout (svjg_geno.h)
 
 // slots the passes of svjg_run_begin rotate through: two may be in flight, and the one the NEXT pass will use is zeroed while the newest computes
 constexpr int RUN_SLOTS = 3;
@@ -986,7 +986,7 @@ static int build_logfact(svjg_ctx *c, uint32_t upto) {
     return 0;
 }
 
-// ---- one genotype leg, for the four step-by-step calls (genotype_leg) and the fused pass alike ----
+// ---- one genotype leg, for the five step-by-step calls (genotype_leg) and the fused pass alike ----
 // k_genotype's arguments but where the results go (the callers' layouts, svjg_geno.h); p: device block with the rows' inputs at I
 static GenoArgs geno_args(const svjg_ctx *c, const unsigned long long *counts, const uint8_t *p, const RowsIn &I, uint64_t n_rows, uint32_t min_support, double err) {
     GenoArgs a{};
@@ -1018,7 +1018,7 @@ static int launch_genotype(svjg_ctx *c, GenoArgs &a) {
 // d_back come back to h_back (what the caller reads, the pair included) and the check repeats.  relaunch_first: the launch itself is still
 // owed (svjg_run_end behind a repeated pass).  max_n is the maximum over ALL rows, so one growth is enough; the second only guards this reasoning.
 // launch(): the kernel over all its items again with the table at hand; it zeroes again whatever the kernel adds to (launch_genotype,
-// launch_ploidy, launch_sites, launch_cohort).
+// launch_ploidy, launch_sites, launch_cohort, launch_cohort_ploidy).
 template <class Launch>
 static int settle_launch(svjg_ctx *c, const unsigned int *h_maxn, void *h_back, const void *d_back, uint64_t bytes, bool relaunch_first, Launch launch) {
     for (int growths = 0;; relaunch_first = false) {
@@ -1302,6 +1302,53 @@ extern "C" int svjg_genotype_cohort(svjg_ctx *c, const uint8_t *sv_type, const u
     const uint8_t *hb = (const uint8_t *)c->leg[BLOCK_COHORT].h;
     memcpy(pl, hb + L.pl, n * 3 * sizeof *pl); memcpy(raw, hb + L.raw, n * 2 * sizeof *raw);
     memcpy(gt, hb + L.gt, n); memcpy(genotyped, hb + L.flags, n); memcpy(boundary, hb + L.boundary, n); memcpy(site, hb + L.site, n_rows * 8);
+    return 0;
+}
+
+// svjg_genotype_cohort_ploidy goes through genotype_leg in BLOCK_COHORT_PLOIDY: the call's logarithms and the items' ploidy bytes go in with the
+// three input arrays.  launch_cohort_ploidy: as launch_cohort, the row's TWO site words and the max_n pair zeroed in front of every launch.
+// Blocks: a block is four waves, one per SIMD, and a SIMD holds min(8, 512 / VGPRs) waves of a kernel: this one takes 96 VGPRs (the compiler's
+// resource remark), so five, not launch_cohort's eight; the rest in strides of the grid.
+constexpr uint64_t COHORT_PLOIDY_WAVES = 5;
+static int launch_cohort_ploidy(svjg_ctx *c, GenoCohortPloidyArgs &p) {
+    p.c.g.logfact = c->d_logfact; p.c.g.logfact_n = c->logfact_n;
+    HIPCHK(c, hipMemsetAsync(p.c.site, 0, p.c.g.n_rows * 16 + 8, c->stream));
+    const uint64_t n_items = p.c.g.n_rows * p.c.n_samples, blocks = (n_items + TPB - 1) / TPB, cap = (uint64_t)c->n_cu * COHORT_PLOIDY_WAVES;
+    hipLaunchKernelGGL(k_genotype_cohort_ploidy, dim3((uint32_t)(blocks < cap ? blocks : cap)), dim3(TPB), 0, c->stream, p);
+    HIPCHK(c, hipGetLastError());
+    return 0;
+}
+
+extern "C" int svjg_genotype_cohort_ploidy(svjg_ctx *c, const uint8_t *sv_type, const uint32_t *slot, const uint8_t *ok, const uint8_t *ploidy,
+                                           uint32_t max_ploidy, uint64_t n_rows, uint32_t min_support, double err, uint8_t *gt, int64_t *pl,
+                                           uint32_t *raw, uint8_t *genotyped, uint8_t *boundary, uint32_t *site) {
+    if (!c) return SVJG_E_ARG;
+    if (!c->d_cm) { c->err = "no cohort matrix"; return SVJG_E_ARG; }
+    if (n_rows == 0) return 0;
+    if (!sv_type || !slot || !ok || !ploidy || !gt || !pl || !raw || !genotyped || !boundary || !site) { c->err = "a null array"; return SVJG_E_ARG; }
+    if (max_ploidy < 1 || max_ploidy > MAX_PLOIDY) { c->err = "max_ploidy is not in 1..SVJG_MAX_PLOIDY"; return SVJG_E_ARG; }
+    const uint64_t S = c->cohort_samples;
+    if (S >= (1ull << 28)) { c->err = "too many samples: AN would not fit 32 bits"; return SVJG_E_ARG; }
+    if (n_rows > (1ull << 40) / S) { c->err = "too many items for one call: genotype the rows in chunks"; return SVJG_E_ARG; }
+    const uint64_t n = n_rows * S;
+    for (uint64_t i = 0; i < n; ++i)
+        if (ploidy[i] > max_ploidy) { c->err = "ploidy above max_ploidy"; return SVJG_E_ARG; }
+    HIPCHK(c, hipSetDevice(c->device));
+    const CohortPloidyLayout L = cohort_ploidy_layout(n_rows, S, max_ploidy);
+    const int rc = genotype_leg(c, c->leg[BLOCK_COHORT_PLOIDY], L,
+        [&](uint8_t *hb) { ploidy_log_table(err, (double *)(hb + L.logtab)); stage_rows(hb, L.in, sv_type, slot, ok, n_rows); memcpy(hb + L.ploidy, ploidy, n); },   // (host libm, as geno_args' three)
+        [&](uint8_t *base) {
+            GenoCohortPloidyArgs p{{block_geno_args(c, c->d_cm, base, L, n_rows, min_support, err), c->d_cpresent, c->cohort_samples, (unsigned long long *)(base + L.site)},
+                                   base + L.ploidy, (const double *)(base + L.logtab), max_ploidy};
+            p.c.g.n_slots = c->cohort_slots;                      // (the matrix's slots, not the count vector's)
+            return launch_cohort_ploidy(c, p);
+        });
+    if (rc) return rc;
+    const uint8_t *hb = (const uint8_t *)c->leg[BLOCK_COHORT_PLOIDY].h;
+    memcpy(pl, hb + L.pl, n * (max_ploidy + 1) * sizeof *pl); memcpy(raw, hb + L.raw, n * 2 * sizeof *raw);
+    memcpy(gt, hb + L.gt, n); memcpy(genotyped, hb + L.flags, n); memcpy(boundary, hb + L.boundary, n);
+    const uint64_t *w = (const uint64_t *)(hb + L.site);          // NS | AC << 32, AN per row -> NS, AN, AC
+    for (uint64_t r = 0; r < n_rows; ++r) { site[r * 3] = (uint32_t)w[r * 2]; site[r * 3 + 1] = (uint32_t)w[r * 2 + 1]; site[r * 3 + 2] = (uint32_t)(w[r * 2] >> 32); }
     return 0;
 }
 

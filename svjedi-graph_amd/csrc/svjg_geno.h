@@ -382,6 +382,26 @@ SVJG_HD CohortSeg cohort_segment(uint64_t i, uint64_t s, uint64_t S, uint32_t la
     return CohortSeg{upto & ~((1ull << lo) - 1), lane == lo};
 }
 
+// ---- many samples at per-sample ploidy (k_genotype_cohort_ploidy) ----
+// With the ploidy differing from item to item a row's site tags are three sums over its called items: NS = their number, AN = the sum of their
+// ploidies, AC = the sum of their alt copies.  Both summands are at most MAX_PLOIDY = 8, four bits: the wave takes one ballot for "called" and
+// one per bit plane of gt and of the ploidy, and a sum over a segment is sum_b 2^b * popcount(plane_b & called & mask).  The planes are taken
+// under `called` here, so a lane that is not called may vote anything (gt = 0xFF, whatever ploidy its item has).
+struct CohortBallots { uint64_t called, gt[4], ploidy[4]; };
+struct CohortSums { uint32_t ns, an, ac; };
+SVJG_HD CohortSums cohort_ploidy_sums(const CohortBallots &b, uint64_t mask) {
+    const uint64_t m = b.called & mask;
+    CohortSums o{(uint32_t)__builtin_popcountll(m), 0, 0};
+    SVJG_UNROLL
+    for (uint32_t k = 0; k < 4; ++k) {
+        o.ac += (uint32_t)__builtin_popcountll(b.gt[k] & m) << k;
+        o.an += (uint32_t)__builtin_popcountll(b.ploidy[k] & m) << k;
+    }
+    return o;
+}
+// the row's two site words: NS | AC << 32 (k_genotype_cohort's word) and AN.  (AC, AN <= 8 S: they fit 32 bits for S < 2^28)
+SVJG_HD uint64_t cohort_site_word(const CohortSums &s) { return (uint64_t)s.ns | ((uint64_t)s.ac << 32); }
+
 // ---- host side of a k_genotype launch: the table's size and where a call's rows lie, in plain integers (pinned without a GPU: tests/test_rows_layout.py) ----
 
 // entries of the log10(i!) table: the first one built; the one that holds max_n (the largest n the kernel met beyond the table, < LOGFACT_CAP) with room to spare
@@ -397,7 +417,7 @@ constexpr uint32_t logfact_reserve_to(uint32_t have, uint32_t entries) { return 
 struct RowsIn { uint64_t slot, type, ok, bytes; };
 inline RowsIn rows_in(uint64_t n, uint64_t at = 0) { return RowsIn{at, at + n * 4, at + n * 5, n * 6}; }
 
-// The four step-by-step calls (svjg_genotype / _view, _ploidy, _sites, _cohort) each own one device block and its pinned host twin, all of ONE
+// The five step-by-step calls (svjg_genotype / _view, _ploidy, _sites, _cohort, _cohort_ploidy) each own one device block and its pinned host twin, all of ONE
 // shape: the outputs (they end at out_end), the max_n pair 8-aligned, ONE contiguous input region right behind the pair, 64 spare bytes -> ONE copy
 // in (in_bytes from in_at), ONE copy out (maxn + 8 bytes from 0).  A layout below IS a LegSpan and adds only what is its own: its outputs and where its inputs lie.
 struct LegSpan { uint64_t maxn, in_at, in_bytes, total; };
@@ -445,6 +465,20 @@ inline CohortLayout cohort_layout(uint64_t n_rows, uint64_t S) {
     L.pl = o; o += n * 24; L.raw = o; o += n * 8; L.gt = o; o += n; L.flags = o; o += n; L.boundary = o; o += n;
     o = (o + 7) & ~7ull; L.site = o; o += n_rows * 8;
     leg_span(L, o, n_rows * 6); L.in = rows_in(n_rows, L.in_at);
+    return L;
+}
+
+// svjg_genotype_cohort_ploidy: [ pl 8 (max_ploidy + 1) | raw 8 | gt 1 | flags 1 | boundary 1 ] x (n_rows * S items, row-major) — the PL stride is the
+// CALL's, not MAX_PLOIDY + 1: a human cohort moves 24 bytes of PLs per item like the diploid call —, then TWO site words per row (NS | AC << 32, AN),
+// 8-aligned, as the last output right in front of the max_n pair (as cohort_layout: one memset zeroes both); in: the call's logarithms
+// (ploidy_log_table), rows_in(n_rows) and the n_rows * S ploidy bytes
+struct CohortPloidyLayout : LegSpan { uint64_t pl, raw, gt, flags, boundary, site, logtab;  RowsIn in;  uint64_t ploidy; };
+inline CohortPloidyLayout cohort_ploidy_layout(uint64_t n_rows, uint64_t S, uint32_t max_ploidy) {
+    CohortPloidyLayout L; uint64_t o = 0; const uint64_t n = n_rows * S;
+    L.pl = o; o += n * 8 * (max_ploidy + 1); L.raw = o; o += n * 8; L.gt = o; o += n; L.flags = o; o += n; L.boundary = o; o += n;
+    o = (o + 7) & ~7ull; L.site = o; o += n_rows * 16;
+    leg_span(L, o, 2 * PLOIDY_TAB * 8 + n_rows * 6 + n);
+    L.logtab = L.in_at; L.in = rows_in(n_rows, L.logtab + 2 * PLOIDY_TAB * 8); L.ploidy = L.in.slot + L.in.bytes;
     return L;
 }
 

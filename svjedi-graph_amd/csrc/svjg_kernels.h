@@ -13,6 +13,7 @@
 //   k_genotype       one VCF row per lane, fp64 / double-double likelihoods (predict-genotype.py:281-325)
 //   k_genotype_sites one site of insertions that share a position per lane, the same arithmetic over (K + 1)(K + 2) / 2 genotypes
 //   k_genotype_cohort one (row, sample) item per lane over a slot-major count matrix, k_genotype's arithmetic; NS / AC per row by wave ballots
+//   k_genotype_cohort_ploidy  the same division of work at a ploidy per item, k_genotype_ploidy's arithmetic; NS / AN / AC per row by wave ballots
 //   k_cohort_store / k_cohort_load  one sample's column of that matrix from / to a dense count vector
 #pragma once
 #include <hip/hip_runtime.h>
@@ -2111,6 +2112,76 @@ __global__ __launch_bounds__(TPB) void k_genotype_cohort(GenoCohortArgs p) {
         const unsigned long long ns = (unsigned long long)__popcll(called & seg.mask);
         const unsigned long long ac = (unsigned long long)__popcll(het & seg.mask) + 2ull * (unsigned long long)__popcll(hom & seg.mask);
         if (ns) atomicAdd(p.site + r, ns | (ac << 32));
+    }
+  }
+}
+
+// ---- cohort at per-sample ploidy (svjg_genotype_cohort_ploidy) ----
+// c: as for k_genotype_cohort, but c.g.pl holds max_ploidy + 1 integers per item (entries beyond an item's ploidy: 0), c.g.pl32 and the three
+// logarithms are unused and c.site holds TWO words per row, NS | AC << 32 and AN.  ploidy[i]: one byte per item, row-major like the outputs.
+struct GenoCohortPloidyArgs {
+    GenoCohortArgs c;
+    const uint8_t *ploidy;
+    const double *logtab;              // ploidy_log_table of the call's err: 2 x PLOIDY_TAB doubles
+    uint32_t max_ploidy;               // 1..MAX_PLOIDY: the PL stride is max_ploidy + 1, and an item of a higher ploidy is not genotyped
+};
+
+// k_genotype_cohort's division of the work (item i = r * S + s per lane, a wave of 64 consecutive items at a time in strides of the grid) and its
+// gate, plus the ploidy byte: 1 <= ploidy[i] <= max_ploidy.  The arithmetic is geno_row_ploidy's with the call's logarithms staged in LDS, as
+// k_genotype_ploidy does.  NS, AN and AC of a row come from the same pass in integers: one ballot for "called" and one per bit plane of gt and of the
+// ploidy (both fit four bits), summed under the segment's mask (svjg_geno.h: cohort_ploidy_sums); the segment's first lane adds them to the row's
+// two site words.  Every ballot is executed by all 64 lanes on every trip: the loop's bound is the WAVE's first item, and lanes beyond the last item
+// vote "not called".  (blocks of a multiple of 64 threads)
+__global__ __launch_bounds__(TPB) void k_genotype_cohort_ploidy(GenoCohortPloidyArgs p) {
+  __shared__ double tab[2 * PLOIDY_TAB];
+  for (uint32_t i = threadIdx.x; i < 2 * PLOIDY_TAB; i += blockDim.x) tab[i] = p.logtab[i];
+  __syncthreads();
+  const GenoArgs &a = p.c.g;
+  const uint64_t S = p.c.n_samples, n_items = a.n_rows * S;
+  const uint32_t lane = threadIdx.x & 63u, NPL = p.max_ploidy + 1;
+  for (uint64_t w0 = (uint64_t)blockIdx.x * blockDim.x + (threadIdx.x - lane); w0 < n_items; w0 += (uint64_t)gridDim.x * blockDim.x) {
+    const uint64_t i = w0 + lane;
+    uint64_t r = 0, s = 0;
+    uint32_t gt = 0xFF, P = 0;
+    if (i < n_items) {
+        r = i / S; s = i - r * S;
+        uint32_t ref = 0, alt = 0;
+        bool go = false;
+        const uint32_t ok = a.ok[r], sl = a.slot[r];
+        P = p.ploidy[i];
+        if (sl != NONE32 && sl >= a.n_slots) atomicOr(a.max_n + 1, 1u);       // a caller error, reported after the pass
+        else if ((ok & 1u) && sl != NONE32 && P >= 1 && P <= p.max_ploidy) {
+            const uint64_t at = (uint64_t)sl * S + s;
+            if (p.c.present[at]) { const unsigned long long c = a.counts[at]; ref = (uint32_t)c; alt = (uint32_t)(c >> 32); go = true; }
+        }
+        a.raw[i * 2] = ref; a.raw[i * 2 + 1] = alt;
+        a.genotyped[i] = go;
+        int64_t *pl = a.pl + i * NPL;
+        uint8_t near = 0;
+        if (go) {
+            GenoRowPloidy o;
+            const uint32_t st = geno_row_ploidy(a.sv_type[r], ref, alt, P, a.min_support, tab, tab + PLOIDY_TAB, a.logfact, a.logfact_n, o);
+            if (st == GENO_ROW_GROW) atomicMax(a.max_n, (uint32_t)o.n);        // the table is too short: the host grows it and runs the items again
+            gt = o.gt; near = o.near;
+#pragma unroll
+            for (uint32_t g = 0; g <= MAX_PLOIDY; ++g)                         // (o.pl[] only ever indexed by constants: registers, no scratch)
+                if (g < NPL) pl[g] = o.pl[g];
+        } else {
+#pragma unroll
+            for (uint32_t g = 0; g <= MAX_PLOIDY; ++g)
+                if (g < NPL) pl[g] = 0;
+        }
+        a.gt[i] = (uint8_t)gt; a.boundary[i] = near;
+    }
+    const bool called = gt != 0xFF;
+    CohortBallots b;
+    b.called = __ballot(called);
+#pragma unroll
+    for (uint32_t k = 0; k < 4; ++k) { b.gt[k] = __ballot((gt >> k) & 1u); b.ploidy[k] = __ballot((P >> k) & 1u); }
+    const CohortSeg seg = cohort_segment(i, s, S, lane, n_items);
+    if (seg.leader) {
+        const CohortSums t = cohort_ploidy_sums(b, seg.mask);
+        if (t.ns) { atomicAdd(p.c.site + r * 2, (unsigned long long)cohort_site_word(t)); atomicAdd(p.c.site + r * 2 + 1, (unsigned long long)t.an); }
     }
   }
 }

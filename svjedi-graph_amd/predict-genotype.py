@@ -3,6 +3,7 @@
 
     predict-genotype.py -d P_informative_aln.json -v VCF --minsupport N -o P_genotype.vcf   (svjedi-graph.py:124)
     predict-genotype.py --cohort LIST -v VCF --minsupport N -o COHORT_genotype.vcf          (extension: one column per sample)
+    predict-genotype.py --cohort LIST --cohort-ploidy FILE -v VCF ...                       (extension: a ploidy per sample and contig or region)
 """
 import argparse
 import os
@@ -28,19 +29,25 @@ def main():
                     help="genotype insertions that share a CHROM and POS together, 2..6 per site, diploid only (extension)")
     ap.add_argument("--cohort", metavar="<samplelist>",
                     help="many samples, one multi-sample VCF with NS / AN / AC / AF in INFO: lines `NAME<TAB>PATH_TO_informative_aln.json` "
-                         "(extension; takes the place of -d; diploid, row by row)")
+                         "(extension; takes the place of -d; diploid, row by row, unless --cohort-ploidy is given)")
+    ap.add_argument("--cohort-ploidy", metavar="<cohortploidyfile>",
+                    help="with --cohort: per-sample ploidy, 0..8, TAB-separated lines `SAMPLE<TAB>CHROM<TAB>PLOIDY` or "
+                         "`SAMPLE<TAB>CHROM<TAB>FROM<TAB>TO<TAB>PLOIDY`, SAMPLE a name of the list or `*`; the first matching line wins, 2 otherwise (extension)")
     args = ap.parse_args()
     if args.cohort is not None and args.aln is not None:
         ap.error("exactly one of -d and --cohort")
     if args.cohort is not None and (args.ploidy is not None or args.ploidy_file is not None or args.joint_ins):
-        ap.error("--cohort is diploid, row by row: it cannot be combined with --ploidy, --ploidy-file or --joint-ins")
+        ap.error("--cohort is diploid, row by row: it cannot be combined with --ploidy, --ploidy-file or --joint-ins "
+                 "(per-sample ploidy in a cohort: --cohort-ploidy)")
+    if args.cohort_ploidy is not None and args.cohort is None:
+        ap.error("--cohort-ploidy needs --cohort")
     if args.joint_ins and (args.ploidy is not None or args.ploidy_file is not None):
         ap.error("--joint-ins is diploid only: it cannot be combined with --ploidy or --ploidy-file")
     out = "genotype_results.txt" if args.output is None else args.output[0]
     err = args.err[0] if args.err is not None else 0.00005
     from svjg import genotype
     if args.cohort is not None:
-        genotype.run_cohort(args.cohort, args.vcf, out, args.minsupport, err)
+        genotype.run_cohort(args.cohort, args.vcf, out, args.minsupport, err, ploidy_file=args.cohort_ploidy)
         return
     genotype.run(args.aln[0], args.vcf, out, args.minsupport, err, ploidy=args.ploidy, ploidy_file=args.ploidy_file, joint_ins=args.joint_ins)
 

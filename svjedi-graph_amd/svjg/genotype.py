@@ -229,6 +229,26 @@ def _plain_int(text):
     return int(text)
 
 
+def _ploidy_region(f, path, no, line, forms="`CHROM PLOIDY` or `CHROM FROM TO PLOIDY`"):
+    """the fields `CHROM PLOIDY` or `CHROM FROM TO PLOIDY` of line `no` of a ploidy file -> (chrom, from, to, ploidy); the one place that reads
+    them, for load_ploidy_file and load_cohort_ploidy_file (forms: how the error message spells the file's lines)"""
+    try:
+        if len(f) == 2:
+            lo = hi = None
+        elif len(f) == 4:
+            lo, hi = _plain_int(f[1]), _plain_int(f[2])
+            if lo < 1 or hi < lo:
+                raise ValueError
+        else:
+            raise ValueError
+        p = _plain_int(f[-1])
+    except ValueError:
+        raise ValueError("%s:%d: expected %s: %r" % (path, no, forms, line.rstrip("\n"))) from None
+    if p > MAX_PLOIDY:
+        raise ValueError("%s:%d: ploidy %d is not in 0..%d" % (path, no, p, MAX_PLOIDY))
+    return f[0], lo, hi, p
+
+
 def load_ploidy_file(path):
     """-> [(chrom, from, to, ploidy)] in file order; from = to = None for a whole-chromosome line.  Lines: `CHROM PLOIDY` or
     `CHROM FROM TO PLOIDY`, separated by tabs or blanks, coordinates 1-based and inclusive; `#` lines and empty lines are skipped.
@@ -239,21 +259,7 @@ def load_ploidy_file(path):
             f = line.split()
             if not f or f[0].startswith("#"):
                 continue
-            try:
-                if len(f) == 2:
-                    lo = hi = None
-                elif len(f) == 4:
-                    lo, hi = _plain_int(f[1]), _plain_int(f[2])
-                    if lo < 1 or hi < lo:
-                        raise ValueError
-                else:
-                    raise ValueError
-                p = _plain_int(f[-1])
-            except ValueError:
-                raise ValueError("%s:%d: expected `CHROM PLOIDY` or `CHROM FROM TO PLOIDY`: %r" % (path, no, line.rstrip("\n"))) from None
-            if p > MAX_PLOIDY:
-                raise ValueError("%s:%d: ploidy %d is not in 0..%d" % (path, no, p, MAX_PLOIDY))
-            regions.append((f[0], lo, hi, p))
+            regions.append(_ploidy_region(f, path, no, line))
     return regions
 
 
@@ -515,13 +521,14 @@ def cohort_union(samples):
     return list(slot_of), per
 
 
-def cohort_info(info, ns, ac):
+def cohort_info(info, ns, ac, an=None):
     """the INFO column of a cohort row: the input's without any NS= / AN= / AC= / AF= field (whole fields, exact key), a lone `.` replaced,
-    then NS, AN = 2 NS, AC and, when AN > 0, AF = "%.6g" % (AC / AN)"""
+    then NS, AN (2 NS unless given: the called samples' ploidies summed, --cohort-ploidy), AC and, when AN > 0, AF = "%.6g" % (AC / AN)"""
     keep = [f for f in info.split(";") if not f.startswith(_SITE_TAGS)]
     if keep == ["."]:
         keep = []
-    an = 2 * ns
+    if an is None:
+        an = 2 * ns
     keep += ["NS=%d" % ns, "AN=%d" % an, "AC=%d" % ac]
     if an > 0:
         keep.append("AF=%s" % ("%.6g" % (ac / an)))
@@ -581,27 +588,143 @@ def genotype_cohort_rows(ctx, rows, n_samples, min_support, err):
     return tuple(np.concatenate([p[k] for p in parts]) for k in range(5))
 
 
-def run_cohort(list_path, vcf_path, out_path, min_support=3, err=0.00005, device=0):
+# ---- cohort at per-sample ploidy (--cohort LIST --cohort-ploidy FILE): svjg_genotype_cohort_ploidy, Python rows and the writer below ----
+
+COHORT_PLOIDY_FORMS = "`SAMPLE<TAB>CHROM<TAB>PLOIDY` or `SAMPLE<TAB>CHROM<TAB>FROM<TAB>TO<TAB>PLOIDY`"
+
+
+def load_cohort_ploidy_file(path, names):
+    """-> per sample of `names`, in their order: [(chrom, from, to, ploidy)] as load_ploidy_file gives them, the lines of the file whose first
+    field is the sample's name or `*` (every sample), in file order.  Lines are TAB-separated (a sample name may hold blanks):
+    `SAMPLE<TAB>CHROM<TAB>PLOIDY` or `SAMPLE<TAB>CHROM<TAB>FROM<TAB>TO<TAB>PLOIDY`, the fields behind SAMPLE under load_ploidy_file's rules
+    (_ploidy_region); `#` lines and empty lines are skipped.  ValueError naming file and line for anything else, a SAMPLE that is neither `*`
+    nor in `names` included."""
+    at = {name: s for s, name in enumerate(names)}
+    per = [[] for _ in names]
+    with open(path) as fh:
+        for no, line in enumerate(fh, 1):
+            text = line.rstrip("\n").rstrip("\r")
+            if not text.strip() or text.startswith("#"):
+                continue
+            f = text.split("\t")
+            rest = f[1:]
+            if not f[0] or any(x.split() != [x] for x in rest):    # (an empty field, or one with a blank in it: no line of a --ploidy-file says that)
+                rest = []
+            region = _ploidy_region(rest, path, no, line, COHORT_PLOIDY_FORMS)
+            if f[0] == "*":
+                for regions in per:
+                    regions.append(region)
+            elif f[0] in at:
+                per[at[f[0]]].append(region)
+            else:
+                raise ValueError("%s:%d: sample %r is not in the cohort list (`*`: every sample)" % (path, no, f[0]))
+    return per
+
+
+def cohort_ploidy_matrix(rows, per_sample_regions):
+    """ploidy[n_rows, S] uint8: column s = rows_ploidy(rows, regions=the sample's lines) — the first matching line wins, 2 where none matches.
+    Samples with the same lines share one pass over the rows."""
+    out = np.empty((len(rows.chrom), len(per_sample_regions)), dtype=np.uint8)
+    seen = {}
+    for s, regions in enumerate(per_sample_regions):
+        key = tuple(regions)
+        if key not in seen:
+            seen[key] = rows_ploidy(rows, None, regions)
+        out[:, s] = seen[key]
+    return out
+
+
+def cohort_ploidy_chunk_rows(n_samples, max_ploidy):
+    """rows per svjg_genotype_cohort_ploidy call: n_rows x S x (8 (max_ploidy + 1) + 12) bytes stays under 1 GiB"""
+    return max(1, COHORT_CALL_BYTES // ((8 * (int(max_ploidy) + 1) + 12) * max(1, int(n_samples))))
+
+
+def genotype_cohort_ploidy_rows(ctx, rows, ploidy, min_support, err):
+    """genotype_cohort_rows at ploidy[n, S] per item -> (gt, pl[n, S, max_ploidy + 1], raw, done, site[n, 3] = NS, AN, AC) over all rows;
+    max_ploidy = the matrix's maximum, at least 1; the flagged items recomputed by exact_pl_ploidy (the GT does not depend on the PL integers)"""
+    ploidy = np.ascontiguousarray(ploidy, dtype=np.uint8)
+    n, S = ploidy.shape
+    max_ploidy = max(1, int(ploidy.max())) if ploidy.size else 1
+    min_support = max(0, int(min_support))
+    bad_err = not (0.0 < float(err) < 1.0)
+    step = cohort_ploidy_chunk_rows(S, max_ploidy)
+    parts = []
+    for at in range(0, n, step):
+        pld = ploidy[at:at + step]
+        gt, pl, raw, done, boundary, site = ctx.genotype_cohort_ploidy(rows.sv_type[at:at + step], rows.slot[at:at + step], rows.ok[at:at + step],
+                                                                       pld, max_ploidy, min_support, 0.5 if bad_err else err)
+        if bad_err and done.any():
+            raise ValueError("math domain error")               # (as genotype_cohort_rows)
+        for r, s in zip(*np.nonzero((boundary != 0) & (done != 0))):
+            P = int(pld[r, s])
+            pl[r, s, :P + 1] = exact_pl_ploidy(int(rows.sv_type[at + r]), int(raw[r, s, 0]), int(raw[r, s, 1]), P, err)
+        parts.append((gt, pl, raw, done, site))
+    if not parts:
+        return (np.zeros((0, S), np.uint8), np.zeros((0, S, max_ploidy + 1), np.int64), np.zeros((0, S, 2), np.uint32), np.zeros((0, S), np.uint8),
+                np.zeros((0, 3), np.uint32))
+    return tuple(np.concatenate([p[k] for p in parts]) for k in range(5))
+
+
+def write_vcf_cohort_ploidy(out_path, rows, names, ploidy, gt, pl, raw, done, site):
+    """write_vcf_cohort with every item in write_vcf_ploidy's forms (ploidy, gt, done: [n, S]; pl: [n, S, >= P + 1]; site: [n, 3] = NS, AN,
+    AC) and `Number=G` in the PL header line -> the number of genotyped rows of every sample"""
+    S = len(names)
+    n_done = [0] * S
+    with open(out_path, "w") as out:
+        for kind, v in rows.items:
+            if kind == "h":
+                if v is FORMAT_HEADER:
+                    v = COHORT_INFO_LINES + v.replace(_PL_3, _PL_G).replace("\tFORMAT\tSAMPLE\n", "\tFORMAT\t" + "\t".join(names) + "\n")
+                out.write(v)
+                continue
+            first7, info = rows.prefix[v].rsplit("\t", 1)
+            cols = []
+            t = int(rows.sv_type[v])
+            for s in range(S):
+                P = int(ploidy[v, s])
+                if P == 0:
+                    cols.append(".:0:0,0:.")
+                elif done[v, s]:
+                    n_done[s] += 1
+                    dp, ad = _fmt_counts(t, int(raw[v, s, 0]), int(raw[v, s, 1]))
+                    cols.append("%s:%s:%s:%s" % (gt_text_ploidy(P, int(gt[v, s])), dp, ad, ",".join(str(int(x)) for x in pl[v, s, :P + 1])))
+                else:
+                    cols.append("%s:0:0,0:%s" % ("/".join("." * P), ",".join("." * (P + 1))))
+            out.write(first7 + "\t" + cohort_info(info, int(site[v, 0]), int(site[v, 2]), int(site[v, 1])) + "\tGT:DP:AD:PL\t" + "\t".join(cols) + "\n")
+    return n_done
+
+
+def run_cohort(list_path, vcf_path, out_path, min_support=3, err=0.00005, device=0, ploidy_file=None):
     """predict-genotype.py --cohort: the samples of a cohort list (load_cohort_list), one multi-sample VCF.  Sample column s is what the
-    reference writes as SAMPLE for sample s alone; INFO gains NS, AN, AC and AF.  -> the number of genotyped rows of every sample"""
+    reference writes as SAMPLE for sample s alone; INFO gains NS, AN, AC and AF.  ploidy_file (--cohort-ploidy, load_cohort_ploidy_file): a
+    ploidy per sample and contig or region; column s is then what --ploidy-file with the sample's lines writes for sample s alone, and AN is
+    the called samples' ploidies summed.  -> the number of genotyped rows of every sample"""
     from . import capi, filter as flt
     samples = load_cohort_list(list_path)                        # (raises before any output exists)
+    names = [name for name, _ in samples]
+    regions = load_cohort_ploidy_file(ploidy_file, names) if ploidy_file is not None else None   # (so does this)
     loaded = []
     for _, path in samples:
         got = flt.read_handoff(path)                             # left by our filter-alignments.py for exactly this file, else None
         loaded.append(got if got is not None else capi.count_informative_json(path))
     keys, per = cohort_union(loaded)
     rows = VcfRows(vcf_path, {k: i for i, k in enumerate(keys)})
-    names = [name for name, _ in samples]
+    ploidy = cohort_ploidy_matrix(rows, regions) if regions is not None else None
     ctx = capi.Context(device)
     try:
         ctx.cohort_alloc(len(samples), len(keys))
         for s, (slots, counts) in enumerate(per):
             ctx.cohort_set_counts(s, slots, counts)
-        gt, pl, raw, done, site = genotype_cohort_rows(ctx, rows, len(samples), min_support, err)
+        if ploidy is None:
+            gt, pl, raw, done, site = genotype_cohort_rows(ctx, rows, len(samples), min_support, err)
+        else:
+            gt, pl, raw, done, site = genotype_cohort_ploidy_rows(ctx, rows, ploidy, min_support, err)
     finally:
         ctx.close()
-    n_done = write_vcf_cohort(out_path, rows, names, gt, pl, raw, done, site)
+    if ploidy is None:
+        n_done = write_vcf_cohort(out_path, rows, names, gt, pl, raw, done, site)
+    else:
+        n_done = write_vcf_cohort_ploidy(out_path, rows, names, ploidy, gt, pl, raw, done, site)
     for name, n in zip(names, n_done):
         print("Genotyped svs (%s): %d" % (name, n))
     return n_done
