@@ -38,51 +38,19 @@ SVJG_HD int64_t trunc_dd(dd v) {                         // int(Decimal): toward
     return (int64_t)t;
 }
 
-// The reference's lik0 and lik2 are SUMS of two Decimals, rounded to the context's 28 significant digits (half to even); its lik1 is ONE
-// Decimal, the exact image of a double, which no operation ever rounds.  Where the exact sum of the two products IS the double h of lik1
-// (every row at e = 0.5, where log10(1 - e) = log10(e) = log10(1 / 2), whenever the two roundings cancel), the reference therefore compares
-// round28(h) with h itself, and the 29th digit of h decides its GT.  -> the sign of round28(h) - h, 0: h has at most 28 digits.
-// h = (c1 + c2) * log10(1 / 2) with c1 + c2 in [0.5, 2^33]: 0.15 <= |h| < 2^32, so 10^s |h| with s = 27 - floor(log10 |h|) in 18..28 is
-// m * 5^s / 2^r (m: the 53 bits of |h| = m * 2^(ex - 53), r = 53 - ex - s in 1..27; r < 1: an integer): the fraction and the parity of the
-// 28th digit are the low r + 1 bits of m * 5^s, and a 64-bit product that wraps holds them.  (Differences of less than one unit of the 28th digit that are not zero cannot occur: they are
-// multiples of an ulp of the smallest product, > 2^-86 of the largest.)
-#ifdef __clang__
-#define SVJG_NOUNROLL _Pragma("nounroll")
-#else
-#define SVJG_NOUNROLL
-#endif
-SVJG_HD int dec28_round_dir(double h) {
-    const double x = fabs(h);
-    const bool inside = x >= 0.125 && x < 4294967296.0;  // (outside: 0, the row without reads; nothing else)
-    int ex; const double f = frexp(inside ? x : 1.0, &ex);
-    int p10 = -1; double ten = 1.0;
-    SVJG_NOUNROLL                                        // (unrolled, the ten powers would sit in twenty scalar registers of every kernel that inlines this)
-    for (int k = 0; k < 10; ++k) { if (x >= ten) p10 = k; ten *= 10.0; }      // (powers of ten up to 10^9: exact doubles)
-    const int s = 27 - p10, r = 53 - ex - s;             // |h| 10^s = m 5^s / 2^r, s in 18..28
-    uint64_t N = (uint64_t)ldexp(f, 53) * 3814697265625ull;                   // m * 5^18 mod 2^64
-    for (int i = 18; i < 28; ++i) N *= i < s ? 5u : 1u;                       // m * 5^s mod 2^64 (no branch: the lanes of a wave differ in s)
-    const int rr = r < 1 ? 1 : r;
-    const uint64_t frac = N & ((1ull << rr) - 1), half = 1ull << (rr - 1);
-    const bool up = frac > half || (frac == half && ((N >> rr) & 1));         // the magnitude grows (half to even)
-    if (!inside || r < 1 || frac == 0) return 0;         // (r < 1: an integer of 28 digits)
-    return (up == (h > 0)) ? 1 : -1;
-}
-
 // The log10(i!) table (k_logfact_*) never grows beyond LOGFACT_CAP entries (256 MB).  A row whose binomial term would need more
 // (n = r1 + r2 >= LOGFACT_CAP, both r1 and r2 > 0) is not computed from the table: the kernel flags it like a row next to an
 // integer boundary, and the host recomputes it with the reference's arithmetic (svjg/genotype.py: exact_pl).
 constexpr uint32_t LOGFACT_CAP = 1u << 24;
 
-// A row is flagged for the host when one of its three -10 * (lik + comb) lies within PL_GUARD of an integer.  The budget, for
+// A row is flagged for the host when one of its -10 * (lik + comb) lies within PL_GUARD of an integer.  The budget, for
 // n < LOGFACT_CAP: every table entry is a sum of at most n values log10(i) < 7.3, each within 1 ulp (2^-50) of the true value,
 // summed in double-double: |table error| <= 2^24 * 2^-50 = 1.5e-8 per entry, and comb takes one
 // entry of n terms and two of n terms together: <= 3e-8.  The reference's log10 of a big integer goes through CPython's frexp
 // path, log10(x) + log10(2) * e: a few ulps of L = log10(comb) <= 5.1e6 (ulp 9.3e-10): <= 4e-9.  Both sides round L to a
 // double (1 ulp each).  The likelihood sums are exact here and at 28 digits in the reference BECAUSE each product c * L is rounded to a double
-// before it is added, as the reference's Decimal(c * L) is: geno_row, geno_row_ploidy and geno_site form them under `fp contract(off)`.  (Until
-// r12 geno_row did not, and hipcc fused the first product of each pair into two_sum: the sum then held the exact products, and the budget would
-// have had to gain two half-ulps of a product, times ten — 1e-5 at c = 2^27 —, on rows with comb = 0 that are never flagged.  Measured on the
-// device: tests/test_genotype_products_gpu.py)  Times ten: < 3.6e-7 < 1e-6.
+// before it is added, as the reference's Decimal(c * L) is: geno_row_pairs and geno_site form them under `fp contract(off)`
+// (measured on the device where fused products would change the answer: tests/test_genotype_products_gpu.py).  Times ten: < 3.6e-7 < 1e-6.
 // The "1 ulp" of the device's log10 is measured, not assumed (2026-10-18, one MI355X, ROCm 7.2.0; the table at the cap read back through
 // svjg_logfact_read and held against 60-digit values, tests/test_logfact_gpu.py asserts each bound on every run): all 2^24 - 2 increments
 // table[i] - table[i-1] lie within 0.504 * 2^-50 of log10(i) (worst at i = 5 638 997: the device's log10 is correctly rounded or next to
@@ -105,67 +73,38 @@ SVJG_HD uint64_t geno_n(uint32_t r1, uint32_t r2) { return (uint64_t)r1 + r2; }
 
 enum : uint32_t { GENO_ROW_OK = 0, GENO_ROW_GROW = 1, GENO_ROW_HOST = 2 };
 
-struct GenoRow {
-    int64_t pl[3];
-    uint8_t gt;
-    bool near;       // one of the three PLs lies within PL_GUARD of an integer, or the row is beyond the table's cap: the host recomputes it
-    uint64_t n;      // r1 + r2
-};
+// log10 comb(n, k) = log10 n! - log10 (n - k)! - log10 k! from the table, in double-double (n below the table's entries)
+SVJG_HD dd logfact_comb(const dd *logfact, uint32_t n, uint32_t k) { return dd_add(dd_add(logfact[n], dd_neg(logfact[n - k])), dd_neg(logfact[k])); }
 
-// One genotyped row.  -> GENO_ROW_OK, GENO_ROW_GROW (the table is too short for n < LOGFACT_CAP: the host grows it and runs the rows
-// again; the PLs are without the binomial term) or GENO_ROW_HOST (n >= LOGFACT_CAP: row flagged, PLs without the binomial term).
-SVJG_HD uint32_t geno_row(uint32_t type, uint32_t ref, uint32_t alt, uint32_t min_support, double l_ok, double l_err, double l_half,
-                          const dd *logfact, uint32_t logfact_n, GenoRow &o) {
-#ifdef __clang__
-#pragma clang fp contract(off)                           // the products are rounded to doubles before the exact sums
-#endif
-    double c1, c2; uint32_t r1, r2;
-    geno_counts(type, ref, alt, c1, c2, r1, r2);
-    // products in double, sums exact (the reference adds Decimal images of the doubles, :295-297): each product is ROUNDED before two_sum
-    // sees it.  Fused into the sum (hipcc's default contraction), the first product of each pair entered all five operations unrounded.
-    dd l0 = two_sum(c1 * l_ok, c2 * l_err);
-    dd l1 = dd{(c1 + c2) * l_half, 0.0};
-    dd l2 = two_sum(c2 * l_ok, c1 * l_err);
-    int c01 = dd_cmp(l0, l1), c02 = dd_cmp(l0, l2), c12 = dd_cmp(l1, l2);
-    if (c01 == 0 || c12 == 0) {                          // a rounded sum against the one unrounded product of the same value
-        const int d = dec28_round_dir(l1.hi);
-        if (c01 == 0) c01 = d;
-        if (c12 == 0) c12 = -d;
-    }
-    uint8_t g = 3;
-    if (c01 > 0 && c02 > 0) g = 0; else if (c01 < 0 && c12 > 0) g = 1; else if (c02 < 0 && c12 < 0) g = 2;
-    if (!(c1 + c2 >= (double)min_support)) g = 3;
-    o.gt = g;
-    const uint64_t n = geno_n(r1, r2);                  // (never a wrapped sum: no index comes from one)
-    o.n = n;
-    uint32_t st = GENO_ROW_OK;
-    dd comb{0.0, 0.0};                                   // comb(n, 0) = comb(n, n) = 1: no table needed
-    if (r1 && r2) {
-        if (n < logfact_n) comb = dd_add(dd_add(logfact[n], dd_neg(logfact[n - r1])), dd_neg(logfact[r1]));
-        else st = n < LOGFACT_CAP ? GENO_ROW_GROW : GENO_ROW_HOST;
-    }
-    comb = dd{comb.hi, 0.0};                             // the reference rounds log10(comb) to a double first (:313)
-    dd ls[3] = {l0, l1, l2};
-    bool near = false;
-    for (int i = 0; i < 3; ++i) {
-        dd s = dd_add(ls[i], comb);
-        dd p = dd_add(dd_add(dd_add(s, s), dd_add(s, s)), s);             // 5 s
-        p = dd_add(p, p);                                                 // 10 s
-        o.pl[i] = trunc_dd(dd_neg(p));
-        // The reference adds Decimal(math.log10(math.comb(n, k))) (:313): libm's log10 of a big integer rounded to a double, which
-        // need not be the correctly rounded value this kernel uses.  The two can differ in the last places; times ten, next to an
-        // integer, that could turn a PL by one.  Rows that close are flagged and recomputed on the host (svjg/genotype.py).
-        // (the fraction from hi AND lo: above |p| ~ 2^33 hi alone cannot resolve PL_GUARD)
-        { const double fr = fabs((p.hi - rint(p.hi)) + p.lo); if (fr < PL_GUARD && comb.hi != 0.0) near = true; }   // (comb = log10(1) = 0 on both sides: nothing to disagree about)
-    }
-    o.near = near || st == GENO_ROW_HOST;
-    return st;
+// The binomial term of a row with the rounded counts r1, r2, rounded to a double first like the reference (:313), and n = r1 + r2.
+// -> GENO_ROW_OK, GENO_ROW_GROW (the table is too short for n < LOGFACT_CAP: the host grows it and runs the rows again; the term is 0) or
+// GENO_ROW_HOST (n >= LOGFACT_CAP: the row is flagged for the host, the term is 0).
+SVJG_HD uint32_t geno_comb(uint32_t r1, uint32_t r2, const dd *logfact, uint32_t logfact_n, dd &comb, uint64_t &n) {
+    n = geno_n(r1, r2);                                  // (never a wrapped sum: no index comes from one)
+    comb = dd{0.0, 0.0};                                 // comb(n, 0) = comb(n, n) = 1: no table needed
+    if (!(r1 && r2)) return GENO_ROW_OK;
+    if (n >= logfact_n) return n < LOGFACT_CAP ? GENO_ROW_GROW : GENO_ROW_HOST;
+    comb = dd{logfact_comb(logfact, (uint32_t)n, r1).hi, 0.0};
+    return GENO_ROW_OK;
 }
 
-// ---- any ploidy from 1 to MAX_PLOIDY (k_genotype_ploidy) ----
+// One PL integer: int(-10 (lik + term)), and whether -10 (lik + term) lies within `guard` of an integer.  The reference adds
+// Decimal(math.log10(math.comb(n, k))) (:313): libm's log10 of a big integer rounded to a double, which need not be the correctly rounded
+// value the table holds.  The two can differ in the last places; times ten, next to an integer, that could turn a PL by one.  Values that
+// close are flagged and recomputed on the host (svjg/genotype.py).  The fraction is taken from hi AND lo: above |p| ~ 2^33 hi alone cannot
+// resolve the guard.  term = log10(1) = 0 on both sides: nothing to disagree about, never inside.
+SVJG_HD int64_t geno_pl(dd lik, dd term, double guard, bool &inside) {
+    const dd s = dd_add(lik, term);
+    dd p = dd_add(dd_add(dd_add(s, s), dd_add(s, s)), s);                     // 5 s
+    p = dd_add(p, p);                                                         // 10 s
+    inside = fabs((p.hi - rint(p.hi)) + p.lo) < guard && term.hi != 0.0;
+    return trunc_dd(dd_neg(p));
+}
+
+// ---- one row at any ploidy from 1 to MAX_PLOIDY (k_genotype_ploidy; k_genotype at P = 2) ----
 // A row of ploidy P has P + 1 genotypes, g = 0..P alt copies.  A read shows the alt allele with probability (g (1 - e) + (P - g) e) / P,
 // the ref allele with ((P - g) (1 - e) + g e) / P: lik_g = c1 * Lr[P][g] + c2 * La[P][g].  g = 0 and g = P are the reference's lik0 and
-// lik2 (log10(1 - e), log10(e)), 2 g = P its lik1, ONE product (c1 + c2) * log10(1/2): at P = 2 this is geno_row term for term.
+// lik2 (log10(1 - e), log10(e)), 2 g = P its lik1, ONE product (c1 + c2) * log10(1/2).
 constexpr uint32_t MAX_PLOIDY = 8;
 #ifdef __clang__
 #define SVJG_UNROLL _Pragma("unroll")
@@ -198,39 +137,62 @@ inline void ploidy_log_table(double err, double *tab) {
 struct GenoRowPloidy {
     int64_t pl[MAX_PLOIDY + 1];   // PL_g for g = 0..P, 0 beyond
     uint8_t gt;                   // alt copies of the call, 0xFF: no call
-    bool near;                    // as GenoRow::near, over the P + 1 values
+    bool near;                    // one of the P + 1 PLs lies within PL_GUARD of an integer, or the row is beyond the table's cap: the host recomputes it
     uint64_t n;                   // r1 + r2
 };
 
-// One genotyped row of ploidy P in 1..MAX_PLOIDY; lr / la: the two halves of ploidy_log_table.  Status and flag as geno_row.  The loop
-// over g is unrolled with a predicate so that pl[] is only ever indexed by constants (registers on the device, no scratch).
-SVJG_HD uint32_t geno_row_ploidy(uint32_t type, uint32_t ref, uint32_t alt, uint32_t P, uint32_t min_support, const double *lr, const double *la,
+// The reference's lik0 and lik2 are SUMS of two Decimals, rounded to the context's 28 significant digits (half to even); its lik1 is ONE
+// Decimal, the exact image of a double, which no operation ever rounds.  Where the exact sum of the two products IS the double h of lik1
+// (every row at e = 0.5, where log10(1 - e) = log10(e) = log10(1 / 2), whenever the two roundings cancel), the reference therefore compares
+// round28(h) with h itself, and the 29th digit of h decides its GT.  -> the sign of round28(h) - h, 0: h has at most 28 digits.
+// h = (c1 + c2) * log10(1 / 2) with c1 + c2 in [0.5, 2^33]: 0.15 <= |h| < 2^32, so 10^s |h| with s = 27 - floor(log10 |h|) in 18..28 is
+// m * 5^s / 2^r (m: the 53 bits of |h| = m * 2^(ex - 53), r = 53 - ex - s in 1..27; r < 1: an integer): the fraction and the parity of the
+// 28th digit are the low r + 1 bits of m * 5^s, and a 64-bit product that wraps holds them.  (Differences of less than one unit of the 28th digit that are not zero cannot occur: they are
+// multiples of an ulp of the smallest product, > 2^-86 of the largest.)
+#ifdef __clang__
+#define SVJG_NOUNROLL _Pragma("nounroll")
+#else
+#define SVJG_NOUNROLL
+#endif
+SVJG_HD int dec28_round_dir(double h) {
+    const double x = fabs(h);
+    const bool inside = x >= 0.125 && x < 4294967296.0;  // (outside: 0, the row without reads; nothing else)
+    int ex; const double f = frexp(inside ? x : 1.0, &ex);
+    int p10 = -1; double ten = 1.0;
+    SVJG_NOUNROLL                                        // (unrolled, the ten powers would sit in twenty scalar registers of every kernel that inlines this)
+    for (int k = 0; k < 10; ++k) { if (x >= ten) p10 = k; ten *= 10.0; }      // (powers of ten up to 10^9: exact doubles)
+    const int s = 27 - p10, r = 53 - ex - s;             // |h| 10^s = m 5^s / 2^r, s in 18..28
+    uint64_t N = (uint64_t)ldexp(f, 53) * 3814697265625ull;                   // m * 5^18 mod 2^64
+    for (int i = 18; i < 28; ++i) N *= i < s ? 5u : 1u;                       // m * 5^s mod 2^64 (no branch: the lanes of a wave differ in s)
+    const int rr = r < 1 ? 1 : r;
+    const uint64_t frac = N & ((1ull << rr) - 1), half = 1ull << (rr - 1);
+    const bool up = frac > half || (frac == half && ((N >> rr) & 1));         // the magnitude grows (half to even)
+    if (!inside || r < 1 || frac == 0) return 0;         // (r < 1: an integer of 28 digits)
+    return (up == (h > 0)) ? 1 : -1;
+}
+
+// One genotyped row of ploidy P in 1..MAX_PLOIDY; lr / la: the row's own P + 1 logarithms (geno_row_ploidy and geno_row below say which).
+// Status as geno_comb (the PLs of a row that is not GENO_ROW_OK are without the binomial term).  The loop over g is unrolled with a predicate
+// so that pl[] is only ever indexed by constants (registers on the device, no scratch).
+SVJG_HD uint32_t geno_row_pairs(uint32_t type, uint32_t ref, uint32_t alt, uint32_t P, uint32_t min_support, const double *lr, const double *la,
                                  const dd *logfact, uint32_t logfact_n, GenoRowPloidy &o) {
 #ifdef __clang__
 #pragma clang fp contract(off)                           // the products are rounded to doubles before the exact sums
 #endif
     double c1, c2; uint32_t r1, r2;
     geno_counts(type, ref, alt, c1, c2, r1, r2);
-    const uint64_t n = geno_n(r1, r2);
-    o.n = n;
-    uint32_t st = GENO_ROW_OK;
-    dd comb{0.0, 0.0};
-    if (r1 && r2) {
-        if (n < logfact_n) comb = dd_add(dd_add(logfact[n], dd_neg(logfact[n - r1])), dd_neg(logfact[r1]));
-        else st = n < LOGFACT_CAP ? GENO_ROW_GROW : GENO_ROW_HOST;
-    }
-    comb = dd{comb.hi, 0.0};                             // rounded to a double first, like the reference (:313)
-    const uint32_t base = ploidy_tab_at(P, 0);
-    // (as geno_row) the one product of an even ploidy, g = P / 2, is never rounded to 28 digits, the sums are: where a sum IS that double, the
-    // 29th digit decides.  Looked for ahead of the loop, so that the digits are worked out at one place and only for such a row.
+    dd comb;
+    const uint32_t st = geno_comb(r1, r2, logfact, logfact_n, comb, o.n);
+    // The one product of an even ploidy, g = P / 2, is never rounded to 28 digits, the sums are: where a sum IS that double, the 29th digit
+    // decides (above).  Looked for ahead of the loop, so that the digits are worked out at one place and only for such a row.
     int dir = 0;
     if ((P & 1) == 0) {
-        const double h = (c1 + c2) * lr[base + P / 2];
+        const double h = (c1 + c2) * lr[P / 2];
         bool same = false;
         SVJG_UNROLL
         for (uint32_t g = 0; g <= MAX_PLOIDY; ++g) {
             if (g > P || 2 * g == P) continue;
-            const dd l = two_sum(c1 * lr[base + g], c2 * la[base + g]);
+            const dd l = two_sum(c1 * lr[g], c2 * la[g]);
             if (l.hi == h && l.lo == 0.0) same = true;
         }
         if (same) dir = dec28_round_dir(h);
@@ -240,21 +202,45 @@ SVJG_HD uint32_t geno_row_ploidy(uint32_t type, uint32_t ref, uint32_t alt, uint
     for (uint32_t g = 0; g <= MAX_PLOIDY; ++g) {
         o.pl[g] = 0;
         if (g > P) continue;
-        const double a = c1 * lr[base + g], b = c2 * la[base + g], h = (c1 + c2) * lr[base + g];
+        // products in double, sums exact (the reference adds Decimal images of the doubles, :295-297): each product is ROUNDED before two_sum sees it
+        const double a = c1 * lr[g], b = c2 * la[g], h = (c1 + c2) * lr[g];
         const bool single = g != 0 && 2 * g == P;
         const dd l = single ? dd{h, 0.0} : two_sum(a, b);
         int c = g ? dd_cmp(l, best) : 1;
         if (c == 0 && single != best_single) c = single ? -dir : dir;      // sign of (the rounded sum - the product) seen from l
         if (c > 0) { best = l; g_best = (uint8_t)g; best_single = single; tie = false; } else if (c == 0) tie = true;
-        dd s = dd_add(l, comb);
-        dd p = dd_add(dd_add(dd_add(s, s), dd_add(s, s)), s);             // 5 s
-        p = dd_add(p, p);                                                 // 10 s
-        o.pl[g] = trunc_dd(dd_neg(p));
-        { const double fr = fabs((p.hi - rint(p.hi)) + p.lo); if (fr < PL_GUARD && comb.hi != 0.0) near = true; }   // (as geno_row)
+        bool inside;
+        o.pl[g] = geno_pl(l, comb, PL_GUARD, inside);
+        near |= inside;
     }
     if (tie || !(c1 + c2 >= (double)min_support)) g_best = 0xFF;
     o.gt = g_best;
     o.near = near || st == GENO_ROW_HOST;
+    return st;
+}
+
+// The row of ploidy P on a call's table (k_genotype_ploidy, k_genotype_cohort_ploidy); lr / la: the two halves of ploidy_log_table, the row's
+// own entries start at ploidy_tab_at(P, 0) of either.
+SVJG_HD uint32_t geno_row_ploidy(uint32_t type, uint32_t ref, uint32_t alt, uint32_t P, uint32_t min_support, const double *lr, const double *la,
+                                 const dd *logfact, uint32_t logfact_n, GenoRowPloidy &o) {
+    return geno_row_pairs(type, ref, alt, P, min_support, lr + ploidy_tab_at(P, 0), la + ploidy_tab_at(P, 0), logfact, logfact_n, o);
+}
+
+// The diploid row (k_genotype, k_genotype_cohort): geno_row_pairs at the literal ploidy 2, the reference's three likelihoods as the row's
+// three pairs, no table.  gt: 0 / 1 / 2 alt copies, 3: no call.
+struct GenoRow {
+    int64_t pl[3];
+    uint8_t gt;
+    bool near;       // as GenoRowPloidy::near
+    uint64_t n;      // r1 + r2
+};
+SVJG_HD uint32_t geno_row(uint32_t type, uint32_t ref, uint32_t alt, uint32_t min_support, double l_ok, double l_err, double l_half,
+                          const dd *logfact, uint32_t logfact_n, GenoRow &o) {
+    const double lr[3] = {l_ok, l_half, l_err}, la[3] = {l_err, l_half, l_ok};
+    GenoRowPloidy w;
+    const uint32_t st = geno_row_pairs(type, ref, alt, 2, min_support, lr, la, logfact, logfact_n, w);
+    o.pl[0] = w.pl[0]; o.pl[1] = w.pl[1]; o.pl[2] = w.pl[2];
+    o.gt = w.gt == 0xFF ? 3 : w.gt; o.near = w.near; o.n = w.n;
     return st;
 }
 
@@ -298,7 +284,7 @@ struct GenoSite {
 
 // One site of K in 2..MAX_SITE_ALTS members: ref = the raw ref maximum, alt[0..K) the raw alt counts (entries beyond K are not read).  pl:
 // SITE_GENOTYPES integers, written as they are produced (the kernel hands in the site's place in global memory), 0 beyond the site's
-// (K + 1)(K + 2) / 2.  Status and flag as geno_row.  Both loops are unrolled under a predicate: c[] and r[] are only ever indexed by constants.
+// (K + 1)(K + 2) / 2.  Status and flag as geno_row_pairs.  Both loops are unrolled under a predicate: c[] and r[] are only ever indexed by constants.
 SVJG_HD uint32_t geno_site(uint32_t K, uint32_t ref, const uint32_t *alt, uint32_t min_support, double l_ok, double l_x, double l_he,
                            const dd *logfact, uint32_t logfact_n, int64_t *pl, GenoSite &o) {
 #ifdef __clang__
@@ -331,14 +317,12 @@ SVJG_HD uint32_t geno_site(uint32_t K, uint32_t ref, const uint32_t *alt, uint32
                 if (j > K) continue;
                 const uint32_t t = s + r[j];             // <= s_K < logfact_n: every index below is inside the table
                 if (r[j] && s) {
-                    const dd term = dd_add(dd_add(logfact[t], dd_neg(logfact[s])), dd_neg(logfact[r[j]]));
-                    T = dd_add(T, dd{term.hi, 0.0});     // each term rounded to a double first, like the model's Decimal(math.log10(...))
+                    T = dd_add(T, dd{logfact_comb(logfact, t, r[j]).hi, 0.0});    // each term rounded to a double first, like the model's Decimal(math.log10(...))
                 }
                 s = t;
             }
         } else st = s_K < LOGFACT_CAP ? GENO_ROW_GROW : GENO_ROW_HOST;
     }
-    const bool guard = T.hi != 0.0;                      // (T = 0 on both sides: nothing to disagree about)
     dd best{0.0, 0.0}; uint8_t best_a = SITE_NO_CALL, best_b = SITE_NO_CALL; bool tie = false, near = false;
     SVJG_UNROLL
     for (uint32_t b = 0; b <= MAX_SITE_ALTS; ++b) {
@@ -352,11 +336,9 @@ SVJG_HD uint32_t geno_site(uint32_t K, uint32_t ref, const uint32_t *alt, uint32
             const dd l = two_sum(p1, p2);
             const int cmp = at ? dd_cmp(l, best) : 1;
             if (cmp > 0) { best = l; best_a = (uint8_t)a; best_b = (uint8_t)b; tie = false; } else if (cmp == 0) tie = true;
-            dd s = dd_add(l, T);
-            dd p = dd_add(dd_add(dd_add(s, s), dd_add(s, s)), s);             // 5 s
-            p = dd_add(p, p);                                                 // 10 s
-            pl[at] = trunc_dd(dd_neg(p));
-            { const double fr = fabs((p.hi - rint(p.hi)) + p.lo); if (fr < SITE_PL_GUARD && guard) near = true; }   // (as geno_row)
+            bool inside;
+            pl[at] = geno_pl(l, T, SITE_PL_GUARD, inside);
+            near |= inside;
         }
     }
     if (tie || !(N >= (double)min_support)) best_a = best_b = SITE_NO_CALL;

@@ -1957,11 +1957,17 @@ struct GenoArgs {
     uint32_t n_slots;
 };
 
+// a row names a slot beyond the counts: a caller error, reported after the pass (both gates below)
+__device__ inline bool geno_slot_out_of_range(const GenoArgs &a, uint32_t sl) {
+    const bool out = sl != NONE32 && sl >= a.n_slots;
+    if (out) atomicOr(a.max_n + 1, 1u);
+    return out;
+}
+
 __device__ inline bool geno_gate(const GenoArgs &a, uint64_t r, uint32_t &ref, uint32_t &alt) {
     ref = alt = 0;
     const uint32_t ok = a.ok[r], sl = a.slot[r];
-    if (sl != NONE32 && sl >= a.n_slots) { atomicOr(a.max_n + 1, 1u); return false; }   // a caller error, reported after the pass
-    if (!(ok & 1u) || sl == NONE32) return false;
+    if (geno_slot_out_of_range(a, sl) || !(ok & 1u) || sl == NONE32) return false;
     unsigned long long c = a.counts[sl];
     ref = (uint32_t)c; alt = (uint32_t)(c >> 32);
     // sv_id is a key of the informative dict (:216): a key exists iff it has >= 1 informative alignment,
@@ -2006,11 +2012,15 @@ struct GenoPloidyArgs {
 };
 
 // The ploidy differs from lane to lane, so the logarithms are looked up per lane: the block stages the table in LDS (720 bytes) and each
-// lane reads its P + 1 pairs from there.
+// lane reads its P + 1 pairs from there (k_genotype_ploidy, k_genotype_cohort_ploidy).
+__device__ inline void stage_ploidy_tab(double *tab, const double *logtab) {
+  for (uint32_t i = threadIdx.x; i < 2 * PLOIDY_TAB; i += blockDim.x) tab[i] = logtab[i];
+  __syncthreads();
+}
+
 __global__ __launch_bounds__(TPB) void k_genotype_ploidy(GenoPloidyArgs p) {
   __shared__ double tab[2 * PLOIDY_TAB];
-  for (uint32_t i = threadIdx.x; i < 2 * PLOIDY_TAB; i += blockDim.x) tab[i] = p.logtab[i];
-  __syncthreads();
+  stage_ploidy_tab(tab, p.logtab);
   const GenoArgs &a = p.g;
   constexpr uint32_t NPL = MAX_PLOIDY + 1;
   for (uint64_t r = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; r < a.n_rows; r += (uint64_t)gridDim.x * blockDim.x) {
@@ -2019,20 +2029,15 @@ __global__ __launch_bounds__(TPB) void k_genotype_ploidy(GenoPloidyArgs p) {
     bool go = geno_gate(a, r, ref, alt) && P >= 1 && P <= MAX_PLOIDY;
     a.raw[r * 2] = go ? ref : 0; a.raw[r * 2 + 1] = go ? alt : 0;
     a.genotyped[r] = go;
-    a.boundary[r] = 0;
-    if (!go) {
-        a.gt[r] = 0xFF;
-#pragma unroll
-        for (uint32_t i = 0; i < NPL; ++i) a.pl[r * NPL + i] = 0;
-        continue;
+    GenoRowPloidy o{};                                             // (a row that is not genotyped: zeros, no call)
+    o.gt = 0xFF;
+    if (go) {
+        const uint32_t st = geno_row_ploidy(a.sv_type[r], ref, alt, P, a.min_support, tab, tab + PLOIDY_TAB, a.logfact, a.logfact_n, o);
+        if (st == GENO_ROW_GROW) atomicMax(a.max_n, (uint32_t)o.n);
     }
-    GenoRowPloidy o;
-    const uint32_t st = geno_row_ploidy(a.sv_type[r], ref, alt, P, a.min_support, tab, tab + PLOIDY_TAB, a.logfact, a.logfact_n, o);
-    if (st == GENO_ROW_GROW) atomicMax(a.max_n, (uint32_t)o.n);
-    a.gt[r] = o.gt;
+    a.gt[r] = o.gt; a.boundary[r] = o.near;
 #pragma unroll
     for (uint32_t i = 0; i < NPL; ++i) a.pl[r * NPL + i] = o.pl[i];
-    if (o.near) a.boundary[r] = 1;
   }
 }
 
@@ -2069,8 +2074,20 @@ struct GenoCohortArgs {
     unsigned long long *site;
 };
 
-// Item i = r * S + s per lane, items in strides of the grid.  What k_genotype does per row, gate included, but the presence test: the item is
-// genotyped iff ok[r] & 1, the row has a slot and present[slot][s] (ok bit 1 is not looked at).  The site tags come from the same pass in
+// The gate of item (r, s) of both cohort kernels: geno_gate but for the presence test.  The item is genotyped iff ok[r] & 1, the row has a slot,
+// `wanted` (the kernel's own condition, the ploidy byte: nothing is read for an item that fails it) and present[slot][s]; ok bit 1 is not looked at.
+__device__ inline bool cohort_gate(const GenoArgs &a, const uint8_t *present, uint64_t r, uint64_t s, uint64_t S, bool wanted, uint32_t &ref, uint32_t &alt) {
+    ref = alt = 0;
+    const uint32_t ok = a.ok[r], sl = a.slot[r];
+    if (geno_slot_out_of_range(a, sl) || !(ok & 1u) || sl == NONE32 || !wanted) return false;
+    const uint64_t at = (uint64_t)sl * S + s;
+    if (!present[at]) return false;
+    const unsigned long long c = a.counts[at];
+    ref = (uint32_t)c; alt = (uint32_t)(c >> 32);
+    return true;
+}
+
+// Item i = r * S + s per lane, items in strides of the grid.  What k_genotype does per row behind cohort_gate.  The site tags come from the same pass in
 // integers: the lanes of one row are a segment of the wave (svjg_geno.h: cohort_segment), its NS and AC are popcounts of ballots under the
 // segment's mask, and the segment's first lane adds them to site[r] with one 64-bit atomic.  Every ballot is executed by all 64 lanes on
 // every trip: the loop's bound is the WAVE's first item, and lanes beyond the last item take part with "not called".  (blocks of a multiple
@@ -2085,26 +2102,18 @@ __global__ __launch_bounds__(TPB) void k_genotype_cohort(GenoCohortArgs p) {
     uint8_t gt = 3;
     if (i < n_items) {
         r = i / S; s = i - r * S;
-        uint32_t ref = 0, alt = 0;
-        bool go = false;
-        const uint32_t ok = a.ok[r], sl = a.slot[r];
-        if (sl != NONE32 && sl >= a.n_slots) atomicOr(a.max_n + 1, 1u);       // a caller error, reported after the pass
-        else if ((ok & 1u) && sl != NONE32) {
-            const uint64_t at = (uint64_t)sl * S + s;
-            if (p.present[at]) { const unsigned long long c = a.counts[at]; ref = (uint32_t)c; alt = (uint32_t)(c >> 32); go = true; }
-        }
+        uint32_t ref, alt;
+        const bool go = cohort_gate(a, p.present, r, s, S, true, ref, alt);
         a.raw[i * 2] = ref; a.raw[i * 2 + 1] = alt;
         a.genotyped[i] = go;
-        uint8_t near = 0;
-        int64_t pl0 = 0, pl1 = 0, pl2 = 0;
+        GenoRow o{};                                                           // (an item that is not genotyped: zeros)
         if (go) {
-            GenoRow o;
             const uint32_t st = geno_row(a.sv_type[r], ref, alt, a.min_support, a.l_ok, a.l_err, a.l_half, a.logfact, a.logfact_n, o);
             if (st == GENO_ROW_GROW) atomicMax(a.max_n, (uint32_t)o.n);        // the table is too short: the host grows it and runs the items again
-            gt = o.gt; near = o.near; pl0 = o.pl[0]; pl1 = o.pl[1]; pl2 = o.pl[2];
+            gt = o.gt;
         }
-        a.gt[i] = gt; a.boundary[i] = near;
-        a.pl[i * 3] = pl0; a.pl[i * 3 + 1] = pl1; a.pl[i * 3 + 2] = pl2;
+        a.gt[i] = gt; a.boundary[i] = o.near;
+        a.pl[i * 3] = o.pl[0]; a.pl[i * 3 + 1] = o.pl[1]; a.pl[i * 3 + 2] = o.pl[2];
     }
     const uint64_t called = __ballot(gt != 3), het = __ballot(gt == 1), hom = __ballot(gt == 2);
     const CohortSeg seg = cohort_segment(i, s, S, lane, n_items);
@@ -2126,16 +2135,13 @@ struct GenoCohortPloidyArgs {
     uint32_t max_ploidy;               // 1..MAX_PLOIDY: the PL stride is max_ploidy + 1, and an item of a higher ploidy is not genotyped
 };
 
-// k_genotype_cohort's division of the work (item i = r * S + s per lane, a wave of 64 consecutive items at a time in strides of the grid) and its
-// gate, plus the ploidy byte: 1 <= ploidy[i] <= max_ploidy.  The arithmetic is geno_row_ploidy's with the call's logarithms staged in LDS, as
-// k_genotype_ploidy does.  NS, AN and AC of a row come from the same pass in integers: one ballot for "called" and one per bit plane of gt and of the
-// ploidy (both fit four bits), summed under the segment's mask (svjg_geno.h: cohort_ploidy_sums); the segment's first lane adds them to the row's
-// two site words.  Every ballot is executed by all 64 lanes on every trip: the loop's bound is the WAVE's first item, and lanes beyond the last item
-// vote "not called".  (blocks of a multiple of 64 threads)
+// k_genotype_cohort's division of the work, its loop bound and block shape, and its gate with wanted = 1 <= ploidy[i] <= max_ploidy.  The arithmetic
+// is geno_row_ploidy's on the call's logarithms staged in LDS.  NS, AN and AC of a row: one ballot for "called" and one per bit plane of gt and of
+// the ploidy (both fit four bits), summed under the segment's mask (svjg_geno.h: cohort_ploidy_sums); the segment's first lane adds them to the
+// row's two site words.
 __global__ __launch_bounds__(TPB) void k_genotype_cohort_ploidy(GenoCohortPloidyArgs p) {
   __shared__ double tab[2 * PLOIDY_TAB];
-  for (uint32_t i = threadIdx.x; i < 2 * PLOIDY_TAB; i += blockDim.x) tab[i] = p.logtab[i];
-  __syncthreads();
+  stage_ploidy_tab(tab, p.logtab);
   const GenoArgs &a = p.c.g;
   const uint64_t S = p.c.n_samples, n_items = a.n_rows * S;
   const uint32_t lane = threadIdx.x & 63u, NPL = p.max_ploidy + 1;
@@ -2145,33 +2151,21 @@ __global__ __launch_bounds__(TPB) void k_genotype_cohort_ploidy(GenoCohortPloidy
     uint32_t gt = 0xFF, P = 0;
     if (i < n_items) {
         r = i / S; s = i - r * S;
-        uint32_t ref = 0, alt = 0;
-        bool go = false;
-        const uint32_t ok = a.ok[r], sl = a.slot[r];
+        uint32_t ref, alt;
         P = p.ploidy[i];
-        if (sl != NONE32 && sl >= a.n_slots) atomicOr(a.max_n + 1, 1u);       // a caller error, reported after the pass
-        else if ((ok & 1u) && sl != NONE32 && P >= 1 && P <= p.max_ploidy) {
-            const uint64_t at = (uint64_t)sl * S + s;
-            if (p.c.present[at]) { const unsigned long long c = a.counts[at]; ref = (uint32_t)c; alt = (uint32_t)(c >> 32); go = true; }
-        }
+        const bool go = cohort_gate(a, p.c.present, r, s, S, P >= 1 && P <= p.max_ploidy, ref, alt);
         a.raw[i * 2] = ref; a.raw[i * 2 + 1] = alt;
         a.genotyped[i] = go;
-        int64_t *pl = a.pl + i * NPL;
-        uint8_t near = 0;
+        GenoRowPloidy o{};                                                     // (an item that is not genotyped: zeros)
         if (go) {
-            GenoRowPloidy o;
             const uint32_t st = geno_row_ploidy(a.sv_type[r], ref, alt, P, a.min_support, tab, tab + PLOIDY_TAB, a.logfact, a.logfact_n, o);
             if (st == GENO_ROW_GROW) atomicMax(a.max_n, (uint32_t)o.n);        // the table is too short: the host grows it and runs the items again
-            gt = o.gt; near = o.near;
-#pragma unroll
-            for (uint32_t g = 0; g <= MAX_PLOIDY; ++g)                         // (o.pl[] only ever indexed by constants: registers, no scratch)
-                if (g < NPL) pl[g] = o.pl[g];
-        } else {
-#pragma unroll
-            for (uint32_t g = 0; g <= MAX_PLOIDY; ++g)
-                if (g < NPL) pl[g] = 0;
+            gt = o.gt;
         }
-        a.gt[i] = (uint8_t)gt; a.boundary[i] = near;
+#pragma unroll
+        for (uint32_t g = 0; g <= MAX_PLOIDY; ++g)                             // (o.pl[] only ever indexed by constants: registers, no scratch)
+            if (g < NPL) a.pl[i * NPL + g] = o.pl[g];
+        a.gt[i] = (uint8_t)gt; a.boundary[i] = o.near;
     }
     const bool called = gt != 0xFF;
     CohortBallots b;

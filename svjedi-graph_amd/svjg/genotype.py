@@ -3,6 +3,8 @@
 Mirrors predict-genotype.py's decision_vcf (:89-279) for everything that is file format; the likelihood
 (:281-338) and the presence gate (:216) run on the GPU.
 """
+import functools
+
 import numpy as np
 
 NONE = 0xFFFFFFFF
@@ -90,14 +92,27 @@ class VcfRows:
         self.ok = np.array(oks, dtype=np.uint8)
 
 
-def _fmt_counts(svtype_code, ref, alt):
-    """AD and DP text after the in-place normalisation of predict-genotype.py:327-338 (Python formatting)."""
-    c = [ref, alt]
+def _norm_counts(svtype_code, ref, alt):
+    """-> (c1, c2): the counts after the in-place normalisation of predict-genotype.py:327-338"""
     if svtype_code == 0 and ref > 0:
-        c[0] = round(ref / 2, 1)
-    elif svtype_code == 1 and alt > 0:
-        c[1] = round(alt / 2, 1)
-    return str(round(sum(c), 3)), "%s,%s" % (c[0], c[1])
+        return round(ref / 2, 1), alt
+    if svtype_code == 1 and alt > 0:
+        return ref, round(alt / 2, 1)
+    return ref, alt
+
+
+def _fmt_counts(svtype_code, ref, alt):
+    """DP and AD text of the normalised counts (Python formatting)."""
+    c1, c2 = _norm_counts(svtype_code, ref, alt)
+    return str(round(c1 + c2, 3)), "%s,%s" % (c1, c2)
+
+
+def _call_args(min_support, err):
+    """what every genotype call starts with -> (min_support, the err to call with, bad_err).  A negative threshold: `sum(nbAln) >= minNbAln` always
+    holds (predict-genotype.py:310).  bad_err: math.log10(e) / math.log10(1 - e) raise in likelihood(), i.e. only once a row gets there
+    (:295-297: the reference dies at the first genotyped row), so the call runs at 0.5 and the caller raises if anything was genotyped."""
+    bad_err = not (0.0 < float(err) < 1.0)
+    return max(0, int(min_support)), 0.5 if bad_err else err, bad_err
 
 
 # ln(z!) by Stirling's series at 60 digits: ln z! = (z + 1/2) ln z - z + ln(2 pi) / 2 + sum B_2j / (2j (2j - 1) z^(2j - 1)).  With
@@ -152,33 +167,29 @@ def exact_pl(svtype_code, ref, alt, err):
     """The three PL integers of one row with the reference's own arithmetic (predict-genotype.py:284-323): double products, Decimal
     sums at precision 28, log10 of the binomial coefficient as CPython computes it for the exact integer, truncation.  For the rows
     the kernel flags as lying within 1e-6 of an integer boundary or beyond its log10(i!) table (svjg_genotype_boundary): there
-    libm's log10 of a big integer — not necessarily the correctly rounded value the kernel uses — could decide the integer."""
-    import math
-    from decimal import Decimal, localcontext
-    c1, c2 = ref, alt
-    if svtype_code == 0 and ref > 0:
-        c1 = round(ref / 2, 1)
-    elif svtype_code == 1 and alt > 0:
-        c2 = round(alt / 2, 1)
-    rc1, rc2 = int(round(c1, 0)), int(round(c2, 0))
-    l_ok, l_err, l_half = math.log10(1 - err), math.log10(err), math.log10(1 / 2)
-    with localcontext() as ctx:
-        ctx.prec = 28
-        comb = Decimal(_log10_comb(rc1 + rc2, rc1))
-        liks = (Decimal(c1 * l_ok) + Decimal(c2 * l_err), Decimal((c1 + c2) * l_half), Decimal(c2 * l_ok) + Decimal(c1 * l_err))
-        return [int(-10 * (x + comb)) for x in liks]
+    libm's log10 of a big integer — not necessarily the correctly rounded value the kernel uses — could decide the integer.  The diploid
+    case of exact_pl_ploidy: lik0, lik1 (one product) and lik2 are its g = 0, 1, 2."""
+    return exact_pl_ploidy(svtype_code, ref, alt, 2, err)
+
+
+def recompute_flagged(sv_type, pl, raw, done, boundary, err, ploidy=None):
+    """The boundary guard of every genotype call: the items that are flagged and genotyped get exact_pl_ploidy's integers, in place.  done,
+    boundary, ploidy: one entry per item, of any leading shape ([n], or [n, S] in a cohort) whose first index is the row of sv_type; pl and
+    raw: that shape + [>= P + 1] and + [2]; ploidy None: 2 everywhere.  -> the number of flagged items"""
+    idx = np.argwhere((np.asarray(boundary) != 0) & (np.asarray(done) != 0))
+    for at in map(tuple, idx):
+        P = 2 if ploidy is None else int(ploidy[at])
+        pl[at][:P + 1] = exact_pl_ploidy(int(sv_type[at[0]]), int(raw[at][0]), int(raw[at][1]), P, err)
+    return len(idx)
 
 
 def apply_boundary_guard(ctx, rows, pl, raw, done, err):
-    """-> pl with the flagged rows recomputed by exact_pl (a copy only if a row is flagged), number of flagged rows"""
+    """-> pl with the flagged rows recomputed (a copy only if a row is flagged), number of flagged rows"""
     flags = ctx.boundary_flags(len(rows.sv_type))
-    idx = np.flatnonzero(flags & (np.asarray(done) != 0))
-    if len(idx) == 0:
+    if not (flags & (np.asarray(done) != 0)).any():
         return pl, 0
     pl = np.array(pl, dtype=np.int64)
-    for r in idx:
-        pl[r] = exact_pl(int(rows.sv_type[r]), int(raw[r, 0]), int(raw[r, 1]), err)
-    return pl, len(idx)
+    return pl, recompute_flagged(rows.sv_type, pl, raw, done, flags, err)
 
 
 # ---- any ploidy from 1 to 8 (--ploidy / --ploidy-file): svjg_genotype_ploidy, Python rows and the writer below ----
@@ -192,18 +203,15 @@ _PL_G = "##FORMAT=<ID=PL,Number=G,"
 def exact_pl_ploidy(svtype_code, ref, alt, ploidy, err):
     """The ploidy + 1 PL integers of one row, PL_g for g = 0..ploidy alt copies, with the reference's arithmetic generalised: a read
     shows the alt allele with probability (g (1 - e) + (P - g) e) / P.  g = 0 and g = P are the reference's lik0 and lik2, 2 g = P its
-    lik1 (one product); at ploidy 2 this is exact_pl.  For the rows svjg_genotype_ploidy flags."""
+    lik1 (one product): double products, Decimal sums at precision 28, log10 of the binomial coefficient as CPython computes it for the
+    exact integer, truncation.  For the rows and items the kernels flag (recompute_flagged)."""
     import math
     from decimal import Decimal, localcontext
     P = int(ploidy)
     if not 1 <= P <= MAX_PLOIDY:
         raise ValueError("ploidy %r is not in 1..%d" % (ploidy, MAX_PLOIDY))
-    c1, c2 = ref, alt
-    if svtype_code == 0 and ref > 0:
-        c1 = round(ref / 2, 1)
-    elif svtype_code == 1 and alt > 0:
-        c2 = round(alt / 2, 1)
-    rc1, rc2 = int(round(c1, 0)), int(round(c2, 0))
+    c1, c2 = _norm_counts(svtype_code, ref, alt)
+    rc1, rc2 = int(round(c1, 0)), int(round(c2, 0))              # the rounded counts fed to comb()
     with localcontext() as ctx:
         ctx.prec = 28
         comb = Decimal(_log10_comb(rc1 + rc2, rc1))
@@ -286,6 +294,7 @@ def rows_ploidy(rows, ploidy=None, regions=()):
     return out
 
 
+@functools.lru_cache(maxsize=None)
 def gt_text_ploidy(P, g):
     """GT of g alt copies out of P: (P - g) zeros then g ones joined by `/`; a no-call: P dots"""
     if g == NO_CALL:
@@ -293,34 +302,61 @@ def gt_text_ploidy(P, g):
     return "/".join("0" * (P - g) + "1" * g)
 
 
-def write_vcf_ploidy(out_path, rows, ploidy, gt, pl, raw, done):
-    """write_vcf for rows of any ploidy: P + 1 PLs per row, `Number=G` in the PL header line; a ploidy-0 row prints `.:0:0,0:.`"""
-    n_done = 0
+def sample_column(svtype_code, P, g, pl, ref, alt, done):
+    """One sample column GT:DP:AD:PL of every writer.  P: the item's ploidy (0: `.:0:0,0:.`); g: the alt copies of the call, NO_CALL = 0xFF for
+    none (at P >= 3 a 3 is a call: the diploid callers translate their 3 themselves); pl: at least P + 1 integers; ref, alt: the raw counts;
+    done false: P dots as GT, no counts, P + 1 dots as PL."""
+    if P == 0:
+        return ".:0:0,0:."
+    if not done:
+        return "%s:0:0,0:%s" % ("/".join("." * P), ",".join("." * (P + 1)))
+    dp, ad = _fmt_counts(svtype_code, ref, alt)
+    return "%s:%s:%s:%s" % (gt_text_ploidy(P, g), dp, ad, ",".join(map(str, pl[:P + 1])))
+
+
+def _write_rows(out_path, rows, header, columns, info=None):
+    """The one writer loop over a VcfRows.  header: the text that stands for FORMAT_HEADER; columns(v): FORMAT and the sample columns of data
+    row v, as a list; info(v, text): the INFO column of row v from the input's (None: as it stands)."""
     with open(out_path, "w") as out:
         for kind, v in rows.items:
             if kind == "h":
-                out.write(v.replace(_PL_3, _PL_G) if v is FORMAT_HEADER else v)
+                out.write(header if v is FORMAT_HEADER else v)
                 continue
-            P = int(ploidy[v])
-            if P == 0:
-                tail = ".:0:0,0:."
-            elif done[v]:
-                n_done += 1
-                dp, ad = _fmt_counts(int(rows.sv_type[v]), int(raw[v, 0]), int(raw[v, 1]))
-                tail = "%s:%s:%s:%s" % (gt_text_ploidy(P, int(gt[v])), dp, ad, ",".join(str(int(x)) for x in pl[v, :P + 1]))
-            else:
-                tail = "%s:0:0,0:%s" % ("/".join("." * P), ",".join("." * (P + 1)))
-            out.write(rows.prefix[v] + "\tGT:DP:AD:PL\t" + tail + "\n")
-    return n_done
+            prefix = rows.prefix[v]
+            if info is not None:
+                first7, text = prefix.rsplit("\t", 1)
+                prefix = first7 + "\t" + info(v, text)
+            out.write(prefix + "\t" + "\t".join(columns(v)) + "\n")
+
+
+def _item_columns(rows, ploidy, gt, pl, raw, done):
+    """-> (columns(v) for _write_rows: GT:DP:AD:PL and one sample_column per sample, the number of genotyped rows per sample).  The arrays hold
+    one item per row ([n]: one sample) or [n, S]; ploidy None: diploid arrays, whose gt says 3 for no call"""
+    gt, pl, raw, done = np.asarray(gt), np.asarray(pl), np.asarray(raw), np.asarray(done)
+    if ploidy is None:
+        ploidy, gt = np.full(gt.shape, 2, np.uint8), np.where(gt == 3, NO_CALL, gt)
+    ploidy = np.asarray(ploidy)
+    if gt.ndim == 1:
+        ploidy, gt, pl, raw, done = ploidy[:, None], gt[:, None], pl[:, None], raw[:, None], done[:, None]
+    n_done = np.count_nonzero((done != 0) & (ploidy != 0), axis=0).tolist()
+
+    def columns(v):
+        t = int(rows.sv_type[v])
+        items = zip(ploidy[v].tolist(), gt[v].tolist(), pl[v].tolist(), raw[v].tolist(), done[v].tolist())
+        return ["GT:DP:AD:PL"] + [sample_column(t, P, g, p, r[0], r[1], d) for P, g, p, r, d in items]
+    return columns, n_done
+
+
+def write_vcf_ploidy(out_path, rows, ploidy, gt, pl, raw, done):
+    """write_vcf for rows of any ploidy: P + 1 PLs per row, `Number=G` in the PL header line; a ploidy-0 row prints `.:0:0,0:.`"""
+    columns, n_done = _item_columns(rows, ploidy, gt, pl, raw, done)
+    _write_rows(out_path, rows, FORMAT_HEADER.replace(_PL_3, _PL_G), columns)
+    return n_done[0]
 
 
 def apply_boundary_guard_ploidy(rows, ploidy, pl, raw, done, boundary, err):
-    """-> pl with the flagged rows recomputed by exact_pl_ploidy, number of flagged rows"""
-    idx = np.flatnonzero((np.asarray(boundary) != 0) & (np.asarray(done) != 0))
-    for r in idx:
-        P = int(ploidy[r])
-        pl[r, :P + 1] = exact_pl_ploidy(int(rows.sv_type[r]), int(raw[r, 0]), int(raw[r, 1]), P, err)
-    return pl, len(idx)
+    """-> pl with the flagged rows recomputed, number of flagged rows"""
+    return pl, recompute_flagged(rows.sv_type, pl, raw, done, boundary, err, ploidy)
 
 
 def genotype_with_counts_ploidy(ctx, vcf_path, slot_of, out_path, min_support, err, slot_is_presence, ploidy, ploidy_file):
@@ -330,9 +366,8 @@ def genotype_with_counts_ploidy(ctx, vcf_path, slot_of, out_path, min_support, e
         slot_of = {k: i for i, k in enumerate(slot_of)}
     rows = VcfRows(vcf_path, slot_of, slot_is_presence)
     pld = rows_ploidy(rows, ploidy, regions)
-    min_support = max(0, int(min_support))
-    bad_err = not (0.0 < float(err) < 1.0)
-    gt, pl, raw, done, boundary = ctx.genotype_ploidy(rows.sv_type, rows.slot, rows.ok, pld, min_support, 0.5 if bad_err else err)
+    min_support, call_err, bad_err = _call_args(min_support, err)
+    gt, pl, raw, done, boundary = ctx.genotype_ploidy(rows.sv_type, rows.slot, rows.ok, pld, min_support, call_err)
     if bad_err and done.any():
         raise ValueError("math domain error")
     pl, _ = apply_boundary_guard_ploidy(rows, pld, pl, raw, done, boundary, err)
@@ -411,26 +446,16 @@ def project_site(K, i, gt_pair, site_pl):
 
 def write_vcf_joint(out_path, rows, gt, pl, raw, done, member):
     """write_vcf with the members of a site printed as GT:DP:AD:PL:SGT:SAL; member: row -> (g, [three PLs], site call text, allele number)"""
-    n_done = 0
-    with open(out_path, "w") as out:
-        for kind, v in rows.items:
-            if kind == "h":
-                out.write(v.replace(_PL_LINE, _PL_LINE + SITE_FORMAT_LINES) if v is FORMAT_HEADER else v)
-                continue
-            fmt = "GT:DP:AD:PL"
-            if done[v]:
-                n_done += 1
-                dp, ad = _fmt_counts(int(rows.sv_type[v]), int(raw[v, 0]), int(raw[v, 1]))
-                if v in member:
-                    g, p, sgt, sal = member[v]
-                    fmt = "GT:DP:AD:PL:SGT:SAL"
-                    tail = "%s:%s:%s:%d,%d,%d:%s:%d" % (GT_TEXT[g], dp, ad, p[0], p[1], p[2], sgt, sal)
-                else:
-                    tail = "%s:%s:%s:%d,%d,%d" % (GT_TEXT[gt[v]], dp, ad, pl[v, 0], pl[v, 1], pl[v, 2])
-            else:
-                tail = "./.:0:0,0:.,.,."
-            out.write(rows.prefix[v] + "\t" + fmt + "\t" + tail + "\n")
-    return n_done
+    plain, n_done = _item_columns(rows, None, gt, pl, raw, done)
+
+    def columns(v):
+        if not (done[v] and v in member):
+            return plain(v)
+        g, p, sgt, sal = member[v]
+        col = sample_column(int(rows.sv_type[v]), 2, NO_CALL if g == 3 else g, p, int(raw[v, 0]), int(raw[v, 1]), True)
+        return ["GT:DP:AD:PL:SGT:SAL", "%s:%s:%d" % (col, sgt, sal)]
+    _write_rows(out_path, rows, FORMAT_HEADER.replace(_PL_LINE, _PL_LINE + SITE_FORMAT_LINES), columns)
+    return n_done[0]
 
 
 def genotype_with_counts_joint(ctx, vcf_path, slot_of, out_path, min_support, err, slot_is_presence):
@@ -440,9 +465,8 @@ def genotype_with_counts_joint(ctx, vcf_path, slot_of, out_path, min_support, er
     if not isinstance(slot_of, dict):
         slot_of = {k: i for i, k in enumerate(slot_of)}
     rows = VcfRows(vcf_path, slot_of, slot_is_presence)
-    min_support = max(0, int(min_support))
-    bad_err = not (0.0 < float(err) < 1.0)
-    gt, pl, raw, done = ctx.genotype(rows.sv_type, rows.slot, rows.ok, min_support, 0.5 if bad_err else err)
+    min_support, call_err, bad_err = _call_args(min_support, err)
+    gt, pl, raw, done = ctx.genotype(rows.sv_type, rows.slot, rows.ok, min_support, call_err)
     if bad_err and np.asarray(done).any():
         raise ValueError("math domain error")
     pl, _ = apply_boundary_guard(ctx, rows, pl, raw, done, err)
@@ -521,6 +545,11 @@ def cohort_union(samples):
     return list(slot_of), per
 
 
+def _cohort_header(header, names):
+    """the header text of a cohort VCF: the site tags' INFO lines in front, one column name per sample"""
+    return COHORT_INFO_LINES + header.replace("\tFORMAT\tSAMPLE\n", "\tFORMAT\t" + "\t".join(names) + "\n")
+
+
 def cohort_info(info, ns, ac, an=None):
     """the INFO column of a cohort row: the input's without any NS= / AN= / AC= / AF= field (whole fields, exact key), a lone `.` replaced,
     then NS, AN (2 NS unless given: the called samples' ploidies summed, --cohort-ploidy), AC and, when AN > 0, AF = "%.6g" % (AC / AN)"""
@@ -538,26 +567,8 @@ def cohort_info(info, ns, ac, an=None):
 def write_vcf_cohort(out_path, rows, names, gt, pl, raw, done, site):
     """write_vcf with one column per sample (gt, done: [n, S]; pl: [n, S, 3]; raw: [n, S, 2]; site: [n, 2] = NS, AC) and the site tags in
     INFO -> the number of genotyped rows of every sample"""
-    S = len(names)
-    n_done = [0] * S
-    with open(out_path, "w") as out:
-        for kind, v in rows.items:
-            if kind == "h":
-                if v is FORMAT_HEADER:
-                    v = COHORT_INFO_LINES + v.replace("\tFORMAT\tSAMPLE\n", "\tFORMAT\t" + "\t".join(names) + "\n")
-                out.write(v)
-                continue
-            first7, info = rows.prefix[v].rsplit("\t", 1)
-            cols = []
-            t = int(rows.sv_type[v])
-            for s in range(S):
-                if done[v, s]:
-                    n_done[s] += 1
-                    dp, ad = _fmt_counts(t, int(raw[v, s, 0]), int(raw[v, s, 1]))
-                    cols.append("%s:%s:%s:%d,%d,%d" % (GT_TEXT[gt[v, s]], dp, ad, pl[v, s, 0], pl[v, s, 1], pl[v, s, 2]))
-                else:
-                    cols.append("./.:0:0,0:.,.,.")
-            out.write(first7 + "\t" + cohort_info(info, int(site[v, 0]), int(site[v, 1])) + "\tGT:DP:AD:PL\t" + "\t".join(cols) + "\n")
+    columns, n_done = _item_columns(rows, None, gt, pl, raw, done)
+    _write_rows(out_path, rows, _cohort_header(FORMAT_HEADER, names), columns, lambda v, info: cohort_info(info, int(site[v, 0]), int(site[v, 1])))
     return n_done
 
 
@@ -566,26 +577,33 @@ def cohort_chunk_rows(n_samples):
     return max(1, COHORT_CALL_BYTES // (COHORT_ITEM_BYTES * max(1, int(n_samples))))
 
 
-def genotype_cohort_rows(ctx, rows, n_samples, min_support, err):
-    """the rows of a VcfRows against the context's cohort matrix, in row chunks -> (gt, pl, raw, done, site) over all rows, the flagged items
-    recomputed by exact_pl (the GT does not depend on the PL integers: NS and AC stay as the kernel gave them)"""
-    n, S = len(rows.sv_type), int(n_samples)
-    min_support = max(0, int(min_support))
-    bad_err = not (0.0 < float(err) < 1.0)
-    step = cohort_chunk_rows(S)
+def _cohort_rows(call, rows, step, empty, min_support, err, ploidy=None):
+    """The one cohort driver: the rows of a VcfRows against the context's cohort matrix in chunks of `step` rows, call(lo, hi, min_support,
+    err) -> (gt, pl, raw, done, boundary, site) per chunk -> (gt, pl, raw, done, site) over all rows (empty: the same for no row at all), the
+    flagged items recomputed (the GT does not depend on the PL integers: the site words stay as the kernel gave them)"""
+    min_support, call_err, bad_err = _call_args(min_support, err)
     parts = []
-    for at in range(0, n, step):
-        gt, pl, raw, done, boundary, site = ctx.genotype_cohort(rows.sv_type[at:at + step], rows.slot[at:at + step], rows.ok[at:at + step],
-                                                                min_support, 0.5 if bad_err else err)
+    for at in range(0, len(rows.sv_type), step):
+        gt, pl, raw, done, boundary, site = call(at, at + step, min_support, call_err)
         if bad_err and done.any():
-            raise ValueError("math domain error")               # (as genotype_with_counts: the reference dies at the first genotyped row)
-        for r, s in zip(*np.nonzero((boundary != 0) & (done != 0))):
-            pl[r, s] = exact_pl(int(rows.sv_type[at + r]), int(raw[r, s, 0]), int(raw[r, s, 1]), err)
+            raise ValueError("math domain error")               # (as genotype_with_counts)
+        recompute_flagged(rows.sv_type[at:at + step], pl, raw, done, boundary, err, None if ploidy is None else ploidy[at:at + step])
         parts.append((gt, pl, raw, done, site))
     if not parts:
-        return (np.zeros((0, S), np.uint8), np.zeros((0, S, 3), np.int64), np.zeros((0, S, 2), np.uint32), np.zeros((0, S), np.uint8),
-                np.zeros((0, 2), np.uint32))
+        return empty
     return tuple(np.concatenate([p[k] for p in parts]) for k in range(5))
+
+
+def _cohort_empty(S, n_pl, n_site):
+    return (np.zeros((0, S), np.uint8), np.zeros((0, S, n_pl), np.int64), np.zeros((0, S, 2), np.uint32), np.zeros((0, S), np.uint8),
+            np.zeros((0, n_site), np.uint32))
+
+
+def genotype_cohort_rows(ctx, rows, n_samples, min_support, err):
+    """the diploid cohort call over all rows -> (gt, pl[n, S, 3], raw, done, site[n, 2] = NS, AC)"""
+    S = int(n_samples)
+    return _cohort_rows(lambda lo, hi, ms, e: ctx.genotype_cohort(rows.sv_type[lo:hi], rows.slot[lo:hi], rows.ok[lo:hi], ms, e),
+                        rows, cohort_chunk_rows(S), _cohort_empty(S, 3, 2), min_support, err)
 
 
 # ---- cohort at per-sample ploidy (--cohort LIST --cohort-ploidy FILE): svjg_genotype_cohort_ploidy, Python rows and the writer below ----
@@ -640,57 +658,21 @@ def cohort_ploidy_chunk_rows(n_samples, max_ploidy):
 
 
 def genotype_cohort_ploidy_rows(ctx, rows, ploidy, min_support, err):
-    """genotype_cohort_rows at ploidy[n, S] per item -> (gt, pl[n, S, max_ploidy + 1], raw, done, site[n, 3] = NS, AN, AC) over all rows;
-    max_ploidy = the matrix's maximum, at least 1; the flagged items recomputed by exact_pl_ploidy (the GT does not depend on the PL integers)"""
+    """the cohort call at ploidy[n, S] per item over all rows -> (gt, pl[n, S, max_ploidy + 1], raw, done, site[n, 3] = NS, AN, AC); max_ploidy =
+    the matrix's maximum, at least 1"""
     ploidy = np.ascontiguousarray(ploidy, dtype=np.uint8)
-    n, S = ploidy.shape
+    S = ploidy.shape[1]
     max_ploidy = max(1, int(ploidy.max())) if ploidy.size else 1
-    min_support = max(0, int(min_support))
-    bad_err = not (0.0 < float(err) < 1.0)
-    step = cohort_ploidy_chunk_rows(S, max_ploidy)
-    parts = []
-    for at in range(0, n, step):
-        pld = ploidy[at:at + step]
-        gt, pl, raw, done, boundary, site = ctx.genotype_cohort_ploidy(rows.sv_type[at:at + step], rows.slot[at:at + step], rows.ok[at:at + step],
-                                                                       pld, max_ploidy, min_support, 0.5 if bad_err else err)
-        if bad_err and done.any():
-            raise ValueError("math domain error")               # (as genotype_cohort_rows)
-        for r, s in zip(*np.nonzero((boundary != 0) & (done != 0))):
-            P = int(pld[r, s])
-            pl[r, s, :P + 1] = exact_pl_ploidy(int(rows.sv_type[at + r]), int(raw[r, s, 0]), int(raw[r, s, 1]), P, err)
-        parts.append((gt, pl, raw, done, site))
-    if not parts:
-        return (np.zeros((0, S), np.uint8), np.zeros((0, S, max_ploidy + 1), np.int64), np.zeros((0, S, 2), np.uint32), np.zeros((0, S), np.uint8),
-                np.zeros((0, 3), np.uint32))
-    return tuple(np.concatenate([p[k] for p in parts]) for k in range(5))
+    return _cohort_rows(lambda lo, hi, ms, e: ctx.genotype_cohort_ploidy(rows.sv_type[lo:hi], rows.slot[lo:hi], rows.ok[lo:hi], ploidy[lo:hi], max_ploidy, ms, e),
+                        rows, cohort_ploidy_chunk_rows(S, max_ploidy), _cohort_empty(S, max_ploidy + 1, 3), min_support, err, ploidy)
 
 
 def write_vcf_cohort_ploidy(out_path, rows, names, ploidy, gt, pl, raw, done, site):
     """write_vcf_cohort with every item in write_vcf_ploidy's forms (ploidy, gt, done: [n, S]; pl: [n, S, >= P + 1]; site: [n, 3] = NS, AN,
     AC) and `Number=G` in the PL header line -> the number of genotyped rows of every sample"""
-    S = len(names)
-    n_done = [0] * S
-    with open(out_path, "w") as out:
-        for kind, v in rows.items:
-            if kind == "h":
-                if v is FORMAT_HEADER:
-                    v = COHORT_INFO_LINES + v.replace(_PL_3, _PL_G).replace("\tFORMAT\tSAMPLE\n", "\tFORMAT\t" + "\t".join(names) + "\n")
-                out.write(v)
-                continue
-            first7, info = rows.prefix[v].rsplit("\t", 1)
-            cols = []
-            t = int(rows.sv_type[v])
-            for s in range(S):
-                P = int(ploidy[v, s])
-                if P == 0:
-                    cols.append(".:0:0,0:.")
-                elif done[v, s]:
-                    n_done[s] += 1
-                    dp, ad = _fmt_counts(t, int(raw[v, s, 0]), int(raw[v, s, 1]))
-                    cols.append("%s:%s:%s:%s" % (gt_text_ploidy(P, int(gt[v, s])), dp, ad, ",".join(str(int(x)) for x in pl[v, s, :P + 1])))
-                else:
-                    cols.append("%s:0:0,0:%s" % ("/".join("." * P), ",".join("." * (P + 1))))
-            out.write(first7 + "\t" + cohort_info(info, int(site[v, 0]), int(site[v, 2]), int(site[v, 1])) + "\tGT:DP:AD:PL\t" + "\t".join(cols) + "\n")
+    columns, n_done = _item_columns(rows, ploidy, gt, pl, raw, done)
+    _write_rows(out_path, rows, _cohort_header(FORMAT_HEADER.replace(_PL_3, _PL_G), names), columns,
+                lambda v, info: cohort_info(info, int(site[v, 0]), int(site[v, 2]), int(site[v, 1])))
     return n_done
 
 
@@ -731,20 +713,9 @@ def run_cohort(list_path, vcf_path, out_path, min_support=3, err=0.00005, device
 
 
 def write_vcf(out_path, rows, gt, pl, raw, done):
-    n_done = 0
-    with open(out_path, "w") as out:
-        for kind, v in rows.items:
-            if kind == "h":
-                out.write(v)
-                continue
-            if done[v]:
-                n_done += 1
-                dp, ad = _fmt_counts(int(rows.sv_type[v]), int(raw[v, 0]), int(raw[v, 1]))
-                tail = "%s:%s:%s:%d,%d,%d" % (GT_TEXT[gt[v]], dp, ad, pl[v, 0], pl[v, 1], pl[v, 2])
-            else:
-                tail = "./.:0:0,0:.,.,."
-            out.write(rows.prefix[v] + "\tGT:DP:AD:PL\t" + tail + "\n")
-    return n_done
+    columns, n_done = _item_columns(rows, None, gt, pl, raw, done)
+    _write_rows(out_path, rows, FORMAT_HEADER, columns)
+    return n_done[0]
 
 
 def open_rows(vcf_path, slot_of, slot_is_presence=False):
@@ -778,9 +749,8 @@ def genotype_with_counts(ctx, vcf_path, slot_of, out_path, min_support=3, err=0.
     if ploidy is not None or ploidy_file is not None:
         return genotype_with_counts_ploidy(ctx, vcf_path, slot_of, out_path, min_support, err, slot_is_presence, ploidy, ploidy_file)
     rows = open_rows(vcf_path, slot_of, slot_is_presence)
-    min_support = max(0, int(min_support))                       # (a negative threshold: `sum(nbAln) >= minNbAln` always holds, predict-genotype.py:310)
-    bad_err = not (0.0 < float(err) < 1.0)                       # math.log10(e) / math.log10(1 - e) raise in likelihood(), i.e. only once a row gets there
-    gt, pl, raw, done = ctx.genotype(rows.sv_type, rows.slot, rows.ok, min_support, 0.5 if bad_err else err, reuse_outputs=True)   # views: written out right away
+    min_support, call_err, bad_err = _call_args(min_support, err)
+    gt, pl, raw, done = ctx.genotype(rows.sv_type, rows.slot, rows.ok, min_support, call_err, reuse_outputs=True)   # views: written out right away
     if bad_err and np.asarray(done).any():
         raise ValueError("math domain error")                   # (predict-genotype.py:295-297: the reference dies at the first genotyped row)
     pl, _ = apply_boundary_guard(ctx, rows, pl, raw, done, err)

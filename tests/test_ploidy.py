@@ -77,7 +77,8 @@ def test_log_table_is_the_models():
 
 
 def test_ploidy_2_equals_the_diploid_routine(golden):
-    """geno_row_ploidy at P = 2 against geno_row on the lik_kat rows: gt, three PLs, near"""
+    """geno_row_ploidy at P = 2 against geno_row on the lik_kat rows: gt, three PLs, near — and, geno_row being that routine at the literal
+    ploidy 2, both against the fixture's own columns (the reference's answers): GT on every row, the PLs on every row that is not flagged"""
     from tests.ploidy_sim import sim
     z = np.load(f"{golden}/lik/lik_kat.npz")
     cases, errs = z["cases"], z["err"]
@@ -94,6 +95,10 @@ def test_ploidy_2_equals_the_diploid_routine(golden):
             g, p, n, s = sim.genotype_rows(c[:, 0], c[:, 1:3], np.full(len(c), 2), int(ms), float(e), tab)
             assert np.array_equal(np.where(g == NO_CALL, 3, g), g2) and np.array_equal(p[:, :3], p2) and not p[:, 3:].any()
             assert np.array_equal(n, n2) and np.array_equal(s, s2)
+            for gt_, pl_, near_ in ((g2, p2, n2), (np.where(g == NO_CALL, 3, g), p[:, :3], n)):
+                assert np.array_equal(gt_, c[:, 4]), c[gt_ != c[:, 4]][:5]
+                bad = np.flatnonzero((near_ == 0) & (pl_ != c[:, 5:8]).any(axis=1))
+                assert len(bad) == 0, (c[bad[:5]], pl_[bad[:5]])
             seen += len(sel)
     assert seen == len(cases)
 
