@@ -85,6 +85,19 @@ enum { BLOCK_ROWS, BLOCK_PLOIDY, BLOCK_SITES, BLOCK_COHORT, BLOCK_COHORT_PLOIDY,
 // slots the passes of svjg_run_begin rotate through: two may be in flight, and the one the NEXT pass will use is zeroed while the newest computes
 constexpr int RUN_SLOTS = 3;
 
+// What one k_classify_main launch, and the k_classify_exact behind it, may write into.  Two main kernels may be alive at once (consecutive
+// overlapped passes), and a launch shares NONE of this with the launch beside it: count vector and status block (the slot's), the two lists
+// (the slot's), the workers' scratch words (the compute stream's).  Text and graph tables are read-only; a fused pass writes no hit records
+// (want_hits 0).  The step-by-step calls have one set (step_targets), every fused pass its slot's (slot_targets); main_launch_setup fills
+// ClassifyArgs from a set, and nobody assigns one of these fields of ClassifyArgs afterwards.
+struct PassTargets {
+    unsigned long long *counts;  DevStatus *st;
+    uint64_t *deferred;  uint64_t deferred_cap;
+    uint64_t *host;  uint64_t host_cap;              // offsets of the lines set aside for the host (SVJG_EXC_ASK_HOST)
+    svjg_hitrec *recs;  uint64_t rec_cap;
+    int scratch;                                     // the compute stream the launch runs on (0: stream, 1: stream2): svjg_ctx::d_long[scratch]
+};
+
 struct svjg_ctx {
     int device = 0;
     int wall_khz = 0;                    // rate of wall_clock64(), the clock of the kernels' time stamps
@@ -118,8 +131,7 @@ struct svjg_ctx {
     uint64_t *d_host = nullptr;      uint64_t host_cap = 0;     // offsets of the lines set aside for the host (SVJG_EXC_ASK_HOST)
     DevStatus *d_st = nullptr;
     unsigned long long *d_dbg = nullptr;
-    uint32_t *d_long = nullptr;          // LONG_WORDS words per worker of k_classify_main (ClassifyArgs::long_pre): of the launches on `stream`
-    uint32_t *d_long2 = nullptr;         // the same for the launches on stream2: two main kernels may be alive at once, worker numbers are per launch
+    uint32_t *d_long[2] = {};            // LONG_WORDS words per worker of k_classify_main (ClassifyArgs::long_pre), [k]: of the launches on compute stream k — two main kernels may be alive at once, worker numbers are per launch (scratch_words)
     const uint64_t *host_lines_src = nullptr;  uint64_t host_lines_cap = 0;   // the list hs().n_host counts (svjg_get_host_lines): d_host (nullptr), or the last finished pass's own
     DevStatus *h_stp = nullptr;          // host twin of d_st in pinned memory: the status copies are asynchronous in both directions
     DevStatus &hs() { return *h_stp; }
@@ -138,7 +150,7 @@ struct svjg_ctx {
         unsigned long long *counts = nullptr;  uint64_t counts_cap = 0;   // the pass's own count vector (+ guard words): the next pass may zero its own while this one is genotyped
         hipEvent_t ev[6] = {};  hipEvent_t computed = nullptr, copied = nullptr;
         uint64_t base_offset = 0;  uint32_t min_support = 0;  double err = 0;  bool had_text = false, slow_end_own = false, timed_by_events = false;
-        // the pass's own lists (two main kernels may be alive at once): deferred lines, lines for the host; sized in svjg_run_begin, while no pass uses the slot
+        // the pass's own lists (two main kernels may be alive at once): deferred lines, lines for the host; sized in pass_lists, while no pass uses the slot
         uint64_t *deferred = nullptr;  uint64_t deferred_cap = 0;  uint64_t *host = nullptr;  uint64_t host_cap = 0;
         bool overlapped = false;         // the pass's form (svjg_pass.h: pass_overlaps): no exact-path launch on its stream, svjg_run_end settles it
         bool inflight = false;           // begun, not yet ended
@@ -236,7 +248,7 @@ extern "C" void svjg_destroy(svjg_ctx *c) {
     if (c->copy_stream) hipStreamSynchronize(c->copy_stream);
     if (c->comm) ncclCommDestroy(c->comm);
     free_graph(c);
-    hipFree(c->d_long); hipFree(c->d_long2);
+    hipFree(c->d_long[0]); hipFree(c->d_long[1]);
     hipFree(c->d_gaf); hipFree(c->d_deferred); hipFree(c->d_recs); hipFree(c->d_host); hipFree(c->d_st); hipFree(c->d_logfact);
     hipFree(c->d_bsum); hipFree(c->d_run_in);
     hipFree(c->d_cm); hipFree(c->d_cstage);
@@ -306,8 +318,8 @@ static int alloc_count_vectors(svjg_ctx *c, uint32_t n_slots) {
     c->have_counts = true;
     return 0;
 }
-// blocks of TPB over n items, 1 to 1024 (the kernels stride)
-static uint32_t capped_grid(uint64_t n) { const uint64_t g = (n + TPB - 1) / TPB; return g > 1024 ? 1024u : g < 1 ? 1u : (uint32_t)g; }
+// blocks of tpb over n items, 1 to 1024 (the kernels stride)
+static uint32_t capped_grid(uint64_t n, uint32_t tpb = TPB) { const uint64_t g = (n + tpb - 1) / tpb; return g > 1024 ? 1024u : g < 1 ? 1u : (uint32_t)g; }
 
 static int reset_status(svjg_ctx *c, bool all) {
     if (all) {                                                // from the constant copy: the host's own status may be written again at once
@@ -515,7 +527,6 @@ static int ensure_pinned(svjg_ctx *c, void **p, uint64_t *cap, uint64_t want, un
     return 0;
 }
 
-// arguments and geometry of one k_classify_main launch over the lines of the resident text that lie in [begin, end)
 // The passes of svjg_run_begin keep their counts in vectors of their own; the rest of the API works on d_counts: the newest pass's
 // vector is copied there when someone asks for it (svjg_get_counts, svjg_genotype, svjg_classify adding to it, ...).
 static int settle_pass(svjg_ctx *c, svjg_ctx::RunSlot &r);
@@ -533,47 +544,49 @@ static int fetch_slot_counts(svjg_ctx *c) {
     return 0;
 }
 
-static uint64_t deferred_want(const svjg_ctx *c, uint64_t n) { return (c->gflags & SVJG_GRAPH_ALL_SLOW) ? n / 24 + 64 : (n / 4096 + 65536); }
+// the two sets of targets there are, each from its fields in this one place: the step-by-step calls' (the context's own lists, d_counts, on c->stream) ...
+static PassTargets step_targets(const svjg_ctx *c) { return PassTargets{c->d_counts, c->d_st, c->d_deferred, c->deferred_cap, c->d_host, c->host_cap, c->d_recs, c->rec_cap, 0}; }
+// ... and a fused pass's: everything its slot's (the status block lies in the slot's row block: its tail goes to the host in one small copy)
+static PassTargets slot_targets(const svjg_ctx *c, const svjg_ctx::RunSlot &r, const RunLayout &L) {
+    return PassTargets{r.counts, (DevStatus *)((uint8_t *)r.d + L.status), r.deferred, r.deferred_cap, r.host, r.host_cap, nullptr, 0, r.on == c->stream2 ? 1 : 0};
+}
 
-static void main_launch_setup(svjg_ctx *c, uint64_t begin, uint64_t end, uint64_t base_offset, int want_hits, ClassifyArgs &a, uint32_t &grid, size_t &lds) {
-    const uint64_t n = end - begin;
-    const bool all_slow = (c->gflags & SVJG_GRAPH_ALL_SLOW) != 0;
-    a.gaf = c->d_gaf; a.begin = begin; a.n_bytes = end; a.base_offset = base_offset; a.g = c->gv;
-    a.all_slow = all_slow; a.want_hits = want_hits != 0;
+// the scratch words of the launches on compute stream k, allocated at the stream's first launch (the second block: only a context that overlaps
+// passes has one); nullptr: no memory.  Both are freed where the occupancy becomes known (main_launch_setup).
+static uint32_t *scratch_words(svjg_ctx *c, int k) {
+    if (!c->d_long[k] && hipMalloc((void **)&c->d_long[k], (uint64_t)c->n_cu * (uint64_t)c->occ_main * LONG_WORDS * sizeof(uint32_t)) != hipSuccess) { (void)hipGetLastError(); c->d_long[k] = nullptr; }
+    return c->d_long[k];
+}
+
 #ifdef SVJG_ABLATE
-    { const char *dg = getenv("SVJG_DIAG"); a.diag = dg ? (uint32_t)atoi(dg) : 0u; }   // ablation knob (measurement builds only)
+// ablation knobs (measurement builds only): ClassifyArgs::diag from SVJG_DIAG; the occupancy the API gave, printed, and SVJG_OCC in its place
+static uint32_t ablate_diag() { const char *dg = getenv("SVJG_DIAG"); return dg ? (uint32_t)atoi(dg) : 0u; }
+static void ablate_occupancy(svjg_ctx *c, int occ, size_t lds) { const char *oc = getenv("SVJG_OCC"); fprintf(stderr, "[svjg diag] occupancy API: %d workgroups of %u threads per CU (LDS %zu)\n", occ, WG, lds); if (oc && atoi(oc) > 0) c->occ_main = atoi(oc); }
 #endif
-    a.counts = c->d_counts; a.deferred = c->d_deferred; a.deferred_cap = c->deferred_cap;
-    a.recs = c->d_recs; a.rec_cap = c->rec_cap; a.host_lines = c->d_host; a.host_cap = c->host_cap; a.st = c->d_st; a.dbg = c->d_dbg;
+
+// arguments and geometry of one k_classify_main launch over the lines of the resident text that lie in [begin, end), writing into `t`
+static int main_launch_setup(svjg_ctx *c, const PassTargets &t, uint64_t begin, uint64_t end, uint64_t base_offset, int want_hits, ClassifyArgs &a, uint32_t &grid, size_t &lds) {
+    a.gaf = c->d_gaf; a.begin = begin; a.n_bytes = end; a.base_offset = base_offset; a.g = c->gv;
+    a.all_slow = (c->gflags & SVJG_GRAPH_ALL_SLOW) != 0; a.want_hits = want_hits != 0;
+#ifdef SVJG_ABLATE
+    a.diag = ablate_diag();
+#endif
+    a.counts = t.counts; a.st = t.st; a.deferred = t.deferred; a.deferred_cap = t.deferred_cap;
+    a.host_lines = t.host; a.host_cap = t.host_cap; a.recs = t.recs; a.rec_cap = t.rec_cap; a.dbg = c->d_dbg;
     lds = LDS_MAIN;
     if (c->occ_main < 1) {                                // persistent grid: every CU filled to what LDS / registers admit (asked once)
         int occ = 0;
         if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, k_classify_main, (int)WG, lds) != hipSuccess || occ < 1) occ = 1;
-        // LDS is handed out in units of LDS_GRANULE bytes (measured: a 15 568-byte workgroup is admitted 9 times per CU where the
-        // API says 10); a worker too many would run in a second round behind the others
-        const int by_lds = (int)((160u * 1024u) / ((lds + LDS_GRANULE - 1) / LDS_GRANULE * LDS_GRANULE));
-        if (by_lds >= 1 && occ > by_lds) occ = by_lds;
-        c->occ_main = occ;
-        hipFree(c->d_long); hipFree(c->d_long2); c->d_long = nullptr; c->d_long2 = nullptr;
+        c->occ_main = occ = main_occupancy(occ, lds, LDS_GRANULE);
+        for (auto &w : c->d_long) { hipFree(w); w = nullptr; }
 #ifdef SVJG_ABLATE
-        { const char *oc = getenv("SVJG_OCC"); fprintf(stderr, "[svjg diag] occupancy API: %d workgroups of %u threads per CU (LDS %zu)\n", occ, WG, lds); if (oc && atoi(oc) > 0) c->occ_main = atoi(oc); }
+        ablate_occupancy(c, occ, lds);
 #endif
     }
-    // one worker (wave) per resident slot; every worker owns the lines starting in its region of the text.  Small inputs:
-    // regions of at least one stripe, fewer workers.
-    // A worker's first chunk is most of an even share, fixed; what is left goes in small chunks to whoever is free next
-    // (svjg_kernels.h: the workers of a CU do not run equally fast).  Inputs too small for that: even shares of at least a stripe.
-    const uint64_t full = (uint64_t)c->n_cu * (uint64_t)c->occ_main;
-    if (!c->d_long && hipMalloc((void **)&c->d_long, full * LONG_WORDS * sizeof(uint32_t)) != hipSuccess) c->d_long = nullptr;   // (checked by the callers: a launch without it is refused)
-    a.long_pre = c->d_long;
-    const uint64_t share = (n + full - 1) / full;
-    uint64_t region = (share + 15) & ~15ull;
-    a.small = 0;
-    if (share >= 8 * SMALL_CHUNK) { region = ((uint64_t)(share * FIRST_CHUNK_SHARE) + 15) & ~15ull; a.small = SMALL_CHUNK; }
-    if (region < TEXT) region = TEXT;
-    a.region = region;
-    const uint64_t want_grid = (n + region - 1) / region;
-    grid = (uint32_t)(want_grid < full ? want_grid : full);
+    if (!(a.long_pre = scratch_words(c, t.scratch))) { c->err = "no memory for the workers' scratch words"; return SVJG_E_NOMEM; }
+    const MainPlan p = main_plan(end - begin, (uint64_t)c->n_cu * (uint64_t)c->occ_main, TEXT, SMALL_CHUNK, FIRST_CHUNK_SHARE);
+    a.region = p.region; a.small = p.small; grid = p.grid;
+    return 0;
 }
 
 // The exact path's one launch, k_classify_exact behind a k_classify_main with the same arguments: its blocks take the wave role up to
@@ -589,6 +602,38 @@ static int launch_exact(svjg_ctx *c, const ClassifyArgs &a, uint64_t wave_rounds
     return 0;
 }
 
+// k_classify_main on `on`, for the step-by-step calls and the fused pass alike; ev (or nullptr): an event pair recorded around it
+static int enqueue_main(svjg_ctx *c, hipStream_t on, const ClassifyArgs &a, uint32_t grid, size_t lds, hipEvent_t *ev) {
+    if (ev) HIPCHK(c, hipEventRecord(ev[0], on));
+    hipLaunchKernelGGL(k_classify_main, dim3(grid), dim3(WG), lds, on, a);
+    HIPCHK(c, hipGetLastError());
+    if (ev) HIPCHK(c, hipEventRecord(ev[1], on));
+    return 0;
+}
+
+#ifdef SVJG_TIMING
+// measurement only (SVJG_DIAG & 16): what the kernels of a step-by-step call left in d_dbg, behind the main kernel / behind the exact path
+static int timing_print_main(svjg_ctx *c) {
+    unsigned long long d[16];
+    HIPCHK(c, hipMemcpy(d, c->d_dbg, sizeof d, hipMemcpyDeviceToHost));
+    fprintf(stderr, "[svjg diag] sub-passes of long lines: first sweep counting %llu, first sweep measuring only %llu, second sweep %llu; nodes in sub-passes %llu\n", d[12], d[13], d[14], d[15]);
+    fprintf(stderr, "[svjg diag] wave time per phase (sum over waves, counter ticks)  A+B1 %llu  prefix %llu  B2 %llu  R1 %llu  NP: lists %llu  names+disp %llu  records %llu  scan+search %llu  links+atomics %llu  R6+end %llu;  passes %llu (sub-passes of long lines %llu), nodes in them %llu\n",
+            d[0], d[1], d[2], d[3], d[8], d[9], d[4], 0ull, d[6], d[7], d[10], d[11], d[5]);
+    return 0;
+}
+static int timing_print_exact(svjg_ctx *c) {
+    unsigned long long d[8];
+    HIPCHK(c, hipMemcpy(d, c->d_dbg + 16, sizeof d, hipMemcpyDeviceToHost));
+    fprintf(stderr, "[svjg diag] one wave per line, the longest any line took per step (counter ticks): terminator + staging %llu  per-line part %llu  piece table %llu  nodes %llu  links %llu\n",
+            d[0], d[1], d[2], d[3], d[4]);
+    unsigned long long l[5];
+    HIPCHK(c, hipMemcpy(l, c->d_dbg + 24, sizeof l, hipMemcpyDeviceToHost));
+    fprintf(stderr, "[svjg diag] one lane per line, ticks summed over the blocks of 64 lines: terminators + staging %llu  per-line part %llu  nodes %llu  links %llu  rest %llu\n",
+            l[0], l[1], l[2], l[3], l[4]);
+    return 0;
+}
+#endif
+
 // the lines of the resident text that lie in [begin, end): begin is a line start, end the byte behind a terminator (or the text's end)
 static int classify_range(svjg_ctx *c, uint64_t begin, uint64_t end, uint64_t base_offset, int want_hits) {
     HIPCHK(c, hipSetDevice(c->device));
@@ -597,41 +642,28 @@ static int classify_range(svjg_ctx *c, uint64_t begin, uint64_t end, uint64_t ba
     c->host_lines_src = nullptr;                                  // (d_host, wherever ensure() puts it)
     if (end <= begin) return 0;
     const uint64_t n = end - begin;
-    uint64_t def_want = deferred_want(c, n);
-    uint64_t rec_want = want_hits ? c->hs().n_recs + n / 40 + 65536 : 0;   // (the synthetic workloads: one hit per 60 bytes of text)
-    uint64_t host_want = c->hs().n_host + 4096;
+    ListSizes want = lists_first((c->gflags & SVJG_GRAPH_ALL_SLOW) != 0, want_hits != 0, n, c->hs());
     int rc;
     for (int attempt = 0; attempt < 3; ++attempt) {
-        if ((rc = ensure(c, (void **)&c->d_deferred, &c->deferred_cap, def_want, sizeof(uint64_t), false))) return rc;
-        if ((rc = ensure(c, (void **)&c->d_host, &c->host_cap, host_want, sizeof(uint64_t), true))) return rc;
-        if (want_hits && (rc = ensure(c, (void **)&c->d_recs, &c->rec_cap, rec_want, sizeof(svjg_hitrec), true))) return rc;
+        if ((rc = ensure(c, (void **)&c->d_deferred, &c->deferred_cap, want.deferred, sizeof(uint64_t), false))) return rc;
+        if ((rc = ensure(c, (void **)&c->d_host, &c->host_cap, want.host, sizeof(uint64_t), true))) return rc;
+        if (want_hits && (rc = ensure(c, (void **)&c->d_recs, &c->rec_cap, want.recs, sizeof(svjg_hitrec), true))) return rc;
         // snapshot so that an overflowed attempt can be rolled back
         HIPCHK(c, hipMemcpyAsync(c->d_snap, c->d_counts, counts_bytes(c), hipMemcpyDeviceToDevice, c->stream));
         DevStatus before = c->hs();
         if ((rc = reset_status(c, false))) return rc;
         ClassifyArgs a{};
-        uint32_t grid = 0;
-        size_t lds = 0;
-        main_launch_setup(c, begin, end, base_offset, want_hits, a, grid, lds);
-        if (!a.long_pre) { c->err = "no memory for the workers' scratch words"; return SVJG_E_NOMEM; }
+        uint32_t grid = 0;  size_t lds = 0;
+        if ((rc = main_launch_setup(c, step_targets(c), begin, end, base_offset, want_hits, a, grid, lds))) return rc;
 #ifdef SVJG_TIMING
         if (a.diag & 16u) HIPCHK(c, hipMemsetAsync(c->d_dbg, 0, 32 * 8, c->stream));
 #endif
-        HIPCHK(c, hipEventRecord(c->ev[0], c->stream));
-        hipLaunchKernelGGL(k_classify_main, dim3(grid), dim3(WG), lds, c->stream, a);
-        HIPCHK(c, hipGetLastError());
-        HIPCHK(c, hipEventRecord(c->ev[1], c->stream));
+        if ((rc = enqueue_main(c, c->stream, a, grid, lds, c->ev))) return rc;
         HIPCHK(c, hipMemcpyAsync(&c->hs(), c->d_st, sizeof(DevStatus), hipMemcpyDeviceToHost, c->stream));
         HIPCHK(c, hipStreamSynchronize(c->stream));
         const uint64_t n_def = c->hs().n_deferred;
 #ifdef SVJG_TIMING
-        if (a.diag & 16u) {
-            unsigned long long d[16];
-            HIPCHK(c, hipMemcpy(d, c->d_dbg, sizeof d, hipMemcpyDeviceToHost));
-            fprintf(stderr, "[svjg diag] sub-passes of long lines: first sweep counting %llu, first sweep measuring only %llu, second sweep %llu; nodes in sub-passes %llu\n", d[12], d[13], d[14], d[15]);
-            fprintf(stderr, "[svjg diag] wave time per phase (sum over waves, counter ticks)  A+B1 %llu  prefix %llu  B2 %llu  R1 %llu  NP: lists %llu  names+disp %llu  records %llu  scan+search %llu  links+atomics %llu  R6+end %llu;  passes %llu (sub-passes of long lines %llu), nodes in them %llu\n",
-                    d[0], d[1], d[2], d[3], d[8], d[9], d[4], 0ull, d[6], d[7], d[10], d[11], d[5]);
-        }
+        if ((a.diag & 16u) && (rc = timing_print_main(c))) return rc;
 #endif
         c->ms_slow = 0;
         if (n_def && !(c->hs().overflow & 1u)) {
@@ -642,16 +674,7 @@ static int classify_range(svjg_ctx *c, uint64_t begin, uint64_t end, uint64_t ba
             HIPCHK(c, hipStreamSynchronize(c->stream));
             HIPCHK(c, hipEventElapsedTime(&c->ms_slow, c->ev[2], c->ev[3]));
 #ifdef SVJG_TIMING
-            if (a.diag & 16u) {
-                unsigned long long d[8];
-                HIPCHK(c, hipMemcpy(d, c->d_dbg + 16, sizeof d, hipMemcpyDeviceToHost));
-                fprintf(stderr, "[svjg diag] one wave per line, the longest any line took per step (counter ticks): terminator + staging %llu  per-line part %llu  piece table %llu  nodes %llu  links %llu\n",
-                        d[0], d[1], d[2], d[3], d[4]);
-                unsigned long long l[5];
-                HIPCHK(c, hipMemcpy(l, c->d_dbg + 24, sizeof l, hipMemcpyDeviceToHost));
-                fprintf(stderr, "[svjg diag] one lane per line, ticks summed over the blocks of 64 lines: terminators + staging %llu  per-line part %llu  nodes %llu  links %llu  rest %llu\n",
-                        l[0], l[1], l[2], l[3], l[4]);
-            }
+            if ((a.diag & 16u) && (rc = timing_print_exact(c))) return rc;
 #endif
         }
         HIPCHK(c, hipEventElapsedTime(&c->ms_main, c->ev[0], c->ev[1]));
@@ -661,9 +684,7 @@ static int classify_range(svjg_ctx *c, uint64_t begin, uint64_t end, uint64_t ba
         }
         // roll back and retry with worst-case buffers
         if (attempt == 2) { c->err = "output buffers overflowed repeatedly"; return SVJG_E_NOMEM; }
-        if (c->hs().overflow & 1u) def_want = n / 24 + 64;
-        if (c->hs().overflow & 2u) rec_want = before.n_recs + (c->hs().n_recs - before.n_recs) * 2 + n / 24 + 64;
-        if (c->hs().overflow & 4u) host_want = before.n_host + n / 24 + 64;
+        want = lists_grown(want, n, before, c->hs());
         HIPCHK(c, hipMemcpyAsync(c->d_counts, c->d_snap, counts_bytes(c), hipMemcpyDeviceToDevice, c->stream));
         uint64_t keep_err = before.err;
         c->hs() = before; c->hs().err = keep_err;
@@ -1415,145 +1436,182 @@ static GenoArgs run_geno_args(svjg_ctx *c, const svjg_ctx::RunSlot &r, const Run
     return a;
 }
 
+// ---- svjg_run_begin's steps, in the order it takes them: what they enqueue, on which stream, is the design ----
+
+// (a slot's count vector, status block and max_n as what a k_step_reset or a k_classify_exact zeroes)
+static NextPass slot_reset_args(const svjg_ctx::RunSlot &s, const RunLayout &L, uint64_t words) {
+    return NextPass{s.counts, words, (DevStatus *)((uint8_t *)s.d + L.status), (unsigned int *)((uint8_t *)s.d + L.maxn)};
+}
+
+// the slot's own lists (no pass in flight uses this slot: the host has ended the pass that last did)
+static int pass_lists(svjg_ctx *c, svjg_ctx::RunSlot &r, uint64_t n) {
+    const ListSizes want = lists_fused((c->gflags & SVJG_GRAPH_ALL_SLOW) != 0, n);
+    if (const int rc = ensure(c, (void **)&r.deferred, &r.deferred_cap, want.deferred, sizeof(uint64_t), false)) return rc;
+    return ensure(c, (void **)&r.host, &r.host_cap, want.host, sizeof(uint64_t), false);
+}
+
+// The pass's form and compute stream (svjg_pass.h).  Overlapped: pass k on stream k mod 2 — k_step_reset of its OWN slot in one-wave blocks
+// (early: behind the main kernel of pass k - 2, beside that of pass k - 1), k_classify_main, the `computed` record, and nothing else: what
+// was deferred is settled by svjg_run_end.  Otherwise, as before r11: on c->stream, k_classify_exact behind the main kernel.
+static int pass_form_and_stream(svjg_ctx *c, svjg_ctx::RunSlot &r) {
+    r.overlapped = pass_overlaps(c->comm != nullptr, (c->gflags & SVJG_GRAPH_ALL_SLOW) != 0, kernel_ms_by_events(c), c->last_pass_deferred);
+    r.on = (r.overlapped && (c->pass_seq & 1)) ? c->stream2 : c->stream;
+    ++c->pass_seq;
+    r.chained = c->run_inflight > 0;
+    r.inflight = false; r.settled = false; r.geno_owed = false; r.ms_settle = 0;
+    if (!r.overlapped) return serial_enter(c);                    // (behind an overlapped pass on stream2: its `computed` is that stream's tail)
+    if (c->first_dirty) {                                         // stream2 behind what c->stream holds beside overlapped passes (a pass in the other form, a step-by-step call)
+        HIPCHK(c, hipEventRecord(c->ev_join[0], c->stream));
+        HIPCHK(c, hipStreamWaitEvent(c->stream2, c->ev_join[0], 0));
+        c->first_dirty = false;
+    }
+    if (r.on == c->stream2) c->second_busy = true;
+    return 0;
+}
+
+// k_step_reset of the pass's own slot, unless the pass before has zeroed it: an overlapped pass; the first pass behind svjg_set_rows /
+// svjg_load_graph, or behind a pass without text
+static void pass_reset(svjg_ctx::RunSlot &r, const RunLayout &L, uint64_t words) {
+    if (!r.clean) {
+        const uint32_t rb = r.overlapped ? 64u : TPB;            // (one-wave blocks find room beside fourteen classify workers a CU)
+        hipLaunchKernelGGL(k_step_reset, dim3(capped_grid(words, rb)), dim3(rb), 0, r.on, slot_reset_args(r, L, words));
+    }
+    r.clean = false;
+}
+
+#ifdef SVJG_ENDTIMES
+// measurement only: how long before the launch's last worker the others ended
+static int endtimes_print(svjg_ctx *c) {
+    static unsigned long long d[DBG_WORDS];
+    HIPCHK(c, hipMemcpy(d, c->d_dbg, sizeof d, hipMemcpyDeviceToHost));
+    const unsigned long long nw = d[ENDT_N], span = c->hs().t_last - c->hs().t_first;
+    const double us = c->wall_khz ? 1e3 / c->wall_khz : 0.0;
+    double q[3] = {0, 0, 0};                                  // quartiles of (t_last - end), from the histogram (bucket centres)
+    unsigned long long seen = 0;
+    for (uint32_t b = 0, k = 0; b < ENDT_BUCKETS && k < 3; ++b)
+        for (seen += d[ENDT_HIST + b]; k < 3 && seen * 4 >= nw * (k + 1) && nw; ++k) q[2 - k] = ((double)span - (b + 0.5) * ENDT_TICKS) * us;
+    fprintf(stderr, "[svjg endtimes] %llu workers, launch %.1f us; a worker ended before the last one: mean %.1f us, quartiles %.1f / %.1f / %.1f us; ended in the last 20/50/100/200 us:",
+            nw, span * us, nw ? ((double)span - (double)d[ENDT_SUM] / nw) * us : 0.0, q[0], q[1], q[2]);
+    for (const double w : {20.0, 50.0, 100.0, 200.0}) {
+        unsigned long long in = 0;
+        for (uint32_t b = 0; b < ENDT_BUCKETS; ++b) if (((double)span - (b + 1.0) * ENDT_TICKS) * us < w) in += d[ENDT_HIST + b];
+        fprintf(stderr, " %llu", in);
+    }
+    fprintf(stderr, "\n");
+    return 0;
+}
+#endif
+
+// k_classify_main over the whole resident text into the slot's targets; its arguments stay in r.cargs (the settle step's k_classify_exact takes
+// the same).  SVJG_KERNEL_MS=events: its time from an event pair around it, as before r07 (two barrier packets a pass; for comparing the two
+// clocks: svjg_last_main_ms).  Otherwise from the time stamps the kernel leaves in the pass's status block.
+static int pass_main(svjg_ctx *c, svjg_ctx::RunSlot &r, const RunLayout &L, uint64_t n) {
+    uint32_t grid = 0;  size_t lds = 0;
+    r.cargs = ClassifyArgs{};
+    if (const int rc = main_launch_setup(c, slot_targets(c, r, L), 0, n, r.base_offset, 0, r.cargs, grid, lds)) return rc;
+#ifdef SVJG_ENDTIMES
+    HIPCHK(c, hipMemsetAsync(c->d_dbg + ENDT_SUM, 0, (DBG_WORDS - ENDT_SUM) * 8, r.on));   // (one launch at a time: svjg_run_resident)
+#endif
+    return enqueue_main(c, r.on, r.cargs, grid, lds, r.timed_by_events ? r.ev : nullptr);
+}
+
+// Between this k_classify_main and the next pass's the compute stream carries ONE launch and ONE event record (`computed`):
+//   k_classify_exact  the exact path, the number of deferred lines read on the device (launch_exact above).  So whatever a shard defers
+//                     is counted before the pass's all-reduce; only a LIST that overflowed makes the pass repeat (svjg_pass.h).  The same
+//                     blocks zero what the NEXT pass starts from — the count vector, status block and max_n of the slot behind this
+//                     one, which no pass in flight uses: two are in flight at most, the slots are three — so the next pass launches no
+//                     k_step_reset.
+// Before r07 there were three launches (two exact-path kernels, k_step_reset) and three event records; the timeline of both:
+// profiles/r07/experiments/pass_tail.txt.
+// An OVERLAPPED pass has none of this: its stream carries k_step_reset, k_classify_main and `computed`, so that the next pass's workers —
+// on the other stream — move into the slots this one's vacate; 53 760 B of LDS a block would only be there when THAT pass drains.
+static int pass_exact_and_next(svjg_ctx *c, const svjg_ctx::RunSlot &r, const RunLayout &L, uint64_t words) {
+    svjg_ctx::RunSlot &nxt = c->run[(c->run_head + 1) % RUN_SLOTS];
+    const NextPass nx = (nxt.d && nxt.counts && nxt.counts_cap >= words) ? slot_reset_args(nxt, L, words) : NextPass{};
+    if (const int rc = launch_exact(c, r.cargs, FUSED_WAVE_ROUNDS, nx)) return rc;
+    nxt.clean = nx.counts != nullptr;
+    return 0;
+}
+
+// The count all-reduce of this pass — every rank issues its collectives in the same order, one per pass — runs on the compute
+// stream, between this pass's kernels and the next pass's: the classify kernel fills every CU (fourteen workers take 126 of a
+// CU's 128 LDS granules and all the registers of two SIMDs), so a collective's workgroups find no room beside it and one queued
+// on the second stream would only start when the NEXT pass's classify kernel drains — and hold back this pass's results, which
+// the host waits for before it may enqueue the pass after.  (SVJG_ALLREDUCE_STREAM=second puts it there all the same: for a
+// measurement on a multi-GPU box.)
+static bool allreduce_on_second(const svjg_ctx *c) {
+    static const bool env_second = [] { const char *e = getenv("SVJG_ALLREDUCE_STREAM"); return e && !strcmp(e, "second"); }();
+    return env_second || c->allreduce_second;
+}
+static int pass_allreduce(svjg_ctx *c, svjg_ctx::RunSlot &r, const RunLayout &L, hipStream_t st) {
+    // (the exact-path kernel's interval must not hold the collective: under a communicator it gets an end event of its own — 6 us of a
+    //  multi-GPU pass, none of a one-GPU pass, whose interval `computed` ends)
+    if (st == c->stream && r.had_text && r.timed_by_events) { HIPCHK(c, hipEventRecord(r.ev[2], c->stream)); r.slow_end_own = true; }
+    if (const int rc = launch_guard(c, r.counts, st, (DevStatus *)((uint8_t *)r.d + L.status))) return rc;   // (guard word 2: "this rank's lists overflowed")
+    ncclResult_t nr = ncclAllReduce(r.counts, r.counts, (size_t)c->n_slots + GUARD_WORDS, ncclUint64, ncclSum, c->comm, st);
+    if (nr != ncclSuccess) { c->err = std::string("ncclAllReduce: ") + ncclGetErrorString(nr); return SVJG_E_RCCL; }
+    HIPCHK(c, hipMemcpyAsync((uint8_t *)r.d + L.guard, r.counts + c->n_slots, GUARD_WORDS * 8, hipMemcpyDeviceToDevice, st));
+    return 0;
+}
+
+// SVJG_GENO_GRID / SVJG_GENO_BLOCK: measurement only (read at every pass)
+static void geno_grid_override(uint32_t &gb, uint32_t &gg) {
+    if (const char *e = getenv("SVJG_GENO_BLOCK")) if (atoi(e) > 0) gb = (uint32_t)atoi(e);
+    if (const char *e = getenv("SVJG_GENO_GRID")) if (atoi(e) > 0) gg = (uint32_t)atoi(e);
+}
+// Behind `computed`, on the second (low-priority) stream, the genotypes: one wave per CU (see k_genotype) fits beside the classify workers;
+// the kernel writes its results straight into the pinned host block — they cross PCIe as they are produced —, which takes ~45 us for
+// 100 k rows.  Meanwhile the compute stream already runs the next pass (that one zeroes and fills ITS count vector).
+static int pass_genotypes(svjg_ctx *c, svjg_ctx::RunSlot &r, const GenoArgs &ga, uint64_t n_rows) {
+    HIPCHK(c, hipEventRecord(r.ev[4], c->copy_stream));
+    uint32_t gb = 64, gg = (uint32_t)c->n_cu;
+    geno_grid_override(gb, gg);
+    if (gb > TPB) gb = TPB;
+    if ((uint64_t)gg * gb > n_rows + gb) gg = (uint32_t)((n_rows + gb - 1) / gb);
+    hipLaunchKernelGGL(k_genotype, dim3(gg), dim3(gb), 0, c->copy_stream, ga);
+    HIPCHK(c, hipGetLastError());
+    HIPCHK(c, hipEventRecord(r.ev[5], c->copy_stream));
+    return 0;
+}
+
+// the pass's tail: max_n, status, guard words — one wave that writes them into the mapped host block, as k_genotype does its results (a
+// hipMemcpyAsync here is the runtime's copy kernel, whose 256-thread blocks wait for the next pass's classify kernel to drain); then `copied`
+static int pass_tail(svjg_ctx *c, svjg_ctx::RunSlot &r, const RunLayout &L) {
+    static_assert(sizeof(DevStatus) % 8 == 0, "the tail is copied in 8-byte words");
+    hipLaunchKernelGGL(k_pass_tail, dim3(1), dim3(64), 0, c->copy_stream, (unsigned long long *)((uint8_t *)r.h_dev + L.h_tail), (const unsigned long long *)r.d, (uint32_t)(L.tail_bytes / 8));
+    HIPCHK(c, hipGetLastError());
+    HIPCHK(c, hipEventRecord(r.copied, c->copy_stream));
+    return 0;
+}
+
 extern "C" int svjg_run_begin(svjg_ctx *c, uint64_t base_offset, uint32_t min_support, double err) {
     if (!c) return SVJG_E_ARG;
     if (!c->have_graph || !c->have_gaf) { c->err = "svjg_run_begin needs a graph and an uploaded GAF"; return SVJG_E_ARG; }
     if (!c->have_rows) { c->err = "svjg_set_rows has not been called"; return SVJG_E_ARG; }
     if (c->run_inflight >= 2) { c->err = "two passes are in flight: svjg_run_end first"; return SVJG_E_ARG; }
     HIPCHK(c, hipSetDevice(c->device));
-    const uint64_t n = c->gaf_bytes, n_rows = c->run_rows;
+    const uint64_t n = c->gaf_bytes, n_rows = c->run_rows, words = (uint64_t)c->n_slots + GUARD_WORDS;
     const RunLayout L = run_layout(n_rows);
     svjg_ctx::RunSlot &r = c->run[c->run_head];
     int rc;
-    // the slot's own lists (no pass in flight uses this slot: the host has ended the pass that last did)
-    if ((rc = ensure(c, (void **)&r.deferred, &r.deferred_cap, deferred_want(c, n), sizeof(uint64_t), false))) return rc;
-    if ((rc = ensure(c, (void **)&r.host, &r.host_cap, 4096, sizeof(uint64_t), false))) return rc;
+    if ((rc = pass_lists(c, r, n))) return rc;
     if (c->logfact_n == 0 && (rc = build_logfact(c, logfact_first()))) return rc;
-    // The pass's form and compute stream (svjg_pass.h).  Overlapped: pass k on stream k mod 2 — k_step_reset of its OWN slot in one-wave blocks
-    // (early: behind the main kernel of pass k - 2, beside that of pass k - 1), k_classify_main, the `computed` record, and nothing else: what
-    // was deferred is settled by svjg_run_end.  Otherwise, as before r11: on c->stream, k_classify_exact behind the main kernel.
-    const bool all_slow = (c->gflags & SVJG_GRAPH_ALL_SLOW) != 0;
-    r.overlapped = pass_overlaps(c->comm != nullptr, all_slow, kernel_ms_by_events(c), c->last_pass_deferred);
-    r.on = (r.overlapped && (c->pass_seq & 1)) ? c->stream2 : c->stream;
-    ++c->pass_seq;
-    r.chained = c->run_inflight > 0;
-    r.inflight = false; r.settled = false; r.geno_owed = false; r.ms_settle = 0;
-    if (r.overlapped) {
-        if (c->first_dirty) {                                     // stream2 behind what c->stream holds beside overlapped passes (a pass in the other form, a step-by-step call)
-            HIPCHK(c, hipEventRecord(c->ev_join[0], c->stream));
-            HIPCHK(c, hipStreamWaitEvent(c->stream2, c->ev_join[0], 0));
-            c->first_dirty = false;
-        }
-        if (r.on == c->stream2) c->second_busy = true;
-    } else if ((rc = serial_enter(c))) return rc;                 // (behind an overlapped pass on stream2: its `computed` is that stream's tail)
-    const hipStream_t on = r.on;
+    if ((rc = pass_form_and_stream(c, r))) return rc;
     r.base_offset = base_offset; r.min_support = min_support; r.err = err;
-    uint8_t *base = (uint8_t *)r.d;
-    DevStatus *d_st = (DevStatus *)(base + L.status);             // (the pass's own status block: its tail goes to the host in one small copy)
-    if (r.counts_cap < (uint64_t)c->n_slots + GUARD_WORDS) { c->err = "svjg_set_rows must follow svjg_load_graph"; return SVJG_E_ARG; }
-    GenoArgs ga = run_geno_args(c, r, L, min_support, err, r.counts);
-    const uint64_t words = (uint64_t)c->n_slots + GUARD_WORDS;
-    if (!r.clean) {                                           // an overlapped pass; the first pass behind svjg_set_rows / svjg_load_graph, or behind a pass without text
-        const uint32_t rb = r.overlapped ? 64u : TPB;            // (one-wave blocks find room beside fourteen classify workers a CU)
-        const uint64_t rg = (words + rb - 1) / rb;
-        hipLaunchKernelGGL(k_step_reset, dim3(rg > 1024 ? 1024u : rg < 1 ? 1u : (uint32_t)rg), dim3(rb), 0, on, NextPass{r.counts, words, d_st, ga.max_n});
-    }
-    r.clean = false;
-    // SVJG_KERNEL_MS=events: k_classify_main's time from an event pair around it, as before r07 (two barrier packets a pass; for
-    // comparing the two clocks: svjg_last_main_ms).  Otherwise from the time stamps the kernel leaves in the pass's status block.
-    r.timed_by_events = kernel_ms_by_events(c);
-    if (n) {
-        ClassifyArgs a{};
-        uint32_t grid = 0;
-        size_t lds = 0;
-        main_launch_setup(c, 0, n, base_offset, 0, a, grid, lds);
-        if (!a.long_pre) { c->err = "no memory for the workers' scratch words"; return SVJG_E_NOMEM; }
-        // what this launch may NOT share with the main kernel of the pass beside it: count vector and status block (the slot's), the two lists
-        // (the slot's), the workers' scratch words (the stream's).  Text and graph tables are read-only; hit records are not written (want_hits 0).
-        a.st = d_st; a.counts = r.counts;
-        a.deferred = r.deferred; a.deferred_cap = r.deferred_cap; a.host_lines = r.host; a.host_cap = r.host_cap;
-        if (on == c->stream2) {                                   // (the second block of scratch words: only a context that overlaps passes has one)
-            if (!c->d_long2 && hipMalloc((void **)&c->d_long2, (uint64_t)c->n_cu * (uint64_t)c->occ_main * LONG_WORDS * sizeof(uint32_t)) != hipSuccess) c->d_long2 = nullptr;
-            if (!c->d_long2) { (void)hipGetLastError(); c->err = "no memory for the workers' scratch words"; return SVJG_E_NOMEM; }
-            a.long_pre = c->d_long2;
-        }
-        r.cargs = a;
-#ifdef SVJG_ENDTIMES
-        HIPCHK(c, hipMemsetAsync(c->d_dbg + ENDT_SUM, 0, (DBG_WORDS - ENDT_SUM) * 8, on));   // (one launch at a time: svjg_run_resident)
-#endif
-        if (r.timed_by_events) HIPCHK(c, hipEventRecord(r.ev[0], on));
-        hipLaunchKernelGGL(k_classify_main, dim3(grid), dim3(WG), lds, on, a);
-        HIPCHK(c, hipGetLastError());
-        if (r.timed_by_events) HIPCHK(c, hipEventRecord(r.ev[1], on));
-        // Between this k_classify_main and the next pass's the compute stream carries ONE launch and ONE event record (`computed`):
-        //   k_classify_exact  the exact path, the number of deferred lines read on the device (launch_exact above).  So whatever a shard defers
-        //                     is counted before the pass's all-reduce; only a LIST that overflowed makes the pass repeat (svjg_pass.h).  The same
-        //                     blocks zero what the NEXT pass starts from — the count vector, status block and max_n of the slot behind this
-        //                     one, which no pass in flight uses: two are in flight at most, the slots are three — so the next pass launches no
-        //                     k_step_reset.
-        // Before r07 there were three launches (two exact-path kernels, k_step_reset) and three event records; the timeline of both:
-        // profiles/r07/experiments/pass_tail.txt.
-        // An OVERLAPPED pass has none of this: its stream carries k_step_reset, k_classify_main and `computed`, so that the next pass's workers —
-        // on the other stream — move into the slots this one's vacate; 53 760 B of LDS a block would only be there when THAT pass drains.
-        if (!r.overlapped) {
-            svjg_ctx::RunSlot &nxt = c->run[(c->run_head + 1) % RUN_SLOTS];
-            NextPass nx{};
-            if (nxt.d && nxt.counts && nxt.counts_cap >= words) {
-                nx.counts = nxt.counts; nx.n_words = words; nx.st = (DevStatus *)((uint8_t *)nxt.d + L.status); nx.max_n = (unsigned int *)((uint8_t *)nxt.d + L.maxn);
-            }
-            if ((rc = launch_exact(c, a, FUSED_WAVE_ROUNDS, nx))) return rc;
-            nxt.clean = nx.counts != nullptr;
-        }
-    }
-    // The count all-reduce of this pass — every rank issues its collectives in the same order, one per pass — runs on the compute
-    // stream, between this pass's kernels and the next pass's: the classify kernel fills every CU (fourteen workers take 126 of a
-    // CU's 128 LDS granules and all the registers of two SIMDs), so a collective's workgroups find no room beside it and one queued
-    // on the second stream would only start when the NEXT pass's classify kernel drains — and hold back this pass's results, which
-    // the host waits for before it may enqueue the pass after.  (SVJG_ALLREDUCE_STREAM=second puts it there all the same: for a
-    // measurement on a multi-GPU box.)  Then, behind an event, on the second (low-priority) stream, the genotypes: one wave per CU
-    // fits beside the classify workers; the kernel writes its results straight into the pinned host block — they cross PCIe as they
-    // are produced —, which takes ~45 us for 100 k rows.  Meanwhile the compute stream already runs the next pass (that one zeroes
-    // and fills ITS count vector).
-    static const bool env_second = [] { const char *e = getenv("SVJG_ALLREDUCE_STREAM"); return e && !strcmp(e, "second"); }();
-    const bool allreduce_second = env_second || c->allreduce_second;
-    auto reduce_on = [&](hipStream_t st) -> int {
-        int rc2 = launch_guard(c, r.counts, st, d_st);                  // (guard word 2: "this rank's lists overflowed")
-        if (rc2) return rc2;
-        ncclResult_t nr = ncclAllReduce(r.counts, r.counts, (size_t)c->n_slots + GUARD_WORDS, ncclUint64, ncclSum, c->comm, st);
-        if (nr != ncclSuccess) { c->err = std::string("ncclAllReduce: ") + ncclGetErrorString(nr); return SVJG_E_RCCL; }
-        HIPCHK(c, hipMemcpyAsync(base + L.guard, r.counts + c->n_slots, GUARD_WORDS * 8, hipMemcpyDeviceToDevice, st));
-        return 0;
-    };
-    r.slow_end_own = false;
-    if (c->comm && !allreduce_second) {
-        // (the exact-path kernel's interval must not hold the collective: under a communicator it gets an end event of its own — 6 us of a
-        //  multi-GPU pass, none of a one-GPU pass, whose interval `computed` ends)
-        if (n && r.timed_by_events) { HIPCHK(c, hipEventRecord(r.ev[2], c->stream)); r.slow_end_own = true; }
-        if ((rc = reduce_on(c->stream))) return rc;
-    }
-    HIPCHK(c, hipEventRecord(r.computed, on));
+    r.had_text = n != 0; r.timed_by_events = kernel_ms_by_events(c); r.slow_end_own = false;
+    if (r.counts_cap < words) { c->err = "svjg_set_rows must follow svjg_load_graph"; return SVJG_E_ARG; }
+    pass_reset(r, L, words);
+    if (n && (rc = pass_main(c, r, L, n))) return rc;
+    if (n && !r.overlapped && (rc = pass_exact_and_next(c, r, L, words))) return rc;
+    const bool second = allreduce_on_second(c);
+    if (c->comm && !second && (rc = pass_allreduce(c, r, L, c->stream))) return rc;
+    HIPCHK(c, hipEventRecord(r.computed, r.on));
     HIPCHK(c, hipStreamWaitEvent(c->copy_stream, r.computed, 0));
-    if (c->comm && allreduce_second && (rc = reduce_on(c->copy_stream))) return rc;
-    if (n_rows) {
-        HIPCHK(c, hipEventRecord(r.ev[4], c->copy_stream));
-        // one wave per CU (see k_genotype); SVJG_GENO_GRID / SVJG_GENO_BLOCK: measurement only
-        uint32_t gb = 64, gg = (uint32_t)c->n_cu;
-        { const char *e = getenv("SVJG_GENO_BLOCK"); if (e && atoi(e) > 0) gb = (uint32_t)atoi(e); }
-        { const char *e = getenv("SVJG_GENO_GRID"); if (e && atoi(e) > 0) gg = (uint32_t)atoi(e); }
-        if (gb > TPB) gb = TPB;
-        if ((uint64_t)gg * gb > n_rows + gb) gg = (uint32_t)((n_rows + gb - 1) / gb);
-        hipLaunchKernelGGL(k_genotype, dim3(gg), dim3(gb), 0, c->copy_stream, ga);
-        HIPCHK(c, hipGetLastError());
-        HIPCHK(c, hipEventRecord(r.ev[5], c->copy_stream));
-    }
-    // the pass's tail: max_n, status, guard words — one wave that writes them into the mapped host block, as k_genotype does its results (a
-    // hipMemcpyAsync here is the runtime's copy kernel, whose 256-thread blocks wait for the next pass's classify kernel to drain)
-    static_assert(sizeof(DevStatus) % 8 == 0, "the tail is copied in 8-byte words");
-    hipLaunchKernelGGL(k_pass_tail, dim3(1), dim3(64), 0, c->copy_stream, (unsigned long long *)((uint8_t *)r.h_dev + L.h_tail), (const unsigned long long *)r.d, (uint32_t)(L.tail_bytes / 8));
-    HIPCHK(c, hipGetLastError());
-    HIPCHK(c, hipEventRecord(r.copied, c->copy_stream));
+    if (c->comm && second && (rc = pass_allreduce(c, r, L, c->copy_stream))) return rc;
+    if (n_rows && (rc = pass_genotypes(c, r, run_geno_args(c, r, L, min_support, err, r.counts), n_rows))) return rc;
+    if ((rc = pass_tail(c, r, L))) return rc;
     c->counts_in_slot = c->run_head;
-    r.had_text = n != 0; r.inflight = true;
+    r.inflight = true;
     c->run_head = (c->run_head + 1) % RUN_SLOTS; ++c->run_inflight;
     return 0;
 }
@@ -1582,6 +1640,59 @@ static int settle_pass(svjg_ctx *c, svjg_ctx::RunSlot &r) {
     return 0;
 }
 
+// ---- svjg_run_end's steps ----
+
+// The finished pass's times.  By the device's clock: first worker's start to last worker's end, and from there to the end of the last block of
+// the exact path that had work (never the all-reduce).  wall_clock64() counts at wall_khz.
+static int pass_times(svjg_ctx *c, svjg_ctx::RunSlot &r) {
+    c->ms_slow = 0;
+    if (!r.had_text) return 0;
+    const DevStatus &t = c->hs();
+    const float per_tick = c->wall_khz ? 1.0f / (float)c->wall_khz : 0.0f;
+    // (overlapped launches: the interval this one shares with the pass in front of it counts once — pass_main_ticks)
+    c->ms_main_stamps = (float)pass_main_ticks(t.t_first, t.t_last, r.chained ? c->prev_t_last : 0) * per_tick;
+    c->prev_t_last = t.t_last;
+    c->ms_main_events = 0;
+    c->ms_main = c->ms_main_stamps;
+    if (r.geno_owed) c->ms_slow = r.ms_settle;            // (the settle step's launch, long behind t_last)
+    else if (t.n_deferred && t.t_exact > t.t_last) c->ms_slow = (float)(t.t_exact - t.t_last) * per_tick;
+    if (r.timed_by_events) {
+        HIPCHK(c, hipEventElapsedTime(&c->ms_main_events, r.ev[0], r.ev[1]));
+        c->ms_main = c->ms_main_events;
+        if (t.n_deferred) HIPCHK(c, hipEventElapsedTime(&c->ms_slow, r.ev[1], r.slow_end_own ? r.ev[2] : r.computed));   // (the exact-path kernel alone: never the all-reduce)
+    }
+#ifdef SVJG_ENDTIMES
+    if (const int rc = endtimes_print(c)) return rc;
+#endif
+    return 0;
+}
+
+// What the host would have decided in between: repeat the pass, let it stand, or refuse it.  `gd`: the pass's guard words (meaningful under
+// a communicator: the sums over the ranks).  repeated: the pass was repeated step by step, its counts are in d_counts.
+static int pass_verdict(svjg_ctx *c, const svjg_ctx::RunSlot &r, const unsigned long long *gd, uint64_t n, bool &repeated) {
+    repeated = false;
+    if (pass_repeats(c->comm != nullptr, c->hs().overflow, gd[GUARD_REPEAT])) {
+        // a list of this rank — or, under a communicator, of ANY rank (svjg_pass.h: the ranks decide together, so all of them issue the
+        // one more all-reduce below) — was too short: the pass again, step by step (classify_range sizes the lists and
+        // retries), behind whatever is enqueued already.  The all-reduce is issued even when this rank's text turns out to be malformed:
+        // its peers are waiting in theirs.
+        int rc;
+        if ((rc = svjg_reset_counts(c))) return rc;
+        rc = classify_range(c, 0, n, r.base_offset, 0);
+        if (rc && rc != SVJG_E_INPUT) return rc;
+        if (c->comm) { const std::string keep = c->err; const int rc2 = svjg_allreduce_counts(c); if (rc2 && !rc) return rc2; if (rc) c->err = keep; }
+        if (rc) return rc;
+        repeated = true;
+    } else {
+        c->total_deferred = c->hs().n_deferred;
+        if (c->hs().err != ~0ull) return SVJG_E_INPUT;
+        if (c->comm && pass_counts_overflowed(gd[GUARD_MAX_REF], gd[GUARD_MAX_ALT])) { c->err = "more than 2^32 informative alignments for one SV"; return SVJG_E_OVERFLOW; }
+    }
+    // (either way: lines the kernels set aside for the host are neither counted nor fatal — the caller has to know)
+    if (c->hs().n_host) { c->err = "the text holds lines only the host can decide (non-ASCII digits in a decimal column: svjg_get_host_lines); classify it with svjg_classify"; return SVJG_E_ARG; }
+    return 0;
+}
+
 extern "C" int svjg_run_end(svjg_ctx *c, const uint8_t **gt, const int32_t **pl, const uint32_t **raw, const uint8_t **flags, const uint8_t **boundary) {
     if (!c || !gt || !pl || !raw || !flags || !boundary) return SVJG_E_ARG;
     *gt = nullptr; *pl = nullptr; *raw = nullptr; *flags = nullptr; *boundary = nullptr;
@@ -1598,79 +1709,21 @@ extern "C" int svjg_run_end(svjg_ctx *c, const uint8_t **gt, const int32_t **pl,
     if ((rc = settle_pass(c, r))) return rc;                               // (an overlapped pass that deferred lines: one more; nothing if somebody asked for its counts before)
     const uint8_t *tail = hb + L.h_tail;
     c->hs() = *(const DevStatus *)(tail + L.status);
-    // ---- what the host would have decided in between ----
-    c->ms_slow = 0;
-    if (r.had_text) {
-        // the device's clock: first worker's start to last worker's end, and from there to the end of the last block of the exact path
-        // that had work (never the all-reduce).  wall_clock64() counts at wall_khz.
-        const DevStatus &t = c->hs();
-        const float per_tick = c->wall_khz ? 1.0f / (float)c->wall_khz : 0.0f;
-        // (overlapped launches: the interval this one shares with the pass in front of it counts once — pass_main_ticks)
-        c->ms_main_stamps = (float)pass_main_ticks(t.t_first, t.t_last, r.chained ? c->prev_t_last : 0) * per_tick;
-        c->prev_t_last = t.t_last;
-        c->ms_main_events = 0;
-        c->ms_main = c->ms_main_stamps;
-        if (r.geno_owed) c->ms_slow = r.ms_settle;            // (the settle step's launch, long behind t_last)
-        else if (t.n_deferred && t.t_exact > t.t_last) c->ms_slow = (float)(t.t_exact - t.t_last) * per_tick;
-        if (r.timed_by_events) {
-            HIPCHK(c, hipEventElapsedTime(&c->ms_main_events, r.ev[0], r.ev[1]));
-            c->ms_main = c->ms_main_events;
-            if (t.n_deferred) HIPCHK(c, hipEventElapsedTime(&c->ms_slow, r.ev[1], r.slow_end_own ? r.ev[2] : r.computed));   // (the exact-path kernel alone: never the all-reduce)
-        }
-    }
-#ifdef SVJG_ENDTIMES
-    if (r.had_text) {                                             // measurement only: how long before the launch's last worker the others ended
-        static unsigned long long d[DBG_WORDS];
-        HIPCHK(c, hipMemcpy(d, c->d_dbg, sizeof d, hipMemcpyDeviceToHost));
-        const unsigned long long nw = d[ENDT_N], span = c->hs().t_last - c->hs().t_first;
-        const double us = c->wall_khz ? 1e3 / c->wall_khz : 0.0;
-        double q[3] = {0, 0, 0};                                  // quartiles of (t_last - end), from the histogram (bucket centres)
-        unsigned long long seen = 0;
-        for (uint32_t b = 0, k = 0; b < ENDT_BUCKETS && k < 3; ++b)
-            for (seen += d[ENDT_HIST + b]; k < 3 && seen * 4 >= nw * (k + 1) && nw; ++k) q[2 - k] = ((double)span - (b + 0.5) * ENDT_TICKS) * us;
-        fprintf(stderr, "[svjg endtimes] %llu workers, launch %.1f us; a worker ended before the last one: mean %.1f us, quartiles %.1f / %.1f / %.1f us; ended in the last 20/50/100/200 us:",
-                nw, span * us, nw ? ((double)span - (double)d[ENDT_SUM] / nw) * us : 0.0, q[0], q[1], q[2]);
-        for (const double w : {20.0, 50.0, 100.0, 200.0}) {
-            unsigned long long in = 0;
-            for (uint32_t b = 0; b < ENDT_BUCKETS; ++b) if (((double)span - (b + 1.0) * ENDT_TICKS) * us < w) in += d[ENDT_HIST + b];
-            fprintf(stderr, " %llu", in);
-        }
-        fprintf(stderr, "\n");
-    }
-#endif
+    if ((rc = pass_times(c, r))) return rc;
     if (n_rows) HIPCHK(c, hipEventElapsedTime(&c->ms_geno, r.ev[4], r.ev[5]));
     c->last_pass_deferred = r.had_text && c->hs().n_deferred != 0;
     c->host_lines_src = r.host; c->host_lines_cap = r.host_cap;
-    bool repeated = false;                                        // the pass was repeated step by step: its counts are in d_counts
-    bool again = false;                                           // the genotypes are owed once more (a repeated pass, a settle step)
-    const unsigned long long *gd = (const unsigned long long *)(tail + L.guard);   // (meaningful under a communicator: the sums over the ranks)
-    if (pass_repeats(c->comm != nullptr, c->hs().overflow, gd[GUARD_REPEAT])) {
-        // a list of this rank — or, under a communicator, of ANY rank (svjg_pass.h: the ranks decide together, so all of them issue the
-        // one more all-reduce below) — was too short: the pass again, step by step (classify_range sizes the lists and
-        // retries), behind whatever is enqueued already.  The all-reduce is issued even when this rank's text turns out to be malformed:
-        // its peers are waiting in theirs.
-        if ((rc = svjg_reset_counts(c))) return rc;
-        rc = classify_range(c, 0, n, r.base_offset, 0);
-        if (rc && rc != SVJG_E_INPUT) return rc;
-        if (c->comm) { const std::string keep = c->err; const int rc2 = svjg_allreduce_counts(c); if (rc2 && !rc) return rc2; if (rc) c->err = keep; }
-        if (rc) return rc;
-        again = true; repeated = true;
-    } else {
-        again = r.geno_owed;
-        c->total_deferred = c->hs().n_deferred;
-        if (c->hs().err != ~0ull) return SVJG_E_INPUT;
-        if (c->comm && pass_counts_overflowed(gd[GUARD_MAX_REF], gd[GUARD_MAX_ALT])) { c->err = "more than 2^32 informative alignments for one SV"; return SVJG_E_OVERFLOW; }
-    }
-    // (either way: lines the kernels set aside for the host are neither counted nor fatal — the caller has to know)
-    if (c->hs().n_host) { c->err = "the text holds lines only the host can decide (non-ASCII digits in a decimal column: svjg_get_host_lines); classify it with svjg_classify"; return SVJG_E_ARG; }
-    if (n_rows) {
+    bool repeated = false;
+    if ((rc = pass_verdict(c, r, (const unsigned long long *)(tail + L.guard), n, repeated))) return rc;
+    if (n_rows) {                                                 // the genotypes once more where they are owed: a repeated pass, a settle step, a log10(i!) table too short
         GenoArgs ga = run_geno_args(c, r, L, r.min_support, r.err, repeated ? c->d_counts : r.counts);
         uint8_t *h_maxn = hb + L.h_tail + L.maxn;                 // (the results are already in the mapped host block: only the pair comes back)
-        if ((rc = settle_launch(c, (const unsigned int *)h_maxn, h_maxn, (const uint8_t *)r.d + L.maxn, 8, again, [&] { return launch_genotype(c, ga); }))) return rc;
+        if ((rc = settle_launch(c, (const unsigned int *)h_maxn, h_maxn, (const uint8_t *)r.d + L.maxn, 8, repeated || r.geno_owed, [&] { return launch_genotype(c, ga); }))) return rc;
     }
     *pl = (const int32_t *)(hb + L.pl32); *raw = (const uint32_t *)(hb + L.raw); *gt = hb + L.gt; *flags = hb + L.flags; *boundary = hb + L.boundary;
     return 0;
 }
+
 
 extern "C" int svjg_run_resident(svjg_ctx *c, uint64_t base_offset, uint32_t min_support, double err,
                                  const uint8_t **gt, const int32_t **pl, const uint32_t **raw, const uint8_t **flags, const uint8_t **boundary) {

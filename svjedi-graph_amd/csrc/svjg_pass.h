@@ -1,5 +1,6 @@
 // What a finished fused pass (svjg_run_begin / svjg_run_end) means for the ranks of a job — host logic shared by libsvjg_hip.so
-// and the CPU harness (tests/hostsim), so that the decision the ranks must take TOGETHER is tested where there is no GPU.
+// and the CPU harness (tests/hostsim), so that the decision the ranks must take TOGETHER is tested where there is no GPU.  Further down, in
+// the same spirit: how one k_classify_main launch divides the text among its workers and how long its lists are (main_plan, ListSizes).
 //
 // A pass enqueues, with no host round trip: k_classify_main, k_classify_exact (the exact path: it reads the number of deferred
 // lines on the device and takes its wave role, one wave per line, up to `wave_limit` lines, its lane role, one lane per line,
@@ -74,6 +75,53 @@ inline uint64_t pass_main_ticks(uint64_t t_first, uint64_t t_last, uint64_t prev
     const uint64_t from = prev_t_last > t_first ? prev_t_last : t_first;
     return t_last > from ? t_last - from : 0;
 }
+
+// ---- one k_classify_main launch: how the text is divided among its workers, how long its lists are ----
+// (the kernel's constants come in as arguments: this header knows no kernel)
+
+// Workgroups of k_classify_main one CU holds: what the occupancy API says, capped by the LDS.  LDS is handed out in units of `granule`
+// bytes (measured: a 15 568-byte workgroup is admitted 9 times per CU where the API says 10); a worker too many would run in a second
+// round behind the others.
+inline int main_occupancy(int api, uint64_t lds, uint64_t granule) {
+    const int by_lds = (int)((160u * 1024u) / ((lds + granule - 1) / granule * granule));
+    return by_lds >= 1 && api > by_lds ? by_lds : api;
+}
+
+// One worker (wave) per resident slot, `workers` = CUs x main_occupancy of them; every worker owns the lines starting in its region of
+// the text.  A worker's first chunk is most of an even share (`first_share` of it), fixed; what is left goes in chunks of `small_chunk`
+// bytes to whoever is free next (svjg_kernels.h: the workers of a CU do not run equally fast).  Inputs too small for that — an even
+// share below 8 chunks —: even shares, small = 0.  Smaller still: regions of one `stripe`, fewer workers.
+struct MainPlan { uint64_t region, small; uint32_t grid; };
+inline MainPlan main_plan(uint64_t n_bytes, uint64_t workers, uint64_t stripe, uint64_t small_chunk, double first_share) {
+    MainPlan p;
+    const uint64_t share = (n_bytes + workers - 1) / workers;
+    p.region = (share + 15) & ~15ull;
+    p.small = 0;
+    if (share >= 8 * small_chunk) { p.region = ((uint64_t)(share * first_share) + 15) & ~15ull; p.small = small_chunk; }
+    if (p.region < stripe) p.region = stripe;
+    const uint64_t want_grid = (n_bytes + p.region - 1) / p.region;
+    p.grid = (uint32_t)(want_grid < workers ? want_grid : workers);
+    return p;
+}
+
+// Entries of the three lists a launch over n bytes of text appends to: deferred lines, hit records, lines for the host.
+struct ListSizes { uint64_t deferred, recs, host; };
+inline uint64_t deferred_want(bool all_slow, uint64_t n) { return all_slow ? n / 24 + 64 : (n / 4096 + 65536); }
+// a step-by-step call's first attempt; `now`: the status before it (hit records and host lines add up over the calls)
+inline ListSizes lists_first(bool all_slow, bool want_hits, uint64_t n, const DevStatus &now) {
+    return ListSizes{deferred_want(all_slow, n),
+                     want_hits ? now.n_recs + n / 40 + 65536 : 0,      // (the synthetic workloads: one hit per 60 bytes of text)
+                     now.n_host + 4096};
+}
+// ... and what an attempt that ended with overflow bits is repeated with: worst-case lists (before, after: the status around the attempt)
+inline ListSizes lists_grown(ListSizes s, uint64_t n, const DevStatus &before, const DevStatus &after) {
+    if (after.overflow & 1u) s.deferred = n / 24 + 64;
+    if (after.overflow & 2u) s.recs = before.n_recs + (after.n_recs - before.n_recs) * 2 + n / 24 + 64;
+    if (after.overflow & 4u) s.host = before.n_host + n / 24 + 64;
+    return s;
+}
+// a fused pass's own lists: no hit records, a fixed list of lines for the host (one that overflows repeats the pass step by step)
+inline ListSizes lists_fused(bool all_slow, uint64_t n) { return ListSizes{deferred_want(all_slow, n), 0, 4096}; }
 
 // 32-bit halves of the packed ref | alt << 32 counters cannot have carried into each other iff the SUMS of the ranks' maxima fit
 inline bool pass_counts_overflowed(uint64_t guard_max_ref_sum, uint64_t guard_max_alt_sum) {

@@ -1,10 +1,11 @@
-"""Build + call the host harness of the overlapped fused pass's decisions (svjedi-graph_amd/csrc/svjg_pass.h; tests only)."""
+"""Build + call the host harness of the fused pass's decisions and of a classify launch's plan (svjedi-graph_amd/csrc/svjg_pass.h; tests only)."""
 import ctypes
 import os
 import subprocess
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 SO = os.path.join(HERE, "_overlapsim.so")
+MAIN = os.path.join(HERE, "_overlapsim_main")
 
 
 def build():
@@ -12,6 +13,45 @@ def build():
     if not os.path.exists(SO) or os.path.getmtime(SO) < max(os.path.getmtime(s) for s in src):
         subprocess.run(["g++", "-O2", "-std=c++17", "-Wall", "-shared", "-fPIC", "-o", SO, src[0]], check=True)
     return SO
+
+
+def build_main():
+    """the stand-alone program under AddressSanitizer and UBSan (its own main: nothing is preloaded into anything)"""
+    src = [os.path.join(HERE, "overlap_sim.cpp"), os.path.join(HERE, "..", "..", "svjedi-graph_amd", "csrc", "svjg_pass.h")]
+    if not os.path.exists(MAIN) or os.path.getmtime(MAIN) < max(os.path.getmtime(s) for s in src):
+        subprocess.run(["g++", "-O1", "-g", "-std=c++17", "-Wall", "-DOVERLAP_SIM_MAIN", "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined",
+                        "-fno-omit-frame-pointer", "-o", MAIN, src[0]], check=True)
+    return MAIN
+
+
+def plan_logic():
+    """-> (main_plan(n, workers, stripe, small_chunk, first_share) -> (region, small, grid), main_occupancy(api, lds, granule),
+    lists_first(all_slow, want_hits, n, n_recs, n_host) -> (deferred, recs, host),
+    lists_grown((deferred, recs, host), n, recs_before, host_before, recs_after, overflow) -> the same,
+    lists_fused(all_slow, n) -> the same)"""
+    lib = ctypes.CDLL(build())
+    u64, out3 = ctypes.c_uint64, ctypes.c_uint64 * 3
+    lib.overlapsim_main_plan.restype = None
+    lib.overlapsim_main_plan.argtypes = [u64] * 4 + [ctypes.c_double, ctypes.POINTER(u64)]
+    lib.overlapsim_main_occupancy.restype = ctypes.c_int
+    lib.overlapsim_main_occupancy.argtypes = [ctypes.c_int, u64, u64]
+    lib.overlapsim_lists_first.restype = None
+    lib.overlapsim_lists_first.argtypes = [ctypes.c_int, ctypes.c_int, u64, u64, u64, ctypes.POINTER(u64)]
+    lib.overlapsim_lists_grown.restype = None
+    lib.overlapsim_lists_grown.argtypes = [ctypes.POINTER(u64)] + [u64] * 4 + [ctypes.c_uint32, ctypes.POINTER(u64)]
+    lib.overlapsim_lists_fused.restype = None
+    lib.overlapsim_lists_fused.argtypes = [ctypes.c_int, u64, ctypes.POINTER(u64)]
+
+    def call(fn, *args):
+        o = out3()
+        fn(*args, o)
+        return tuple(int(v) for v in o)
+
+    return (lambda n, w, stripe, small, share: call(lib.overlapsim_main_plan, n, w, stripe, small, share),
+            lambda api, lds, granule: int(lib.overlapsim_main_occupancy(api, lds, granule)),
+            lambda slow, hits, n, recs, host: call(lib.overlapsim_lists_first, int(slow), int(hits), n, recs, host),
+            lambda s, n, rb, hb, ra, bits: call(lib.overlapsim_lists_grown, out3(*s), n, rb, hb, ra, bits),
+            lambda slow, n: call(lib.overlapsim_lists_fused, int(slow), n))
 
 
 def overlap_logic():
