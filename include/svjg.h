@@ -396,6 +396,15 @@ void svjg_vcf_free(svjg_vcf *v);
 int svjg_last_kernel_ms(svjg_ctx *ctx, float *classify_main_ms, float *classify_slow_ms, float *genotype_ms);
 int svjg_last_main_ms(svjg_ctx *ctx, float *by_stamps, float *by_events);
 int svjg_sync(svjg_ctx *ctx);
+/* ---- test hooks: k_classify_main's chunked regime (a first chunk per worker, then 64 KB chunks from one counter) begins at an even share
+ * of 8 x 64 KB, 1.88 GB of text on 256 CUs x 14 workers.  svjg_set_main_workers caps the workers the launch plan is made for at
+ * min(CUs x occupancy, workers) on this context (0, the default: no cap), for the step-by-step calls and the fused pass alike: with 3
+ * workers the regime begins at 1.5 MB.  svjg_last_main_plan gives the plan of the last k_classify_main launch that finished on this context
+ * (of a fused pass: the pass svjg_run_end last returned) — bytes of a worker's first chunk, bytes of a small chunk (0: even shares or
+ * stripes), workers launched — and how often that launch asked the chunk counter (every worker ends on one claim at or behind the text's
+ * end); all zero before the first launch.  Any pointer may be NULL. ---- */
+int svjg_set_main_workers(svjg_ctx *ctx, uint32_t workers);
+int svjg_last_main_plan(svjg_ctx *ctx, uint64_t *region, uint64_t *small, uint32_t *grid, uint64_t *chunks_claimed);
 /* what plain streams of n_bytes reach on this GPU right now (16 B per lane, non-temporal, four in flight per lane; best of three), in
  * GB/s: copy = a device-to-device copy, bytes read + bytes written per second; read = a kernel that only reads (and folds what it read
  * into one word) — the measured ceilings bench.py reports beside the 8 TB/s of the data sheet.  Either pointer may be NULL. */

@@ -103,6 +103,8 @@ struct svjg_ctx {
     int wall_khz = 0;                    // rate of wall_clock64(), the clock of the kernels' time stamps
     int n_cu = 256;
     int occ_main = 0;                    // workgroups of k_classify_main one CU holds
+    uint32_t main_workers = 0;           // svjg_set_main_workers: the plan is made for at most that many workers (0: no cap; a test hook)
+    MainPlan last_plan{0, 0, 0};  uint64_t last_claimed = 0;   // svjg_last_main_plan: the last k_classify_main launch that finished, and its status block's next_chunk
     hipStream_t stream = nullptr, copy_stream = nullptr;
     // The second compute stream: overlapped fused passes alternate between `stream` and it, everything else runs on `stream`.
     // second_busy: stream2 holds work `stream` is not ordered behind; first_dirty: `stream` holds work other than overlapped passes that
@@ -159,6 +161,7 @@ struct svjg_ctx {
         bool chained = false;            // another pass was in flight when this one was enqueued: its main kernel may have started under that one's drain
         hipStream_t on = nullptr;        // the compute stream of its kernels
         ClassifyArgs cargs{};            // its k_classify_main's arguments (the settle step's k_classify_exact takes the same)
+        uint32_t grid = 0;               // ... and its workers (svjg_last_main_plan)
         bool clean = false;              // the pass before has already zeroed this slot's vector, status block and max_n (k_classify_exact)
     } run[RUN_SLOTS];
     int run_head = 0, run_tail = 0, run_inflight = 0;
@@ -584,7 +587,9 @@ static int main_launch_setup(svjg_ctx *c, const PassTargets &t, uint64_t begin, 
 #endif
     }
     if (!(a.long_pre = scratch_words(c, t.scratch))) { c->err = "no memory for the workers' scratch words"; return SVJG_E_NOMEM; }
-    const MainPlan p = main_plan(end - begin, (uint64_t)c->n_cu * (uint64_t)c->occ_main, TEXT, SMALL_CHUNK, FIRST_CHUNK_SHARE);
+    uint64_t workers = (uint64_t)c->n_cu * (uint64_t)c->occ_main;     // (the scratch words are sized by this, whatever the cap)
+    if (c->main_workers && c->main_workers < workers) workers = c->main_workers;
+    const MainPlan p = main_plan(end - begin, workers, TEXT, SMALL_CHUNK, FIRST_CHUNK_SHARE);
     a.region = p.region; a.small = p.small; grid = p.grid;
     return 0;
 }
@@ -661,6 +666,7 @@ static int classify_range(svjg_ctx *c, uint64_t begin, uint64_t end, uint64_t ba
         if ((rc = enqueue_main(c, c->stream, a, grid, lds, c->ev))) return rc;
         HIPCHK(c, hipMemcpyAsync(&c->hs(), c->d_st, sizeof(DevStatus), hipMemcpyDeviceToHost, c->stream));
         HIPCHK(c, hipStreamSynchronize(c->stream));
+        c->last_plan = MainPlan{a.region, a.small, grid}; c->last_claimed = c->hs().next_chunk;
         const uint64_t n_def = c->hs().n_deferred;
 #ifdef SVJG_TIMING
         if ((a.diag & 16u) && (rc = timing_print_main(c))) return rc;
@@ -1509,6 +1515,7 @@ static int pass_main(svjg_ctx *c, svjg_ctx::RunSlot &r, const RunLayout &L, uint
     uint32_t grid = 0;  size_t lds = 0;
     r.cargs = ClassifyArgs{};
     if (const int rc = main_launch_setup(c, slot_targets(c, r, L), 0, n, r.base_offset, 0, r.cargs, grid, lds)) return rc;
+    r.grid = grid;
 #ifdef SVJG_ENDTIMES
     HIPCHK(c, hipMemsetAsync(c->d_dbg + ENDT_SUM, 0, (DBG_WORDS - ENDT_SUM) * 8, r.on));   // (one launch at a time: svjg_run_resident)
 #endif
@@ -1709,6 +1716,7 @@ extern "C" int svjg_run_end(svjg_ctx *c, const uint8_t **gt, const int32_t **pl,
     if ((rc = settle_pass(c, r))) return rc;                               // (an overlapped pass that deferred lines: one more; nothing if somebody asked for its counts before)
     const uint8_t *tail = hb + L.h_tail;
     c->hs() = *(const DevStatus *)(tail + L.status);
+    if (r.had_text) { c->last_plan = MainPlan{r.cargs.region, r.cargs.small, r.grid}; c->last_claimed = c->hs().next_chunk; }
     if ((rc = pass_times(c, r))) return rc;
     if (n_rows) HIPCHK(c, hipEventElapsedTime(&c->ms_geno, r.ev[4], r.ev[5]));
     c->last_pass_deferred = r.had_text && c->hs().n_deferred != 0;
@@ -1813,6 +1821,21 @@ extern "C" int svjg_copy_rate(svjg_ctx *c, uint64_t n_bytes, double *copy_gb_per
         }
         *out = best > 0 ? (what ? 1.0 : 2.0) * (double)n_bytes / (best * 1e-3) / 1e9 : 0.0;
     }
+    return 0;
+}
+
+extern "C" int svjg_set_main_workers(svjg_ctx *c, uint32_t workers) {
+    if (!c) return SVJG_E_ARG;
+    c->main_workers = workers;
+    return 0;
+}
+
+extern "C" int svjg_last_main_plan(svjg_ctx *c, uint64_t *region, uint64_t *small, uint32_t *grid, uint64_t *chunks_claimed) {
+    if (!c) return SVJG_E_ARG;
+    if (region) *region = c->last_plan.region;
+    if (small) *small = c->last_plan.small;
+    if (grid) *grid = c->last_plan.grid;
+    if (chunks_claimed) *chunks_claimed = c->last_claimed;
     return 0;
 }
 

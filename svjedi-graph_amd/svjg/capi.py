@@ -102,6 +102,9 @@ _SIGS = {
                                            ctypes.POINTER(ctypes.c_float)]),
     "svjg_last_main_ms": (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(ctypes.c_float), ctypes.POINTER(ctypes.c_float)]),
     "svjg_sync": (ctypes.c_int, [ctypes.c_void_p]),
+    "svjg_set_main_workers": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_uint32]),
+    "svjg_last_main_plan": (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(ctypes.c_uint64), ctypes.POINTER(ctypes.c_uint64), ctypes.POINTER(ctypes.c_uint32),
+                                           ctypes.POINTER(ctypes.c_uint64)]),
 }
 
 EXPORTS = tuple(_SIGS) + ("svjg_write_informative_json", "svjg_count_informative_json", "svjg_host_free",
@@ -676,6 +679,18 @@ class Context:
 
     def sync(self):
         self._chk(self.lib.svjg_sync(self.h))
+
+    def set_main_workers(self, workers):
+        """a test hook (svjg_set_main_workers): k_classify_main's launch plan is made for at most `workers` workers on this context, so that
+        its chunked regime begins at 8 x 65 536 x workers bytes of text; 0: no cap"""
+        self._chk(self.lib.svjg_set_main_workers(self.h, int(workers)))
+
+    def last_main_plan(self):
+        """-> (region, small, grid, chunks_claimed) of the last k_classify_main launch that finished on this context — of a fused pass: the
+        pass run_end() last returned — (svjg_last_main_plan)"""
+        region, small, grid, claimed = ctypes.c_uint64(0), ctypes.c_uint64(0), ctypes.c_uint32(0), ctypes.c_uint64(0)
+        self._chk(self.lib.svjg_last_main_plan(self.h, ctypes.byref(region), ctypes.byref(small), ctypes.byref(grid), ctypes.byref(claimed)))
+        return region.value, small.value, grid.value, claimed.value
 
 
 def release_host_tables():
