@@ -326,6 +326,36 @@ int svjg_genotype_cohort_ploidy(svjg_ctx *ctx, const uint8_t *sv_type, const uin
                                 uint8_t *gt, int64_t *pl /* [n_rows][n_samples][max_ploidy+1] */, uint32_t *raw,
                                 uint8_t *genotyped, uint8_t *boundary, uint32_t *site /* [n_rows][3] = NS, AN, AC */);
 
+/* svjg_genotype_cohort_prior: the cohort call with an allele-frequency prior (--cohort-prior).  The arguments of svjg_genotype_cohort_ploidy,
+ * with `ploidy` nullable: NULL = every item diploid, max_ploidy must be 2, and the first launch is svjg_genotype_cohort's kernel.  pl, raw,
+ * genotyped and boundary are exactly what svjg_genotype_cohort / svjg_genotype_cohort_ploidy return on the same inputs (pl: max_ploidy + 1 per
+ * item).  Behind that kernel, on the same stream, a second one estimates every row's alt-allele frequency f from all its samples' likelihoods by
+ * EM under Hardy-Weinberg and calls each item at the maximum of likelihood x prior (the model: DESIGN.md 4.3, svjg_geno.h):
+ *   gt        [n_rows][n_samples]  alt copies of the POSTERIOR call, 0xFF = no call (in both modes: never 3 for "no call")
+ *   gq        [n_rows][n_samples]  min(99, int(-10 log10(1 - q_best))), 0xFF where gt is 0xFF
+ *   af        [n_rows]             the row's f; NaN: no item took part (genotyped and with a read), no estimate
+ *   em_steps  [n_rows]             EM steps taken (0..128) in the low bits; bit 31 set: 128 steps without |f' - f| <= 1e-9 ("not converged")
+ *   site      [n_rows][3]          NS, AN, AC of the posterior calls, summed in integers
+ * No atomics take part in the second kernel (a row lies within one wave; its sums go through a fixed butterfly): equal bytes from run to run.
+ * The call works in a block of its own (8 (max_ploidy + 1) + 13 bytes per item, 46 per row).  n_rows = 0 returns 0.  SVJG_E_ARG with a
+ * message, all found before any launch: as svjg_genotype_cohort_ploidy, and ploidy == NULL with max_ploidy != 2.  svjg_last_kernel_ms reports
+ * both kernels together as genotype_ms.
+ * The items of a lane beyond its first (more than 64 samples) keep their weights in LDS across the EM steps, up to 256 samples; beyond, they are
+ * recomputed at every step.  SVJG_PRIOR_STAGE=recompute / lds in the environment forces one way (for tools/cohort_prior_timing.py).
+ * Measured once, with the change that added it (one MI355X, 2026-10-19, ROCm 7.2.0, tools/cohort_prior_timing.py: 100 000 rows, counts 0..60,
+ * e = 5e-5, median of 30 calls behind 5, the legs alternated twice in one process; genotype_ms, both kernels): 64 samples 0.730 / 0.730 ms against
+ * 0.159 / 0.160 ms of svjg_genotype_cohort alone (+0.571 / +0.570 ms; 4.79 EM steps a row, 7 at the most); 64 samples with ploidies 1..8 at
+ * max_ploidy 8 1.419 / 1.419 ms against 0.456 / 0.456 ms of svjg_genotype_cohort_ploidy (+0.963 / +0.963 ms; 8.82 steps, at most 12); 4 samples
+ * 0.084 / 0.084 ms against 0.029 / 0.029 ms (+0.055 ms; 2.64 steps, at most 18); 256 samples 2.549 / 2.549 ms against 0.597 / 0.597 ms (+1.952 ms;
+ * 4.90 steps, at most 6), and 3.685 / 3.692 ms with the further items recomputed instead of staged in LDS.  A call from Python took 32.6 / 29.7 ms at
+ * 64 samples (30.5 / 30.8 ms without the prior): the copies to the host dominate either way.  Nothing else about this kernel has been measured. */
+int svjg_genotype_cohort_prior(svjg_ctx *ctx, const uint8_t *sv_type, const uint32_t *slot, const uint8_t *ok,
+                               const uint8_t *ploidy /* [n_rows][n_samples], or NULL */, uint32_t max_ploidy, uint64_t n_rows,
+                               uint32_t min_support, double err,
+                               uint8_t *gt, int64_t *pl /* [n_rows][n_samples][max_ploidy+1] */, uint32_t *raw,
+                               uint8_t *genotyped, uint8_t *boundary, uint32_t *site /* [n_rows][3] = NS, AN, AC */,
+                               uint8_t *gq, double *af, uint32_t *em_steps);
+
 /* ---- the whole pass in one call (what a fused svjedi-graph run and bench.py do per batch) -----------------------------------
  * svjg_set_rows copies the three per-row input arrays of svjg_genotype to the device once (they stay until the next
  * svjg_set_rows / svjg_destroy).  svjg_run_resident then does, for the resident text of svjg_gaf_upload and those rows:

@@ -80,7 +80,7 @@ constexpr uint64_t STAGE_PIECE = 8ull << 20;
 // The device block of a step-by-step genotype call and its pinned host twin (genotype_leg).  Every call has a block of its own: svjg_genotype_view
 // hands out pointers into BLOCK_ROWS' twin and svjg_genotype_boundary reads it later, and both must survive calls of the other four.
 struct LegBlock { void *d = nullptr;  uint64_t d_cap = 0;  void *h = nullptr;  uint64_t h_cap = 0; };
-enum { BLOCK_ROWS, BLOCK_PLOIDY, BLOCK_SITES, BLOCK_COHORT, BLOCK_COHORT_PLOIDY, LEG_BLOCKS };   // rows_layout, ploidy_layout, sites_layout, cohort_layout, cohort_ploidy_layout (svjg_geno.h)
+enum { BLOCK_ROWS, BLOCK_PLOIDY, BLOCK_SITES, BLOCK_COHORT, BLOCK_COHORT_PLOIDY, BLOCK_COHORT_PRIOR, LEG_BLOCKS };   // rows_layout, ploidy_layout, sites_layout, cohort_layout, cohort_ploidy_layout, cohort_prior_layout (svjg_geno.h)
 
 // slots the passes of svjg_run_begin rotate through: two may be in flight, and the one the NEXT pass will use is zeroed while the newest computes
 constexpr int RUN_SLOTS = 3;
@@ -1013,7 +1013,7 @@ static int build_logfact(svjg_ctx *c, uint32_t upto) {
     return 0;
 }
 
-// ---- one genotype leg, for the five step-by-step calls (genotype_leg) and the fused pass alike ----
+// ---- one genotype leg, for the six step-by-step calls (genotype_leg) and the fused pass alike ----
 // k_genotype's arguments but where the results go (the callers' layouts, svjg_geno.h); p: device block with the rows' inputs at I
 static GenoArgs geno_args(const svjg_ctx *c, const unsigned long long *counts, const uint8_t *p, const RowsIn &I, uint64_t n_rows, uint32_t min_support, double err) {
     GenoArgs a{};
@@ -1376,6 +1376,68 @@ extern "C" int svjg_genotype_cohort_ploidy(svjg_ctx *c, const uint8_t *sv_type, 
     memcpy(gt, hb + L.gt, n); memcpy(genotyped, hb + L.flags, n); memcpy(boundary, hb + L.boundary, n);
     const uint64_t *w = (const uint64_t *)(hb + L.site);          // NS | AC << 32, AN per row -> NS, AN, AC
     for (uint64_t r = 0; r < n_rows; ++r) { site[r * 3] = (uint32_t)w[r * 2]; site[r * 3 + 1] = (uint32_t)w[r * 2 + 1]; site[r * 3 + 2] = (uint32_t)(w[r * 2] >> 32); }
+    return 0;
+}
+
+// svjg_genotype_cohort_prior goes through genotype_leg in BLOCK_COHORT_PRIOR: the cohort kernel of the call's kind (ploidy == NULL: k_genotype_cohort,
+// else k_genotype_cohort_ploidy), launched as launch_cohort / launch_cohort_ploidy launch it — the table's grow-and-rerun is theirs —, and behind it
+// k_cohort_prior on what it left in the block.  Blocks: a wave holds 64 / width rows (prior_segment_width), a block four waves, eight blocks a unit
+// at the most; the rest in strides of the grid.
+constexpr bool PRIOR_STAGE_DEFAULT = true;                          // measured: see k_cohort_prior
+static int launch_cohort_prior(svjg_ctx *c, CohortPriorArgs &p) {
+    const char *e = getenv("SVJG_PRIOR_STAGE");                   // "lds" / "recompute": the other way for the items beyond a lane's first (tools/cohort_prior_timing.py)
+    const uint64_t further = (p.n_samples + 63) / 64 - 1;
+    p.staged = PRIOR_STAGE_DEFAULT ? (uint32_t)(further < PRIOR_STAGE_MAX ? further : PRIOR_STAGE_MAX) : 0u;
+    if (e && !strcmp(e, "recompute")) p.staged = 0;
+    if (e && !strcmp(e, "lds")) p.staged = (uint32_t)(further < PRIOR_STAGE_MAX ? further : PRIOR_STAGE_MAX);
+    const uint64_t rows_per_wave = 64u / prior_segment_width(p.n_samples), waves = (p.n_rows + rows_per_wave - 1) / rows_per_wave;
+    const uint64_t blocks = (waves * 64 + TPB - 1) / TPB, cap = (uint64_t)c->n_cu * 8;
+    hipLaunchKernelGGL(k_cohort_prior, dim3((uint32_t)(blocks < cap ? blocks : cap)), dim3(TPB), prior_stage_bytes(p.staged, TPB), c->stream, p);
+    HIPCHK(c, hipGetLastError());
+    return 0;
+}
+
+extern "C" int svjg_genotype_cohort_prior(svjg_ctx *c, const uint8_t *sv_type, const uint32_t *slot, const uint8_t *ok, const uint8_t *ploidy,
+                                          uint32_t max_ploidy, uint64_t n_rows, uint32_t min_support, double err, uint8_t *gt, int64_t *pl,
+                                          uint32_t *raw, uint8_t *genotyped, uint8_t *boundary, uint32_t *site, uint8_t *gq, double *af,
+                                          uint32_t *em_steps) {
+    if (!c) return SVJG_E_ARG;
+    if (!c->d_cm) { c->err = "no cohort matrix"; return SVJG_E_ARG; }
+    if (n_rows == 0) return 0;
+    if (!sv_type || !slot || !ok || !gt || !pl || !raw || !genotyped || !boundary || !site || !gq || !af || !em_steps) { c->err = "a null array"; return SVJG_E_ARG; }
+    if (max_ploidy < 1 || max_ploidy > MAX_PLOIDY) { c->err = "max_ploidy is not in 1..SVJG_MAX_PLOIDY"; return SVJG_E_ARG; }
+    if (!ploidy && max_ploidy != 2) { c->err = "without a ploidy array every item is diploid: max_ploidy must be 2"; return SVJG_E_ARG; }
+    const uint64_t S = c->cohort_samples;
+    if (S >= (1ull << 28)) { c->err = "too many samples: AN would not fit 32 bits"; return SVJG_E_ARG; }
+    if (n_rows > (1ull << 40) / S) { c->err = "too many items for one call: genotype the rows in chunks"; return SVJG_E_ARG; }
+    const uint64_t n = n_rows * S;
+    if (ploidy)
+        for (uint64_t i = 0; i < n; ++i)
+            if (ploidy[i] > max_ploidy) { c->err = "ploidy above max_ploidy"; return SVJG_E_ARG; }
+    HIPCHK(c, hipSetDevice(c->device));
+    const CohortPriorLayout L = cohort_prior_layout(n_rows, S, max_ploidy, ploidy != nullptr);
+    const int rc = genotype_leg(c, c->leg[BLOCK_COHORT_PRIOR], L,
+        [&](uint8_t *hb) {
+            ploidy_log_table(err, (double *)(hb + L.logtab)); stage_rows(hb, L.in, sv_type, slot, ok, n_rows);   // (host libm, as geno_args' three)
+            if (ploidy) memcpy(hb + L.ploidy, ploidy, n);
+        },
+        [&](uint8_t *base) {
+            GenoCohortArgs g{block_geno_args(c, c->d_cm, base, L, n_rows, min_support, err), c->d_cpresent, c->cohort_samples, (unsigned long long *)(base + L.site)};
+            g.g.n_slots = c->cohort_slots;                        // (the matrix's slots, not the count vector's)
+            int rc1;
+            if (ploidy) { GenoCohortPloidyArgs q{g, base + L.ploidy, (const double *)(base + L.logtab), max_ploidy}; rc1 = launch_cohort_ploidy(c, q); }
+            else rc1 = launch_cohort(c, g);
+            if (rc1) return rc1;
+            CohortPriorArgs p{(const uint32_t *)(base + L.raw), base + L.flags, ploidy ? base + L.ploidy : nullptr, base + L.in.type,
+                                    (const double *)(base + L.logtab), n_rows, c->cohort_samples, min_support,
+                                    base + L.gt, base + L.gq, (double *)(base + L.af), (uint32_t *)(base + L.steps), (uint32_t *)(base + L.psite), 0u};
+            return launch_cohort_prior(c, p);
+        });
+    if (rc) return rc;
+    const uint8_t *hb = (const uint8_t *)c->leg[BLOCK_COHORT_PRIOR].h;
+    memcpy(pl, hb + L.pl, n * (max_ploidy + 1) * sizeof *pl); memcpy(raw, hb + L.raw, n * 2 * sizeof *raw);
+    memcpy(gt, hb + L.gt, n); memcpy(genotyped, hb + L.flags, n); memcpy(boundary, hb + L.boundary, n); memcpy(gq, hb + L.gq, n);
+    memcpy(af, hb + L.af, n_rows * sizeof *af); memcpy(em_steps, hb + L.steps, n_rows * sizeof *em_steps); memcpy(site, hb + L.psite, n_rows * 3 * sizeof *site);
     return 0;
 }
 

@@ -384,6 +384,152 @@ SVJG_HD CohortSums cohort_ploidy_sums(const CohortBallots &b, uint64_t mask) {
 // the row's two site words: NS | AC << 32 (k_genotype_cohort's word) and AN.  (AC, AN <= 8 S: they fit 32 bits for S < 2^28)
 SVJG_HD uint64_t cohort_site_word(const CohortSums &s) { return (uint64_t)s.ns | ((uint64_t)s.ac << 32); }
 
+// ---- cohort with an allele-frequency prior (k_cohort_prior) ----
+// The row's alt-allele frequency f is estimated from all its samples' likelihoods by EM under Hardy-Weinberg, each item is then called at
+// the maximum of likelihood x prior.  An item (r, s) takes part iff the cohort call genotyped it and c1 + c2 > 0.  Its weights: l_g as
+// geno_row_pairs compares them (the exact sum of the two rounded products, the one product at 2 g = P), d_g = l_g - max l_g subtracted in
+// double-double and collapsed to one double, w_g = 10^d_g (the binomial term is the same for every g and cancels).  The prior is
+// pi_g(f; P) = C(P, g) f^g (1 - f)^(P - g), powers by repeated multiplication (0^0 = 1); posterior q_g = pi_g w_g / sum_g pi_g w_g, one-hot at
+// the item's largest w_g where that sum is 0; expected copies x = sum_g g q_g.  f_0 = 0.5, f_(k+1) = sum_s x_s / sum_s P_s over the row's items
+// that take part; the row stops after the first step with |f_(k+1) - f_k| <= EM_TOL, or after EM_MAX_IT steps without one ("not converged").
+// Every routine below is compiled without fused multiply-adds, so the host harness (tests/cohort_prior_sim) and the kernel differ in exp10,
+// log10 and nothing else.
+constexpr double EM_TOL = 1e-9;
+constexpr uint32_t EM_MAX_IT = 128;
+constexpr uint32_t EM_NOT_CONVERGED = 1u << 31;          // top bit of a row's step word
+// |f_device - f_model|, the model being tests/cohort_prior_model.py at 60 digits, is measured, not assumed (2026-10-19, one MI355X, ROCm 7.2.0,
+// tests/test_cohort_prior_gpu.py: 25 cases of 400 or 1 500 rows x 1..130 samples, 30 133 rows with an estimate): at most 3.668e-16 absolute
+// (1 sample a row, ploidies 0..8) and 1.187e-14 relative among the rows with f > 1e-6 (the same case; 3.7e-16 relative at 31 samples and more).
+// The tests assert 8 x the absolute maximum: the margin is for other seeds, not for other arithmetic.
+constexpr double EM_F_BOUND = 8 * 3.668e-16;
+
+// What an item keeps across the EM steps: w[g] = C(P, g) * 10^d_g for g = 0..P (0 beyond), the binomial coefficient folded in once (an exact
+// integer <= 70 times a double: one rounding, and 0 iff 10^d_g is 0).  P = 0: the item takes no part.  gmax: the first g with d_g = 0.
+struct PriorItem { double w[MAX_PLOIDY + 1]; uint32_t P, gmax; };
+
+SVJG_HD double prior_exp10(double d) {
+#if defined(__HIP_DEVICE_COMPILE__)
+    return exp10(d);
+#else
+    return pow(10.0, d);                                 // (glibc's pow is correctly rounded in nearly every case; the harness compares against 60 digits)
+#endif
+}
+
+// lr / la: the item's own P + 1 logarithms, as for geno_row_pairs.  Both loops under a predicate: w[] is only ever indexed by constants.
+SVJG_HD void prior_item(uint32_t type, uint32_t ref, uint32_t alt, uint32_t P, const double *lr, const double *la, double &c_sum, PriorItem &o) {
+#ifdef __clang__
+#pragma clang fp contract(off)                           // the products are rounded to doubles before the exact sums
+#endif
+    double c1, c2; uint32_t r1, r2;
+    geno_counts(type, ref, alt, c1, c2, r1, r2);
+    c_sum = c1 + c2;
+    o.P = c_sum > 0.0 ? P : 0u; o.gmax = 0;
+    dd best{0.0, 0.0};
+    SVJG_UNROLL
+    for (uint32_t g = 0; g <= MAX_PLOIDY; ++g) {
+        if (g > o.P || o.P == 0) continue;
+        const double a = c1 * lr[g], b = c2 * la[g], h = (c1 + c2) * lr[g];
+        const dd l = (g != 0 && 2 * g == P) ? dd{h, 0.0} : two_sum(a, b);
+        if (g == 0 || dd_cmp(l, best) > 0) { best = l; o.gmax = g; }
+    }
+    uint32_t comb = 1;                                   // C(P, g), exact in integers
+    SVJG_UNROLL
+    for (uint32_t g = 0; g <= MAX_PLOIDY; ++g) {
+        o.w[g] = 0.0;
+        if (g > o.P || o.P == 0) continue;
+        if (g) comb = comb * (P - g + 1) / g;
+        const double a = c1 * lr[g], b = c2 * la[g], h = (c1 + c2) * lr[g];
+        const dd l = (g != 0 && 2 * g == P) ? dd{h, 0.0} : two_sum(a, b);
+        const dd d = dd_add(l, dd_neg(best));
+        o.w[g] = (double)comb * prior_exp10(d.hi + d.lo);
+    }
+}
+
+// t[g] = pi_g(f; P) w_g for g = 0..P (0 beyond): (1 - f)^(P - g) from the top down, f^g from the bottom up.  P = 0: all 0, f is not looked at.
+SVJG_HD void prior_terms(const PriorItem &it, double f, double *t) {
+#ifdef __clang__
+#pragma clang fp contract(off)
+#endif
+    const double q = 1.0 - f;
+    double b = 1.0;
+    SVJG_UNROLL
+    for (int g = (int)MAX_PLOIDY; g >= 0; --g) {
+        t[g] = 0.0;
+        if ((uint32_t)g > it.P || it.P == 0) continue;
+        if ((uint32_t)g < it.P) b *= q;
+        t[g] = it.w[g] * b;
+    }
+    double a = 1.0;
+    SVJG_UNROLL
+    for (uint32_t g = 1; g <= MAX_PLOIDY; ++g) {
+        if (g > it.P) continue;
+        a *= f;
+        t[g] *= a;
+    }
+}
+
+// x = sum_g g q_g of one item under f (0 for an item that takes no part); both sums in increasing g
+SVJG_HD double prior_expected(const PriorItem &it, double f) {
+#ifdef __clang__
+#pragma clang fp contract(off)
+#endif
+    double t[MAX_PLOIDY + 1];
+    prior_terms(it, f, t);
+    double z = 0.0, x = 0.0;
+    SVJG_UNROLL
+    for (uint32_t g = 0; g <= MAX_PLOIDY; ++g) { z += t[g]; x += (double)g * t[g]; }
+    if (it.P == 0) return 0.0;
+    return z > 0.0 ? x / z : (double)it.gmax;
+}
+
+// The call of one item under the row's final f: gt = argmax q_g (0xFF: a tie at the maximum, below min_support, or the item takes no part),
+// gq = min(99, int(-10 log10(sum of the other q_g, in increasing g))), 99 where that sum is 0, 0xFF without a call.
+struct PriorCall { uint8_t gt, gq; };
+SVJG_HD PriorCall prior_call(const PriorItem &it, double f, double c_sum, uint32_t min_support) {
+#ifdef __clang__
+#pragma clang fp contract(off)
+#endif
+    double t[MAX_PLOIDY + 1];
+    prior_terms(it, f, t);
+    double z = 0.0, top = 0.0; uint32_t best = 0; bool tie = false;
+    SVJG_UNROLL
+    for (uint32_t g = 0; g <= MAX_PLOIDY; ++g) {
+        if (g > it.P) continue;
+        z += t[g];
+        if (g == 0 || t[g] > top) { top = t[g]; best = g; tie = false; } else if (t[g] == top) tie = true;
+    }
+    if (it.P == 0) return PriorCall{0xFF, 0xFF};
+    double rest = 0.0;
+    SVJG_UNROLL
+    for (uint32_t g = 0; g <= MAX_PLOIDY; ++g) if (g <= it.P && g != best) rest += t[g];
+    if (z > 0.0) rest /= z; else { best = it.gmax; tie = false; rest = 0.0; }
+    if (tie || !(c_sum >= (double)min_support)) return PriorCall{0xFF, 0xFF};
+    double v = rest > 0.0 ? -10.0 * log10(rest) : 99.0;
+    if (!(v < 99.0)) v = 99.0;
+    return PriorCall{(uint8_t)best, (uint8_t)(v > 0.0 ? (uint32_t)v : 0u)};
+}
+
+// One EM step's outcome for a row: sum_x over sum_p against the f it was computed under; r.done: the row has stopped.
+struct PriorRow { double f; uint32_t steps; bool done; };
+SVJG_HD void prior_step(PriorRow &r, double sum_x, uint32_t sum_p) {
+    if (r.done) return;                                  // a converged row keeps its f while its wave goes on
+    const double fn = sum_x / (double)sum_p;
+    const bool conv = fabs(fn - r.f) <= EM_TOL;
+    r.f = fn; ++r.steps;
+    if (conv) r.done = true;
+    else if (r.steps == EM_MAX_IT) { r.done = true; r.steps |= EM_NOT_CONVERGED; }
+}
+// a row before its first step: no item takes part (sum_p = 0): no estimate (NaN), 0 steps
+SVJG_HD PriorRow prior_row_start(uint32_t sum_p) { return PriorRow{sum_p ? 0.5 : NAN, 0u, sum_p == 0}; }
+
+// The lanes a row takes in k_cohort_prior: the next power of two >= min(S, 64); 64 / width rows share a wave, a row never spans two.
+SVJG_HD uint32_t prior_segment_width(uint64_t S) {
+    const uint32_t m = S < 64 ? (uint32_t)S : 64u;
+    uint32_t w = 1;
+    while (w < m) w <<= 1;
+    return w;
+}
+
 // ---- host side of a k_genotype launch: the table's size and where a call's rows lie, in plain integers (pinned without a GPU: tests/test_rows_layout.py) ----
 
 // entries of the log10(i!) table: the first one built; the one that holds max_n (the largest n the kernel met beyond the table, < LOGFACT_CAP) with room to spare
@@ -399,7 +545,7 @@ constexpr uint32_t logfact_reserve_to(uint32_t have, uint32_t entries) { return 
 struct RowsIn { uint64_t slot, type, ok, bytes; };
 inline RowsIn rows_in(uint64_t n, uint64_t at = 0) { return RowsIn{at, at + n * 4, at + n * 5, n * 6}; }
 
-// The five step-by-step calls (svjg_genotype / _view, _ploidy, _sites, _cohort, _cohort_ploidy) each own one device block and its pinned host twin, all of ONE
+// The six step-by-step calls (svjg_genotype / _view, _ploidy, _sites, _cohort, _cohort_ploidy, _cohort_prior) each own one device block and its pinned host twin, all of ONE
 // shape: the outputs (they end at out_end), the max_n pair 8-aligned, ONE contiguous input region right behind the pair, 64 spare bytes -> ONE copy
 // in (in_bytes from in_at), ONE copy out (maxn + 8 bytes from 0).  A layout below IS a LegSpan and adds only what is its own: its outputs and where its inputs lie.
 struct LegSpan { uint64_t maxn, in_at, in_bytes, total; };
@@ -460,6 +606,22 @@ inline CohortPloidyLayout cohort_ploidy_layout(uint64_t n_rows, uint64_t S, uint
     L.pl = o; o += n * 8 * (max_ploidy + 1); L.raw = o; o += n * 8; L.gt = o; o += n; L.flags = o; o += n; L.boundary = o; o += n;
     o = (o + 7) & ~7ull; L.site = o; o += n_rows * 16;
     leg_span(L, o, 2 * PLOIDY_TAB * 8 + n_rows * 6 + n);
+    L.logtab = L.in_at; L.in = rows_in(n_rows, L.logtab + 2 * PLOIDY_TAB * 8); L.ploidy = L.in.slot + L.in.bytes;
+    return L;
+}
+
+// svjg_genotype_cohort_prior: the first kernel's five outputs as cohort_layout (ploidy == NULL: per_item false, max_ploidy 2) or
+// cohort_ploidy_layout holds them — gt is then overwritten by k_cohort_prior with the posterior call —, k_cohort_prior's own outputs [ gq 1 ] x
+// items, [ af 8 | psite 12 (NS, AN, AC) | steps 4 ] x rows, and last the first kernel's site words (one per row, or two), 8-aligned right in front
+// of the max_n pair as in those layouts; in: the call's logarithms (ploidy_log_table; k_cohort_prior reads them in either case), rows_in(n_rows)
+// and, per_item, the n_rows * S ploidy bytes
+struct CohortPriorLayout : LegSpan { uint64_t pl, raw, gt, flags, boundary, gq, af, psite, steps, site, logtab;  RowsIn in;  uint64_t ploidy; };
+inline CohortPriorLayout cohort_prior_layout(uint64_t n_rows, uint64_t S, uint32_t max_ploidy, bool per_item) {
+    CohortPriorLayout L; uint64_t o = 0; const uint64_t n = n_rows * S;
+    L.pl = o; o += n * 8 * (max_ploidy + 1); L.raw = o; o += n * 8; L.gt = o; o += n; L.flags = o; o += n; L.boundary = o; o += n; L.gq = o; o += n;
+    o = (o + 7) & ~7ull; L.af = o; o += n_rows * 8; L.psite = o; o += n_rows * 12; L.steps = o; o += n_rows * 4;
+    L.site = o; o += n_rows * (per_item ? 16 : 8);
+    leg_span(L, o, 2 * PLOIDY_TAB * 8 + n_rows * 6 + (per_item ? n : 0));
     L.logtab = L.in_at; L.in = rows_in(n_rows, L.logtab + 2 * PLOIDY_TAB * 8); L.ploidy = L.in.slot + L.in.bytes;
     return L;
 }

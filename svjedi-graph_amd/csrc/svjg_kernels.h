@@ -14,6 +14,7 @@
 //   k_genotype_sites one site of insertions that share a position per lane, the same arithmetic over (K + 1)(K + 2) / 2 genotypes
 //   k_genotype_cohort one (row, sample) item per lane over a slot-major count matrix, k_genotype's arithmetic; NS / AC per row by wave ballots
 //   k_genotype_cohort_ploidy  the same division of work at a ploidy per item, k_genotype_ploidy's arithmetic; NS / AN / AC per row by wave ballots
+//   k_cohort_prior    behind either cohort kernel: a row per wave segment, its allele frequency by EM over its samples, posterior GT and GQ per item
 //   k_cohort_store / k_cohort_load  one sample's column of that matrix from / to a dense count vector
 #pragma once
 #include <hip/hip_runtime.h>
@@ -2176,6 +2177,125 @@ __global__ __launch_bounds__(TPB) void k_genotype_cohort_ploidy(GenoCohortPloidy
     if (seg.leader) {
         const CohortSums t = cohort_ploidy_sums(b, seg.mask);
         if (t.ns) { atomicAdd(p.c.site + r * 2, (unsigned long long)cohort_site_word(t)); atomicAdd(p.c.site + r * 2 + 1, (unsigned long long)t.an); }
+    }
+  }
+}
+
+// ---- cohort with an allele-frequency prior (svjg_genotype_cohort_prior; the model: svjg_geno.h) ----
+// Enqueued behind k_genotype_cohort / k_genotype_cohort_ploidy on the same stream: it reads what they left in the call's block (raw counts, the
+// `genotyped` bytes) and the call's inputs (type, ploidy bytes or nullptr = 2 everywhere, the logarithms), and writes the posterior gt over the
+// first kernel's, gq, and per row f, the step word and NS / AN / AC of the posterior calls.
+struct CohortPriorArgs {
+    const uint32_t *raw; const uint8_t *genotyped; const uint8_t *ploidy; const uint8_t *sv_type;
+    const double *logtab;              // ploidy_log_table of the call's err
+    uint64_t n_rows; uint32_t n_samples, min_support;
+    uint8_t *gt, *gq; double *af; uint32_t *steps, *site;
+    uint32_t staged;                   // S > 64: the first `staged` further items of a lane keep their weights in LDS across the steps (prior_stage_bytes of dynamic LDS a block)
+};
+constexpr uint32_t PRIOR_STAGE_MAX = 3;                                        // 3 x 256 lanes x 76 bytes = 58 368 bytes of the 64 KiB a block may ask for
+constexpr uint32_t prior_stage_bytes(uint32_t staged, uint32_t block) { return staged * block * ((MAX_PLOIDY + 1) * 8 + 4); }
+
+// item (r, s) as the EM sees it; the item takes no part (it.P = 0) unless the first kernel genotyped it and it has a read
+__device__ inline void prior_load(const CohortPriorArgs &p, const double *tab, uint64_t r, uint64_t s, double &c_sum, PriorItem &it) {
+    const uint64_t i = r * p.n_samples + s;
+    const uint32_t P = p.genotyped[i] ? (p.ploidy ? p.ploidy[i] : 2u) : 0u;
+    it.P = 0; it.gmax = 0; c_sum = 0.0;
+#pragma unroll
+    for (uint32_t g = 0; g <= MAX_PLOIDY; ++g) it.w[g] = 0.0;
+    if (P >= 1 && P <= MAX_PLOIDY) prior_item(p.sv_type[r], p.raw[i * 2], p.raw[i * 2 + 1], P, tab + ploidy_tab_at(P, 0), tab + PLOIDY_TAB + ploidy_tab_at(P, 0), c_sum, it);
+}
+
+// the k-th further item of a lane in the block's dynamic LDS: w[g] at [(k * 9 + g) * block + lane of the block] (neighbouring lanes, neighbouring
+// banks), P | gmax << 8 behind all weights.  A lane reads only what it wrote itself: no barrier.
+__device__ inline void prior_stage_put(double *sw, uint32_t *sm, uint32_t k, const PriorItem &it) {
+#pragma unroll
+    for (uint32_t g = 0; g <= MAX_PLOIDY; ++g) sw[(k * (MAX_PLOIDY + 1) + g) * blockDim.x + threadIdx.x] = it.w[g];
+    sm[k * blockDim.x + threadIdx.x] = it.P | (it.gmax << 8);
+}
+__device__ inline void prior_stage_get(const double *sw, const uint32_t *sm, uint32_t k, PriorItem &it) {
+#pragma unroll
+    for (uint32_t g = 0; g <= MAX_PLOIDY; ++g) it.w[g] = sw[(k * (MAX_PLOIDY + 1) + g) * blockDim.x + threadIdx.x];
+    const uint32_t m = sm[k * blockDim.x + threadIdx.x];
+    it.P = m & 0xFFu; it.gmax = m >> 8;
+}
+
+// the sum over a row's segment of `width` lanes (a power of two), the same bits in every lane of it: an xor butterfly, whose partners add the same
+// two numbers at every level.  Executed by all 64 lanes.
+template <class T>
+__device__ inline T prior_segment_sum(T v, uint32_t width) {
+    for (uint32_t m = 1; m < width; m <<= 1) v += __shfl_xor(v, (int)m);
+    return v;
+}
+
+// A row takes a segment of W = prior_segment_width(S) lanes, 64 / W rows share a wave, a row never spans two waves; lane j of a segment holds
+// sample j and, for S > 64, strides over j + 64, j + 128, ...; lanes at or beyond S idle (items that take no part).  The loop's bound is the
+// WAVE's first row and every shuffle is executed by all 64 lanes on every trip; the EM loop runs until the wave's last row has stopped, a row that
+// stopped earlier keeps its f (prior_step).  The sum of the ploidies does not change from step to step: it is reduced once, in integers; the sum
+// of the x goes through the butterfly at every step — no atomics of any kind, equal bytes from run to run.  The weights of a lane's FIRST item
+// stay in registers across the steps (it.w[], indexed by constants only).  The further items of a lane (S > 64): the first p.staged of them keep
+// their weights in the block's dynamic LDS (prior_stage_put / _get, 76 bytes an item and lane, at most PRIOR_STAGE_MAX = 3: S <= 256), the ones
+// beyond are recomputed at every step (P + 1 exp10 each).  Chosen by a measurement (2026-10-19, one MI355X, ROCm 7.2.0,
+// tools/cohort_prior_timing.py, 100 000 rows x 256 samples, 4.9 steps a row, both kernels of the call, median of 30 calls behind 5, alternated
+// twice): 2.549 / 2.549 ms staged in LDS against 3.685 / 3.692 ms recomputed, the cohort kernel alone 0.597 / 0.597 ms — LDS, although its 58 KB a
+// block leave room for two blocks a unit only.  SVJG_PRIOR_STAGE=recompute (or lds) in the environment selects the other way, for that tool.
+// Compile remarks (ROCm 7.2.0, gfx950): 175 VGPRs, 106 SGPRs (50 of them spilled to VGPR lanes), 0 bytes of scratch, 2 waves a SIMD, 720 bytes of
+// static LDS.
+__global__ __launch_bounds__(TPB) void k_cohort_prior(CohortPriorArgs p) {
+  __shared__ double tab[2 * PLOIDY_TAB];
+  extern __shared__ double prior_stage[];
+  stage_ploidy_tab(tab, p.logtab);
+  double *sw = prior_stage; uint32_t *sm = (uint32_t *)(prior_stage + (size_t)p.staged * (MAX_PLOIDY + 1) * blockDim.x);
+  const uint64_t S = p.n_samples;
+  const uint32_t lane = threadIdx.x & 63u, W = prior_segment_width(S), rows_per_wave = 64u / W, j = lane & (W - 1), sub = lane / W;
+  const uint64_t n_waves = (p.n_rows + rows_per_wave - 1) / rows_per_wave;
+  for (uint64_t wv = ((uint64_t)blockIdx.x * blockDim.x + threadIdx.x) >> 6; wv < n_waves; wv += ((uint64_t)gridDim.x * blockDim.x) >> 6) {
+    const uint64_t r = wv * rows_per_wave + sub;
+    const bool mine = r < p.n_rows && j < S;                                   // the lane holds items of a row
+    PriorItem it; double c_sum = 0.0;
+    it.P = 0; it.gmax = 0;
+#pragma unroll
+    for (uint32_t g = 0; g <= MAX_PLOIDY; ++g) it.w[g] = 0.0;
+    uint32_t sum_p = 0;
+    if (mine) {
+        prior_load(p, tab, r, j, c_sum, it);
+        sum_p = it.P;
+        uint32_t k = 0;
+        for (uint64_t s = (uint64_t)j + 64; s < S; s += 64, ++k) {
+            PriorItem o; double c;
+            prior_load(p, tab, r, s, c, o);
+            sum_p += o.P;
+            if (k < p.staged) prior_stage_put(sw, sm, k, o);
+        }
+    }
+    sum_p = prior_segment_sum(sum_p, W);
+    PriorRow row = prior_row_start(sum_p);
+    while (__ballot(!row.done)) {
+        double x = prior_expected(it, row.f);
+        if (mine && !row.done) {
+            uint32_t k = 0;
+            for (uint64_t s = (uint64_t)j + 64; s < S; s += 64, ++k) {
+                PriorItem o; double c;
+                if (k < p.staged) prior_stage_get(sw, sm, k, o); else prior_load(p, tab, r, s, c, o);
+                x += prior_expected(o, row.f);
+            }
+        }
+        x = prior_segment_sum(x, W);
+        prior_step(row, x, sum_p);
+    }
+    uint32_t ns = 0, an = 0, ac = 0;
+    if (mine) {
+        for (uint64_t s = j; s < S; s += 64) {
+            PriorItem o = it; double c = c_sum;
+            if (s != j) prior_load(p, tab, r, s, c, o);
+            const PriorCall k = prior_call(o, row.f, c, p.min_support);
+            p.gt[r * S + s] = k.gt; p.gq[r * S + s] = k.gq;
+            if (k.gt != 0xFF) { ++ns; an += o.P; ac += k.gt; }
+        }
+    }
+    ns = prior_segment_sum(ns, W); an = prior_segment_sum(an, W); ac = prior_segment_sum(ac, W);
+    if (mine && j == 0) {
+        p.af[r] = row.f; p.steps[r] = row.steps;
+        p.site[r * 3] = ns; p.site[r * 3 + 1] = an; p.site[r * 3 + 2] = ac;
     }
   }
 }

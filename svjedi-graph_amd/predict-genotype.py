@@ -4,6 +4,7 @@
     predict-genotype.py -d P_informative_aln.json -v VCF --minsupport N -o P_genotype.vcf   (svjedi-graph.py:124)
     predict-genotype.py --cohort LIST -v VCF --minsupport N -o COHORT_genotype.vcf          (extension: one column per sample)
     predict-genotype.py --cohort LIST --cohort-ploidy FILE -v VCF ...                       (extension: a ploidy per sample and contig or region)
+    predict-genotype.py --cohort LIST --cohort-prior [--cohort-ploidy FILE] -v VCF ...      (extension: calls under the cohort's allele frequency, with GQ)
 """
 import argparse
 import os
@@ -33,6 +34,9 @@ def main():
     ap.add_argument("--cohort-ploidy", metavar="<cohortploidyfile>",
                     help="with --cohort: per-sample ploidy, 0..8, TAB-separated lines `SAMPLE<TAB>CHROM<TAB>PLOIDY` or "
                          "`SAMPLE<TAB>CHROM<TAB>FROM<TAB>TO<TAB>PLOIDY`, SAMPLE a name of the list or `*`; the first matching line wins, 2 otherwise (extension)")
+    ap.add_argument("--cohort-prior", action="store_true",
+                    help="with --cohort: estimate each row's allele frequency from all samples by EM under Hardy-Weinberg and call every sample at "
+                         "the maximum of likelihood x prior; FORMAT gains GQ, INFO gains EMAF and EMNC, DP / AD / PL stay as without it (extension)")
     args = ap.parse_args()
     if args.cohort is not None and args.aln is not None:
         ap.error("exactly one of -d and --cohort")
@@ -41,13 +45,15 @@ def main():
                  "(per-sample ploidy in a cohort: --cohort-ploidy)")
     if args.cohort_ploidy is not None and args.cohort is None:
         ap.error("--cohort-ploidy needs --cohort")
+    if args.cohort_prior and args.cohort is None:
+        ap.error("--cohort-prior needs --cohort")
     if args.joint_ins and (args.ploidy is not None or args.ploidy_file is not None):
         ap.error("--joint-ins is diploid only: it cannot be combined with --ploidy or --ploidy-file")
     out = "genotype_results.txt" if args.output is None else args.output[0]
     err = args.err[0] if args.err is not None else 0.00005
     from svjg import genotype
     if args.cohort is not None:
-        genotype.run_cohort(args.cohort, args.vcf, out, args.minsupport, err, ploidy_file=args.cohort_ploidy)
+        genotype.run_cohort(args.cohort, args.vcf, out, args.minsupport, err, ploidy_file=args.cohort_ploidy, prior=args.cohort_prior)
         return
     genotype.run(args.aln[0], args.vcf, out, args.minsupport, err, ploidy=args.ploidy, ploidy_file=args.ploidy_file, joint_ins=args.joint_ins)
 

@@ -91,6 +91,7 @@ _SIGS = {
     "svjg_cohort_get_counts": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_uint32, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint32]),
     "svjg_genotype_cohort": (ctypes.c_int, [ctypes.c_void_p] * 4 + [ctypes.c_uint64, ctypes.c_uint32, ctypes.c_double] + [ctypes.c_void_p] * 6),
     "svjg_genotype_cohort_ploidy": (ctypes.c_int, [ctypes.c_void_p] * 5 + [ctypes.c_uint32, ctypes.c_uint64, ctypes.c_uint32, ctypes.c_double] + [ctypes.c_void_p] * 6),
+    "svjg_genotype_cohort_prior": (ctypes.c_int, [ctypes.c_void_p] * 5 + [ctypes.c_uint32, ctypes.c_uint64, ctypes.c_uint32, ctypes.c_double] + [ctypes.c_void_p] * 9),
     "svjg_set_rows": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64]),
     "svjg_run_resident": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_uint64, ctypes.c_uint32, ctypes.c_double] + [ctypes.POINTER(ctypes.c_void_p)] * 5),
     "svjg_run_begin": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_uint64, ctypes.c_uint32, ctypes.c_double]),
@@ -590,6 +591,38 @@ class Context:
                                                        n, min_support, float(err), gt.ctypes.data, pl.ctypes.data, raw.ctypes.data,
                                                        done.ctypes.data, boundary.ctypes.data, site.ctypes.data))
         return gt, pl, raw, done, boundary, site
+
+    def genotype_cohort_prior(self, sv_type, slot, ok, ploidy, max_ploidy, min_support, err):
+        """The cohort call with an allele-frequency prior (svjg_genotype_cohort_prior).  ploidy: [n, S] in 0..max_ploidy, or None = every item
+        diploid (max_ploidy must then be 2).  -> (gt[n, S] = alt copies of the POSTERIOR call or 0xFF, pl[n, S, max_ploidy + 1], raw[n, S, 2],
+        genotyped[n, S], boundary[n, S] — pl, raw, genotyped and boundary as genotype_cohort / genotype_cohort_ploidy give them —, site[n, 3] =
+        NS, AN, AC of the posterior calls, gq[n, S] (0xFF: none), af[n] (NaN: no estimate), em_steps[n] (bit 31: not converged))"""
+        n = len(sv_type)
+        S = getattr(self, "_cohort", (0, 0))[0]
+        max_ploidy = int(max_ploidy)
+        if not 0 <= max_ploidy <= 0xFFFFFFFF:
+            raise SvjgError("max_ploidy: 1..%d" % MAX_PLOIDY)
+        width = min(max_ploidy, MAX_PLOIDY) + 1                  # (a max_ploidy out of range is the library's to refuse: nothing is written then)
+        sv_type, slot, ok = _row_inputs(sv_type, slot, ok)
+        if ploidy is not None:
+            ploidy = np.asarray(ploidy)
+            if ploidy.shape != (n, S) or (ploidy.size and (int(ploidy.min()) < 0 or int(ploidy.max()) > 255)):
+                raise SvjgError("ploidy: one value in 0..max_ploidy per (row, sample)")
+            ploidy = np.ascontiguousarray(ploidy, dtype=np.uint8)
+        gt = np.empty((n, S), dtype=np.uint8)
+        pl = np.empty((n, S, width), dtype=np.int64)
+        raw = np.empty((n, S, 2), dtype=np.uint32)
+        done = np.empty((n, S), dtype=np.uint8)
+        boundary = np.empty((n, S), dtype=np.uint8)
+        site = np.empty((n, 3), dtype=np.uint32)
+        gq = np.empty((n, S), dtype=np.uint8)
+        af = np.empty(n, dtype=np.float64)
+        steps = np.empty(n, dtype=np.uint32)
+        self._chk(self.lib.svjg_genotype_cohort_prior(self.h, sv_type.ctypes.data, slot.ctypes.data, ok.ctypes.data,
+                                                      None if ploidy is None else ploidy.ctypes.data, max_ploidy, n, min_support, float(err),
+                                                      gt.ctypes.data, pl.ctypes.data, raw.ctypes.data, done.ctypes.data, boundary.ctypes.data,
+                                                      site.ctypes.data, gq.ctypes.data, af.ctypes.data, steps.ctypes.data))
+        return gt, pl, raw, done, boundary, site, gq, af, steps
 
     def set_rows(self, sv_type, slot, ok):
         """the VCF rows' input arrays of genotype(), left on the device for run_resident()"""

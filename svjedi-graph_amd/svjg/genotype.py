@@ -302,16 +302,18 @@ def gt_text_ploidy(P, g):
     return "/".join("0" * (P - g) + "1" * g)
 
 
-def sample_column(svtype_code, P, g, pl, ref, alt, done):
+def sample_column(svtype_code, P, g, pl, ref, alt, done, gq=None):
     """One sample column GT:DP:AD:PL of every writer.  P: the item's ploidy (0: `.:0:0,0:.`); g: the alt copies of the call, NO_CALL = 0xFF for
     none (at P >= 3 a 3 is a call: the diploid callers translate their 3 themselves); pl: at least P + 1 integers; ref, alt: the raw counts;
-    done false: P dots as GT, no counts, P + 1 dots as PL."""
+    done false: P dots as GT, no counts, P + 1 dots as PL.  gq (--cohort-prior; None: no such field): one more field, GQ, `.` where there is
+    no call (NO_CALL)."""
+    tail = "" if gq is None else ":." if gq == NO_CALL or g == NO_CALL or P == 0 or not done else ":%d" % gq
     if P == 0:
-        return ".:0:0,0:."
+        return ".:0:0,0:." + tail
     if not done:
-        return "%s:0:0,0:%s" % ("/".join("." * P), ",".join("." * (P + 1)))
+        return "%s:0:0,0:%s%s" % ("/".join("." * P), ",".join("." * (P + 1)), tail)
     dp, ad = _fmt_counts(svtype_code, ref, alt)
-    return "%s:%s:%s:%s" % (gt_text_ploidy(P, g), dp, ad, ",".join(map(str, pl[:P + 1])))
+    return "%s:%s:%s:%s%s" % (gt_text_ploidy(P, g), dp, ad, ",".join(map(str, pl[:P + 1])), tail)
 
 
 def _write_rows(out_path, rows, header, columns, info=None):
@@ -329,9 +331,10 @@ def _write_rows(out_path, rows, header, columns, info=None):
             out.write(prefix + "\t" + "\t".join(columns(v)) + "\n")
 
 
-def _item_columns(rows, ploidy, gt, pl, raw, done):
+def _item_columns(rows, ploidy, gt, pl, raw, done, gq=None):
     """-> (columns(v) for _write_rows: GT:DP:AD:PL and one sample_column per sample, the number of genotyped rows per sample).  The arrays hold
-    one item per row ([n]: one sample) or [n, S]; ploidy None: diploid arrays, whose gt says 3 for no call"""
+    one item per row ([n]: one sample) or [n, S]; ploidy None: diploid arrays, whose gt says 3 for no call; gq ([n, S], --cohort-prior): the
+    fifth field, GT:DP:AD:PL:GQ"""
     gt, pl, raw, done = np.asarray(gt), np.asarray(pl), np.asarray(raw), np.asarray(done)
     if ploidy is None:
         ploidy, gt = np.full(gt.shape, 2, np.uint8), np.where(gt == 3, NO_CALL, gt)
@@ -339,11 +342,13 @@ def _item_columns(rows, ploidy, gt, pl, raw, done):
     if gt.ndim == 1:
         ploidy, gt, pl, raw, done = ploidy[:, None], gt[:, None], pl[:, None], raw[:, None], done[:, None]
     n_done = np.count_nonzero((done != 0) & (ploidy != 0), axis=0).tolist()
+    if gq is not None:
+        gq = np.asarray(gq)
 
     def columns(v):
         t = int(rows.sv_type[v])
-        items = zip(ploidy[v].tolist(), gt[v].tolist(), pl[v].tolist(), raw[v].tolist(), done[v].tolist())
-        return ["GT:DP:AD:PL"] + [sample_column(t, P, g, p, r[0], r[1], d) for P, g, p, r, d in items]
+        items = zip(ploidy[v].tolist(), gt[v].tolist(), pl[v].tolist(), raw[v].tolist(), done[v].tolist(), gq[v].tolist() if gq is not None else [None] * len(gt[v]))
+        return ["GT:DP:AD:PL" if gq is None else "GT:DP:AD:PL:GQ"] + [sample_column(t, P, g, p, r[0], r[1], d, q) for P, g, p, r, d, q in items]
     return columns, n_done
 
 
@@ -501,6 +506,7 @@ COHORT_INFO_LINES = (
     '##INFO=<ID=AF,Number=A,Type=Float,Description="Allele frequency in called genotypes: AC / AN">\n'
 )
 _SITE_TAGS = ("NS=", "AN=", "AC=", "AF=")
+_EM_KEYS = ("EMAF", "EMNC")
 COHORT_ITEM_BYTES = 37             # svjg.h: what one (row, sample) item takes in a svjg_genotype_cohort call
 COHORT_CALL_BYTES = 1 << 30
 
@@ -550,10 +556,14 @@ def _cohort_header(header, names):
     return COHORT_INFO_LINES + header.replace("\tFORMAT\tSAMPLE\n", "\tFORMAT\t" + "\t".join(names) + "\n")
 
 
-def cohort_info(info, ns, ac, an=None):
+def cohort_info(info, ns, ac, an=None, em=None):
     """the INFO column of a cohort row: the input's without any NS= / AN= / AC= / AF= field (whole fields, exact key), a lone `.` replaced,
-    then NS, AN (2 NS unless given: the called samples' ploidies summed, --cohort-ploidy), AC and, when AN > 0, AF = "%.6g" % (AC / AN)"""
+    then NS, AN (2 NS unless given: the called samples' ploidies summed, --cohort-ploidy), AC and, when AN > 0, AF = "%.6g" % (AC / AN).
+    em (--cohort-prior): (f, not_converged) of the row's EM — the input's EMAF= and EMNC fields are dropped too, EMAF = "%.6g" % f follows
+    unless f is NaN (no estimate), and the flag EMNC when the step cap was reached"""
     keep = [f for f in info.split(";") if not f.startswith(_SITE_TAGS)]
+    if em is not None:
+        keep = [f for f in keep if f.split("=", 1)[0] not in _EM_KEYS]
     if keep == ["."]:
         keep = []
     if an is None:
@@ -561,6 +571,12 @@ def cohort_info(info, ns, ac, an=None):
     keep += ["NS=%d" % ns, "AN=%d" % an, "AC=%d" % ac]
     if an > 0:
         keep.append("AF=%s" % ("%.6g" % (ac / an)))
+    if em is not None:
+        f, not_converged = em
+        if f == f:
+            keep.append("EMAF=%s" % ("%.6g" % f))
+        if not_converged:
+            keep.append("EMNC")
     return ";".join(keep)
 
 
@@ -580,18 +596,19 @@ def cohort_chunk_rows(n_samples):
 def _cohort_rows(call, rows, step, empty, min_support, err, ploidy=None):
     """The one cohort driver: the rows of a VcfRows against the context's cohort matrix in chunks of `step` rows, call(lo, hi, min_support,
     err) -> (gt, pl, raw, done, boundary, site) per chunk -> (gt, pl, raw, done, site) over all rows (empty: the same for no row at all), the
-    flagged items recomputed (the GT does not depend on the PL integers: the site words stay as the kernel gave them)"""
+    flagged items recomputed (the GT does not depend on the PL integers: the site words stay as the kernel gave them).  Whatever a call
+    returns behind site (--cohort-prior: gq, af, em_steps) is joined over the chunks and returned behind site as well"""
     min_support, call_err, bad_err = _call_args(min_support, err)
     parts = []
     for at in range(0, len(rows.sv_type), step):
-        gt, pl, raw, done, boundary, site = call(at, at + step, min_support, call_err)
+        gt, pl, raw, done, boundary, site, *more = call(at, at + step, min_support, call_err)
         if bad_err and done.any():
             raise ValueError("math domain error")               # (as genotype_with_counts)
         recompute_flagged(rows.sv_type[at:at + step], pl, raw, done, boundary, err, None if ploidy is None else ploidy[at:at + step])
-        parts.append((gt, pl, raw, done, site))
+        parts.append((gt, pl, raw, done, site, *more))
     if not parts:
         return empty
-    return tuple(np.concatenate([p[k] for p in parts]) for k in range(5))
+    return tuple(np.concatenate([p[k] for p in parts]) for k in range(len(parts[0])))
 
 
 def _cohort_empty(S, n_pl, n_site):
@@ -676,11 +693,54 @@ def write_vcf_cohort_ploidy(out_path, rows, names, ploidy, gt, pl, raw, done, si
     return n_done
 
 
-def run_cohort(list_path, vcf_path, out_path, min_support=3, err=0.00005, device=0, ploidy_file=None):
+# ---- cohort with an allele-frequency prior (--cohort LIST --cohort-prior [--cohort-ploidy FILE]): svjg_genotype_cohort_prior ----
+
+COHORT_PRIOR_INFO_LINES = (
+    '##INFO=<ID=EMAF,Number=A,Type=Float,Description="Allele frequency estimated from all samples\' genotype likelihoods by EM under Hardy-Weinberg">\n'
+    '##INFO=<ID=EMNC,Number=0,Type=Flag,Description="The EM for EMAF reached its step limit without converging">\n'
+)
+_GQ_LINE = '##FORMAT=<ID=GQ,Number=1,Type=Integer,Description="Genotype quality: -10 log10 of the posterior probability that the call is wrong, at most 99">\n'
+EM_NOT_CONVERGED = 1 << 31         # svjg.h: bit 31 of a row's em_steps word
+
+
+def cohort_prior_chunk_rows(n_samples, max_ploidy):
+    """rows per svjg_genotype_cohort_prior call: n_rows x (S x (8 (max_ploidy + 1) + 13) + 46) bytes stays under 1 GiB"""
+    return max(1, COHORT_CALL_BYTES // ((8 * (int(max_ploidy) + 1) + 13) * max(1, int(n_samples)) + 46))
+
+
+def genotype_cohort_prior_rows(ctx, rows, n_samples, ploidy, min_support, err, step=None):
+    """the cohort call with the allele-frequency prior over all rows, ploidy[n, S] or None (diploid) -> (gt = the posterior calls (0xFF: none),
+    pl, raw, done, site[n, 3] = NS, AN, AC of the posterior calls, gq[n, S], af[n], em_steps[n]); step: rows per call (None: what fits 1 GiB)"""
+    S = int(n_samples)
+    if ploidy is not None:
+        ploidy = np.ascontiguousarray(ploidy, dtype=np.uint8)
+    max_ploidy = 2 if ploidy is None else max(1, int(ploidy.max())) if ploidy.size else 1
+    empty = _cohort_empty(S, max_ploidy + 1, 3) + (np.zeros((0, S), np.uint8), np.zeros(0, np.float64), np.zeros(0, np.uint32))
+    return _cohort_rows(lambda lo, hi, ms, e: ctx.genotype_cohort_prior(rows.sv_type[lo:hi], rows.slot[lo:hi], rows.ok[lo:hi],
+                                                                        None if ploidy is None else ploidy[lo:hi], max_ploidy, ms, e),
+                        rows, cohort_prior_chunk_rows(S, max_ploidy) if step is None else int(step), empty, min_support, err, ploidy)
+
+
+def write_vcf_cohort_prior(out_path, rows, names, ploidy, gt, pl, raw, done, site, gq, af, em_steps):
+    """write_vcf_cohort / write_vcf_cohort_ploidy (ploidy None: diploid, `Number=3`) with the posterior calls: one more FORMAT field, GQ, and
+    EMAF / EMNC in INFO (gt: alt copies or 0xFF in either case; site: [n, 3] = NS, AN, AC) -> the number of genotyped rows of every sample"""
+    gt = np.asarray(gt)
+    columns, n_done = _item_columns(rows, np.full(gt.shape, 2, np.uint8) if ploidy is None else ploidy, gt, pl, raw, done, gq)
+    header = FORMAT_HEADER if ploidy is None else FORMAT_HEADER.replace(_PL_3, _PL_G)
+    header = header.replace("#CHROM\t", _GQ_LINE + "#CHROM\t")
+    _write_rows(out_path, rows, COHORT_INFO_LINES + COHORT_PRIOR_INFO_LINES + _cohort_header(header, names)[len(COHORT_INFO_LINES):], columns,
+                lambda v, info: cohort_info(info, int(site[v, 0]), int(site[v, 2]), int(site[v, 1]),
+                                            em=(float(af[v]), bool(int(em_steps[v]) & EM_NOT_CONVERGED))))
+    return n_done
+
+
+def run_cohort(list_path, vcf_path, out_path, min_support=3, err=0.00005, device=0, ploidy_file=None, prior=False):
     """predict-genotype.py --cohort: the samples of a cohort list (load_cohort_list), one multi-sample VCF.  Sample column s is what the
     reference writes as SAMPLE for sample s alone; INFO gains NS, AN, AC and AF.  ploidy_file (--cohort-ploidy, load_cohort_ploidy_file): a
     ploidy per sample and contig or region; column s is then what --ploidy-file with the sample's lines writes for sample s alone, and AN is
-    the called samples' ploidies summed.  -> the number of genotyped rows of every sample"""
+    the called samples' ploidies summed.  prior (--cohort-prior): GT is the call under the row's allele frequency, estimated from all samples by EM
+    (svjg_genotype_cohort_prior), with GQ beside it and EMAF / EMNC in INFO; DP, AD and PL stay those of the plain run.  -> the number of genotyped
+    rows of every sample"""
     from . import capi, filter as flt
     samples = load_cohort_list(list_path)                        # (raises before any output exists)
     names = [name for name, _ in samples]
@@ -697,13 +757,17 @@ def run_cohort(list_path, vcf_path, out_path, min_support=3, err=0.00005, device
         ctx.cohort_alloc(len(samples), len(keys))
         for s, (slots, counts) in enumerate(per):
             ctx.cohort_set_counts(s, slots, counts)
-        if ploidy is None:
+        if prior:
+            gt, pl, raw, done, site, gq, af, em_steps = genotype_cohort_prior_rows(ctx, rows, len(samples), ploidy, min_support, err)
+        elif ploidy is None:
             gt, pl, raw, done, site = genotype_cohort_rows(ctx, rows, len(samples), min_support, err)
         else:
             gt, pl, raw, done, site = genotype_cohort_ploidy_rows(ctx, rows, ploidy, min_support, err)
     finally:
         ctx.close()
-    if ploidy is None:
+    if prior:
+        n_done = write_vcf_cohort_prior(out_path, rows, names, ploidy, gt, pl, raw, done, site, gq, af, em_steps)
+    elif ploidy is None:
         n_done = write_vcf_cohort(out_path, rows, names, gt, pl, raw, done, site)
     else:
         n_done = write_vcf_cohort_ploidy(out_path, rows, names, ploidy, gt, pl, raw, done, site)

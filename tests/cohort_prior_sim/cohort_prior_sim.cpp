@@ -1,0 +1,107 @@
+// TEST HARNESS ONLY (never shipped, never loaded by the product): the per-item routines of the cohort call with an allele-frequency prior
+// (svjg_geno.h: prior_item, prior_expected, prior_call, prior_step, prior_segment_width, cohort_prior_layout) compiled with g++, and a row's
+// EM run sequentially over its samples (the kernel sums the same x through a butterfly: another order of the same additions).  With
+// -DCOHORT_PRIOR_SIM_MAIN it is a stand-alone program (for -fsanitize=address,undefined) that runs random rows and checks what holds without a model.
+#define SVJG_HD inline
+#include "../../svjedi-graph_amd/csrc/svjg_geno.h"
+#include <stdio.h>
+#include <initializer_list>
+
+using namespace svjg;
+
+static void load(uint32_t type, const uint32_t *raw, const uint8_t *done, const uint8_t *ploidy, uint64_t s, const double *tab, double &c_sum, PriorItem &it) {
+    const uint32_t P = done[s] ? (ploidy ? ploidy[s] : 2u) : 0u;
+    it.P = 0; it.gmax = 0; c_sum = 0.0;
+    for (uint32_t g = 0; g <= MAX_PLOIDY; ++g) it.w[g] = 0.0;
+    if (P >= 1 && P <= MAX_PLOIDY) prior_item(type, raw[s * 2], raw[s * 2 + 1], P, tab + ploidy_tab_at(P, 0), tab + PLOIDY_TAB + ploidy_tab_at(P, 0), c_sum, it);
+}
+
+// One row of S samples: raw[S][2], done[S], ploidy[S] or NULL (2 everywhere) -> *f (NaN: no estimate), *steps (the kernel's word: bit 31 = not
+// converged), gt[S], gq[S], site[3] = NS, AN, AC
+extern "C" void cprsim_row(uint32_t type, const uint32_t *raw, const uint8_t *done, const uint8_t *ploidy, uint64_t S, double err, uint32_t min_support,
+                           double *f, uint32_t *steps, uint8_t *gt, uint8_t *gq, uint32_t *site) {
+    double tab[2 * PLOIDY_TAB];
+    ploidy_log_table(err, tab);
+    uint32_t sum_p = 0;
+    for (uint64_t s = 0; s < S; ++s) { PriorItem it; double c; load(type, raw, done, ploidy, s, tab, c, it); sum_p += it.P; }
+    PriorRow row = prior_row_start(sum_p);
+    while (!row.done) {
+        double x = 0.0;
+        for (uint64_t s = 0; s < S; ++s) { PriorItem it; double c; load(type, raw, done, ploidy, s, tab, c, it); x += prior_expected(it, row.f); }
+        prior_step(row, x, sum_p);
+    }
+    site[0] = site[1] = site[2] = 0;
+    for (uint64_t s = 0; s < S; ++s) {
+        PriorItem it; double c;
+        load(type, raw, done, ploidy, s, tab, c, it);
+        const PriorCall k = prior_call(it, row.f, c, min_support);
+        gt[s] = k.gt; gq[s] = k.gq;
+        if (k.gt != 0xFF) { ++site[0]; site[1] += it.P; site[2] += k.gt; }
+    }
+    *f = row.f; *steps = row.steps;
+}
+
+// the weights of one item: w[9] = C(P, g) 10^d_g, -> the item's ploidy as the EM sees it (0: it takes no part); *gmax
+extern "C" uint32_t cprsim_item(uint32_t type, uint32_t ref, uint32_t alt, uint32_t P, double err, double *w, uint32_t *gmax) {
+    double tab[2 * PLOIDY_TAB];
+    ploidy_log_table(err, tab);
+    const uint32_t raw[2] = {ref, alt}; const uint8_t done = 1, p = (uint8_t)P;
+    PriorItem it; double c;
+    load(type, raw, &done, &p, 0, tab, c, it);
+    for (uint32_t g = 0; g <= MAX_PLOIDY; ++g) w[g] = it.w[g];
+    *gmax = it.gmax;
+    return it.P;
+}
+
+extern "C" uint32_t cprsim_width(uint64_t S) { return prior_segment_width(S); }
+extern "C" void cprsim_constants(double *tol, uint32_t *max_it, uint32_t *flag_bit, double *f_bound) { *tol = EM_TOL; *max_it = EM_MAX_IT; *flag_bit = EM_NOT_CONVERGED; *f_bound = EM_F_BOUND; }
+
+// cohort_prior_layout(n_rows, S, max_ploidy, per_item) -> out[19]: pl, raw, gt, flags, boundary, gq, af, psite, steps, site, maxn, in_at, logtab, slot, type, ok,
+// ploidy, total, in_bytes
+extern "C" void cprsim_layout(uint64_t n_rows, uint64_t S, uint32_t max_ploidy, int per_item, uint64_t *out) {
+    const CohortPriorLayout L = cohort_prior_layout(n_rows, S, max_ploidy, per_item != 0);
+    const uint64_t v[19] = {L.pl, L.raw, L.gt, L.flags, L.boundary, L.gq, L.af, L.psite, L.steps, L.site, L.maxn, L.in_at, L.logtab, L.in.slot, L.in.type, L.in.ok,
+                            L.ploidy, L.total, L.in_bytes};
+    for (int i = 0; i < 19; ++i) out[i] = v[i];
+}
+
+#ifdef COHORT_PRIOR_SIM_MAIN
+#include <vector>
+int main() {
+    const uint64_t sizes[11] = {1, 3, 4, 5, 31, 32, 33, 63, 64, 65, 130};
+    uint64_t rows = 0, bad = 0, x = 88172645463325252ull;
+    auto next = [&] { x ^= x << 13; x ^= x >> 7; x ^= x << 17; return x; };
+    for (uint64_t S : sizes)
+        for (int mode = 0; mode < 3; ++mode)                                          // diploid, mixed ploidy 0..8, deep counts
+            for (int k = 0; k < 40; ++k) {
+                std::vector<uint32_t> raw(S * 2); std::vector<uint8_t> done(S), pld(S), gt(S), gq(S), gt2(S), gq2(S);
+                for (uint64_t s = 0; s < S; ++s) {
+                    const uint64_t v = next();
+                    raw[s * 2] = (uint32_t)(v % (mode == 2 ? 5001 : (v >> 40) % 3 ? 61 : 5)); raw[s * 2 + 1] = (uint32_t)((v >> 16) % ((v >> 44) % 3 ? 61 : 5));
+                    done[s] = (v >> 32) % 5 != 0; pld[s] = (uint8_t)((v >> 36) % 9);
+                }
+                double f, f2; uint32_t steps, steps2, site[3], site2[3];
+                const uint32_t type = (uint32_t)(next() % 4), ms = k & 1 ? 3 : 0;
+                cprsim_row(type, raw.data(), done.data(), mode == 1 ? pld.data() : nullptr, S, 5e-5, ms, &f, &steps, gt.data(), gq.data(), site);
+                cprsim_row(type, raw.data(), done.data(), mode == 1 ? pld.data() : nullptr, S, 5e-5, ms, &f2, &steps2, gt2.data(), gq2.data(), site2);
+                ++rows;
+                uint32_t ns = 0, an = 0, ac = 0, part = 0;
+                for (uint64_t s = 0; s < S; ++s) {
+                    const uint32_t P = done[s] ? (mode == 1 ? pld[s] : 2u) : 0u;
+                    if (P && raw[s * 2] + raw[s * 2 + 1]) ++part;
+                    if (gt[s] != 0xFF) { ++ns; an += P; ac += gt[s]; if (gt[s] > P || gq[s] > 99 || !P) ++bad; } else if (gq[s] != 0xFF) ++bad;
+                    if (gt[s] != gt2[s] || gq[s] != gq2[s]) ++bad;
+                }
+                if (ns != site[0] || an != site[1] || ac != site[2] || steps != steps2 || site[0] != site2[0]) ++bad;
+                if (part ? !(f >= 0.0 && f <= 1.0 && f == f2 && (steps & ~EM_NOT_CONVERGED) >= 1 && (steps & ~EM_NOT_CONVERGED) <= EM_MAX_IT) : !(f != f && steps == 0)) ++bad;
+            }
+    for (uint64_t n_rows : {1, 7, 1000}) for (uint64_t S : {1, 3, 64, 65}) for (uint32_t mp : {1u, 2u, 8u}) for (int per : {0, 1}) {
+        uint64_t L[19];
+        cprsim_layout(n_rows, S, mp, per, L);
+        if (L[9] % 8 || L[6] % 8 || L[10] != L[9] + (per ? 16 : 8) * n_rows || L[11] != L[10] + 8 || L[13] + 6 * n_rows + (per ? n_rows * S : 0) != L[11] + L[18]) ++bad;
+    }
+    for (uint64_t S : sizes) { const uint32_t w = cprsim_width(S); if (w < (S < 64 ? S : 64) || w > 64 || (w & (w - 1)) || (w > 1 && w / 2 >= (S < 64 ? S : 64))) ++bad; }
+    printf("cohort_prior_sim %s: %llu rows, %llu checks failed\n", bad ? "FAILED" : "ok", (unsigned long long)rows, (unsigned long long)bad);
+    return bad ? 1 : 0;
+}
+#endif
