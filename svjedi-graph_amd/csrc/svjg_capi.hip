@@ -78,9 +78,9 @@ constexpr int STAGE_THREADS = 4;
 constexpr uint64_t STAGE_PIECE = 8ull << 20;
 
 // The device block of a step-by-step genotype call and its pinned host twin (genotype_leg).  Every call has a block of its own: svjg_genotype_view
-// hands out pointers into BLOCK_ROWS' twin and svjg_genotype_boundary reads it later, and both must survive calls of the other four.
+// hands out pointers into BLOCK_ROWS' twin and svjg_genotype_boundary reads it later, and both must survive calls of the other five.
 struct LegBlock { void *d = nullptr;  uint64_t d_cap = 0;  void *h = nullptr;  uint64_t h_cap = 0; };
-enum { BLOCK_ROWS, BLOCK_PLOIDY, BLOCK_SITES, BLOCK_COHORT, BLOCK_COHORT_PLOIDY, BLOCK_COHORT_PRIOR, LEG_BLOCKS };   // rows_layout, ploidy_layout, sites_layout, cohort_layout, cohort_ploidy_layout, cohort_prior_layout (svjg_geno.h)
+enum { BLOCK_ROWS, BLOCK_PLOIDY, BLOCK_SITES, BLOCK_COHORT, BLOCK_COHORT_PLOIDY, BLOCK_COHORT_PRIOR, LEG_BLOCKS };   // rows_layout, ploidy_layout, sites_layout, and cohort_layout for the three cohort blocks (svjg_geno.h)
 
 // slots the passes of svjg_run_begin rotate through: two may be in flight, and the one the NEXT pass will use is zeroed while the newest computes
 constexpr int RUN_SLOTS = 3;
@@ -1045,7 +1045,7 @@ static int launch_genotype(svjg_ctx *c, GenoArgs &a) {
 // d_back come back to h_back (what the caller reads, the pair included) and the check repeats.  relaunch_first: the launch itself is still
 // owed (svjg_run_end behind a repeated pass).  max_n is the maximum over ALL rows, so one growth is enough; the second only guards this reasoning.
 // launch(): the kernel over all its items again with the table at hand; it zeroes again whatever the kernel adds to (launch_genotype,
-// launch_ploidy, launch_sites, launch_cohort, launch_cohort_ploidy).
+// launch_ploidy, launch_sites, launch_cohort).
 template <class Launch>
 static int settle_launch(svjg_ctx *c, const unsigned int *h_maxn, void *h_back, const void *d_back, uint64_t bytes, bool relaunch_first, Launch launch) {
     for (int growths = 0;; relaunch_first = false) {
@@ -1293,96 +1293,25 @@ extern "C" int svjg_cohort_get_counts(svjg_ctx *c, uint32_t sample, uint32_t *ou
     return 0;
 }
 
-// svjg_genotype_cohort goes through genotype_leg in BLOCK_COHORT.  launch_cohort: all items with the table at hand.  The site words lie right in
-// front of the max_n pair (cohort_layout): both are zeroed in front of EVERY launch — settle_launch runs the kernel over all items again after
-// the table grew, and the atomics would add to the first launch's sums.
-// Blocks: enough for eight waves on every SIMD (the kernel holds 64 VGPRs or fewer: svjg.h), the rest in strides of the grid.
-static int launch_cohort(svjg_ctx *c, GenoCohortArgs &p) {
-    p.g.logfact = c->d_logfact; p.g.logfact_n = c->logfact_n;
-    HIPCHK(c, hipMemsetAsync(p.site, 0, p.g.n_rows * 8 + 8, c->stream));
-    const uint64_t n_items = p.g.n_rows * p.n_samples, blocks = (n_items + TPB - 1) / TPB, cap = (uint64_t)c->n_cu * 8;
-    hipLaunchKernelGGL(k_genotype_cohort, dim3((uint32_t)(blocks < cap ? blocks : cap)), dim3(TPB), 0, c->stream, p);
-    HIPCHK(c, hipGetLastError());
-    return 0;
-}
-
-extern "C" int svjg_genotype_cohort(svjg_ctx *c, const uint8_t *sv_type, const uint32_t *slot, const uint8_t *ok, uint64_t n_rows,
-                                    uint32_t min_support, double err, uint8_t *gt, int64_t *pl, uint32_t *raw, uint8_t *genotyped,
-                                    uint8_t *boundary, uint32_t *site) {
-    if (!c) return SVJG_E_ARG;
-    if (!c->d_cm) { c->err = "no cohort matrix"; return SVJG_E_ARG; }
-    if (n_rows == 0) return 0;
-    if (!sv_type || !slot || !ok || !gt || !pl || !raw || !genotyped || !boundary || !site) return SVJG_E_ARG;
-    const uint64_t S = c->cohort_samples;
-    if (n_rows > (1ull << 40) / S) { c->err = "too many items for one call: genotype the rows in chunks"; return SVJG_E_ARG; }
-    HIPCHK(c, hipSetDevice(c->device));
-    const CohortLayout L = cohort_layout(n_rows, S);
-    const uint64_t n = n_rows * S;
-    const int rc = genotype_leg(c, c->leg[BLOCK_COHORT], L,
-        [&](uint8_t *hb) { stage_rows(hb, L.in, sv_type, slot, ok, n_rows); },
-        [&](uint8_t *base) {
-            GenoCohortArgs p{block_geno_args(c, c->d_cm, base, L, n_rows, min_support, err), c->d_cpresent, c->cohort_samples, (unsigned long long *)(base + L.site)};
-            p.g.n_slots = c->cohort_slots;                        // (the matrix's slots, not the count vector's)
-            return launch_cohort(c, p);
-        });
-    if (rc) return rc;
-    const uint8_t *hb = (const uint8_t *)c->leg[BLOCK_COHORT].h;
-    memcpy(pl, hb + L.pl, n * 3 * sizeof *pl); memcpy(raw, hb + L.raw, n * 2 * sizeof *raw);
-    memcpy(gt, hb + L.gt, n); memcpy(genotyped, hb + L.flags, n); memcpy(boundary, hb + L.boundary, n); memcpy(site, hb + L.site, n_rows * 8);
-    return 0;
-}
-
-// svjg_genotype_cohort_ploidy goes through genotype_leg in BLOCK_COHORT_PLOIDY: the call's logarithms and the items' ploidy bytes go in with the
-// three input arrays.  launch_cohort_ploidy: as launch_cohort, the row's TWO site words and the max_n pair zeroed in front of every launch.
-// Blocks: a block is four waves, one per SIMD, and a SIMD holds min(8, 512 / VGPRs) waves of a kernel: this one takes 96 VGPRs (the compiler's
-// resource remark), so five, not launch_cohort's eight; the rest in strides of the grid.
+// The three cohort calls go through genotype_leg, each in its own block (svjg.h: a call does not disturb another's), by ONE leg: cohort_call.
+// launch_cohort: all items with the table at hand.  The site words lie right in front of the max_n pair (cohort_layout): both are zeroed in front
+// of EVERY launch — settle_launch runs the kernel over all items again after the table grew, and the atomics would add to the first launch's sums.
+// Blocks: a block is four waves, one per SIMD, and a SIMD holds min(8, 512 / VGPRs) waves of a kernel: eight of k_genotype_cohort (64 VGPRs:
+// svjg.h), five of k_genotype_cohort_ploidy (96 VGPRs: the compiler's resource remark); the rest in strides of the grid.
 constexpr uint64_t COHORT_PLOIDY_WAVES = 5;
-static int launch_cohort_ploidy(svjg_ctx *c, GenoCohortPloidyArgs &p) {
-    p.c.g.logfact = c->d_logfact; p.c.g.logfact_n = c->logfact_n;
-    HIPCHK(c, hipMemsetAsync(p.c.site, 0, p.c.g.n_rows * 16 + 8, c->stream));
-    const uint64_t n_items = p.c.g.n_rows * p.c.n_samples, blocks = (n_items + TPB - 1) / TPB, cap = (uint64_t)c->n_cu * COHORT_PLOIDY_WAVES;
-    hipLaunchKernelGGL(k_genotype_cohort_ploidy, dim3((uint32_t)(blocks < cap ? blocks : cap)), dim3(TPB), 0, c->stream, p);
+static int launch_cohort(svjg_ctx *c, GenoCohortArgs &p, bool per_item) {
+    p.g.logfact = c->d_logfact; p.g.logfact_n = c->logfact_n;
+    HIPCHK(c, hipMemsetAsync(p.site, 0, p.g.n_rows * (per_item ? 16 : 8) + 8, c->stream));
+    const uint64_t n_items = p.g.n_rows * p.n_samples, blocks = (n_items + TPB - 1) / TPB, cap = (uint64_t)c->n_cu * (per_item ? COHORT_PLOIDY_WAVES : 8);
+    const dim3 grid((uint32_t)(blocks < cap ? blocks : cap));
+    if (per_item) hipLaunchKernelGGL(k_genotype_cohort_ploidy, grid, dim3(TPB), 0, c->stream, p);
+    else hipLaunchKernelGGL(k_genotype_cohort, grid, dim3(TPB), 0, c->stream, p);
     HIPCHK(c, hipGetLastError());
     return 0;
 }
 
-extern "C" int svjg_genotype_cohort_ploidy(svjg_ctx *c, const uint8_t *sv_type, const uint32_t *slot, const uint8_t *ok, const uint8_t *ploidy,
-                                           uint32_t max_ploidy, uint64_t n_rows, uint32_t min_support, double err, uint8_t *gt, int64_t *pl,
-                                           uint32_t *raw, uint8_t *genotyped, uint8_t *boundary, uint32_t *site) {
-    if (!c) return SVJG_E_ARG;
-    if (!c->d_cm) { c->err = "no cohort matrix"; return SVJG_E_ARG; }
-    if (n_rows == 0) return 0;
-    if (!sv_type || !slot || !ok || !ploidy || !gt || !pl || !raw || !genotyped || !boundary || !site) { c->err = "a null array"; return SVJG_E_ARG; }
-    if (max_ploidy < 1 || max_ploidy > MAX_PLOIDY) { c->err = "max_ploidy is not in 1..SVJG_MAX_PLOIDY"; return SVJG_E_ARG; }
-    const uint64_t S = c->cohort_samples;
-    if (S >= (1ull << 28)) { c->err = "too many samples: AN would not fit 32 bits"; return SVJG_E_ARG; }
-    if (n_rows > (1ull << 40) / S) { c->err = "too many items for one call: genotype the rows in chunks"; return SVJG_E_ARG; }
-    const uint64_t n = n_rows * S;
-    for (uint64_t i = 0; i < n; ++i)
-        if (ploidy[i] > max_ploidy) { c->err = "ploidy above max_ploidy"; return SVJG_E_ARG; }
-    HIPCHK(c, hipSetDevice(c->device));
-    const CohortPloidyLayout L = cohort_ploidy_layout(n_rows, S, max_ploidy);
-    const int rc = genotype_leg(c, c->leg[BLOCK_COHORT_PLOIDY], L,
-        [&](uint8_t *hb) { ploidy_log_table(err, (double *)(hb + L.logtab)); stage_rows(hb, L.in, sv_type, slot, ok, n_rows); memcpy(hb + L.ploidy, ploidy, n); },   // (host libm, as geno_args' three)
-        [&](uint8_t *base) {
-            GenoCohortPloidyArgs p{{block_geno_args(c, c->d_cm, base, L, n_rows, min_support, err), c->d_cpresent, c->cohort_samples, (unsigned long long *)(base + L.site)},
-                                   base + L.ploidy, (const double *)(base + L.logtab), max_ploidy};
-            p.c.g.n_slots = c->cohort_slots;                      // (the matrix's slots, not the count vector's)
-            return launch_cohort_ploidy(c, p);
-        });
-    if (rc) return rc;
-    const uint8_t *hb = (const uint8_t *)c->leg[BLOCK_COHORT_PLOIDY].h;
-    memcpy(pl, hb + L.pl, n * (max_ploidy + 1) * sizeof *pl); memcpy(raw, hb + L.raw, n * 2 * sizeof *raw);
-    memcpy(gt, hb + L.gt, n); memcpy(genotyped, hb + L.flags, n); memcpy(boundary, hb + L.boundary, n);
-    const uint64_t *w = (const uint64_t *)(hb + L.site);          // NS | AC << 32, AN per row -> NS, AN, AC
-    for (uint64_t r = 0; r < n_rows; ++r) { site[r * 3] = (uint32_t)w[r * 2]; site[r * 3 + 1] = (uint32_t)w[r * 2 + 1]; site[r * 3 + 2] = (uint32_t)(w[r * 2] >> 32); }
-    return 0;
-}
-
-// svjg_genotype_cohort_prior goes through genotype_leg in BLOCK_COHORT_PRIOR: the cohort kernel of the call's kind (ploidy == NULL: k_genotype_cohort,
-// else k_genotype_cohort_ploidy), launched as launch_cohort / launch_cohort_ploidy launch it — the table's grow-and-rerun is theirs —, and behind it
-// k_cohort_prior on what it left in the block.  Blocks: a wave holds 64 / width rows (prior_segment_width), a block four waves, eight blocks a unit
-// at the most; the rest in strides of the grid.
+// k_cohort_prior on what the cohort kernel left in the block.  Blocks: a wave holds 64 / width rows (prior_segment_width), a block four waves, eight
+// blocks a unit at the most; the rest in strides of the grid.
 constexpr bool PRIOR_STAGE_DEFAULT = true;                          // measured: see k_cohort_prior
 static int launch_cohort_prior(svjg_ctx *c, CohortPriorArgs &p) {
     const char *e = getenv("SVJG_PRIOR_STAGE");                   // "lds" / "recompute": the other way for the items beyond a lane's first (tools/cohort_prior_timing.py)
@@ -1397,48 +1326,78 @@ static int launch_cohort_prior(svjg_ctx *c, CohortPriorArgs &p) {
     return 0;
 }
 
-extern "C" int svjg_genotype_cohort_prior(svjg_ctx *c, const uint8_t *sv_type, const uint32_t *slot, const uint8_t *ok, const uint8_t *ploidy,
-                                          uint32_t max_ploidy, uint64_t n_rows, uint32_t min_support, double err, uint8_t *gt, int64_t *pl,
-                                          uint32_t *raw, uint8_t *genotyped, uint8_t *boundary, uint32_t *site, uint8_t *gq, double *af,
-                                          uint32_t *em_steps) {
+// The host leg of svjg_genotype_cohort (block BLOCK_COHORT: ploidy NULL, max_ploidy 2), svjg_genotype_cohort_ploidy (BLOCK_COHORT_PLOIDY: a
+// ploidy per item) and svjg_genotype_cohort_prior (BLOCK_COHORT_PRIOR: ploidy or NULL, gq / af / em_steps): the checks, the call's logarithms
+// (by the host's libm, as geno_args' three) and ploidy bytes in with the three input arrays, the cohort kernel of the call's kind — the table's
+// grow-and-rerun is the leg's — with k_cohort_prior behind it, the copy out.  site: NS, AC (BLOCK_COHORT) or NS, AN, AC per row.
+static int cohort_call(svjg_ctx *c, int block, const uint8_t *sv_type, const uint32_t *slot, const uint8_t *ok, const uint8_t *ploidy, uint32_t max_ploidy,
+                       uint64_t n_rows, uint32_t min_support, double err, uint8_t *gt, int64_t *pl, uint32_t *raw, uint8_t *genotyped, uint8_t *boundary,
+                       uint32_t *site, uint8_t *gq, double *af, uint32_t *em_steps) {
+    const bool prior = block == BLOCK_COHORT_PRIOR, per_item = ploidy != nullptr;
     if (!c) return SVJG_E_ARG;
     if (!c->d_cm) { c->err = "no cohort matrix"; return SVJG_E_ARG; }
     if (n_rows == 0) return 0;
-    if (!sv_type || !slot || !ok || !gt || !pl || !raw || !genotyped || !boundary || !site || !gq || !af || !em_steps) { c->err = "a null array"; return SVJG_E_ARG; }
+    if (!sv_type || !slot || !ok || (!ploidy && block == BLOCK_COHORT_PLOIDY) || !gt || !pl || !raw || !genotyped || !boundary || !site ||
+        (prior && (!gq || !af || !em_steps))) { c->err = "a null array"; return SVJG_E_ARG; }
     if (max_ploidy < 1 || max_ploidy > MAX_PLOIDY) { c->err = "max_ploidy is not in 1..SVJG_MAX_PLOIDY"; return SVJG_E_ARG; }
     if (!ploidy && max_ploidy != 2) { c->err = "without a ploidy array every item is diploid: max_ploidy must be 2"; return SVJG_E_ARG; }
     const uint64_t S = c->cohort_samples;
-    if (S >= (1ull << 28)) { c->err = "too many samples: AN would not fit 32 bits"; return SVJG_E_ARG; }
+    if (block != BLOCK_COHORT && S >= (1ull << 28)) { c->err = "too many samples: AN would not fit 32 bits"; return SVJG_E_ARG; }
     if (n_rows > (1ull << 40) / S) { c->err = "too many items for one call: genotype the rows in chunks"; return SVJG_E_ARG; }
     const uint64_t n = n_rows * S;
     if (ploidy)
         for (uint64_t i = 0; i < n; ++i)
             if (ploidy[i] > max_ploidy) { c->err = "ploidy above max_ploidy"; return SVJG_E_ARG; }
     HIPCHK(c, hipSetDevice(c->device));
-    const CohortPriorLayout L = cohort_prior_layout(n_rows, S, max_ploidy, ploidy != nullptr);
-    const int rc = genotype_leg(c, c->leg[BLOCK_COHORT_PRIOR], L,
+    const CohortLayout L = cohort_layout(n_rows, S, max_ploidy, per_item, prior);
+    const int rc = genotype_leg(c, c->leg[block], L,
         [&](uint8_t *hb) {
-            ploidy_log_table(err, (double *)(hb + L.logtab)); stage_rows(hb, L.in, sv_type, slot, ok, n_rows);   // (host libm, as geno_args' three)
+            if (per_item || prior) ploidy_log_table(err, (double *)(hb + L.logtab));
+            stage_rows(hb, L.in, sv_type, slot, ok, n_rows);
             if (ploidy) memcpy(hb + L.ploidy, ploidy, n);
         },
         [&](uint8_t *base) {
-            GenoCohortArgs g{block_geno_args(c, c->d_cm, base, L, n_rows, min_support, err), c->d_cpresent, c->cohort_samples, (unsigned long long *)(base + L.site)};
+            GenoCohortArgs g{block_geno_args(c, c->d_cm, base, L, n_rows, min_support, err), c->d_cpresent, c->cohort_samples, (unsigned long long *)(base + L.site),
+                             base + L.ploidy, (const double *)(base + L.logtab), max_ploidy};
             g.g.n_slots = c->cohort_slots;                        // (the matrix's slots, not the count vector's)
-            int rc1;
-            if (ploidy) { GenoCohortPloidyArgs q{g, base + L.ploidy, (const double *)(base + L.logtab), max_ploidy}; rc1 = launch_cohort_ploidy(c, q); }
-            else rc1 = launch_cohort(c, g);
-            if (rc1) return rc1;
+            if (const int rc1 = launch_cohort(c, g, per_item)) return rc1;
+            if (!prior) return 0;
             CohortPriorArgs p{(const uint32_t *)(base + L.raw), base + L.flags, ploidy ? base + L.ploidy : nullptr, base + L.in.type,
-                                    (const double *)(base + L.logtab), n_rows, c->cohort_samples, min_support,
-                                    base + L.gt, base + L.gq, (double *)(base + L.af), (uint32_t *)(base + L.steps), (uint32_t *)(base + L.psite), 0u};
+                              (const double *)(base + L.logtab), n_rows, c->cohort_samples, min_support,
+                              base + L.gt, base + L.gq, (double *)(base + L.af), (uint32_t *)(base + L.steps), (uint32_t *)(base + L.psite), 0u};
             return launch_cohort_prior(c, p);
         });
     if (rc) return rc;
-    const uint8_t *hb = (const uint8_t *)c->leg[BLOCK_COHORT_PRIOR].h;
+    const uint8_t *hb = (const uint8_t *)c->leg[block].h;
     memcpy(pl, hb + L.pl, n * (max_ploidy + 1) * sizeof *pl); memcpy(raw, hb + L.raw, n * 2 * sizeof *raw);
-    memcpy(gt, hb + L.gt, n); memcpy(genotyped, hb + L.flags, n); memcpy(boundary, hb + L.boundary, n); memcpy(gq, hb + L.gq, n);
-    memcpy(af, hb + L.af, n_rows * sizeof *af); memcpy(em_steps, hb + L.steps, n_rows * sizeof *em_steps); memcpy(site, hb + L.psite, n_rows * 3 * sizeof *site);
+    memcpy(gt, hb + L.gt, n); memcpy(genotyped, hb + L.flags, n); memcpy(boundary, hb + L.boundary, n);
+    if (prior) {
+        memcpy(gq, hb + L.gq, n); memcpy(af, hb + L.af, n_rows * sizeof *af); memcpy(em_steps, hb + L.steps, n_rows * sizeof *em_steps);
+        memcpy(site, hb + L.psite, n_rows * 3 * sizeof *site);
+    } else if (per_item) {
+        const uint64_t *w = (const uint64_t *)(hb + L.site);      // the kernel's two words a row: NS | AC << 32, AN
+        for (uint64_t r = 0; r < n_rows; ++r) { site[r * 3] = (uint32_t)w[r * 2]; site[r * 3 + 1] = (uint32_t)w[r * 2 + 1]; site[r * 3 + 2] = (uint32_t)(w[r * 2] >> 32); }
+    } else memcpy(site, hb + L.site, n_rows * 8);                 // NS, AC: the two halves of the kernel's one word a row
     return 0;
+}
+
+extern "C" int svjg_genotype_cohort(svjg_ctx *c, const uint8_t *sv_type, const uint32_t *slot, const uint8_t *ok, uint64_t n_rows,
+                                    uint32_t min_support, double err, uint8_t *gt, int64_t *pl, uint32_t *raw, uint8_t *genotyped,
+                                    uint8_t *boundary, uint32_t *site) {
+    return cohort_call(c, BLOCK_COHORT, sv_type, slot, ok, nullptr, 2, n_rows, min_support, err, gt, pl, raw, genotyped, boundary, site, nullptr, nullptr, nullptr);
+}
+
+extern "C" int svjg_genotype_cohort_ploidy(svjg_ctx *c, const uint8_t *sv_type, const uint32_t *slot, const uint8_t *ok, const uint8_t *ploidy,
+                                           uint32_t max_ploidy, uint64_t n_rows, uint32_t min_support, double err, uint8_t *gt, int64_t *pl,
+                                           uint32_t *raw, uint8_t *genotyped, uint8_t *boundary, uint32_t *site) {
+    return cohort_call(c, BLOCK_COHORT_PLOIDY, sv_type, slot, ok, ploidy, max_ploidy, n_rows, min_support, err, gt, pl, raw, genotyped, boundary, site, nullptr, nullptr, nullptr);
+}
+
+extern "C" int svjg_genotype_cohort_prior(svjg_ctx *c, const uint8_t *sv_type, const uint32_t *slot, const uint8_t *ok, const uint8_t *ploidy,
+                                          uint32_t max_ploidy, uint64_t n_rows, uint32_t min_support, double err, uint8_t *gt, int64_t *pl,
+                                          uint32_t *raw, uint8_t *genotyped, uint8_t *boundary, uint32_t *site, uint8_t *gq, double *af,
+                                          uint32_t *em_steps) {
+    return cohort_call(c, BLOCK_COHORT_PRIOR, sv_type, slot, ok, ploidy, max_ploidy, n_rows, min_support, err, gt, pl, raw, genotyped, boundary, site, gq, af, em_steps);
 }
 
 // ---- the whole pass in one call, one host wait; two passes in flight ------------------------------------------------------

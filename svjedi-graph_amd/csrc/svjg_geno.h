@@ -171,6 +171,16 @@ SVJG_HD int dec28_round_dir(double h) {
     return (up == (h > 0)) ? 1 : -1;
 }
 
+// lik_g of a row of ploidy P as every caller compares it: the exact sum of the two ROUNDED products, the one product at 2 g = P.  (its own
+// pragma: the caller's does not reach into an inlined callee)
+SVJG_HD dd geno_lik(double c1, double c2, uint32_t P, uint32_t g, const double *lr, const double *la) {
+#ifdef __clang__
+#pragma clang fp contract(off)                           // the products are rounded to doubles before the exact sums
+#endif
+    const double a = c1 * lr[g], b = c2 * la[g], h = (c1 + c2) * lr[g];
+    return (g != 0 && 2 * g == P) ? dd{h, 0.0} : two_sum(a, b);
+}
+
 // One genotyped row of ploidy P in 1..MAX_PLOIDY; lr / la: the row's own P + 1 logarithms (geno_row_ploidy and geno_row below say which).
 // Status as geno_comb (the PLs of a row that is not GENO_ROW_OK are without the binomial term).  The loop over g is unrolled with a predicate
 // so that pl[] is only ever indexed by constants (registers on the device, no scratch).
@@ -192,7 +202,7 @@ SVJG_HD uint32_t geno_row_pairs(uint32_t type, uint32_t ref, uint32_t alt, uint3
         SVJG_UNROLL
         for (uint32_t g = 0; g <= MAX_PLOIDY; ++g) {
             if (g > P || 2 * g == P) continue;
-            const dd l = two_sum(c1 * lr[g], c2 * la[g]);
+            const dd l = geno_lik(c1, c2, P, g, lr, la);
             if (l.hi == h && l.lo == 0.0) same = true;
         }
         if (same) dir = dec28_round_dir(h);
@@ -203,9 +213,8 @@ SVJG_HD uint32_t geno_row_pairs(uint32_t type, uint32_t ref, uint32_t alt, uint3
         o.pl[g] = 0;
         if (g > P) continue;
         // products in double, sums exact (the reference adds Decimal images of the doubles, :295-297): each product is ROUNDED before two_sum sees it
-        const double a = c1 * lr[g], b = c2 * la[g], h = (c1 + c2) * lr[g];
         const bool single = g != 0 && 2 * g == P;
-        const dd l = single ? dd{h, 0.0} : two_sum(a, b);
+        const dd l = geno_lik(c1, c2, P, g, lr, la);
         int c = g ? dd_cmp(l, best) : 1;
         if (c == 0 && single != best_single) c = single ? -dir : dir;      // sign of (the rounded sum - the product) seen from l
         if (c > 0) { best = l; g_best = (uint8_t)g; best_single = single; tie = false; } else if (c == 0) tie = true;
@@ -381,13 +390,19 @@ SVJG_HD CohortSums cohort_ploidy_sums(const CohortBallots &b, uint64_t mask) {
     }
     return o;
 }
+// k_genotype_cohort's sums of a segment, every item diploid, from its three ballots (called: gt != 3, het: gt == 1, hom: gt == 2): NS, AC = het + 2 hom
+// (AN = 2 NS: the kernel leaves it to the host)
+SVJG_HD CohortSums cohort_diploid_sums(uint64_t called, uint64_t het, uint64_t hom, uint64_t mask) {
+    const uint32_t ns = (uint32_t)__builtin_popcountll(called & mask);
+    return CohortSums{ns, 2 * ns, (uint32_t)__builtin_popcountll(het & mask) + 2 * (uint32_t)__builtin_popcountll(hom & mask)};
+}
 // the row's two site words: NS | AC << 32 (k_genotype_cohort's word) and AN.  (AC, AN <= 8 S: they fit 32 bits for S < 2^28)
 SVJG_HD uint64_t cohort_site_word(const CohortSums &s) { return (uint64_t)s.ns | ((uint64_t)s.ac << 32); }
 
 // ---- cohort with an allele-frequency prior (k_cohort_prior) ----
 // The row's alt-allele frequency f is estimated from all its samples' likelihoods by EM under Hardy-Weinberg, each item is then called at
-// the maximum of likelihood x prior.  An item (r, s) takes part iff the cohort call genotyped it and c1 + c2 > 0.  Its weights: l_g as
-// geno_row_pairs compares them (the exact sum of the two rounded products, the one product at 2 g = P), d_g = l_g - max l_g subtracted in
+// the maximum of likelihood x prior.  An item (r, s) takes part iff the cohort call genotyped it and c1 + c2 > 0.  Its weights: l_g = geno_lik,
+// what geno_row_pairs compares, d_g = l_g - max l_g subtracted in
 // double-double and collapsed to one double, w_g = 10^d_g (the binomial term is the same for every g and cancels).  The prior is
 // pi_g(f; P) = C(P, g) f^g (1 - f)^(P - g), powers by repeated multiplication (0^0 = 1); posterior q_g = pi_g w_g / sum_g pi_g w_g, one-hot at
 // the item's largest w_g where that sum is 0; expected copies x = sum_g g q_g.  f_0 = 0.5, f_(k+1) = sum_s x_s / sum_s P_s over the row's items
@@ -428,8 +443,7 @@ SVJG_HD void prior_item(uint32_t type, uint32_t ref, uint32_t alt, uint32_t P, c
     SVJG_UNROLL
     for (uint32_t g = 0; g <= MAX_PLOIDY; ++g) {
         if (g > o.P || o.P == 0) continue;
-        const double a = c1 * lr[g], b = c2 * la[g], h = (c1 + c2) * lr[g];
-        const dd l = (g != 0 && 2 * g == P) ? dd{h, 0.0} : two_sum(a, b);
+        const dd l = geno_lik(c1, c2, P, g, lr, la);
         if (g == 0 || dd_cmp(l, best) > 0) { best = l; o.gmax = g; }
     }
     uint32_t comb = 1;                                   // C(P, g), exact in integers
@@ -438,11 +452,20 @@ SVJG_HD void prior_item(uint32_t type, uint32_t ref, uint32_t alt, uint32_t P, c
         o.w[g] = 0.0;
         if (g > o.P || o.P == 0) continue;
         if (g) comb = comb * (P - g + 1) / g;
-        const double a = c1 * lr[g], b = c2 * la[g], h = (c1 + c2) * lr[g];
-        const dd l = (g != 0 && 2 * g == P) ? dd{h, 0.0} : two_sum(a, b);
-        const dd d = dd_add(l, dd_neg(best));
+        const dd d = dd_add(geno_lik(c1, c2, P, g, lr, la), dd_neg(best));
         o.w[g] = (double)comb * prior_exp10(d.hi + d.lo);
     }
+}
+
+// Item i as the EM sees it (k_cohort_prior and tests/cohort_prior_sim), from what the first kernel left: raw[i][2], genotyped[i], and the call's
+// ploidy[i] (nullptr: 2 everywhere), the row's type byte and tab = ploidy_log_table.  The item takes no part (it.P = 0) unless the first kernel
+// genotyped it and it has a read; the type is read only for an item that does (a pointer, so that the kernel's load stays behind that test).
+SVJG_HD void prior_load(const uint8_t *type, const uint32_t *raw, const uint8_t *genotyped, const uint8_t *ploidy, uint64_t i, const double *tab, double &c_sum, PriorItem &it) {
+    const uint32_t P = genotyped[i] ? (ploidy ? ploidy[i] : 2u) : 0u;
+    it.P = 0; it.gmax = 0; c_sum = 0.0;
+    SVJG_UNROLL
+    for (uint32_t g = 0; g <= MAX_PLOIDY; ++g) it.w[g] = 0.0;
+    if (P >= 1 && P <= MAX_PLOIDY) prior_item(*type, raw[i * 2], raw[i * 2 + 1], P, tab + ploidy_tab_at(P, 0), tab + PLOIDY_TAB + ploidy_tab_at(P, 0), c_sum, it);
 }
 
 // t[g] = pi_g(f; P) w_g for g = 0..P (0 beyond): (1 - f)^(P - g) from the top down, f^g from the bottom up.  P = 0: all 0, f is not looked at.
@@ -584,47 +607,32 @@ inline SitesLayout sites_layout(uint64_t n) {
     return L;
 }
 
-// svjg_genotype_cohort: [ pl 24 | raw 8 | gt 1 | flags 1 | boundary 1 ] x (n_rows * S items, row-major), then the rows' site words (NS | AC << 32),
-// 8-aligned, as the LAST output: the max_n pair lies right behind them (8 n_rows is a multiple of 8, so leg_span pads nothing), and ONE memset
-// zeroes both in front of every launch; in: rows_in(n_rows)
-struct CohortLayout : LegSpan { uint64_t pl, raw, gt, flags, boundary, site;  RowsIn in; };
-inline CohortLayout cohort_layout(uint64_t n_rows, uint64_t S) {
-    CohortLayout L; uint64_t o = 0; const uint64_t n = n_rows * S;
-    L.pl = o; o += n * 24; L.raw = o; o += n * 8; L.gt = o; o += n; L.flags = o; o += n; L.boundary = o; o += n;
-    o = (o + 7) & ~7ull; L.site = o; o += n_rows * 8;
-    leg_span(L, o, n_rows * 6); L.in = rows_in(n_rows, L.in_at);
-    return L;
-}
-
-// svjg_genotype_cohort_ploidy: [ pl 8 (max_ploidy + 1) | raw 8 | gt 1 | flags 1 | boundary 1 ] x (n_rows * S items, row-major) — the PL stride is the
-// CALL's, not MAX_PLOIDY + 1: a human cohort moves 24 bytes of PLs per item like the diploid call —, then TWO site words per row (NS | AC << 32, AN),
-// 8-aligned, as the last output right in front of the max_n pair (as cohort_layout: one memset zeroes both); in: the call's logarithms
-// (ploidy_log_table), rows_in(n_rows) and the n_rows * S ploidy bytes
-struct CohortPloidyLayout : LegSpan { uint64_t pl, raw, gt, flags, boundary, site, logtab;  RowsIn in;  uint64_t ploidy; };
-inline CohortPloidyLayout cohort_ploidy_layout(uint64_t n_rows, uint64_t S, uint32_t max_ploidy) {
-    CohortPloidyLayout L; uint64_t o = 0; const uint64_t n = n_rows * S;
+// svjg_genotype_cohort (max_ploidy 2, neither switch), _cohort_ploidy (per_item) and _cohort_prior (prior; per_item iff it has a ploidy array):
+// [ pl 8 (max_ploidy + 1) | raw 8 | gt 1 | flags 1 | boundary 1 ] x (n_rows * S items, row-major) — the PL stride is the CALL's, not MAX_PLOIDY + 1:
+// a human cohort moves 24 bytes of PLs per item —; prior: k_cohort_prior's own outputs [ gq 1 ] x items and, 8-aligned, [ af 8 | psite 12 (NS, AN,
+// AC) | steps 4 ] x rows (it writes the posterior call over gt); then the first kernel's site words, 8-aligned, as the LAST output: NS | AC << 32
+// per row, per_item a second one, AN.  The max_n pair lies right behind them (a multiple of 8: leg_span pads nothing), and ONE memset zeroes both
+// in front of every launch.  in: the call's logarithms (ploidy_log_table) iff per_item or prior, rows_in(n_rows), per_item the n_rows * S ploidy
+// bytes.  A field the call does not have is 0 (ploidy: where the bytes would begin).
+struct CohortLayout : LegSpan { uint64_t pl, raw, gt, flags, boundary, gq, af, psite, steps, site, logtab;  RowsIn in;  uint64_t ploidy; };
+inline CohortLayout cohort_layout(uint64_t n_rows, uint64_t S, uint32_t max_ploidy = 2, bool per_item = false, bool prior = false) {
+    CohortLayout L{}; uint64_t o = 0; const uint64_t n = n_rows * S, logs = per_item || prior ? 2 * PLOIDY_TAB * 8 : 0;
     L.pl = o; o += n * 8 * (max_ploidy + 1); L.raw = o; o += n * 8; L.gt = o; o += n; L.flags = o; o += n; L.boundary = o; o += n;
-    o = (o + 7) & ~7ull; L.site = o; o += n_rows * 16;
-    leg_span(L, o, 2 * PLOIDY_TAB * 8 + n_rows * 6 + n);
-    L.logtab = L.in_at; L.in = rows_in(n_rows, L.logtab + 2 * PLOIDY_TAB * 8); L.ploidy = L.in.slot + L.in.bytes;
-    return L;
-}
-
-// svjg_genotype_cohort_prior: the first kernel's five outputs as cohort_layout (ploidy == NULL: per_item false, max_ploidy 2) or
-// cohort_ploidy_layout holds them — gt is then overwritten by k_cohort_prior with the posterior call —, k_cohort_prior's own outputs [ gq 1 ] x
-// items, [ af 8 | psite 12 (NS, AN, AC) | steps 4 ] x rows, and last the first kernel's site words (one per row, or two), 8-aligned right in front
-// of the max_n pair as in those layouts; in: the call's logarithms (ploidy_log_table; k_cohort_prior reads them in either case), rows_in(n_rows)
-// and, per_item, the n_rows * S ploidy bytes
-struct CohortPriorLayout : LegSpan { uint64_t pl, raw, gt, flags, boundary, gq, af, psite, steps, site, logtab;  RowsIn in;  uint64_t ploidy; };
-inline CohortPriorLayout cohort_prior_layout(uint64_t n_rows, uint64_t S, uint32_t max_ploidy, bool per_item) {
-    CohortPriorLayout L; uint64_t o = 0; const uint64_t n = n_rows * S;
-    L.pl = o; o += n * 8 * (max_ploidy + 1); L.raw = o; o += n * 8; L.gt = o; o += n; L.flags = o; o += n; L.boundary = o; o += n; L.gq = o; o += n;
-    o = (o + 7) & ~7ull; L.af = o; o += n_rows * 8; L.psite = o; o += n_rows * 12; L.steps = o; o += n_rows * 4;
+    if (prior) { L.gq = o; o += n; }
+    o = (o + 7) & ~7ull;
+    if (prior) { L.af = o; o += n_rows * 8; L.psite = o; o += n_rows * 12; L.steps = o; o += n_rows * 4; }
     L.site = o; o += n_rows * (per_item ? 16 : 8);
-    leg_span(L, o, 2 * PLOIDY_TAB * 8 + n_rows * 6 + (per_item ? n : 0));
-    L.logtab = L.in_at; L.in = rows_in(n_rows, L.logtab + 2 * PLOIDY_TAB * 8); L.ploidy = L.in.slot + L.in.bytes;
+    leg_span(L, o, logs + n_rows * 6 + (per_item ? n : 0));
+    L.logtab = logs ? L.in_at : 0; L.in = rows_in(n_rows, L.in_at + logs); L.ploidy = L.in.slot + L.in.bytes;
     return L;
 }
+// The parent's three layout entry points: cohort_layout(n_rows, S) through the defaults above, and these.  Nothing in this tree calls them; the host
+// harnesses of the tests written before the one layout (tests/cohort_sim, cohort_ploidy_sim, cohort_prior_sim as they stood) compile against them, and
+// those tests are held against every later build.
+using CohortPloidyLayout = CohortLayout;
+using CohortPriorLayout = CohortLayout;
+inline CohortLayout cohort_ploidy_layout(uint64_t n_rows, uint64_t S, uint32_t max_ploidy) { return cohort_layout(n_rows, S, max_ploidy, true, false); }
+inline CohortLayout cohort_prior_layout(uint64_t n_rows, uint64_t S, uint32_t max_ploidy, bool per_item) { return cohort_layout(n_rows, S, max_ploidy, per_item, true); }
 
 // fused pass (svjg_set_rows, svjg_run_begin, svjg_run_end), per slot.  Host block (pinned, mapped into the device: the genotype kernel
 // writes its results straight into it — they cross PCIe as they are produced, no copy kernel competes with the next pass —): pl32, raw,

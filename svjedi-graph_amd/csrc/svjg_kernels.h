@@ -2067,16 +2067,21 @@ __global__ __launch_bounds__(TPB) void k_cohort_load(const unsigned long long *c
 }
 
 // g: as for k_genotype with counts = the matrix, n_slots = its slots, n_rows = the ROWS, and gt / pl / raw / genotyped / boundary holding
-// n_rows * n_samples items, row-major; g.pl32 is unused.  site[r] = NS | AC << 32, zeroed by the host in front of every launch.
+// n_rows * n_samples items, row-major; g.pl32 is unused.  site: the rows' site words, zeroed by the host in front of every launch.  ONE struct
+// for both cohort kernels.  k_genotype_cohort: every item diploid, g's three logarithms, 3 PLs an item, gt 3 = no call, site[r] = NS | AC << 32;
+// the last three fields are unused.  k_genotype_cohort_ploidy: ploidy[i], one byte per item, row-major like the outputs; logtab =
+// ploidy_log_table of the call's err (g's three logarithms are unused); max_ploidy + 1 PLs an item (entries beyond an item's ploidy: 0; an item
+// of a higher ploidy is not genotyped), gt 0xFF = no call, site[2 r] = NS | AC << 32 and site[2 r + 1] = AN.
 struct GenoCohortArgs {
     GenoArgs g;
     const uint8_t *present;
     uint32_t n_samples;
     unsigned long long *site;
+    const uint8_t *ploidy; const double *logtab; uint32_t max_ploidy;          // k_genotype_cohort_ploidy only
 };
 
-// The gate of item (r, s) of both cohort kernels: geno_gate but for the presence test.  The item is genotyped iff ok[r] & 1, the row has a slot,
-// `wanted` (the kernel's own condition, the ploidy byte: nothing is read for an item that fails it) and present[slot][s]; ok bit 1 is not looked at.
+// The gate of item (r, s): geno_gate but for the presence test.  The item is genotyped iff ok[r] & 1, the row has a slot, `wanted` (1 <= ploidy[i]
+// <= max_ploidy in k_genotype_cohort_ploidy: nothing is read for an item that fails it) and present[slot][s]; ok bit 1 is not looked at.
 __device__ inline bool cohort_gate(const GenoArgs &a, const uint8_t *present, uint64_t r, uint64_t s, uint64_t S, bool wanted, uint32_t &ref, uint32_t &alt) {
     ref = alt = 0;
     const uint32_t ok = a.ok[r], sl = a.slot[r];
@@ -2090,7 +2095,7 @@ __device__ inline bool cohort_gate(const GenoArgs &a, const uint8_t *present, ui
 
 // Item i = r * S + s per lane, items in strides of the grid.  What k_genotype does per row behind cohort_gate.  The site tags come from the same pass in
 // integers: the lanes of one row are a segment of the wave (svjg_geno.h: cohort_segment), its NS and AC are popcounts of ballots under the
-// segment's mask, and the segment's first lane adds them to site[r] with one 64-bit atomic.  Every ballot is executed by all 64 lanes on
+// segment's mask (cohort_diploid_sums), and the segment's first lane adds them to site[r] with one 64-bit atomic.  Every ballot is executed by all 64 lanes on
 // every trip: the loop's bound is the WAVE's first item, and lanes beyond the last item take part with "not called".  (blocks of a multiple
 // of 64 threads)
 __global__ __launch_bounds__(TPB) void k_genotype_cohort(GenoCohortArgs p) {
@@ -2119,32 +2124,26 @@ __global__ __launch_bounds__(TPB) void k_genotype_cohort(GenoCohortArgs p) {
     const uint64_t called = __ballot(gt != 3), het = __ballot(gt == 1), hom = __ballot(gt == 2);
     const CohortSeg seg = cohort_segment(i, s, S, lane, n_items);
     if (seg.leader) {
-        const unsigned long long ns = (unsigned long long)__popcll(called & seg.mask);
-        const unsigned long long ac = (unsigned long long)__popcll(het & seg.mask) + 2ull * (unsigned long long)__popcll(hom & seg.mask);
-        if (ns) atomicAdd(p.site + r, ns | (ac << 32));
+        const CohortSums t = cohort_diploid_sums(called, het, hom, seg.mask);
+        if (t.ns) atomicAdd(p.site + r, (unsigned long long)cohort_site_word(t));
     }
   }
 }
 
-// ---- cohort at per-sample ploidy (svjg_genotype_cohort_ploidy) ----
-// c: as for k_genotype_cohort, but c.g.pl holds max_ploidy + 1 integers per item (entries beyond an item's ploidy: 0), c.g.pl32 and the three
-// logarithms are unused and c.site holds TWO words per row, NS | AC << 32 and AN.  ploidy[i]: one byte per item, row-major like the outputs.
-struct GenoCohortPloidyArgs {
-    GenoCohortArgs c;
-    const uint8_t *ploidy;
-    const double *logtab;              // ploidy_log_table of the call's err: 2 x PLOIDY_TAB doubles
-    uint32_t max_ploidy;               // 1..MAX_PLOIDY: the PL stride is max_ploidy + 1, and an item of a higher ploidy is not genotyped
-};
+// The two cohort kernels stay TWO bodies that share the gate, the segment and the argument struct: written as one `template <bool PER_ITEM>`
+// body the diploid instantiation came out at the same registers and 3 instructions longer, and ran 5 % slower at 64 samples on the device
+// (0.169 against 0.160 ms, profiles/r16/experiments/one_cohort_leg.txt), for no reason the instruction stream shows; k_genotype_cohort's text above
+// is the one that measures 0.160.
 
 // k_genotype_cohort's division of the work, its loop bound and block shape, and its gate with wanted = 1 <= ploidy[i] <= max_ploidy.  The arithmetic
 // is geno_row_ploidy's on the call's logarithms staged in LDS.  NS, AN and AC of a row: one ballot for "called" and one per bit plane of gt and of
 // the ploidy (both fit four bits), summed under the segment's mask (svjg_geno.h: cohort_ploidy_sums); the segment's first lane adds them to the
 // row's two site words.
-__global__ __launch_bounds__(TPB) void k_genotype_cohort_ploidy(GenoCohortPloidyArgs p) {
+__global__ __launch_bounds__(TPB) void k_genotype_cohort_ploidy(GenoCohortArgs p) {
   __shared__ double tab[2 * PLOIDY_TAB];
   stage_ploidy_tab(tab, p.logtab);
-  const GenoArgs &a = p.c.g;
-  const uint64_t S = p.c.n_samples, n_items = a.n_rows * S;
+  const GenoArgs &a = p.g;
+  const uint64_t S = p.n_samples, n_items = a.n_rows * S;
   const uint32_t lane = threadIdx.x & 63u, NPL = p.max_ploidy + 1;
   for (uint64_t w0 = (uint64_t)blockIdx.x * blockDim.x + (threadIdx.x - lane); w0 < n_items; w0 += (uint64_t)gridDim.x * blockDim.x) {
     const uint64_t i = w0 + lane;
@@ -2154,7 +2153,7 @@ __global__ __launch_bounds__(TPB) void k_genotype_cohort_ploidy(GenoCohortPloidy
         r = i / S; s = i - r * S;
         uint32_t ref, alt;
         P = p.ploidy[i];
-        const bool go = cohort_gate(a, p.c.present, r, s, S, P >= 1 && P <= p.max_ploidy, ref, alt);
+        const bool go = cohort_gate(a, p.present, r, s, S, P >= 1 && P <= p.max_ploidy, ref, alt);
         a.raw[i * 2] = ref; a.raw[i * 2 + 1] = alt;
         a.genotyped[i] = go;
         GenoRowPloidy o{};                                                     // (an item that is not genotyped: zeros)
@@ -2168,15 +2167,14 @@ __global__ __launch_bounds__(TPB) void k_genotype_cohort_ploidy(GenoCohortPloidy
             if (g < NPL) a.pl[i * NPL + g] = o.pl[g];
         a.gt[i] = (uint8_t)gt; a.boundary[i] = o.near;
     }
-    const bool called = gt != 0xFF;
     CohortBallots b;
-    b.called = __ballot(called);
+    b.called = __ballot(gt != 0xFF);
 #pragma unroll
     for (uint32_t k = 0; k < 4; ++k) { b.gt[k] = __ballot((gt >> k) & 1u); b.ploidy[k] = __ballot((P >> k) & 1u); }
     const CohortSeg seg = cohort_segment(i, s, S, lane, n_items);
     if (seg.leader) {
         const CohortSums t = cohort_ploidy_sums(b, seg.mask);
-        if (t.ns) { atomicAdd(p.c.site + r * 2, (unsigned long long)cohort_site_word(t)); atomicAdd(p.c.site + r * 2 + 1, (unsigned long long)t.an); }
+        if (t.ns) { atomicAdd(p.site + r * 2, (unsigned long long)cohort_site_word(t)); atomicAdd(p.site + r * 2 + 1, (unsigned long long)t.an); }
     }
   }
 }
@@ -2195,14 +2193,9 @@ struct CohortPriorArgs {
 constexpr uint32_t PRIOR_STAGE_MAX = 3;                                        // 3 x 256 lanes x 76 bytes = 58 368 bytes of the 64 KiB a block may ask for
 constexpr uint32_t prior_stage_bytes(uint32_t staged, uint32_t block) { return staged * block * ((MAX_PLOIDY + 1) * 8 + 4); }
 
-// item (r, s) as the EM sees it; the item takes no part (it.P = 0) unless the first kernel genotyped it and it has a read
+// item (r, s) as the EM sees it (svjg_geno.h: prior_load)
 __device__ inline void prior_load(const CohortPriorArgs &p, const double *tab, uint64_t r, uint64_t s, double &c_sum, PriorItem &it) {
-    const uint64_t i = r * p.n_samples + s;
-    const uint32_t P = p.genotyped[i] ? (p.ploidy ? p.ploidy[i] : 2u) : 0u;
-    it.P = 0; it.gmax = 0; c_sum = 0.0;
-#pragma unroll
-    for (uint32_t g = 0; g <= MAX_PLOIDY; ++g) it.w[g] = 0.0;
-    if (P >= 1 && P <= MAX_PLOIDY) prior_item(p.sv_type[r], p.raw[i * 2], p.raw[i * 2 + 1], P, tab + ploidy_tab_at(P, 0), tab + PLOIDY_TAB + ploidy_tab_at(P, 0), c_sum, it);
+    prior_load(p.sv_type + r, p.raw, p.genotyped, p.ploidy, r * p.n_samples + s, tab, c_sum, it);
 }
 
 // the k-th further item of a lane in the block's dynamic LDS: w[g] at [(k * 9 + g) * block + lane of the block] (neighbouring lanes, neighbouring

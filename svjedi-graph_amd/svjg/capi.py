@@ -548,28 +548,10 @@ class Context:
         self._chk(self.lib.svjg_cohort_get_counts(self.h, int(sample), out.ctypes.data, present.ctypes.data, n_slots))
         return out, present
 
-    def genotype_cohort(self, sv_type, slot, ok, min_support, err):
-        """Every row against every sample of the cohort matrix (svjg_genotype_cohort; ok bit 1 is ignored: the presence bytes decide).
-        -> (gt[n, S], pl[n, S, 3], raw[n, S, 2], genotyped[n, S], boundary[n, S] = the items to recompute with svjg.genotype.exact_pl,
-        site[n, 2] = NS and AC of each row)"""
-        n = len(sv_type)
-        S = getattr(self, "_cohort", (0, 0))[0]
-        sv_type, slot, ok = _row_inputs(sv_type, slot, ok)
-        gt = np.empty((n, S), dtype=np.uint8)
-        pl = np.empty((n, S, 3), dtype=np.int64)
-        raw = np.empty((n, S, 2), dtype=np.uint32)
-        done = np.empty((n, S), dtype=np.uint8)
-        boundary = np.empty((n, S), dtype=np.uint8)
-        site = np.empty((n, 2), dtype=np.uint32)
-        self._chk(self.lib.svjg_genotype_cohort(self.h, sv_type.ctypes.data, slot.ctypes.data, ok.ctypes.data, n, min_support, float(err),
-                                                gt.ctypes.data, pl.ctypes.data, raw.ctypes.data, done.ctypes.data, boundary.ctypes.data,
-                                                site.ctypes.data))
-        return gt, pl, raw, done, boundary, site
-
-    def genotype_cohort_ploidy(self, sv_type, slot, ok, ploidy, max_ploidy, min_support, err):
-        """Every row against every sample of the cohort matrix at a ploidy per item (svjg_genotype_cohort_ploidy): ploidy[n, S] in 0..max_ploidy,
-        0 = the item is never genotyped.  -> (gt[n, S] = alt copies or 0xFF, pl[n, S, max_ploidy + 1] = PL_0..PL_P then zeros, raw[n, S, 2],
-        genotyped[n, S], boundary[n, S] = the items to recompute with svjg.genotype.exact_pl_ploidy, site[n, 3] = NS, AN and AC of each row)"""
+    def _cohort_call(self, name, sv_type, slot, ok, ploidy, max_ploidy, min_support, err):
+        """The three cohort calls: the checks, the output arrays and the call of library function `name`.  -> (gt[n, S], pl[n, S, max_ploidy + 1],
+        raw[n, S, 2], genotyped[n, S], boundary[n, S], site[n, 2 or 3]) and, from svjg_genotype_cohort_prior, (gq[n, S], af[n], em_steps[n])"""
+        plain, prior = name == "svjg_genotype_cohort", name == "svjg_genotype_cohort_prior"
         n = len(sv_type)
         S = getattr(self, "_cohort", (0, 0))[0]
         max_ploidy = int(max_ploidy)
@@ -577,52 +559,38 @@ class Context:
             raise SvjgError("max_ploidy: 1..%d" % MAX_PLOIDY)
         width = min(max_ploidy, MAX_PLOIDY) + 1                  # (a max_ploidy out of range is the library's to refuse: nothing is written then)
         sv_type, slot, ok = _row_inputs(sv_type, slot, ok)
-        ploidy = np.asarray(ploidy)
-        if ploidy.shape != (n, S) or (ploidy.size and (int(ploidy.min()) < 0 or int(ploidy.max()) > 255)):
-            raise SvjgError("ploidy: one value in 0..max_ploidy per (row, sample)")
-        ploidy = np.ascontiguousarray(ploidy, dtype=np.uint8)
-        gt = np.empty((n, S), dtype=np.uint8)
-        pl = np.empty((n, S, width), dtype=np.int64)
-        raw = np.empty((n, S, 2), dtype=np.uint32)
-        done = np.empty((n, S), dtype=np.uint8)
-        boundary = np.empty((n, S), dtype=np.uint8)
-        site = np.empty((n, 3), dtype=np.uint32)
-        self._chk(self.lib.svjg_genotype_cohort_ploidy(self.h, sv_type.ctypes.data, slot.ctypes.data, ok.ctypes.data, ploidy.ctypes.data, max_ploidy,
-                                                       n, min_support, float(err), gt.ctypes.data, pl.ctypes.data, raw.ctypes.data,
-                                                       done.ctypes.data, boundary.ctypes.data, site.ctypes.data))
-        return gt, pl, raw, done, boundary, site
+        if ploidy is not None or not (plain or prior):
+            ploidy = np.asarray(ploidy)
+            if ploidy.shape != (n, S) or (ploidy.size and (int(ploidy.min()) < 0 or int(ploidy.max()) > 255)):
+                raise SvjgError("ploidy: one value in 0..max_ploidy per (row, sample)")
+            ploidy = np.ascontiguousarray(ploidy, dtype=np.uint8)
+        out = (np.empty((n, S), np.uint8), np.empty((n, S, width), np.int64), np.empty((n, S, 2), np.uint32), np.empty((n, S), np.uint8),
+               np.empty((n, S), np.uint8), np.empty((n, 2 if plain else 3), np.uint32))
+        if prior:
+            out += (np.empty((n, S), np.uint8), np.empty(n, np.float64), np.empty(n, np.uint32))
+        kind = () if plain else (None if ploidy is None else ploidy.ctypes.data, max_ploidy)
+        self._chk(getattr(self.lib, name)(self.h, sv_type.ctypes.data, slot.ctypes.data, ok.ctypes.data, *kind, n, min_support, float(err),
+                                          *(a.ctypes.data for a in out)))
+        return out
+
+    def genotype_cohort(self, sv_type, slot, ok, min_support, err):
+        """Every row against every sample of the cohort matrix (svjg_genotype_cohort; ok bit 1 is ignored: the presence bytes decide).
+        -> (gt[n, S], pl[n, S, 3], raw[n, S, 2], genotyped[n, S], boundary[n, S] = the items to recompute with svjg.genotype.exact_pl,
+        site[n, 2] = NS and AC of each row)"""
+        return self._cohort_call("svjg_genotype_cohort", sv_type, slot, ok, None, 2, min_support, err)
+
+    def genotype_cohort_ploidy(self, sv_type, slot, ok, ploidy, max_ploidy, min_support, err):
+        """Every row against every sample of the cohort matrix at a ploidy per item (svjg_genotype_cohort_ploidy): ploidy[n, S] in 0..max_ploidy,
+        0 = the item is never genotyped.  -> (gt[n, S] = alt copies or 0xFF, pl[n, S, max_ploidy + 1] = PL_0..PL_P then zeros, raw[n, S, 2],
+        genotyped[n, S], boundary[n, S] = the items to recompute with svjg.genotype.exact_pl_ploidy, site[n, 3] = NS, AN and AC of each row)"""
+        return self._cohort_call("svjg_genotype_cohort_ploidy", sv_type, slot, ok, ploidy, max_ploidy, min_support, err)
 
     def genotype_cohort_prior(self, sv_type, slot, ok, ploidy, max_ploidy, min_support, err):
         """The cohort call with an allele-frequency prior (svjg_genotype_cohort_prior).  ploidy: [n, S] in 0..max_ploidy, or None = every item
         diploid (max_ploidy must then be 2).  -> (gt[n, S] = alt copies of the POSTERIOR call or 0xFF, pl[n, S, max_ploidy + 1], raw[n, S, 2],
         genotyped[n, S], boundary[n, S] — pl, raw, genotyped and boundary as genotype_cohort / genotype_cohort_ploidy give them —, site[n, 3] =
         NS, AN, AC of the posterior calls, gq[n, S] (0xFF: none), af[n] (NaN: no estimate), em_steps[n] (bit 31: not converged))"""
-        n = len(sv_type)
-        S = getattr(self, "_cohort", (0, 0))[0]
-        max_ploidy = int(max_ploidy)
-        if not 0 <= max_ploidy <= 0xFFFFFFFF:
-            raise SvjgError("max_ploidy: 1..%d" % MAX_PLOIDY)
-        width = min(max_ploidy, MAX_PLOIDY) + 1                  # (a max_ploidy out of range is the library's to refuse: nothing is written then)
-        sv_type, slot, ok = _row_inputs(sv_type, slot, ok)
-        if ploidy is not None:
-            ploidy = np.asarray(ploidy)
-            if ploidy.shape != (n, S) or (ploidy.size and (int(ploidy.min()) < 0 or int(ploidy.max()) > 255)):
-                raise SvjgError("ploidy: one value in 0..max_ploidy per (row, sample)")
-            ploidy = np.ascontiguousarray(ploidy, dtype=np.uint8)
-        gt = np.empty((n, S), dtype=np.uint8)
-        pl = np.empty((n, S, width), dtype=np.int64)
-        raw = np.empty((n, S, 2), dtype=np.uint32)
-        done = np.empty((n, S), dtype=np.uint8)
-        boundary = np.empty((n, S), dtype=np.uint8)
-        site = np.empty((n, 3), dtype=np.uint32)
-        gq = np.empty((n, S), dtype=np.uint8)
-        af = np.empty(n, dtype=np.float64)
-        steps = np.empty(n, dtype=np.uint32)
-        self._chk(self.lib.svjg_genotype_cohort_prior(self.h, sv_type.ctypes.data, slot.ctypes.data, ok.ctypes.data,
-                                                      None if ploidy is None else ploidy.ctypes.data, max_ploidy, n, min_support, float(err),
-                                                      gt.ctypes.data, pl.ctypes.data, raw.ctypes.data, done.ctypes.data, boundary.ctypes.data,
-                                                      site.ctypes.data, gq.ctypes.data, af.ctypes.data, steps.ctypes.data))
-        return gt, pl, raw, done, boundary, site, gq, af, steps
+        return self._cohort_call("svjg_genotype_cohort_prior", sv_type, slot, ok, ploidy, max_ploidy, min_support, err)
 
     def set_rows(self, sv_type, slot, ok):
         """the VCF rows' input arrays of genotype(), left on the device for run_resident()"""

@@ -497,7 +497,7 @@ def genotype_with_counts_joint(ctx, vcf_path, slot_of, out_path, min_support, er
     return write_vcf_joint(out_path, rows, gt, pl, raw, done, member)
 
 
-# ---- cohort (--cohort): many samples' counts, one multi-sample VCF: svjg_genotype_cohort, Python rows and the writer below ----
+# ---- cohort (--cohort [--cohort-ploidy FILE] [--cohort-prior]): many samples' counts, one multi-sample VCF: the three svjg_genotype_cohort* calls, Python rows, one driver and one writer ----
 
 COHORT_INFO_LINES = (
     '##INFO=<ID=NS,Number=1,Type=Integer,Description="Number of samples with a called genotype">\n'
@@ -551,11 +551,6 @@ def cohort_union(samples):
     return list(slot_of), per
 
 
-def _cohort_header(header, names):
-    """the header text of a cohort VCF: the site tags' INFO lines in front, one column name per sample"""
-    return COHORT_INFO_LINES + header.replace("\tFORMAT\tSAMPLE\n", "\tFORMAT\t" + "\t".join(names) + "\n")
-
-
 def cohort_info(info, ns, ac, an=None, em=None):
     """the INFO column of a cohort row: the input's without any NS= / AN= / AC= / AF= field (whole fields, exact key), a lone `.` replaced,
     then NS, AN (2 NS unless given: the called samples' ploidies summed, --cohort-ploidy), AC and, when AN > 0, AF = "%.6g" % (AC / AN).
@@ -580,17 +575,48 @@ def cohort_info(info, ns, ac, an=None, em=None):
     return ";".join(keep)
 
 
-def write_vcf_cohort(out_path, rows, names, gt, pl, raw, done, site):
-    """write_vcf with one column per sample (gt, done: [n, S]; pl: [n, S, 3]; raw: [n, S, 2]; site: [n, 2] = NS, AC) and the site tags in
-    INFO -> the number of genotyped rows of every sample"""
-    columns, n_done = _item_columns(rows, None, gt, pl, raw, done)
-    _write_rows(out_path, rows, _cohort_header(FORMAT_HEADER, names), columns, lambda v, info: cohort_info(info, int(site[v, 0]), int(site[v, 1])))
+def write_vcf_cohort(out_path, rows, names, gt, pl, raw, done, site, ploidy=None, gq=None, af=None, em_steps=None):
+    """The one cohort writer: write_vcf with one column per sample (gt, done: [n, S]; pl: [n, S, >= 3]; raw: [n, S, 2]), the site tags' INFO lines
+    in front of the header and the tags in INFO; site: [n, 2] = NS, AC or [n, 3] = NS, AN, AC.  ploidy ([n, S]; None: diploid arrays, `Number=3`):
+    every item in write_vcf_ploidy's forms (pl: [n, S, >= P + 1]) and `Number=G` in the PL header line.  --cohort-prior: gq[n, S], one more
+    FORMAT field, GQ; af[n] and em_steps[n], EMAF / EMNC in INFO.  -> the number of genotyped rows of every sample"""
+    columns, n_done = _item_columns(rows, ploidy, gt, pl, raw, done, gq)
+    header = FORMAT_HEADER if ploidy is None else FORMAT_HEADER.replace(_PL_3, _PL_G)
+    if gq is not None:
+        header = header.replace("#CHROM\t", _GQ_LINE + "#CHROM\t")
+    header = COHORT_INFO_LINES + (COHORT_PRIOR_INFO_LINES if af is not None else "") + header.replace("\tFORMAT\tSAMPLE\n", "\tFORMAT\t" + "\t".join(names) + "\n")
+    an = np.shape(site)[1] == 3
+    _write_rows(out_path, rows, header, columns,
+                lambda v, info: cohort_info(info, int(site[v, 0]), int(site[v, -1]), int(site[v, 1]) if an else None,
+                                            None if af is None else (float(af[v]), bool(int(em_steps[v]) & EM_NOT_CONVERGED))))
     return n_done
 
 
-def cohort_chunk_rows(n_samples):
-    """rows per svjg_genotype_cohort call: n_rows x S x 37 bytes stays under 1 GiB"""
-    return max(1, COHORT_CALL_BYTES // (COHORT_ITEM_BYTES * max(1, int(n_samples))))
+def write_vcf_cohort_ploidy(out_path, rows, names, ploidy, gt, pl, raw, done, site):
+    """write_vcf_cohort at per-sample ploidy, in the argument order of its earlier writer"""
+    return write_vcf_cohort(out_path, rows, names, gt, pl, raw, done, site, ploidy)
+
+
+def write_vcf_cohort_prior(out_path, rows, names, ploidy, gt, pl, raw, done, site, gq, af, em_steps):
+    """write_vcf_cohort with the posterior calls, in the argument order of its earlier writer"""
+    return write_vcf_cohort(out_path, rows, names, gt, pl, raw, done, site, ploidy, gq, af, em_steps)
+
+
+def cohort_chunk_rows(n_samples, max_ploidy=None, prior=False):
+    """rows per cohort call, so that it stays under 1 GiB.  An item takes 37 bytes in svjg_genotype_cohort (max_ploidy None; svjg.h), else
+    8 (max_ploidy + 1) + 12, with the prior one more and 46 a row"""
+    item = COHORT_ITEM_BYTES if max_ploidy is None else 8 * (int(max_ploidy) + 1) + 12 + bool(prior)
+    return max(1, COHORT_CALL_BYTES // (item * max(1, int(n_samples)) + (46 if prior else 0)))
+
+
+def cohort_ploidy_chunk_rows(n_samples, max_ploidy):
+    """rows per svjg_genotype_cohort_ploidy call"""
+    return cohort_chunk_rows(n_samples, max_ploidy)
+
+
+def cohort_prior_chunk_rows(n_samples, max_ploidy):
+    """rows per svjg_genotype_cohort_prior call"""
+    return cohort_chunk_rows(n_samples, max_ploidy, True)
 
 
 def _cohort_rows(call, rows, step, empty, min_support, err, ploidy=None):
@@ -611,19 +637,37 @@ def _cohort_rows(call, rows, step, empty, min_support, err, ploidy=None):
     return tuple(np.concatenate([p[k] for p in parts]) for k in range(len(parts[0])))
 
 
-def _cohort_empty(S, n_pl, n_site):
-    return (np.zeros((0, S), np.uint8), np.zeros((0, S, n_pl), np.int64), np.zeros((0, S, 2), np.uint32), np.zeros((0, S), np.uint8),
-            np.zeros((0, n_site), np.uint32))
-
-
-def genotype_cohort_rows(ctx, rows, n_samples, min_support, err):
-    """the diploid cohort call over all rows -> (gt, pl[n, S, 3], raw, done, site[n, 2] = NS, AC)"""
+def genotype_cohort_rows(ctx, rows, n_samples, min_support, err, ploidy=None, prior=False, step=None):
+    """The cohort call over all rows.  ploidy None and no prior: svjg_genotype_cohort -> (gt (3: no call), pl[n, S, 3], raw, done, site[n, 2] = NS,
+    AC).  ploidy[n, S]: svjg_genotype_cohort_ploidy -> (gt (0xFF: no call), pl[n, S, max_ploidy + 1], raw, done, site[n, 3] = NS, AN, AC);
+    max_ploidy = the matrix's maximum, at least 1.  prior: svjg_genotype_cohort_prior, ploidy[n, S] or None (diploid) -> gt = the posterior calls
+    (0xFF: none), site of them, and behind site gq[n, S], af[n], em_steps[n].  step: rows per call (None: what fits 1 GiB)"""
     S = int(n_samples)
-    return _cohort_rows(lambda lo, hi, ms, e: ctx.genotype_cohort(rows.sv_type[lo:hi], rows.slot[lo:hi], rows.ok[lo:hi], ms, e),
-                        rows, cohort_chunk_rows(S), _cohort_empty(S, 3, 2), min_support, err)
+    if ploidy is not None:
+        ploidy = np.ascontiguousarray(ploidy, dtype=np.uint8)
+    plain = ploidy is None and not prior
+    max_ploidy = 2 if ploidy is None else max(1, int(ploidy.max())) if ploidy.size else 1
+
+    def call(lo, hi, ms, e):
+        if plain:
+            return ctx.genotype_cohort(rows.sv_type[lo:hi], rows.slot[lo:hi], rows.ok[lo:hi], ms, e)
+        fn = ctx.genotype_cohort_prior if prior else ctx.genotype_cohort_ploidy
+        return fn(rows.sv_type[lo:hi], rows.slot[lo:hi], rows.ok[lo:hi], None if ploidy is None else ploidy[lo:hi], max_ploidy, ms, e)
+    empty = (np.zeros((0, S), np.uint8), np.zeros((0, S, max_ploidy + 1), np.int64), np.zeros((0, S, 2), np.uint32), np.zeros((0, S), np.uint8),
+             np.zeros((0, 2 if plain else 3), np.uint32))
+    if prior:
+        empty += (np.zeros((0, S), np.uint8), np.zeros(0, np.float64), np.zeros(0, np.uint32))
+    if step is None:
+        step = cohort_chunk_rows(S, None if plain else max_ploidy, prior)
+    return _cohort_rows(call, rows, int(step), empty, min_support, err, ploidy)
 
 
-# ---- cohort at per-sample ploidy (--cohort LIST --cohort-ploidy FILE): svjg_genotype_cohort_ploidy, Python rows and the writer below ----
+def genotype_cohort_prior_rows(ctx, rows, n_samples, ploidy, min_support, err, step=None):
+    """genotype_cohort_rows with the prior"""
+    return genotype_cohort_rows(ctx, rows, n_samples, min_support, err, ploidy, True, step)
+
+
+# ---- cohort at per-sample ploidy (--cohort LIST --cohort-ploidy FILE): the file and the ploidy matrix of svjg_genotype_cohort_ploidy ----
 
 COHORT_PLOIDY_FORMS = "`SAMPLE<TAB>CHROM<TAB>PLOIDY` or `SAMPLE<TAB>CHROM<TAB>FROM<TAB>TO<TAB>PLOIDY`"
 
@@ -669,31 +713,7 @@ def cohort_ploidy_matrix(rows, per_sample_regions):
     return out
 
 
-def cohort_ploidy_chunk_rows(n_samples, max_ploidy):
-    """rows per svjg_genotype_cohort_ploidy call: n_rows x S x (8 (max_ploidy + 1) + 12) bytes stays under 1 GiB"""
-    return max(1, COHORT_CALL_BYTES // ((8 * (int(max_ploidy) + 1) + 12) * max(1, int(n_samples))))
-
-
-def genotype_cohort_ploidy_rows(ctx, rows, ploidy, min_support, err):
-    """the cohort call at ploidy[n, S] per item over all rows -> (gt, pl[n, S, max_ploidy + 1], raw, done, site[n, 3] = NS, AN, AC); max_ploidy =
-    the matrix's maximum, at least 1"""
-    ploidy = np.ascontiguousarray(ploidy, dtype=np.uint8)
-    S = ploidy.shape[1]
-    max_ploidy = max(1, int(ploidy.max())) if ploidy.size else 1
-    return _cohort_rows(lambda lo, hi, ms, e: ctx.genotype_cohort_ploidy(rows.sv_type[lo:hi], rows.slot[lo:hi], rows.ok[lo:hi], ploidy[lo:hi], max_ploidy, ms, e),
-                        rows, cohort_ploidy_chunk_rows(S, max_ploidy), _cohort_empty(S, max_ploidy + 1, 3), min_support, err, ploidy)
-
-
-def write_vcf_cohort_ploidy(out_path, rows, names, ploidy, gt, pl, raw, done, site):
-    """write_vcf_cohort with every item in write_vcf_ploidy's forms (ploidy, gt, done: [n, S]; pl: [n, S, >= P + 1]; site: [n, 3] = NS, AN,
-    AC) and `Number=G` in the PL header line -> the number of genotyped rows of every sample"""
-    columns, n_done = _item_columns(rows, ploidy, gt, pl, raw, done)
-    _write_rows(out_path, rows, _cohort_header(FORMAT_HEADER.replace(_PL_3, _PL_G), names), columns,
-                lambda v, info: cohort_info(info, int(site[v, 0]), int(site[v, 2]), int(site[v, 1])))
-    return n_done
-
-
-# ---- cohort with an allele-frequency prior (--cohort LIST --cohort-prior [--cohort-ploidy FILE]): svjg_genotype_cohort_prior ----
+# ---- cohort with an allele-frequency prior (--cohort LIST --cohort-prior [--cohort-ploidy FILE]): the header lines of svjg_genotype_cohort_prior's fields ----
 
 COHORT_PRIOR_INFO_LINES = (
     '##INFO=<ID=EMAF,Number=A,Type=Float,Description="Allele frequency estimated from all samples\' genotype likelihoods by EM under Hardy-Weinberg">\n'
@@ -701,37 +721,6 @@ COHORT_PRIOR_INFO_LINES = (
 )
 _GQ_LINE = '##FORMAT=<ID=GQ,Number=1,Type=Integer,Description="Genotype quality: -10 log10 of the posterior probability that the call is wrong, at most 99">\n'
 EM_NOT_CONVERGED = 1 << 31         # svjg.h: bit 31 of a row's em_steps word
-
-
-def cohort_prior_chunk_rows(n_samples, max_ploidy):
-    """rows per svjg_genotype_cohort_prior call: n_rows x (S x (8 (max_ploidy + 1) + 13) + 46) bytes stays under 1 GiB"""
-    return max(1, COHORT_CALL_BYTES // ((8 * (int(max_ploidy) + 1) + 13) * max(1, int(n_samples)) + 46))
-
-
-def genotype_cohort_prior_rows(ctx, rows, n_samples, ploidy, min_support, err, step=None):
-    """the cohort call with the allele-frequency prior over all rows, ploidy[n, S] or None (diploid) -> (gt = the posterior calls (0xFF: none),
-    pl, raw, done, site[n, 3] = NS, AN, AC of the posterior calls, gq[n, S], af[n], em_steps[n]); step: rows per call (None: what fits 1 GiB)"""
-    S = int(n_samples)
-    if ploidy is not None:
-        ploidy = np.ascontiguousarray(ploidy, dtype=np.uint8)
-    max_ploidy = 2 if ploidy is None else max(1, int(ploidy.max())) if ploidy.size else 1
-    empty = _cohort_empty(S, max_ploidy + 1, 3) + (np.zeros((0, S), np.uint8), np.zeros(0, np.float64), np.zeros(0, np.uint32))
-    return _cohort_rows(lambda lo, hi, ms, e: ctx.genotype_cohort_prior(rows.sv_type[lo:hi], rows.slot[lo:hi], rows.ok[lo:hi],
-                                                                        None if ploidy is None else ploidy[lo:hi], max_ploidy, ms, e),
-                        rows, cohort_prior_chunk_rows(S, max_ploidy) if step is None else int(step), empty, min_support, err, ploidy)
-
-
-def write_vcf_cohort_prior(out_path, rows, names, ploidy, gt, pl, raw, done, site, gq, af, em_steps):
-    """write_vcf_cohort / write_vcf_cohort_ploidy (ploidy None: diploid, `Number=3`) with the posterior calls: one more FORMAT field, GQ, and
-    EMAF / EMNC in INFO (gt: alt copies or 0xFF in either case; site: [n, 3] = NS, AN, AC) -> the number of genotyped rows of every sample"""
-    gt = np.asarray(gt)
-    columns, n_done = _item_columns(rows, np.full(gt.shape, 2, np.uint8) if ploidy is None else ploidy, gt, pl, raw, done, gq)
-    header = FORMAT_HEADER if ploidy is None else FORMAT_HEADER.replace(_PL_3, _PL_G)
-    header = header.replace("#CHROM\t", _GQ_LINE + "#CHROM\t")
-    _write_rows(out_path, rows, COHORT_INFO_LINES + COHORT_PRIOR_INFO_LINES + _cohort_header(header, names)[len(COHORT_INFO_LINES):], columns,
-                lambda v, info: cohort_info(info, int(site[v, 0]), int(site[v, 2]), int(site[v, 1]),
-                                            em=(float(af[v]), bool(int(em_steps[v]) & EM_NOT_CONVERGED))))
-    return n_done
 
 
 def run_cohort(list_path, vcf_path, out_path, min_support=3, err=0.00005, device=0, ploidy_file=None, prior=False):
@@ -757,20 +746,10 @@ def run_cohort(list_path, vcf_path, out_path, min_support=3, err=0.00005, device
         ctx.cohort_alloc(len(samples), len(keys))
         for s, (slots, counts) in enumerate(per):
             ctx.cohort_set_counts(s, slots, counts)
-        if prior:
-            gt, pl, raw, done, site, gq, af, em_steps = genotype_cohort_prior_rows(ctx, rows, len(samples), ploidy, min_support, err)
-        elif ploidy is None:
-            gt, pl, raw, done, site = genotype_cohort_rows(ctx, rows, len(samples), min_support, err)
-        else:
-            gt, pl, raw, done, site = genotype_cohort_ploidy_rows(ctx, rows, ploidy, min_support, err)
+        gt, pl, raw, done, site, *em = genotype_cohort_rows(ctx, rows, len(samples), min_support, err, ploidy, prior)   # (em: gq, af, em_steps with the prior)
     finally:
         ctx.close()
-    if prior:
-        n_done = write_vcf_cohort_prior(out_path, rows, names, ploidy, gt, pl, raw, done, site, gq, af, em_steps)
-    elif ploidy is None:
-        n_done = write_vcf_cohort(out_path, rows, names, gt, pl, raw, done, site)
-    else:
-        n_done = write_vcf_cohort_ploidy(out_path, rows, names, ploidy, gt, pl, raw, done, site)
+    n_done = write_vcf_cohort(out_path, rows, names, gt, pl, raw, done, site, ploidy, *em)
     for name, n in zip(names, n_done):
         print("Genotyped svs (%s): %d" % (name, n))
     return n_done

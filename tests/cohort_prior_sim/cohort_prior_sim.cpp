@@ -1,5 +1,5 @@
 // TEST HARNESS ONLY (never shipped, never loaded by the product): the per-item routines of the cohort call with an allele-frequency prior
-// (svjg_geno.h: prior_item, prior_expected, prior_call, prior_step, prior_segment_width, cohort_prior_layout) compiled with g++, and a row's
+// (svjg_geno.h: prior_load, prior_expected, prior_call, prior_step, prior_segment_width, and cohort_layout with the prior) compiled with g++, and a row's
 // EM run sequentially over its samples (the kernel sums the same x through a butterfly: another order of the same additions).  With
 // -DCOHORT_PRIOR_SIM_MAIN it is a stand-alone program (for -fsanitize=address,undefined) that runs random rows and checks what holds without a model.
 #define SVJG_HD inline
@@ -9,31 +9,25 @@
 
 using namespace svjg;
 
-static void load(uint32_t type, const uint32_t *raw, const uint8_t *done, const uint8_t *ploidy, uint64_t s, const double *tab, double &c_sum, PriorItem &it) {
-    const uint32_t P = done[s] ? (ploidy ? ploidy[s] : 2u) : 0u;
-    it.P = 0; it.gmax = 0; c_sum = 0.0;
-    for (uint32_t g = 0; g <= MAX_PLOIDY; ++g) it.w[g] = 0.0;
-    if (P >= 1 && P <= MAX_PLOIDY) prior_item(type, raw[s * 2], raw[s * 2 + 1], P, tab + ploidy_tab_at(P, 0), tab + PLOIDY_TAB + ploidy_tab_at(P, 0), c_sum, it);
-}
-
 // One row of S samples: raw[S][2], done[S], ploidy[S] or NULL (2 everywhere) -> *f (NaN: no estimate), *steps (the kernel's word: bit 31 = not
 // converged), gt[S], gq[S], site[3] = NS, AN, AC
-extern "C" void cprsim_row(uint32_t type, const uint32_t *raw, const uint8_t *done, const uint8_t *ploidy, uint64_t S, double err, uint32_t min_support,
+extern "C" void cprsim_row(uint32_t sv_type, const uint32_t *raw, const uint8_t *done, const uint8_t *ploidy, uint64_t S, double err, uint32_t min_support,
                            double *f, uint32_t *steps, uint8_t *gt, uint8_t *gq, uint32_t *site) {
     double tab[2 * PLOIDY_TAB];
     ploidy_log_table(err, tab);
+    const uint8_t t8 = (uint8_t)sv_type, *type = &t8;
     uint32_t sum_p = 0;
-    for (uint64_t s = 0; s < S; ++s) { PriorItem it; double c; load(type, raw, done, ploidy, s, tab, c, it); sum_p += it.P; }
+    for (uint64_t s = 0; s < S; ++s) { PriorItem it; double c; prior_load(type, raw, done, ploidy, s, tab, c, it); sum_p += it.P; }
     PriorRow row = prior_row_start(sum_p);
     while (!row.done) {
         double x = 0.0;
-        for (uint64_t s = 0; s < S; ++s) { PriorItem it; double c; load(type, raw, done, ploidy, s, tab, c, it); x += prior_expected(it, row.f); }
+        for (uint64_t s = 0; s < S; ++s) { PriorItem it; double c; prior_load(type, raw, done, ploidy, s, tab, c, it); x += prior_expected(it, row.f); }
         prior_step(row, x, sum_p);
     }
     site[0] = site[1] = site[2] = 0;
     for (uint64_t s = 0; s < S; ++s) {
         PriorItem it; double c;
-        load(type, raw, done, ploidy, s, tab, c, it);
+        prior_load(type, raw, done, ploidy, s, tab, c, it);
         const PriorCall k = prior_call(it, row.f, c, min_support);
         gt[s] = k.gt; gq[s] = k.gq;
         if (k.gt != 0xFF) { ++site[0]; site[1] += it.P; site[2] += k.gt; }
@@ -42,12 +36,12 @@ extern "C" void cprsim_row(uint32_t type, const uint32_t *raw, const uint8_t *do
 }
 
 // the weights of one item: w[9] = C(P, g) 10^d_g, -> the item's ploidy as the EM sees it (0: it takes no part); *gmax
-extern "C" uint32_t cprsim_item(uint32_t type, uint32_t ref, uint32_t alt, uint32_t P, double err, double *w, uint32_t *gmax) {
+extern "C" uint32_t cprsim_item(uint32_t sv_type, uint32_t ref, uint32_t alt, uint32_t P, double err, double *w, uint32_t *gmax) {
     double tab[2 * PLOIDY_TAB];
     ploidy_log_table(err, tab);
-    const uint32_t raw[2] = {ref, alt}; const uint8_t done = 1, p = (uint8_t)P;
+    const uint32_t raw[2] = {ref, alt}; const uint8_t done = 1, p = (uint8_t)P, t8 = (uint8_t)sv_type, *type = &t8;
     PriorItem it; double c;
-    load(type, raw, &done, &p, 0, tab, c, it);
+    prior_load(type, raw, &done, &p, 0, tab, c, it);
     for (uint32_t g = 0; g <= MAX_PLOIDY; ++g) w[g] = it.w[g];
     *gmax = it.gmax;
     return it.P;
@@ -56,10 +50,10 @@ extern "C" uint32_t cprsim_item(uint32_t type, uint32_t ref, uint32_t alt, uint3
 extern "C" uint32_t cprsim_width(uint64_t S) { return prior_segment_width(S); }
 extern "C" void cprsim_constants(double *tol, uint32_t *max_it, uint32_t *flag_bit, double *f_bound) { *tol = EM_TOL; *max_it = EM_MAX_IT; *flag_bit = EM_NOT_CONVERGED; *f_bound = EM_F_BOUND; }
 
-// cohort_prior_layout(n_rows, S, max_ploidy, per_item) -> out[19]: pl, raw, gt, flags, boundary, gq, af, psite, steps, site, maxn, in_at, logtab, slot, type, ok,
+// cohort_layout(n_rows, S, max_ploidy, per_item, true) -> out[19]: pl, raw, gt, flags, boundary, gq, af, psite, steps, site, maxn, in_at, logtab, slot, type, ok,
 // ploidy, total, in_bytes
 extern "C" void cprsim_layout(uint64_t n_rows, uint64_t S, uint32_t max_ploidy, int per_item, uint64_t *out) {
-    const CohortPriorLayout L = cohort_prior_layout(n_rows, S, max_ploidy, per_item != 0);
+    const CohortLayout L = cohort_layout(n_rows, S, max_ploidy, per_item != 0, true);
     const uint64_t v[19] = {L.pl, L.raw, L.gt, L.flags, L.boundary, L.gq, L.af, L.psite, L.steps, L.site, L.maxn, L.in_at, L.logtab, L.in.slot, L.in.type, L.in.ok,
                             L.ploidy, L.total, L.in_bytes};
     for (int i = 0; i < 19; ++i) out[i] = v[i];

@@ -82,7 +82,7 @@ def constants():
 
 
 def layout(n_rows, S, max_ploidy, per_item):
-    """svjg_geno.h: cohort_prior_layout -> dict of byte offsets (and in_bytes, total)"""
+    """svjg_geno.h: cohort_layout with the prior -> dict of byte offsets (and in_bytes, total)"""
     out = np.zeros(19, np.uint64)
     _lib().cprsim_layout(int(n_rows), int(S), int(max_ploidy), int(bool(per_item)), out.ctypes.data)
     return dict(zip(LAYOUT_FIELDS, (int(x) for x in out)))

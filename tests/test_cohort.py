@@ -134,7 +134,9 @@ def test_writer_against_the_reference_columns(golden, tmp_path, which):
 
 @pytest.mark.parametrize("n_rows, S", [(0, 1), (1, 1), (1, 65), (257, 3), (1000, 130)])
 def test_cohort_layout(n_rows, S):
-    L = sim.layout(n_rows, S)
+    full = sim.layout(n_rows, S, 2, False, False)                 # the one layout at max_ploidy 2, neither switch
+    assert not any(full[k] for k in ("gq", "af", "psite", "steps", "logtab")) and full["slot"] == full["in_at"] and full["ploidy"] == full["ok"] + n_rows
+    L = {k: full[k] for k in ("pl", "raw", "gt", "flags", "boundary", "site", "maxn", "slot", "type", "ok", "in_bytes", "total")}
     n = n_rows * S
     site = (35 * n + 7) & ~7
     maxn = site + 8 * n_rows
@@ -170,3 +172,29 @@ def test_segment_mask_is_the_set_of_lanes_with_the_same_row(S):
             assert np.array_equal(leader != 0, first == np.arange(64)), (S, n_items, w0)
             # exactly one leader per (wave, row) segment
             assert int(leader.sum()) == len(np.unique(row[inside]))
+
+
+
+@pytest.mark.parametrize("S", [1, 2, 3, 31, 63, 64, 65, 130])
+def test_diploid_site_sums_from_the_leaders_against_brute_force(S):
+    """k_genotype_cohort's three ballots (called, het, hom; gt 3 = no call) under cohort_segment's masks: NS and AC of every row, summed over its
+    segments' leaders, are the brute-force counts, and the word a leader adds is NS | AC << 32"""
+    rng = np.random.default_rng(700 + S)
+    full = 3 * 64 * S
+    for n_items in (full, full - S, (full // S // 2) * S + S):     # (the segment test's waves)
+        gt = rng.integers(0, 4, n_items).astype(np.uint8)          # 0, 1, 2, no call
+        R = n_items // S
+        tot, words = np.zeros((R, 2), np.int64), np.zeros(R, np.uint64)
+        for w0 in range(0, n_items, 64):
+            leader, ns, an, ac, word = sim.sums(w0, S, n_items, gt)
+            assert np.array_equal(leader, sim.wave(w0, S, n_items)[1]) and np.array_equal(an, 2 * ns)
+            assert np.array_equal(word, ns.astype(np.uint64) | (ac.astype(np.uint64) << np.uint64(32)))
+            off = leader == 0
+            assert not ns[off].any() and not ac[off].any() and not word[off].any()
+            r = (w0 + np.flatnonzero(leader)) // S
+            np.add.at(tot, r, np.stack([ns[leader != 0], ac[leader != 0]], axis=1))
+            np.add.at(words, r, word[leader != 0])
+        g2 = gt.reshape(R, S).astype(np.int64)
+        want = np.stack([(g2 != 3).sum(axis=1), np.where(g2 != 3, g2, 0).sum(axis=1)], axis=1)
+        assert np.array_equal(tot, want), (S, n_items)
+        assert np.array_equal(words, (want[:, 0] | (want[:, 1] << 32)).astype(np.uint64))

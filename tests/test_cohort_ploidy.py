@@ -1,5 +1,5 @@
 """Cohort genotyping at per-sample ploidy without a GPU: the --cohort-ploidy file, the ploidy matrix, the INFO rewrite with AN, the writer's
-text, and the integer pieces of the device leg compiled with g++ (tests/cohort_ploidy_sim: cohort_ploidy_layout, cohort_ploidy_sums under
+text, and the integer pieces of the device leg compiled with g++ (tests/cohort_sim: cohort_layout per item, cohort_ploidy_sums under
 cohort_segment's masks)."""
 import os
 import subprocess
@@ -10,8 +10,7 @@ import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
-from tests.cohort_sim import sim as seg_sim          # noqa: E402
-from tests.cohort_ploidy_sim import sim              # noqa: E402
+from tests.cohort_sim import sim                     # noqa: E402
 
 NAMES = ["A", "B b", "C"]
 VCF = ("##fileformat=VCFv4.2\n"
@@ -187,7 +186,7 @@ def test_writer_text_of_a_mixed_row(tmp_path):
 @pytest.mark.parametrize("S", [1, 3, 64, 65])
 @pytest.mark.parametrize("n_rows", [1, 7, 1000])
 def test_cohort_ploidy_layout(n_rows, S, max_ploidy):
-    L = sim.layout(n_rows, S, max_ploidy)
+    L = sim.layout(n_rows, S, max_ploidy, True, False)
     n, npl = n_rows * S, max_ploidy + 1
     assert (L["pl"], L["raw"], L["gt"], L["flags"], L["boundary"]) == (0, 8 * npl * n, 8 * npl * n + 8 * n, 8 * npl * n + 9 * n, 8 * npl * n + 10 * n)
     at = 0
@@ -220,8 +219,8 @@ def test_site_sums_from_ballots_against_brute_force(S):
         words = np.zeros(R, np.uint64)
         adds = np.zeros(R, np.int64)
         for w0 in range(0, n_items, 64):
-            leader, ns, an, ac, word = sim.wave(w0, S, n_items, gt, ploidy)
-            mask, seg_leader = seg_sim.wave(w0, S, n_items)          # cohort_segment's own masks
+            leader, ns, an, ac, word = sim.sums(w0, S, n_items, gt, ploidy)
+            mask, seg_leader = sim.wave(w0, S, n_items)              # cohort_segment's own masks
             assert np.array_equal(leader, seg_leader)
             for lane in np.flatnonzero(leader):
                 at = w0 + np.array([l for l in range(64) if (int(mask[lane]) >> l) & 1])
@@ -246,5 +245,5 @@ def test_site_sums_from_ballots_against_brute_force(S):
 def test_harness_under_the_sanitizers():
     """the stand-alone program (its own main) built with -fsanitize=address,undefined: every wave again, and the layouts"""
     p = subprocess.run([sim.build_main()], capture_output=True, text=True)
-    assert p.returncode == 0 and p.stdout.startswith("cohort_ploidy_sim ok:"), p.stdout + p.stderr
+    assert p.returncode == 0 and p.stdout.startswith("cohort_sim ok:"), p.stdout + p.stderr
     assert "runtime error" not in p.stderr and "AddressSanitizer" not in p.stderr

@@ -1,6 +1,6 @@
-"""The four step-by-step genotype calls share one host leg (svjg_capi.hip: genotype_leg) and keep a block each (svjg_ctx::leg[]): run on ONE
-context in either order, every call returns the bytes it returns on a context of its own, whichever calls ran in between, and a view of
-the diploid call's pinned block outlives the other three.  Needs an MI355X: run with -m gpu."""
+"""The six step-by-step genotype calls share one host leg (svjg_capi.hip: genotype_leg; the three cohort calls one more, cohort_call) and keep a
+block each (svjg_ctx::leg[]): run on ONE context in either order, every call returns the bytes it returns on a context of its own, whichever
+calls ran in between, and a view of the diploid call's pinned block outlives the other five.  Needs an MI355X: run with -m gpu."""
 import numpy as np
 import pytest
 
@@ -9,7 +9,7 @@ pytestmark = pytest.mark.gpu
 NONE = 0xFFFFFFFF
 R, S, N_SLOTS = 65, 3, 90              # two waves of rows with a ragged end; three samples; the sites' members lie behind the rows' slots
 MS, ERR = 3, 5e-5
-CALLS = ("rows", "ploidy", "sites", "cohort")
+CALLS = ("rows", "ploidy", "sites", "cohort", "cohort_ploidy", "cohort_prior")
 
 
 def _case():
@@ -22,6 +22,7 @@ def _case():
     c["ok"] = np.full(R, 3, np.uint8)
     c["ok"][11] = 0
     c["ploidy"] = np.resize(np.array([1, 2, 3, 8], np.uint8), R)
+    c["item_ploidy"] = np.resize(np.array([1, 2, 3, 8], np.uint8), R * S).reshape(R, S)       # cycled over the items
     sites = np.full((5, 6), NONE, np.uint32)
     at = R
     for i, K in enumerate((2, 3, 6, 2, 3)):
@@ -30,7 +31,7 @@ def _case():
     assert at <= N_SLOTS
     c["sites"] = sites
     # the matrix: its own counts, a fifth of the entries absent, and ONE item with ref + alt = 80 000 > 65 536 (sv_type 2: nothing is halved):
-    # only the cohort call meets it, so the table grows inside that leg, whichever legs ran in front of it
+    # only the three cohort-matrix calls meet it, so the table grows inside the first of their legs, whichever legs ran in front of it
     cm = rng.integers(0, 61, size=(N_SLOTS, S, 2)).astype(np.uint32)
     present = (rng.random((N_SLOTS, S)) >= 0.2).astype(np.uint8)
     deep = 20
@@ -60,6 +61,10 @@ def _call(ctx, c, which, view=False):
         return ctx.genotype_ploidy(c["t"], c["slot"], c["ok"], c["ploidy"], MS, ERR)
     if which == "sites":
         return ctx.genotype_sites(c["sites"], MS, ERR)
+    if which == "cohort_ploidy":
+        return ctx.genotype_cohort_ploidy(c["t"], c["slot"], c["ok"], c["item_ploidy"], 8, MS, ERR)
+    if which == "cohort_prior":
+        return ctx.genotype_cohort_prior(c["t"], c["slot"], c["ok"], None, 2, MS, ERR)
     return ctx.genotype_cohort(c["t"], c["slot"], c["ok"], MS, ERR)
 
 
@@ -83,17 +88,18 @@ def alone(case):
             _load(ctx, case)
             assert ctx.logfact_entries() == 0
             want[which] = _bytes(_call(ctx, case, which))
-            assert (ctx.logfact_entries() > 65536) == (which == "cohort")     # the deep item is the cohort call's alone
+            assert (ctx.logfact_entries() > 65536) == which.startswith("cohort")   # the deep item is the cohort-matrix calls' alone
         finally:
             ctx.close()
     gt, pl, raw, done, boundary, site = (np.frombuffer(b, dt) for b, dt in zip(want["cohort"], (np.uint8, np.int64, np.uint32, np.uint8, np.uint8, np.uint32)))
     item = case["deep"] * S + 1
     assert done[item] == 1 and raw[2 * item: 2 * item + 2].tolist() == [40_000, 40_000] and pl[3 * item: 3 * item + 3].any()
-    assert any(want["rows"][0]) and any(want["ploidy"][1]) and any(want["sites"][1])
+    assert any(want["rows"][0]) and any(want["ploidy"][1]) and any(want["sites"][1]) and any(want["cohort_ploidy"][1]) and any(want["cohort_prior"][1])
     return want
 
 
-@pytest.mark.parametrize("order", [("rows", "ploidy", "sites", "cohort", "rows"), ("rows", "cohort", "sites", "ploidy", "rows")])
+@pytest.mark.parametrize("order", [("rows", "ploidy", "sites", "cohort", "cohort_ploidy", "cohort_prior", "rows"),
+                                   ("rows", "cohort_prior", "cohort", "sites", "cohort_ploidy", "ploidy", "rows")])
 def test_every_call_in_a_block_of_its_own(case, alone, order):
     from svjg import capi
     ctx = capi.Context(0)
@@ -101,11 +107,11 @@ def test_every_call_in_a_block_of_its_own(case, alone, order):
         _load(ctx, case)
         view = _call(ctx, case, order[0], view=True)[:4]             # gt, pl, raw, genotyped: pointers into the pinned block
         assert _bytes(view) == alone["rows"][:4] and ctx.logfact_entries() == 65536
-        for which in order[1:4]:
+        for which in order[1:-1]:
             assert _bytes(_call(ctx, case, which)) == alone[which], which
             assert _bytes(view) == alone["rows"][:4], f"the view after {which}"
             assert ctx.boundary_flags(R).tobytes() == alone["rows"][4], f"the boundary bytes after {which}"
         assert ctx.logfact_entries() > 65536                         # the table grew inside a leg that was not the first
-        assert _bytes(_call(ctx, case, order[4])) == alone["rows"]
+        assert _bytes(_call(ctx, case, order[-1])) == alone["rows"]
     finally:
         ctx.close()
