@@ -4,6 +4,7 @@
 #include "svjg_kernels.h"
 #include "svjg_host_tables.h"
 #include "svjg_pass.h"
+#include "svjg_own.h"
 #include <rccl/rccl.h>
 #include <errno.h>
 #include <math.h>
@@ -79,7 +80,8 @@ constexpr uint64_t STAGE_PIECE = 8ull << 20;
 
 // The device block of a step-by-step genotype call and its pinned host twin (genotype_leg).  Every call has a block of its own: svjg_genotype_view
 // hands out pointers into BLOCK_ROWS' twin and svjg_genotype_boundary reads it later, and both must survive calls of the other five.
-struct LegBlock { void *d = nullptr;  uint64_t d_cap = 0;  void *h = nullptr;  uint64_t h_cap = 0; };
+// A fused pass's slot holds the same pair (RunSlot).
+struct LegBlock { DevBuf<uint8_t> d;  PinBuf h; };
 enum { BLOCK_ROWS, BLOCK_PLOIDY, BLOCK_SITES, BLOCK_COHORT, BLOCK_COHORT_PLOIDY, BLOCK_COHORT_PRIOR, LEG_BLOCKS };   // rows_layout, ploidy_layout, sites_layout, and cohort_layout for the three cohort blocks (svjg_geno.h)
 
 // slots the passes of svjg_run_begin rotate through: two may be in flight, and the one the NEXT pass will use is zeroed while the newest computes
@@ -98,62 +100,70 @@ struct PassTargets {
     int scratch;                                     // the compute stream the launch runs on (0: stream, 1: stream2): svjg_ctx::d_long[scratch]
 };
 
+// The graph on the device: the tables svjg_load_graph uploads and the two count vectors (counts: what the API works on; snap: what an overflowed classify
+// attempt is rolled back to).  free_graph resets it; GraphView gv looks into it.
+struct GraphTables {
+    DevBuf<svjg_node> nodes;  DevBuf<svjg_edge> edges;  DevBuf<uint32_t> hits;
+    DevBuf<uint8_t> cnames;  DevBuf<uint32_t> coff, clo, chash, names, links, nok;  DevBuf<uint16_t> disp;  DevBuf<uint32_t> ihits, pfx;
+    DevBuf<unsigned long long> counts, snap;
+};
+
+// Every allocation, event and stream is an owner (svjg_own.h) and goes with the context; members are destroyed last to first, so the streams stand first: buffers and events go before them.
 struct svjg_ctx {
+    Stream stream, copy_stream;
+    // The second compute stream: overlapped fused passes alternate between `stream` and it, everything else runs on `stream`.
+    // second_busy: stream2 holds work `stream` is not ordered behind; first_dirty: `stream` holds work other than overlapped passes that
+    // stream2 is not ordered behind (serial_enter / svjg_run_begin order them, ev_join[i] recorded on stream i).
+    Stream stream2;
+    Stream stage_stream[STAGE_THREADS];  // ingest: each feeder thread with a copy stream of its own
+    Event ev_join[2];
+    bool second_busy = false, first_dirty = false;
+    Event ev[6];
     int device = 0;
     int wall_khz = 0;                    // rate of wall_clock64(), the clock of the kernels' time stamps
     int n_cu = 256;
     int occ_main = 0;                    // workgroups of k_classify_main one CU holds
     uint32_t main_workers = 0;           // svjg_set_main_workers: the plan is made for at most that many workers (0: no cap; a test hook)
     MainPlan last_plan{0, 0, 0};  uint64_t last_claimed = 0;   // svjg_last_main_plan: the last k_classify_main launch that finished, and its status block's next_chunk
-    hipStream_t stream = nullptr, copy_stream = nullptr;
-    // The second compute stream: overlapped fused passes alternate between `stream` and it, everything else runs on `stream`.
-    // second_busy: stream2 holds work `stream` is not ordered behind; first_dirty: `stream` holds work other than overlapped passes that
-    // stream2 is not ordered behind (serial_enter / svjg_run_begin order them, ev_join[i] recorded on stream i).
-    hipStream_t stream2 = nullptr;
-    hipEvent_t ev_join[2] = {};
-    bool second_busy = false, first_dirty = false;
-    hipEvent_t ev[6] = {};
     std::string err;
     // graph
     bool have_graph = false, have_counts = false;
-    svjg_node *d_nodes = nullptr;  svjg_edge *d_edges = nullptr;  uint32_t *d_hits = nullptr;
-    uint8_t *d_cnames = nullptr;   uint32_t *d_coff = nullptr, *d_clo = nullptr, *d_chash = nullptr, *d_names = nullptr, *d_links = nullptr, *d_nok = nullptr;  uint16_t *d_disp = nullptr;  uint32_t *d_ihits = nullptr, *d_pfx = nullptr;
+    GraphTables graph;
     GraphView gv{};
     uint32_t gflags = 0, n_slots = 0;
-    unsigned long long *d_counts = nullptr, *d_snap = nullptr;
     // text
-    uint8_t *d_gaf = nullptr;  uint64_t gaf_cap = 0, gaf_bytes = 0;  bool have_gaf = false;
-    // ingest: pinned staging buffers, two per feeder thread, each feeder with a copy stream of its own
-    char *h_stage[STAGE_THREADS * 2] = {};
-    hipStream_t stage_stream[STAGE_THREADS] = {};
-    hipEvent_t stage_ev[STAGE_THREADS * 2] = {};
+    DevBuf<uint8_t> d_gaf;  uint64_t gaf_bytes = 0;  bool have_gaf = false;
+    // ingest: pinned staging buffers, two per feeder thread
+    PinBuf h_stage[STAGE_THREADS * 2];
+    Event stage_ev[STAGE_THREADS * 2];
     // outputs
-    uint64_t *d_deferred = nullptr;  uint64_t deferred_cap = 0;
-    svjg_hitrec *d_recs = nullptr;   uint64_t rec_cap = 0;
-    uint64_t *d_host = nullptr;      uint64_t host_cap = 0;     // offsets of the lines set aside for the host (SVJG_EXC_ASK_HOST)
-    DevStatus *d_st = nullptr;
-    unsigned long long *d_dbg = nullptr;
-    uint32_t *d_long[2] = {};            // LONG_WORDS words per worker of k_classify_main (ClassifyArgs::long_pre), [k]: of the launches on compute stream k — two main kernels may be alive at once, worker numbers are per launch (scratch_words)
+    DevBuf<uint64_t> d_deferred;
+    DevBuf<svjg_hitrec> d_recs;
+    DevBuf<uint64_t> d_host;             // offsets of the lines set aside for the host (SVJG_EXC_ASK_HOST)
+    DevBuf<DevStatus> d_st;
+    DevBuf<unsigned long long> d_dbg;
+    DevBuf<uint32_t> d_long[2];          // LONG_WORDS words per worker of k_classify_main (ClassifyArgs::long_pre), [k]: of the launches on compute stream k — two main kernels may be alive at once, worker numbers are per launch (scratch_words)
     const uint64_t *host_lines_src = nullptr;  uint64_t host_lines_cap = 0;   // the list hs().n_host counts (svjg_get_host_lines): d_host (nullptr), or the last finished pass's own
-    DevStatus *h_stp = nullptr;          // host twin of d_st in pinned memory: the status copies are asynchronous in both directions
-    DevStatus &hs() { return *h_stp; }
+    PinBuf h_stp;                        // host twin of d_st in pinned memory: the status copies are asynchronous in both directions; [1]: a fresh status (svjg_init)
+    DevStatus &hs(int k = 0) { return ((DevStatus *)h_stp.p)[k]; }
     uint64_t total_deferred = 0;
     // genotype scratch
-    dd *d_logfact = nullptr;  uint32_t logfact_n = 0;  dd *d_bsum = nullptr;
+    DevBuf<dd> d_logfact, d_bsum;  uint32_t logfact_n = 0;
     LegBlock leg[LEG_BLOCKS];
     uint64_t geno_rows = 0;                              // rows of the last svjg_genotype / svjg_genotype_view (svjg_genotype_boundary)
     // cohort: the slot-major count matrix (svjg_cohort_alloc: counts, then the presence bytes, ONE allocation) and the dense vector a sample's
     // column is staged in
-    unsigned long long *d_cm = nullptr;  uint8_t *d_cpresent = nullptr;  uint32_t cohort_samples = 0, cohort_slots = 0;
-    void *d_cstage = nullptr;  uint64_t cstage_cap = 0;
-    // resident VCF rows of svjg_set_rows / svjg_run_resident: device block (results, row inputs) and the pinned host block the results land in
-    struct RunSlot {
-        void *d = nullptr;  uint64_t d_cap = 0;  void *h = nullptr;  uint64_t h_cap = 0;  void *h_dev = nullptr;   // h_dev: the pinned block as the device sees it
-        unsigned long long *counts = nullptr;  uint64_t counts_cap = 0;   // the pass's own count vector (+ guard words): the next pass may zero its own while this one is genotyped
-        hipEvent_t ev[6] = {};  hipEvent_t computed = nullptr, copied = nullptr;
+    DevBuf<uint8_t> d_cm;  uint8_t *d_cpresent = nullptr;  uint32_t cohort_samples = 0, cohort_slots = 0;
+    unsigned long long *cm() const { return (unsigned long long *)d_cm.p; }
+    DevBuf<uint8_t> d_cstage;
+    // resident VCF rows of svjg_set_rows / svjg_run_resident: device block d (results, row inputs) and the pinned host block h the results land in
+    struct RunSlot : LegBlock {
+        void *h_dev = nullptr;           // the pinned block as the device sees it
+        DevBuf<unsigned long long> counts;   // the pass's own count vector (+ guard words): the next pass may zero its own while this one is genotyped
+        Event ev[6], computed, copied;
         uint64_t base_offset = 0;  uint32_t min_support = 0;  double err = 0;  bool had_text = false, slow_end_own = false, timed_by_events = false;
         // the pass's own lists (two main kernels may be alive at once): deferred lines, lines for the host; sized in pass_lists, while no pass uses the slot
-        uint64_t *deferred = nullptr;  uint64_t deferred_cap = 0;  uint64_t *host = nullptr;  uint64_t host_cap = 0;
+        DevBuf<uint64_t> deferred, host;
         bool overlapped = false;         // the pass's form (svjg_pass.h: pass_overlaps): no exact-path launch on its stream, svjg_run_end settles it
         bool inflight = false;           // begun, not yet ended
         bool settled = false;            // settle_pass has looked at it; geno_owed: it ran the exact path, the genotypes are owed once more
@@ -168,8 +178,8 @@ struct svjg_ctx {
     uint64_t pass_seq = 0;                               // passes begun: an overlapped pass k runs on compute stream k mod 2
     bool last_pass_deferred = false;                     // the last pass that finished deferred lines (pass_overlaps)
     uint64_t prev_t_last = 0;                            // t_last of the last finished pass's main kernel (pass_main_ticks); 0: none since the last host sync
-    int counts_in_slot = -1;                             // >= 0: the newest counts live in that slot's vector, not yet in d_counts (fetch_slot_counts)
-    void *d_run_in = nullptr;  uint64_t d_run_in_cap = 0;  uint64_t run_rows = 0;  bool have_rows = false;
+    int counts_in_slot = -1;                             // >= 0: the newest counts live in that slot's vector, not yet in graph.counts (fetch_slot_counts)
+    DevBuf<uint8_t> d_run_in;  uint64_t run_rows = 0;  bool have_rows = false;
     // timing of the last calls
     float ms_main = 0, ms_slow = 0, ms_geno = 0;
     float ms_main_stamps = 0, ms_main_events = 0;   // the last fused pass's k_classify_main by the device's clock / by the event pair (svjg_last_main_ms)
@@ -210,35 +220,30 @@ extern "C" int svjg_init(int device, svjg_ctx **out) {
     if (device < 0 || device >= n) { g_init_error = "device index out of range"; return SVJG_E_ARG; }
     svjg_ctx *c = new svjg_ctx();
     c->device = device;
-    if (hipSetDevice(device) != hipSuccess || hipStreamCreate(&c->stream) != hipSuccess || hipStreamCreate(&c->stream2) != hipSuccess ||
-        hipEventCreateWithFlags(&c->ev_join[0], hipEventDisableTiming) != hipSuccess || hipEventCreateWithFlags(&c->ev_join[1], hipEventDisableTiming) != hipSuccess) {
+    if (hipSetDevice(device) != hipSuccess || c->stream.create() != hipSuccess || c->stream2.create() != hipSuccess ||
+        c->ev_join[0].create(hipEventDisableTiming) != hipSuccess || c->ev_join[1].create(hipEventDisableTiming) != hipSuccess) {
         g_init_error = "hipSetDevice / hipStreamCreate failed";
-        delete c;
+        delete c;                                                 // (with whatever it made so far, here and below)
         return SVJG_E_HIP;
     }
     hipDeviceProp_t prop;
     if (hipGetDeviceProperties(&prop, device) == hipSuccess) c->n_cu = prop.multiProcessorCount;
     if (hipDeviceGetAttribute(&c->wall_khz, hipDeviceAttributeWallClockRate, device) != hipSuccess || c->wall_khz < 1) c->wall_khz = 0;
-    for (auto &ev : c->ev) hipEventCreate(&ev);
-    if (hipMalloc(&c->d_dbg, DBG_WORDS * 8) != hipSuccess || hipMalloc(&c->d_st, sizeof(DevStatus)) != hipSuccess ||
-        hipHostMalloc((void **)&c->h_stp, 2 * sizeof(DevStatus), hipHostMallocDefault) != hipSuccess) {
+    for (auto &ev : c->ev) (void)ev.create();
+    if (c->d_dbg.reserve(DBG_WORDS) != hipSuccess || c->d_st.reserve(1) != hipSuccess || c->h_stp.reserve(2 * sizeof(DevStatus), hipHostMallocDefault) != hipSuccess) {
         g_init_error = "hipMalloc failed";
         delete c;
         return SVJG_E_NOMEM;
     }
     memset(c->h_stp, 0, 2 * sizeof(DevStatus));
-    c->h_stp[1].err = ~0ull;                                  // [1]: a fresh status, never written again (reset_status copies from it without a sync)
+    c->hs(1).err = ~0ull;                                     // [1]: a fresh status, never written again (reset_status copies from it without a sync)
     hipFuncSetAttribute((const void *)k_classify_main, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
     *out = c;
     return 0;
 }
 
 static void free_graph(svjg_ctx *c) {
-    hipFree(c->d_nodes); hipFree(c->d_edges); hipFree(c->d_hits); hipFree(c->d_cnames); hipFree(c->d_coff);
-    hipFree(c->d_clo); hipFree(c->d_chash); hipFree(c->d_counts); hipFree(c->d_snap); hipFree(c->d_names); hipFree(c->d_links); hipFree(c->d_disp); hipFree(c->d_ihits); hipFree(c->d_nok); hipFree(c->d_pfx);
-    c->d_pfx = nullptr; c->d_nok = nullptr; c->d_names = nullptr; c->d_links = nullptr; c->d_disp = nullptr; c->d_ihits = nullptr;
-    c->d_nodes = nullptr; c->d_edges = nullptr; c->d_hits = nullptr; c->d_cnames = nullptr; c->d_coff = nullptr;
-    c->d_clo = nullptr; c->d_chash = nullptr; c->d_counts = nullptr; c->d_snap = nullptr;
+    c->graph = GraphTables{};
     c->have_graph = false; c->have_counts = false;
     for (auto &r : c->run) r.clean = false;                   // (the next graph's vector may be longer than what was zeroed)
 }
@@ -250,28 +255,6 @@ extern "C" void svjg_destroy(svjg_ctx *c) {
     if (c->stream2) hipStreamSynchronize(c->stream2);
     if (c->copy_stream) hipStreamSynchronize(c->copy_stream);
     if (c->comm) ncclCommDestroy(c->comm);
-    free_graph(c);
-    hipFree(c->d_long[0]); hipFree(c->d_long[1]);
-    hipFree(c->d_gaf); hipFree(c->d_deferred); hipFree(c->d_recs); hipFree(c->d_host); hipFree(c->d_st); hipFree(c->d_logfact);
-    hipFree(c->d_bsum); hipFree(c->d_run_in);
-    hipFree(c->d_cm); hipFree(c->d_cstage);
-    for (auto &b : c->leg) { hipFree(b.d); if (b.h) hipHostFree(b.h); }
-    for (auto &r : c->run) {
-        hipFree(r.d); hipFree(r.counts); hipFree(r.deferred); hipFree(r.host);
-        if (r.h) hipHostFree(r.h);
-        for (auto &e : r.ev) if (e) hipEventDestroy(e);
-        if (r.computed) hipEventDestroy(r.computed);
-        if (r.copied) hipEventDestroy(r.copied);
-    }
-    if (c->h_stp) hipHostFree(c->h_stp);
-    for (auto &b : c->h_stage) if (b) hipHostFree(b);
-    for (auto &ev : c->stage_ev) if (ev) hipEventDestroy(ev);
-    for (auto &st : c->stage_stream) if (st) hipStreamDestroy(st);
-    for (auto &ev : c->ev) if (ev) hipEventDestroy(ev);
-    for (auto &ev : c->ev_join) if (ev) hipEventDestroy(ev);
-    if (c->copy_stream) hipStreamDestroy(c->copy_stream);
-    if (c->stream2) hipStreamDestroy(c->stream2);
-    if (c->stream) hipStreamDestroy(c->stream);
     delete c;
 }
 
@@ -296,9 +279,9 @@ static int sync_compute(svjg_ctx *c) {
 }
 
 template <class T>
-static int upload(svjg_ctx *c, T **dst, const T *src, uint64_t n, uint64_t extra = 0) {
-    HIPCHK(c, hipMalloc((void **)dst, (n + extra + 1) * sizeof(T)));
-    if (n) HIPCHK(c, hipMemcpyAsync(*dst, src, n * sizeof(T), hipMemcpyHostToDevice, c->stream));
+static int upload(svjg_ctx *c, DevBuf<T> &dst, const T *src, uint64_t n, uint64_t extra = 0) {
+    HIPCHK(c, dst.reserve(n + extra + 1));
+    if (n) HIPCHK(c, hipMemcpyAsync(dst, src, n * sizeof(T), hipMemcpyHostToDevice, c->stream));
     return 0;
 }
 
@@ -313,12 +296,10 @@ constexpr double FIRST_CHUNK_SHARE = SVJG_FIRST_SHARE;       // of an even share
 
 // the count vector and its guard words (svjg_pass.h), in bytes
 static uint64_t counts_bytes(const svjg_ctx *c) { return ((uint64_t)c->n_slots + GUARD_WORDS) * 8; }
-// d_counts and the snapshot an overflowed classify attempt is rolled back to
-static int alloc_count_vectors(svjg_ctx *c, uint32_t n_slots) {
-    c->n_slots = n_slots;
-    HIPCHK(c, hipMalloc((void **)&c->d_counts, counts_bytes(c)));
-    HIPCHK(c, hipMalloc((void **)&c->d_snap, counts_bytes(c)));
-    c->have_counts = true;
+// graph.counts and the snapshot an overflowed classify attempt is rolled back to
+static int alloc_count_vectors(svjg_ctx *c, GraphTables &t, uint32_t n_slots) {
+    HIPCHK(c, t.counts.reserve((uint64_t)n_slots + GUARD_WORDS));
+    HIPCHK(c, t.snap.reserve((uint64_t)n_slots + GUARD_WORDS));
     return 0;
 }
 // blocks of tpb over n items, 1 to 1024 (the kernels stride)
@@ -326,8 +307,8 @@ static uint32_t capped_grid(uint64_t n, uint32_t tpb = TPB) { const uint64_t g =
 
 static int reset_status(svjg_ctx *c, bool all) {
     if (all) {                                                // from the constant copy: the host's own status may be written again at once
-        c->hs() = c->h_stp[1]; c->total_deferred = 0;
-        HIPCHK(c, hipMemcpyAsync(c->d_st, &c->h_stp[1], sizeof(DevStatus), hipMemcpyHostToDevice, c->stream));
+        c->hs() = c->hs(1); c->total_deferred = 0;
+        HIPCHK(c, hipMemcpyAsync(c->d_st, &c->hs(1), sizeof(DevStatus), hipMemcpyHostToDevice, c->stream));
         return 0;
     }
     // (every earlier writer of hs() on the stream — the status read-backs — was followed by a synchronisation)
@@ -336,45 +317,50 @@ static int reset_status(svjg_ctx *c, bool all) {
     return 0;
 }
 
+// the graph's tables and count vectors into `t`, the view of them into c->gv (the copies on c->stream, waited for)
+static int upload_graph(svjg_ctx *c, const svjg_graph *g, GraphTables &t) {
+    int rc;
+    if ((rc = upload(c, t.nodes, g->nodes, g->n_nodes + 1))) return rc;
+    if ((rc = upload(c, t.edges, g->edges, g->n_edges))) return rc;
+    if ((rc = upload(c, t.hits, g->hits, g->n_hits))) return rc;
+    if ((rc = upload(c, t.cnames, (const uint8_t *)g->chrom_names, g->chrom_off[g->n_chrom], 8))) return rc;
+    if ((rc = upload(c, t.coff, g->chrom_off, g->n_chrom + 1))) return rc;
+    if ((rc = upload(c, t.clo, g->chrom_node_lo, g->n_chrom + 1))) return rc;
+    std::vector<uint32_t> hash = build_chrom_hash(*g);
+    if ((rc = upload(c, t.chash, hash.data(), hash.size()))) return rc;
+    const std::shared_ptr<const KernelTables> ktp = kernel_tables_for(*g);   // (built once per graph and process)
+    const KernelTables &kt = *ktp;
+    if ((rc = upload(c, t.names, kt.names.data(), kt.names.size()))) return rc;
+    if ((rc = upload(c, t.links, kt.links.data(), kt.links.size()))) return rc;
+    if ((rc = upload(c, t.disp, kt.disp.data(), kt.disp.size()))) return rc;
+    if ((rc = upload(c, t.ihits, kt.ihits.data(), kt.ihits.size()))) return rc;
+    if ((rc = upload(c, t.nok, kt.node_of_kid.data(), kt.node_of_kid.size()))) return rc;
+    if (!kt.name_pfx.empty() && (rc = upload(c, t.pfx, kt.name_pfx.data(), kt.name_pfx.size()))) return rc;   // (names of 49..64 bytes: rare)
+    HIPCHK(c, hipStreamSynchronize(c->stream));           // `hash` and `kt` are locals
+    c->gv.nodes = t.nodes; c->gv.n_nodes = (uint32_t)g->n_nodes; c->gv.edges = t.edges; c->gv.hits = t.hits;
+    c->gv.chrom_names = t.cnames; c->gv.chrom_off = t.coff; c->gv.chrom_lo = t.clo; c->gv.chrom_hash = t.chash;
+    c->gv.n_chrom = g->n_chrom; c->gv.hash_mask = (uint32_t)hash.size() - 1; c->gv.d_over = g->d_over;
+    c->gv.dover_list = (g->flags & SVJG_GRAPH_DOVER_LIST) ? 1u : 0u;
+    c->gv.name_pfx = t.pfx;
+    c->gv.node_of_kid = t.nok; c->gv.name_tab = t.names; c->gv.name_ihits = t.ihits; c->gv.name_disp = t.disp; c->gv.name_slots = kt.name_slots; c->gv.name_buckets = kt.name_buckets;
+    c->gv.name_complete = (kt.names_left_out == 0 && kt.names_skipped == 0) ? 1u : 0u;
+    c->gv.link_tab = t.links; c->gv.link_mask = kt.link_mask; c->gv.link_seed = kt.link_seed;
+    c->gflags = g->flags;
+    if (g->flags & SVJG_GRAPH_DOVER_LIST) c->gflags |= SVJG_GRAPH_ALL_SLOW;   // (the exact routine knows where the reference's TypeError sits)
+    if (kt.links_left_out) c->gflags |= SVJG_GRAPH_ALL_SLOW;   // a link the main kernel could not find would be a silent miss
+    return alloc_count_vectors(c, t, g->n_slots);
+}
+
 extern "C" int svjg_load_graph(svjg_ctx *c, const svjg_graph *g) {
     if (!c || !g || !g->nodes || !g->chrom_off || !g->chrom_node_lo) return SVJG_E_ARG;
     if (g->n_nodes >= 0x7FFFFFFFull || g->n_edges >= 0x7FFFFFFFull || g->n_chrom >= 65535) { c->err = "graph too large"; return SVJG_E_ARG; }
     if (g->d_over >= 0x80000000u) { c->err = "d_over too large"; return SVJG_E_ARG; }   // (the overlap sums of the main kernel are 32 bits wide)
     HIPCHK(c, hipSetDevice(c->device));
-    free_graph(c);
-    int rc;
-    struct Undo { svjg_ctx *c; bool armed = true; ~Undo() { if (armed) { hipStreamSynchronize(c->stream); free_graph(c); } } } undo{c};   // a failure midway leaves nothing behind
-    if ((rc = upload(c, &c->d_nodes, g->nodes, g->n_nodes + 1))) return rc;
-    if ((rc = upload(c, &c->d_edges, g->edges, g->n_edges))) return rc;
-    if ((rc = upload(c, &c->d_hits, g->hits, g->n_hits))) return rc;
-    if ((rc = upload(c, &c->d_cnames, (const uint8_t *)g->chrom_names, g->chrom_off[g->n_chrom], 8))) return rc;
-    if ((rc = upload(c, &c->d_coff, g->chrom_off, g->n_chrom + 1))) return rc;
-    if ((rc = upload(c, &c->d_clo, g->chrom_node_lo, g->n_chrom + 1))) return rc;
-    std::vector<uint32_t> hash = build_chrom_hash(*g);
-    if ((rc = upload(c, &c->d_chash, hash.data(), hash.size()))) return rc;
-    const std::shared_ptr<const KernelTables> ktp = kernel_tables_for(*g);   // (built once per graph and process)
-    const KernelTables &kt = *ktp;
-    if ((rc = upload(c, &c->d_names, kt.names.data(), kt.names.size()))) return rc;
-    if ((rc = upload(c, &c->d_links, kt.links.data(), kt.links.size()))) return rc;
-    if ((rc = upload(c, &c->d_disp, kt.disp.data(), kt.disp.size()))) return rc;
-    if ((rc = upload(c, &c->d_ihits, kt.ihits.data(), kt.ihits.size()))) return rc;
-    if ((rc = upload(c, &c->d_nok, kt.node_of_kid.data(), kt.node_of_kid.size()))) return rc;
-    if (!kt.name_pfx.empty() && (rc = upload(c, &c->d_pfx, kt.name_pfx.data(), kt.name_pfx.size()))) return rc;   // (names of 49..64 bytes: rare)
-    HIPCHK(c, hipStreamSynchronize(c->stream));           // `hash` and `kt` are locals
-    c->gv.nodes = c->d_nodes; c->gv.n_nodes = (uint32_t)g->n_nodes; c->gv.edges = c->d_edges; c->gv.hits = c->d_hits;
-    c->gv.chrom_names = c->d_cnames; c->gv.chrom_off = c->d_coff; c->gv.chrom_lo = c->d_clo; c->gv.chrom_hash = c->d_chash;
-    c->gv.n_chrom = g->n_chrom; c->gv.hash_mask = (uint32_t)hash.size() - 1; c->gv.d_over = g->d_over;
-    c->gv.dover_list = (g->flags & SVJG_GRAPH_DOVER_LIST) ? 1u : 0u;
-    c->gv.name_pfx = c->d_pfx;
-    c->gv.node_of_kid = c->d_nok; c->gv.name_tab = c->d_names; c->gv.name_ihits = c->d_ihits; c->gv.name_disp = c->d_disp; c->gv.name_slots = kt.name_slots; c->gv.name_buckets = kt.name_buckets;
-    c->gv.name_complete = (kt.names_left_out == 0 && kt.names_skipped == 0) ? 1u : 0u;
-    c->gv.link_tab = c->d_links; c->gv.link_mask = kt.link_mask; c->gv.link_seed = kt.link_seed;
-    c->gflags = g->flags;
-    if (g->flags & SVJG_GRAPH_DOVER_LIST) c->gflags |= SVJG_GRAPH_ALL_SLOW;   // (the exact routine knows where the reference's TypeError sits)
-    if (kt.links_left_out) c->gflags |= SVJG_GRAPH_ALL_SLOW;   // a link the main kernel could not find would be a silent miss
-    if ((rc = alloc_count_vectors(c, g->n_slots))) return rc;
-    c->have_graph = true;
-    undo.armed = false;
+    free_graph(c);                                            // (first: the old graph and the new one are never both on the device)
+    GraphTables t;                                            // a failure midway leaves nothing behind: t goes, behind whatever is still being copied into it
+    if (const int rc = upload_graph(c, g, t)) { hipStreamSynchronize(c->stream); return rc; }
+    c->graph = std::move(t);
+    c->n_slots = g->n_slots; c->have_counts = true; c->have_graph = true;
     return svjg_reset_counts(c);
 }
 
@@ -382,8 +368,9 @@ extern "C" int svjg_alloc_counts(svjg_ctx *c, uint32_t n_slots) {
     if (!c) return SVJG_E_ARG;
     HIPCHK(c, hipSetDevice(c->device));
     free_graph(c);
-    const int rc = alloc_count_vectors(c, n_slots);
-    return rc ? rc : svjg_reset_counts(c);
+    if (const int rc = alloc_count_vectors(c, c->graph, n_slots)) return rc;
+    c->n_slots = n_slots; c->have_counts = true;
+    return svjg_reset_counts(c);
 }
 
 extern "C" int svjg_reset_counts(svjg_ctx *c) {
@@ -391,18 +378,17 @@ extern "C" int svjg_reset_counts(svjg_ctx *c) {
     c->counts_in_slot = -1;
     HIPCHK(c, hipSetDevice(c->device));
     { const int rc0 = serial_enter(c); if (rc0) return rc0; }
-    HIPCHK(c, hipMemsetAsync(c->d_counts, 0, counts_bytes(c), c->stream));
+    HIPCHK(c, hipMemsetAsync(c->graph.counts, 0, counts_bytes(c), c->stream));
     return reset_status(c, true);                             // (nothing to wait for: the next call on the stream comes behind both)
 }
 
 // room for n bytes of text plus the zero padding the kernels read past the end without bounds tests
 static int gaf_reserve(svjg_ctx *c, uint64_t n, uint64_t *need_out) {
     const uint64_t need = ((n + 15) & ~15ull) + TEXT + 64;
-    if (need > c->gaf_cap) {
+    if (need > c->d_gaf.cap) {
         { const int rc0 = sync_compute(c); if (rc0) return rc0; }     // (both compute streams read the text)
-        hipFree(c->d_gaf); c->d_gaf = nullptr; c->gaf_cap = 0;
-        HIPCHK(c, hipMalloc((void **)&c->d_gaf, need));
-        c->gaf_cap = need;
+        c->d_gaf.release();                                           // (first: the old text and the new one are never both on the device)
+        HIPCHK(c, c->d_gaf.reserve(need));
     }
     *need_out = need;
     return 0;
@@ -411,11 +397,10 @@ static int gaf_reserve(svjg_ctx *c, uint64_t n, uint64_t *need_out) {
 // bytes [offset, offset + n) of the open file -> d_gaf through the pinned staging buffers
 static int staged_upload(svjg_ctx *c, int fd, uint64_t offset, uint64_t n, uint64_t dst_off = 0) {
     for (int i = 0; i < STAGE_THREADS * 2; ++i) {
-        if (!c->h_stage[i]) HIPCHK(c, hipHostMalloc((void **)&c->h_stage[i], STAGE_PIECE, hipHostMallocDefault));
-        if (!c->stage_ev[i]) HIPCHK(c, hipEventCreateWithFlags(&c->stage_ev[i], hipEventDisableTiming));
+        HIPCHK(c, c->h_stage[i].reserve(STAGE_PIECE, hipHostMallocDefault));
+        HIPCHK(c, c->stage_ev[i].create(hipEventDisableTiming));
     }
-    for (int t = 0; t < STAGE_THREADS; ++t)
-        if (!c->stage_stream[t]) HIPCHK(c, hipStreamCreateWithFlags(&c->stage_stream[t], hipStreamNonBlocking));
+    for (int t = 0; t < STAGE_THREADS; ++t) HIPCHK(c, c->stage_stream[t].create(hipStreamNonBlocking));
     const uint64_t n_pieces = (n + STAGE_PIECE - 1) / STAGE_PIECE;
     std::string errs[STAGE_THREADS];
     int rcs[STAGE_THREADS] = {};
@@ -503,34 +488,22 @@ extern "C" int svjg_gaf_upload_file(svjg_ctx *c, const char *path, uint64_t offs
     return gaf_finish(c, n, need);
 }
 
-static int ensure(svjg_ctx *c, void **p, uint64_t *cap, uint64_t want, size_t elem, bool keep) {
-    if (want <= *cap) return 0;
-    // a buffer that keeps its contents grows by at least half: the hit records of a file classified in pieces used to be moved into a
-    // buffer a piece larger 2 x 169 times at configs[3] (hipMalloc / copy / hipFree of up to 5.7 GB each: 7 of the 8.9 s of its ingest)
-    const uint64_t asked = want;
-    if (keep && *cap && want < *cap + *cap / 2) want = *cap + *cap / 2;
-    void *q = nullptr;
-    if (want != asked && hipMalloc(&q, want * elem) != hipSuccess) { (void)hipGetLastError(); q = nullptr; want = asked; }   // (no room for the margin: what was asked for)
-    if (!q) HIPCHK(c, hipMalloc(&q, want * elem));
-    if (keep && *p && *cap) HIPCHK(c, hipMemcpyAsync(q, *p, *cap * elem, hipMemcpyDeviceToDevice, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    if (c->second_busy) HIPCHK(c, hipStreamSynchronize(c->stream2));      // (nothing enqueued anywhere still uses the old block)
-    hipFree(*p);
-    *p = q; *cap = want;
+// Room in a device buffer the kernels of this context may still be using (DevBuf::reserve): the contents, if kept, are copied on c->stream, and the
+// old block is freed once nothing enqueued anywhere still uses it.
+struct ComputeIdle {
+    const svjg_ctx *c;
+    hipError_t operator()() const {
+        const hipError_t e = hipStreamSynchronize(c->stream);
+        return e == hipSuccess && c->second_busy ? hipStreamSynchronize(c->stream2) : e;
+    }
+};
+template <class T>
+static int ensure(svjg_ctx *c, DevBuf<T> &b, uint64_t want, bool keep) {
+    HIPCHK(c, b.reserve(want, keep, c->stream, ComputeIdle{c}));
     return 0;
 }
 
-// the same for a pinned host block (contents not kept)
-static int ensure_pinned(svjg_ctx *c, void **p, uint64_t *cap, uint64_t want, unsigned int flags) {
-    if (want <= *cap) return 0;
-    if (*p) hipHostFree(*p);
-    *p = nullptr; *cap = 0;
-    HIPCHK(c, hipHostMalloc(p, want, flags));
-    *cap = want;
-    return 0;
-}
-
-// The passes of svjg_run_begin keep their counts in vectors of their own; the rest of the API works on d_counts: the newest pass's
+// The passes of svjg_run_begin keep their counts in vectors of their own; the rest of the API works on graph.counts: the newest pass's
 // vector is copied there when someone asks for it (svjg_get_counts, svjg_genotype, svjg_classify adding to it, ...).
 static int settle_pass(svjg_ctx *c, svjg_ctx::RunSlot &r);
 static int fetch_slot_counts(svjg_ctx *c) {
@@ -543,21 +516,21 @@ static int fetch_slot_counts(svjg_ctx *c) {
     if (c->run[k].inflight && c->run[k].overlapped) { const int rc0 = settle_pass(c, c->run[k]); if (rc0) return rc0; }
     { const int rc0 = serial_enter(c); if (rc0) return rc0; }      // (the pass that uses this slot next may run on stream2: it comes behind the copy)
     if (c->run[k].copied) HIPCHK(c, hipStreamWaitEvent(c->stream, c->run[k].copied, 0));   // (the pass's all-reduce runs on the second stream)
-    HIPCHK(c, hipMemcpyAsync(c->d_counts, c->run[k].counts, counts_bytes(c), hipMemcpyDeviceToDevice, c->stream));
+    HIPCHK(c, hipMemcpyAsync(c->graph.counts, c->run[k].counts, counts_bytes(c), hipMemcpyDeviceToDevice, c->stream));
     return 0;
 }
 
-// the two sets of targets there are, each from its fields in this one place: the step-by-step calls' (the context's own lists, d_counts, on c->stream) ...
-static PassTargets step_targets(const svjg_ctx *c) { return PassTargets{c->d_counts, c->d_st, c->d_deferred, c->deferred_cap, c->d_host, c->host_cap, c->d_recs, c->rec_cap, 0}; }
+// the two sets of targets there are, each from its fields in this one place: the step-by-step calls' (the context's own lists, graph.counts, on c->stream) ...
+static PassTargets step_targets(const svjg_ctx *c) { return PassTargets{c->graph.counts, c->d_st, c->d_deferred, c->d_deferred.cap, c->d_host, c->d_host.cap, c->d_recs, c->d_recs.cap, 0}; }
 // ... and a fused pass's: everything its slot's (the status block lies in the slot's row block: its tail goes to the host in one small copy)
 static PassTargets slot_targets(const svjg_ctx *c, const svjg_ctx::RunSlot &r, const RunLayout &L) {
-    return PassTargets{r.counts, (DevStatus *)((uint8_t *)r.d + L.status), r.deferred, r.deferred_cap, r.host, r.host_cap, nullptr, 0, r.on == c->stream2 ? 1 : 0};
+    return PassTargets{r.counts, (DevStatus *)((uint8_t *)r.d + L.status), r.deferred, r.deferred.cap, r.host, r.host.cap, nullptr, 0, r.on == c->stream2 ? 1 : 0};
 }
 
 // the scratch words of the launches on compute stream k, allocated at the stream's first launch (the second block: only a context that overlaps
 // passes has one); nullptr: no memory.  Both are freed where the occupancy becomes known (main_launch_setup).
 static uint32_t *scratch_words(svjg_ctx *c, int k) {
-    if (!c->d_long[k] && hipMalloc((void **)&c->d_long[k], (uint64_t)c->n_cu * (uint64_t)c->occ_main * LONG_WORDS * sizeof(uint32_t)) != hipSuccess) { (void)hipGetLastError(); c->d_long[k] = nullptr; }
+    if (!c->d_long[k] && c->d_long[k].reserve((uint64_t)c->n_cu * (uint64_t)c->occ_main * LONG_WORDS) != hipSuccess) (void)hipGetLastError();
     return c->d_long[k];
 }
 
@@ -581,7 +554,7 @@ static int main_launch_setup(svjg_ctx *c, const PassTargets &t, uint64_t begin, 
         int occ = 0;
         if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, k_classify_main, (int)WG, lds) != hipSuccess || occ < 1) occ = 1;
         c->occ_main = occ = main_occupancy(occ, lds, LDS_GRANULE);
-        for (auto &w : c->d_long) { hipFree(w); w = nullptr; }
+        for (auto &w : c->d_long) w.release();
 #ifdef SVJG_ABLATE
         ablate_occupancy(c, occ, lds);
 #endif
@@ -608,7 +581,7 @@ static int launch_exact(svjg_ctx *c, const ClassifyArgs &a, uint64_t wave_rounds
 }
 
 // k_classify_main on `on`, for the step-by-step calls and the fused pass alike; ev (or nullptr): an event pair recorded around it
-static int enqueue_main(svjg_ctx *c, hipStream_t on, const ClassifyArgs &a, uint32_t grid, size_t lds, hipEvent_t *ev) {
+static int enqueue_main(svjg_ctx *c, hipStream_t on, const ClassifyArgs &a, uint32_t grid, size_t lds, Event *ev) {
     if (ev) HIPCHK(c, hipEventRecord(ev[0], on));
     hipLaunchKernelGGL(k_classify_main, dim3(grid), dim3(WG), lds, on, a);
     HIPCHK(c, hipGetLastError());
@@ -650,11 +623,11 @@ static int classify_range(svjg_ctx *c, uint64_t begin, uint64_t end, uint64_t ba
     ListSizes want = lists_first((c->gflags & SVJG_GRAPH_ALL_SLOW) != 0, want_hits != 0, n, c->hs());
     int rc;
     for (int attempt = 0; attempt < 3; ++attempt) {
-        if ((rc = ensure(c, (void **)&c->d_deferred, &c->deferred_cap, want.deferred, sizeof(uint64_t), false))) return rc;
-        if ((rc = ensure(c, (void **)&c->d_host, &c->host_cap, want.host, sizeof(uint64_t), true))) return rc;
-        if (want_hits && (rc = ensure(c, (void **)&c->d_recs, &c->rec_cap, want.recs, sizeof(svjg_hitrec), true))) return rc;
+        if ((rc = ensure(c, c->d_deferred, want.deferred, false))) return rc;
+        if ((rc = ensure(c, c->d_host, want.host, true))) return rc;
+        if (want_hits && (rc = ensure(c, c->d_recs, want.recs, true))) return rc;
         // snapshot so that an overflowed attempt can be rolled back
-        HIPCHK(c, hipMemcpyAsync(c->d_snap, c->d_counts, counts_bytes(c), hipMemcpyDeviceToDevice, c->stream));
+        HIPCHK(c, hipMemcpyAsync(c->graph.snap, c->graph.counts, counts_bytes(c), hipMemcpyDeviceToDevice, c->stream));
         DevStatus before = c->hs();
         if ((rc = reset_status(c, false))) return rc;
         ClassifyArgs a{};
@@ -691,7 +664,7 @@ static int classify_range(svjg_ctx *c, uint64_t begin, uint64_t end, uint64_t ba
         // roll back and retry with worst-case buffers
         if (attempt == 2) { c->err = "output buffers overflowed repeatedly"; return SVJG_E_NOMEM; }
         want = lists_grown(want, n, before, c->hs());
-        HIPCHK(c, hipMemcpyAsync(c->d_counts, c->d_snap, counts_bytes(c), hipMemcpyDeviceToDevice, c->stream));
+        HIPCHK(c, hipMemcpyAsync(c->graph.counts, c->graph.snap, counts_bytes(c), hipMemcpyDeviceToDevice, c->stream));
         uint64_t keep_err = before.err;
         c->hs() = before; c->hs().err = keep_err;
     }
@@ -758,7 +731,7 @@ extern "C" int svjg_classify(svjg_ctx *c, const char *gaf, uint64_t n, uint64_t 
     std::string uerr;
     auto fetch = [&](uint64_t dst, uint64_t src, uint64_t len) -> int {
         if (hipSetDevice(c->device) != hipSuccess) { uerr = "hipSetDevice (upload thread)"; return SVJG_E_HIP; }
-        if (!c->copy_stream && hipStreamCreateWithFlags(&c->copy_stream, hipStreamNonBlocking) != hipSuccess) { uerr = "hipStreamCreate (upload)"; return SVJG_E_HIP; }
+        if (c->copy_stream.create(hipStreamNonBlocking) != hipSuccess) { uerr = "hipStreamCreate (upload)"; return SVJG_E_HIP; }
         if (hipMemcpyAsync(c->d_gaf + dst, gaf + src, len, hipMemcpyHostToDevice, c->copy_stream) != hipSuccess ||
             hipStreamSynchronize(c->copy_stream) != hipSuccess) { uerr = "hipMemcpyAsync (upload)"; return SVJG_E_HIP; }
         return 0;
@@ -834,7 +807,7 @@ extern "C" int svjg_get_counts(svjg_ctx *c, uint32_t *out, uint32_t n_slots) {
     HIPCHK(c, hipSetDevice(c->device));
     { const int rc0 = fetch_slot_counts(c); if (rc0) return rc0; }
     std::vector<unsigned long long> tmp(n_slots);
-    if (n_slots) HIPCHK(c, hipMemcpyAsync(tmp.data(), c->d_counts, (uint64_t)n_slots * 8, hipMemcpyDeviceToHost, c->stream));
+    if (n_slots) HIPCHK(c, hipMemcpyAsync(tmp.data(), c->graph.counts, (uint64_t)n_slots * 8, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
     for (uint32_t i = 0; i < n_slots; ++i) { out[2 * i] = (uint32_t)tmp[i]; out[2 * i + 1] = (uint32_t)(tmp[i] >> 32); }
     return 0;
@@ -846,7 +819,7 @@ extern "C" int svjg_set_counts(svjg_ctx *c, const uint32_t *in, uint32_t n_slots
     HIPCHK(c, hipSetDevice(c->device));
     std::vector<unsigned long long> tmp(n_slots);
     for (uint32_t i = 0; i < n_slots; ++i) tmp[i] = (unsigned long long)in[2 * i] | ((unsigned long long)in[2 * i + 1] << 32);
-    if (n_slots) HIPCHK(c, hipMemcpyAsync(c->d_counts, tmp.data(), (uint64_t)n_slots * 8, hipMemcpyHostToDevice, c->stream));
+    if (n_slots) HIPCHK(c, hipMemcpyAsync(c->graph.counts, tmp.data(), (uint64_t)n_slots * 8, hipMemcpyHostToDevice, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
     return 0;
 }
@@ -855,7 +828,7 @@ extern "C" int svjg_get_host_lines(svjg_ctx *c, uint64_t *out, uint64_t cap, uin
     if (!c || !n) return SVJG_E_ARG;
     HIPCHK(c, hipSetDevice(c->device));
     *n = c->hs().n_host;
-    const uint64_t held = c->host_lines_src ? c->host_lines_cap : c->host_cap;       // (never beyond the list itself)
+    const uint64_t held = c->host_lines_src ? c->host_lines_cap : c->d_host.cap;       // (never beyond the list itself)
     uint64_t have = c->hs().n_host < cap ? c->hs().n_host : cap;
     if (have > held) have = held;
     if (have && !out) return SVJG_E_ARG;
@@ -906,7 +879,7 @@ extern "C" int svjg_comm_set_stream(svjg_ctx *c, int second_stream) {
 // the guard elements behind the count vector (svjg_pass.h) <- largest ref / alt field, and — st given: a fused pass — whether this
 // rank's pass must be repeated (k_counts_guard)
 static int launch_guard(svjg_ctx *c, unsigned long long *counts = nullptr, hipStream_t stream = nullptr, const DevStatus *st = nullptr) {
-    if (!counts) counts = c->d_counts;
+    if (!counts) counts = c->graph.counts;
     if (!stream) stream = c->stream;
     HIPCHK(c, hipSetDevice(c->device));
     HIPCHK(c, hipMemsetAsync(counts + c->n_slots, 0, GUARD_WORDS * 8, stream));
@@ -919,7 +892,7 @@ static int launch_guard(svjg_ctx *c, unsigned long long *counts = nullptr, hipSt
 static int check_guard(svjg_ctx *c) {
     unsigned long long g[GUARD_WORDS] = {0, 0, 0};
     HIPCHK(c, hipSetDevice(c->device));
-    HIPCHK(c, hipMemcpyAsync(g, c->d_counts + c->n_slots, sizeof g, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipMemcpyAsync(g, c->graph.counts + c->n_slots, sizeof g, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
     if (pass_counts_overflowed(g[GUARD_MAX_REF], g[GUARD_MAX_ALT])) { c->err = "more than 2^32 informative alignments for one SV"; return SVJG_E_OVERFLOW; }
     return 0;
@@ -932,7 +905,7 @@ extern "C" int svjg_allreduce_counts(svjg_ctx *c) {
     if (!c->comm) { c->err = "svjg_comm_init has not been called"; return SVJG_E_ARG; }
     int rc = launch_guard(c);
     if (rc) return rc;
-    ncclResult_t r = ncclAllReduce(c->d_counts, c->d_counts, (size_t)c->n_slots + GUARD_WORDS, ncclUint64, ncclSum, c->comm, c->stream);
+    ncclResult_t r = ncclAllReduce(c->graph.counts, c->graph.counts, (size_t)c->n_slots + GUARD_WORDS, ncclUint64, ncclSum, c->comm, c->stream);
     if (r != ncclSuccess) { c->err = std::string("ncclAllReduce: ") + ncclGetErrorString(r); return SVJG_E_RCCL; }
     return check_guard(c);
 }
@@ -984,7 +957,7 @@ extern "C" int svjg_allreduce_counts_all(svjg_ctx *const *ctxs, int n) {
         for (int i = 0; i < n && r == ncclSuccess; ++i) {
             svjg_ctx *c = ctxs[i];
             if (hipSetDevice(c->device) != hipSuccess) { ctxs[0]->err = "hipSetDevice"; ncclGroupEnd(); return SVJG_E_HIP; }
-            r = ncclAllReduce(c->d_counts, c->d_counts, (size_t)c->n_slots + GUARD_WORDS, ncclUint64, ncclSum, c->comm, c->stream);
+            r = ncclAllReduce(c->graph.counts, c->graph.counts, (size_t)c->n_slots + GUARD_WORDS, ncclUint64, ncclSum, c->comm, c->stream);
         }
         const ncclResult_t r2 = ncclGroupEnd();
         if (r == ncclSuccess) r = r2;
@@ -1002,9 +975,9 @@ static int build_logfact(svjg_ctx *c, uint32_t upto) {
     static_assert(LF_BLOCK == LOGFACT_BLOCK, "svjg_kernels.h and svjg_geno.h disagree");
     const uint32_t want = logfact_built(upto);
     { const int rc0 = serial_enter(c); if (rc0) return rc0; }
-    hipFree(c->d_logfact); hipFree(c->d_bsum); c->d_logfact = nullptr; c->d_bsum = nullptr; c->logfact_n = 0;
-    HIPCHK(c, hipMalloc((void **)&c->d_logfact, (uint64_t)want * sizeof(dd)));
-    HIPCHK(c, hipMalloc((void **)&c->d_bsum, (uint64_t)(want / LF_BLOCK) * sizeof(dd)));
+    c->d_logfact.release(); c->d_bsum.release(); c->logfact_n = 0;      // (the callers have waited for whatever used the old table)
+    HIPCHK(c, c->d_logfact.reserve(want));
+    HIPCHK(c, c->d_bsum.reserve(want / LF_BLOCK));
     hipLaunchKernelGGL(k_logfact_local, dim3(want / LF_BLOCK), dim3(LF_BLOCK), 0, c->stream, c->d_logfact, c->d_bsum, want);
     hipLaunchKernelGGL(k_logfact_bsum, dim3(1), dim3(64), 0, c->stream, c->d_bsum, want / LF_BLOCK);
     hipLaunchKernelGGL(k_logfact_add, dim3(want / LF_BLOCK), dim3(LF_BLOCK), 0, c->stream, c->d_logfact, c->d_bsum, want);
@@ -1070,9 +1043,9 @@ static int settle_launch(svjg_ctx *c, const unsigned int *h_maxn, void *h_back, 
 template <class Fill, class Launch>
 static int genotype_leg(svjg_ctx *c, LegBlock &b, const LegSpan &S, Fill fill, Launch launch) {
     int rc;
-    if ((rc = ensure(c, &b.d, &b.d_cap, S.total, 1, false))) return rc;
-    if ((rc = ensure_pinned(c, &b.h, &b.h_cap, S.total, hipHostMallocDefault))) return rc;
-    uint8_t *base = (uint8_t *)b.d, *hb = (uint8_t *)b.h;
+    if ((rc = ensure(c, b.d, S.total, false))) return rc;
+    HIPCHK(c, b.h.reserve(S.total, hipHostMallocDefault));
+    uint8_t *base = b.d, *hb = b.h;
     fill(hb);
     HIPCHK(c, hipMemcpyAsync(base + S.in_at, hb + S.in_at, S.in_bytes, hipMemcpyHostToDevice, c->stream));
     HIPCHK(c, hipEventRecord(c->ev[4], c->stream));
@@ -1097,7 +1070,7 @@ static int genotype_rows(svjg_ctx *c, const uint8_t *sv_type, const uint32_t *sl
     const RowsLayout L = rows_layout(n_rows);
     return genotype_leg(c, c->leg[BLOCK_ROWS], L,
         [&](uint8_t *hb) { stage_rows(hb, L.in, sv_type, slot, ok, n_rows); c->geno_rows = n_rows; },   // (from here on the block is this call's)
-        [&](uint8_t *base) { GenoArgs a = block_geno_args(c, c->d_counts, base, L, n_rows, min_support, err); return launch_genotype(c, a); });
+        [&](uint8_t *base) { GenoArgs a = block_geno_args(c, c->graph.counts, base, L, n_rows, min_support, err); return launch_genotype(c, a); });
 }
 
 // The results where the device's copy left them: the four pointers look into the context's pinned host block and stay
@@ -1111,7 +1084,7 @@ extern "C" int svjg_genotype_view(svjg_ctx *c, const uint8_t *sv_type, const uin
     if (!sv_type || !slot || !ok) return SVJG_E_ARG;
     const int rc = genotype_rows(c, sv_type, slot, ok, n_rows, min_support, err);
     if (rc) return rc;
-    const uint8_t *hb = (const uint8_t *)c->leg[BLOCK_ROWS].h;
+    const uint8_t *hb = c->leg[BLOCK_ROWS].h;
     const RowsLayout L = rows_layout(n_rows);
     *pl = (const int64_t *)(hb + L.pl); *raw = (const uint32_t *)(hb + L.raw); *gt = hb + L.gt; *genotyped = hb + L.flags;
     return 0;
@@ -1153,11 +1126,11 @@ extern "C" int svjg_genotype_ploidy(svjg_ctx *c, const uint8_t *sv_type, const u
     const int rc = genotype_leg(c, c->leg[BLOCK_PLOIDY], L,
         [&](uint8_t *hb) { ploidy_log_table(err, (double *)(hb + L.logtab)); stage_rows(hb, L.in, sv_type, slot, ok, n_rows); memcpy(hb + L.ploidy, ploidy, n_rows); },   // (the logarithms by the host's libm, as geno_args' three)
         [&](uint8_t *base) {
-            GenoPloidyArgs p{block_geno_args(c, c->d_counts, base, L, n_rows, min_support, err), base + L.ploidy, (const double *)(base + L.logtab)};
+            GenoPloidyArgs p{block_geno_args(c, c->graph.counts, base, L, n_rows, min_support, err), base + L.ploidy, (const double *)(base + L.logtab)};
             return launch_ploidy(c, p);
         });
     if (rc) return rc;
-    const uint8_t *hb = (const uint8_t *)c->leg[BLOCK_PLOIDY].h;
+    const uint8_t *hb = c->leg[BLOCK_PLOIDY].h;
     memcpy(pl, hb + L.pl, n_rows * (MAX_PLOIDY + 1) * sizeof *pl); memcpy(raw, hb + L.raw, n_rows * 2 * sizeof *raw);
     memcpy(gt, hb + L.gt, n_rows); memcpy(genotyped, hb + L.flags, n_rows); memcpy(boundary, hb + L.boundary, n_rows);
     return 0;
@@ -1198,14 +1171,14 @@ extern "C" int svjg_genotype_sites(svjg_ctx *c, const uint32_t *slots, uint64_t 
         [&](uint8_t *hb) { site_log_table(err, (double *)(hb + L.logs)); memcpy(hb + L.slots, slots, n_sites * MAX_SITE_ALTS * 4); },   // (host libm, as geno_args' three)
         [&](uint8_t *base) {
             GenoSitesArgs a{};
-            a.counts = c->d_counts; a.n_slots = c->n_slots; a.slots = (const uint32_t *)(base + L.slots); a.n_sites = n_sites; a.min_support = min_support;
+            a.counts = c->graph.counts; a.n_slots = c->n_slots; a.slots = (const uint32_t *)(base + L.slots); a.n_sites = n_sites; a.min_support = min_support;
             a.logs = (const double *)(base + L.logs);
             a.pl = (int64_t *)(base + L.pl); a.raw = (uint32_t *)(base + L.raw); a.gt = base + L.gt; a.boundary = base + L.boundary;
             a.max_n = (unsigned int *)(base + L.maxn);
             return launch_sites(c, a);
         });
     if (rc) return rc;
-    const uint8_t *hb = (const uint8_t *)c->leg[BLOCK_SITES].h;
+    const uint8_t *hb = c->leg[BLOCK_SITES].h;
     memcpy(pl, hb + L.pl, n_sites * SITE_GENOTYPES * sizeof *pl); memcpy(raw, hb + L.raw, n_sites * (MAX_SITE_ALTS + 1) * sizeof *raw);
     memcpy(gt, hb + L.gt, n_sites * 2); memcpy(boundary, hb + L.boundary, n_sites);
     return 0;
@@ -1219,18 +1192,17 @@ extern "C" int svjg_cohort_alloc(svjg_ctx *c, uint32_t n_samples, uint32_t n_slo
     if (n_samples == 0) { c->err = "a cohort has at least one sample"; return SVJG_E_ARG; }
     HIPCHK(c, hipSetDevice(c->device));
     HIPCHK(c, hipStreamSynchronize(c->stream));
-    hipFree(c->d_cm); c->d_cm = nullptr; c->d_cpresent = nullptr; c->cohort_samples = c->cohort_slots = 0;
+    c->d_cm.release(); c->d_cpresent = nullptr; c->cohort_samples = c->cohort_slots = 0;
     const uint64_t n = (uint64_t)n_samples * n_slots;             // (< 2^64; times nine it is below 2^68: checked)
-    void *q = nullptr;
-    if (n > (1ull << 60) || hipMalloc(&q, n * 9 + 8) != hipSuccess) { (void)hipGetLastError(); c->err = "no memory for the cohort matrix"; return SVJG_E_NOMEM; }
-    c->d_cm = (unsigned long long *)q; c->d_cpresent = (uint8_t *)q + n * 8;
+    if (n > (1ull << 60) || c->d_cm.reserve(n * 9 + 8) != hipSuccess) { (void)hipGetLastError(); c->err = "no memory for the cohort matrix"; return SVJG_E_NOMEM; }
+    c->d_cpresent = c->d_cm + n * 8;
     c->cohort_samples = n_samples; c->cohort_slots = n_slots;
-    HIPCHK(c, hipMemsetAsync(q, 0, n * 9 + 8, c->stream));
+    HIPCHK(c, hipMemsetAsync(c->d_cm, 0, n * 9 + 8, c->stream));
     return 0;
 }
 
 // the staging vector of one column: [ counts 8 | present 1 ] x n_slots
-static int cohort_stage(svjg_ctx *c) { return ensure(c, &c->d_cstage, &c->cstage_cap, (uint64_t)c->cohort_slots * 9 + 16, 1, false); }
+static int cohort_stage(svjg_ctx *c) { return ensure(c, c->d_cstage, (uint64_t)c->cohort_slots * 9 + 16, false); }
 
 extern "C" int svjg_cohort_set_counts(svjg_ctx *c, uint32_t sample, const uint32_t *slots, const uint32_t *counts, uint64_t n) {
     if (!c) return SVJG_E_ARG;
@@ -1250,10 +1222,10 @@ extern "C" int svjg_cohort_set_counts(svjg_ctx *c, uint32_t sample, const uint32
     HIPCHK(c, hipSetDevice(c->device));
     if (ns == 0) return 0;
     if (const int rc = cohort_stage(c)) return rc;
-    unsigned long long *d_col = (unsigned long long *)c->d_cstage; uint8_t *d_pres = (uint8_t *)c->d_cstage + (uint64_t)ns * 8;
+    unsigned long long *d_col = (unsigned long long *)c->d_cstage.p; uint8_t *d_pres = c->d_cstage + (uint64_t)ns * 8;
     HIPCHK(c, hipMemcpyAsync(d_col, col.data(), (uint64_t)ns * 8, hipMemcpyHostToDevice, c->stream));
     HIPCHK(c, hipMemcpyAsync(d_pres, pres.data(), ns, hipMemcpyHostToDevice, c->stream));
-    hipLaunchKernelGGL(k_cohort_store, dim3(capped_grid(ns)), dim3(TPB), 0, c->stream, c->d_cm, c->d_cpresent, c->cohort_samples, sample, d_col, d_pres, ns);
+    hipLaunchKernelGGL(k_cohort_store, dim3(capped_grid(ns)), dim3(TPB), 0, c->stream, c->cm(), c->d_cpresent, c->cohort_samples, sample, d_col, d_pres, ns);
     HIPCHK(c, hipGetLastError());
     HIPCHK(c, hipStreamSynchronize(c->stream));                   // `col` and `pres` are locals
     return 0;
@@ -1267,8 +1239,8 @@ extern "C" int svjg_cohort_store_counts(svjg_ctx *c, uint32_t sample) {
     HIPCHK(c, hipSetDevice(c->device));
     { const int rc0 = fetch_slot_counts(c); if (rc0) return rc0; }
     if (c->n_slots == 0) return 0;
-    hipLaunchKernelGGL(k_cohort_store, dim3(capped_grid(c->n_slots)), dim3(TPB), 0, c->stream, c->d_cm, c->d_cpresent, c->cohort_samples, sample,
-                       (const unsigned long long *)c->d_counts, (const uint8_t *)nullptr, c->n_slots);
+    hipLaunchKernelGGL(k_cohort_store, dim3(capped_grid(c->n_slots)), dim3(TPB), 0, c->stream, c->cm(), c->d_cpresent, c->cohort_samples, sample,
+                       (const unsigned long long *)c->graph.counts, (const uint8_t *)nullptr, c->n_slots);
     HIPCHK(c, hipGetLastError());
     return 0;
 }
@@ -1281,8 +1253,8 @@ extern "C" int svjg_cohort_get_counts(svjg_ctx *c, uint32_t sample, uint32_t *ou
     HIPCHK(c, hipSetDevice(c->device));
     if (n_slots == 0) return 0;
     if (const int rc = cohort_stage(c)) return rc;
-    unsigned long long *d_col = (unsigned long long *)c->d_cstage; uint8_t *d_pres = (uint8_t *)c->d_cstage + (uint64_t)n_slots * 8;
-    hipLaunchKernelGGL(k_cohort_load, dim3(capped_grid(n_slots)), dim3(TPB), 0, c->stream, (const unsigned long long *)c->d_cm, (const uint8_t *)c->d_cpresent,
+    unsigned long long *d_col = (unsigned long long *)c->d_cstage.p; uint8_t *d_pres = c->d_cstage + (uint64_t)n_slots * 8;
+    hipLaunchKernelGGL(k_cohort_load, dim3(capped_grid(n_slots)), dim3(TPB), 0, c->stream, (const unsigned long long *)c->cm(), (const uint8_t *)c->d_cpresent,
                        c->cohort_samples, sample, d_col, d_pres, n_slots);
     HIPCHK(c, hipGetLastError());
     std::vector<unsigned long long> tmp(n_slots);
@@ -1357,7 +1329,7 @@ static int cohort_call(svjg_ctx *c, int block, const uint8_t *sv_type, const uin
             if (ploidy) memcpy(hb + L.ploidy, ploidy, n);
         },
         [&](uint8_t *base) {
-            GenoCohortArgs g{block_geno_args(c, c->d_cm, base, L, n_rows, min_support, err), c->d_cpresent, c->cohort_samples, (unsigned long long *)(base + L.site),
+            GenoCohortArgs g{block_geno_args(c, c->cm(), base, L, n_rows, min_support, err), c->d_cpresent, c->cohort_samples, (unsigned long long *)(base + L.site),
                              base + L.ploidy, (const double *)(base + L.logtab), max_ploidy};
             g.g.n_slots = c->cohort_slots;                        // (the matrix's slots, not the count vector's)
             if (const int rc1 = launch_cohort(c, g, per_item)) return rc1;
@@ -1368,7 +1340,7 @@ static int cohort_call(svjg_ctx *c, int block, const uint8_t *sv_type, const uin
             return launch_cohort_prior(c, p);
         });
     if (rc) return rc;
-    const uint8_t *hb = (const uint8_t *)c->leg[block].h;
+    const uint8_t *hb = c->leg[block].h;
     memcpy(pl, hb + L.pl, n * (max_ploidy + 1) * sizeof *pl); memcpy(raw, hb + L.raw, n * 2 * sizeof *raw);
     memcpy(gt, hb + L.gt, n); memcpy(genotyped, hb + L.flags, n); memcpy(boundary, hb + L.boundary, n);
     if (prior) {
@@ -1427,24 +1399,24 @@ extern "C" int svjg_set_rows(svjg_ctx *c, const uint8_t *sv_type, const uint32_t
     const RunLayout L = run_layout(n_rows);
     const RowsIn I = rows_in(n_rows);
     int rc;
-    if ((rc = ensure(c, &c->d_run_in, &c->d_run_in_cap, I.bytes + 64, 1, false))) return rc;
+    if ((rc = ensure(c, c->d_run_in, I.bytes + 64, false))) return rc;
     for (int k = 0; k < RUN_SLOTS; ++k) {
         svjg_ctx::RunSlot &r = c->run[k];
         r.clean = false;                                      // (the blocks may move)
-        if ((rc = ensure(c, &r.d, &r.d_cap, L.total, 1, false))) return rc;
-        if ((rc = ensure_pinned(c, &r.h, &r.h_cap, L.out_bytes, hipHostMallocMapped))) return rc;
+        if ((rc = ensure(c, r.d, L.total, false))) return rc;
+        HIPCHK(c, r.h.reserve(L.out_bytes, hipHostMallocMapped));
         HIPCHK(c, hipHostGetDevicePointer(&r.h_dev, r.h, 0));
-        if ((rc = ensure(c, (void **)&r.counts, &r.counts_cap, (uint64_t)c->n_slots + GUARD_WORDS, sizeof(unsigned long long), false))) return rc;
-        for (auto &e : r.ev) if (!e) HIPCHK(c, hipEventCreate(&e));
-        if (!r.computed) HIPCHK(c, hipEventCreate(&r.computed));          // (with a time stamp: under SVJG_KERNEL_MS=events it also ends the exact-path kernel's interval)
-        if (!r.copied) HIPCHK(c, hipEventCreateWithFlags(&r.copied, hipEventDisableTiming));
+        if ((rc = ensure(c, r.counts, (uint64_t)c->n_slots + GUARD_WORDS, false))) return rc;
+        for (auto &e : r.ev) HIPCHK(c, e.create());
+        HIPCHK(c, r.computed.create());                               // (with a time stamp: under SVJG_KERNEL_MS=events it also ends the exact-path kernel's interval)
+        HIPCHK(c, r.copied.create(hipEventDisableTiming));
     }
     if (!c->copy_stream) {                                    // (the lowest priority there is: what runs on it must not take issue slots from the classify kernel)
         int least = 0, greatest = 0;
         if (hipDeviceGetStreamPriorityRange(&least, &greatest) != hipSuccess) least = 0;
-        HIPCHK(c, hipStreamCreateWithPriority(&c->copy_stream, hipStreamNonBlocking, least));
+        HIPCHK(c, c->copy_stream.create(hipStreamNonBlocking, least));
     }
-    uint8_t *in = (uint8_t *)c->d_run_in;
+    uint8_t *in = c->d_run_in;
     if (n_rows) {
         HIPCHK(c, hipMemcpyAsync(in + I.slot, slot, n_rows * 4, hipMemcpyHostToDevice, c->stream));
         HIPCHK(c, hipMemcpyAsync(in + I.type, sv_type, n_rows, hipMemcpyHostToDevice, c->stream));
@@ -1456,8 +1428,8 @@ extern "C" int svjg_set_rows(svjg_ctx *c, const uint8_t *sv_type, const uint32_t
 }
 
 static GenoArgs run_geno_args(svjg_ctx *c, const svjg_ctx::RunSlot &r, const RunLayout &L, uint32_t min_support, double err, const unsigned long long *counts) {
-    uint8_t *base = (uint8_t *)r.d, *hostb = (uint8_t *)r.h_dev;
-    GenoArgs a = geno_args(c, counts, (const uint8_t *)c->d_run_in, rows_in(c->run_rows), c->run_rows, min_support, err);
+    uint8_t *base = r.d, *hostb = (uint8_t *)r.h_dev;
+    GenoArgs a = geno_args(c, counts, c->d_run_in, rows_in(c->run_rows), c->run_rows, min_support, err);
     a.gt = hostb + L.gt; a.pl = (int64_t *)(base + L.pl64); a.raw = (uint32_t *)(hostb + L.raw); a.genotyped = hostb + L.flags;
     a.pl32 = (int32_t *)(hostb + L.pl32); a.boundary = hostb + L.boundary; a.max_n = (unsigned int *)(base + L.maxn);
     return a;
@@ -1473,8 +1445,8 @@ static NextPass slot_reset_args(const svjg_ctx::RunSlot &s, const RunLayout &L, 
 // the slot's own lists (no pass in flight uses this slot: the host has ended the pass that last did)
 static int pass_lists(svjg_ctx *c, svjg_ctx::RunSlot &r, uint64_t n) {
     const ListSizes want = lists_fused((c->gflags & SVJG_GRAPH_ALL_SLOW) != 0, n);
-    if (const int rc = ensure(c, (void **)&r.deferred, &r.deferred_cap, want.deferred, sizeof(uint64_t), false)) return rc;
-    return ensure(c, (void **)&r.host, &r.host_cap, want.host, sizeof(uint64_t), false);
+    if (const int rc = ensure(c, r.deferred, want.deferred, false)) return rc;
+    return ensure(c, r.host, want.host, false);
 }
 
 // The pass's form and compute stream (svjg_pass.h).  Overlapped: pass k on stream k mod 2 — k_step_reset of its OWN slot in one-wave blocks
@@ -1555,7 +1527,7 @@ static int pass_main(svjg_ctx *c, svjg_ctx::RunSlot &r, const RunLayout &L, uint
 // on the other stream — move into the slots this one's vacate; 53 760 B of LDS a block would only be there when THAT pass drains.
 static int pass_exact_and_next(svjg_ctx *c, const svjg_ctx::RunSlot &r, const RunLayout &L, uint64_t words) {
     svjg_ctx::RunSlot &nxt = c->run[(c->run_head + 1) % RUN_SLOTS];
-    const NextPass nx = (nxt.d && nxt.counts && nxt.counts_cap >= words) ? slot_reset_args(nxt, L, words) : NextPass{};
+    const NextPass nx = (nxt.d && nxt.counts && nxt.counts.cap >= words) ? slot_reset_args(nxt, L, words) : NextPass{};
     if (const int rc = launch_exact(c, r.cargs, FUSED_WAVE_ROUNDS, nx)) return rc;
     nxt.clean = nx.counts != nullptr;
     return 0;
@@ -1606,7 +1578,7 @@ static int pass_genotypes(svjg_ctx *c, svjg_ctx::RunSlot &r, const GenoArgs &ga,
 // hipMemcpyAsync here is the runtime's copy kernel, whose 256-thread blocks wait for the next pass's classify kernel to drain); then `copied`
 static int pass_tail(svjg_ctx *c, svjg_ctx::RunSlot &r, const RunLayout &L) {
     static_assert(sizeof(DevStatus) % 8 == 0, "the tail is copied in 8-byte words");
-    hipLaunchKernelGGL(k_pass_tail, dim3(1), dim3(64), 0, c->copy_stream, (unsigned long long *)((uint8_t *)r.h_dev + L.h_tail), (const unsigned long long *)r.d, (uint32_t)(L.tail_bytes / 8));
+    hipLaunchKernelGGL(k_pass_tail, dim3(1), dim3(64), 0, c->copy_stream, (unsigned long long *)((uint8_t *)r.h_dev + L.h_tail), (const unsigned long long *)r.d.p, (uint32_t)(L.tail_bytes / 8));
     HIPCHK(c, hipGetLastError());
     HIPCHK(c, hipEventRecord(r.copied, c->copy_stream));
     return 0;
@@ -1627,7 +1599,7 @@ extern "C" int svjg_run_begin(svjg_ctx *c, uint64_t base_offset, uint32_t min_su
     if ((rc = pass_form_and_stream(c, r))) return rc;
     r.base_offset = base_offset; r.min_support = min_support; r.err = err;
     r.had_text = n != 0; r.timed_by_events = kernel_ms_by_events(c); r.slow_end_own = false;
-    if (r.counts_cap < words) { c->err = "svjg_set_rows must follow svjg_load_graph"; return SVJG_E_ARG; }
+    if (r.counts.cap < words) { c->err = "svjg_set_rows must follow svjg_load_graph"; return SVJG_E_ARG; }
     pass_reset(r, L, words);
     if (n && (rc = pass_main(c, r, L, n))) return rc;
     if (n && !r.overlapped && (rc = pass_exact_and_next(c, r, L, words))) return rc;
@@ -1696,7 +1668,7 @@ static int pass_times(svjg_ctx *c, svjg_ctx::RunSlot &r) {
 }
 
 // What the host would have decided in between: repeat the pass, let it stand, or refuse it.  `gd`: the pass's guard words (meaningful under
-// a communicator: the sums over the ranks).  repeated: the pass was repeated step by step, its counts are in d_counts.
+// a communicator: the sums over the ranks).  repeated: the pass was repeated step by step, its counts are in graph.counts.
 static int pass_verdict(svjg_ctx *c, const svjg_ctx::RunSlot &r, const unsigned long long *gd, uint64_t n, bool &repeated) {
     repeated = false;
     if (pass_repeats(c->comm != nullptr, c->hs().overflow, gd[GUARD_REPEAT])) {
@@ -1741,11 +1713,11 @@ extern "C" int svjg_run_end(svjg_ctx *c, const uint8_t **gt, const int32_t **pl,
     if ((rc = pass_times(c, r))) return rc;
     if (n_rows) HIPCHK(c, hipEventElapsedTime(&c->ms_geno, r.ev[4], r.ev[5]));
     c->last_pass_deferred = r.had_text && c->hs().n_deferred != 0;
-    c->host_lines_src = r.host; c->host_lines_cap = r.host_cap;
+    c->host_lines_src = r.host; c->host_lines_cap = r.host.cap;
     bool repeated = false;
     if ((rc = pass_verdict(c, r, (const unsigned long long *)(tail + L.guard), n, repeated))) return rc;
     if (n_rows) {                                                 // the genotypes once more where they are owed: a repeated pass, a settle step, a log10(i!) table too short
-        GenoArgs ga = run_geno_args(c, r, L, r.min_support, r.err, repeated ? c->d_counts : r.counts);
+        GenoArgs ga = run_geno_args(c, r, L, r.min_support, r.err, repeated ? c->graph.counts : r.counts);
         uint8_t *h_maxn = hb + L.h_tail + L.maxn;                 // (the results are already in the mapped host block: only the pair comes back)
         if ((rc = settle_launch(c, (const unsigned int *)h_maxn, h_maxn, (const uint8_t *)r.d + L.maxn, 8, repeated || r.geno_owed, [&] { return launch_genotype(c, ga); }))) return rc;
     }
@@ -1766,9 +1738,9 @@ extern "C" int svjg_run_resident(svjg_ctx *c, uint64_t base_offset, uint32_t min
 // which rows of the last svjg_genotype / svjg_genotype_view call lie so close to a PL's integer boundary that the caller should
 // recompute them with the reference's own arithmetic (predict-genotype.py:313: log10 of an exact big integer)
 extern "C" int svjg_genotype_boundary(svjg_ctx *c, uint8_t *out, uint64_t n_rows) {
-    const void *hb = c ? c->leg[BLOCK_ROWS].h : nullptr;
+    const uint8_t *hb = c ? c->leg[BLOCK_ROWS].h.p : nullptr;
     if (!hb || (n_rows && !out) || n_rows != c->geno_rows) return SVJG_E_ARG;
-    memcpy(out, (const uint8_t *)hb + rows_layout(n_rows).boundary, n_rows);
+    memcpy(out, hb + rows_layout(n_rows).boundary, n_rows);
     return 0;
 }
 
@@ -1819,9 +1791,8 @@ extern "C" int svjg_copy_rate(svjg_ctx *c, uint64_t n_bytes, double *copy_gb_per
     if (!c || n_bytes < (1u << 20)) return SVJG_E_ARG;
     HIPCHK(c, hipSetDevice(c->device));
     n_bytes &= ~4095ull;
-    uint4 *src = nullptr, *dst = nullptr;
-    if (hipMalloc((void **)&src, n_bytes) != hipSuccess || hipMalloc((void **)&dst, n_bytes) != hipSuccess) { hipFree(src); c->err = "svjg_copy_rate: no memory for the two buffers"; return SVJG_E_NOMEM; }
-    struct Free { uint4 *a, *b; ~Free() { hipFree(a); hipFree(b); } } fr{src, dst};
+    DevBuf<uint4> src, dst;
+    if (src.reserve(n_bytes / 16) != hipSuccess || dst.reserve(n_bytes / 16) != hipSuccess) { c->err = "svjg_copy_rate: no memory for the two buffers"; return SVJG_E_NOMEM; }
     HIPCHK(c, hipMemsetAsync(src, 0x5A, n_bytes, c->stream));
     HIPCHK(c, hipMemsetAsync(dst, 0, n_bytes, c->stream));
     const uint32_t grid = (uint32_t)c->n_cu * 16;
