@@ -356,6 +356,30 @@ int svjg_genotype_cohort_prior(svjg_ctx *ctx, const uint8_t *sv_type, const uint
                                uint8_t *genotyped, uint8_t *boundary, uint32_t *site /* [n_rows][3] = NS, AN, AC */,
                                uint8_t *gq, double *af, uint32_t *em_steps);
 
+/* svjg_genotype_cohort_sites: svjg_genotype_sites for every sample of the cohort matrix in one launch (--cohort --joint-ins; diploid).  slots holds
+ * SVJG_MAX_SITE_ALTS CANDIDATE slots of the matrix per site (the rows of the merged catalogue at one CHROM and POS), the candidates first, 0xFFFFFFFF
+ * behind them, checked as svjg_genotype_sites checks its members (2..6, no hole, each below the matrix's n_slots, none twice).  An item is (site k,
+ * sample s): sample s's site consists of the candidates whose presence byte is set for s, in candidate order, numbered 1..K' — the members
+ * svjg_genotype_sites would be given in a single-sample run of s — with c_0 = the largest raw ref count over THOSE members.  Outputs,
+ * [n_sites][n_samples] row-major: gt[2], pl[SVJG_SITE_GENOTYPES], raw[7] and boundary exactly what svjg_genotype_sites returns for the item's members
+ * (recompute flagged items with svjedi-graph_amd/svjg/genotype.py: exact_pl_site on the item's own K' alt counts); members = a byte whose bit j says
+ * that candidate j took part.  An item with K' < 2 has no site call: gt = 0xFF, 0xFF, zero PLs, raw = 0, boundary = 0, and members still names the
+ * candidate that was present, if any.  site[k*12 + j*2..] = NS_j, AC_j of candidate j of site k: the items with a site call of which j is a member, and
+ * the copies of j's allele in those calls, summed in integers in the same launch (three wave ballots a candidate, one 64-bit atomic per candidate,
+ * site and wave), so they are equal from run to run.  The call reads the cohort matrix and not the count vector, and works in a block of its own: it
+ * neither reads nor changes the other calls' blocks, what svjg_genotype_view and svjg_genotype_boundary hand out, or the count vector.  The caller
+ * bounds memory by calling with site chunks (256 bytes per item, 72 per site, on the device and on the host).  n_sites = 0 returns 0.  SVJG_E_ARG with
+ * a message in svjg_last_error, all found before any launch: no matrix, a null array, a malformed site, n_sites x n_samples beyond 2^40.
+ * svjg_last_kernel_ms reports the kernel as genotype_ms.
+ * Measured once, with the change that added it (one MI355X, 2026-10-20, ROCm 7.2.0, tools/cohort_sites_timing.py: 10 000 sites x 64 samples, K mixed
+ * 2..6, presence 0.9, counts 0..60, e = 5e-5, median of 30 calls behind 5, the legs alternated twice in one process): 0.129 / 0.129 ms for the one
+ * launch, against 1.910 / 1.919 ms of kernels summed and 20.0 / 20.7 ms of wall time for the loop 64 x (svjg_set_counts + svjg_genotype_sites) on the
+ * same columns; one call from Python took 18.6 / 18.6 ms (164 MB to the host).  Nothing else about this kernel has been measured. */
+int svjg_genotype_cohort_sites(svjg_ctx *ctx, const uint32_t *slots /* [n_sites][SVJG_MAX_SITE_ALTS] */, uint64_t n_sites, uint32_t min_support, double err,
+                               uint8_t *gt /* [n_sites][n_samples][2] */, int64_t *pl /* [n_sites][n_samples][SVJG_SITE_GENOTYPES] */,
+                               uint32_t *raw /* [n_sites][n_samples][7] */, uint8_t *members, uint8_t *boundary,
+                               uint32_t *site /* [n_sites][SVJG_MAX_SITE_ALTS][2] = NS_j, AC_j */);
+
 /* ---- the whole pass in one call (what a fused svjedi-graph run and bench.py do per batch) -----------------------------------
  * svjg_set_rows copies the three per-row input arrays of svjg_genotype to the device once (they stay until the next
  * svjg_set_rows / svjg_destroy).  svjg_run_resident then does, for the resident text of svjg_gaf_upload and those rows:

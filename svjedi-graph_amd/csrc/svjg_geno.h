@@ -399,6 +399,47 @@ SVJG_HD CohortSums cohort_diploid_sums(uint64_t called, uint64_t het, uint64_t h
 // the row's two site words: NS | AC << 32 (k_genotype_cohort's word) and AN.  (AC, AN <= 8 S: they fit 32 bits for S < 2^28)
 SVJG_HD uint64_t cohort_site_word(const CohortSums &s) { return (uint64_t)s.ns | ((uint64_t)s.ac << 32); }
 
+// ---- many samples, insertions that share a position (k_genotype_cohort_sites; diploid) ----
+// An item is (site k, sample s), i = k * S + s, walked like k_genotype_cohort's: the samples of one site are consecutive lanes, cohort_segment gives
+// the site's lanes.  A site has up to MAX_SITE_ALTS CANDIDATES (the rows of the merged catalogue at one CHROM and POS); sample s's site consists of
+// the candidates whose presence byte is set for s, in candidate order, numbered 1..K' — what form_sites makes of that sample's `done` bytes in a
+// single-sample run.  K' < 2: the item has no site call.
+
+// The present candidates (bit j of `bits`: candidate j is present, cref[j] / calt[j] its raw counts) compacted into alt[0..K): the reference count is
+// the largest raw ref count over the PRESENT candidates only.  Both loops are unrolled and every array is indexed by constants only (the k-th place
+// is chosen by selects), so that the kernel keeps cref, calt and alt in registers.  alt beyond K: 0.
+struct SiteMembers { uint32_t K, ref, alt[MAX_SITE_ALTS]; };
+SVJG_HD void site_compact(uint32_t bits, const uint32_t *cref, const uint32_t *calt, SiteMembers &m) {
+    m.K = 0; m.ref = 0;
+    SVJG_UNROLL
+    for (uint32_t t = 0; t < MAX_SITE_ALTS; ++t) m.alt[t] = 0;
+    SVJG_UNROLL
+    for (uint32_t j = 0; j < MAX_SITE_ALTS; ++j) {
+        const bool in = (bits >> j) & 1u;
+        SVJG_UNROLL
+        for (uint32_t t = 0; t <= j; ++t) m.alt[t] = in && t == m.K ? calt[j] : m.alt[t];      // (K <= j here: the place is one of 0..j)
+        m.ref = in && cref[j] > m.ref ? cref[j] : m.ref;
+        m.K += in;
+    }
+}
+
+// Copies of candidate j's allele in an item's call (a, b), 0..2; SITE_NO_CALL: the item has no site call (a == SITE_NO_CALL: K' < 2, a tie, below
+// min_support, or a lane beyond the last item) or candidate j is no member.  The candidate's allele number is 1 + the members in front of it.
+SVJG_HD uint32_t site_candidate_copies(uint32_t members, uint32_t a, uint32_t b, uint32_t j) {
+    if (a == SITE_NO_CALL || !((members >> j) & 1u)) return SITE_NO_CALL;
+    const uint32_t al = 1u + (uint32_t)__builtin_popcount(members & ((1u << j) - 1u));
+    return (uint32_t)(a == al) + (uint32_t)(b == al);
+}
+
+// Per candidate j three ballots of the wave: in = the lane's copies are not SITE_NO_CALL, one / two = they are 1 / 2.  The sums of a segment for
+// candidate j: NS_j = the site-called items where j is a member, AC_j = the copies of its allele in those calls; the word the segment's first lane
+// adds to site[k][j] is NS_j | AC_j << 32 (cohort_site_word).
+struct SiteBallots { uint64_t in[MAX_SITE_ALTS], one[MAX_SITE_ALTS], two[MAX_SITE_ALTS]; };
+SVJG_HD CohortSums cohort_site_member_sums(const SiteBallots &b, uint32_t j, uint64_t mask) {
+    const uint32_t ns = (uint32_t)__builtin_popcountll(b.in[j] & mask);
+    return CohortSums{ns, 2 * ns, (uint32_t)__builtin_popcountll(b.one[j] & mask) + 2 * (uint32_t)__builtin_popcountll(b.two[j] & mask)};
+}
+
 // ---- cohort with an allele-frequency prior (k_cohort_prior) ----
 // The row's alt-allele frequency f is estimated from all its samples' likelihoods by EM under Hardy-Weinberg, each item is then called at
 // the maximum of likelihood x prior.  An item (r, s) takes part iff the cohort call genotyped it and c1 + c2 > 0.  Its weights: l_g = geno_lik,
@@ -568,7 +609,7 @@ constexpr uint32_t logfact_reserve_to(uint32_t have, uint32_t entries) { return 
 struct RowsIn { uint64_t slot, type, ok, bytes; };
 inline RowsIn rows_in(uint64_t n, uint64_t at = 0) { return RowsIn{at, at + n * 4, at + n * 5, n * 6}; }
 
-// The six step-by-step calls (svjg_genotype / _view, _ploidy, _sites, _cohort, _cohort_ploidy, _cohort_prior) each own one device block and its pinned host twin, all of ONE
+// The seven step-by-step calls (svjg_genotype / _view, _ploidy, _sites, _cohort, _cohort_ploidy, _cohort_prior, _cohort_sites) each own one device block and its pinned host twin, all of ONE
 // shape: the outputs (they end at out_end), the max_n pair 8-aligned, ONE contiguous input region right behind the pair, 64 spare bytes -> ONE copy
 // in (in_bytes from in_at), ONE copy out (maxn + 8 bytes from 0).  A layout below IS a LegSpan and adds only what is its own: its outputs and where its inputs lie.
 struct LegSpan { uint64_t maxn, in_at, in_bytes, total; };
@@ -633,6 +674,20 @@ using CohortPloidyLayout = CohortLayout;
 using CohortPriorLayout = CohortLayout;
 inline CohortLayout cohort_ploidy_layout(uint64_t n_rows, uint64_t S, uint32_t max_ploidy) { return cohort_layout(n_rows, S, max_ploidy, true, false); }
 inline CohortLayout cohort_prior_layout(uint64_t n_rows, uint64_t S, uint32_t max_ploidy, bool per_item) { return cohort_layout(n_rows, S, max_ploidy, per_item, true); }
+
+// svjg_genotype_cohort_sites: [ pl 224 | raw 28 | gt 2 | members 1 | boundary 1 ] x (n_sites * S items, site-major: 256 bytes an item), then the
+// site words, 8-aligned, as the LAST output: MAX_SITE_ALTS words a site, NS_j | AC_j << 32.  The max_n pair lies right behind them, and ONE memset
+// zeroes both in front of every launch (as cohort_layout).  in: the call's logarithms (site_log_table) and the sites' candidate slots.
+struct CohortSitesLayout : LegSpan { uint64_t pl, raw, gt, members, boundary, site, logs, slots; };
+inline CohortSitesLayout cohort_sites_layout(uint64_t n_sites, uint64_t S) {
+    CohortSitesLayout L; uint64_t o = 0; const uint64_t n = n_sites * S;
+    L.pl = o; o += n * 8 * SITE_GENOTYPES; L.raw = o; o += n * 4 * (MAX_SITE_ALTS + 1); L.gt = o; o += n * 2; L.members = o; o += n; L.boundary = o; o += n;
+    o = (o + 7) & ~7ull;
+    L.site = o; o += n_sites * 8 * MAX_SITE_ALTS;
+    leg_span(L, o, SITE_LOGS * 8 + n_sites * 4 * MAX_SITE_ALTS);
+    L.logs = L.in_at; L.slots = L.logs + SITE_LOGS * 8;
+    return L;
+}
 
 // fused pass (svjg_set_rows, svjg_run_begin, svjg_run_end), per slot.  Host block (pinned, mapped into the device: the genotype kernel
 // writes its results straight into it — they cross PCIe as they are produced, no copy kernel competes with the next pass —): pl32, raw,

@@ -14,6 +14,7 @@
 //   k_genotype_sites one site of insertions that share a position per lane, the same arithmetic over (K + 1)(K + 2) / 2 genotypes
 //   k_genotype_cohort one (row, sample) item per lane over a slot-major count matrix, k_genotype's arithmetic; NS / AC per row by wave ballots
 //   k_genotype_cohort_ploidy  the same division of work at a ploidy per item, k_genotype_ploidy's arithmetic; NS / AN / AC per row by wave ballots
+//   k_genotype_cohort_sites   one (site, sample) item per lane: the candidates present for the sample, k_genotype_sites' arithmetic; NS / AC per candidate by wave ballots
 //   k_cohort_prior    behind either cohort kernel: a row per wave segment, its allele frequency by EM over its samples, posterior GT and GQ per item
 //   k_cohort_store / k_cohort_load  one sample's column of that matrix from / to a dense count vector
 #pragma once
@@ -2345,6 +2346,91 @@ __global__ __launch_bounds__(TPB) void k_genotype_sites(GenoSitesArgs a) {
     if (st == GENO_ROW_GROW) atomicMax(a.max_n, (uint32_t)o.n);    // the log10(i!) table is too short: the host grows it and runs the sites again
     a.gt[s * 2] = o.a; a.gt[s * 2 + 1] = o.b;
     if (o.near) a.boundary[s] = 1;
+  }
+}
+
+// ---- cohort calls for insertions that share a position (svjg_genotype_cohort_sites; svjg_geno.h) ----
+// slots: MAX_SITE_ALTS CANDIDATE slots of the cohort matrix per site, checked by the host as k_genotype_sites' are.  Outputs per item (k, s),
+// [n_sites][S] row-major: k_genotype_sites' four and members (bit j: candidate j is present for sample s); site: MAX_SITE_ALTS words a site, zeroed
+// by the host in front of every launch.
+struct GenoCohortSitesArgs {
+    const unsigned long long *cm; const uint8_t *present; uint32_t n_slots, n_samples;
+    const uint32_t *slots; uint64_t n_sites; uint32_t min_support;
+    const double *logs;                // site_log_table of the call's err: SITE_LOGS doubles
+    const dd *logfact; uint32_t logfact_n;
+    uint8_t *gt; int64_t *pl; uint32_t *raw; uint8_t *members; uint8_t *boundary;
+    unsigned long long *site;
+    unsigned int *max_n;               // as GenoArgs::max_n
+};
+
+// Item i = k * S + s per lane, walked as k_genotype_cohort walks its items (the loop's bound is the WAVE's first item, every ballot is executed by
+// all 64 lanes on every trip, lanes beyond the last item vote "not called").  The lane gathers the candidates that are present for its sample
+// under a predicate, compacts them (site_compact: constant indices only) and runs geno_site on the K' it found — K' differs from lane to lane, so
+// the call's logarithms are staged in LDS as in k_genotype_sites; K' < 2: no site call, zeros.  The PLs go to pl + i * SITE_GENOTYPES, the item's
+// own 224 bytes (DESIGN 4.3 says why).  Site sums: three ballots per candidate (site_candidate_copies), the segment's first lane adds NS_j | AC_j << 32
+// to site[k][j] with one 64-bit atomic per candidate that has a call.
+// Compile remarks (ROCm 7.2.0, gfx950): 104 VGPRs, 87 SGPRs, none spilled, 0 bytes of scratch, 4 waves a SIMD, 128 bytes of LDS.
+__global__ __launch_bounds__(TPB) void k_genotype_cohort_sites(GenoCohortSitesArgs p) {
+  __shared__ double logs[SITE_LOGS];
+  for (uint32_t i = threadIdx.x; i < SITE_LOGS; i += blockDim.x) logs[i] = p.logs[i];
+  __syncthreads();
+  constexpr uint32_t NRAW = MAX_SITE_ALTS + 1;
+  const uint64_t S = p.n_samples, n_items = p.n_sites * S;
+  const uint32_t lane = threadIdx.x & 63u;
+  for (uint64_t w0 = (uint64_t)blockIdx.x * blockDim.x + (threadIdx.x - lane); w0 < n_items; w0 += (uint64_t)gridDim.x * blockDim.x) {
+    const uint64_t i = w0 + lane;
+    uint64_t k = 0, s = 0;
+    uint32_t members = 0, ga = SITE_NO_CALL, gb = SITE_NO_CALL;
+    if (i < n_items) {
+        k = i / S; s = i - k * S;
+        uint32_t cref[MAX_SITE_ALTS], calt[MAX_SITE_ALTS];
+        bool open = true, bad = false;
+#pragma unroll
+        for (uint32_t j = 0; j < MAX_SITE_ALTS; ++j) {
+            const uint32_t sl = p.slots[k * MAX_SITE_ALTS + j];
+            cref[j] = calt[j] = 0;
+            if (sl == NONE32) open = false;
+            else if (!open || sl >= p.n_slots) bad = true;         // (never, behind the host's checks; nothing is read through such a slot)
+            else {
+                const uint64_t at = (uint64_t)sl * S + s;
+                if (p.present[at]) {
+                    const unsigned long long c = p.cm[at];
+                    cref[j] = (uint32_t)c; calt[j] = (uint32_t)(c >> 32); members |= 1u << j;
+                }
+            }
+        }
+        if (bad) { atomicOr(p.max_n + 1, 1u); members = 0; }
+        SiteMembers m;
+        site_compact(members, cref, calt, m);
+        const bool call = m.K >= 2;
+        p.raw[i * NRAW] = call ? m.ref : 0;
+#pragma unroll
+        for (uint32_t j = 0; j < MAX_SITE_ALTS; ++j) p.raw[i * NRAW + 1 + j] = call ? m.alt[j] : 0;
+        GenoSite o{SITE_NO_CALL, SITE_NO_CALL, false, 0};
+        if (call) {
+            const uint32_t st = geno_site(m.K, m.ref, m.alt, p.min_support, logs[0], logs[m.K], logs[8 + m.K], p.logfact, p.logfact_n, p.pl + i * SITE_GENOTYPES, o);
+            if (st == GENO_ROW_GROW) atomicMax(p.max_n, (uint32_t)o.n);    // the table is too short: the host grows it and runs the items again
+        } else {
+#pragma unroll
+            for (uint32_t g = 0; g < SITE_GENOTYPES; ++g) p.pl[i * SITE_GENOTYPES + g] = 0;
+        }
+        p.gt[i * 2] = o.a; p.gt[i * 2 + 1] = o.b; p.members[i] = (uint8_t)members; p.boundary[i] = o.near;
+        ga = o.a; gb = o.b;
+    }
+    SiteBallots b;
+#pragma unroll
+    for (uint32_t j = 0; j < MAX_SITE_ALTS; ++j) {
+        const uint32_t c = site_candidate_copies(members, ga, gb, j);
+        b.in[j] = __ballot(c != SITE_NO_CALL); b.one[j] = __ballot(c == 1u); b.two[j] = __ballot(c == 2u);
+    }
+    const CohortSeg seg = cohort_segment(i, s, S, lane, n_items);
+    if (seg.leader) {
+#pragma unroll
+        for (uint32_t j = 0; j < MAX_SITE_ALTS; ++j) {
+            const CohortSums t = cohort_site_member_sums(b, j, seg.mask);
+            if (t.ns) atomicAdd(p.site + k * MAX_SITE_ALTS + j, (unsigned long long)cohort_site_word(t));
+        }
+    }
   }
 }
 

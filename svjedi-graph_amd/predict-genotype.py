@@ -5,6 +5,7 @@
     predict-genotype.py --cohort LIST -v VCF --minsupport N -o COHORT_genotype.vcf          (extension: one column per sample)
     predict-genotype.py --cohort LIST --cohort-ploidy FILE -v VCF ...                       (extension: a ploidy per sample and contig or region)
     predict-genotype.py --cohort LIST --cohort-prior [--cohort-ploidy FILE] -v VCF ...      (extension: calls under the cohort's allele frequency, with GQ)
+    predict-genotype.py --cohort LIST --joint-ins -v VCF ...                                (extension: insertions that share a position, together per sample)
 """
 import argparse
 import os
@@ -27,10 +28,13 @@ def main():
     ap.add_argument("--ploidy-file", metavar="<ploidyfile>",
                     help="per-contig or per-region ploidy, 0..8: lines `CHROM PLOIDY` or `CHROM FROM TO PLOIDY` (extension)")
     ap.add_argument("--joint-ins", action="store_true",
-                    help="genotype insertions that share a CHROM and POS together, 2..6 per site, diploid only (extension)")
+                    help="genotype insertions that share a CHROM and POS together, 2..6 per site, diploid only (extension).  With --cohort: per "
+                         "sample, over the rows that sample has counts for; a position with more than six such rows in the VCF is skipped for "
+                         "every sample (a single-sample run forms a site there when at most six of them are present in that sample)")
     ap.add_argument("--cohort", metavar="<samplelist>",
                     help="many samples, one multi-sample VCF with NS / AN / AC / AF in INFO: lines `NAME<TAB>PATH_TO_informative_aln.json` "
-                         "(extension; takes the place of -d; diploid, row by row, unless --cohort-ploidy is given)")
+                         "(extension; takes the place of -d; diploid, row by row, unless --cohort-ploidy is given; --joint-ins genotypes "
+                         "insertions that share a position together)")
     ap.add_argument("--cohort-ploidy", metavar="<cohortploidyfile>",
                     help="with --cohort: per-sample ploidy, 0..8, TAB-separated lines `SAMPLE<TAB>CHROM<TAB>PLOIDY` or "
                          "`SAMPLE<TAB>CHROM<TAB>FROM<TAB>TO<TAB>PLOIDY`, SAMPLE a name of the list or `*`; the first matching line wins, 2 otherwise (extension)")
@@ -40,8 +44,8 @@ def main():
     args = ap.parse_args()
     if args.cohort is not None and args.aln is not None:
         ap.error("exactly one of -d and --cohort")
-    if args.cohort is not None and (args.ploidy is not None or args.ploidy_file is not None or args.joint_ins):
-        ap.error("--cohort is diploid, row by row: it cannot be combined with --ploidy, --ploidy-file or --joint-ins "
+    if args.cohort is not None and (args.ploidy is not None or args.ploidy_file is not None):
+        ap.error("--cohort is diploid, row by row: it cannot be combined with --ploidy or --ploidy-file "
                  "(per-sample ploidy in a cohort: --cohort-ploidy)")
     if args.cohort_ploidy is not None and args.cohort is None:
         ap.error("--cohort-ploidy needs --cohort")
@@ -49,11 +53,13 @@ def main():
         ap.error("--cohort-prior needs --cohort")
     if args.joint_ins and (args.ploidy is not None or args.ploidy_file is not None):
         ap.error("--joint-ins is diploid only: it cannot be combined with --ploidy or --ploidy-file")
+    if args.joint_ins and (args.cohort_ploidy is not None or args.cohort_prior):
+        ap.error("--joint-ins is diploid only: with --cohort it cannot be combined with --cohort-ploidy or --cohort-prior")
     out = "genotype_results.txt" if args.output is None else args.output[0]
     err = args.err[0] if args.err is not None else 0.00005
     from svjg import genotype
     if args.cohort is not None:
-        genotype.run_cohort(args.cohort, args.vcf, out, args.minsupport, err, ploidy_file=args.cohort_ploidy, prior=args.cohort_prior)
+        genotype.run_cohort(args.cohort, args.vcf, out, args.minsupport, err, ploidy_file=args.cohort_ploidy, prior=args.cohort_prior, joint_ins=args.joint_ins)
         return
     genotype.run(args.aln[0], args.vcf, out, args.minsupport, err, ploidy=args.ploidy, ploidy_file=args.ploidy_file, joint_ins=args.joint_ins)
 

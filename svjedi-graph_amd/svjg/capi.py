@@ -92,6 +92,7 @@ _SIGS = {
     "svjg_genotype_cohort": (ctypes.c_int, [ctypes.c_void_p] * 4 + [ctypes.c_uint64, ctypes.c_uint32, ctypes.c_double] + [ctypes.c_void_p] * 6),
     "svjg_genotype_cohort_ploidy": (ctypes.c_int, [ctypes.c_void_p] * 5 + [ctypes.c_uint32, ctypes.c_uint64, ctypes.c_uint32, ctypes.c_double] + [ctypes.c_void_p] * 6),
     "svjg_genotype_cohort_prior": (ctypes.c_int, [ctypes.c_void_p] * 5 + [ctypes.c_uint32, ctypes.c_uint64, ctypes.c_uint32, ctypes.c_double] + [ctypes.c_void_p] * 9),
+    "svjg_genotype_cohort_sites": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_uint32, ctypes.c_double] + [ctypes.c_void_p] * 6),
     "svjg_set_rows": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64]),
     "svjg_run_resident": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_uint64, ctypes.c_uint32, ctypes.c_double] + [ctypes.POINTER(ctypes.c_void_p)] * 5),
     "svjg_run_begin": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_uint64, ctypes.c_uint32, ctypes.c_double]),
@@ -591,6 +592,21 @@ class Context:
         genotyped[n, S], boundary[n, S] — pl, raw, genotyped and boundary as genotype_cohort / genotype_cohort_ploidy give them —, site[n, 3] =
         NS, AN, AC of the posterior calls, gq[n, S] (0xFF: none), af[n] (NaN: no estimate), em_steps[n] (bit 31: not converged))"""
         return self._cohort_call("svjg_genotype_cohort_prior", sv_type, slot, ok, ploidy, max_ploidy, min_support, err)
+
+    def genotype_cohort_sites(self, slots, min_support, err):
+        """genotype_sites for every sample of the cohort matrix in one launch (svjg_genotype_cohort_sites).  slots[n, 6]: the CANDIDATE slots of each
+        site first, 0xFFFFFFFF behind them; sample s's site = the candidates present for s.  -> (gt[n, S, 2] = the pair or 0xFF, 0xFF, pl[n, S, 28],
+        raw[n, S, 7], members[n, S] = bit j: candidate j took part (fewer than two: no site call), boundary[n, S] = the items to recompute with
+        svjg.genotype.exact_pl_site, site[n, 6, 2] = NS_j and AC_j of every candidate over the items with a site call)"""
+        slots = np.ascontiguousarray(slots, dtype=np.uint32)
+        if slots.ndim != 2 or slots.shape[1] != MAX_SITE_ALTS:
+            raise SvjgError("slots: %d per site" % MAX_SITE_ALTS)
+        n = len(slots)
+        S = getattr(self, "_cohort", (0, 0))[0]
+        out = (np.empty((n, S, 2), np.uint8), np.empty((n, S, SITE_GENOTYPES), np.int64), np.empty((n, S, MAX_SITE_ALTS + 1), np.uint32),
+               np.empty((n, S), np.uint8), np.empty((n, S), np.uint8), np.empty((n, MAX_SITE_ALTS, 2), np.uint32))
+        self._chk(self.lib.svjg_genotype_cohort_sites(self.h, slots.ctypes.data, n, min_support, float(err), *(a.ctypes.data for a in out)))
+        return out
 
     def set_rows(self, sv_type, slot, ok):
         """the VCF rows' input arrays of genotype(), left on the device for run_resident()"""

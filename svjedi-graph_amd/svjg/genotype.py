@@ -497,7 +497,7 @@ def genotype_with_counts_joint(ctx, vcf_path, slot_of, out_path, min_support, er
     return write_vcf_joint(out_path, rows, gt, pl, raw, done, member)
 
 
-# ---- cohort (--cohort [--cohort-ploidy FILE] [--cohort-prior]): many samples' counts, one multi-sample VCF: the three svjg_genotype_cohort* calls, Python rows, one driver and one writer ----
+# ---- cohort (--cohort [--cohort-ploidy FILE] [--cohort-prior] | [--joint-ins]): many samples' counts, one multi-sample VCF: the three svjg_genotype_cohort* calls (and svjg_genotype_cohort_sites behind the plain one), Python rows, one driver and one writer ----
 
 COHORT_INFO_LINES = (
     '##INFO=<ID=NS,Number=1,Type=Integer,Description="Number of samples with a called genotype">\n'
@@ -575,13 +575,40 @@ def cohort_info(info, ns, ac, an=None, em=None):
     return ";".join(keep)
 
 
-def write_vcf_cohort(out_path, rows, names, gt, pl, raw, done, site, ploidy=None, gq=None, af=None, em_steps=None):
+def _joint_columns(rows, raw, plain, joint):
+    """columns(v) of a --cohort --joint-ins run from the plain cohort's: a row of `joint` (row -> (covered[S], g[S], pl3[S, 3], a[S], b[S], sal[S]),
+    cohort_joint_sites) prints GT:DP:AD:PL:SGT:SAL — a covered sample what write_vcf_joint prints (the projection of its site call; DP and AD stay
+    the row's own), every other sample its independent column and `:.:.` —; every other row is the plain one"""
+    raw = np.asarray(raw)
+
+    def columns(v):
+        cols = plain(v)
+        if v not in joint:
+            return cols
+        covered, g, p3, a, b, sal = (x.tolist() for x in joint[v])
+        t = int(rows.sv_type[v])
+        out = ["GT:DP:AD:PL:SGT:SAL"]
+        for s, col in enumerate(cols[1:]):
+            if not covered[s]:
+                out.append(col + ":.:.")
+                continue
+            own = sample_column(t, 2, NO_CALL if g[s] == 3 else g[s], p3[s], int(raw[v, s, 0]), int(raw[v, s, 1]), True)
+            out.append("%s:%s:%d" % (own, "./." if a[s] == NO_CALL else "%d/%d" % (a[s], b[s]), sal[s]))
+        return out
+    return columns
+
+
+def write_vcf_cohort(out_path, rows, names, gt, pl, raw, done, site, ploidy=None, gq=None, af=None, em_steps=None, joint=None):
     """The one cohort writer: write_vcf with one column per sample (gt, done: [n, S]; pl: [n, S, >= 3]; raw: [n, S, 2]), the site tags' INFO lines
     in front of the header and the tags in INFO; site: [n, 2] = NS, AC or [n, 3] = NS, AN, AC.  ploidy ([n, S]; None: diploid arrays, `Number=3`):
     every item in write_vcf_ploidy's forms (pl: [n, S, >= P + 1]) and `Number=G` in the PL header line.  --cohort-prior: gq[n, S], one more
-    FORMAT field, GQ; af[n] and em_steps[n], EMAF / EMNC in INFO.  -> the number of genotyped rows of every sample"""
+    FORMAT field, GQ; af[n] and em_steps[n], EMAF / EMNC in INFO.  joint (--joint-ins; cohort_joint_sites): the rows that are members of a site
+    for at least one sample, printed by _joint_columns, and SITE_FORMAT_LINES behind the PL line.  -> the number of genotyped rows of every sample"""
     columns, n_done = _item_columns(rows, ploidy, gt, pl, raw, done, gq)
     header = FORMAT_HEADER if ploidy is None else FORMAT_HEADER.replace(_PL_3, _PL_G)
+    if joint is not None:
+        columns = _joint_columns(rows, raw, columns, joint)
+        header = header.replace(_PL_LINE, _PL_LINE + SITE_FORMAT_LINES)
     if gq is not None:
         header = header.replace("#CHROM\t", _GQ_LINE + "#CHROM\t")
     header = COHORT_INFO_LINES + (COHORT_PRIOR_INFO_LINES if af is not None else "") + header.replace("\tFORMAT\tSAMPLE\n", "\tFORMAT\t" + "\t".join(names) + "\n")
@@ -723,14 +750,102 @@ _GQ_LINE = '##FORMAT=<ID=GQ,Number=1,Type=Integer,Description="Genotype quality:
 EM_NOT_CONVERGED = 1 << 31         # svjg.h: bit 31 of a row's em_steps word
 
 
-def run_cohort(list_path, vcf_path, out_path, min_support=3, err=0.00005, device=0, ploidy_file=None, prior=False):
+# ---- cohort calls for insertions that share a position (--cohort LIST --joint-ins): svjg_genotype_cohort_sites behind the plain cohort call ----
+
+JOINT_INS_COHORT = "--joint-ins is diploid only: with --cohort it cannot be combined with --cohort-ploidy or --cohort-prior"
+COHORT_SITES_ITEM_BYTES = 256      # svjg.h: what one (site, sample) item takes in a svjg_genotype_cohort_sites call,
+COHORT_SITES_SITE_BYTES = 72       # and one site
+
+
+def cohort_sites_chunk(n_samples):
+    """sites per svjg_genotype_cohort_sites call, so that it stays under 1 GiB"""
+    return max(1, COHORT_CALL_BYTES // (COHORT_SITES_ITEM_BYTES * max(1, int(n_samples)) + COHORT_SITES_SITE_BYTES))
+
+
+@functools.lru_cache(maxsize=None)
+def _site_copy_sets(K, i):
+    """the genotype indices of a site of K members with 0, 1 and 2 copies of allele i (project_site's three groups)"""
+    return tuple(np.array([k for k, (x, y) in enumerate(site_genotypes(K)) if (x == i) + (y == i) == n], dtype=np.int64) for n in range(3))
+
+
+def project_cohort_sites(s_gt, s_pl, members):
+    """project_site for every (site, sample, candidate) at once.  s_gt[n, S, 2], s_pl[n, S, 28], members[n, S] as svjg_genotype_cohort_sites returns
+    them -> (covered[n, S, 6]: the candidate is a member of the sample's site, K' >= 2; g[n, S, 6]: its copies 0..2, 3 = the site has no call;
+    pl3[n, S, 6, 3]: the smallest site PL per copy number; sal[n, S, 6]: its allele number, 0 where it is absent).  numpy over the index sets of
+    every (K', allele): no loop over items."""
+    members = np.asarray(members)
+    bits = ((members[..., None] >> np.arange(MAX_SITE_ALTS, dtype=np.uint8)) & 1).astype(np.int64)
+    k_of = bits.sum(axis=-1)
+    sal = np.cumsum(bits, axis=-1) * bits
+    covered = (bits != 0) & (k_of[..., None] >= 2)
+    a, b = np.asarray(s_gt)[..., 0, None].astype(np.int64), np.asarray(s_gt)[..., 1, None].astype(np.int64)
+    g = np.where(a == NO_CALL, 3, (a == sal).astype(np.int64) + (b == sal)).astype(np.uint8)
+    pl3 = np.zeros(members.shape + (MAX_SITE_ALTS, 3), dtype=np.int64)
+    for K in range(2, MAX_SITE_ALTS + 1):
+        of_k = covered & (k_of[..., None] == K)
+        if not of_k.any():
+            continue
+        for i in range(1, K + 1):
+            at = np.nonzero(of_k & (sal == i))
+            if not len(at[0]):
+                continue
+            site_pl = s_pl[at[0], at[1]]
+            for n, idx in enumerate(_site_copy_sets(K, i)):
+                pl3[at[0], at[1], at[2], n] = site_pl[:, idx].min(axis=1)
+    return covered, g, pl3, sal
+
+
+def cohort_joint_sites(ctx, rows, gt, site, min_support, err, step=None):
+    """Behind the plain cohort call (gt[n, S], site[n, 2] = NS, AC): the candidate sites at the VCF level — the INS rows with ok & 1 and a slot
+    that share CHROM and POS text, 2..6 of them in file order (form_sites; more than six: skipped for every sample, one stderr line) —, ONE
+    svjg_genotype_cohort_sites call over them (chunks of `step` sites, None: what fits 1 GiB), the flagged items recomputed with their own K'
+    (exact_pl_site), the projection.  -> (site with the candidate rows' NS and AC replaced: the kernel's sums over the covered samples plus the
+    independent calls of the others; joint: row -> (covered[S], g[S], pl3[S, 3], a[S], b[S], sal[S]) for the rows covered in at least one sample)"""
+    import sys
+    min_support, call_err, _ = _call_args(min_support, err)
+    sites, skipped = form_sites(rows, ((rows.ok & 1) != 0) & (rows.slot != NONE))
+    for chrom, pos, count in skipped:
+        print("--joint-ins: %s:%s has %d insertions, more than %d: they keep their independent calls" % (chrom, pos, count, MAX_SITE_ALTS), file=sys.stderr)
+    site, joint = np.array(site), {}
+    if not sites:
+        return site, joint
+    slots = np.full((len(sites), MAX_SITE_ALTS), NONE, dtype=np.uint32)
+    for k, m in enumerate(sites):
+        slots[k, :len(m)] = rows.slot[m]
+    if step is None:
+        step = cohort_sites_chunk(np.shape(gt)[1])
+    parts = [ctx.genotype_cohort_sites(slots[at:at + step], min_support, call_err) for at in range(0, len(sites), int(step))]
+    s_gt, s_pl, s_raw, members, boundary, s_site = (np.concatenate([p[k] for p in parts]) for k in range(6))
+    for k, s in map(tuple, np.argwhere(boundary != 0)):
+        K = bin(int(members[k, s])).count("1")
+        s_pl[k, s, :(K + 1) * (K + 2) // 2] = exact_pl_site(int(s_raw[k, s, 0]), [int(x) for x in s_raw[k, s, 1:K + 1]], err)
+    covered, g, pl3, sal = project_cohort_sites(s_gt, s_pl, members)
+    k_of = np.repeat(np.arange(len(sites)), [len(m) for m in sites])
+    j_of = np.concatenate([np.arange(len(m)) for m in sites])
+    r_of = np.concatenate([np.asarray(m, dtype=np.int64) for m in sites])
+    cov = covered[k_of, :, j_of]                                 # [candidate rows, S]
+    own = np.asarray(gt)[r_of]
+    alone = (own != 3) & ~cov                                    # the samples whose item has no site there keep their independent call
+    site[r_of, 0] = s_site[k_of, j_of, 0] + alone.sum(axis=1)
+    site[r_of, 1] = s_site[k_of, j_of, 1] + np.where(alone, own, 0).sum(axis=1)
+    for c in np.flatnonzero(cov.any(axis=1)).tolist():
+        k, j = k_of[c], j_of[c]
+        joint[int(r_of[c])] = (cov[c], g[k, :, j], pl3[k, :, j], s_gt[k, :, 0], s_gt[k, :, 1], sal[k, :, j])
+    return site, joint
+
+
+def run_cohort(list_path, vcf_path, out_path, min_support=3, err=0.00005, device=0, ploidy_file=None, prior=False, joint_ins=False):
     """predict-genotype.py --cohort: the samples of a cohort list (load_cohort_list), one multi-sample VCF.  Sample column s is what the
     reference writes as SAMPLE for sample s alone; INFO gains NS, AN, AC and AF.  ploidy_file (--cohort-ploidy, load_cohort_ploidy_file): a
     ploidy per sample and contig or region; column s is then what --ploidy-file with the sample's lines writes for sample s alone, and AN is
     the called samples' ploidies summed.  prior (--cohort-prior): GT is the call under the row's allele frequency, estimated from all samples by EM
-    (svjg_genotype_cohort_prior), with GQ beside it and EMAF / EMNC in INFO; DP, AD and PL stay those of the plain run.  -> the number of genotyped
-    rows of every sample"""
+    (svjg_genotype_cohort_prior), with GQ beside it and EMAF / EMNC in INFO; DP, AD and PL stay those of the plain run.  joint_ins (--joint-ins,
+    diploid only: neither ploidy_file nor prior): the insertions that share a position are genotyped together per sample (cohort_joint_sites);
+    column s is then what --joint-ins writes for sample s alone, but for `:.:.` behind a sample that has no site on a row another sample has one
+    on, and for a position with more than six candidate rows, which is skipped for EVERY sample.  -> the number of genotyped rows of every sample"""
     from . import capi, filter as flt
+    if joint_ins and (ploidy_file is not None or prior):
+        raise ValueError(JOINT_INS_COHORT)                       # (before anything is read, asked of the device or written)
     samples = load_cohort_list(list_path)                        # (raises before any output exists)
     names = [name for name, _ in samples]
     regions = load_cohort_ploidy_file(ploidy_file, names) if ploidy_file is not None else None   # (so does this)
@@ -747,9 +862,12 @@ def run_cohort(list_path, vcf_path, out_path, min_support=3, err=0.00005, device
         for s, (slots, counts) in enumerate(per):
             ctx.cohort_set_counts(s, slots, counts)
         gt, pl, raw, done, site, *em = genotype_cohort_rows(ctx, rows, len(samples), min_support, err, ploidy, prior)   # (em: gq, af, em_steps with the prior)
+        joint = None
+        if joint_ins:
+            site, joint = cohort_joint_sites(ctx, rows, gt, site, min_support, err)
     finally:
         ctx.close()
-    n_done = write_vcf_cohort(out_path, rows, names, gt, pl, raw, done, site, ploidy, *em)
+    n_done = write_vcf_cohort(out_path, rows, names, gt, pl, raw, done, site, ploidy, *em, joint=joint)
     for name, n in zip(names, n_done):
         print("Genotyped svs (%s): %d" % (name, n))
     return n_done
