@@ -82,7 +82,7 @@ constexpr uint64_t STAGE_PIECE = 8ull << 20;
 // hands out pointers into BLOCK_ROWS' twin and svjg_genotype_boundary reads it later, and both must survive calls of the other six.
 // A fused pass's slot holds the same pair (RunSlot).
 struct LegBlock { DevBuf<uint8_t> d;  PinBuf h; };
-enum { BLOCK_ROWS, BLOCK_PLOIDY, BLOCK_SITES, BLOCK_COHORT, BLOCK_COHORT_PLOIDY, BLOCK_COHORT_PRIOR, BLOCK_COHORT_SITES, LEG_BLOCKS };   // rows_layout, ploidy_layout, sites_layout, cohort_layout for the three cohort blocks, cohort_sites_layout (svjg_geno.h)
+enum { BLOCK_ROWS, BLOCK_PLOIDY, BLOCK_SITES, BLOCK_COHORT, BLOCK_COHORT_PLOIDY, BLOCK_COHORT_PRIOR, BLOCK_COHORT_SITES, LEG_BLOCKS };   // rows_layout, ploidy_layout, sites_layout, cohort_layout for the three cohort blocks, sites_layout again (svjg_geno.h)
 
 // slots the passes of svjg_run_begin rotate through: two may be in flight, and the one the NEXT pass will use is zeroed while the newest computes
 constexpr int RUN_SLOTS = 3;
@@ -1136,17 +1136,29 @@ extern "C" int svjg_genotype_ploidy(svjg_ctx *c, const uint8_t *sv_type, const u
     return 0;
 }
 
-// Insertions that share a position, genotyped together (k_genotype_sites; svjg.h), through genotype_leg in BLOCK_SITES: the call's logarithms
-// and the sites' slots go in.  Everything a caller can get wrong is found here, before any launch.
-static int launch_sites(svjg_ctx *c, GenoSitesArgs &a) {
+// Insertions that share a position, genotyped together (svjg.h), through genotype_leg by ONE leg, sites_call: svjg_genotype_sites in BLOCK_SITES
+// (k_genotype_sites on the count vector) and svjg_genotype_cohort_sites in BLOCK_COHORT_SITES (k_genotype_cohort_sites on the cohort matrix; it reads
+// nothing else of the context).  launch_sites: all items with the table at hand.  The cohort's site words lie right in front of the max_n pair
+// (sites_layout): ONE memset zeroes both in front of EVERY launch, as launch_cohort's.  Blocks: capped_grid(n_sites) for the single-sample kernel;
+// the cohort kernel takes 104 VGPRs (the compiler's resource remark), so a SIMD holds 512 / 104 = four of its waves and a unit four
+// blocks of four waves; the rest in strides of the grid.
+constexpr uint64_t COHORT_SITES_WAVES = 4;
+static int launch_sites(svjg_ctx *c, GenoCohortSitesArgs &p, bool cohort) {
+    GenoSitesArgs &a = p.g;
     a.logfact = c->d_logfact; a.logfact_n = c->logfact_n;
-    HIPCHK(c, hipMemsetAsync(a.max_n, 0, 8, c->stream));
-    hipLaunchKernelGGL(k_genotype_sites, dim3(capped_grid(a.n_sites)), dim3(TPB), 0, c->stream, a);
+    if (cohort) {
+        HIPCHK(c, hipMemsetAsync(p.site, 0, a.n_sites * MAX_SITE_ALTS * 8 + 8, c->stream));
+        const uint64_t n_items = a.n_sites * p.n_samples, blocks = (n_items + TPB - 1) / TPB, cap = (uint64_t)c->n_cu * COHORT_SITES_WAVES;
+        hipLaunchKernelGGL(k_genotype_cohort_sites, dim3((uint32_t)(blocks < cap ? blocks : cap)), dim3(TPB), 0, c->stream, p);
+    } else {
+        HIPCHK(c, hipMemsetAsync(a.max_n, 0, 8, c->stream));
+        hipLaunchKernelGGL(k_genotype_sites, dim3(capped_grid(a.n_sites)), dim3(TPB), 0, c->stream, a);
+    }
     HIPCHK(c, hipGetLastError());
     return 0;
 }
 
-// what a caller can get wrong about its sites (svjg_genotype_sites, svjg_genotype_cohort_sites): 2..MAX_SITE_ALTS slots below n_slots, no hole, none twice
+// what a caller can get wrong about its sites: 2..MAX_SITE_ALTS slots below n_slots, no hole, none twice
 static int check_sites(svjg_ctx *c, const uint32_t *slots, uint64_t n_sites, uint32_t n_slots) {
     for (uint64_t s = 0; s < n_sites; ++s) {
         const uint32_t *m = slots + s * MAX_SITE_ALTS;
@@ -1163,31 +1175,50 @@ static int check_sites(svjg_ctx *c, const uint32_t *slots, uint64_t n_sites, uin
     return 0;
 }
 
-extern "C" int svjg_genotype_sites(svjg_ctx *c, const uint32_t *slots, uint64_t n_sites, uint32_t min_support, double err,
-                                   uint8_t *gt, int64_t *pl, uint32_t *raw, uint8_t *boundary) {
+// The host leg of both: the checks of the call's kind (all of them before any launch), the call's logarithms by the host's libm and the sites' slots in, the kernel of the call's kind, the copy out.  members, site: the cohort's only.
+static int sites_call(svjg_ctx *c, int block, const uint32_t *slots, uint64_t n_sites, uint32_t min_support, double err,
+                      uint8_t *gt, int64_t *pl, uint32_t *raw, uint8_t *members, uint8_t *boundary, uint32_t *site) {
     static_assert(SVJG_MAX_SITE_ALTS == MAX_SITE_ALTS && SVJG_SITE_GENOTYPES == SITE_GENOTYPES, "svjg.h and svjg_geno.h disagree");
-    if (!c || !c->have_counts) return SVJG_E_ARG;
+    const bool cohort = block == BLOCK_COHORT_SITES;
+    if (!c || (!cohort && !c->have_counts)) return SVJG_E_ARG;
+    if (cohort && !c->d_cm) { c->err = "no cohort matrix"; return SVJG_E_ARG; }
     if (n_sites == 0) return 0;
-    if (!slots || !gt || !pl || !raw || !boundary) return SVJG_E_ARG;
-    if (const int rc0 = check_sites(c, slots, n_sites, c->n_slots)) return rc0;
+    if (!slots || !gt || !pl || !raw || !boundary || (cohort && (!members || !site))) { if (cohort) c->err = "a null array"; return SVJG_E_ARG; }
+    const uint64_t S = cohort ? c->cohort_samples : 1;
+    if (cohort && n_sites > (1ull << 40) / S) { c->err = "too many items for one call: genotype the sites in chunks"; return SVJG_E_ARG; }
+    if (const int rc0 = check_sites(c, slots, n_sites, cohort ? c->cohort_slots : c->n_slots)) return rc0;
     HIPCHK(c, hipSetDevice(c->device));
-    { const int rc0 = fetch_slot_counts(c); if (rc0) return rc0; }
-    const SitesLayout L = sites_layout(n_sites);
-    const int rc = genotype_leg(c, c->leg[BLOCK_SITES], L,
-        [&](uint8_t *hb) { site_log_table(err, (double *)(hb + L.logs)); memcpy(hb + L.slots, slots, n_sites * MAX_SITE_ALTS * 4); },   // (host libm, as geno_args' three)
+    if (!cohort) { const int rc0 = fetch_slot_counts(c); if (rc0) return rc0; }
+    const SitesLayout L = sites_layout(n_sites, S, cohort);
+    const int rc = genotype_leg(c, c->leg[block], L,
+        [&](uint8_t *hb) { site_log_table(err, (double *)(hb + L.logs)); memcpy(hb + L.slots, slots, n_sites * MAX_SITE_ALTS * 4); },
         [&](uint8_t *base) {
-            GenoSitesArgs a{};
-            a.counts = c->graph.counts; a.n_slots = c->n_slots; a.slots = (const uint32_t *)(base + L.slots); a.n_sites = n_sites; a.min_support = min_support;
-            a.logs = (const double *)(base + L.logs);
+            GenoCohortSitesArgs p{};
+            GenoSitesArgs &a = p.g;
+            a.counts = cohort ? c->cm() : c->graph.counts; a.n_slots = cohort ? c->cohort_slots : c->n_slots;
+            a.slots = (const uint32_t *)(base + L.slots); a.n_sites = n_sites; a.min_support = min_support; a.logs = (const double *)(base + L.logs);
             a.pl = (int64_t *)(base + L.pl); a.raw = (uint32_t *)(base + L.raw); a.gt = base + L.gt; a.boundary = base + L.boundary;
             a.max_n = (unsigned int *)(base + L.maxn);
-            return launch_sites(c, a);
+            p.present = c->d_cpresent; p.n_samples = (uint32_t)S; p.members = base + L.members; p.site = (unsigned long long *)(base + L.site);
+            return launch_sites(c, p, cohort);
         });
     if (rc) return rc;
-    const uint8_t *hb = c->leg[BLOCK_SITES].h;
-    memcpy(pl, hb + L.pl, n_sites * SITE_GENOTYPES * sizeof *pl); memcpy(raw, hb + L.raw, n_sites * (MAX_SITE_ALTS + 1) * sizeof *raw);
-    memcpy(gt, hb + L.gt, n_sites * 2); memcpy(boundary, hb + L.boundary, n_sites);
+    const uint8_t *hb = c->leg[block].h;
+    const uint64_t n = n_sites * S;
+    memcpy(pl, hb + L.pl, n * SITE_GENOTYPES * sizeof *pl); memcpy(raw, hb + L.raw, n * (MAX_SITE_ALTS + 1) * sizeof *raw);
+    memcpy(gt, hb + L.gt, n * 2); memcpy(boundary, hb + L.boundary, n);
+    if (cohort) { memcpy(members, hb + L.members, n); memcpy(site, hb + L.site, n_sites * MAX_SITE_ALTS * 8); }   // (NS_j, AC_j: the two halves of the kernel's one word a candidate)
     return 0;
+}
+
+extern "C" int svjg_genotype_sites(svjg_ctx *c, const uint32_t *slots, uint64_t n_sites, uint32_t min_support, double err,
+                                   uint8_t *gt, int64_t *pl, uint32_t *raw, uint8_t *boundary) {
+    return sites_call(c, BLOCK_SITES, slots, n_sites, min_support, err, gt, pl, raw, nullptr, boundary, nullptr);
+}
+
+extern "C" int svjg_genotype_cohort_sites(svjg_ctx *c, const uint32_t *slots, uint64_t n_sites, uint32_t min_support, double err,
+                                          uint8_t *gt, int64_t *pl, uint32_t *raw, uint8_t *members, uint8_t *boundary, uint32_t *site) {
+    return sites_call(c, BLOCK_COHORT_SITES, slots, n_sites, min_support, err, gt, pl, raw, members, boundary, site);
 }
 
 // ---- cohort: many samples' counts against one row set (svjg.h) -------------------------------------------------------------
@@ -1376,50 +1407,6 @@ extern "C" int svjg_genotype_cohort_prior(svjg_ctx *c, const uint8_t *sv_type, c
                                           uint32_t *raw, uint8_t *genotyped, uint8_t *boundary, uint32_t *site, uint8_t *gq, double *af,
                                           uint32_t *em_steps) {
     return cohort_call(c, BLOCK_COHORT_PRIOR, sv_type, slot, ok, ploidy, max_ploidy, n_rows, min_support, err, gt, pl, raw, genotyped, boundary, site, gq, af, em_steps);
-}
-
-// Cohort calls for insertions that share a position (k_genotype_cohort_sites; svjg.h), through genotype_leg in BLOCK_COHORT_SITES: the call's
-// logarithms and the sites' candidate slots go in; it reads the cohort matrix and nothing else of the context.  The site words lie right in front of
-// the max_n pair (cohort_sites_layout): ONE memset zeroes both in front of EVERY launch, as launch_cohort's.  Blocks: the kernel takes 104 VGPRs
-// (the compiler's resource remark), so a SIMD holds 512 / 104 = four of its waves and a unit four blocks of four waves; the rest in strides of the grid.
-constexpr uint64_t COHORT_SITES_WAVES = 4;
-static int launch_cohort_sites(svjg_ctx *c, GenoCohortSitesArgs &p) {
-    p.logfact = c->d_logfact; p.logfact_n = c->logfact_n;
-    HIPCHK(c, hipMemsetAsync(p.site, 0, p.n_sites * MAX_SITE_ALTS * 8 + 8, c->stream));
-    const uint64_t n_items = p.n_sites * p.n_samples, blocks = (n_items + TPB - 1) / TPB, cap = (uint64_t)c->n_cu * COHORT_SITES_WAVES;
-    hipLaunchKernelGGL(k_genotype_cohort_sites, dim3((uint32_t)(blocks < cap ? blocks : cap)), dim3(TPB), 0, c->stream, p);
-    HIPCHK(c, hipGetLastError());
-    return 0;
-}
-
-extern "C" int svjg_genotype_cohort_sites(svjg_ctx *c, const uint32_t *slots, uint64_t n_sites, uint32_t min_support, double err,
-                                          uint8_t *gt, int64_t *pl, uint32_t *raw, uint8_t *members, uint8_t *boundary, uint32_t *site) {
-    if (!c) return SVJG_E_ARG;
-    if (!c->d_cm) { c->err = "no cohort matrix"; return SVJG_E_ARG; }
-    if (n_sites == 0) return 0;
-    if (!slots || !gt || !pl || !raw || !members || !boundary || !site) { c->err = "a null array"; return SVJG_E_ARG; }
-    const uint64_t S = c->cohort_samples;
-    if (n_sites > (1ull << 40) / S) { c->err = "too many items for one call: genotype the sites in chunks"; return SVJG_E_ARG; }
-    if (const int rc0 = check_sites(c, slots, n_sites, c->cohort_slots)) return rc0;
-    HIPCHK(c, hipSetDevice(c->device));
-    const CohortSitesLayout L = cohort_sites_layout(n_sites, S);
-    const int rc = genotype_leg(c, c->leg[BLOCK_COHORT_SITES], L,
-        [&](uint8_t *hb) { site_log_table(err, (double *)(hb + L.logs)); memcpy(hb + L.slots, slots, n_sites * MAX_SITE_ALTS * 4); },   // (host libm, as geno_args' three)
-        [&](uint8_t *base) {
-            GenoCohortSitesArgs p{};
-            p.cm = c->cm(); p.present = c->d_cpresent; p.n_slots = c->cohort_slots; p.n_samples = c->cohort_samples;
-            p.slots = (const uint32_t *)(base + L.slots); p.n_sites = n_sites; p.min_support = min_support; p.logs = (const double *)(base + L.logs);
-            p.pl = (int64_t *)(base + L.pl); p.raw = (uint32_t *)(base + L.raw); p.gt = base + L.gt; p.members = base + L.members; p.boundary = base + L.boundary;
-            p.site = (unsigned long long *)(base + L.site); p.max_n = (unsigned int *)(base + L.maxn);
-            return launch_cohort_sites(c, p);
-        });
-    if (rc) return rc;
-    const uint8_t *hb = c->leg[BLOCK_COHORT_SITES].h;
-    const uint64_t n = n_sites * S;
-    memcpy(pl, hb + L.pl, n * SITE_GENOTYPES * sizeof *pl); memcpy(raw, hb + L.raw, n * (MAX_SITE_ALTS + 1) * sizeof *raw);
-    memcpy(gt, hb + L.gt, n * 2); memcpy(members, hb + L.members, n); memcpy(boundary, hb + L.boundary, n);
-    memcpy(site, hb + L.site, n_sites * MAX_SITE_ALTS * 8);        // NS_j, AC_j: the two halves of the kernel's one word a candidate
-    return 0;
 }
 
 // ---- the whole pass in one call, one host wait; two passes in flight ------------------------------------------------------

@@ -440,6 +440,72 @@ SVJG_HD CohortSums cohort_site_member_sums(const SiteBallots &b, uint32_t j, uin
     return CohortSums{ns, 2 * ns, (uint32_t)__builtin_popcountll(b.one[j] & mask) + 2 * (uint32_t)__builtin_popcountll(b.two[j] & mask)};
 }
 
+// ---- what both site kernels do per item (k_genotype_sites, k_genotype_cohort_sites; tests/site_sim runs the same code on the CPU) ----
+// The ONE place that reads a site's slots (the named ones first, SITE_NO_SLOT behind them), into sample s of a slot-major count matrix of S samples
+// and n_slots slots (counts[slot * S + s], present[slot * S + s]); the count vector is the matrix of S = 1, s = 0, and present == nullptr says every
+// named slot is a member (the single-sample call).  members: bit j = candidate j is present, cref[j] / calt[j] its raw counts (0 where it is not).
+// bad: a slot behind a hole, or at or beyond n_slots — never, behind the host's checks; NOTHING is read through such a slot.  Unrolled, every array
+// indexed by constants only (registers on the device, no scratch).
+constexpr uint32_t SITE_NO_SLOT = 0xFFFFFFFFu;          // (svjg_line.h: NONE32)
+struct SiteGather { uint32_t members, cref[MAX_SITE_ALTS], calt[MAX_SITE_ALTS]; bool bad; };
+SVJG_HD void site_gather(const unsigned long long *counts, const uint8_t *present, uint64_t S, uint64_t s, uint32_t n_slots, const uint32_t *slots, SiteGather &g) {
+    g.members = 0; g.bad = false;
+    bool open = true;
+    uint32_t named[MAX_SITE_ALTS];                       // (all six ahead of the first count: one round trip to the site's 24 bytes, not one per slot between the counts')
+    SVJG_UNROLL
+    for (uint32_t j = 0; j < MAX_SITE_ALTS; ++j) named[j] = slots[j];
+    SVJG_UNROLL
+    for (uint32_t j = 0; j < MAX_SITE_ALTS; ++j) {
+        const uint32_t sl = named[j];
+        g.cref[j] = g.calt[j] = 0;
+        if (sl == SITE_NO_SLOT) open = false;
+        else if (!open || sl >= n_slots) g.bad = true;
+        else {
+            const uint64_t at = (uint64_t)sl * S + s;
+            if (!present || present[at]) {
+                const unsigned long long c = counts[at];
+                g.cref[j] = (uint32_t)c; g.calt[j] = (uint32_t)(c >> 32); g.members |= 1u << j;
+            }
+        }
+    }
+}
+
+// One item behind the gather: the members compacted into alt[0..K') (site_compact), `call` = K' >= 2 and not bad, raw[1 + MAX_SITE_ALTS] = the ref
+// maximum and the members' alt counts, geno_site into the item's SITE_GENOTYPES PLs or zeros, the two gt bytes, the boundary byte.  logs:
+// site_log_table of the call's err.  dense (a literal at both calls): the single-sample call, present == nullptr — every named slot is a member and
+// the host has refused holes, so the compaction is the identity, alt[j] = calt[j] and K = popcount(members), and is not run (through site_compact
+// k_genotype_sites is 90 instructions longer and ran 1.914 .. 1.949 ms, 64 calls summed, against 1.910 .. 1.914 without it in the same job:
+// profiles/r18/experiments/one_sites_leg.txt); K < 2 counts as bad there.  -> status as geno_site (GENO_ROW_OK without a call), n = s_K, members
+// (0 for a bad item), the pair, bad.  What a kernel adds to max_n for it stays in the kernel: this is plain C++.
+struct SiteItem { uint32_t status; uint64_t n; uint32_t members; uint8_t a, b; bool bad; };
+SVJG_HD SiteItem site_item(const unsigned long long *counts, const uint8_t *present, bool dense, uint64_t S, uint64_t s, uint32_t n_slots, const uint32_t *slots,
+                           uint32_t min_support, const double *logs, const dd *logfact, uint32_t logfact_n,
+                           uint32_t *raw, int64_t *pl, uint8_t *gt, uint8_t *boundary) {
+    const double l_ok = logs[0];                         // (ahead of the gather: the kernels' LDS read travels beside the global ones)
+    SiteGather g;
+    site_gather(counts, dense ? nullptr : present, S, s, n_slots, slots, g);
+    if (g.bad) g.members = 0;
+    SiteMembers m;
+    if (dense) {
+        m.K = (uint32_t)__builtin_popcount(g.members); m.ref = 0;
+        SVJG_UNROLL
+        for (uint32_t j = 0; j < MAX_SITE_ALTS; ++j) { m.alt[j] = g.calt[j]; m.ref = g.cref[j] > m.ref ? g.cref[j] : m.ref; }     // (a bad item: K = 0, neither is looked at)
+    } else site_compact(g.members, g.cref, g.calt, m);
+    const bool bad = g.bad || (dense && m.K < 2), call = m.K >= 2;
+    raw[0] = call ? m.ref : 0;
+    SVJG_UNROLL
+    for (uint32_t j = 0; j < MAX_SITE_ALTS; ++j) raw[1 + j] = call ? m.alt[j] : 0;
+    GenoSite o{SITE_NO_CALL, SITE_NO_CALL, false, 0};
+    uint32_t st = GENO_ROW_OK;
+    if (call) st = geno_site(m.K, m.ref, m.alt, min_support, l_ok, logs[m.K], logs[8 + m.K], logfact, logfact_n, pl, o);
+    else {
+        SVJG_UNROLL
+        for (uint32_t i = 0; i < SITE_GENOTYPES; ++i) pl[i] = 0;
+    }
+    gt[0] = o.a; gt[1] = o.b; *boundary = o.near;
+    return SiteItem{st, o.n, g.members, o.a, o.b, bad};
+}
+
 // ---- cohort with an allele-frequency prior (k_cohort_prior) ----
 // The row's alt-allele frequency f is estimated from all its samples' likelihoods by EM under Hardy-Weinberg, each item is then called at
 // the maximum of likelihood x prior.  An item (r, s) takes part iff the cohort call genotyped it and c1 + c2 > 0.  Its weights: l_g = geno_lik,
@@ -638,15 +704,24 @@ inline PloidyLayout ploidy_layout(uint64_t n) {
     return L;
 }
 
-// svjg_genotype_sites: [ pl 224 | raw 28 | gt 2 | boundary 1 ] x n; in: the call's logarithms (site_log_table) and the sites' slots
-struct SitesLayout : LegSpan { uint64_t pl, raw, gt, boundary, logs, slots; };
-inline SitesLayout sites_layout(uint64_t n) {
-    SitesLayout L; uint64_t o = 0;
-    L.pl = o; o += n * 8 * SITE_GENOTYPES; L.raw = o; o += n * 4 * (MAX_SITE_ALTS + 1); L.gt = o; o += n * 2; L.boundary = o; o += n;
-    leg_span(L, o, SITE_LOGS * 8 + n * 4 * MAX_SITE_ALTS);
+// svjg_genotype_sites (S = 1, not cohort): [ pl 224 | raw 28 | gt 2 | boundary 1 ] x n_sites.  svjg_genotype_cohort_sites (cohort): [ pl 224 | raw 28 |
+// gt 2 | members 1 | boundary 1 ] x (n_sites * S items, site-major: 256 bytes an item), then the site words, 8-aligned, as the LAST output:
+// MAX_SITE_ALTS words a site, NS_j | AC_j << 32; the max_n pair lies right behind them, and ONE memset zeroes both in front of every launch (as
+// cohort_layout).  in, both: the call's logarithms (site_log_table) and the sites' slots.  A field the call does not have is 0.
+struct SitesLayout : LegSpan { uint64_t pl, raw, gt, members, boundary, site, logs, slots; };
+inline SitesLayout sites_layout(uint64_t n_sites, uint64_t S = 1, bool cohort = false) {
+    SitesLayout L{}; uint64_t o = 0; const uint64_t n = n_sites * S;
+    L.pl = o; o += n * 8 * SITE_GENOTYPES; L.raw = o; o += n * 4 * (MAX_SITE_ALTS + 1); L.gt = o; o += n * 2;
+    if (cohort) { L.members = o; o += n; }
+    L.boundary = o; o += n;
+    if (cohort) { o = (o + 7) & ~7ull; L.site = o; o += n_sites * 8 * MAX_SITE_ALTS; }
+    leg_span(L, o, SITE_LOGS * 8 + n_sites * 4 * MAX_SITE_ALTS);
     L.logs = L.in_at; L.slots = L.logs + SITE_LOGS * 8;
     return L;
 }
+// (the parent's cohort entry point, kept like cohort_ploidy_layout above: the harness of earlier tests, tests/cohort_sites_sim as it stood, compiles against it)
+using CohortSitesLayout = SitesLayout;
+inline SitesLayout cohort_sites_layout(uint64_t n_sites, uint64_t S) { return sites_layout(n_sites, S, true); }
 
 // svjg_genotype_cohort (max_ploidy 2, neither switch), _cohort_ploidy (per_item) and _cohort_prior (prior; per_item iff it has a ploidy array):
 // [ pl 8 (max_ploidy + 1) | raw 8 | gt 1 | flags 1 | boundary 1 ] x (n_rows * S items, row-major) — the PL stride is the CALL's, not MAX_PLOIDY + 1:
@@ -674,20 +749,6 @@ using CohortPloidyLayout = CohortLayout;
 using CohortPriorLayout = CohortLayout;
 inline CohortLayout cohort_ploidy_layout(uint64_t n_rows, uint64_t S, uint32_t max_ploidy) { return cohort_layout(n_rows, S, max_ploidy, true, false); }
 inline CohortLayout cohort_prior_layout(uint64_t n_rows, uint64_t S, uint32_t max_ploidy, bool per_item) { return cohort_layout(n_rows, S, max_ploidy, per_item, true); }
-
-// svjg_genotype_cohort_sites: [ pl 224 | raw 28 | gt 2 | members 1 | boundary 1 ] x (n_sites * S items, site-major: 256 bytes an item), then the
-// site words, 8-aligned, as the LAST output: MAX_SITE_ALTS words a site, NS_j | AC_j << 32.  The max_n pair lies right behind them, and ONE memset
-// zeroes both in front of every launch (as cohort_layout).  in: the call's logarithms (site_log_table) and the sites' candidate slots.
-struct CohortSitesLayout : LegSpan { uint64_t pl, raw, gt, members, boundary, site, logs, slots; };
-inline CohortSitesLayout cohort_sites_layout(uint64_t n_sites, uint64_t S) {
-    CohortSitesLayout L; uint64_t o = 0; const uint64_t n = n_sites * S;
-    L.pl = o; o += n * 8 * SITE_GENOTYPES; L.raw = o; o += n * 4 * (MAX_SITE_ALTS + 1); L.gt = o; o += n * 2; L.members = o; o += n; L.boundary = o; o += n;
-    o = (o + 7) & ~7ull;
-    L.site = o; o += n_sites * 8 * MAX_SITE_ALTS;
-    leg_span(L, o, SITE_LOGS * 8 + n_sites * 4 * MAX_SITE_ALTS);
-    L.logs = L.in_at; L.slots = L.logs + SITE_LOGS * 8;
-    return L;
-}
 
 // fused pass (svjg_set_rows, svjg_run_begin, svjg_run_end), per slot.  Host block (pinned, mapped into the device: the genotype kernel
 // writes its results straight into it — they cross PCIe as they are produced, no copy kernel competes with the next pass —): pl32, raw,

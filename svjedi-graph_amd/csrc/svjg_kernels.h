@@ -2294,9 +2294,9 @@ __global__ __launch_bounds__(TPB) void k_cohort_prior(CohortPriorArgs p) {
   }
 }
 
-// Insertions that share a position, genotyped together (svjg_geno.h: geno_site).  slots: MAX_SITE_ALTS count slots per site, the members
-// first, NONE32 behind them (the host has checked them: 2..6 members, no hole, in range, none twice).  Outputs per site: gt[2] = the pair
-// (a, b) or 0xFF, 0xFF; pl[SITE_GENOTYPES]; raw[1 + MAX_SITE_ALTS] = the ref maximum and the members' alt counts; boundary as k_genotype.
+// Insertions that share a position, genotyped together (svjg_geno.h: site_item = site_gather, site_compact, geno_site).  slots: MAX_SITE_ALTS count
+// slots per site, the members first, NONE32 behind them (the host has checked them: 2..6 members, no hole, in range, none twice).  Outputs per site:
+// gt[2] = the pair (a, b) or 0xFF, 0xFF; pl[SITE_GENOTYPES]; raw[1 + MAX_SITE_ALTS] = the ref maximum and the members' alt counts; boundary as k_genotype.
 struct GenoSitesArgs {
     const unsigned long long *counts; uint32_t n_slots;
     const uint32_t *slots; uint64_t n_sites; uint32_t min_support;
@@ -2306,76 +2306,52 @@ struct GenoSitesArgs {
     unsigned int *max_n;               // as GenoArgs::max_n
 };
 
-// One site per lane, sites in strides of the grid.  K differs from lane to lane, so the block stages the call's logarithms in LDS (128 bytes)
-// and each lane reads its three from there; the members' counts are gathered under a predicate into registers, and geno_site writes the PLs
-// straight to the site's place in global memory.
+// K differs from lane to lane: the block stages the call's logarithms in LDS (128 bytes), each lane reads its three from there (both site kernels)
+__device__ inline void stage_site_logs(double *tab, const double *logs) {
+  for (uint32_t i = threadIdx.x; i < SITE_LOGS; i += blockDim.x) tab[i] = logs[i];
+  __syncthreads();
+}
+
+// what an item tells the host through the max_n pair: the table is too short (the host grows it and runs the items again), or a bad slot
+__device__ inline void site_report(unsigned int *max_n, const SiteItem &t) {
+    if (t.bad) atomicOr(max_n + 1, 1u);
+    if (t.status == GENO_ROW_GROW) atomicMax(max_n, (uint32_t)t.n);
+}
+
+// One site per lane, sites in strides of the grid: site_item on the count vector (the matrix of one sample, every named slot a member)
 __global__ __launch_bounds__(TPB) void k_genotype_sites(GenoSitesArgs a) {
   __shared__ double logs[SITE_LOGS];
-  for (uint32_t i = threadIdx.x; i < SITE_LOGS; i += blockDim.x) logs[i] = a.logs[i];
-  __syncthreads();
-  constexpr uint32_t NRAW = MAX_SITE_ALTS + 1;
+  stage_site_logs(logs, a.logs);
   for (uint64_t s = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; s < a.n_sites; s += (uint64_t)gridDim.x * blockDim.x) {
-    uint32_t K = 0, ref = 0, alt[MAX_SITE_ALTS];
-    bool open = true, bad = false;
-#pragma unroll
-    for (uint32_t j = 0; j < MAX_SITE_ALTS; ++j) {
-        const uint32_t sl = a.slots[s * MAX_SITE_ALTS + j];
-        alt[j] = 0;
-        if (sl == NONE32) open = false;
-        else if (!open || sl >= a.n_slots) bad = true;           // (never, behind the host's checks; no count is read through such a slot)
-        else {
-            const unsigned long long c = a.counts[sl];
-            const uint32_t rf = (uint32_t)c;
-            alt[j] = (uint32_t)(c >> 32); ref = rf > ref ? rf : ref; ++K;
-        }
-    }
-    if (K < 2) bad = true;
-    a.raw[s * NRAW] = bad ? 0 : ref;
-#pragma unroll
-    for (uint32_t j = 0; j < MAX_SITE_ALTS; ++j) a.raw[s * NRAW + 1 + j] = bad ? 0 : alt[j];
-    a.boundary[s] = 0;
-    if (bad) {
-        atomicOr(a.max_n + 1, 1u);
-        a.gt[s * 2] = a.gt[s * 2 + 1] = SITE_NO_CALL;
-#pragma unroll
-        for (uint32_t i = 0; i < SITE_GENOTYPES; ++i) a.pl[s * SITE_GENOTYPES + i] = 0;
-        continue;
-    }
-    GenoSite o;
-    const uint32_t st = geno_site(K, ref, alt, a.min_support, logs[0], logs[K], logs[8 + K], a.logfact, a.logfact_n, a.pl + s * SITE_GENOTYPES, o);
-    if (st == GENO_ROW_GROW) atomicMax(a.max_n, (uint32_t)o.n);    // the log10(i!) table is too short: the host grows it and runs the sites again
-    a.gt[s * 2] = o.a; a.gt[s * 2 + 1] = o.b;
-    if (o.near) a.boundary[s] = 1;
+    const SiteItem t = site_item(a.counts, nullptr, true, 1, 0, a.n_slots, a.slots + s * MAX_SITE_ALTS, a.min_support, logs, a.logfact, a.logfact_n,
+                                 a.raw + s * (MAX_SITE_ALTS + 1), a.pl + s * SITE_GENOTYPES, a.gt + s * 2, a.boundary + s);
+    site_report(a.max_n, t);
   }
 }
 
 // ---- cohort calls for insertions that share a position (svjg_genotype_cohort_sites; svjg_geno.h) ----
-// slots: MAX_SITE_ALTS CANDIDATE slots of the cohort matrix per site, checked by the host as k_genotype_sites' are.  Outputs per item (k, s),
-// [n_sites][S] row-major: k_genotype_sites' four and members (bit j: candidate j is present for sample s); site: MAX_SITE_ALTS words a site, zeroed
-// by the host in front of every launch.
+// g: as for k_genotype_sites with counts = the matrix, n_slots = its slots, slots = MAX_SITE_ALTS CANDIDATE slots per site (checked by the host as
+// k_genotype_sites' are) and gt / pl / raw / boundary holding n_sites * n_samples items, [n_sites][S] row-major; members: bit j = candidate j is
+// present for sample s; site: MAX_SITE_ALTS words a site, zeroed by the host in front of every launch.
 struct GenoCohortSitesArgs {
-    const unsigned long long *cm; const uint8_t *present; uint32_t n_slots, n_samples;
-    const uint32_t *slots; uint64_t n_sites; uint32_t min_support;
-    const double *logs;                // site_log_table of the call's err: SITE_LOGS doubles
-    const dd *logfact; uint32_t logfact_n;
-    uint8_t *gt; int64_t *pl; uint32_t *raw; uint8_t *members; uint8_t *boundary;
+    GenoSitesArgs g;
+    const uint8_t *present;
+    uint32_t n_samples;
+    uint8_t *members;
     unsigned long long *site;
-    unsigned int *max_n;               // as GenoArgs::max_n
 };
 
 // Item i = k * S + s per lane, walked as k_genotype_cohort walks its items (the loop's bound is the WAVE's first item, every ballot is executed by
-// all 64 lanes on every trip, lanes beyond the last item vote "not called").  The lane gathers the candidates that are present for its sample
-// under a predicate, compacts them (site_compact: constant indices only) and runs geno_site on the K' it found — K' differs from lane to lane, so
-// the call's logarithms are staged in LDS as in k_genotype_sites; K' < 2: no site call, zeros.  The PLs go to pl + i * SITE_GENOTYPES, the item's
-// own 224 bytes (DESIGN 4.3 says why).  Site sums: three ballots per candidate (site_candidate_copies), the segment's first lane adds NS_j | AC_j << 32
-// to site[k][j] with one 64-bit atomic per candidate that has a call.
-// Compile remarks (ROCm 7.2.0, gfx950): 104 VGPRs, 87 SGPRs, none spilled, 0 bytes of scratch, 4 waves a SIMD, 128 bytes of LDS.
+// all 64 lanes on every trip, lanes beyond the last item vote "not called").  site_item on the candidates present for the lane's sample — K' differs
+// from lane to lane; K' < 2: no site call, zeros.  The PLs go to pl + i * SITE_GENOTYPES, the item's own 224 bytes (DESIGN 4.3 says why).  Site
+// sums: three ballots per candidate (site_candidate_copies), the segment's first lane adds NS_j | AC_j << 32 to site[k][j] with one 64-bit atomic
+// per candidate that has a call.  The two site kernels stay TWO bodies around site_item, as the two cohort kernels above.
+// Compile remarks (ROCm 7.2.0, gfx950): 104 VGPRs, 91 SGPRs, none spilled, 0 bytes of scratch, 4 waves a SIMD, 128 bytes of LDS.
 __global__ __launch_bounds__(TPB) void k_genotype_cohort_sites(GenoCohortSitesArgs p) {
   __shared__ double logs[SITE_LOGS];
-  for (uint32_t i = threadIdx.x; i < SITE_LOGS; i += blockDim.x) logs[i] = p.logs[i];
-  __syncthreads();
-  constexpr uint32_t NRAW = MAX_SITE_ALTS + 1;
-  const uint64_t S = p.n_samples, n_items = p.n_sites * S;
+  const GenoSitesArgs &a = p.g;
+  stage_site_logs(logs, a.logs);
+  const uint64_t S = p.n_samples, n_items = a.n_sites * S;
   const uint32_t lane = threadIdx.x & 63u;
   for (uint64_t w0 = (uint64_t)blockIdx.x * blockDim.x + (threadIdx.x - lane); w0 < n_items; w0 += (uint64_t)gridDim.x * blockDim.x) {
     const uint64_t i = w0 + lane;
@@ -2383,39 +2359,11 @@ __global__ __launch_bounds__(TPB) void k_genotype_cohort_sites(GenoCohortSitesAr
     uint32_t members = 0, ga = SITE_NO_CALL, gb = SITE_NO_CALL;
     if (i < n_items) {
         k = i / S; s = i - k * S;
-        uint32_t cref[MAX_SITE_ALTS], calt[MAX_SITE_ALTS];
-        bool open = true, bad = false;
-#pragma unroll
-        for (uint32_t j = 0; j < MAX_SITE_ALTS; ++j) {
-            const uint32_t sl = p.slots[k * MAX_SITE_ALTS + j];
-            cref[j] = calt[j] = 0;
-            if (sl == NONE32) open = false;
-            else if (!open || sl >= p.n_slots) bad = true;         // (never, behind the host's checks; nothing is read through such a slot)
-            else {
-                const uint64_t at = (uint64_t)sl * S + s;
-                if (p.present[at]) {
-                    const unsigned long long c = p.cm[at];
-                    cref[j] = (uint32_t)c; calt[j] = (uint32_t)(c >> 32); members |= 1u << j;
-                }
-            }
-        }
-        if (bad) { atomicOr(p.max_n + 1, 1u); members = 0; }
-        SiteMembers m;
-        site_compact(members, cref, calt, m);
-        const bool call = m.K >= 2;
-        p.raw[i * NRAW] = call ? m.ref : 0;
-#pragma unroll
-        for (uint32_t j = 0; j < MAX_SITE_ALTS; ++j) p.raw[i * NRAW + 1 + j] = call ? m.alt[j] : 0;
-        GenoSite o{SITE_NO_CALL, SITE_NO_CALL, false, 0};
-        if (call) {
-            const uint32_t st = geno_site(m.K, m.ref, m.alt, p.min_support, logs[0], logs[m.K], logs[8 + m.K], p.logfact, p.logfact_n, p.pl + i * SITE_GENOTYPES, o);
-            if (st == GENO_ROW_GROW) atomicMax(p.max_n, (uint32_t)o.n);    // the table is too short: the host grows it and runs the items again
-        } else {
-#pragma unroll
-            for (uint32_t g = 0; g < SITE_GENOTYPES; ++g) p.pl[i * SITE_GENOTYPES + g] = 0;
-        }
-        p.gt[i * 2] = o.a; p.gt[i * 2 + 1] = o.b; p.members[i] = (uint8_t)members; p.boundary[i] = o.near;
-        ga = o.a; gb = o.b;
+        const SiteItem t = site_item(a.counts, p.present, false, S, s, a.n_slots, a.slots + k * MAX_SITE_ALTS, a.min_support, logs, a.logfact, a.logfact_n,
+                                     a.raw + i * (MAX_SITE_ALTS + 1), a.pl + i * SITE_GENOTYPES, a.gt + i * 2, a.boundary + i);
+        site_report(a.max_n, t);
+        members = t.members; ga = t.a; gb = t.b;
+        p.members[i] = (uint8_t)members;
     }
     SiteBallots b;
 #pragma unroll

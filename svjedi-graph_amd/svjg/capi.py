@@ -511,17 +511,22 @@ class Context:
         """Insertions that share a position, genotyped together (svjg_genotype_sites).  slots[n, 6]: the members' count slots first, 0xFFFFFFFF
         behind them.  -> (gt[n, 2] = the pair (a, b) or 0xFF, 0xFF, pl[n, 28] in VCF order then zeros, raw[n, 7] = ref maximum and alt_1..alt_6,
         boundary = the sites to recompute with svjg.genotype.exact_pl_site)"""
+        return self._sites_call("svjg_genotype_sites", slots, min_support, err)
+
+    def _sites_call(self, name, slots, min_support, err):
+        """The two site calls: the slot matrix's check, the output arrays (per site, or per (site, sample) item with members and the site words
+        for svjg_genotype_cohort_sites) and the call of library function `name`"""
         slots = np.ascontiguousarray(slots, dtype=np.uint32)
         if slots.ndim != 2 or slots.shape[1] != MAX_SITE_ALTS:
             raise SvjgError("slots: %d per site" % MAX_SITE_ALTS)
         n = len(slots)
-        gt = np.empty((n, 2), dtype=np.uint8)
-        pl = np.empty((n, SITE_GENOTYPES), dtype=np.int64)
-        raw = np.empty((n, MAX_SITE_ALTS + 1), dtype=np.uint32)
-        boundary = np.empty(n, dtype=np.uint8)
-        self._chk(self.lib.svjg_genotype_sites(self.h, slots.ctypes.data, n, min_support, float(err), gt.ctypes.data, pl.ctypes.data,
-                                               raw.ctypes.data, boundary.ctypes.data))
-        return gt, pl, raw, boundary
+        cohort = name == "svjg_genotype_cohort_sites"
+        at = (n, getattr(self, "_cohort", (0, 0))[0]) if cohort else (n,)
+        out = (np.empty(at + (2,), np.uint8), np.empty(at + (SITE_GENOTYPES,), np.int64), np.empty(at + (MAX_SITE_ALTS + 1,), np.uint32), np.empty(at, np.uint8))
+        if cohort:
+            out = out[:3] + (np.empty(at, np.uint8), out[3], np.empty((n, MAX_SITE_ALTS, 2), np.uint32))
+        self._chk(getattr(self.lib, name)(self.h, slots.ctypes.data, n, min_support, float(err), *(a.ctypes.data for a in out)))
+        return out
 
     def cohort_alloc(self, n_samples, n_slots):
         """a zeroed count matrix of n_samples x n_slots with its presence bytes (svjg_cohort_alloc); a second call replaces it"""
@@ -598,15 +603,7 @@ class Context:
         site first, 0xFFFFFFFF behind them; sample s's site = the candidates present for s.  -> (gt[n, S, 2] = the pair or 0xFF, 0xFF, pl[n, S, 28],
         raw[n, S, 7], members[n, S] = bit j: candidate j took part (fewer than two: no site call), boundary[n, S] = the items to recompute with
         svjg.genotype.exact_pl_site, site[n, 6, 2] = NS_j and AC_j of every candidate over the items with a site call)"""
-        slots = np.ascontiguousarray(slots, dtype=np.uint32)
-        if slots.ndim != 2 or slots.shape[1] != MAX_SITE_ALTS:
-            raise SvjgError("slots: %d per site" % MAX_SITE_ALTS)
-        n = len(slots)
-        S = getattr(self, "_cohort", (0, 0))[0]
-        out = (np.empty((n, S, 2), np.uint8), np.empty((n, S, SITE_GENOTYPES), np.int64), np.empty((n, S, MAX_SITE_ALTS + 1), np.uint32),
-               np.empty((n, S), np.uint8), np.empty((n, S), np.uint8), np.empty((n, MAX_SITE_ALTS, 2), np.uint32))
-        self._chk(self.lib.svjg_genotype_cohort_sites(self.h, slots.ctypes.data, n, min_support, float(err), *(a.ctypes.data for a in out)))
-        return out
+        return self._sites_call("svjg_genotype_cohort_sites", slots, min_support, err)
 
     def set_rows(self, sv_type, slot, ok):
         """the VCF rows' input arrays of genotype(), left on the device for run_resident()"""

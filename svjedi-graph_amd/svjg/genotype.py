@@ -436,17 +436,51 @@ def form_sites(rows, done):
     return sites, skipped
 
 
+def _site_slots(rows, sites):
+    """the slot matrix of a site call from form_sites' lists: [n, 6], a site's rows' slots first, NONE behind them"""
+    slots = np.full((len(sites), MAX_SITE_ALTS), NONE, dtype=np.uint32)
+    for k, m in enumerate(sites):
+        slots[k, :len(m)] = rows.slot[m]
+    return slots
+
+
+def _report_skipped(skipped):
+    import sys
+    for chrom, pos, count in skipped:
+        print("--joint-ins: %s:%s has %d insertions, more than %d: they keep their independent calls" % (chrom, pos, count, MAX_SITE_ALTS), file=sys.stderr)
+
+
+def recompute_flagged_sites(s_pl, s_raw, boundary, k_of, err):
+    """recompute_flagged for the site calls: the flagged items get exact_pl_site's integers on their own K' = k_of[item] members, in place.
+    boundary, k_of: one entry per item, [n] or [n, S] in a cohort; s_pl, s_raw: that shape + [28] and + [7].  -> the number of flagged items"""
+    idx = np.argwhere(np.asarray(boundary) != 0)
+    for at in map(tuple, idx):
+        K = int(k_of[at])
+        s_pl[at][:(K + 1) * (K + 2) // 2] = exact_pl_site(int(s_raw[at][0]), [int(x) for x in s_raw[at][1:K + 1]], err)
+    return len(idx)
+
+
+@functools.lru_cache(maxsize=None)
+def _site_copy_sets(K, i):
+    """the genotype indices of a site of K members with 0, 1 and 2 copies of allele i (the projection's three groups)"""
+    return tuple(np.array([k for k, (x, y) in enumerate(site_genotypes(K)) if (x == i) + (y == i) == n], dtype=np.int64) for n in range(3))
+
+
 def project_site(K, i, gt_pair, site_pl):
     """member i (1..K) of a site called gt_pair = (a, b) or (0xFF, 0xFF) -> (its copies g = 0..2, or 3 for a no-call; [PL_0, PL_1, PL_2]: the
-    smallest site PL over the genotypes with exactly that many copies of allele i)"""
+    smallest site PL over the genotypes with exactly that many copies of allele i).  The scalar face of project_cohort_sites."""
     a, b = int(gt_pair[0]), int(gt_pair[1])
-    g = 3 if a == NO_CALL else (a == i) + (b == i)
-    pl = [None, None, None]
-    for k, (x, y) in enumerate(site_genotypes(K)):
-        n = (x == i) + (y == i)
-        v = int(site_pl[k])
-        pl[n] = v if pl[n] is None else min(pl[n], v)
-    return g, pl
+    site_pl = np.asarray(site_pl)
+    return 3 if a == NO_CALL else (a == i) + (b == i), [int(site_pl[idx].min()) for idx in _site_copy_sets(K, i)]
+
+
+def _member_column(svtype_code, g, pl3, ref, alt, sgt, sal):
+    """a member's sample column: GT and PL the site call's projection, DP and AD the row's own, then the site call's text and the allele number"""
+    return "%s:%s:%d" % (sample_column(svtype_code, 2, NO_CALL if g == 3 else g, pl3, ref, alt, True), sgt, sal)
+
+
+def _sgt_text(a, b):
+    return "./." if a == NO_CALL else "%d/%d" % (a, b)
 
 
 def write_vcf_joint(out_path, rows, gt, pl, raw, done, member):
@@ -456,17 +490,14 @@ def write_vcf_joint(out_path, rows, gt, pl, raw, done, member):
     def columns(v):
         if not (done[v] and v in member):
             return plain(v)
-        g, p, sgt, sal = member[v]
-        col = sample_column(int(rows.sv_type[v]), 2, NO_CALL if g == 3 else g, p, int(raw[v, 0]), int(raw[v, 1]), True)
-        return ["GT:DP:AD:PL:SGT:SAL", "%s:%s:%d" % (col, sgt, sal)]
+        return ["GT:DP:AD:PL:SGT:SAL", _member_column(int(rows.sv_type[v]), *member[v][:2], int(raw[v, 0]), int(raw[v, 1]), *member[v][2:])]
     _write_rows(out_path, rows, FORMAT_HEADER.replace(_PL_LINE, _PL_LINE + SITE_FORMAT_LINES), columns)
     return n_done[0]
 
 
 def genotype_with_counts_joint(ctx, vcf_path, slot_of, out_path, min_support, err, slot_is_presence):
     """genotype_with_counts with --joint-ins: the Python rows, the ordinary diploid call on all of them, then ONE svjg_genotype_sites call
-    over the sites of form_sites; the members' GT and PL become the site call's projection (project_site), DP and AD stay the row's own"""
-    import sys
+    over the sites of form_sites; the members' GT and PL become the site call's projection (project_cohort_sites at S = 1), DP and AD stay the row's own"""
     if not isinstance(slot_of, dict):
         slot_of = {k: i for i, k in enumerate(slot_of)}
     rows = VcfRows(vcf_path, slot_of, slot_is_presence)
@@ -476,24 +507,17 @@ def genotype_with_counts_joint(ctx, vcf_path, slot_of, out_path, min_support, er
         raise ValueError("math domain error")
     pl, _ = apply_boundary_guard(ctx, rows, pl, raw, done, err)
     sites, skipped = form_sites(rows, done)
-    for chrom, pos, count in skipped:
-        print("--joint-ins: %s:%s has %d insertions, more than %d: they keep their independent calls" % (chrom, pos, count, MAX_SITE_ALTS), file=sys.stderr)
+    _report_skipped(skipped)
     member = {}
     if sites:
-        slots = np.full((len(sites), MAX_SITE_ALTS), NONE, dtype=np.uint32)
+        s_gt, s_pl, s_raw, s_boundary = ctx.genotype_sites(_site_slots(rows, sites), min_support, err)
+        k_of, s_pl = np.array([len(m) for m in sites]), np.array(s_pl, dtype=np.int64)
+        recompute_flagged_sites(s_pl, s_raw, s_boundary, k_of, err)
+        _, g, pl3, _ = project_cohort_sites(np.asarray(s_gt)[:, None], s_pl[:, None], ((1 << k_of) - 1)[:, None])      # (every named slot is a member)
         for k, m in enumerate(sites):
-            slots[k, :len(m)] = rows.slot[m]
-        s_gt, s_pl, s_raw, s_boundary = ctx.genotype_sites(slots, min_support, err)
-        for k, m in enumerate(sites):
-            K = len(m)
-            spl = s_pl[k, :(K + 1) * (K + 2) // 2]
-            if s_boundary[k]:
-                spl = exact_pl_site(int(s_raw[k, 0]), [int(x) for x in s_raw[k, 1:K + 1]], err)
-            a, b = int(s_gt[k, 0]), int(s_gt[k, 1])
-            sgt = "./." if a == NO_CALL else "%d/%d" % (a, b)
-            for i, r in enumerate(m, 1):
-                g, p = project_site(K, i, (a, b), spl)
-                member[r] = (g, p, sgt, i)
+            sgt = _sgt_text(int(s_gt[k, 0]), int(s_gt[k, 1]))
+            for j, r in enumerate(m):
+                member[r] = (int(g[k, 0, j]), pl3[k, 0, j].tolist(), sgt, j + 1)
     return write_vcf_joint(out_path, rows, gt, pl, raw, done, member)
 
 
@@ -587,14 +611,8 @@ def _joint_columns(rows, raw, plain, joint):
             return cols
         covered, g, p3, a, b, sal = (x.tolist() for x in joint[v])
         t = int(rows.sv_type[v])
-        out = ["GT:DP:AD:PL:SGT:SAL"]
-        for s, col in enumerate(cols[1:]):
-            if not covered[s]:
-                out.append(col + ":.:.")
-                continue
-            own = sample_column(t, 2, NO_CALL if g[s] == 3 else g[s], p3[s], int(raw[v, s, 0]), int(raw[v, s, 1]), True)
-            out.append("%s:%s:%d" % (own, "./." if a[s] == NO_CALL else "%d/%d" % (a[s], b[s]), sal[s]))
-        return out
+        return ["GT:DP:AD:PL:SGT:SAL"] + [_member_column(t, g[s], p3[s], int(raw[v, s, 0]), int(raw[v, s, 1]), _sgt_text(a[s], b[s]), sal[s]) if covered[s]
+                                          else col + ":.:." for s, col in enumerate(cols[1:])]
     return columns
 
 
@@ -762,12 +780,6 @@ def cohort_sites_chunk(n_samples):
     return max(1, COHORT_CALL_BYTES // (COHORT_SITES_ITEM_BYTES * max(1, int(n_samples)) + COHORT_SITES_SITE_BYTES))
 
 
-@functools.lru_cache(maxsize=None)
-def _site_copy_sets(K, i):
-    """the genotype indices of a site of K members with 0, 1 and 2 copies of allele i (project_site's three groups)"""
-    return tuple(np.array([k for k, (x, y) in enumerate(site_genotypes(K)) if (x == i) + (y == i) == n], dtype=np.int64) for n in range(3))
-
-
 def project_cohort_sites(s_gt, s_pl, members):
     """project_site for every (site, sample, candidate) at once.  s_gt[n, S, 2], s_pl[n, S, 28], members[n, S] as svjg_genotype_cohort_sites returns
     them -> (covered[n, S, 6]: the candidate is a member of the sample's site, K' >= 2; g[n, S, 6]: its copies 0..2, 3 = the site has no call;
@@ -801,24 +813,18 @@ def cohort_joint_sites(ctx, rows, gt, site, min_support, err, step=None):
     svjg_genotype_cohort_sites call over them (chunks of `step` sites, None: what fits 1 GiB), the flagged items recomputed with their own K'
     (exact_pl_site), the projection.  -> (site with the candidate rows' NS and AC replaced: the kernel's sums over the covered samples plus the
     independent calls of the others; joint: row -> (covered[S], g[S], pl3[S, 3], a[S], b[S], sal[S]) for the rows covered in at least one sample)"""
-    import sys
     min_support, call_err, _ = _call_args(min_support, err)
     sites, skipped = form_sites(rows, ((rows.ok & 1) != 0) & (rows.slot != NONE))
-    for chrom, pos, count in skipped:
-        print("--joint-ins: %s:%s has %d insertions, more than %d: they keep their independent calls" % (chrom, pos, count, MAX_SITE_ALTS), file=sys.stderr)
+    _report_skipped(skipped)
     site, joint = np.array(site), {}
     if not sites:
         return site, joint
-    slots = np.full((len(sites), MAX_SITE_ALTS), NONE, dtype=np.uint32)
-    for k, m in enumerate(sites):
-        slots[k, :len(m)] = rows.slot[m]
+    slots = _site_slots(rows, sites)
     if step is None:
         step = cohort_sites_chunk(np.shape(gt)[1])
     parts = [ctx.genotype_cohort_sites(slots[at:at + step], min_support, call_err) for at in range(0, len(sites), int(step))]
     s_gt, s_pl, s_raw, members, boundary, s_site = (np.concatenate([p[k] for p in parts]) for k in range(6))
-    for k, s in map(tuple, np.argwhere(boundary != 0)):
-        K = bin(int(members[k, s])).count("1")
-        s_pl[k, s, :(K + 1) * (K + 2) // 2] = exact_pl_site(int(s_raw[k, s, 0]), [int(x) for x in s_raw[k, s, 1:K + 1]], err)
+    recompute_flagged_sites(s_pl, s_raw, boundary, ((members[..., None] >> np.arange(MAX_SITE_ALTS, dtype=np.uint8)) & 1).sum(axis=-1), err)
     covered, g, pl3, sal = project_cohort_sites(s_gt, s_pl, members)
     k_of = np.repeat(np.arange(len(sites)), [len(m) for m in sites])
     j_of = np.concatenate([np.arange(len(m)) for m in sites])

@@ -1,5 +1,5 @@
 """Cohort calls for insertions that share a position (--cohort LIST --joint-ins), on the CPU: the plain pieces of the device leg compiled with
-g++ (tests/cohort_sites_sim: the member compaction, the site sums under cohort_segment's masks, the layout, and geno_site behind the compaction
+g++ (tests/site_sim: the member compaction, the site sums under cohort_segment's masks, the layout, and geno_site behind the compaction
 against tests/site_model.py on the present members); the host flow with a stand-in context that answers from the models — grouping, the ONE
 sites call, every column against the single-sample --joint-ins run of that sample, the site tags, the header; the golden cohort; the refusals."""
 import json
@@ -12,7 +12,7 @@ import pytest
 
 from tests import ploidy_model as PM
 from tests import site_model as SM
-from tests.cohort_sites_sim import sim
+from tests.site_sim import sim
 from tests.test_joint_ins import _ROWS, KEYS, COUNTS, VCF_TEXT, ModelCtx
 
 NO_CALL = 0xFF
@@ -84,7 +84,7 @@ def test_site_sums_from_the_leaders_against_brute_force(S):
 def test_harness_under_the_sanitizers():
     """the same pieces as a stand-alone program with its own main under -fsanitize=address,undefined (nothing is loaded into Python)"""
     p = subprocess.run([sim.build_main()], capture_output=True, text=True)
-    assert p.returncode == 0 and p.stdout.startswith("cohort_sites_sim ok") and not p.stderr, (p.stdout, p.stderr)
+    assert p.returncode == 0 and p.stdout.startswith("site_sim ok") and not p.stderr, (p.stdout, p.stderr)
 
 
 @pytest.mark.parametrize("n_sites, S", [(0, 1), (1, 1), (1, 65), (257, 3), (1000, 130)])

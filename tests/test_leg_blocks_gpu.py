@@ -1,6 +1,6 @@
-"""The six step-by-step genotype calls share one host leg (svjg_capi.hip: genotype_leg; the three cohort calls one more, cohort_call) and keep a
-block each (svjg_ctx::leg[]): run on ONE context in either order, every call returns the bytes it returns on a context of its own, whichever
-calls ran in between, and a view of the diploid call's pinned block outlives the other five.  Needs an MI355X: run with -m gpu."""
+"""The seven step-by-step genotype calls share one host leg (svjg_capi.hip: genotype_leg; the three cohort calls one more, cohort_call, the two
+site calls another, sites_call) and keep a block each (svjg_ctx::leg[]): run on ONE context in either order, every call returns the bytes it
+returns on a context of its own, whichever calls ran in between, and a view of the diploid call's pinned block outlives the other six.  Needs an MI355X: run with -m gpu."""
 import numpy as np
 import pytest
 
@@ -9,7 +9,7 @@ pytestmark = pytest.mark.gpu
 NONE = 0xFFFFFFFF
 R, S, N_SLOTS = 65, 3, 90              # two waves of rows with a ragged end; three samples; the sites' members lie behind the rows' slots
 MS, ERR = 3, 5e-5
-CALLS = ("rows", "ploidy", "sites", "cohort", "cohort_ploidy", "cohort_prior")
+CALLS = ("rows", "ploidy", "sites", "cohort", "cohort_ploidy", "cohort_prior", "cohort_sites")
 
 
 def _case():
@@ -61,6 +61,8 @@ def _call(ctx, c, which, view=False):
         return ctx.genotype_ploidy(c["t"], c["slot"], c["ok"], c["ploidy"], MS, ERR)
     if which == "sites":
         return ctx.genotype_sites(c["sites"], MS, ERR)
+    if which == "cohort_sites":
+        return ctx.genotype_cohort_sites(c["sites"], MS, ERR)              # (the same five sites, as candidates in the matrix)
     if which == "cohort_ploidy":
         return ctx.genotype_cohort_ploidy(c["t"], c["slot"], c["ok"], c["item_ploidy"], 8, MS, ERR)
     if which == "cohort_prior":
@@ -88,18 +90,19 @@ def alone(case):
             _load(ctx, case)
             assert ctx.logfact_entries() == 0
             want[which] = _bytes(_call(ctx, case, which))
-            assert (ctx.logfact_entries() > 65536) == which.startswith("cohort")   # the deep item is the cohort-matrix calls' alone
+            assert (ctx.logfact_entries() > 65536) == (which in ("cohort", "cohort_ploidy", "cohort_prior"))   # the deep item is a ROW's, in the matrix alone
         finally:
             ctx.close()
     gt, pl, raw, done, boundary, site = (np.frombuffer(b, dt) for b, dt in zip(want["cohort"], (np.uint8, np.int64, np.uint32, np.uint8, np.uint8, np.uint32)))
     item = case["deep"] * S + 1
     assert done[item] == 1 and raw[2 * item: 2 * item + 2].tolist() == [40_000, 40_000] and pl[3 * item: 3 * item + 3].any()
     assert any(want["rows"][0]) and any(want["ploidy"][1]) and any(want["sites"][1]) and any(want["cohort_ploidy"][1]) and any(want["cohort_prior"][1])
+    assert any(want["cohort_sites"][1]) and any(want["cohort_sites"][5])      # PLs and site words
     return want
 
 
-@pytest.mark.parametrize("order", [("rows", "ploidy", "sites", "cohort", "cohort_ploidy", "cohort_prior", "rows"),
-                                   ("rows", "cohort_prior", "cohort", "sites", "cohort_ploidy", "ploidy", "rows")])
+@pytest.mark.parametrize("order", [("rows", "ploidy", "sites", "cohort", "cohort_sites", "cohort_ploidy", "cohort_prior", "rows"),
+                                   ("rows", "cohort_sites", "cohort_prior", "cohort", "sites", "cohort_ploidy", "ploidy", "rows")])
 def test_every_call_in_a_block_of_its_own(case, alone, order):
     from svjg import capi
     ctx = capi.Context(0)
