@@ -108,7 +108,9 @@ def fused_two_sum(x1, y1, x2, y2):
     """What k_genotype's device code computed for two_sum(x1 * y1, x2 * y2) while geno_row was compiled with fused multiply-adds (before
     it carried `fp contract(off)`): only the SECOND product is rounded to a double, the first one enters every operation exactly.
     The five instructions in Fraction, float() for each rounding, then the add of the two tail halves -> (hi, lo).  Used by the
-    generator of lik_products.npz (tests/golden/make_golden.py) to find rows on which that differs from the plain C++; no test calls it."""
+    generators of lik_products.npz (tests/golden/make_golden.py) and site_products.npz (tests/golden/make_site_products.py) to find items on
+    which that differs from the plain C++, and by the CPU tests that count such items in every set the device tests run
+    (tests/products_items.py: sensitive_*)."""
     from fractions import Fraction
     p1 = Fraction(x1) * Fraction(y1)
     p2 = Fraction(x2) * Fraction(y2)
@@ -118,6 +120,24 @@ def fused_two_sum(x1, y1, x2, y2):
     t2 = float(p2 - Fraction(bb))                        # v_fma_f64   fl(x2 * y2 - bb)
     t1 = float(p1 - Fraction(s - bb))                    # v_fma_f64   fl(x1 * y1 - fl(s - bb))
     return s, t1 + t2
+
+
+def fused_two_sum_second(x1, y1, x2, y2):
+    """The other order a compiler that fuses wherever it can may choose for two_sum(x1 * y1, x2 * y2): in s = a + b the SECOND product is the
+    one multiplied inside the instruction and the first its rounded addend; every other operation reads its product exactly, as in
+    fused_two_sum (there s is fl(x1 * y1 + fl(x2 * y2)), and the other four lines are the same).  -> (hi, lo)"""
+    from fractions import Fraction
+    p1 = Fraction(x1) * Fraction(y1)
+    p2 = Fraction(x2) * Fraction(y2)
+    a = float(p1)                                        # v_mul_f64   a  = fl(x1 * y1)
+    s = float(Fraction(a) + p2)                          # v_fmac_f64  s  = fl(a + x2 * y2)
+    bb = float(Fraction(s) - p1)                         # v_fma_f64   bb = fl(s - x1 * y1)
+    t2 = float(p2 - Fraction(bb))                        # v_fma_f64   fl(x2 * y2 - bb)
+    t1 = float(p1 - Fraction(s - bb))                    # v_fma_f64   fl(x1 * y1 - fl(s - bb))
+    return s, t1 + t2
+
+
+FUSED_ORDERS = {"first": fused_two_sum, "second": fused_two_sum_second}      # the product that is multiplied inside s = a + b
 
 
 def pl_fractions(svtype_code, ref, alt, e):

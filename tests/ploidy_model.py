@@ -69,6 +69,28 @@ def genotype(svtype_code, ref, alt, P, min_support, e):
         return gt, [int(-10 * (x + comb)) for x in lik]
 
 
+def fused(svtype_code, ref, alt, P, min_support, e, order):
+    """(gt, PLs) as geno_row_pairs would give them if the compiler fused one product of every pair into geno_lik's two_sum
+    (tests/lik_model.py: FUSED_ORDERS[order]): the g whose value (hi + lo, the one product at 2 g = P) alone is largest; the double-double
+    steps behind the sums are taken as exact, the sums are not rounded to 28 digits"""
+    from fractions import Fraction
+    two_sum = lik_model.FUSED_ORDERS[order]
+    c1, c2, rc1, rc2 = normalised(svtype_code, ref, alt)
+    lik = []
+    for g in range(P + 1):
+        lr, la, single = log_pair(P, g, e)
+        if single:
+            lik.append(Fraction((c1 + c2) * lr))
+        else:
+            hi, lo = two_sum(float(c1), lr, float(c2), la)
+            lik.append(Fraction(hi) + Fraction(lo))
+    top = max(lik)
+    best = [g for g, x in enumerate(lik) if x == top]
+    gt = best[0] if len(best) == 1 and c1 + c2 >= min_support else None
+    comb = Fraction(_log10_comb(rc1 + rc2, rc1))
+    return gt, [int(-10 * (x + comb)) for x in lik]
+
+
 def pl_fractions(svtype_code, ref, alt, P, e):
     """(distance of each -10 * (lik_g + comb) from the nearest integer at 80 digits, log10 comb as a float)"""
     _, _, rc1, rc2 = normalised(svtype_code, ref, alt)

@@ -82,6 +82,28 @@ def genotype(ref, alts, min_support, e):
         return call, [int(-10 * (x + T)) for x in lik]
 
 
+def factors(ref, alts, e):
+    """per genotype: (own, L_own, rest, L_x), the factors of products()' two doubles"""
+    K = len(alts)
+    c, _ = counts(ref, alts)
+    N = sum(c)
+    l_ok, l_x, l_he = logs(K, e)
+    return [(c[a], l_ok, N - c[a], l_x) if a == b else (c[a] + c[b], l_he, N - c[a] - c[b], l_x) for a, b in genotypes(K)]
+
+
+def fused_pls(ref, alts, e, order):
+    """the PLs geno_site would give for a site whose chain term T is 0 if the compiler fused one product of every pair into two_sum
+    (tests/lik_model.py: FUSED_ORDERS[order]); the double-double steps behind the sum are taken as exact"""
+    from fractions import Fraction
+    assert not any(chain(ref, alts))
+    fused = lik_model.FUSED_ORDERS[order]
+    out = []
+    for own, l_own, rest, l_x in factors(ref, alts, e):
+        hi, lo = fused(float(own), l_own, float(rest), l_x)
+        out.append(int(-10 * (Fraction(hi) + Fraction(lo))))
+    return out
+
+
 def pl_fractions(ref, alts, e):
     """(distance of each -10 * (lik + T) from the nearest integer at 80 digits, whether T is non-zero)"""
     with mpmath.workdps(lik_model.DPS):

@@ -10,6 +10,7 @@ import sys
 import numpy as np
 import pytest
 
+from tests import products_items as PI
 from tests import site_model as SM
 
 pytestmark = pytest.mark.gpu
@@ -44,12 +45,7 @@ def _cohort(S, n_sites=N_SITES, seed=0, presence=0.75):
     return slots, counts, rng.random((S, at)) < presence
 
 
-def _load(c, counts, present):
-    S, n_slots = present.shape
-    c.cohort_alloc(S, n_slots)
-    for s in range(S):
-        sl = np.flatnonzero(present[s]).astype(np.uint32)
-        c.cohort_set_counts(s, sl, counts[s, sl])
+_load = PI.load_cohort                          # (shared with tests/test_genotype_products_gpu.py)
 
 
 def _members(slots, present):
@@ -59,13 +55,7 @@ def _members(slots, present):
     return (bits << np.arange(6)).sum(axis=2).astype(np.uint8).T
 
 
-def _brute_site(gt, members):
-    """site[n, 6, 2] = NS_j, AC_j from the items' calls"""
-    bits = (members[..., None] >> np.arange(6, dtype=np.uint8)) & 1
-    sal = np.cumsum(bits, axis=-1) * bits
-    called = (gt[..., 0] != NO_CALL)[..., None] & (bits != 0)
-    copies = (gt[..., 0, None] == sal).astype(np.int64) + (gt[..., 1, None] == sal)
-    return np.stack([called.sum(axis=1), np.where(called, copies, 0).sum(axis=1)], axis=2).astype(np.uint32)
+_brute_site = PI.brute_site                     # site[n, 6, 2] = NS_j, AC_j from the items' calls
 
 
 def _single_sample(c, slots, counts_s, present_s):

@@ -1,14 +1,23 @@
-"""The four genotype kernels on the device where the ROUNDING of each product c * L decides the answer (tests/golden/lik/lik_products.npz,
-tests/products_items.py): deep one-sided rows whose PL turns by one if a product enters its sum unrounded (a fused multiply-add), rows at
-err = 0.5 whose GT the roundings alone decide, ties l0 == l2.  k_genotype and k_genotype_cohort against the reference's own answers,
-k_genotype_ploidy and k_genotype_sites against the models the CPU stand-ins are held to (tests/test_ploidy.py, tests/test_joint_ins.py), on
-the same items.  The CPU stand-ins cannot speak for the device here: g++ on x86-64 never fuses.  Needs an MI355X: run with -m gpu.
+"""The six bit-exact genotype kernels on the device where the ROUNDING of each product c * L decides the answer (tests/golden/lik/lik_products.npz,
+tests/golden/lik/site_products.npz, tests/products_items.py): deep one-sided rows whose PL turns by one if a product enters its sum unrounded
+(a fused multiply-add), rows at err = 0.5 whose GT the roundings alone decide, ties l0 == l2, and sites found by search on which a PL turns.
+k_genotype and k_genotype_cohort against the reference's own answers, k_genotype_ploidy, k_genotype_cohort_ploidy, k_genotype_sites and
+k_genotype_cohort_sites against the models the CPU stand-ins are held to (tests/test_ploidy.py, tests/test_joint_ins.py), on the same
+items.  The CPU stand-ins cannot speak for the device here: g++ on x86-64 never fuses; what the CPU tests do assert is that every set has
+items a fused product would turn, by an exact emulation of the fused instructions in both orders (PI.sensitive_rows, PI.sensitive_sites).
+By that emulation 18 of the 1 392 "one_sided" sites change a PL, every "searched" site does, 26 or 27 per K and order; of the 2 077 "half"
+sites none was red even on a library built without the pragmas (at e = 0.5 the three site logarithms differ and nothing is near a tie).
+k_cohort_prior stays out: it is not bit-exact but held to the 60-digit model within EM_F_BOUND, on deep one-sided items its weights underflow to 0, at the fixture's small counts a fused product moves f by less than that bound, and its PL / raw / genotyped / boundary
+arrays are compared array for array with the two first kernels (tests/test_cohort_prior_gpu.py).  Needs an MI355X: run with -m gpu.
 
 On one MI355X (2026-10-19, ROCm 7.2.0; profiles/r12/experiments/geno_row_products.txt has the runs), rows that differ from the reference while
 geno_row was compiled with fused multiply-adds: 5 788 GTs and 40 PLs in test_rows_kernel (PL0 of (INV, 0, 3 000 280 009): 129042943140 for
 129042943141), the same items in test_cohort_kernel, all 40 rows of the fresh context; with `fp contract(off)` alone 1 236 GTs remained (here and
 at ploidy 2, 4, 8), where the reference's rounding of a SUM to 28 digits decides against the one product it never rounds (svjg_geno.h:
-dec28_round_dir)."""
+dec28_round_dir).  A later run (2026-10-20, ROCm 7.2, profiles/r19/experiments/cohort_products.txt) against a library without the three pragmas of
+svjg_geno.h: 26 of these 28 tests red — all but test_sites_kernel[half] and test_ploidy_kernel[half-1], where the emulation predicts no
+change either —, every searched site, every cohort site item and 37 / 112 one-sided cohort-ploidy items (S = 1 / 3), the counts the
+emulation predicts."""
 import types
 
 import numpy as np
@@ -76,15 +85,7 @@ def test_rows_kernel(ctx):
     assert not flagged_one_sided and not bad_gt and not bad_pl and not bad_guarded
 
 
-def _rotation(c, s):
-    """row r of sample s holds the counts (and the reference's answers) of row _rotation(c, s)[r]: the rows of r's own SV type (the halving
-    of a count depends on it) rotated by s * (their number // 3)"""
-    src_row = np.arange(len(c))
-    for t in range(4):
-        at = np.flatnonzero(c[:, 0] == t)
-        if len(at):
-            src_row[at] = np.roll(at, -s * (len(at) // 3))
-    return src_row
+_rotation = PI.rotation                        # row r of sample s holds the rows of r's own SV type rotated
 
 
 @pytest.mark.parametrize("S", [1, 3])
@@ -179,15 +180,95 @@ def _site_call(ctx, sites, ms, e):
     return ctx.genotype_sites(slots, ms, e)
 
 
-@pytest.mark.parametrize("kind", ["one_sided", "half"])
+@pytest.mark.parametrize("kind", ["one_sided", "half", "searched"])
 def test_sites_kernel(ctx, kind):
     """k_genotype_sites on the sites of tests/test_joint_ins.py::test_site_arithmetic_where_the_products_roundings_decide, held to the model
-    through the same call; no site with one deep count beside zeros is flagged (T = 0)"""
+    through the same call; no site with one deep count beside zeros is flagged (T = 0).  "searched": every site has a PL that a fused product
+    turns, nothing is flagged, the PLs are compared straight from the kernel"""
     for ms, e, sites, want in PI.site_items(kind):
         gt, pl, raw, boundary = _site_call(ctx, sites, ms, e)
         assert all(raw[s, 0] == ref and raw[s, 1:len(alts) + 1].tolist() == alts for s, (ref, alts) in enumerate(sites))
+        red = [(sites[s], pl[s, :len(w_pl)].tolist(), w_pl) for s, (w_call, w_pl) in enumerate(want)
+               if not boundary[s] and (pl[s, :len(w_pl)].tolist() != w_pl or tuple(gt[s]) != ((NO_CALL, NO_CALL) if w_call is None else w_call))]
+        _report("k_genotype_sites %s err %g" % (kind, e), "unflagged sites whose call or PLs differ from the model, of %d" % len(sites), red)
         n_flagged = SM.check_against_model(sites, want, lambda s: (e, ms), gt, pl, boundary)
         assert kind == "half" or n_flagged == 0
+
+
+@pytest.mark.parametrize("S", [1, 3])
+def test_cohort_sites_kernel(ctx, S):
+    """k_genotype_cohort_sites on the searched sites (PI.cohort_site_items, the arrays of
+    tests/test_joint_ins.py::test_cohort_site_items_where_the_products_roundings_decide): every (site, sample) item is one searched site of K'
+    members on a subset of the site's six candidates, K' and the masks differ from lane to lane, one item in eight has no site call.  GT pair
+    and PLs are the model's for the embedded site, members the mask, raw the site's counts, nothing is flagged, NS_j / AC_j are recounted from
+    the model's calls (PI.brute_site)"""
+    for item in PI.cohort_site_items(S):
+        PI.load_cohort(ctx, item.counts, item.present)
+        gt, pl, raw, members, boundary, site = ctx.genotype_cohort_sites(item.slots, item.ms, item.e)
+        red = [(int(k), int(s), raw[k, s].tolist(), gt[k, s].tolist(), [(int(g), int(pl[k, s, g]), int(item.pl[k, s, g])) for g in np.flatnonzero(pl[k, s] != item.pl[k, s])])
+               for k, s in zip(*np.nonzero((pl != item.pl).any(axis=2) | (gt != item.gt).any(axis=2)))]
+        _report("k_genotype_cohort_sites S=%d err %g" % (S, item.e), "items whose call or PLs differ from the model, of %d with a site call" % (item.site_of >= 0).sum(), red)
+        assert np.array_equal(members, item.members) and np.array_equal(raw, item.raw) and not boundary.any()
+        want_site = PI.brute_site(item.gt, item.members)
+        bad_site = np.flatnonzero((site != want_site).any(axis=(1, 2)))
+        _report("k_genotype_cohort_sites S=%d err %g" % (S, item.e), "sites whose NS_j / AC_j differ from the model's", bad_site.tolist())
+        assert want_site[:, :, 0].max() == S and want_site[:, :, 1].any()
+        assert not red and len(bad_site) == 0
+
+
+def _cohort_ploidy_call(ctx, item):
+    n, S = item.on.shape
+    slot = np.arange(n, dtype=np.uint32)
+    ctx.cohort_alloc(S, n)
+    for s in range(S):
+        ctx.cohort_set_counts(s, slot, np.ascontiguousarray(item.counts[:, s]))
+    return ctx.genotype_cohort_ploidy(item.type, slot, np.full(n, 1, np.uint8), item.ploidy, 8, item.ms, item.e)
+
+
+@pytest.mark.parametrize("S", [1, 3])
+@pytest.mark.parametrize("kind", ["one_sided", "half"])
+def test_cohort_ploidy_kernel(ctx, kind, S):
+    """k_genotype_cohort_ploidy on the fixture's rows (PI.cohort_ploidy_items, the items of
+    tests/test_ploidy.py::test_cohort_items_where_the_products_roundings_decide): sample s holds the rows rotated, the ploidy of item (r, s) is
+    1 + (r + 3 s) mod 8 so that every ploidy occurs and ploidies mix within a row and a wave, every 11th item has ploidy 0.  Every item
+    against the model through PM.check_against_model (no one-sided item flagged, fewer than 1 % of the half ones), the items at ploidy 0 not
+    genotyped, NS / AN / AC against counts over the model's GTs"""
+    for item in PI.cohort_ploidy_items(kind, S):
+        gt, pl, raw, done, boundary, site = _cohort_ploidy_call(ctx, item)
+        on, rows = item.on, item.rows
+        assert pl.shape == on.shape + (9,) and np.array_equal(done != 0, on) and np.array_equal(raw, np.where(on[:, :, None], item.counts, 0))
+        assert (gt[~on] == NO_CALL).all() and not pl[~on].any() and not boundary[~on].any()
+        w_gt, w_site = PI.cohort_ploidy_expected(item)
+        i_gt, i_pl, i_flag = gt[on], pl[on], boundary[on]
+        red = [(rows[r].tolist(), int(i_gt[r]), i_pl[r, :rows[r, 3] + 1].tolist(), item.want[r]) for r in range(len(rows))
+               if int(i_gt[r]) != (NO_CALL if item.want[r][0] is None else item.want[r][0]) or (not i_flag[r] and i_pl[r, :rows[r, 3] + 1].tolist() != item.want[r][1])]
+        name = "k_genotype_cohort_ploidy %s S=%d min_support %d" % (kind, S, item.ms)
+        _report(name, "items whose GT or (unflagged) PLs differ from the model, of %d" % len(rows), red)
+        bad_site = np.flatnonzero((site != w_site).any(axis=1))
+        _report(name, "rows whose NS / AN / AC differ from the model's", [(int(r), site[r].tolist(), w_site[r].tolist()) for r in bad_site])
+        n_flagged = PM.check_against_model(rows, item.want, lambda r: (item.e, item.ms), i_gt, i_pl, i_flag)
+        print("%s: %d of %d items flagged" % (name, n_flagged, len(rows)))
+        assert n_flagged == 0 if kind == "one_sided" else n_flagged < 0.01 * len(rows)
+        assert not red and len(bad_site) == 0
+
+
+@pytest.mark.parametrize("kind", ["one_sided", "half"])
+def test_cohort_ploidy_all_diploid_is_the_reference(ctx, kind):
+    """the same calls at S = 1 with every ploidy 2: GT and the three PLs are the REFERENCE's stored answers (a flagged item: after
+    exact_pl_ploidy), no one-sided item is flagged"""
+    from svjg import genotype
+    for item in PI.cohort_ploidy_items(kind, 1, True):
+        gt, pl, raw, done, boundary, site = _cohort_ploidy_call(ctx, item)
+        gt, pl, boundary, ref = gt[:, 0], pl[:, 0].copy(), boundary[:, 0], item.ref[:, 0]
+        assert done.all() and not pl[:, 3:].any() and (kind == "half" or not boundary.any())
+        for i in np.flatnonzero(boundary):
+            pl[i, :3] = genotype.exact_pl_ploidy(int(item.type[i]), int(item.counts[i, 0, 0]), int(item.counts[i, 0, 1]), 2, item.e)
+        off = np.flatnonzero((np.where(gt == NO_CALL, 3, gt) != ref[:, 0]) | (pl[:, :3] != ref[:, 1:4]).any(axis=1))
+        _report("k_genotype_cohort_ploidy %s, every ploidy 2, min_support %d" % (kind, item.ms), "items that differ from the reference, of %d" % len(gt),
+                [(int(item.type[i]), item.counts[i, 0].tolist(), int(gt[i]), pl[i, :3].tolist(), ref[i].tolist()) for i in off])
+        called = ref[:, 0] != 3
+        assert np.array_equal(site, np.stack([called, 2 * called, np.where(called, ref[:, 0], 0)], axis=1).astype(np.uint32))
+        assert len(off) == 0
 
 
 def test_deep_one_sided_on_a_fresh_context():

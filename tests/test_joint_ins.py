@@ -64,18 +64,73 @@ def test_site_arithmetic_against_the_model():
     print("flagged sites:", n_flagged, "of", n)
 
 
-@pytest.mark.parametrize("kind", ["one_sided", "half"])
+@pytest.mark.parametrize("kind", ["one_sided", "half", "searched"])
 def test_site_arithmetic_where_the_products_roundings_decide(kind):
     """geno_site on the sites formed from lik_products.npz (tests/products_items.py): one deep count beside zeros at K = 2 and 6 — the chain
-    term T is 0, so none may be flagged and every PL is the routine's own — and K = 2 sites at err = 0.5 over the half pairs"""
+    term T is 0, so none may be flagged and every PL is the routine's own — and K = 2 sites at err = 0.5 over the half pairs; and on the
+    sites of site_products.npz, found by search (T = 0, none flagged)"""
     from tests import products_items as PI
     from tests.site_sim import sim
     for ms, e, sites, want in PI.site_items(kind):
-        assert len(sites) > 500
+        assert len(sites) > (25 if kind == "searched" else 500)
         gt, pl, near, st, s_k = sim.genotype_sites(sites, ms, e, host_table())
         assert not st.any() and s_k.tolist() == [sum(SM.counts(*s)[1]) for s in sites]
         n_flagged = SM.check_against_model(sites, want, lambda s: (e, ms), gt, pl, near)
         assert kind == "half" or n_flagged == 0
+
+
+def test_searched_sites_are_the_models_and_a_fused_product_turns_them():
+    """site_products.npz: the stored answers are the model's, recomputed here; every site has one deep count in [2^27, 2^32) beside zeros or
+    one raw 1; and, by an exact emulation of a fused multiply-add in either order the compiler may choose (tests/lik_model.py: FUSED_ORDERS),
+    for every K in 2..6 and either order at least 20 sites have a PL that the contraction turns — what gives the device tests on this set
+    their teeth (tests/test_genotype_products_gpu.py), asserted where no device is needed; all three err values and the product c * L_ok
+    (the homozygous PL of the deep allele) take part"""
+    from tests import products_items as PI
+    z = PI.searched()
+    n_by, at, l_ok_turns = {}, 0, 0
+    for ms, e, sites, want in PI.site_items("searched"):
+        sel = np.flatnonzero(z["err"] == e)
+        assert ms == 3 and e in (5e-5, 0.01, 0.3) and len(sel) == len(sites)
+        orders = PI.sensitive_sites(sites, want, e)
+        for i, (ref, alts), (call, pls), o in zip(sel.tolist(), sites, want, orders):
+            K = len(alts)
+            v = sorted([ref] + alts)
+            assert 2**27 <= v[-1] < 2**32 and v[-2] <= 1 and not any(v[:-2]) and (ref == v[-1] or ref == 0) and not any(SM.chain(ref, alts))
+            assert z["K"][i] == K and not z["alt"][i, K:].any() and z["pl"][i, :len(pls)].tolist() == pls and not z["pl"][i, len(pls):].any()
+            assert tuple(z["call"][i]) == ((NO_CALL, NO_CALL) if call is None else call)
+            assert o and z["orders"][i] == sum(1 << PI.ORDERS.index(x) for x in o)
+            for x in o:
+                n_by[(K, x)] = n_by.get((K, x), 0) + 1
+            d = ([ref] + alts).index(v[-1])
+            hom = d * (d + 1) // 2 + d
+            l_ok_turns += "first" in o and SM.fused_pls(ref, alts, e, "first")[hom] != pls[hom]
+        at += len(sites)
+    print("searched sites: %d; sensitive per (K, order):" % at, sorted(n_by.items()), "; c * L_ok turns on", l_ok_turns)
+    assert at == len(z["K"]) and sorted(n_by) == [(K, o) for K in range(2, 7) for o in PI.ORDERS] and min(n_by.values()) >= 20
+    assert l_ok_turns >= 20
+
+
+@pytest.mark.parametrize("S", [1, 3])
+def test_cohort_site_items_where_the_products_roundings_decide(S):
+    """site_item (svjg_geno.h, through tests/site_sim) over the cohort sites calls that tests/test_genotype_products_gpu.py hands to
+    k_genotype_cohort_sites (PI.cohort_site_items): every (site, sample) item is one searched site embedded on a subset of six candidates —
+    gt, PLs, raw, members as expected from the model, nothing flagged, no table needed; the set mixes K' within a site, has masks with holes
+    and items without a site call inside full waves"""
+    from tests import products_items as PI
+    from tests.site_sim import sim
+    for item in PI.cohort_site_items(S):
+        n = len(item.slots)
+        assert n == PI.N_COHORT_SITES
+        k_of = np.array([bin(int(m)).count("1") for m in item.members.ravel()]).reshape(n, S)
+        none = item.site_of < 0
+        assert np.array_equal(none, k_of < 2) and 0.1 < none.mean() < 0.15 and none.ravel()[:n * S // 64 * 64].any()
+        assert {2, 3, 4, 6} <= set(k_of[~none].tolist()) and (5 in k_of or item.e == 5e-5) and {0, 1} <= set(k_of[none].tolist())      # (at err 5e-5 and K = 5 L_x is -5: no site)
+        assert S == 1 or (k_of.min(axis=1) != k_of.max(axis=1)).mean() > 0.8                   # K' differs within a site
+        assert 0b100101 in item.members and sum(1 for m in item.members.ravel().tolist() if m & (m + 1)) > n * S // 2       # masks with holes
+        gt, pl, raw, boundary, members, st, _, bad = sim.site_items(item.counts.transpose(1, 0, 2), item.present.T, item.slots, item.ms, item.e, host_table()[:16])
+        assert not bad.any() and not st.any() and not boundary.any()
+        assert np.array_equal(members, item.members) and np.array_equal(gt, item.gt) and np.array_equal(pl, item.pl) and np.array_equal(raw, item.raw)
+        assert (item.gt[none] == NO_CALL).all() and not item.pl[none].any() and not item.raw[none].any()
 
 
 def test_flagged_sites_of_a_large_set():

@@ -105,9 +105,9 @@ def test_ploidy_2_equals_the_diploid_routine(golden):
 
 @pytest.mark.parametrize("kind,P", PI.PLOIDY_CASES)
 def test_row_arithmetic_where_the_products_roundings_decide(kind, P):
-    """geno_row_ploidy on the rows of lik_products.npz (tests/products_items.py): deep one-sided rows at P = 1, 2, 3, 8 — their binomial
+    """geno_row_ploidy on the rows of lik_products.npz (tests/products_items.py): deep one-sided rows at P = 1, 2, 3, 5, 6, 7, 8 — their binomial
     term is log10(1), so none may be flagged and every PL is the routine's own — and the rows at err = 0.5, where all P + 1 likelihoods
-    coincide mathematically and the roundings of the products (and of the reference's 28-digit sums) decide GT, at P = 1, 2, 4, 8"""
+    coincide mathematically and the roundings of the products (and of the reference's 28-digit sums) decide GT, at P = 1, 2, 4, 6, 8"""
     from tests.ploidy_sim import sim
     seen = 0
     for ms, e, rows, want in PI.ploidy_items(kind, P):
@@ -117,6 +117,40 @@ def test_row_arithmetic_where_the_products_roundings_decide(kind, P):
         assert kind == "half" or n_flagged == 0
         seen += len(rows)
     assert seen == int((PI.one_sided() if kind == "one_sided" else PI.fixture()[2] == "half").sum())
+
+
+@pytest.mark.parametrize("S", [1, 3])
+@pytest.mark.parametrize("kind", ["one_sided", "half"])
+def test_cohort_items_where_the_products_roundings_decide(kind, S):
+    """geno_row_ploidy on the items of the cohort calls at per-sample ploidy that tests/test_genotype_products_gpu.py hands to
+    k_genotype_cohort_ploidy (PI.cohort_ploidy_items: the fixture's rows rotated from sample to sample, ploidy 1 + (r + 3 s) mod 8, every
+    11th item off), and, by an exact emulation of a fused product in either order, that the set could fail on the device: under either order at
+    least 5 one-sided items at EVERY ploidy 1..8 change a PL or the GT at S = 3, and at least 4 at S = 1 (the ploidy formula and "every 11th
+    item off" leave 219 items there, 37 of them sensitive: 4 at ploidies 1, 3 and 6, 5 at the others — 5 at every ploidy cannot be reached by
+    one sample); half items at every even ploidy change their GT (at an odd ploidy all P + 1 likelihoods are one value: a tie stays a tie)"""
+    from tests.ploidy_sim import sim
+    for item in PI.cohort_ploidy_items(kind, S):
+        rows = item.rows
+        assert len(item.type) * S < 8000 and set(rows[:, 3].tolist()) == set(range(1, 9)) and 0.08 < 1 - item.on.mean() < 0.1
+        assert S == 1 or (item.ploidy.min(axis=1) != item.ploidy.max(axis=1)).all()          # ploidies mix within every row
+        gt, pl, near, st = sim.genotype_rows(rows[:, 0], rows[:, 1:3], rows[:, 3], item.ms, item.e, host_table())
+        assert not st.any()
+        n_flagged = PM.check_against_model(rows, item.want, lambda r: (item.e, item.ms), gt, pl, near)
+        assert n_flagged == 0 if kind == "one_sided" else n_flagged < 0.01 * len(rows)
+        w_gt, w_site = PI.cohort_ploidy_expected(item)
+        assert (w_gt[~item.on] == NO_CALL).all() and (w_site[:, 0] <= S).all() and w_site[:, 0].any()
+        if kind == "one_sided":
+            orders = PI.sensitive_rows(rows, item.want, item.ms, item.e)
+            per_p = {P: {o: sum(1 for r, x in enumerate(orders) if rows[r, 3] == P and o in x) for o in PI.ORDERS} for P in range(1, 9)}
+            either = {P: sum(1 for r, x in enumerate(orders) if rows[r, 3] == P and x) for P in range(1, 9)}
+            print("one_sided, S = %d: sensitive items per ploidy (first, second, either):" % S, [(P, *per_p[P].values(), either[P]) for P in range(1, 9)])
+            assert min(min(v.values()) for v in per_p.values()) >= (4 if S == 1 else 5)    # (under either order)
+        else:
+            orders = PI.sensitive_rows(rows, item.want, item.ms, item.e, gt_only=True)
+            per_p = {P: {o: sum(1 for r, x in enumerate(orders) if rows[r, 3] == P and o in x) for o in PI.ORDERS} for P in range(1, 9)}
+            print("half, S = %d, min_support %d: items whose GT a fused product changes, per ploidy (first, second):" % (S, item.ms),
+                  [(P, *per_p[P].values()) for P in range(1, 9)], "of", len(rows))
+            assert all(min(per_p[P].values()) >= 20 for P in (2, 4, 6, 8)) and not any(max(per_p[P].values()) for P in (1, 3, 5, 7))
 
 
 def test_ties_are_no_calls():
