@@ -2227,8 +2227,10 @@ __device__ inline T prior_segment_sum(T v, uint32_t width) {
 // stopped earlier keeps its f (prior_step).  The sum of the ploidies does not change from step to step: it is reduced once, in integers; the sum
 // of the x goes through the butterfly at every step — no atomics of any kind, equal bytes from run to run.  The weights of a lane's FIRST item
 // stay in registers across the steps (it.w[], indexed by constants only).  The further items of a lane (S > 64): the first p.staged of them keep
-// their weights in the block's dynamic LDS (prior_stage_put / _get, 76 bytes an item and lane, at most PRIOR_STAGE_MAX = 3: S <= 256), the ones
-// beyond are recomputed at every step (P + 1 exp10 each).  Chosen by a measurement (2026-10-19, one MI355X, ROCm 7.2.0,
+// their weights in the block's dynamic LDS (prior_stage_put / _get, 76 bytes an item and lane, at most PRIOR_STAGE_MAX = 3: up to S = 256 every
+// further item is staged), the ones beyond are recomputed at every step (P + 1 exp10 each): at S > 256 a lane's items j + 256, j + 320, ... take
+// that arm while its first three further ones still come from LDS, for any S the driver accepts, the same bytes as with everything recomputed
+// (tests/test_cohort_prior_gpu.py at S = 257 and 320).  Chosen by a measurement (2026-10-19, one MI355X, ROCm 7.2.0,
 // tools/cohort_prior_timing.py, 100 000 rows x 256 samples, 4.9 steps a row, both kernels of the call, median of 30 calls behind 5, alternated
 // twice): 2.549 / 2.549 ms staged in LDS against 3.685 / 3.692 ms recomputed, the cohort kernel alone 0.597 / 0.597 ms — LDS, although its 58 KB a
 // block leave room for two blocks a unit only.  SVJG_PRIOR_STAGE=recompute (or lds) in the environment selects the other way, for that tool.

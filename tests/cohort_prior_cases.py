@@ -13,12 +13,20 @@ NONE = 0xFFFFFFFF
 ERR = 5e-5
 ROWS = 1500
 SIZES = (1, 3, 4, 5, 31, 32, 33, 63, 64, 65, 130)
+# the shapes that only the kernel's body knows (300 rows each): segment width 2, width 8 full and plus one, width 16 full and plus one; two
+# further items on every lane (192), the third from its first sample to full (193, 256), one and then 64 items behind the three staged ones,
+# which are recomputed at every step (257, 320)
+SHAPE_SIZES, SHAPE_ROWS = (2, 8, 9, 16, 17, 192, 193, 256, 257, 320), 300
 # (At S = 1 an item of odd ploidy with c1 = c2 keeps f = 1/2 and ties g with P - g exactly: such items are undecidable and left out, and with the
 # low counts they are about 1.5 % of a draw; the seed of mixed_1 is the first of 7201 + 1000 k whose draw stays inside the 1 % cap.)
 # (name, S, rows, ploidy pattern, seed): every S once with every item diploid (ploidy NULL) and once with 0..8 mixed within rows; the sex pattern
 # (0 / 1 / 2 by row class and sample) on both sides of a wave; one case of deep counts (up to 5 000 reads on one allele: w_g underflows to 0)
 CASES = tuple([("null_%d" % S, S, ROWS, None, 7000 + S) for S in SIZES] + [("mixed_%d" % S, S, ROWS, "mixed", 7200 + S if S > 1 else 33201) for S in SIZES]
-              + [("sex_4", 4, ROWS, "sex", 7404), ("sex_65", 65, ROWS, "sex", 7465), ("deep_33", 33, 400, "deep", 7533)])
+              + [("sex_4", 4, ROWS, "sex", 7404), ("sex_65", 65, ROWS, "sex", 7465), ("deep_33", 33, 400, "deep", 7533)]
+              + [("null_%d" % S, S, SHAPE_ROWS, None, 7000 + S) for S in SHAPE_SIZES] + [("mixed_%d" % S, S, SHAPE_ROWS, "mixed", 7200 + S) for S in SHAPE_SIZES]
+              # staged slots that hold items of ploidy 0 (sex); weights that underflow to 0 in the staged and the recomputed arm (deep)
+              + [("sex_193", 193, SHAPE_ROWS, "sex", 7593), ("deep_257", 257, 200, "deep", 7757)])
+SHAPE_CASES = tuple(c[0] for c in CASES[-2 * len(SHAPE_SIZES) - 2:])
 GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "cohort_prior")
 PLANTED = ("hom_ref", "hom_alt", "one_carrier", "absent", "zero_reads")
 # what may be left out of the comparisons (the issue's margins), and the cap on it per case

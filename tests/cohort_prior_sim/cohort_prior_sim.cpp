@@ -1,6 +1,6 @@
 // TEST HARNESS ONLY (never shipped, never loaded by the product): the per-item routines of the cohort call with an allele-frequency prior
 // (svjg_geno.h: prior_load, prior_expected, prior_call, prior_step, prior_segment_width, and cohort_layout with the prior) compiled with g++, and a row's
-// EM run sequentially over its samples (the kernel sums the same x through a butterfly: another order of the same additions).  With
+// EM run sequentially over its samples (cprsim_row) or with every step's sum in the kernel's order (cprsim_row_wave: lanes, strides, butterfly).  With
 // -DCOHORT_PRIOR_SIM_MAIN it is a stand-alone program (for -fsanitize=address,undefined) that runs random rows and checks what holds without a model.
 #define SVJG_HD inline
 #include "../../svjedi-graph_amd/csrc/svjg_geno.h"
@@ -10,18 +10,36 @@
 using namespace svjg;
 
 // One row of S samples: raw[S][2], done[S], ploidy[S] or NULL (2 everywhere) -> *f (NaN: no estimate), *steps (the kernel's word: bit 31 = not
-// converged), gt[S], gq[S], site[3] = NS, AN, AC
-extern "C" void cprsim_row(uint32_t sv_type, const uint32_t *raw, const uint8_t *done, const uint8_t *ploidy, uint64_t S, double err, uint32_t min_support,
-                           double *f, uint32_t *steps, uint8_t *gt, uint8_t *gq, uint32_t *site) {
+// converged), gt[S], gq[S], site[3] = NS, AN, AC.  wave: a step's x are summed in k_cohort_prior's order (cprsim_row_wave), else sample after sample
+static void row_em(bool wave, uint32_t sv_type, const uint32_t *raw, const uint8_t *done, const uint8_t *ploidy, uint64_t S, double err, uint32_t min_support,
+                   double *f, uint32_t *steps, uint8_t *gt, uint8_t *gq, uint32_t *site) {
     double tab[2 * PLOIDY_TAB];
     ploidy_log_table(err, tab);
     const uint8_t t8 = (uint8_t)sv_type, *type = &t8;
+    const uint32_t W = prior_segment_width(S);
     uint32_t sum_p = 0;
     for (uint64_t s = 0; s < S; ++s) { PriorItem it; double c; prior_load(type, raw, done, ploidy, s, tab, c, it); sum_p += it.P; }
     PriorRow row = prior_row_start(sum_p);
     while (!row.done) {
         double x = 0.0;
-        for (uint64_t s = 0; s < S; ++s) { PriorItem it; double c; prior_load(type, raw, done, ploidy, s, tab, c, it); x += prior_expected(it, row.f); }
+        if (wave) {
+            double v[64], u[64];
+            for (uint32_t j = 0; j < W; ++j) {                                        // lane j: its items j, j + 64, j + 128, ... from the first one on
+                v[j] = 0.0;
+                for (uint64_t s = j; s < S; s += 64) {
+                    PriorItem it; double c;
+                    prior_load(type, raw, done, ploidy, s, tab, c, it);
+                    const double e = prior_expected(it, row.f);
+                    v[j] = s == j ? e : v[j] + e;
+                }
+            }
+            for (uint32_t m = 1; m < W; m <<= 1) {                                    // the butterfly: every lane adds its partner's value of the level before
+                for (uint32_t j = 0; j < W; ++j) u[j] = v[j] + v[j ^ m];
+                for (uint32_t j = 0; j < W; ++j) v[j] = u[j];
+            }
+            x = v[0];
+        } else
+            for (uint64_t s = 0; s < S; ++s) { PriorItem it; double c; prior_load(type, raw, done, ploidy, s, tab, c, it); x += prior_expected(it, row.f); }
         prior_step(row, x, sum_p);
     }
     site[0] = site[1] = site[2] = 0;
@@ -33,6 +51,19 @@ extern "C" void cprsim_row(uint32_t sv_type, const uint32_t *raw, const uint8_t 
         if (k.gt != 0xFF) { ++site[0]; site[1] += it.P; site[2] += k.gt; }
     }
     *f = row.f; *steps = row.steps;
+}
+
+extern "C" void cprsim_row(uint32_t sv_type, const uint32_t *raw, const uint8_t *done, const uint8_t *ploidy, uint64_t S, double err, uint32_t min_support,
+                           double *f, uint32_t *steps, uint8_t *gt, uint8_t *gq, uint32_t *site) {
+    row_em(false, sv_type, raw, done, ploidy, S, err, min_support, f, steps, gt, gq, site);
+}
+
+// The same row with every step's sum in the kernel's order: lane j of W = prior_segment_width(S) lanes adds its items j, j + 64, j + 128, ... in
+// that order, starting from the first; then the levels m = 1, 2, ..., W / 2 of the xor butterfly; lanes at or beyond S hold 0.0.  The kernel
+// differs from this in exp10 and log10 only.
+extern "C" void cprsim_row_wave(uint32_t sv_type, const uint32_t *raw, const uint8_t *done, const uint8_t *ploidy, uint64_t S, double err, uint32_t min_support,
+                                double *f, uint32_t *steps, uint8_t *gt, uint8_t *gq, uint32_t *site) {
+    row_em(true, sv_type, raw, done, ploidy, S, err, min_support, f, steps, gt, gq, site);
 }
 
 // the weights of one item: w[9] = C(P, g) 10^d_g, -> the item's ploidy as the EM sees it (0: it takes no part); *gmax
@@ -62,7 +93,7 @@ extern "C" void cprsim_layout(uint64_t n_rows, uint64_t S, uint32_t max_ploidy, 
 #ifdef COHORT_PRIOR_SIM_MAIN
 #include <vector>
 int main() {
-    const uint64_t sizes[11] = {1, 3, 4, 5, 31, 32, 33, 63, 64, 65, 130};
+    const uint64_t sizes[21] = {1, 2, 3, 4, 5, 8, 9, 16, 17, 31, 32, 33, 63, 64, 65, 130, 192, 193, 256, 257, 320};
     uint64_t rows = 0, bad = 0, x = 88172645463325252ull;
     auto next = [&] { x ^= x << 13; x ^= x >> 7; x ^= x << 17; return x; };
     for (uint64_t S : sizes)
@@ -78,6 +109,13 @@ int main() {
                 const uint32_t type = (uint32_t)(next() % 4), ms = k & 1 ? 3 : 0;
                 cprsim_row(type, raw.data(), done.data(), mode == 1 ? pld.data() : nullptr, S, 5e-5, ms, &f, &steps, gt.data(), gq.data(), site);
                 cprsim_row(type, raw.data(), done.data(), mode == 1 ? pld.data() : nullptr, S, 5e-5, ms, &f2, &steps2, gt2.data(), gq2.data(), site2);
+                // the kernel's order of the sums: what holds of any order (the model decides the rest: tests/test_cohort_prior.py)
+                std::vector<uint8_t> gt3(S), gq3(S); double f3; uint32_t steps3, site3[3];
+                cprsim_row_wave(type, raw.data(), done.data(), mode == 1 ? pld.data() : nullptr, S, 5e-5, ms, &f3, &steps3, gt3.data(), gq3.data(), site3);
+                uint32_t ns3 = 0, ac3 = 0;
+                for (uint64_t s = 0; s < S; ++s) { if (gt3[s] != 0xFF) { ++ns3; ac3 += gt3[s]; if (gq3[s] > 99) ++bad; } else if (gq3[s] != 0xFF) ++bad; }
+                if (ns3 != site3[0] || ac3 != site3[2] || (f != f) != (f3 != f3) || (f3 == f3 && !(f3 >= 0.0 && f3 <= 1.0 && steps3 && (steps3 & ~EM_NOT_CONVERGED) <= EM_MAX_IT))
+                    || (f3 != f3 && steps3)) ++bad;
                 ++rows;
                 uint32_t ns = 0, an = 0, ac = 0, part = 0;
                 for (uint64_t s = 0; s < S; ++s) {

@@ -34,8 +34,9 @@ def build_main():
 
 def _lib():
     lib = ctypes.CDLL(build())
-    lib.cprsim_row.restype = None
-    lib.cprsim_row.argtypes = [ctypes.c_uint32, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_double, ctypes.c_uint32] + [ctypes.c_void_p] * 5
+    for fn in (lib.cprsim_row, lib.cprsim_row_wave):
+        fn.restype = None
+        fn.argtypes = [ctypes.c_uint32, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_double, ctypes.c_uint32] + [ctypes.c_void_p] * 5
     lib.cprsim_item.restype = ctypes.c_uint32
     lib.cprsim_item.argtypes = [ctypes.c_uint32] * 4 + [ctypes.c_double, ctypes.c_void_p, ctypes.c_void_p]
     lib.cprsim_width.restype = ctypes.c_uint32
@@ -47,9 +48,11 @@ def _lib():
     return lib
 
 
-def rows(sv_type, raw, done, ploidy, err, min_support):
-    """every row through cprsim_row -> (f[R], steps[R] (bit 31: not converged), gt[R, S], gq[R, S], site[R, 3])"""
+def rows(sv_type, raw, done, ploidy, err, min_support, wave=False):
+    """every row through cprsim_row, or with wave through cprsim_row_wave (every step's sum in the kernel's order)
+    -> (f[R], steps[R] (bit 31: not converged), gt[R, S], gq[R, S], site[R, 3])"""
     lib = _lib()
+    row = lib.cprsim_row_wave if wave else lib.cprsim_row
     raw, done = np.ascontiguousarray(raw, np.uint32), np.ascontiguousarray(done, np.uint8)
     R, S = done.shape
     if ploidy is not None:
@@ -57,8 +60,8 @@ def rows(sv_type, raw, done, ploidy, err, min_support):
     f, steps = np.zeros(R), np.zeros(R, np.uint32)
     gt, gq, site = np.zeros((R, S), np.uint8), np.zeros((R, S), np.uint8), np.zeros((R, 3), np.uint32)
     for r in range(R):
-        lib.cprsim_row(int(sv_type[r]), raw[r].ctypes.data, done[r].ctypes.data, None if ploidy is None else ploidy[r].ctypes.data, S, float(err),
-                       int(min_support), f[r:].ctypes.data, steps[r:].ctypes.data, gt[r].ctypes.data, gq[r].ctypes.data, site[r].ctypes.data)
+        row(int(sv_type[r]), raw[r].ctypes.data, done[r].ctypes.data, None if ploidy is None else ploidy[r].ctypes.data, S, float(err),
+            int(min_support), f[r:].ctypes.data, steps[r:].ctypes.data, gt[r].ctypes.data, gq[r].ctypes.data, site[r].ctypes.data)
     return f, steps, gt, gq, site
 
 

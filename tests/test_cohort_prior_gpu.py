@@ -1,11 +1,14 @@
 """The cohort call with an allele-frequency prior on the GPU (svjg_genotype_cohort_prior, k_cohort_prior) against the 60-digit model of
 tests/cohort_prior_model.py, whose answers for the cases of tests/cohort_prior_cases.py are stored under tests/golden/cohort_prior/: about
 1 500 rows x S for S on both sides of every segment width, once with every item diploid (ploidy NULL) and once with ploidies 0..8 mixed
-within rows, min_support 0 and 3, planted rows, one case of deep counts.  Needs an MI355X: run with -m gpu.
+within rows, min_support 0 and 3, planted rows, one case of deep counts; 200 or 300 rows x S at the shapes that only the kernel's body knows
+(segment widths 2 and 16, two and three staged items on every lane, recomputed items behind three staged ones: S up to 320), and calls of more
+rows than one trip of the grid holds.  Needs an MI355X: run with -m gpu.
 
 What may be left out of a comparison is decided by the model alone, before any device ran (tests/golden/make_cohort_prior.py): rows whose
 deciding EM step lies within 1e-6 of EM_TOL (left out of everything), items whose -10 log10(rest) lies within 1e-6 of an integer or whose two
 largest posteriors lie within 1e-9 of each other (left out of GT / GQ); at most 1 % of the rows and of the items of a case, asserted here."""
+import functools
 import os
 import subprocess
 import sys
@@ -140,10 +143,11 @@ def test_one_sample_rows(ctx):
     assert np.array_equal(site, np.stack([called, 2 * called, np.where(called, gt[:, 0], 0)], axis=1).astype(np.uint32))
 
 
-@pytest.mark.parametrize("name", ["null_65", "null_130", "mixed_130"])
+@pytest.mark.parametrize("name", ["null_65", "null_130", "mixed_130", "null_192", "mixed_193", "null_256", "mixed_257", "mixed_320", "deep_257"])
 def test_further_items_staged_in_lds_or_recomputed(ctx, monkeypatch, name):
     """S > 64: a lane's items beyond its first are recomputed at every step or kept in LDS (SVJG_PRIOR_STAGE, tools/cohort_prior_timing.py
-    measures the two): the same bytes either way"""
+    measures the two): the same bytes either way.  Two staged items on every lane (192), the third on one lane and on all (193, 256), one and 64
+    recomputed items behind three staged ones (257, 320), weights that underflow to 0 in both arms (deep_257)"""
     c = CC.inputs(name)
     _load_matrix(ctx, c["n_slots"], c["counts"], c["present"])
     got = {}
@@ -157,13 +161,52 @@ def test_further_items_staged_in_lds_or_recomputed(ctx, monkeypatch, name):
 
 def test_chunks_equal_one_call(ctx):
     from svjg import genotype
-    for name in ("null_33", "mixed_5"):
+    for name in ("null_33", "mixed_5", "null_9", "mixed_257"):            # (at 9 samples a wave holds 4 rows: chunks of 97 end inside a wave)
         c = CC.inputs(name)
         _load_matrix(ctx, c["n_slots"], c["counts"], c["present"])
         rows = types.SimpleNamespace(sv_type=c["t"], slot=c["slot"], ok=c["ok"])
         one = genotype.genotype_cohort_prior_rows(ctx, rows, c["S"], c["ploidy"], 3, CC.ERR)
         parts = genotype.genotype_cohort_prior_rows(ctx, rows, c["S"], c["ploidy"], 3, CC.ERR, step=97)
         assert len(one) == 8 and all(x.tobytes() == y.tobytes() and x.shape == y.shape for x, y in zip(one, parts))
+
+
+def _equal_bytes_in_every_copy(got, one, K):
+    """got[K * R, ...] holds K times the bytes of one[R, ...] (NaN included)"""
+    u = "u%d" % one.dtype.itemsize
+    return got.shape == (K * one.shape[0],) + one.shape[1:] and np.array_equal(got.view(u).reshape(K, -1), np.broadcast_to(one.view(u).reshape(1, -1), (K, one.size)))
+
+
+@functools.lru_cache(maxsize=None)
+def _compute_units():
+    """the device's compute units as the library's launch cap counts them, else 256.  Asked of torch in a child process, once: torch brings a HIP
+    runtime of its own, and a second runtime in this process is what tests/test_context_teardown_gpu.py would then measure the free memory with"""
+    p = subprocess.run([sys.executable, "-c", "import torch; print(torch.cuda.get_device_properties(0).multi_processor_count)"], capture_output=True, text=True)
+    last = p.stdout.split()[-1:] if p.returncode == 0 else []
+    return int(last[0]) if last and last[0].isdigit() and int(last[0]) > 0 else 256
+
+
+@pytest.mark.parametrize("name", ["mixed_33", "null_3", "mixed_257"])
+def test_more_rows_than_one_trip_of_the_grid(ctx, name):
+    """The launch is capped at 8 blocks of 4 waves a compute unit: a case's rows, repeated until the call has more waves than that plus a partial
+    last trip (row i of copy k has the type, slot, ok and ploidy of row i), so that waves take the grid-stride loop a second time and set up
+    `it`, `sum_p` and `row` again.  Every output of every copy has the bytes of the one-trip call on the case itself, which
+    test_case_against_the_model holds to the model.  One row a wave (mixed_33), 16 rows a wave (null_3), staged and recomputed items on the
+    second trip (mixed_257).  (A trip's rows are no multiple of a case's rows on 256 or 304 units: a wave's second row is another one than its first.)"""
+    cus = _compute_units()
+    c = CC.inputs(name)
+    R, per_wave = len(c["t"]), 64 // sim.width(c["S"])
+    trip = 32 * cus                                                # waves
+    K = -(-(trip + trip // 8) * per_wave // R)
+    waves = -(-K * R // per_wave)
+    assert waves > 32 * cus and waves % trip != 0
+    _load_matrix(ctx, c["n_slots"], c["counts"], c["present"])
+    one = _prior(ctx, c, 3)
+    assert R <= trip * per_wave and np.array_equal(one[5], M.site_of(one[0], c["ploidy"]))
+    many = dict(c, t=np.tile(c["t"], K), slot=np.tile(c["slot"], K), ok=np.tile(c["ok"], K), ploidy=None if c["ploidy"] is None else np.tile(c["ploidy"], (K, 1)))
+    got = _prior(ctx, many, 3)
+    for k in range(9):
+        assert _equal_bytes_in_every_copy(got[k], one[k], K), NAMES[k]
+    assert np.array_equal(got[5], M.site_of(got[0], many["ploidy"]))
 
 
 def test_empty_and_bad_calls(ctx):
