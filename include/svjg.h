@@ -380,6 +380,31 @@ int svjg_genotype_cohort_sites(svjg_ctx *ctx, const uint32_t *slots /* [n_sites]
                                uint32_t *raw /* [n_sites][n_samples][7] */, uint8_t *members, uint8_t *boundary,
                                uint32_t *site /* [n_sites][SVJG_MAX_SITE_ALTS][2] = NS_j, AC_j */);
 
+/* svjg_cohort_qual: the site quality of every row of a cohort (--cohort-qual): how sure are we that at least one alt copy exists in the cohort.
+ *   The exact allele-count posterior (the "exact model" of Li 2011): the samples' genotype likelihoods folded in one by one into y_k, the
+ *   likelihood of k alt copies among the M chromosomes folded in so far, in its normalised form, rescaled by exact powers of two;
+ *   prior phi_k = theta / k (k >= 1), phi_0 = 1 - theta H_M; qual = -10 log10 of the posterior of k = 0, mlac = the k at the posterior's maximum.
+ *   The model in full: DESIGN.md 4.3 "Site quality (k_cohort_qual)" and svjg_geno.h.
+ * It reads the cohort matrix, not the count vector.  Item (r, s) takes part iff ok[r] & 1, slot[r] != 0xFFFFFFFF, present[slot[r]][s], its ploidy
+ * is in 1..max_ploidy (ploidy == NULL: 2 everywhere, max_ploidy must be 2) and it has a read.  There is no min_support: support gates calls, not
+ * likelihoods, as in the EM of svjg_genotype_cohort_prior.  Outputs per row: chroms = M, the chromosomes of the items that took part; mlac in
+ * 0..M; qual >= 0, NaN (and mlac = 0, chroms = 0) where no item took part.  No atomic takes part in an output (a row lies within one wave, every
+ * sum over k goes through a fixed butterfly): equal bytes from run to run.  The call works in a block of its own (16 bytes a row, the ploidy
+ * bytes, 8 (M_max + 1) + 720 bytes of tables): it neither reads nor changes any other call's block or views.  n_rows = 0 returns 0.  SVJG_E_ARG
+ * with a message in svjg_last_error, all found before any launch: no matrix, a null array, max_ploidy outside 1..SVJG_MAX_PLOIDY, ploidy == NULL with
+ * max_ploidy != 2, a ploidy byte above max_ploidy, n_samples x max_ploidy above SVJG_QUAL_MAX_CHROMS (the row's 2 (M_max + 1) doubles live in one
+ * block's LDS: 65.6 KB at 2 048 diploid samples), theta not in (0, 0.05] (0.05 H_4096 < 1: phi_0 > 0), n_rows x n_samples beyond 2^40; a row
+ * naming a slot >= the matrix's n_slots is reported after the pass, as svjg_genotype reports it.  svjg_last_kernel_ms reports the kernel as
+ * genotype_ms.
+ * Measured once, with the change that added it (one MI355X, 2026-10-20, ROCm 7.2.0, tools/cohort_qual_timing.py: counts 0..60, e = 5e-5, theta = 1e-3,
+ * median of 30 calls behind 5, run twice in one process; genotype_ms): 100 000 rows x 64 samples diploid 8.565 / 8.550 ms; the same matrix with
+ * ploidies 1..8 at max_ploidy 8 15.065 / 15.033 ms; 2 000 rows x 1 024 samples diploid 20.509 / 20.511 ms.  A first reading: nothing is compared
+ * against it, and nothing else has been measured. */
+#define SVJG_QUAL_MAX_CHROMS 4096
+int svjg_cohort_qual(svjg_ctx *ctx, const uint8_t *sv_type, const uint32_t *slot, const uint8_t *ok,
+                     const uint8_t *ploidy /* [n_rows][n_samples], or NULL */, uint32_t max_ploidy, uint64_t n_rows, double err, double theta,
+                     double *qual, uint32_t *mlac, uint32_t *chroms);
+
 /* ---- the whole pass in one call (what a fused svjedi-graph run and bench.py do per batch) -----------------------------------
  * svjg_set_rows copies the three per-row input arrays of svjg_genotype to the device once (they stay until the next
  * svjg_set_rows / svjg_destroy).  svjg_run_resident then does, for the resident text of svjg_gaf_upload and those rows:

@@ -82,7 +82,7 @@ constexpr uint64_t STAGE_PIECE = 8ull << 20;
 // hands out pointers into BLOCK_ROWS' twin and svjg_genotype_boundary reads it later, and both must survive calls of the other six.
 // A fused pass's slot holds the same pair (RunSlot).
 struct LegBlock { DevBuf<uint8_t> d;  PinBuf h; };
-enum { BLOCK_ROWS, BLOCK_PLOIDY, BLOCK_SITES, BLOCK_COHORT, BLOCK_COHORT_PLOIDY, BLOCK_COHORT_PRIOR, BLOCK_COHORT_SITES, LEG_BLOCKS };   // rows_layout, ploidy_layout, sites_layout, cohort_layout for the three cohort blocks, sites_layout again (svjg_geno.h)
+enum { BLOCK_ROWS, BLOCK_PLOIDY, BLOCK_SITES, BLOCK_COHORT, BLOCK_COHORT_PLOIDY, BLOCK_COHORT_PRIOR, BLOCK_COHORT_SITES, BLOCK_COHORT_QUAL, LEG_BLOCKS };   // rows_layout, ploidy_layout, sites_layout, cohort_layout for the three cohort blocks, sites_layout again, qual_layout (svjg_geno.h)
 
 // slots the passes of svjg_run_begin rotate through: two may be in flight, and the one the NEXT pass will use is zeroed while the newest computes
 constexpr int RUN_SLOTS = 3;
@@ -1407,6 +1407,67 @@ extern "C" int svjg_genotype_cohort_prior(svjg_ctx *c, const uint8_t *sv_type, c
                                           uint32_t *raw, uint8_t *genotyped, uint8_t *boundary, uint32_t *site, uint8_t *gq, double *af,
                                           uint32_t *em_steps) {
     return cohort_call(c, BLOCK_COHORT_PRIOR, sv_type, slot, ok, ploidy, max_ploidy, n_rows, min_support, err, gt, pl, raw, genotyped, boundary, site, gq, af, em_steps);
+}
+
+// ---- cohort site quality (svjg.h: svjg_cohort_qual; the model: svjg_geno.h) ----
+// Through genotype_leg in BLOCK_COHORT_QUAL, a block of its own: the call's logarithms, the harmonic numbers H_0..H_m_max (both by the host, in
+// doubles) and the ploidy bytes go in with the three input arrays; k_cohort_qual; qual, mlac and chroms come out.  The kernel reads no log10(i!)
+// table and never asks for a larger one (the leg builds the first one for a context without, as for every call): the max_n pair carries the gate's
+// "slot out of range" word only.  Blocks: one wave each; a unit holds
+// what its LDS admits (160 KiB over the block's request, qual_lds_bytes + the 720 bytes of the staged logarithms), its registers (118 VGPRs: four
+// waves a SIMD, 16 a unit) and the 32-wave cap; the rest in strides of the grid.  A request beyond 64 KiB (m_max > 4050) is announced to the
+// runtime first.
+constexpr uint64_t QUAL_WAVES_PER_CU = 16;
+static int launch_cohort_qual(svjg_ctx *c, CohortQualArgs &p) {
+    HIPCHK(c, hipMemsetAsync(p.g.max_n, 0, 8, c->stream));
+    const uint32_t lds = qual_lds_bytes(p.m_max);
+    if (lds + 2 * PLOIDY_TAB * 8 > 65536) HIPCHK(c, hipFuncSetAttribute((const void *)k_cohort_qual, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    const uint64_t fit = (160u * 1024u) / (lds + 2 * PLOIDY_TAB * 8), per_cu = fit < QUAL_WAVES_PER_CU ? (fit ? fit : 1) : QUAL_WAVES_PER_CU;
+    const uint64_t cap = (uint64_t)c->n_cu * per_cu;
+    hipLaunchKernelGGL(k_cohort_qual, dim3((uint32_t)(p.g.n_rows < cap ? p.g.n_rows : cap)), dim3(QUAL_TPB), lds, c->stream, p);
+    HIPCHK(c, hipGetLastError());
+    return 0;
+}
+
+extern "C" int svjg_cohort_qual(svjg_ctx *c, const uint8_t *sv_type, const uint32_t *slot, const uint8_t *ok, const uint8_t *ploidy, uint32_t max_ploidy,
+                                uint64_t n_rows, double err, double theta, double *qual, uint32_t *mlac, uint32_t *chroms) {
+    if (!c) return SVJG_E_ARG;
+    if (!c->d_cm) { c->err = "no cohort matrix"; return SVJG_E_ARG; }
+    if (n_rows == 0) return 0;
+    if (!sv_type || !slot || !ok || !qual || !mlac || !chroms) { c->err = "a null array"; return SVJG_E_ARG; }
+    if (max_ploidy < 1 || max_ploidy > MAX_PLOIDY) { c->err = "max_ploidy is not in 1..SVJG_MAX_PLOIDY"; return SVJG_E_ARG; }
+    if (!ploidy && max_ploidy != 2) { c->err = "without a ploidy array every item is diploid: max_ploidy must be 2"; return SVJG_E_ARG; }
+    const uint64_t S = c->cohort_samples;
+    static_assert(SVJG_QUAL_MAX_CHROMS == QUAL_MAX_CHROMS, "svjg.h and svjg_geno.h disagree");
+    if (S * max_ploidy > QUAL_MAX_CHROMS) { c->err = "too many chromosomes for the site quality: n_samples * max_ploidy is above SVJG_QUAL_MAX_CHROMS = 4096"; return SVJG_E_ARG; }
+    if (!(theta > 0.0 && theta <= QUAL_THETA_MAX)) { c->err = "theta is not in (0, 0.05]"; return SVJG_E_ARG; }
+    if (n_rows > (1ull << 40) / S) { c->err = "too many items for one call: take the rows in chunks"; return SVJG_E_ARG; }
+    const uint64_t n = n_rows * S;
+    if (ploidy)
+        for (uint64_t i = 0; i < n; ++i)
+            if (ploidy[i] > max_ploidy) { c->err = "ploidy above max_ploidy"; return SVJG_E_ARG; }
+    HIPCHK(c, hipSetDevice(c->device));
+    const uint32_t m_max = (uint32_t)(S * max_ploidy);
+    const QualLayout L = qual_layout(n_rows, S, m_max, ploidy != nullptr);
+    const int rc = genotype_leg(c, c->leg[BLOCK_COHORT_QUAL], L,
+        [&](uint8_t *hb) {
+            ploidy_log_table(err, (double *)(hb + L.logtab));
+            qual_harmonic(m_max, (double *)(hb + L.harm));
+            stage_rows(hb, L.in, sv_type, slot, ok, n_rows);
+            if (ploidy) memcpy(hb + L.ploidy, ploidy, n);
+        },
+        [&](uint8_t *base) {
+            CohortQualArgs p{geno_args(c, c->cm(), base, L.in, n_rows, 0, err), c->d_cpresent, c->cohort_samples, ploidy ? base + L.ploidy : nullptr,
+                             (const double *)(base + L.logtab), (const double *)(base + L.harm), max_ploidy, m_max, qual_rescale_every(m_max, max_ploidy), theta,
+                             (double *)(base + L.qual), (uint32_t *)(base + L.mlac), (uint32_t *)(base + L.chroms)};
+            p.g.n_slots = c->cohort_slots;                        // (the matrix's slots, not the count vector's)
+            p.g.max_n = (unsigned int *)(base + L.maxn);
+            return launch_cohort_qual(c, p);
+        });
+    if (rc) return rc;
+    const uint8_t *hb = c->leg[BLOCK_COHORT_QUAL].h;
+    memcpy(qual, hb + L.qual, n_rows * sizeof *qual); memcpy(mlac, hb + L.mlac, n_rows * sizeof *mlac); memcpy(chroms, hb + L.chroms, n_rows * sizeof *chroms);
+    return 0;
 }
 
 // ---- the whole pass in one call, one host wait; two passes in flight ------------------------------------------------------

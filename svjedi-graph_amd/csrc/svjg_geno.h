@@ -663,6 +663,157 @@ SVJG_HD uint32_t prior_segment_width(uint64_t S) {
     return w;
 }
 
+// ---- cohort site quality: the exact allele-count posterior (k_cohort_qual) ----
+// "Is there at least one alt copy in this cohort": the exact model of Li 2011 (the QUAL of samtools / bcftools), at any ploidy.  An item (r, s)
+// takes part under the rule of the EM above: cohort_gate passes (ok & 1, a slot, presence), its ploidy P is in 1..max_ploidy (2 everywhere
+// without a ploidy array) and c1 + c2 > 0.  Its coefficients are a_g = C(P, g) 10^(d_g), g = 0..P: exactly PriorItem::w of prior_item; beside
+// them d_0 = l_0 - max l is kept in double-double (qual_item).  With M' the chromosomes of the items folded in so far and M = M' + P,
+// y_k = z_k / C(M, k) is the likelihood of "k alt copies among M chromosomes", averaged over which chromosomes carry them: y_0 = 1 at M' = 0,
+// and the items are folded in in sample order by
+//     y_k <- sum_(g = 0..min(P, k)) a_g y_(k-g) (k)_g (M - k)_(P-g) / (M)_P      for k = 0..M,
+// (x)_n the falling factorial x (x - 1) ... (x - n + 1), (x)_0 = 1; a term with k - g > M' is absent.  The factor is a hypergeometric
+// probability (times C(P, g), which a_g carries); at P = 2 this is Li's recurrence term for term.  The normalised form is used on purpose: the
+// plain convolution z_k with one division by C(M, k) at the end fails at scale — with a thousand shallow samples the posterior's mass sits at
+// k where z_k / max z underflows while C(M, k_max) / C(M, k) overflows (tests/test_cohort_qual.py shows the case).
+// Rescaling: 10^(d_g) <= 1 and the hypergeometric probabilities of a k add up to at most 1, so the row's maximum never grows; the item's
+// largest coefficient is C(P, gmax) 10^0 >= 1 and the hypergeometric probability that goes with it is at least 1 / C(M, P), so one step
+// shrinks the maximum by at most 1 / C(M, P) > 1 / M^P > 2^-(P bits), bits = the binary digits of the call's largest M (13 at 4096: one step
+// is always safe, 1 / C(4096, 8) > 2^-82).  Every qual_rescale_every(M_max, max_ploidy) = max(1, 512 / (max_ploidy bits)) steps the row is
+// multiplied by 2^(-ilogb(max y)) — exact, so harness and kernel see the same bits — and -ilogb(max y) is added to the integer E: behind a
+// rescaling the maximum lies in [1, 2), so between two of them it cannot fall below 2^-512, and what then underflows is below 2^-510 of it.
+// Prior over the allele count: phi_k = theta / k for k = 1..M, phi_0 = 1 - theta H_M, H_M = sum_(k = 1..M) 1 / k summed in increasing k in
+// double (qual_harmonic: the host makes the table of a call, the kernel reads entry M).  Per row: chroms = M; without an item that takes part
+// M = 0, qual = NaN, mlac = 0; mlac = the smallest k that attains max_k phi_k y_k; qual = max(0, -10 (log10 phi_0 + D_0 - log10 T + E log10 2)),
+// T = sum_k phi_k y_k over the scaled y, D_0 = sum_s d_(s,0) in double-double in sample order: the log of the TRUE y_0, which may have
+// underflowed in the scaled array.  Every sum over k is fixed once: lane-strided partials in increasing k (lane j: k = j, j + 64, ...), then the
+// xor butterfly over 64 lanes.  Compiled without fused multiply-adds (the one fma() in qual_finish is an exact product, written out): the
+// harness (tests/cohort_qual_sim) and the kernel differ in exp10 and log10 only.
+constexpr uint32_t QUAL_MAX_CHROMS = 4096;               // 2 x 4097 doubles = 65.6 KB of LDS a block: 2 048 diploid samples
+constexpr double QUAL_THETA_MAX = 0.05;                  // 0.05 H_4096 = 0.445 < 1: phi_0 > 0 for every accepted call
+constexpr double QUAL_LOG10_2_HI = 0.3010299956639812, QUAL_LOG10_2_LO = -2.8037281277851704e-18;   // log10 2 as a double-double
+// |qual - model|, the model being tests/cohort_qual_model.py at 60 digits, is measured, not assumed (2026-10-20, one MI355X, ROCm 7.2.0,
+// tests/test_cohort_qual_gpu.py: the 16 cases of tests/cohort_qual_cases.py, 3 235 rows with a quality, 1..2 048 samples): at most 3.769e-15
+// absolute among the rows whose model value is below 1 and 1.993e-15 relative among the others, both at shallow_600 (600 samples of one read;
+// every other case stays below 1.2e-15 and 9.8e-16).  The host harness on the same cases (tests/cohort_qual_sim, glibc's pow and log10):
+// 8.210e-15 and 1.993e-15 with the sums in the kernel's order, 1.043e-14 and 1.993e-15 sequentially.  The tests assert
+// |qual - model| <= QUAL_ABS + QUAL_REL * model with 8 x the device's maximum of each (the EM_F_BOUND convention: the margin is for other
+// seeds, not for other arithmetic).
+constexpr double QUAL_ABS_MEASURED = 3.769e-15, QUAL_REL_MEASURED = 1.993e-15;
+constexpr double QUAL_ABS = 8 * QUAL_ABS_MEASURED, QUAL_REL = 8 * QUAL_REL_MEASURED;
+
+struct QualItem { PriorItem it; dd d0; };                // it: prior_item's, unchanged; d0 = l_0 - l_gmax (0 for an item that takes no part)
+
+// prior_item and, beside it, d_0 (l_gmax is prior_item's `best`: gmax is the first g with the largest l_g)
+SVJG_HD void qual_item(uint32_t type, uint32_t ref, uint32_t alt, uint32_t P, const double *lr, const double *la, QualItem &o) {
+    double c_sum;
+    prior_item(type, ref, alt, P, lr, la, c_sum, o.it);
+    o.d0 = dd{0.0, 0.0};
+    if (o.it.P) {
+        double c1, c2; uint32_t r1, r2;
+        geno_counts(type, ref, alt, c1, c2, r1, r2);
+        o.d0 = dd_add(geno_lik(c1, c2, P, 0, lr, la), dd_neg(geno_lik(c1, c2, P, o.it.gmax, lr, la)));
+    }
+}
+
+// The item of ploidy P (0: the gate or the ploidy keeps it out) with the raw counts ref / alt on the call's table tab = ploidy_log_table
+SVJG_HD void qual_load(uint32_t type, uint32_t ref, uint32_t alt, uint32_t P, const double *tab, QualItem &o) {
+    o.it.P = 0; o.it.gmax = 0; o.d0 = dd{0.0, 0.0};
+    SVJG_UNROLL
+    for (uint32_t g = 0; g <= MAX_PLOIDY; ++g) o.it.w[g] = 0.0;
+    if (P >= 1 && P <= MAX_PLOIDY) qual_item(type, ref, alt, P, tab + ploidy_tab_at(P, 0), tab + PLOIDY_TAB + ploidy_tab_at(P, 0), o);
+}
+
+// steps between two rescalings of a row (above)
+SVJG_HD uint32_t qual_rescale_every(uint32_t m_max, uint32_t max_ploidy) {
+    uint32_t bits = 0;
+    while ((m_max >> bits) != 0) ++bits;
+    const uint32_t n = 512u / (max_ploidy * (bits ? bits : 1u));
+    return n < 1 ? 1u : n;
+}
+
+// (M)_P, the recurrence's denominator, from the top factor down
+SVJG_HD double qual_den(uint32_t M, uint32_t P) {
+#ifdef __clang__
+#pragma clang fp contract(off)
+#endif
+    double d = 1.0;
+    SVJG_UNROLL
+    for (uint32_t i = 0; i < MAX_PLOIDY; ++i) if (i < P) d *= (double)(M - i);
+    return d;
+}
+
+// y_k of M = M0 + P chromosomes from the row y of M0 (entries 0..M0), den = qual_den(M, P).  t_g = (a_g (M - k)_(P-g)) (k)_g: the first factorial
+// from the top genotype down, the second from the bottom up, as prior_terms forms its powers; the sum over g in increasing g, then ONE division.
+// A factorial that runs through 0 makes its term 0 (g > k, or k - g > M0): nothing is read for such a term.  t[] is only ever indexed by constants.
+SVJG_HD double qual_fold(const PriorItem &it, const double *y, uint32_t M0, uint32_t M, uint32_t k, double den) {
+#ifdef __clang__
+#pragma clang fp contract(off)
+#endif
+    double t[MAX_PLOIDY + 1];
+    const double rest = (double)(M - k), kk = (double)k;
+    double b = 1.0;
+    SVJG_UNROLL
+    for (int g = (int)MAX_PLOIDY; g >= 0; --g) {
+        t[g] = 0.0;
+        if ((uint32_t)g > it.P) continue;
+        if ((uint32_t)g < it.P) b *= rest - (double)(it.P - (uint32_t)g - 1u);
+        t[g] = it.w[g] * b;
+    }
+    double a = 1.0;
+    SVJG_UNROLL
+    for (uint32_t g = 1; g <= MAX_PLOIDY; ++g) {
+        if (g > it.P) continue;
+        a *= kk - (double)(g - 1u);
+        t[g] *= a;
+    }
+    double acc = 0.0;
+    SVJG_UNROLL
+    for (uint32_t g = 0; g <= MAX_PLOIDY; ++g) {
+        if (g > it.P) continue;
+        const bool in = g <= k && k - g <= M0;
+        const double v = in ? y[in ? k - g : 0u] : 0.0;
+        acc += t[g] * v;
+    }
+    return acc / den;
+}
+
+// H_0..H_m of a call, each the one before plus 1 / k in double
+inline void qual_harmonic(uint32_t m, double *h) {
+    h[0] = 0.0;
+    for (uint32_t k = 1; k <= m; ++k) h[k] = h[k - 1] + 1.0 / (double)k;
+}
+SVJG_HD double qual_phi0(double theta, double h_m) {
+#ifdef __clang__
+#pragma clang fp contract(off)
+#endif
+    return 1.0 - theta * h_m;
+}
+// phi_k y_k
+SVJG_HD double qual_term(double theta, double phi0, uint32_t k, double y) {
+#ifdef __clang__
+#pragma clang fp contract(off)
+#endif
+    return (k ? theta / (double)k : phi0) * y;
+}
+// The larger of two (phi_k y_k, k), the smaller k at equal values: what a lane keeps over its k and what the butterfly's partners exchange
+struct QualBest { double v; uint32_t k; };
+SVJG_HD QualBest qual_best(QualBest a, QualBest b) { return (b.v > a.v || (b.v == a.v && b.k < a.k)) ? b : a; }
+
+// qual of a row with M > 0 (above): the sum in double-double, E log10 2 as an exact product of the integer and the constant's head plus the tail
+SVJG_HD double qual_finish(double phi0, dd D0, double T, int64_t E) {
+#ifdef __clang__
+#pragma clang fp contract(off)
+#endif
+    dd s = dd_add(dd{log10(phi0), 0.0}, D0);
+    s = dd_add(s, dd{-log10(T), 0.0});
+    const double e = (double)E, p = e * QUAL_LOG10_2_HI, pe = fma(e, QUAL_LOG10_2_HI, -p);
+    s = dd_add(s, two_sum(p, pe + e * QUAL_LOG10_2_LO));
+    dd v = dd_add(dd_add(dd_add(s, s), dd_add(s, s)), s);                      // 5 s
+    v = dd_add(v, v);                                                          // 10 s
+    const double q = -(v.hi + v.lo);
+    return q > 0.0 ? q : 0.0;                                                  // (never -0.0)
+}
+
 // ---- host side of a k_genotype launch: the table's size and where a call's rows lie, in plain integers (pinned without a GPU: tests/test_rows_layout.py) ----
 
 // entries of the log10(i!) table: the first one built; the one that holds max_n (the largest n the kernel met beyond the table, < LOGFACT_CAP) with room to spare
@@ -678,7 +829,7 @@ constexpr uint32_t logfact_reserve_to(uint32_t have, uint32_t entries) { return 
 struct RowsIn { uint64_t slot, type, ok, bytes; };
 inline RowsIn rows_in(uint64_t n, uint64_t at = 0) { return RowsIn{at, at + n * 4, at + n * 5, n * 6}; }
 
-// The seven step-by-step calls (svjg_genotype / _view, _ploidy, _sites, _cohort, _cohort_ploidy, _cohort_prior, _cohort_sites) each own one device block and its pinned host twin, all of ONE
+// The eight step-by-step calls (svjg_genotype / _view, _ploidy, _sites, _cohort, _cohort_ploidy, _cohort_prior, _cohort_sites, svjg_cohort_qual) each own one device block and its pinned host twin, all of ONE
 // shape: the outputs (they end at out_end), the max_n pair 8-aligned, ONE contiguous input region right behind the pair, 64 spare bytes -> ONE copy
 // in (in_bytes from in_at), ONE copy out (maxn + 8 bytes from 0).  A layout below IS a LegSpan and adds only what is its own: its outputs and where its inputs lie.
 struct LegSpan { uint64_t maxn, in_at, in_bytes, total; };
@@ -752,6 +903,17 @@ using CohortPloidyLayout = CohortLayout;
 using CohortPriorLayout = CohortLayout;
 inline CohortLayout cohort_ploidy_layout(uint64_t n_rows, uint64_t S, uint32_t max_ploidy) { return cohort_layout(n_rows, S, max_ploidy, true, false); }
 inline CohortLayout cohort_prior_layout(uint64_t n_rows, uint64_t S, uint32_t max_ploidy, bool per_item) { return cohort_layout(n_rows, S, max_ploidy, per_item, true); }
+
+// svjg_cohort_qual: [ qual 8 | mlac 4 | chroms 4 ] x n_rows of output; in: the call's logarithms (ploidy_log_table), H_0..H_m_max
+// (qual_harmonic), rows_in(n_rows) and, per_item, the n_rows * S ploidy bytes
+struct QualLayout : LegSpan { uint64_t qual, mlac, chroms, logtab, harm;  RowsIn in;  uint64_t ploidy; };
+inline QualLayout qual_layout(uint64_t n_rows, uint64_t S, uint32_t m_max, bool per_item) {
+    QualLayout L{}; uint64_t o = 0; const uint64_t logs = 2 * PLOIDY_TAB * 8, harm = ((uint64_t)m_max + 1) * 8;
+    L.qual = o; o += n_rows * 8; L.mlac = o; o += n_rows * 4; L.chroms = o; o += n_rows * 4;
+    leg_span(L, o, logs + harm + n_rows * 6 + (per_item ? n_rows * S : 0));
+    L.logtab = L.in_at; L.harm = L.logtab + logs; L.in = rows_in(n_rows, L.harm + harm); L.ploidy = L.in.slot + L.in.bytes;
+    return L;
+}
 
 // fused pass (svjg_set_rows, svjg_run_begin, svjg_run_end), per slot.  Host block (pinned, mapped into the device: the genotype kernel
 // writes its results straight into it — they cross PCIe as they are produced, no copy kernel competes with the next pass —): pl32, raw,

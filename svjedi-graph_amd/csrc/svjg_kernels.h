@@ -16,6 +16,7 @@
 //   k_genotype_cohort_ploidy  the same division of work at a ploidy per item, k_genotype_ploidy's arithmetic; NS / AN / AC per row by wave ballots
 //   k_genotype_cohort_sites   one (site, sample) item per lane: the candidates present for the sample, k_genotype_sites' arithmetic; NS / AC per candidate by wave ballots
 //   k_cohort_prior    behind either cohort kernel: a row per wave segment, its allele frequency by EM over its samples, posterior GT and GQ per item
+//   k_cohort_qual     a row per wave over the cohort matrix: the exact allele-count posterior folded in sample by sample in LDS, site quality and MLAC per row
 //   k_cohort_store / k_cohort_load  one sample's column of that matrix from / to a dense count vector
 #pragma once
 #include <hip/hip_runtime.h>
@@ -2293,6 +2294,101 @@ __global__ __launch_bounds__(TPB) void k_cohort_prior(CohortPriorArgs p) {
         p.af[r] = row.f; p.steps[r] = row.steps;
         p.site[r * 3] = ns; p.site[r * 3 + 1] = an; p.site[r * 3 + 2] = ac;
     }
+  }
+}
+
+// ---- cohort site quality: the exact allele-count posterior (svjg_cohort_qual; the model: svjg_geno.h) ----
+// g: the cohort kernels' gate arguments (counts = the matrix, slot / type / ok, n_rows, n_slots, max_n for the gate's "slot out of range" word);
+// nothing else of it is read.  ploidy: one byte per item, row-major, or nullptr = 2 everywhere.  harm: H_0..H_m_max.  every: qual_rescale_every.
+struct CohortQualArgs {
+    GenoArgs g;
+    const uint8_t *present; uint32_t n_samples;
+    const uint8_t *ploidy; const double *logtab, *harm;
+    uint32_t max_ploidy, m_max, every; double theta;
+    double *qual; uint32_t *mlac, *chroms;
+};
+constexpr uint32_t QUAL_TPB = 64;
+constexpr uint32_t qual_lds_bytes(uint32_t m_max) { return 2u * (m_max + 1u) * 8u; }
+
+// the butterfly over the wave's 64 lanes, the same bits in every lane: partners combine the same two values at every level (a sum, or qual_best)
+__device__ inline QualBest qual_wave_best(QualBest b) {
+    for (uint32_t m = 1; m < 64; m <<= 1) b = qual_best(b, QualBest{__shfl_xor(b.v, (int)m), (uint32_t)__shfl_xor((int)b.k, (int)m)});
+    return b;
+}
+
+// One row per wave, one wave per block, rows in strides of the grid.  y lives in the block's dynamic LDS as two rows of m_max + 1 doubles, used
+// ping-pong: a step reads `cur` and writes `nxt`, lane j the entries k = j, j + 64, ..., and ONE barrier stands between a step's writes and the
+// next step's reads (a __syncthreads() of a one-wave block).  The item of a step is loaded through cohort_gate and built by qual_load in ALL 64
+// lanes redundantly: every lane reads the same addresses (one broadcast transaction each) and runs the same P + 1 exp10, which costs the wave
+// what one lane would and needs no broadcast of nine weights; "the item takes part" is then the same in every lane, and made a scalar by
+// readfirstlane so that the branch around a step is the wave's.  A rescaling (every p.every steps) takes the maximum over a lane's own
+// entries, the butterfly, and multiplies the lane's own entries: a lane touches only what it wrote itself, so the step's barrier behind it is
+// the only one it needs.  The row's sums over k (T, and the argmax for mlac) are lane-strided partials in increasing k and the butterfly.
+// Determinism: the outputs come from no atomic — the only one is the gate's flag for a slot out of range, an error word — and two runs give
+// equal bytes.  Every shuffle and barrier is executed by all 64 lanes on every trip: the loop bounds (rows, samples, whether an item takes
+// part, whether a rescaling is due) are the same in every lane, for rows of a later grid trip and rows with M = 0 alike.
+// At S samples of ploidy P a step keeps min(64, M + 1) lanes busy: below 32 diploid samples most lanes of the wave idle (several
+// small rows a wave, and several waves a large row, are left until a measurement asks for them).
+// Compile remarks (ROCm 7.2.0, gfx950): 118 VGPRs, 106 SGPRs (44 of them spilled to VGPR lanes), 0 bytes of scratch, 4 waves a SIMD, 720 bytes of
+// static LDS beside the dynamic 16 (m_max + 1).
+__global__ __launch_bounds__(QUAL_TPB) void k_cohort_qual(CohortQualArgs p) {
+  __shared__ double tab[2 * PLOIDY_TAB];
+  extern __shared__ double qual_y[];
+  stage_ploidy_tab(tab, p.logtab);
+  const GenoArgs &a = p.g;
+  const uint64_t S = p.n_samples;
+  const uint32_t lane = threadIdx.x;
+  for (uint64_t r = blockIdx.x; r < a.n_rows; r += gridDim.x) {
+    double *cur = qual_y, *nxt = qual_y + (p.m_max + 1u);
+    if (lane == 0) cur[0] = 1.0;
+    __syncthreads();
+    uint32_t M = 0, since = 0;
+    int64_t E = 0;
+    dd D0{0.0, 0.0};
+    for (uint64_t s = 0; s < S; ++s) {
+        const uint32_t P = p.ploidy ? p.ploidy[r * S + s] : 2u;
+        uint32_t ref, alt;
+        const bool go = cohort_gate(a, p.present, r, s, S, P >= 1 && P <= p.max_ploidy, ref, alt);
+        QualItem it;
+        qual_load(go ? a.sv_type[r] : 0u, ref, alt, go ? P : 0u, tab, it);
+        const uint32_t Pu = (uint32_t)__builtin_amdgcn_readfirstlane((int)it.it.P);
+        if (Pu == 0 || M + Pu > p.m_max) continue;                             // (the second: never, the host has refused such a call; nothing is written beyond the rows)
+        D0 = dd_add(D0, it.d0);
+        const uint32_t Mn = M + Pu;
+        const double den = qual_den(Mn, Pu);
+        for (uint32_t k = lane; k <= Mn; k += 64) nxt[k] = qual_fold(it.it, cur, M, Mn, k, den);
+        M = Mn;
+        { double *t = cur; cur = nxt; nxt = t; }
+        if (++since == p.every) {
+            since = 0;
+            double m = 0.0;
+            for (uint32_t k = lane; k <= M; k += 64) m = fmax(m, cur[k]);
+            for (uint32_t x = 1; x < 64; x <<= 1) m = fmax(m, __shfl_xor(m, (int)x));
+            if (m > 0.0) {                                                     // (always: the maximum shrinks by a bounded factor a step)
+                const int e = ilogb(m);
+                const double sc = ldexp(1.0, -e);
+                for (uint32_t k = lane; k <= M; k += 64) cur[k] *= sc;
+                E -= e;
+            }
+        }
+        __syncthreads();
+    }
+    double T = 0.0;
+    QualBest best{-1.0, 0u};
+    const double phi0 = qual_phi0(p.theta, p.harm[M]);
+    for (uint32_t k = lane; k <= M; k += 64) {
+        const double v = qual_term(p.theta, phi0, k, cur[k]);
+        T += v;
+        best = qual_best(best, QualBest{v, k});
+    }
+    for (uint32_t x = 1; x < 64; x <<= 1) T += __shfl_xor(T, (int)x);
+    best = qual_wave_best(best);
+    if (lane == 0) {
+        p.chroms[r] = M;
+        p.mlac[r] = M ? best.k : 0u;
+        p.qual[r] = M ? qual_finish(phi0, D0, T, E) : NAN;
+    }
+    __syncthreads();                                                           // the next row's first write lies behind this row's last read
   }
 }
 

@@ -6,6 +6,7 @@
     predict-genotype.py --cohort LIST --cohort-ploidy FILE -v VCF ...                       (extension: a ploidy per sample and contig or region)
     predict-genotype.py --cohort LIST --cohort-prior [--cohort-ploidy FILE] -v VCF ...      (extension: calls under the cohort's allele frequency, with GQ)
     predict-genotype.py --cohort LIST --joint-ins -v VCF ...                                (extension: insertions that share a position, together per sample)
+    predict-genotype.py --cohort LIST --cohort-qual [--cohort-theta X] -v VCF ...           (extension: SVQ / MLAC / MLAF, the cohort's exact allele-count posterior)
 """
 import argparse
 import os
@@ -41,6 +42,12 @@ def main():
     ap.add_argument("--cohort-prior", action="store_true",
                     help="with --cohort: estimate each row's allele frequency from all samples by EM under Hardy-Weinberg and call every sample at "
                          "the maximum of likelihood x prior; FORMAT gains GQ, INFO gains EMAF and EMNC, DP / AD / PL stay as without it (extension)")
+    ap.add_argument("--cohort-qual", action="store_true",
+                    help="with --cohort: INFO gains SVQ, the site quality (-10 log10 of the posterior probability that no sample carries the alt "
+                         "allele, from the exact allele-count posterior over all samples' likelihoods), and MLAC / MLAF at the posterior's maximum; "
+                         "the QUAL column and everything else stay as without it; not with --joint-ins (extension)")
+    ap.add_argument("--cohort-theta", metavar="<theta>", type=float,
+                    help="with --cohort-qual: the prior of k alt copies in the cohort is theta / k, a value in (0, 0.05] (default: 0.001)")
     args = ap.parse_args()
     if args.cohort is not None and args.aln is not None:
         ap.error("exactly one of -d and --cohort")
@@ -55,11 +62,20 @@ def main():
         ap.error("--joint-ins is diploid only: it cannot be combined with --ploidy or --ploidy-file")
     if args.joint_ins and (args.cohort_ploidy is not None or args.cohort_prior):
         ap.error("--joint-ins is diploid only: with --cohort it cannot be combined with --cohort-ploidy or --cohort-prior")
+    if args.cohort_qual and args.cohort is None:
+        ap.error("--cohort-qual needs --cohort")
+    if args.cohort_theta is not None and not args.cohort_qual:
+        ap.error("--cohort-theta needs --cohort-qual")
+    if args.cohort_theta is not None and not 0.0 < args.cohort_theta <= 0.05:
+        ap.error("--cohort-theta: a value in (0, 0.05]")
+    if args.joint_ins and args.cohort_qual:
+        ap.error("--joint-ins cannot be combined with --cohort-qual: the site model there is multi-allelic")
     out = "genotype_results.txt" if args.output is None else args.output[0]
     err = args.err[0] if args.err is not None else 0.00005
     from svjg import genotype
     if args.cohort is not None:
-        genotype.run_cohort(args.cohort, args.vcf, out, args.minsupport, err, ploidy_file=args.cohort_ploidy, prior=args.cohort_prior, joint_ins=args.joint_ins)
+        genotype.run_cohort(args.cohort, args.vcf, out, args.minsupport, err, ploidy_file=args.cohort_ploidy, prior=args.cohort_prior, joint_ins=args.joint_ins,
+                            qual=args.cohort_qual, theta=0.001 if args.cohort_theta is None else args.cohort_theta)
         return
     genotype.run(args.aln[0], args.vcf, out, args.minsupport, err, ploidy=args.ploidy, ploidy_file=args.ploidy_file, joint_ins=args.joint_ins)
 

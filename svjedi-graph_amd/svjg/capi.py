@@ -93,6 +93,7 @@ _SIGS = {
     "svjg_genotype_cohort_ploidy": (ctypes.c_int, [ctypes.c_void_p] * 5 + [ctypes.c_uint32, ctypes.c_uint64, ctypes.c_uint32, ctypes.c_double] + [ctypes.c_void_p] * 6),
     "svjg_genotype_cohort_prior": (ctypes.c_int, [ctypes.c_void_p] * 5 + [ctypes.c_uint32, ctypes.c_uint64, ctypes.c_uint32, ctypes.c_double] + [ctypes.c_void_p] * 9),
     "svjg_genotype_cohort_sites": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_uint32, ctypes.c_double] + [ctypes.c_void_p] * 6),
+    "svjg_cohort_qual": (ctypes.c_int, [ctypes.c_void_p] * 5 + [ctypes.c_uint32, ctypes.c_uint64, ctypes.c_double, ctypes.c_double] + [ctypes.c_void_p] * 3),
     "svjg_set_rows": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64]),
     "svjg_run_resident": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_uint64, ctypes.c_uint32, ctypes.c_double] + [ctypes.POINTER(ctypes.c_void_p)] * 5),
     "svjg_run_begin": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_uint64, ctypes.c_uint32, ctypes.c_double]),
@@ -115,6 +116,7 @@ EXPORTS = tuple(_SIGS) + ("svjg_write_informative_json", "svjg_count_informative
 MAX_PLOIDY = 8                      # svjg.h: SVJG_MAX_PLOIDY
 MAX_SITE_ALTS = 6                   # svjg.h: SVJG_MAX_SITE_ALTS
 SITE_GENOTYPES = 28                 # svjg.h: SVJG_SITE_GENOTYPES
+QUAL_THETA = 1e-3                   # the default theta of the site quality (svjg_cohort_qual; the library takes a value in (0, 0.05])
 _lib = None
 _host_lib = None
 
@@ -597,6 +599,26 @@ class Context:
         genotyped[n, S], boundary[n, S] — pl, raw, genotyped and boundary as genotype_cohort / genotype_cohort_ploidy give them —, site[n, 3] =
         NS, AN, AC of the posterior calls, gq[n, S] (0xFF: none), af[n] (NaN: no estimate), em_steps[n] (bit 31: not converged))"""
         return self._cohort_call("svjg_genotype_cohort_prior", sv_type, slot, ok, ploidy, max_ploidy, min_support, err)
+
+    def cohort_qual(self, sv_type, slot, ok, ploidy, max_ploidy, err, theta=QUAL_THETA):
+        """The site quality of every row against the cohort matrix: the exact allele-count posterior (svjg_cohort_qual).  ploidy: [n, S] in
+        0..max_ploidy, or None = every item diploid (max_ploidy must then be 2).  -> (qual[n] = -10 log10 of the posterior of "no alt copy in the
+        cohort", NaN where no item took part; mlac[n] = the allele count at the posterior's maximum; chroms[n] = the chromosomes that took part)"""
+        n = len(sv_type)
+        S = getattr(self, "_cohort", (0, 0))[0]
+        max_ploidy = int(max_ploidy)
+        if not 0 <= max_ploidy <= 0xFFFFFFFF:
+            raise SvjgError("max_ploidy: 1..%d" % MAX_PLOIDY)
+        sv_type, slot, ok = _row_inputs(sv_type, slot, ok)
+        if ploidy is not None:
+            ploidy = np.asarray(ploidy)
+            if ploidy.shape != (n, S) or (ploidy.size and (int(ploidy.min()) < 0 or int(ploidy.max()) > 255)):
+                raise SvjgError("ploidy: one value in 0..max_ploidy per (row, sample)")
+            ploidy = np.ascontiguousarray(ploidy, dtype=np.uint8)
+        out = (np.empty(n, np.float64), np.empty(n, np.uint32), np.empty(n, np.uint32))
+        self._chk(self.lib.svjg_cohort_qual(self.h, sv_type.ctypes.data, slot.ctypes.data, ok.ctypes.data, None if ploidy is None else ploidy.ctypes.data,
+                                            max_ploidy, n, float(err), float(theta), *(a.ctypes.data for a in out)))
+        return out
 
     def genotype_cohort_sites(self, slots, min_support, err):
         """genotype_sites for every sample of the cohort matrix in one launch (svjg_genotype_cohort_sites).  slots[n, 6]: the CANDIDATE slots of each

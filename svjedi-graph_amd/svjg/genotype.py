@@ -531,6 +531,7 @@ COHORT_INFO_LINES = (
 )
 _SITE_TAGS = ("NS=", "AN=", "AC=", "AF=")
 _EM_KEYS = ("EMAF", "EMNC")
+_QUAL_KEYS = ("SVQ", "MLAC", "MLAF")
 COHORT_ITEM_BYTES = 37             # svjg.h: what one (row, sample) item takes in a svjg_genotype_cohort call
 COHORT_CALL_BYTES = 1 << 30
 
@@ -575,14 +576,18 @@ def cohort_union(samples):
     return list(slot_of), per
 
 
-def cohort_info(info, ns, ac, an=None, em=None):
+def cohort_info(info, ns, ac, an=None, em=None, qual=None):
     """the INFO column of a cohort row: the input's without any NS= / AN= / AC= / AF= field (whole fields, exact key), a lone `.` replaced,
     then NS, AN (2 NS unless given: the called samples' ploidies summed, --cohort-ploidy), AC and, when AN > 0, AF = "%.6g" % (AC / AN).
     em (--cohort-prior): (f, not_converged) of the row's EM — the input's EMAF= and EMNC fields are dropped too, EMAF = "%.6g" % f follows
-    unless f is NaN (no estimate), and the flag EMNC when the step cap was reached"""
+    unless f is NaN (no estimate), and the flag EMNC when the step cap was reached.  qual (--cohort-qual): (svq, mlac, chroms) of the row's
+    allele-count posterior — the input's SVQ= / MLAC= / MLAF= fields are dropped too; behind everything else SVQ = "%.2f" % svq unless it is NaN
+    (a value that prints as -0.00 prints 0.00) and, where chroms > 0, MLAC and MLAF = "%.6g" % (mlac / chroms)"""
     keep = [f for f in info.split(";") if not f.startswith(_SITE_TAGS)]
     if em is not None:
         keep = [f for f in keep if f.split("=", 1)[0] not in _EM_KEYS]
+    if qual is not None:
+        keep = [f for f in keep if f.split("=", 1)[0] not in _QUAL_KEYS]
     if keep == ["."]:
         keep = []
     if an is None:
@@ -596,6 +601,13 @@ def cohort_info(info, ns, ac, an=None, em=None):
             keep.append("EMAF=%s" % ("%.6g" % f))
         if not_converged:
             keep.append("EMNC")
+    if qual is not None:
+        svq, mlac, chroms = qual
+        if svq == svq:
+            text = "%.2f" % svq
+            keep.append("SVQ=%s" % ("0.00" if text == "-0.00" else text))
+        if chroms > 0:
+            keep += ["MLAC=%d" % mlac, "MLAF=%s" % ("%.6g" % (mlac / chroms))]
     return ";".join(keep)
 
 
@@ -616,12 +628,14 @@ def _joint_columns(rows, raw, plain, joint):
     return columns
 
 
-def write_vcf_cohort(out_path, rows, names, gt, pl, raw, done, site, ploidy=None, gq=None, af=None, em_steps=None, joint=None):
+def write_vcf_cohort(out_path, rows, names, gt, pl, raw, done, site, ploidy=None, gq=None, af=None, em_steps=None, joint=None, qual=None):
     """The one cohort writer: write_vcf with one column per sample (gt, done: [n, S]; pl: [n, S, >= 3]; raw: [n, S, 2]), the site tags' INFO lines
     in front of the header and the tags in INFO; site: [n, 2] = NS, AC or [n, 3] = NS, AN, AC.  ploidy ([n, S]; None: diploid arrays, `Number=3`):
     every item in write_vcf_ploidy's forms (pl: [n, S, >= P + 1]) and `Number=G` in the PL header line.  --cohort-prior: gq[n, S], one more
     FORMAT field, GQ; af[n] and em_steps[n], EMAF / EMNC in INFO.  joint (--joint-ins; cohort_joint_sites): the rows that are members of a site
-    for at least one sample, printed by _joint_columns, and SITE_FORMAT_LINES behind the PL line.  -> the number of genotyped rows of every sample"""
+    for at least one sample, printed by _joint_columns, and SITE_FORMAT_LINES behind the PL line.  qual (--cohort-qual; cohort_qual_rows): (svq[n],
+    mlac[n], chroms[n]), SVQ / MLAC / MLAF behind the other tags in INFO and their three header lines; the QUAL column stays the input's.
+    -> the number of genotyped rows of every sample"""
     columns, n_done = _item_columns(rows, ploidy, gt, pl, raw, done, gq)
     header = FORMAT_HEADER if ploidy is None else FORMAT_HEADER.replace(_PL_3, _PL_G)
     if joint is not None:
@@ -629,11 +643,12 @@ def write_vcf_cohort(out_path, rows, names, gt, pl, raw, done, site, ploidy=None
         header = header.replace(_PL_LINE, _PL_LINE + SITE_FORMAT_LINES)
     if gq is not None:
         header = header.replace("#CHROM\t", _GQ_LINE + "#CHROM\t")
-    header = COHORT_INFO_LINES + (COHORT_PRIOR_INFO_LINES if af is not None else "") + header.replace("\tFORMAT\tSAMPLE\n", "\tFORMAT\t" + "\t".join(names) + "\n")
+    header = COHORT_INFO_LINES + (COHORT_PRIOR_INFO_LINES if af is not None else "") + (COHORT_QUAL_INFO_LINES if qual is not None else "") + header.replace("\tFORMAT\tSAMPLE\n", "\tFORMAT\t" + "\t".join(names) + "\n")
     an = np.shape(site)[1] == 3
     _write_rows(out_path, rows, header, columns,
                 lambda v, info: cohort_info(info, int(site[v, 0]), int(site[v, -1]), int(site[v, 1]) if an else None,
-                                            None if af is None else (float(af[v]), bool(int(em_steps[v]) & EM_NOT_CONVERGED))))
+                                            None if af is None else (float(af[v]), bool(int(em_steps[v]) & EM_NOT_CONVERGED)),
+                                            None if qual is None else (float(qual[0][v]), int(qual[1][v]), int(qual[2][v]))))
     return n_done
 
 
@@ -768,6 +783,34 @@ _GQ_LINE = '##FORMAT=<ID=GQ,Number=1,Type=Integer,Description="Genotype quality:
 EM_NOT_CONVERGED = 1 << 31         # svjg.h: bit 31 of a row's em_steps word
 
 
+# ---- cohort site quality (--cohort LIST --cohort-qual [--cohort-theta X]): svjg_cohort_qual beside whichever cohort call the run makes ----
+
+COHORT_QUAL_INFO_LINES = (
+    '##INFO=<ID=SVQ,Number=1,Type=Float,Description="Site quality: -10 log10 of the posterior probability that no sample of the cohort carries the alt allele (exact allele-count posterior)">\n'
+    '##INFO=<ID=MLAC,Number=A,Type=Integer,Description="Allele count at the maximum of the cohort\'s allele-count posterior">\n'
+    '##INFO=<ID=MLAF,Number=A,Type=Float,Description="MLAC over the chromosomes of the samples whose reads took part">\n'
+)
+COHORT_QUAL_THETA = 1e-3           # the default of --cohort-theta
+COHORT_QUAL_THETA_MAX = 0.05       # svjg.h: theta of svjg_cohort_qual lies in (0, 0.05]
+JOINT_INS_QUAL = "--joint-ins cannot be combined with --cohort-qual: the site model there is multi-allelic"
+
+
+def cohort_qual_rows(ctx, rows, n_samples, ploidy, err, theta=COHORT_QUAL_THETA, step=None):
+    """svjg_cohort_qual over all rows, in the row chunks of the cohort call (step: rows per call, None: cohort_chunk_rows of the plain call — a row's
+    answer depends on no other row, so any chunking gives the same bytes).  ploidy[n, S] or None (diploid) -> (qual[n], mlac[n], chroms[n])"""
+    _, call_err, _ = _call_args(0, err)
+    if ploidy is not None:
+        ploidy = np.ascontiguousarray(ploidy, dtype=np.uint8)
+    max_ploidy = 2 if ploidy is None else max(1, int(ploidy.max())) if ploidy.size else 1
+    if step is None:
+        step = cohort_chunk_rows(n_samples, None if ploidy is None else max_ploidy)
+    parts = [ctx.cohort_qual(rows.sv_type[at:at + step], rows.slot[at:at + step], rows.ok[at:at + step], None if ploidy is None else ploidy[at:at + step],
+                             max_ploidy, call_err, theta) for at in range(0, len(rows.sv_type), int(step))]
+    if not parts:
+        return np.zeros(0, np.float64), np.zeros(0, np.uint32), np.zeros(0, np.uint32)
+    return tuple(np.concatenate([p[k] for p in parts]) for k in range(3))
+
+
 # ---- cohort calls for insertions that share a position (--cohort LIST --joint-ins): svjg_genotype_cohort_sites behind the plain cohort call ----
 
 JOINT_INS_COHORT = "--joint-ins is diploid only: with --cohort it cannot be combined with --cohort-ploidy or --cohort-prior"
@@ -840,7 +883,8 @@ def cohort_joint_sites(ctx, rows, gt, site, min_support, err, step=None):
     return site, joint
 
 
-def run_cohort(list_path, vcf_path, out_path, min_support=3, err=0.00005, device=0, ploidy_file=None, prior=False, joint_ins=False):
+def run_cohort(list_path, vcf_path, out_path, min_support=3, err=0.00005, device=0, ploidy_file=None, prior=False, joint_ins=False, qual=False,
+               theta=COHORT_QUAL_THETA):
     """predict-genotype.py --cohort: the samples of a cohort list (load_cohort_list), one multi-sample VCF.  Sample column s is what the
     reference writes as SAMPLE for sample s alone; INFO gains NS, AN, AC and AF.  ploidy_file (--cohort-ploidy, load_cohort_ploidy_file): a
     ploidy per sample and contig or region; column s is then what --ploidy-file with the sample's lines writes for sample s alone, and AN is
@@ -848,10 +892,16 @@ def run_cohort(list_path, vcf_path, out_path, min_support=3, err=0.00005, device
     (svjg_genotype_cohort_prior), with GQ beside it and EMAF / EMNC in INFO; DP, AD and PL stay those of the plain run.  joint_ins (--joint-ins,
     diploid only: neither ploidy_file nor prior): the insertions that share a position are genotyped together per sample (cohort_joint_sites);
     column s is then what --joint-ins writes for sample s alone, but for `:.:.` behind a sample that has no site on a row another sample has one
-    on, and for a position with more than six candidate rows, which is skipped for EVERY sample.  -> the number of genotyped rows of every sample"""
+    on, and for a position with more than six candidate rows, which is skipped for EVERY sample.  qual (--cohort-qual, theta: --cohort-theta; with
+    any of the above but joint_ins): INFO gains SVQ, MLAC and MLAF of the row's exact allele-count posterior (svjg_cohort_qual); every other byte
+    of the file stays what it is without it.  -> the number of genotyped rows of every sample"""
     from . import capi, filter as flt
     if joint_ins and (ploidy_file is not None or prior):
         raise ValueError(JOINT_INS_COHORT)                       # (before anything is read, asked of the device or written)
+    if joint_ins and qual:
+        raise ValueError(JOINT_INS_QUAL)
+    if qual and not 0.0 < theta <= COHORT_QUAL_THETA_MAX:
+        raise ValueError("theta: a value in (0, %g]" % COHORT_QUAL_THETA_MAX)
     samples = load_cohort_list(list_path)                        # (raises before any output exists)
     names = [name for name, _ in samples]
     regions = load_cohort_ploidy_file(ploidy_file, names) if ploidy_file is not None else None   # (so does this)
@@ -871,9 +921,10 @@ def run_cohort(list_path, vcf_path, out_path, min_support=3, err=0.00005, device
         joint = None
         if joint_ins:
             site, joint = cohort_joint_sites(ctx, rows, gt, site, min_support, err)
+        site_qual = cohort_qual_rows(ctx, rows, len(samples), ploidy, err, theta) if qual else None
     finally:
         ctx.close()
-    n_done = write_vcf_cohort(out_path, rows, names, gt, pl, raw, done, site, ploidy, *em, joint=joint)
+    n_done = write_vcf_cohort(out_path, rows, names, gt, pl, raw, done, site, ploidy, *em, joint=joint, qual=site_qual)
     for name, n in zip(names, n_done):
         print("Genotyped svs (%s): %d" % (name, n))
     return n_done

@@ -1,0 +1,291 @@
+"""The cohort site quality without a GPU: the recurrence of the 60-digit model (tests/cohort_qual_model.py) against an enumeration of every
+genotype configuration and against Li's three-term form; the per-row routines of svjg_geno.h compiled with g++ (tests/cohort_qual_sim), in a
+sequential order and in the kernel's order of the sums, against the model's stored answers (tests/golden/cohort_qual/), which are recomputed on a
+sample of rows; the regime that forces the normalised recurrence; the block's layout and the rescaling's cadence; the writer's text; the
+script's argument errors."""
+import itertools
+import math
+import os
+import subprocess
+import sys
+from decimal import Decimal, localcontext
+from fractions import Fraction
+
+import numpy as np
+import pytest
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+from tests import cohort_prior_model as PM            # noqa: E402
+from tests import cohort_qual_cases as QC             # noqa: E402
+from tests import cohort_qual_model as M              # noqa: E402
+from tests.cohort_qual_sim import sim                 # noqa: E402
+from tests.cohort_prior_sim import sim as prior_sim   # noqa: E402
+
+AMD = os.path.join(ROOT, "svjedi-graph_amd")
+ALL = [c[0] for c in QC.CASES]
+
+
+def _random_items(rng, S, ploidies):
+    """S items that take part, inside a 60-digit context"""
+    items = []
+    while len(items) < S:
+        t, P = int(rng.integers(0, 4)), int(rng.choice(ploidies))
+        raw = np.array([rng.integers(0, 9, 2)], np.uint32)
+        items += M.row_items(t, raw, np.ones(1, np.uint8), np.array([P], np.uint8), QC.ERR)
+    return items
+
+
+# ---- the model's recurrence against what it abbreviates ----
+
+def test_recurrence_is_the_posterior_of_the_enumeration():
+    """S <= 5 samples of ploidies 1..4: P(AC = k | D) summed over EVERY genotype configuration — the product of the samples' C(P, g) 10^d_g, divided
+    by the C(M, k) placements of k alt copies that the allele-count prior spreads phi_k over — equals phi_k y_k / T of the recurrence to 1e-40.
+    This pins the hypergeometric factor and the prior."""
+    rng = np.random.default_rng(11)
+    with localcontext() as ctx:
+        ctx.prec = M.PREC
+        for trial in range(40):
+            S = 1 + trial % 5
+            items = _random_items(rng, S, (1, 2, 3, 4))
+            Mtot = sum(P for P, _, _ in items)
+            z = [Decimal(0)] * (Mtot + 1)
+            for conf in itertools.product(*[range(P + 1) for P, _, _ in items]):
+                p = Decimal(1)
+                for g, (_, a, _) in zip(conf, items):
+                    p *= a[g]
+                z[sum(conf)] += p
+            phi = M.prior(QC.THETA, Mtot)
+            want = [phi[k] * z[k] / math.comb(Mtot, k) for k in range(Mtot + 1)]
+            got = M.posterior_terms(items, QC.THETA)
+            assert len(got) == Mtot + 1
+            for k in range(Mtot + 1):
+                assert abs(want[k] / sum(want) - got[k] / sum(got)) <= Decimal("1e-40"), (trial, k)
+            # the prior: theta / k, and what is left for k = 0
+            assert phi[1] == Decimal(float(QC.THETA)) and abs(sum(phi) - 1) < Decimal("1e-15") and phi[0] > 0
+
+
+def test_diploid_recurrence_is_li_three_terms():
+    """P = 2: y_k(M) = ((M - k)(M - k - 1) L0 y_k + 2 k (M - k) L1 y_(k-1) + k (k - 1) L2 y_(k-2)) / (M (M - 1)), L_g the genotype likelihoods
+    (a_1 = 2 L1), term for term"""
+    rng = np.random.default_rng(12)
+    with localcontext() as ctx:
+        ctx.prec = M.PREC
+        items = _random_items(rng, 12, (2,))
+        y = [Decimal(1)]
+        for n, (P, a, _) in enumerate(items, 1):
+            Mn = 2 * n
+            L = (a[0], a[1] / 2, a[2])
+            old = y + [Decimal(0), Decimal(0)]
+            new = []
+            for k in range(Mn + 1):
+                v = (Mn - k) * (Mn - k - 1) * L[0] * old[k]
+                if k >= 1:
+                    v += 2 * k * (Mn - k) * L[1] * old[k - 1]
+                if k >= 2:
+                    v += k * (k - 1) * L[2] * old[k - 2]
+                new.append(v / (Mn * (Mn - 1)))
+            y = new
+            got = M.recurrence(items[:n])
+            assert all(abs(u - v) <= Decimal("1e-50") * max(u, Decimal("1e-300")) for u, v in zip(y, got))
+
+
+# ---- the routines of svjg_geno.h, compiled with g++ ----
+
+def test_constants_and_cadence():
+    k = sim.constants()
+    assert k["max_chroms"] == 4096 and k["theta_max"] == 0.05 and k["abs"] == 8 * k["abs_measured"] and k["rel"] == 8 * k["rel_measured"]
+    assert 0 < k["abs"] < 1e-9 and 0 < k["rel"] < 1e-12
+    assert 0.05 * M.harmonic(4096) < 1                                  # phi_0 > 0 for every accepted call
+    # between two rescalings the maximum cannot fall below 2^-512: one step shrinks it by at most 1 / C(M, P)
+    for m_max, P in ((1, 1), (2, 2), (128, 2), (130, 2), (136, 8), (1200, 2), (4096, 2), (4096, 8), (4095, 5)):
+        n = sim.every(m_max, P)
+        assert n >= 1 and (n == 1 or n * math.log2(math.comb(m_max, min(P, m_max))) <= 512)
+    assert math.log2(math.comb(4096, 8)) < 82
+
+
+def test_item_is_prior_item_with_d0_beside_it():
+    rng = np.random.default_rng(13)
+    with localcontext() as ctx:
+        ctx.prec = M.PREC
+        for k in range(400):
+            t, P = int(rng.integers(0, 4)), int(rng.integers(1, 9))
+            ref, alt = (int(x) for x in (rng.integers(0, 61, 2) if k % 3 else rng.integers(0, 5, 2)))
+            p, w, d0 = sim.item(t, ref, alt, P, QC.ERR)
+            p2, w2, _ = prior_sim.item(t, ref, alt, P, QC.ERR)
+            assert p == p2 and w.tobytes() == w2.tobytes()                 # PriorItem, bit for bit
+            c1, c2 = PM.norm_counts(t, ref, alt)
+            if c1 + c2 == 0:
+                assert p == 0 and d0 == (0.0, 0.0)
+                continue
+            want = M.d0_exact(c1, c2, P, QC.ERR)
+            got = Fraction(d0[0]) + Fraction(d0[1])
+            assert abs(got - want) <= abs(want) * Fraction(1, 2 ** 100), (t, ref, alt, P)
+    assert sim.item(0, 7, 7, 0, QC.ERR)[0] == 0 and sim.item(0, 7, 7, 9, QC.ERR)[0] == 0
+
+
+def _compare(name, want, got, keep=None):
+    """-> (the largest |qual - model| among the rows with model < 1, the largest relative one among the others)"""
+    q, ml, ch = got
+    rows = np.ones(len(q), bool) if keep is None else keep
+    assert want["mlac_out"].mean() <= QC.CAP and want["text_out"].mean() <= QC.CAP
+    assert np.array_equal(ch[rows], want["chroms"][rows]), name
+    has = ~np.isnan(want["qual"])
+    assert np.array_equal(np.isnan(q[rows]), ~has[rows]) and not ml[rows & ~has].any() and not ch[rows & ~has].any()
+    on = rows & ~want["mlac_out"]
+    assert np.array_equal(ml[on], want["mlac"][on]), name
+    sel = rows & has
+    d, m = np.abs((q[sel] - want["qual"][sel]) - want["qual_lo"][sel]), want["qual"][sel]
+    k = sim.constants()
+    assert (d <= k["abs"] + k["rel"] * m).all(), (name, float((d - k["rel"] * m).max()))
+    assert (q[sel] >= 0).all() and not np.signbit(q[sel]).any()
+    return (float(d[m < 1].max()) if (m < 1).any() else 0.0, float((d[m >= 1] / m[m >= 1]).max()) if (m >= 1).any() else 0.0)
+
+
+@pytest.mark.parametrize("name", ALL)
+def test_harness_against_the_model(name):
+    """chroms equal, the NaN pattern equal, mlac equal outside the model's margin, |qual - model| <= QUAL_ABS + QUAL_REL model — sequentially and
+    with every sum over k in the kernel's order; a rescaling behind every step changes nothing beyond that bound"""
+    c = QC.inputs(name)
+    want = QC.load_golden(name, c)
+    done, raw = QC.gate(c)
+    worst = [0.0, 0.0]
+    for wave, every in ((False, 0), (True, 0), (True, 1)):
+        got = sim.rows(c["t"], raw, done, c["ploidy"], c["max_ploidy"], QC.ERR, QC.THETA, wave=wave, every=every)
+        a, r = _compare(name, want, got)
+        if every == 0:
+            worst = [max(worst[0], a), max(worst[1], r)]
+    print("%s: max |qual - model| = %.3e absolute (model < 1), %.3e relative (model >= 1)" % (name, worst[0], worst[1]))
+    assert worst[0] <= 1.044e-14 and worst[1] <= 1.994e-15           # what svjg_geno.h says the harness measured (the asserted bound is 8 x the DEVICE's maxima)
+    QC.check_planted(c, done, raw, *got)
+
+
+@pytest.mark.parametrize("name", ALL)
+def test_stored_answers_are_the_models(name):
+    """a sample of rows of every case, recomputed at 60 digits (all of them takes minutes: tests/golden/make_cohort_qual.py)"""
+    c = QC.inputs(name)
+    want = QC.load_golden(name, c)
+    done, raw = QC.gate(c)
+    R = len(c["t"])
+    rows = sorted(set(c["planted"].values()) | set(np.random.default_rng(5).permutation(R)[:6].tolist())) if c["S"] <= 100 else [R - 1] if c["S"] <= 600 else []
+    m = M.run(c["t"], raw, done, c["ploidy"], QC.ERR, QC.THETA, rows=rows)
+    for r in rows:
+        assert m["chroms"][r] == want["chroms"][r] and m["mlac"][r] == want["mlac"][r]
+        assert (np.isnan(m["qual"][r]) and np.isnan(want["qual"][r])) or (m["qual"][r] == want["qual"][r] and np.float32(m["qual_lo"][r]) == np.float32(want["qual_lo"][r]))
+        if not np.isnan(m["qual"][r]):
+            assert bool(m["gap"][r] < QC.TOP_GAP) == bool(want["mlac_out"][r]) and bool(m["half"][r] < QC.HALF_BAND) == bool(want["text_out"][r])
+
+
+def _plain_convolution(items_a, theta):
+    """The textbook form in doubles: z = the convolution of the samples' coefficient rows, rescaled by its maximum after every step (as fair as a
+    convolution can be made), ONE division by C(M, k) at the end, done exactly.  -> (qual, mlac); either may be non-finite or wrong"""
+    z = np.array([1.0])
+    for a in items_a:
+        z = np.convolve(z, np.asarray(a, np.float64))
+        z = z / z.max()
+    M_ = len(z) - 1
+    y = [Fraction(float(v)) / math.comb(M_, k) for k, v in enumerate(z)]
+    phi = [Fraction(1) - Fraction(theta) * Fraction(M.harmonic(M_))] + [Fraction(theta) / k for k in range(1, M_ + 1)]
+    t = [p * v for p, v in zip(phi, y)]
+    top = max(t)
+    p0 = t[0] / sum(t)
+    return (-10 * math.log10(p0) if p0 > 0 else math.inf), t.index(top)
+
+
+def test_the_regime_that_forces_the_normalised_form():
+    """1 200 diploid samples with one ref read each.  The model: a small SVQ, mlac = 0.  The harness agrees, in both orders.  The plain convolution
+    does not: z_k ~ C(2400, k) peaks near k = 1200 at about 2^2394 times z_0, so z_0 / max z underflows to 0 in doubles and the posterior of k = 0 with it."""
+    c = QC.inputs("shallow_1200")
+    want = QC.load_golden("shallow_1200", c)
+    done, raw = QC.gate(c)
+    assert done.all() and (raw[:, :, 0] == 1).all() and not raw[:, :, 1].any()
+    assert want["chroms"][0] == 2400 and want["mlac"][0] == 0 and 0 < want["qual"][0] < 0.1
+    for wave in (False, True):
+        _compare("shallow_1200", want, sim.rows(c["t"], raw, done, None, 2, QC.ERR, QC.THETA, wave=wave))
+    a = [sim.item(int(c["t"][0]), 1, 0, 2, QC.ERR)[1][:3]] * 1200
+    q, ml = _plain_convolution(a, QC.THETA)
+    print("plain convolution: qual %r, mlac %d; the model: %.6f, 0" % (q, ml, want["qual"][0]))
+    assert not math.isfinite(q) or ml != 0 or abs(q - want["qual"][0]) > 1e-3
+    # the same variant is fine where nothing underflows: it is the scale that breaks it, not the variant
+    q12, ml12 = _plain_convolution(a[:12], QC.THETA)
+    m12 = M.run(c["t"], raw[:, :12], done[:, :12], None, QC.ERR, QC.THETA)
+    assert ml12 == m12["mlac"][0] == 0 and abs(q12 - m12["qual"][0]) < 1e-9
+
+
+def test_layout():
+    for n, S, mp, per in ((1, 1, 2, False), (7, 3, 8, True), (1000, 64, 2, False), (1000, 65, 8, True), (3, 2048, 2, False)):
+        L = sim.layout(n, S, S * mp, per)
+        assert (L["qual"], L["mlac"], L["chroms"]) == (0, 8 * n, 12 * n)
+        assert L["maxn"] % 8 == 0 and L["maxn"] >= 16 * n and L["in_at"] == L["maxn"] + 8 == L["logtab"]
+        assert L["harm"] == L["logtab"] + 720 and L["harm"] % 8 == 0 and L["slot"] == L["harm"] + 8 * (S * mp + 1)
+        assert L["type"] == L["slot"] + 4 * n and L["ok"] == L["type"] + n and L["ploidy"] == L["ok"] + n
+        assert L["total"] == L["ploidy"] + (n * S if per else 0) + 64
+
+
+def test_standalone_program_under_the_sanitizers():
+    """the same routines under -fsanitize=address,undefined, in a program of their own"""
+    p = subprocess.run([sim.build_main()], capture_output=True, text=True)
+    assert p.returncode == 0 and "cohort_qual_sim ok" in p.stdout, p.stdout + p.stderr
+
+
+# ---- the writer ----
+
+def test_info_tags():
+    from svjg import genotype
+    f = genotype.cohort_info
+    assert f("SVTYPE=DEL;END=9", 3, 2, qual=(12.3456, 2, 6)) == "SVTYPE=DEL;END=9;NS=3;AN=6;AC=2;AF=0.333333;SVQ=12.35;MLAC=2;MLAF=0.333333"
+    # the input's own SVQ= / MLAC= / MLAF= fields go, whole fields only; NaN: no SVQ; chroms 0: neither MLAC nor MLAF
+    assert f("SVQ=1;MLAC=7;XMLAC=1;MLAF=0.5;SVQX=2;AC=9", 0, 0, qual=(float("nan"), 0, 0)) == "XMLAC=1;SVQX=2;NS=0;AN=0;AC=0"
+    assert f("SVQ=1;MLAC=7", 0, 0) == "SVQ=1;MLAC=7;NS=0;AN=0;AC=0"                    # without the flag nothing is dropped
+    assert f(".", 1, 0, qual=(-0.0, 0, 2)) == "NS=1;AN=2;AC=0;AF=0;SVQ=0.00;MLAC=0;MLAF=0"
+    assert f(".", 1, 0, qual=(0.004, 0, 2)).endswith("SVQ=0.00;MLAC=0;MLAF=0") and f(".", 1, 0, qual=(1e6 + 0.125, 4, 4)).endswith("SVQ=1000000.12;MLAC=4;MLAF=1")
+    # behind the EM's tags
+    assert f("A=1", 2, 1, 4, (0.25, True), (33.0, 1, 4)) == "A=1;NS=2;AN=4;AC=1;AF=0.25;EMAF=0.25;EMNC;SVQ=33.00;MLAC=1;MLAF=0.25"
+
+
+def test_writer(tmp_path, golden):
+    """write_vcf_cohort with the new argument on the cohort fixtures and hand-made arrays: three more header lines, the tags behind the others, every
+    other byte as without it — the QUAL column too"""
+    from svjg import genotype
+    from tests import cohort_model as CM
+    co = CM.Cohort(golden, "plain")
+    n = len(co.rows.slot)
+    qual = (np.where(np.arange(n) % 3 == 0, np.nan, np.arange(n) * 1.005), (np.arange(n) % 5).astype(np.uint32), np.where(np.arange(n) % 3 == 0, 0, 8).astype(np.uint32))
+    plain, with_q = str(tmp_path / "plain.vcf"), str(tmp_path / "qual.vcf")
+    genotype.write_vcf_cohort(plain, co.rows, co.names, co.gt, co.pl, co.raw, co.done, co.site)
+    assert genotype.write_vcf_cohort(with_q, co.rows, co.names, co.gt, co.pl, co.raw, co.done, co.site, qual=qual) == co.genotyped
+    a, b = open(plain).read().split("\n"), open(with_q).read().split("\n")
+    extra = [ln for ln in b if ln not in a and ln.startswith("##")]
+    assert [ln.split(",")[0] for ln in extra] == ["##INFO=<ID=SVQ", "##INFO=<ID=MLAC", "##INFO=<ID=MLAF"]
+    assert (genotype.COHORT_INFO_LINES + genotype.COHORT_QUAL_INFO_LINES) in open(with_q).read()
+    da, db = [ln.split("\t") for ln in a if ln and ln[0] != "#"], [ln.split("\t") for ln in b if ln and ln[0] != "#"]
+    assert len(da) == len(db) == n
+    for v, (x, y) in enumerate(zip(da, db)):
+        assert x[:7] == y[:7] and x[8:] == y[8:]
+        tail = ([] if v % 3 == 0 else ["SVQ=%.2f" % (v * 1.005), "MLAC=%d" % (v % 5), "MLAF=%.6g" % ((v % 5) / 8)])
+        assert y[7] == ";".join([x[7]] + tail)
+
+
+# ---- the script's argument errors: found before any device is asked ----
+
+@pytest.mark.parametrize("args, text", [
+    (["-d", "x.json", "--cohort-qual"], "--cohort-qual needs --cohort"),
+    (["--cohort", "x.list", "--cohort-theta", "0.01"], "--cohort-theta needs --cohort-qual"),
+    (["--cohort", "x.list", "--cohort-qual", "--cohort-theta", "0"], "--cohort-theta: a value in (0, 0.05]"),
+    (["--cohort", "x.list", "--cohort-qual", "--cohort-theta", "0.0501"], "--cohort-theta: a value in (0, 0.05]"),
+    (["--cohort", "x.list", "--cohort-qual", "--cohort-theta", "nan"], "--cohort-theta: a value in (0, 0.05]"),
+    (["--cohort", "x.list", "--cohort-qual", "--cohort-theta=-1e-3"],"--cohort-theta: a value in (0, 0.05]"),
+    (["--cohort", "x.list", "--cohort-qual", "--joint-ins"], "--joint-ins cannot be combined with --cohort-qual"),
+])
+def test_script_flag_errors(tmp_path, args, text):
+    out = str(tmp_path / "never.vcf")
+    p = subprocess.run([sys.executable, f"{AMD}/predict-genotype.py", *args, "-v", "x.vcf", "-o", out], capture_output=True, text=True, cwd=str(tmp_path))
+    assert p.returncode == 2 and text in p.stderr and not os.path.exists(out)
+
+
+def test_run_cohort_refuses_before_anything_is_read(tmp_path):
+    from svjg import genotype
+    for kw, text in (({"joint_ins": True, "qual": True}, "multi-allelic"), ({"qual": True, "theta": 0.0}, "theta"), ({"qual": True, "theta": 0.06}, "theta")):
+        with pytest.raises(ValueError) as ei:
+            genotype.run_cohort(str(tmp_path / "no.list"), str(tmp_path / "no.vcf"), str(tmp_path / "out.vcf"), **kw)
+        assert text in str(ei.value) and not os.path.exists(str(tmp_path / "out.vcf"))
