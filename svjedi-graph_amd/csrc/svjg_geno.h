@@ -440,7 +440,7 @@ SVJG_HD CohortSums cohort_site_member_sums(const SiteBallots &b, uint32_t j, uin
     return CohortSums{ns, 2 * ns, (uint32_t)__builtin_popcountll(b.one[j] & mask) + 2 * (uint32_t)__builtin_popcountll(b.two[j] & mask)};
 }
 
-// ---- what both site kernels do per item (k_genotype_sites, k_genotype_cohort_sites; tests/site_sim runs the same code on the CPU) ----
+// ---- what both site kernels do per item (k_genotype_sites, k_genotype_cohort_sites; tests/geno_sim runs the same code on the CPU) ----
 // The ONE place that reads a site's slots (the named ones first, SITE_NO_SLOT behind them), into sample s of a slot-major count matrix of S samples
 // and n_slots slots (counts[slot * S + s], present[slot * S + s]); the count vector is the matrix of S = 1, s = 0, and present == nullptr says every
 // named slot is a member (the single-sample call).  members: bit j = candidate j is present, cref[j] / calt[j] its raw counts (0 where it is not).
@@ -514,7 +514,7 @@ SVJG_HD SiteItem site_item(const unsigned long long *counts, const uint8_t *pres
 // pi_g(f; P) = C(P, g) f^g (1 - f)^(P - g), powers by repeated multiplication (0^0 = 1); posterior q_g = pi_g w_g / sum_g pi_g w_g, one-hot at
 // the item's largest w_g where that sum is 0; expected copies x = sum_g g q_g.  f_0 = 0.5, f_(k+1) = sum_s x_s / sum_s P_s over the row's items
 // that take part; the row stops after the first step with |f_(k+1) - f_k| <= EM_TOL, or after EM_MAX_IT steps without one ("not converged").
-// Every routine below is compiled without fused multiply-adds, so the host harness (tests/cohort_prior_sim) and the kernel differ in exp10,
+// Every routine below is compiled without fused multiply-adds, so the host harness (tests/geno_sim: prior) and the kernel differ in exp10,
 // log10 and nothing else.
 constexpr double EM_TOL = 1e-9;
 constexpr uint32_t EM_MAX_IT = 128;
@@ -567,7 +567,7 @@ SVJG_HD void prior_item(uint32_t type, uint32_t ref, uint32_t alt, uint32_t P, c
     }
 }
 
-// Item i as the EM sees it (k_cohort_prior and tests/cohort_prior_sim), from what the first kernel left: raw[i][2], genotyped[i], and the call's
+// Item i as the EM sees it (k_cohort_prior and tests/geno_sim), from what the first kernel left: raw[i][2], genotyped[i], and the call's
 // ploidy[i] (nullptr: 2 everywhere), the row's type byte and tab = ploidy_log_table.  The item takes no part (it.P = 0) unless the first kernel
 // genotyped it and it has a read; the type is read only for an item that does (a pointer, so that the kernel's load stays behind that test).
 SVJG_HD void prior_load(const uint8_t *type, const uint32_t *raw, const uint8_t *genotyped, const uint8_t *ploidy, uint64_t i, const double *tab, double &c_sum, PriorItem &it) {
@@ -687,14 +687,14 @@ SVJG_HD uint32_t prior_segment_width(uint64_t S) {
 // T = sum_k phi_k y_k over the scaled y, D_0 = sum_s d_(s,0) in double-double in sample order: the log of the TRUE y_0, which may have
 // underflowed in the scaled array.  Every sum over k is fixed once: lane-strided partials in increasing k (lane j: k = j, j + 64, ...), then the
 // xor butterfly over 64 lanes.  Compiled without fused multiply-adds (the one fma() in qual_finish is an exact product, written out): the
-// harness (tests/cohort_qual_sim) and the kernel differ in exp10 and log10 only.
+// harness (tests/geno_sim: qual) and the kernel differ in exp10 and log10 only.
 constexpr uint32_t QUAL_MAX_CHROMS = 4096;               // 2 x 4097 doubles = 65.6 KB of LDS a block: 2 048 diploid samples
 constexpr double QUAL_THETA_MAX = 0.05;                  // 0.05 H_4096 = 0.445 < 1: phi_0 > 0 for every accepted call
 constexpr double QUAL_LOG10_2_HI = 0.3010299956639812, QUAL_LOG10_2_LO = -2.8037281277851704e-18;   // log10 2 as a double-double
 // |qual - model|, the model being tests/cohort_qual_model.py at 60 digits, is measured, not assumed (2026-10-20, one MI355X, ROCm 7.2.0,
 // tests/test_cohort_qual_gpu.py: the 16 cases of tests/cohort_qual_cases.py, 3 235 rows with a quality, 1..2 048 samples): at most 3.769e-15
 // absolute among the rows whose model value is below 1 and 1.993e-15 relative among the others, both at shallow_600 (600 samples of one read;
-// every other case stays below 1.2e-15 and 9.8e-16).  The host harness on the same cases (tests/cohort_qual_sim, glibc's pow and log10):
+// every other case stays below 1.2e-15 and 9.8e-16).  The host harness on the same cases (tests/geno_sim, glibc's pow and log10):
 // 8.210e-15 and 1.993e-15 with the sums in the kernel's order, 1.043e-14 and 1.993e-15 sequentially.  The tests assert
 // |qual - model| <= QUAL_ABS + QUAL_REL * model with 8 x the device's maximum of each (the EM_F_BOUND convention: the margin is for other
 // seeds, not for other arithmetic).
@@ -897,7 +897,7 @@ inline CohortLayout cohort_layout(uint64_t n_rows, uint64_t S, uint32_t max_ploi
     return L;
 }
 // The parent's three layout entry points: cohort_layout(n_rows, S) through the defaults above, and these.  Nothing in this tree calls them; the host
-// harnesses of the tests written before the one layout (tests/cohort_sim, cohort_ploidy_sim, cohort_prior_sim as they stood) compile against them, and
+// harnesses of the tests written before the one layout (one directory a feature then; since merged into tests/geno_sim) compile against them, and
 // those tests are held against every later build.
 using CohortPloidyLayout = CohortLayout;
 using CohortPriorLayout = CohortLayout;

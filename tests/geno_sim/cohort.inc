@@ -1,16 +1,9 @@
-// TEST HARNESS ONLY (never shipped, never loaded by the product): the pieces of the cohort genotype leg that are plain integers (svjg_geno.h:
-// cohort_segment, what the cohort kernels mask their ballots with; cohort_diploid_sums and cohort_ploidy_sums, what k_genotype_cohort turns its three
-// ballots into and k_genotype_cohort_ploidy its nine; and cohort_layout) compiled with g++.  With -DCOHORT_SIM_MAIN it is a stand-alone program (for -fsanitize=address,undefined) that checks every
-// wave of 3 * 64 * S items against the brute-force segments and sums, and the layouts.
-#define SVJG_HD inline
-#include "../../svjedi-graph_amd/csrc/svjg_geno.h"
-#include <stdio.h>
-#include <initializer_list>
-
-using namespace svjg;
+// The pieces of the cohort genotype leg that are plain integers (svjg_geno.h: cohort_segment, what the cohort kernels mask their ballots with;
+// cohort_diploid_sums and cohort_ploidy_sums, what k_genotype_cohort turns its three ballots into and k_genotype_cohort_ploidy its nine).  Topic
+// `cohort` of the stand-alone program checks every wave of 3 * 64 * S items against the brute-force segments and sums, and the layouts.
 
 // the 64 lanes of the wave whose first item is w0, for n_rows x S items: mask[lane], leader[lane]
-extern "C" void cohortsim_wave(uint64_t w0, uint64_t S, uint64_t n_items, uint64_t *mask, uint8_t *leader) {
+extern "C" void genosim_cohort_wave(uint64_t w0, uint64_t S, uint64_t n_items, uint64_t *mask, uint8_t *leader) {
     for (uint32_t lane = 0; lane < 64; ++lane) {
         const uint64_t i = w0 + lane;
         const CohortSeg g = cohort_segment(i, i % S, S, lane, n_items);
@@ -22,8 +15,8 @@ extern "C" void cohortsim_wave(uint64_t w0, uint64_t S, uint64_t n_items, uint64
 // the diploid kernel (gt 0 / 1 / 2, 3: no call; its three ballots called / het / hom).  The ballots are formed as the kernel forms them (a lane
 // beyond the last item votes "no call", ploidy 0), then for every lane: leader[lane], and the segment's sums ns / an /
 // ac[lane] and the first site word as the leader would add them (0 where the lane is no leader).
-extern "C" void cohortsim_sums(uint64_t w0, uint64_t S, uint64_t n_items, const uint8_t *gt, const uint8_t *ploidy,
-                               uint8_t *leader, uint32_t *ns, uint32_t *an, uint32_t *ac, uint64_t *word) {
+extern "C" void genosim_cohort_sums(uint64_t w0, uint64_t S, uint64_t n_items, const uint8_t *gt, const uint8_t *ploidy,
+                                    uint8_t *leader, uint32_t *ns, uint32_t *an, uint32_t *ac, uint64_t *word) {
     CohortBallots b{};
     uint64_t het = 0, hom = 0;
     for (uint32_t lane = 0; lane < 64; ++lane) {
@@ -47,18 +40,8 @@ extern "C" void cohortsim_sums(uint64_t w0, uint64_t S, uint64_t n_items, const 
     }
 }
 
-// cohort_layout(n_rows, S, max_ploidy, per_item, prior) -> out[19]: pl, raw, gt, flags, boundary, gq, af, psite, steps, site, maxn, in_at, logtab, slot,
-// type, ok, ploidy, total, in_bytes
-extern "C" void cohortsim_layout(uint64_t n_rows, uint64_t S, uint32_t max_ploidy, int per_item, int prior, uint64_t *out) {
-    const CohortLayout L = cohort_layout(n_rows, S, max_ploidy, per_item != 0, prior != 0);
-    const uint64_t v[19] = {L.pl, L.raw, L.gt, L.flags, L.boundary, L.gq, L.af, L.psite, L.steps, L.site, L.maxn, L.in_at, L.logtab, L.in.slot, L.in.type, L.in.ok,
-                            L.ploidy, L.total, L.in_bytes};
-    for (int i = 0; i < 19; ++i) out[i] = v[i];
-}
-
-#ifdef COHORT_SIM_MAIN
-#include <vector>
-int main() {
+#ifdef GENO_SIM_MAIN
+static int main_cohort() {
     const uint64_t sizes[8] = {1, 2, 3, 31, 63, 64, 65, 130};
     uint64_t waves = 0, bad = 0, x = 88172645463325252ull;
     for (uint64_t S : sizes) {
@@ -76,9 +59,9 @@ int main() {
             std::vector<uint64_t> row_ns(n_items / S, 0), row_an(n_items / S, 0), row_ac(n_items / S, 0), row_word(n_items / S, 0);
             for (uint64_t w0 = 0; w0 < n_items; w0 += 64) {
                 uint64_t mask[64]; uint8_t seg_leader[64];
-                cohortsim_wave(w0, S, n_items, mask, seg_leader);
+                genosim_cohort_wave(w0, S, n_items, mask, seg_leader);
                 uint8_t leader[64]; uint32_t ns[64], an[64], ac[64]; uint64_t word[64];
-                cohortsim_sums(w0, S, n_items, gt.data(), per_item ? pld.data() : nullptr, leader, ns, an, ac, word);
+                genosim_cohort_sums(w0, S, n_items, gt.data(), per_item ? pld.data() : nullptr, leader, ns, an, ac, word);
                 ++waves;
                 for (uint32_t lane = 0; lane < 64; ++lane) {
                     const uint64_t i = w0 + lane;
@@ -100,7 +83,7 @@ int main() {
     }
     for (uint64_t n_rows : {1, 7, 1000}) for (uint64_t S : {1, 3, 64, 65}) for (uint32_t mp : {1u, 2u, 8u}) for (int per : {0, 1}) for (int prior : {0, 1}) {
         uint64_t L[19];
-        cohortsim_layout(n_rows, S, mp, per, prior, L);
+        layout_at(LAYOUT_COHORT, n_rows, S, mp, per | prior << 1, L);
         const uint64_t logs = per || prior ? 720 : 0;
         if (L[9] % 8 || L[6] % 8 || L[10] != L[9] + (per ? 16 : 8) * n_rows || L[11] != L[10] + 8 || L[13] != L[11] + logs ||
             L[16] != L[13] + 6 * n_rows || L[18] != logs + 6 * n_rows + (per ? n_rows * S : 0)) ++bad;

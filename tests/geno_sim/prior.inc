@@ -1,16 +1,10 @@
-// TEST HARNESS ONLY (never shipped, never loaded by the product): the per-item routines of the cohort call with an allele-frequency prior
-// (svjg_geno.h: prior_load, prior_expected, prior_call, prior_step, prior_segment_width, and cohort_layout with the prior) compiled with g++, and a row's
-// EM run sequentially over its samples (cprsim_row) or with every step's sum in the kernel's order (cprsim_row_wave: lanes, strides, butterfly).  With
-// -DCOHORT_PRIOR_SIM_MAIN it is a stand-alone program (for -fsanitize=address,undefined) that runs random rows and checks what holds without a model.
-#define SVJG_HD inline
-#include "../../svjedi-graph_amd/csrc/svjg_geno.h"
-#include <stdio.h>
-#include <initializer_list>
-
-using namespace svjg;
+// The per-item routines of the cohort call with an allele-frequency prior (svjg_geno.h: prior_load, prior_expected, prior_call, prior_step,
+// prior_segment_width), and a row's EM run sequentially over its samples (genosim_prior_row) or with every step's sum in the kernel's order
+// (genosim_prior_row_wave: lanes, strides, butterfly).  Topic `prior` of the stand-alone program runs random rows and checks what holds without a
+// model.
 
 // One row of S samples: raw[S][2], done[S], ploidy[S] or NULL (2 everywhere) -> *f (NaN: no estimate), *steps (the kernel's word: bit 31 = not
-// converged), gt[S], gq[S], site[3] = NS, AN, AC.  wave: a step's x are summed in k_cohort_prior's order (cprsim_row_wave), else sample after sample
+// converged), gt[S], gq[S], site[3] = NS, AN, AC.  wave: a step's x are summed in k_cohort_prior's order (genosim_prior_row_wave), else sample after sample
 static void row_em(bool wave, uint32_t sv_type, const uint32_t *raw, const uint8_t *done, const uint8_t *ploidy, uint64_t S, double err, uint32_t min_support,
                    double *f, uint32_t *steps, uint8_t *gt, uint8_t *gq, uint32_t *site) {
     double tab[2 * PLOIDY_TAB];
@@ -53,21 +47,21 @@ static void row_em(bool wave, uint32_t sv_type, const uint32_t *raw, const uint8
     *f = row.f; *steps = row.steps;
 }
 
-extern "C" void cprsim_row(uint32_t sv_type, const uint32_t *raw, const uint8_t *done, const uint8_t *ploidy, uint64_t S, double err, uint32_t min_support,
-                           double *f, uint32_t *steps, uint8_t *gt, uint8_t *gq, uint32_t *site) {
+extern "C" void genosim_prior_row(uint32_t sv_type, const uint32_t *raw, const uint8_t *done, const uint8_t *ploidy, uint64_t S, double err, uint32_t min_support,
+                                  double *f, uint32_t *steps, uint8_t *gt, uint8_t *gq, uint32_t *site) {
     row_em(false, sv_type, raw, done, ploidy, S, err, min_support, f, steps, gt, gq, site);
 }
 
 // The same row with every step's sum in the kernel's order: lane j of W = prior_segment_width(S) lanes adds its items j, j + 64, j + 128, ... in
 // that order, starting from the first; then the levels m = 1, 2, ..., W / 2 of the xor butterfly; lanes at or beyond S hold 0.0.  The kernel
 // differs from this in exp10 and log10 only.
-extern "C" void cprsim_row_wave(uint32_t sv_type, const uint32_t *raw, const uint8_t *done, const uint8_t *ploidy, uint64_t S, double err, uint32_t min_support,
-                                double *f, uint32_t *steps, uint8_t *gt, uint8_t *gq, uint32_t *site) {
+extern "C" void genosim_prior_row_wave(uint32_t sv_type, const uint32_t *raw, const uint8_t *done, const uint8_t *ploidy, uint64_t S, double err, uint32_t min_support,
+                                       double *f, uint32_t *steps, uint8_t *gt, uint8_t *gq, uint32_t *site) {
     row_em(true, sv_type, raw, done, ploidy, S, err, min_support, f, steps, gt, gq, site);
 }
 
 // the weights of one item: w[9] = C(P, g) 10^d_g, -> the item's ploidy as the EM sees it (0: it takes no part); *gmax
-extern "C" uint32_t cprsim_item(uint32_t sv_type, uint32_t ref, uint32_t alt, uint32_t P, double err, double *w, uint32_t *gmax) {
+extern "C" uint32_t genosim_prior_item(uint32_t sv_type, uint32_t ref, uint32_t alt, uint32_t P, double err, double *w, uint32_t *gmax) {
     double tab[2 * PLOIDY_TAB];
     ploidy_log_table(err, tab);
     const uint32_t raw[2] = {ref, alt}; const uint8_t done = 1, p = (uint8_t)P, t8 = (uint8_t)sv_type, *type = &t8;
@@ -78,21 +72,11 @@ extern "C" uint32_t cprsim_item(uint32_t sv_type, uint32_t ref, uint32_t alt, ui
     return it.P;
 }
 
-extern "C" uint32_t cprsim_width(uint64_t S) { return prior_segment_width(S); }
-extern "C" void cprsim_constants(double *tol, uint32_t *max_it, uint32_t *flag_bit, double *f_bound) { *tol = EM_TOL; *max_it = EM_MAX_IT; *flag_bit = EM_NOT_CONVERGED; *f_bound = EM_F_BOUND; }
+extern "C" uint32_t genosim_prior_width(uint64_t S) { return prior_segment_width(S); }
+extern "C" void genosim_prior_constants(double *tol, uint32_t *max_it, uint32_t *flag_bit, double *f_bound) { *tol = EM_TOL; *max_it = EM_MAX_IT; *flag_bit = EM_NOT_CONVERGED; *f_bound = EM_F_BOUND; }
 
-// cohort_layout(n_rows, S, max_ploidy, per_item, true) -> out[19]: pl, raw, gt, flags, boundary, gq, af, psite, steps, site, maxn, in_at, logtab, slot, type, ok,
-// ploidy, total, in_bytes
-extern "C" void cprsim_layout(uint64_t n_rows, uint64_t S, uint32_t max_ploidy, int per_item, uint64_t *out) {
-    const CohortLayout L = cohort_layout(n_rows, S, max_ploidy, per_item != 0, true);
-    const uint64_t v[19] = {L.pl, L.raw, L.gt, L.flags, L.boundary, L.gq, L.af, L.psite, L.steps, L.site, L.maxn, L.in_at, L.logtab, L.in.slot, L.in.type, L.in.ok,
-                            L.ploidy, L.total, L.in_bytes};
-    for (int i = 0; i < 19; ++i) out[i] = v[i];
-}
-
-#ifdef COHORT_PRIOR_SIM_MAIN
-#include <vector>
-int main() {
+#ifdef GENO_SIM_MAIN
+static int main_prior() {
     const uint64_t sizes[21] = {1, 2, 3, 4, 5, 8, 9, 16, 17, 31, 32, 33, 63, 64, 65, 130, 192, 193, 256, 257, 320};
     uint64_t rows = 0, bad = 0, x = 88172645463325252ull;
     auto next = [&] { x ^= x << 13; x ^= x >> 7; x ^= x << 17; return x; };
@@ -107,11 +91,11 @@ int main() {
                 }
                 double f, f2; uint32_t steps, steps2, site[3], site2[3];
                 const uint32_t type = (uint32_t)(next() % 4), ms = k & 1 ? 3 : 0;
-                cprsim_row(type, raw.data(), done.data(), mode == 1 ? pld.data() : nullptr, S, 5e-5, ms, &f, &steps, gt.data(), gq.data(), site);
-                cprsim_row(type, raw.data(), done.data(), mode == 1 ? pld.data() : nullptr, S, 5e-5, ms, &f2, &steps2, gt2.data(), gq2.data(), site2);
+                genosim_prior_row(type, raw.data(), done.data(), mode == 1 ? pld.data() : nullptr, S, 5e-5, ms, &f, &steps, gt.data(), gq.data(), site);
+                genosim_prior_row(type, raw.data(), done.data(), mode == 1 ? pld.data() : nullptr, S, 5e-5, ms, &f2, &steps2, gt2.data(), gq2.data(), site2);
                 // the kernel's order of the sums: what holds of any order (the model decides the rest: tests/test_cohort_prior.py)
                 std::vector<uint8_t> gt3(S), gq3(S); double f3; uint32_t steps3, site3[3];
-                cprsim_row_wave(type, raw.data(), done.data(), mode == 1 ? pld.data() : nullptr, S, 5e-5, ms, &f3, &steps3, gt3.data(), gq3.data(), site3);
+                genosim_prior_row_wave(type, raw.data(), done.data(), mode == 1 ? pld.data() : nullptr, S, 5e-5, ms, &f3, &steps3, gt3.data(), gq3.data(), site3);
                 uint32_t ns3 = 0, ac3 = 0;
                 for (uint64_t s = 0; s < S; ++s) { if (gt3[s] != 0xFF) { ++ns3; ac3 += gt3[s]; if (gq3[s] > 99) ++bad; } else if (gq3[s] != 0xFF) ++bad; }
                 if (ns3 != site3[0] || ac3 != site3[2] || (f != f) != (f3 != f3) || (f3 == f3 && !(f3 >= 0.0 && f3 <= 1.0 && steps3 && (steps3 & ~EM_NOT_CONVERGED) <= EM_MAX_IT))
@@ -129,10 +113,10 @@ int main() {
             }
     for (uint64_t n_rows : {1, 7, 1000}) for (uint64_t S : {1, 3, 64, 65}) for (uint32_t mp : {1u, 2u, 8u}) for (int per : {0, 1}) {
         uint64_t L[19];
-        cprsim_layout(n_rows, S, mp, per, L);
+        layout_at(LAYOUT_COHORT, n_rows, S, mp, per | 2, L);
         if (L[9] % 8 || L[6] % 8 || L[10] != L[9] + (per ? 16 : 8) * n_rows || L[11] != L[10] + 8 || L[13] + 6 * n_rows + (per ? n_rows * S : 0) != L[11] + L[18]) ++bad;
     }
-    for (uint64_t S : sizes) { const uint32_t w = cprsim_width(S); if (w < (S < 64 ? S : 64) || w > 64 || (w & (w - 1)) || (w > 1 && w / 2 >= (S < 64 ? S : 64))) ++bad; }
+    for (uint64_t S : sizes) { const uint32_t w = genosim_prior_width(S); if (w < (S < 64 ? S : 64) || w > 64 || (w & (w - 1)) || (w > 1 && w / 2 >= (S < 64 ? S : 64))) ++bad; }
     printf("cohort_prior_sim %s: %llu rows, %llu checks failed\n", bad ? "FAILED" : "ok", (unsigned long long)rows, (unsigned long long)bad);
     return bad ? 1 : 0;
 }

@@ -1,14 +1,7 @@
-// TEST HARNESS ONLY (never shipped, never loaded by the product): the per-row routines of the cohort site quality (svjg_geno.h: qual_load,
-// qual_den, qual_fold, qual_rescale_every, qual_term, qual_best, qual_finish, qual_harmonic, qual_layout) compiled with g++, and a row run with its
-// sums over k sequentially (cqsim_row) or in k_cohort_qual's order (cqsim_row_wave: lane-strided partials in increasing k, then the xor butterfly
-// over 64 lanes).  With -DCOHORT_QUAL_SIM_MAIN it is a stand-alone program (for -fsanitize=address,undefined) that runs random rows and checks what
-// holds without a model.
-#define SVJG_HD inline
-#include "../../svjedi-graph_amd/csrc/svjg_geno.h"
-#include <stdio.h>
-#include <vector>
-
-using namespace svjg;
+// The per-row routines of the cohort site quality (svjg_geno.h: qual_load, qual_den, qual_fold, qual_rescale_every, qual_term, qual_best,
+// qual_finish, qual_harmonic), and a row run with its sums over k sequentially or in k_cohort_qual's order (genosim_qual_row's wave arm:
+// lane-strided partials in increasing k, then the xor butterfly over 64 lanes).  Topic `qual` of the stand-alone program runs random rows and
+// checks what holds without a model.
 
 // One row of S samples: raw[S][2], done[S] (the gate's outcome), ploidy[S] or NULL (2 everywhere); max_ploidy as the call's (it sizes the row and
 // sets the rescaling's cadence) -> *qual (NaN: no item took part), *mlac, *chroms.  every: 0 = qual_rescale_every of the call, else that many
@@ -70,13 +63,13 @@ static void row_qual(bool wave, uint32_t sv_type, const uint32_t *raw, const uin
     *qual = M ? qual_finish(phi0, D0, T, E) : NAN;
 }
 
-extern "C" void cqsim_row(int wave, uint32_t sv_type, const uint32_t *raw, const uint8_t *done, const uint8_t *ploidy, uint64_t S, uint32_t max_ploidy, double err,
-                          double theta, uint32_t every, double *qual, uint32_t *mlac, uint32_t *chroms) {
+extern "C" void genosim_qual_row(int wave, uint32_t sv_type, const uint32_t *raw, const uint8_t *done, const uint8_t *ploidy, uint64_t S, uint32_t max_ploidy, double err,
+                                 double theta, uint32_t every, double *qual, uint32_t *mlac, uint32_t *chroms) {
     row_qual(wave != 0, sv_type, raw, done, ploidy, S, max_ploidy, err, theta, every, qual, mlac, chroms);
 }
 
 // the item of a sample: w[9] = C(P, g) 10^d_g, d0 as its two doubles -> the ploidy the recurrence sees (0: it takes no part)
-extern "C" uint32_t cqsim_item(uint32_t sv_type, uint32_t ref, uint32_t alt, uint32_t P, double err, double *w, double *d0) {
+extern "C" uint32_t genosim_qual_item(uint32_t sv_type, uint32_t ref, uint32_t alt, uint32_t P, double err, double *w, double *d0) {
     double tab[2 * PLOIDY_TAB];
     ploidy_log_table(err, tab);
     QualItem it;
@@ -86,18 +79,11 @@ extern "C" uint32_t cqsim_item(uint32_t sv_type, uint32_t ref, uint32_t alt, uin
     return it.it.P;
 }
 
-extern "C" uint32_t cqsim_every(uint32_t m_max, uint32_t max_ploidy) { return qual_rescale_every(m_max, max_ploidy); }
-extern "C" void cqsim_constants(double *out) { out[0] = QUAL_ABS; out[1] = QUAL_REL; out[2] = QUAL_ABS_MEASURED; out[3] = QUAL_REL_MEASURED; out[4] = QUAL_MAX_CHROMS; out[5] = QUAL_THETA_MAX; }
+extern "C" uint32_t genosim_qual_every(uint32_t m_max, uint32_t max_ploidy) { return qual_rescale_every(m_max, max_ploidy); }
+extern "C" void genosim_qual_constants(double *out) { out[0] = QUAL_ABS; out[1] = QUAL_REL; out[2] = QUAL_ABS_MEASURED; out[3] = QUAL_REL_MEASURED; out[4] = QUAL_MAX_CHROMS; out[5] = QUAL_THETA_MAX; }
 
-// qual_layout -> out[12]: qual, mlac, chroms, maxn, in_at, logtab, harm, slot, type, ok, ploidy, total
-extern "C" void cqsim_layout(uint64_t n_rows, uint64_t S, uint32_t m_max, int per_item, uint64_t *out) {
-    const QualLayout L = qual_layout(n_rows, S, m_max, per_item != 0);
-    const uint64_t v[12] = {L.qual, L.mlac, L.chroms, L.maxn, L.in_at, L.logtab, L.harm, L.in.slot, L.in.type, L.in.ok, L.ploidy, L.total};
-    for (int i = 0; i < 12; ++i) out[i] = v[i];
-}
-
-#ifdef COHORT_QUAL_SIM_MAIN
-int main() {
+#ifdef GENO_SIM_MAIN
+static int main_qual() {
     const uint64_t sizes[14] = {1, 2, 3, 8, 9, 17, 31, 32, 33, 63, 64, 65, 200, 600};
     uint64_t rows = 0, bad = 0, x = 88172645463325252ull;
     auto next = [&] { x ^= x << 13; x ^= x >> 7; x ^= x << 17; return x; };
@@ -115,10 +101,10 @@ int main() {
                 const uint32_t type = (uint32_t)(next() % 4), mp = mode == 1 ? 8u : 2u;
                 const uint8_t *pl = mode == 1 ? pld.data() : nullptr;
                 double q[4]; uint32_t ml[4], ch[4];
-                cqsim_row(0, type, raw.data(), done.data(), pl, S, mp, 5e-5, 1e-3, 0, &q[0], &ml[0], &ch[0]);
-                cqsim_row(1, type, raw.data(), done.data(), pl, S, mp, 5e-5, 1e-3, 0, &q[1], &ml[1], &ch[1]);
-                cqsim_row(1, type, raw.data(), done.data(), pl, S, mp, 5e-5, 1e-3, 1, &q[2], &ml[2], &ch[2]);      // a rescaling behind every step
-                cqsim_row(1, type, raw.data(), done.data(), pl, S, mp, 5e-5, 1e-3, 0, &q[3], &ml[3], &ch[3]);
+                genosim_qual_row(0, type, raw.data(), done.data(), pl, S, mp, 5e-5, 1e-3, 0, &q[0], &ml[0], &ch[0]);
+                genosim_qual_row(1, type, raw.data(), done.data(), pl, S, mp, 5e-5, 1e-3, 0, &q[1], &ml[1], &ch[1]);
+                genosim_qual_row(1, type, raw.data(), done.data(), pl, S, mp, 5e-5, 1e-3, 1, &q[2], &ml[2], &ch[2]);      // a rescaling behind every step
+                genosim_qual_row(1, type, raw.data(), done.data(), pl, S, mp, 5e-5, 1e-3, 0, &q[3], &ml[3], &ch[3]);
                 ++rows;
                 for (int i = 0; i < 4; ++i) {
                     if (ch[i] != m_part || ml[i] > ch[i]) ++bad;
@@ -129,11 +115,11 @@ int main() {
             }
     for (uint64_t n_rows : {1, 7, 1000}) for (uint64_t S : {1, 3, 64, 65}) for (uint32_t mp : {1u, 2u, 8u}) for (int per : {0, 1}) {
         uint64_t L[12];
-        cqsim_layout(n_rows, S, (uint32_t)(S * mp), per, L);
+        layout_at(LAYOUT_QUAL, n_rows, S, (uint32_t)(S * mp), per, L);
         if (L[0] != 0 || L[1] != 8 * n_rows || L[2] != 12 * n_rows || L[3] % 8 || L[3] < 16 * n_rows || L[4] != L[3] + 8 || L[5] != L[4] || L[6] != L[5] + 720
             || L[7] != L[6] + 8 * (S * mp + 1) || L[10] != L[7] + 6 * n_rows || L[11] != L[10] + (per ? n_rows * S : 0) + 64) ++bad;
     }
-    if (cqsim_every(4096, 8) != 4 || cqsim_every(4096, 2) != 19 || cqsim_every(128, 2) != 32 || cqsim_every(1, 1) != 512) ++bad;
+    if (genosim_qual_every(4096, 8) != 4 || genosim_qual_every(4096, 2) != 19 || genosim_qual_every(128, 2) != 32 || genosim_qual_every(1, 1) != 512) ++bad;
     printf("cohort_qual_sim %s: %llu rows, %llu checks failed\n", bad ? "FAILED" : "ok", (unsigned long long)rows, (unsigned long long)bad);
     return bad ? 1 : 0;
 }

@@ -1,31 +1,15 @@
-// TEST HARNESS ONLY (never shipped, never loaded by the product): what the two site kernels run per lane, compiled with g++ (svjg_geno.h) — the
-// joint arithmetic for insertions that share a position (geno_site), the slot gather and the item behind it (site_gather, site_item: what
-// k_genotype_sites and k_genotype_cohort_sites do per item), and the plain pieces of the cohort call (site_compact, site_candidate_copies,
-// cohort_site_member_sums under cohort_segment's masks, sites_layout).  With -DSITE_SIM_MAIN it is a stand-alone program (for
-// -fsanitize=address,undefined) that runs the compaction of every presence pattern, every wave of 3 * 64 * S items
-// against brute-force sums, the layouts, and the gather and the item over count and presence arrays allocated at exactly their size, bad slots and
-// counts of every depth among them.
-#define SVJG_HD inline
-#include "../../svjedi-graph_amd/csrc/svjg_geno.h"
-#include <math.h>
-#include <stdio.h>
-#include <initializer_list>
-#include <vector>
-
-using namespace svjg;
-
-// log10(i!) for i < n with the HOST libm's log10, summed in order in double-double (as tests/hostsim does)
-extern "C" void sitesim_logfact(dd *tab, uint32_t n) {
-    dd run{0.0, 0.0};
-    for (uint32_t i = 0; i < n; ++i) { if (i >= 2) run = dd_add(run, dd{log10((double)i), 0.0}); tab[i] = run; }
-}
+// What the two site kernels run per lane (svjg_geno.h) — the joint arithmetic for insertions that share a position (geno_site), the slot gather and
+// the item behind it (site_gather, site_item: what k_genotype_sites and k_genotype_cohort_sites do per item), and the plain pieces of the cohort
+// call (site_compact, site_candidate_copies, cohort_site_member_sums under cohort_segment's masks).  Topic `site` of the stand-alone program runs
+// the compaction of every presence pattern, every wave of 3 * 64 * S items against brute-force sums, the layouts, and the gather and the item over
+// count and presence arrays allocated at exactly their size, bad slots and counts of every depth among them.
 
 // the SITE_LOGS logarithms of a call (svjg_geno.h: site_log_table)
-extern "C" void sitesim_log_table(double err, double *tab) { site_log_table(err, tab); }
+extern "C" void genosim_site_log_table(double err, double *tab) { site_log_table(err, tab); }
 
 // geno_site over sites of (K in 2..6, ref, alt[6]) -> gt[n * 2] (0xFF, 0xFF: no call), pl[n * 28], near, status (GENO_ROW_*), n = s_K
-extern "C" void sitesim_genotype(const uint8_t *K, const uint32_t *ref, const uint32_t *alt, uint64_t n_sites, uint32_t min_support, double err,
-                                 const dd *tab, uint32_t tab_n, uint8_t *gt, int64_t *pl, uint8_t *near, uint8_t *status, uint64_t *n_out) {
+extern "C" void genosim_site_genotype(const uint8_t *K, const uint32_t *ref, const uint32_t *alt, uint64_t n_sites, uint32_t min_support, double err,
+                                      const dd *tab, uint32_t tab_n, uint8_t *gt, int64_t *pl, uint8_t *near, uint8_t *status, uint64_t *n_out) {
     double lt[SITE_LOGS];
     site_log_table(err, lt);
     for (uint64_t s = 0; s < n_sites; ++s) {
@@ -38,8 +22,8 @@ extern "C" void sitesim_genotype(const uint8_t *K, const uint32_t *ref, const ui
 
 // site_gather as the lane of sample s does it: counts[n_slots * S] slot-major (ref | alt << 32), present[n_slots * S] or nullptr, the site's six
 // slots -> out[14] = members, bad, cref[6], calt[6]
-extern "C" void sitesim_gather(const unsigned long long *counts, const uint8_t *present, uint64_t S, uint64_t s, uint32_t n_slots, const uint32_t *slots,
-                               uint32_t *out) {
+extern "C" void genosim_site_gather(const unsigned long long *counts, const uint8_t *present, uint64_t S, uint64_t s, uint32_t n_slots, const uint32_t *slots,
+                                    uint32_t *out) {
     SiteGather g;
     site_gather(counts, present, S, s, n_slots, slots, g);
     out[0] = g.members; out[1] = g.bad;
@@ -48,7 +32,7 @@ extern "C" void sitesim_gather(const unsigned long long *counts, const uint8_t *
 
 // site_item over all (site k, sample s) items, i = k * S + s, as the lanes do: slots[n_sites * 6] -> gt[i * 2..], pl[i * 28..], raw[i * 7..],
 // boundary[i], and what the routine returns: members, status (GENO_ROW_*), n = s_K, bad
-extern "C" void sitesim_site_items(const unsigned long long *counts, const uint8_t *present, uint64_t S, uint32_t n_slots, const uint32_t *slots,
+extern "C" void genosim_site_items(const unsigned long long *counts, const uint8_t *present, uint64_t S, uint32_t n_slots, const uint32_t *slots,
                                    uint64_t n_sites, uint32_t min_support, double err, const dd *tab, uint32_t tab_n, uint8_t *gt, int64_t *pl,
                                    uint32_t *raw, uint8_t *boundary, uint8_t *members, uint8_t *status, uint64_t *n_out, uint8_t *bad) {
     double lt[SITE_LOGS];
@@ -63,7 +47,7 @@ extern "C" void sitesim_site_items(const unsigned long long *counts, const uint8
 }
 
 // site_compact: bits, cref[6], calt[6] -> out[8] = K, ref, alt[0..6)
-extern "C" void sitesim_compact(uint32_t bits, const uint32_t *cref, const uint32_t *calt, uint32_t *out) {
+extern "C" void genosim_site_compact(uint32_t bits, const uint32_t *cref, const uint32_t *calt, uint32_t *out) {
     SiteMembers m;
     site_compact(bits, cref, calt, m);
     out[0] = m.K; out[1] = m.ref;
@@ -73,8 +57,8 @@ extern "C" void sitesim_compact(uint32_t bits, const uint32_t *cref, const uint3
 // The wave whose first item is w0, of n_items items of S samples a site; members[i] and gt[i * 2..] per ITEM as the kernel leaves them (gt 0xFF,
 // 0xFF: no site call).  The ballots are formed as the kernel forms them (a lane beyond the last item votes members 0, no call), then for every
 // lane: leader[lane] and, per candidate j, ns / ac / word[lane * 6 + j] as the leader would add them (0 where the lane is no leader).
-extern "C" void sitesim_sums(uint64_t w0, uint64_t S, uint64_t n_items, const uint8_t *members, const uint8_t *gt,
-                             uint8_t *leader, uint32_t *ns, uint32_t *ac, uint64_t *word) {
+extern "C" void genosim_site_sums(uint64_t w0, uint64_t S, uint64_t n_items, const uint8_t *members, const uint8_t *gt,
+                                  uint8_t *leader, uint32_t *ns, uint32_t *ac, uint64_t *word) {
     SiteBallots b{};
     for (uint32_t lane = 0; lane < 64; ++lane) {
         const uint64_t i = w0 + lane;
@@ -102,8 +86,8 @@ extern "C" void sitesim_sums(uint64_t w0, uint64_t S, uint64_t n_items, const ui
 // Items from the gathered (bits, cref, calt), the compaction and geno_site written out step by step — the second opinion on site_item: bits[i],
 // cref / calt[i * 6..] (those of an absent candidate are not looked at) -> gt[i * 2..], pl[i * 28..], raw[i * 7..], near, status (GENO_ROW_*),
 // n = s_K; K' < 2: 0xFF, 0xFF and zeros
-extern "C" void sitesim_items(uint64_t n_items, const uint8_t *bits, const uint32_t *cref, const uint32_t *calt, uint32_t min_support, double err,
-                              const dd *tab, uint32_t tab_n, uint8_t *gt, int64_t *pl, uint32_t *raw, uint8_t *near, uint8_t *status, uint64_t *n_out) {
+extern "C" void genosim_site_items_by_steps(uint64_t n_items, const uint8_t *bits, const uint32_t *cref, const uint32_t *calt, uint32_t min_support, double err,
+                                            const dd *tab, uint32_t tab_n, uint8_t *gt, int64_t *pl, uint32_t *raw, uint8_t *near, uint8_t *status, uint64_t *n_out) {
     double lt[SITE_LOGS];
     site_log_table(err, lt);
     for (uint64_t i = 0; i < n_items; ++i) {
@@ -120,14 +104,7 @@ extern "C" void sitesim_items(uint64_t n_items, const uint8_t *bits, const uint3
     }
 }
 
-// sites_layout(n_sites, S, cohort) -> out[12]: pl, raw, gt, members, boundary, site, maxn, in_at, logs, slots, in_bytes, total
-extern "C" void sitesim_layout(uint64_t n_sites, uint64_t S, int cohort, uint64_t *out) {
-    const SitesLayout L = sites_layout(n_sites, S, cohort != 0);
-    const uint64_t v[12] = {L.pl, L.raw, L.gt, L.members, L.boundary, L.site, L.maxn, L.in_at, L.logs, L.slots, L.in_bytes, L.total};
-    for (int i = 0; i < 12; ++i) out[i] = v[i];
-}
-
-#ifdef SITE_SIM_MAIN
+#ifdef GENO_SIM_MAIN
 static uint64_t rng_state = 88172645463325252ull;
 static uint64_t rnd() { uint64_t &x = rng_state; x ^= x << 13; x ^= x >> 7; x ^= x << 17; return x; }
 
@@ -165,7 +142,7 @@ static uint64_t run_gather_and_items(uint64_t S, bool vector_call, const std::ve
         const uint64_t k = i / S, s = i % S;
         const uint32_t *m = slots.data() + k * MAX_SITE_ALTS;
         uint32_t out[14], members = 0, cref[6] = {0}, calt[6] = {0};
-        sitesim_gather(counts.data(), pres, S, s, n_slots, m, out);
+        genosim_site_gather(counts.data(), pres, S, s, n_slots, m, out);
         if ((out[1] != 0) != (want_bad[k] != 0)) ++bad;
         bool open = true;
         for (uint32_t j = 0; j < MAX_SITE_ALTS; ++j) {                         // the candidates picked out one by one
@@ -183,15 +160,15 @@ static uint64_t run_gather_and_items(uint64_t S, bool vector_call, const std::ve
     std::vector<int64_t> pl(n * SITE_GENOTYPES), pl2(n * SITE_GENOTYPES);
     std::vector<uint32_t> raw(n * 7), raw2(n * 7), cref(n * 6), calt(n * 6);
     std::vector<uint64_t> nn(n), nn2(n);
-    sitesim_site_items(counts.data(), pres, S, n_slots, slots.data(), n_sites, 3, 5e-5, tab.data(), (uint32_t)tab.size(), gt.data(), pl.data(), raw.data(),
+    genosim_site_items(counts.data(), pres, S, n_slots, slots.data(), n_sites, 3, 5e-5, tab.data(), (uint32_t)tab.size(), gt.data(), pl.data(), raw.data(),
                        boundary.data(), members.data(), st.data(), nn.data(), isbad.data());
     for (uint64_t i = 0; i < n; ++i) {
         uint32_t out[14];
-        sitesim_gather(counts.data(), pres, S, i % S, n_slots, slots.data() + i / S * MAX_SITE_ALTS, out);
+        genosim_site_gather(counts.data(), pres, S, i % S, n_slots, slots.data() + i / S * MAX_SITE_ALTS, out);
         bits[i] = out[1] ? 0 : (uint8_t)out[0];
         for (uint32_t j = 0; j < 6; ++j) { cref[i * 6 + j] = out[2 + j]; calt[i * 6 + j] = out[8 + j]; }
     }
-    sitesim_items(n, bits.data(), cref.data(), calt.data(), 3, 5e-5, tab.data(), (uint32_t)tab.size(), gt2.data(), pl2.data(), raw2.data(), near2.data(), st2.data(), nn2.data());
+    genosim_site_items_by_steps(n, bits.data(), cref.data(), calt.data(), 3, 5e-5, tab.data(), (uint32_t)tab.size(), gt2.data(), pl2.data(), raw2.data(), near2.data(), st2.data(), nn2.data());
     if (gt != gt2 || pl != pl2 || raw != raw2 || boundary != near2 || st != st2 || nn != nn2 || members != bits) ++bad;
     for (uint64_t i = 0; i < n; ++i) {
         const bool few = __builtin_popcount(bits[i]) < 2;
@@ -202,10 +179,10 @@ static uint64_t run_gather_and_items(uint64_t S, bool vector_call, const std::ve
     return bad;
 }
 
-int main() {
+static int main_site() {
     const uint32_t tab_n = 1u << 20;                     // beyond it: sites answer GENO_ROW_GROW / GENO_ROW_HOST and touch no entry
     std::vector<dd> tab(tab_n);
-    sitesim_logfact(tab.data(), tab_n);
+    genosim_logfact(tab.data(), tab_n);
     uint64_t bad = 0, waves = 0;
     bad += run_gather_and_items(1, true, tab) + run_gather_and_items(1, false, tab) + run_gather_and_items(3, false, tab) + run_gather_and_items(65, false, tab);
     // the compaction: every presence pattern, against the members picked out one by one
@@ -213,7 +190,7 @@ int main() {
         uint32_t cref[6], calt[6], out[8], want[8] = {0, 0, 0, 0, 0, 0, 0, 0};
         for (uint32_t j = 0; j < 6; ++j) { cref[j] = (uint32_t)(rnd() % 1000); calt[j] = (uint32_t)(rnd() % 1000) + 1; }
         for (uint32_t j = 0; j < 6; ++j) if ((bits >> j) & 1u) { want[2 + want[0]++] = calt[j]; if (cref[j] > want[1]) want[1] = cref[j]; }
-        sitesim_compact(bits, cref, calt, out);
+        genosim_site_compact(bits, cref, calt, out);
         for (int t = 0; t < 8; ++t) if (out[t] != want[t]) ++bad;
     }
     const uint64_t sizes[8] = {1, 2, 3, 31, 63, 64, 65, 130};
@@ -235,7 +212,7 @@ int main() {
             std::vector<uint64_t> got_ns(n_sites * 6, 0), got_ac(n_sites * 6, 0), got_word(n_sites * 6, 0);
             for (uint64_t w0 = 0; w0 < n_items; w0 += 64) {
                 uint8_t leader[64]; uint32_t ns[64 * 6], ac[64 * 6]; uint64_t word[64 * 6];
-                sitesim_sums(w0, S, n_items, members.data(), gt.data(), leader, ns, ac, word);
+                genosim_site_sums(w0, S, n_items, members.data(), gt.data(), leader, ns, ac, word);
                 ++waves;
                 for (uint32_t lane = 0; lane < 64; ++lane) {
                     const uint64_t i = w0 + lane;
@@ -262,11 +239,11 @@ int main() {
     }
     for (uint64_t n_sites : {1, 7, 1000}) for (uint64_t S : {1, 3, 64, 65}) {
         uint64_t L[12];
-        sitesim_layout(n_sites, S, 1, L);
+        layout_at(LAYOUT_SITES, n_sites, S, 0, 1, L);
         const uint64_t n = n_sites * S;
         if (L[0] != 0 || L[1] != 224 * n || L[2] != 252 * n || L[3] != 254 * n || L[4] != 255 * n || L[5] != ((256 * n + 7) & ~7ull) || L[5] % 8 ||
             L[6] != L[5] + 48 * n_sites || L[7] != L[6] + 8 || L[8] != L[7] || L[9] != L[8] + 128 || L[10] != 128 + 24 * n_sites || L[11] != L[7] + L[10] + 64) ++bad;
-        sitesim_layout(n_sites, 1, 0, L);
+        layout_at(LAYOUT_SITES, n_sites, 1, 0, 0, L);
         if (L[0] != 0 || L[1] != 224 * n_sites || L[2] != 252 * n_sites || L[3] != 0 || L[4] != 254 * n_sites || L[5] != 0 || L[6] != ((255 * n_sites + 7) & ~7ull) ||
             L[7] != L[6] + 8 || L[8] != L[7] || L[9] != L[8] + 128 || L[10] != 128 + 24 * n_sites || L[11] != L[7] + L[10] + 64) ++bad;
     }

@@ -10,6 +10,7 @@
 #include "../../svjedi-graph_amd/csrc/svjg_planes.h"
 #include "../../svjedi-graph_amd/csrc/svjg_pass.h"
 #include "../../svjedi-graph_amd/csrc/svjg_geno.h"
+#include "../host_logfact.h"
 #include <math.h>
 #include <cstring>
 #include <string>
@@ -278,25 +279,12 @@ extern "C" uint32_t hostsim_guard_words(void) { return GUARD_WORDS; }
 
 // where the rows of a genotype call lie (svjg_geno.h), as libsvjg_hip.so lays them out.  which 0: the step-by-step block -> pl, raw, gt, flags,
 // boundary, maxn, slot, type, ok, total; which 1: a fused pass's blocks -> pl32, raw, gt, flags, boundary, h_tail, out_bytes, maxn, status, guard,
-// tail_bytes, pl64, total, then slot, type, ok, bytes of the shared input block; which 2: svjg_genotype_ploidy's block -> pl, raw, gt, flags,
-// boundary, maxn, logtab, slot, type, ok, ploidy, in_bytes, total; which 3: svjg_genotype_sites' block -> pl, raw, gt, boundary, maxn, logs,
-// slots, in_bytes, total.  Returns the number of values written.
+// tail_bytes, pl64, total, then slot, type, ok, bytes of the shared input block (it needs svjg_pass.h's DevStatus; every other layout of
+// svjg_geno.h: tests/geno_sim).  Returns the number of values written.
 extern "C" int hostsim_rows_layout(uint64_t n, int which, uint64_t *out) {
     if (which == 0) {
         const RowsLayout L = rows_layout(n);
         const uint64_t v[] = {L.pl, L.raw, L.gt, L.flags, L.boundary, L.maxn, L.in.slot, L.in.type, L.in.ok, L.total};
-        memcpy(out, v, sizeof v);
-        return (int)(sizeof v / 8);
-    }
-    if (which == 2) {
-        const PloidyLayout L = ploidy_layout(n);
-        const uint64_t v[] = {L.pl, L.raw, L.gt, L.flags, L.boundary, L.maxn, L.logtab, L.in.slot, L.in.type, L.in.ok, L.ploidy, L.in_bytes, L.total};
-        memcpy(out, v, sizeof v);
-        return (int)(sizeof v / 8);
-    }
-    if (which == 3) {
-        const SitesLayout L = sites_layout(n);
-        const uint64_t v[] = {L.pl, L.raw, L.gt, L.boundary, L.maxn, L.logs, L.slots, L.in_bytes, L.total};
         memcpy(out, v, sizeof v);
         return (int)(sizeof v / 8);
     }
@@ -313,12 +301,7 @@ extern "C" uint32_t hostsim_logfact_cap(void) { return LOGFACT_CAP; }
 extern "C" uint32_t hostsim_logfact_built(uint32_t upto) { return logfact_built(upto); }
 extern "C" uint32_t hostsim_logfact_reserve_to(uint32_t have, uint32_t entries) { return logfact_reserve_to(have, entries); }
 
-// the log10(i!) table of k_logfact_* with the HOST libm's log10 (not the device's), summed in order in double-double (the kernels
-// sum in blocks: the association differs, both far below the guard's budget)
-extern "C" void hostsim_logfact(dd *tab, uint32_t n) {
-    dd run{0.0, 0.0};
-    for (uint32_t i = 0; i < n; ++i) { if (i >= 2) run = dd_add(run, dd{log10((double)i), 0.0}); tab[i] = run; }
-}
+extern "C" void hostsim_logfact(dd *tab, uint32_t n) { host_logfact(tab, n); }
 
 // k_genotype's per-row arithmetic (svjg_geno.h: geno_row) over rows of (type, ref, alt); status: GENO_ROW_*, near: the boundary byte
 extern "C" void hostsim_genotype(const uint8_t *type, const uint32_t *cnt, uint64_t n_rows, uint32_t min_support, double err,

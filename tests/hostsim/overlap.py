@@ -1,27 +1,24 @@
 """Build + call the host harness of the fused pass's decisions and of a classify launch's plan (svjedi-graph_amd/csrc/svjg_pass.h; tests only)."""
 import ctypes
 import os
-import subprocess
+
+from tests import sim_build
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 SO = os.path.join(HERE, "_overlapsim.so")
 MAIN = os.path.join(HERE, "_overlapsim_main")
+SRC = os.path.join(HERE, "overlap_sim.cpp")
+DEPS = [os.path.join(HERE, "..", "..", "svjedi-graph_amd", "csrc", "svjg_pass.h")]
 
 
 def build():
-    src = [os.path.join(HERE, "overlap_sim.cpp"), os.path.join(HERE, "..", "..", "svjedi-graph_amd", "csrc", "svjg_pass.h")]
-    if not os.path.exists(SO) or os.path.getmtime(SO) < max(os.path.getmtime(s) for s in src):
-        subprocess.run(["g++", "-O2", "-std=c++17", "-Wall", "-shared", "-fPIC", "-o", SO, src[0]], check=True)
+    sim_build.shared(SO, SRC, DEPS)
     return SO
 
 
 def build_main():
     """the stand-alone program under AddressSanitizer and UBSan (its own main: nothing is preloaded into anything)"""
-    src = [os.path.join(HERE, "overlap_sim.cpp"), os.path.join(HERE, "..", "..", "svjedi-graph_amd", "csrc", "svjg_pass.h")]
-    if not os.path.exists(MAIN) or os.path.getmtime(MAIN) < max(os.path.getmtime(s) for s in src):
-        subprocess.run(["g++", "-O1", "-g", "-std=c++17", "-Wall", "-DOVERLAP_SIM_MAIN", "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined",
-                        "-fno-omit-frame-pointer", "-o", MAIN, src[0]], check=True)
-    return MAIN
+    return sim_build.program(MAIN, SRC, DEPS, ["OVERLAP_SIM_MAIN"])
 
 
 def plan_logic():
@@ -29,7 +26,7 @@ def plan_logic():
     lists_first(all_slow, want_hits, n, n_recs, n_host) -> (deferred, recs, host),
     lists_grown((deferred, recs, host), n, recs_before, host_before, recs_after, overflow) -> the same,
     lists_fused(all_slow, n) -> the same)"""
-    lib = ctypes.CDLL(build())
+    lib = sim_build.shared(SO, SRC, DEPS)
     u64, out3 = ctypes.c_uint64, ctypes.c_uint64 * 3
     lib.overlapsim_main_plan.restype = None
     lib.overlapsim_main_plan.argtypes = [u64] * 4 + [ctypes.c_double, ctypes.POINTER(u64)]
@@ -57,7 +54,7 @@ def plan_logic():
 def overlap_logic():
     """-> (overlaps(has_comm, all_slow, timed_by_events, last_pass_deferred), settles_exact(has_comm, all_slow, overlapped, overflow, n_deferred),
     main_ticks(t_first, t_last, prev_t_last), repeats(has_comm, overflow, guard_sum))"""
-    lib = ctypes.CDLL(build())
+    lib = sim_build.shared(SO, SRC, DEPS)
     lib.overlapsim_pass_overlaps.restype = ctypes.c_int
     lib.overlapsim_pass_overlaps.argtypes = [ctypes.c_int] * 4
     lib.overlapsim_pass_settles_exact.restype = ctypes.c_int

@@ -1,12 +1,16 @@
 """Build + call the host harness of the per-line device routines (tests only)."""
 import ctypes
 import os
-import subprocess
 
 import numpy as np
 
+from tests import geno_sim, sim_build
+
 HERE = os.path.dirname(os.path.abspath(__file__))
 SO = os.path.join(HERE, "_hostsim.so")
+CSRC = os.path.join(HERE, "..", "..", "svjedi-graph_amd", "csrc")
+DEPS = [os.path.join(CSRC, h) for h in ("svjg_line.h", "svjg_host_tables.h", "svjg_planes.h", "svjg_pass.h", "svjg_geno.h")] + [
+    os.path.join(HERE, "..", "host_logfact.h"), os.path.join(HERE, "..", "..", "include", "svjg.h")]
 class HostLine(Exception):
     """the exact routine's "the host decides" (svjg.h: SVJG_EXC_ASK_HOST): a decimal column with non-ASCII bytes"""
 
@@ -14,22 +18,18 @@ class HostLine(Exception):
 EXC = {1: ValueError, 2: IndexError, 3: KeyError, 4: ZeroDivisionError, 5: HostLine, 6: TypeError}
 
 
+def _so():
+    return sim_build.shared(SO, os.path.join(HERE, "hostsim.cpp"), DEPS)
+
+
 def build():
-    src = [os.path.join(HERE, "hostsim.cpp"),
-           os.path.join(HERE, "..", "..", "svjedi-graph_amd", "csrc", "svjg_line.h"),
-           os.path.join(HERE, "..", "..", "svjedi-graph_amd", "csrc", "svjg_host_tables.h"),
-           os.path.join(HERE, "..", "..", "svjedi-graph_amd", "csrc", "svjg_planes.h"),
-           os.path.join(HERE, "..", "..", "svjedi-graph_amd", "csrc", "svjg_pass.h"),
-           os.path.join(HERE, "..", "..", "svjedi-graph_amd", "csrc", "svjg_geno.h"),
-           os.path.join(HERE, "..", "..", "include", "svjg.h")]
-    if not os.path.exists(SO) or os.path.getmtime(SO) < max(os.path.getmtime(s) for s in src):
-        subprocess.run(["g++", "-O2", "-std=c++17", "-Wall", "-shared", "-fPIC", "-o", SO, src[0]], check=True)
+    _so()
     return SO
 
 
 def _lib():
     from svjg import capi
-    lib = ctypes.CDLL(build())
+    lib = _so()
     lib.hostsim_classify.restype = ctypes.c_int
     lib.hostsim_classify.argtypes = [ctypes.POINTER(capi.CGraph), ctypes.c_void_p, ctypes.c_uint64, ctypes.c_void_p] + [ctypes.c_void_p] * 3
     lib.hostsim_check_tables.restype = ctypes.c_uint64
@@ -100,7 +100,7 @@ def table_stats(graph):
 def span_classes(text):
     """Byte-class masks of the 64-byte spans of text (len % 64 == 0) by the main kernel's bit-plane routine:
     uint64[n_spans, 8] = nl, cr, tab, ori, nd, dee, colon, high."""
-    lib = ctypes.CDLL(build())
+    lib = _so()
     buf = np.frombuffer(bytes(text), dtype=np.uint8)
     assert buf.size % 64 == 0
     out = np.zeros((buf.size // 64, 8), np.uint64)
@@ -113,7 +113,7 @@ def span_classes(text):
 def pass_logic():
     """the fused pass's host decisions (svjedi-graph_amd/csrc/svjg_pass.h) -> (repeat_word(overflow), repeats(has_comm, overflow, guard_sum),
     counts_overflowed(max_ref_sum, max_alt_sum), number of guard words)"""
-    lib = ctypes.CDLL(build())
+    lib = _so()
     lib.hostsim_pass_repeat_word.restype = ctypes.c_uint64
     lib.hostsim_pass_repeat_word.argtypes = [ctypes.c_uint32]
     lib.hostsim_pass_repeats.restype = ctypes.c_int
@@ -125,29 +125,26 @@ def pass_logic():
             lambda a, b: bool(lib.hostsim_pass_counts_overflowed(a, b)), int(lib.hostsim_guard_words()))
 
 
-STEP_FIELDS = ("pl", "raw", "gt", "flags", "boundary", "maxn", "slot", "type", "ok", "total")
 FUSED_FIELDS = ("pl32", "raw", "gt", "flags", "boundary", "h_tail", "out_bytes", "maxn", "status", "guard", "tail_bytes", "pl64", "total",
                 "slot", "type", "ok", "in_bytes")
-PLOIDY_FIELDS = ("pl", "raw", "gt", "flags", "boundary", "maxn", "logtab", "slot", "type", "ok", "ploidy", "in_bytes", "total")
-SITES_FIELDS = ("pl", "raw", "gt", "boundary", "maxn", "logs", "slots", "in_bytes", "total")
 
 
-def rows_layout(n, fused=False, which=None):
-    """byte offsets of the row block(s) of a genotype call over n rows (svjg_geno.h: rows_layout / run_layout + rows_in), by field name;
-    which = 2: the block of svjg_genotype_ploidy (ploidy_layout), 3: of svjg_genotype_sites over n sites (sites_layout)"""
-    lib = ctypes.CDLL(build())
-    lib.hostsim_rows_layout.restype = ctypes.c_int
-    lib.hostsim_rows_layout.argtypes = [ctypes.c_uint64, ctypes.c_int, ctypes.c_void_p]
-    out = (ctypes.c_uint64 * 32)()
-    which = int(fused) if which is None else which
-    names = (STEP_FIELDS, FUSED_FIELDS, PLOIDY_FIELDS, SITES_FIELDS)[which]
-    assert lib.hostsim_rows_layout(n, which, out) == len(names)
-    return {k: int(out[i]) for i, k in enumerate(names)}
+def rows_layout(n, fused=False):
+    """byte offsets of the row block(s) of k_genotype's calls over n rows (svjg_geno.h: rows_layout / run_layout + rows_in), by field name (the
+    blocks of the other calls: tests/geno_sim).  The step-by-step block is exported by both libraries: the names are geno_sim's, the values must agree"""
+    out = np.zeros(32, np.uint64)
+    count = sim_build.call(_so(), "hostsim_rows_layout", ctypes.c_int, [ctypes.c_uint64, ctypes.c_int, ctypes.c_void_p], n, int(fused), out)
+    if fused:
+        assert count == len(FUSED_FIELDS)
+        return {k: int(out[i]) for i, k in enumerate(FUSED_FIELDS)}
+    L = geno_sim.layout(geno_sim.ROWS, n)
+    assert list(L.values()) == [int(v) for v in out[:count]]
+    return L
 
 
 def geno_constants():
     """(sizeof(DevStatus), logfact_first(), LOGFACT_CAP, logfact_grow_to) of the library's headers"""
-    lib = ctypes.CDLL(build())
+    lib = _so()
     lib.hostsim_sizeof_devstatus.restype = ctypes.c_uint64
     for f in (lib.hostsim_logfact_first, lib.hostsim_logfact_grow_to, lib.hostsim_logfact_cap):
         f.restype = ctypes.c_uint32
@@ -159,7 +156,7 @@ def geno_constants():
 def logfact_sizes():
     """(logfact_built(upto): the entries a build for `upto` makes, logfact_reserve_to(have, entries): the size svjg_logfact_reserve builds or 0)
     of svjg_geno.h"""
-    lib = ctypes.CDLL(build())
+    lib = _so()
     lib.hostsim_logfact_built.restype = lib.hostsim_logfact_reserve_to.restype = ctypes.c_uint32
     lib.hostsim_logfact_built.argtypes = [ctypes.c_uint32]
     lib.hostsim_logfact_reserve_to.argtypes = [ctypes.c_uint32, ctypes.c_uint32]
@@ -168,25 +165,17 @@ def logfact_sizes():
 
 def logfact_table(n):
     """log10(i!) for i < n in double-double (float64[n, 2]), built with the host libm's log10 — not the device's"""
-    lib = ctypes.CDLL(build())
     tab = np.zeros((n, 2), np.float64)
-    lib.hostsim_logfact.restype = None
-    lib.hostsim_logfact.argtypes = [ctypes.c_void_p, ctypes.c_uint32]
-    lib.hostsim_logfact(tab.ctypes.data, n)
+    sim_build.call(_so(), "hostsim_logfact", None, [ctypes.c_void_p, ctypes.c_uint32], tab, n)
     return tab
 
 
 def genotype_rows(sv_type, counts, min_support, err, tab):
     """k_genotype's per-row arithmetic (svjg_geno.h: geno_row) -> (gt, pl[n, 3], near, status: 0 ok, 1 table too short, 2 beyond the cap)"""
-    lib = ctypes.CDLL(build())
-    sv_type = np.ascontiguousarray(sv_type, np.uint8)
-    counts = np.ascontiguousarray(counts, np.uint32)
-    tab = np.ascontiguousarray(tab, np.float64)
+    sv_type, counts, tab = np.ascontiguousarray(sv_type, np.uint8), np.ascontiguousarray(counts, np.uint32), np.ascontiguousarray(tab, np.float64)
     n = len(sv_type)
     gt, pl, near, st = np.zeros(n, np.uint8), np.zeros((n, 3), np.int64), np.zeros(n, np.uint8), np.zeros(n, np.uint8)
-    lib.hostsim_genotype.restype = None
-    lib.hostsim_genotype.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_uint32, ctypes.c_double, ctypes.c_void_p,
-                                     ctypes.c_uint32] + [ctypes.c_void_p] * 4
-    lib.hostsim_genotype(sv_type.ctypes.data, counts.ctypes.data, n, int(min_support), float(err), tab.ctypes.data, len(tab),
-                         gt.ctypes.data, pl.ctypes.data, near.ctypes.data, st.ctypes.data)
+    sim_build.call(_so(), "hostsim_genotype", None, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_uint32, ctypes.c_double, ctypes.c_void_p,
+                                                     ctypes.c_uint32] + [ctypes.c_void_p] * 4,
+                   sv_type, counts, n, int(min_support), float(err), tab, len(tab), gt, pl, near, st)
     return gt, pl, near, st

@@ -1,6 +1,6 @@
 """Cohort genotyping without a GPU: the cohort list, the union of the samples' keys, the INFO rewrite, the multi-sample writer fed with the
 reference's per-sample columns (tests/golden/cohort/, tests/cohort_model.py), and the two integer pieces of the device leg compiled with
-g++ (tests/cohort_sim: cohort_layout, cohort_segment)."""
+g++ (tests/geno_sim: cohort_layout, cohort_segment)."""
 import os
 import sys
 
@@ -10,7 +10,7 @@ import pytest
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 from tests import cohort_model as CM      # noqa: E402
-from tests.cohort_sim import sim          # noqa: E402
+from tests.geno_sim import cohort as sim  # noqa: E402
 
 
 # ---- the cohort list ----

@@ -1,5 +1,5 @@
 """Cohort calls for insertions that share a position (--cohort LIST --joint-ins), on the CPU: the plain pieces of the device leg compiled with
-g++ (tests/site_sim: the member compaction, the site sums under cohort_segment's masks, the layout, and geno_site behind the compaction
+g++ (tests/geno_sim: the member compaction, the site sums under cohort_segment's masks, the layout, and geno_site behind the compaction
 against tests/site_model.py on the present members); the host flow with a stand-in context that answers from the models — grouping, the ONE
 sites call, every column against the single-sample --joint-ins run of that sample, the site tags, the header; the golden cohort; the refusals."""
 import json
@@ -12,7 +12,7 @@ import pytest
 
 from tests import ploidy_model as PM
 from tests import site_model as SM
-from tests.site_sim import sim
+from tests.geno_sim import site as sim
 from tests.test_joint_ins import _ROWS, KEYS, COUNTS, VCF_TEXT, ModelCtx
 
 NO_CALL = 0xFF
@@ -83,7 +83,7 @@ def test_site_sums_from_the_leaders_against_brute_force(S):
 
 def test_harness_under_the_sanitizers():
     """the same pieces as a stand-alone program with its own main under -fsanitize=address,undefined (nothing is loaded into Python)"""
-    p = subprocess.run([sim.build_main()], capture_output=True, text=True)
+    p = subprocess.run([sim.build_main(), "site"], capture_output=True, text=True)
     assert p.returncode == 0 and p.stdout.startswith("site_sim ok") and not p.stderr, (p.stdout, p.stderr)
 
 
@@ -112,7 +112,7 @@ def test_chunk_keeps_a_call_under_one_gib():
 def test_item_arithmetic_against_the_model_on_the_present_members():
     """random sites of SM.random_sites spread over the six candidate places, candidates dropped at random: K' = 0..6.  An item with K' >= 2 is
     tests/site_model.py on its present members (check_against_model); K' < 2: no call, zeros"""
-    from tests.site_sim import sim as site_sim
+    from tests.geno_sim import site as site_sim
     rng = np.random.default_rng(5)
     sites = SM.random_sites(2_400, seed=99)
     n = len(sites)

@@ -1,5 +1,5 @@
 """Cohort genotyping at per-sample ploidy without a GPU: the --cohort-ploidy file, the ploidy matrix, the INFO rewrite with AN, the writer's
-text, and the integer pieces of the device leg compiled with g++ (tests/cohort_sim: cohort_layout per item, cohort_ploidy_sums under
+text, and the integer pieces of the device leg compiled with g++ (tests/geno_sim: cohort_layout per item, cohort_ploidy_sums under
 cohort_segment's masks)."""
 import os
 import subprocess
@@ -10,7 +10,7 @@ import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
-from tests.cohort_sim import sim                     # noqa: E402
+from tests.geno_sim import cohort as sim             # noqa: E402
 
 NAMES = ["A", "B b", "C"]
 VCF = ("##fileformat=VCFv4.2\n"
@@ -244,6 +244,6 @@ def test_site_sums_from_ballots_against_brute_force(S):
 
 def test_harness_under_the_sanitizers():
     """the stand-alone program (its own main) built with -fsanitize=address,undefined: every wave again, and the layouts"""
-    p = subprocess.run([sim.build_main()], capture_output=True, text=True)
+    p = subprocess.run([sim.build_main(), "cohort"], capture_output=True, text=True)
     assert p.returncode == 0 and p.stdout.startswith("cohort_sim ok:"), p.stdout + p.stderr
     assert "runtime error" not in p.stderr and "AddressSanitizer" not in p.stderr

@@ -1,5 +1,5 @@
 """The cohort call with an allele-frequency prior without a GPU: the per-item routines of svjg_geno.h and a sequential row EM compiled with g++
-(tests/cohort_prior_sim) against the 60-digit model (tests/cohort_prior_model.py), the stored answers of the model
+(tests/geno_sim) against the 60-digit model (tests/cohort_prior_model.py), the stored answers of the model
 (tests/golden/cohort_prior/) against the model itself on a sample of rows, the block's layout, the writer's text over tests/golden/cohort/, the
 driver's joining of chunks, and the script's argument errors."""
 import os
@@ -15,7 +15,7 @@ sys.path.insert(0, ROOT)
 from tests import cohort_model as CM                  # noqa: E402
 from tests import cohort_prior_cases as CC            # noqa: E402
 from tests import cohort_prior_model as M             # noqa: E402
-from tests.cohort_prior_sim import sim                # noqa: E402
+from tests.geno_sim import prior as sim              # noqa: E402
 
 AMD = os.path.join(ROOT, "svjedi-graph_amd")
 NO_CALL = 0xFF
@@ -144,7 +144,7 @@ def test_the_cases_hold_what_the_issue_asks_for():
 
 def test_harness_under_the_sanitizers():
     """the stand-alone program (its own main) built with -fsanitize=address,undefined"""
-    p = subprocess.run([sim.build_main()], capture_output=True, text=True)
+    p = subprocess.run([sim.build_main(), "prior"], capture_output=True, text=True)
     assert p.returncode == 0 and p.stdout.startswith("cohort_prior_sim ok:"), p.stdout + p.stderr
     assert "runtime error" not in p.stderr and "AddressSanitizer" not in p.stderr
 

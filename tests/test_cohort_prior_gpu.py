@@ -20,7 +20,7 @@ import pytest
 from tests import cohort_model as CM
 from tests import cohort_prior_cases as CC
 from tests import cohort_prior_model as M
-from tests.cohort_prior_sim import sim
+from tests.geno_sim import prior as sim
 from tests.test_cohort_gpu import _load_matrix
 
 pytestmark = pytest.mark.gpu

@@ -1,5 +1,5 @@
 """The cohort site quality without a GPU: the recurrence of the 60-digit model (tests/cohort_qual_model.py) against an enumeration of every
-genotype configuration and against Li's three-term form; the per-row routines of svjg_geno.h compiled with g++ (tests/cohort_qual_sim), in a
+genotype configuration and against Li's three-term form; the per-row routines of svjg_geno.h compiled with g++ (tests/geno_sim), in a
 sequential order and in the kernel's order of the sums, against the model's stored answers (tests/golden/cohort_qual/), which are recomputed on a
 sample of rows; the regime that forces the normalised recurrence; the block's layout and the rescaling's cadence; the writer's text; the
 script's argument errors."""
@@ -19,8 +19,8 @@ sys.path.insert(0, ROOT)
 from tests import cohort_prior_model as PM            # noqa: E402
 from tests import cohort_qual_cases as QC             # noqa: E402
 from tests import cohort_qual_model as M              # noqa: E402
-from tests.cohort_qual_sim import sim                 # noqa: E402
-from tests.cohort_prior_sim import sim as prior_sim   # noqa: E402
+from tests.geno_sim import qual as sim                # noqa: E402
+from tests.geno_sim import prior as prior_sim        # noqa: E402
 
 AMD = os.path.join(ROOT, "svjedi-graph_amd")
 ALL = [c[0] for c in QC.CASES]
@@ -224,7 +224,7 @@ def test_layout():
 
 def test_standalone_program_under_the_sanitizers():
     """the same routines under -fsanitize=address,undefined, in a program of their own"""
-    p = subprocess.run([sim.build_main()], capture_output=True, text=True)
+    p = subprocess.run([sim.build_main(), "qual"], capture_output=True, text=True)
     assert p.returncode == 0 and "cohort_qual_sim ok" in p.stdout, p.stdout + p.stderr
 
 

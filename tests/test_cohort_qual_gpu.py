@@ -19,7 +19,7 @@ from tests import cohort_model as CM
 from tests import cohort_prior_model as PM
 from tests import cohort_qual_cases as QC
 from tests import cohort_qual_model as M
-from tests.cohort_qual_sim import sim
+from tests.geno_sim import qual as sim
 from tests.test_cohort_gpu import _load_matrix
 from tests.test_cohort_prior_gpu import _compute_units, _equal_bytes_in_every_copy
 

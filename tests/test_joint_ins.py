@@ -1,5 +1,5 @@
 """Insertions that share a position, genotyped together (--joint-ins), on the CPU: the model of tests/site_model.py against the reference's
-own answers at K = 1; the kernel's per-site arithmetic (svjg_geno.h: geno_site, compiled with g++ by tests/site_sim) against the model, with
+own answers at K = 1; the kernel's per-site arithmetic (svjg_geno.h: geno_site, compiled with g++ by tests/geno_sim) against the model, with
 the boundary guard held to its budget; the host recomputation exact_pl_site; how rows are grouped into sites; the projection and the writer's
 text; the refusal together with --ploidy."""
 import functools
@@ -29,7 +29,7 @@ def random_set():
 
 @functools.lru_cache(maxsize=None)
 def host_table():
-    from tests.site_sim import sim
+    from tests.geno_sim import site as sim
     return sim.logfact_table(TABLE_N)
 
 
@@ -48,7 +48,7 @@ def test_model_at_k_1_is_the_reference(golden):
 
 
 def test_site_arithmetic_against_the_model():
-    from tests.site_sim import sim
+    from tests.geno_sim import site as sim
     sites, want = random_set()
     assert len(sites) >= 6_000 and {len(a) for _, a in sites} == {2, 3, 4, 5, 6}
     deep = np.mean([max([ref] + alts) > 60 for ref, alts in sites])
@@ -70,7 +70,7 @@ def test_site_arithmetic_where_the_products_roundings_decide(kind):
     term T is 0, so none may be flagged and every PL is the routine's own — and K = 2 sites at err = 0.5 over the half pairs; and on the
     sites of site_products.npz, found by search (T = 0, none flagged)"""
     from tests import products_items as PI
-    from tests.site_sim import sim
+    from tests.geno_sim import site as sim
     for ms, e, sites, want in PI.site_items(kind):
         assert len(sites) > (25 if kind == "searched" else 500)
         gt, pl, near, st, s_k = sim.genotype_sites(sites, ms, e, host_table())
@@ -112,12 +112,12 @@ def test_searched_sites_are_the_models_and_a_fused_product_turns_them():
 
 @pytest.mark.parametrize("S", [1, 3])
 def test_cohort_site_items_where_the_products_roundings_decide(S):
-    """site_item (svjg_geno.h, through tests/site_sim) over the cohort sites calls that tests/test_genotype_products_gpu.py hands to
+    """site_item (svjg_geno.h, through tests/geno_sim) over the cohort sites calls that tests/test_genotype_products_gpu.py hands to
     k_genotype_cohort_sites (PI.cohort_site_items): every (site, sample) item is one searched site embedded on a subset of six candidates —
     gt, PLs, raw, members as expected from the model, nothing flagged, no table needed; the set mixes K' within a site, has masks with holes
     and items without a site call inside full waves"""
     from tests import products_items as PI
-    from tests.site_sim import sim
+    from tests.geno_sim import site as sim
     for item in PI.cohort_site_items(S):
         n = len(item.slots)
         assert n == PI.N_COHORT_SITES
@@ -137,7 +137,7 @@ def test_flagged_sites_of_a_large_set():
     """the random set flags about one site in 6 000: the harness alone runs 240 000 more, and the few dozen it flags are held to the model — one
     value within 2 x SITE_PL_GUARD of an integer, the call equal, exact_pl_site equal"""
     from svjg import genotype
-    from tests.site_sim import sim
+    from tests.geno_sim import site as sim
     sites = SM.random_sites(240_000, seed=7)
     e, ms = 5e-5, 3
     gt, pl, near, st, _ = sim.genotype_sites(sites, ms, e, host_table())
@@ -156,7 +156,7 @@ def test_flagged_sites_of_a_large_set():
 
 
 def test_log_table_is_the_models():
-    from tests.site_sim import sim
+    from tests.geno_sim import site as sim
     for e in (5e-5, 1e-2, 0.3, 0.5, 0.999):
         tab = sim.log_table(e)
         for K in range(2, 7):
@@ -164,7 +164,7 @@ def test_log_table_is_the_models():
 
 
 def test_table_too_short_and_beyond_the_cap():
-    from tests.site_sim import sim
+    from tests.geno_sim import site as sim
     tab = host_table()[:4096]
     sites = [(10, [20, 20]), (3000, [4000, 0]), (0, [0, 9000]), (0, [9000, 2]), (1 << 24, [0, 2, 0]), (0, [1 << 25, 0, 0, 0, 0, 0])]
     gt, pl, near, st, s_k = sim.genotype_sites(sites, 3, 5e-5, tab)
@@ -175,7 +175,7 @@ def test_table_too_short_and_beyond_the_cap():
 
 def test_known_answers():
     from svjg import genotype
-    from tests.site_sim import sim
+    from tests.geno_sim import site as sim
     tab = host_table()[:4096]
     e, ms = 5e-5, 3
     sites = [(0, [40, 20]), (10, [20, 20]), (0, [40, 0, 0]), (0, [2, 2])]

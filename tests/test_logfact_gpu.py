@@ -102,7 +102,7 @@ def test_cap_binomial_term(golden, cap_table):
 
 def test_cap_against_the_host_libm_table(cap_table):
     """the CPU stand-ins build the table with the host's log10 in another association: both lie inside the budget, so no entry differs by more
-    than twice the per-entry bound.  This is what lets tests/hostsim, tests/ploidy_sim and tests/site_sim speak for the device."""
+    than twice the per-entry bound.  This is what lets tests/hostsim and tests/geno_sim speak for the device."""
     from tests.hostsim import sim
     host = sim.logfact_table(CAP)
     differ, worst, at = LM.compare_tables(cap_table, host, "device against the host-libm table")

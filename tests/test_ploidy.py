@@ -1,5 +1,5 @@
 """Genotypes at any ploidy from 1 to 8, on the CPU: the model of tests/ploidy_model.py against the reference's own answers at ploidy 2;
-the kernel's per-row arithmetic (svjg_geno.h: geno_row_ploidy, compiled with g++ by tests/ploidy_sim) against the model, with the
+the kernel's per-row arithmetic (svjg_geno.h: geno_row_ploidy, compiled with g++ by tests/geno_sim) against the model, with the
 boundary guard held to its budget; the host recomputation exact_pl_ploidy; the ploidy file; the writer's text."""
 import functools
 
@@ -26,13 +26,13 @@ def random_set():
 
 @functools.lru_cache(maxsize=None)
 def host_table():
-    from tests.ploidy_sim import sim
+    from tests.geno_sim import ploidy as sim
     return sim.logfact_table(TABLE_N)
 
 
 @functools.lru_cache(maxsize=None)
 def harness_on_random_set():
-    from tests.ploidy_sim import sim
+    from tests.geno_sim import ploidy as sim
     rows, _ = random_set()
     n = len(rows)
     gt, pl, near, st = np.zeros(n, np.uint8), np.zeros((n, 9), np.int64), np.zeros(n, np.uint8), np.zeros(n, np.uint8)
@@ -67,7 +67,7 @@ def test_row_arithmetic_against_the_model():
 
 
 def test_log_table_is_the_models():
-    from tests.ploidy_sim import sim
+    from tests.geno_sim import ploidy as sim
     for e in (5e-5, 1e-2, 0.3, 0.5, 0.999):
         lr, la = sim.log_table(e)
         for P in range(1, 9):
@@ -79,7 +79,7 @@ def test_log_table_is_the_models():
 def test_ploidy_2_equals_the_diploid_routine(golden):
     """geno_row_ploidy at P = 2 against geno_row on the lik_kat rows: gt, three PLs, near — and, geno_row being that routine at the literal
     ploidy 2, both against the fixture's own columns (the reference's answers): GT on every row, the PLs on every row that is not flagged"""
-    from tests.ploidy_sim import sim
+    from tests.geno_sim import ploidy as sim
     z = np.load(f"{golden}/lik/lik_kat.npz")
     cases, errs = z["cases"], z["err"]
     tab = host_table()
@@ -108,7 +108,7 @@ def test_row_arithmetic_where_the_products_roundings_decide(kind, P):
     """geno_row_ploidy on the rows of lik_products.npz (tests/products_items.py): deep one-sided rows at P = 1, 2, 3, 5, 6, 7, 8 — their binomial
     term is log10(1), so none may be flagged and every PL is the routine's own — and the rows at err = 0.5, where all P + 1 likelihoods
     coincide mathematically and the roundings of the products (and of the reference's 28-digit sums) decide GT, at P = 1, 2, 4, 6, 8"""
-    from tests.ploidy_sim import sim
+    from tests.geno_sim import ploidy as sim
     seen = 0
     for ms, e, rows, want in PI.ploidy_items(kind, P):
         gt, pl, near, st = sim.genotype_rows(rows[:, 0], rows[:, 1:3], rows[:, 3], ms, e, host_table())
@@ -128,7 +128,7 @@ def test_cohort_items_where_the_products_roundings_decide(kind, S):
     least 5 one-sided items at EVERY ploidy 1..8 change a PL or the GT at S = 3, and at least 4 at S = 1 (the ploidy formula and "every 11th
     item off" leave 219 items there, 37 of them sensitive: 4 at ploidies 1, 3 and 6, 5 at the others — 5 at every ploidy cannot be reached by
     one sample); half items at every even ploidy change their GT (at an odd ploidy all P + 1 likelihoods are one value: a tie stays a tie)"""
-    from tests.ploidy_sim import sim
+    from tests.geno_sim import ploidy as sim
     for item in PI.cohort_ploidy_items(kind, S):
         rows = item.rows
         assert len(item.type) * S < 8000 and set(rows[:, 3].tolist()) == set(range(1, 9)) and 0.08 < 1 - item.on.mean() < 0.1
@@ -154,7 +154,7 @@ def test_cohort_items_where_the_products_roundings_decide(kind, S):
 
 
 def test_ties_are_no_calls():
-    from tests.ploidy_sim import sim
+    from tests.geno_sim import ploidy as sim
     tab = host_table()[:4096]
     # INV (type 2): counts are not normalised.  P = 1: ref == alt ties lik_0 and lik_1.  P = 3: 10 / 10 ties g = 1 and g = 2.
     for P, ref, alt in ((1, 7, 7), (3, 10, 10)):
@@ -165,6 +165,14 @@ def test_ties_are_no_calls():
     assert gt.tolist() == [1, 2]
     gt, _, _, _ = sim.genotype_rows([2, 2], [[1, 0], [0, 40]], [1, 8], 3, 5e-5, tab)       # below min_support; a clear call
     assert gt.tolist() == [NO_CALL, 8]
+
+
+def test_harness_under_the_sanitizers():
+    """the stand-alone program (its own main) built with -fsanitize=address,undefined: 200 000 seeded rows through geno_row_ploidy and geno_row"""
+    import subprocess
+    from tests.geno_sim import ploidy as sim
+    p = subprocess.run([sim.build_main(), "ploidy"], capture_output=True, text=True)
+    assert p.returncode == 0 and p.stdout.startswith("ploidy_sim ok:") and not p.stderr, (p.stdout, p.stderr)
 
 
 def test_exact_pl_ploidy_is_the_model(golden):

@@ -1,5 +1,5 @@
 """Where the rows of a genotype call lie, and how the log10(i!) table grows (svjedi-graph_amd/csrc/svjg_geno.h: rows_layout, ploidy_layout,
-sites_layout, run_layout, rows_in, logfact_grow_to), on the CPU through tests/hostsim.  svjg_genotype_view and svjg_run_end hand out pointers into these blocks and
+sites_layout, run_layout, rows_in, logfact_grow_to), on the CPU through tests/hostsim and tests/geno_sim.  svjg_genotype_view and svjg_run_end hand out pointers into these blocks and
 callers keep them, so every offset is pinned to the formula the library used before the layouts had one description: the formulas are
 written out HERE, as the expectation.  Besides: no two fields overlap, the last one ends inside the block, and every field is aligned
 for its element type."""
@@ -11,6 +11,7 @@ import pytest
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 from tests.hostsim import sim     # noqa: E402
+from tests.geno_sim import ploidy, site    # noqa: E402
 
 NS = (0, 1, 2, 3, 5, 63, 64, 65, 1000)
 
@@ -39,7 +40,7 @@ def test_step_by_step_block(n):
 
 @pytest.mark.parametrize("n", NS)
 def test_ploidy_block(n):
-    L = sim.rows_layout(n, which=2)
+    L = ploidy.layout(n)
     maxn = (83 * n + 7) & ~7
     logtab = maxn + 8                                            # the call's logarithms: 2 x 45 doubles
     slot = logtab + 720
@@ -54,7 +55,7 @@ def test_ploidy_block(n):
 
 @pytest.mark.parametrize("n", NS)
 def test_sites_block(n):
-    L = sim.rows_layout(n, which=3)
+    L = site.layout(n, 1, False, own_fields=True)
     maxn = (255 * n + 7) & ~7
     logs = maxn + 8                                              # the call's logarithms: 16 doubles
     assert L == {"pl": 0, "raw": 224 * n, "gt": 252 * n, "boundary": 254 * n, "maxn": maxn, "logs": logs, "slots": logs + 128,

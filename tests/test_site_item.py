@@ -1,11 +1,11 @@
-"""What both site kernels do per item, on the CPU (svjg_geno.h: site_gather, site_item, sites_layout, compiled with g++ by tests/site_sim): the slot
+"""What both site kernels do per item, on the CPU (svjg_geno.h: site_gather, site_item, sites_layout, compiled with g++ by tests/geno_sim): the slot
 gather against picking the candidates out one by one, bad slots, the item of the single-sample call against geno_site on the same (K, ref, alt),
 the item of the cohort call against the compaction and geno_site step by step, and the one layout in both of its cases."""
 import numpy as np
 import pytest
 
 from tests import site_model as SM
-from tests.site_sim import sim
+from tests.geno_sim import site as sim
 
 NONE = 0xFFFFFFFF
 NO_CALL = 0xFF
@@ -134,7 +134,7 @@ def test_cohort_item_is_the_compaction_and_geno_site_on_the_gathered_counts(tab)
 @pytest.mark.parametrize("n", [1, 7, 1000])
 def test_one_sites_layout_in_both_cases(n, S):
     """sites_layout(n, S, true) gives the offsets tests/test_cohort_joint_ins.py pins for the cohort call, sites_layout(n, 1, false) those
-    tests/test_rows_layout.py pins for the single-sample call (through tests/hostsim); a field the call does not have is 0"""
+    tests/test_rows_layout.py pins for the single-sample call; a field the call does not have is 0"""
     L, items = sim.layout(n, S, True), n * S
     site = (256 * items + 7) & ~7
     assert L == {"pl": 0, "raw": 224 * items, "gt": 252 * items, "members": 254 * items, "boundary": 255 * items, "site": site, "maxn": site + 48 * n,
