@@ -119,6 +119,40 @@ static int main_qual() {
         if (L[0] != 0 || L[1] != 8 * n_rows || L[2] != 12 * n_rows || L[3] % 8 || L[3] < 16 * n_rows || L[4] != L[3] + 8 || L[5] != L[4] || L[6] != L[5] + 720
             || L[7] != L[6] + 8 * (S * mp + 1) || L[10] != L[7] + 6 * n_rows || L[11] != L[10] + (per ? n_rows * S : 0) + 64) ++bad;
     }
+    // The shapes that max_ploidy and the ploidy array decide: the sex pattern (0 / 1 / 2 under max_ploidy 2), haploid with absent items (max_ploidy
+    // 1) and 0..mp at mp = 3..7, on both sides of 64 and 128 entries and at several hundred chromosomes; 512 samples of ploidy 8 with one read
+    // each (M = QUAL_MAX_CHROMS, cadence 4).  Each array is called at its own max_ploidy and at 8: the rows are sized differently, the bits are equal.
+    const uint64_t shape_sizes[10] = {20, 33, 63, 64, 65, 128, 129, 300, 600, 512};
+    for (uint64_t S : shape_sizes)
+        for (uint32_t mp = 1; mp <= 8; ++mp) {
+            if (S == 512 ? mp != 8 : (mp == 8 || (S * 8 > QUAL_MAX_CHROMS && mp > 2))) continue;
+            for (int k = 0; k < (S > 100 ? 2 : 10); ++k) {
+                std::vector<uint32_t> raw(S * 2); std::vector<uint8_t> done(S), pld(S);
+                uint32_t m_part = 0;
+                for (uint64_t s = 0; s < S; ++s) {
+                    const uint64_t v = next();
+                    const bool shallow = S >= 300;
+                    raw[s * 2] = shallow ? (v % 7 != 0) : (uint32_t)(v % ((v >> 40) % 3 ? 61 : 5)); raw[s * 2 + 1] = shallow ? 1u - raw[s * 2] : (uint32_t)((v >> 16) % ((v >> 44) % 3 ? 61 : 5));
+                    done[s] = S == 512 || (v >> 32) % 5 != 0;
+                    pld[s] = S == 512 ? 8 : mp == 2 ? (uint8_t)((v >> 36) % 3) : mp == 1 ? (uint8_t)((v >> 36) % 10 != 0) : (uint8_t)((v >> 36) % (mp + 1));
+                    if (done[s] && raw[s * 2] + raw[s * 2 + 1]) m_part += pld[s];
+                }
+                const uint32_t type = (uint32_t)(next() % 4), wide = S * 8 <= QUAL_MAX_CHROMS ? 8u : mp;
+                double q[3]; uint32_t ml[3], ch[3];
+                genosim_qual_row(0, type, raw.data(), done.data(), pld.data(), S, mp, 5e-5, 1e-3, 0, &q[0], &ml[0], &ch[0]);
+                genosim_qual_row(1, type, raw.data(), done.data(), pld.data(), S, mp, 5e-5, 1e-3, 0, &q[1], &ml[1], &ch[1]);
+                genosim_qual_row(1, type, raw.data(), done.data(), pld.data(), S, wide, 5e-5, 1e-3, 0, &q[2], &ml[2], &ch[2]);
+                ++rows;
+                for (int i = 0; i < 3; ++i) {
+                    if (ch[i] != m_part || ml[i] > ch[i]) ++bad;
+                    if (m_part ? !(q[i] >= 0.0 && q[i] < 1e9) : !(q[i] != q[i] && ml[i] == 0)) ++bad;
+                }
+                if (m_part && (q[1] != q[2] || ml[1] != ml[2])) ++bad;                                              // the same bits under a wider max_ploidy
+                if (m_part && fabs(q[0] - q[1]) > 1e-9 + 1e-12 * q[1]) ++bad;
+                if (S == 512 && ch[1] != QUAL_MAX_CHROMS) ++bad;
+            }
+        }
+    if (genosim_qual_every(1024, 8) != 5 || genosim_qual_every(512, 8) != 6 || genosim_qual_every(63, 1) != 85 || genosim_qual_every(64, 1) != 73) ++bad;
     if (genosim_qual_every(4096, 8) != 4 || genosim_qual_every(4096, 2) != 19 || genosim_qual_every(128, 2) != 32 || genosim_qual_every(1, 1) != 512) ++bad;
     printf("cohort_qual_sim %s: %llu rows, %llu checks failed\n", bad ? "FAILED" : "ok", (unsigned long long)rows, (unsigned long long)bad);
     return bad ? 1 : 0;

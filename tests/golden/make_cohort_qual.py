@@ -3,7 +3,8 @@
 tests/cohort_qual_cases.py.  Per case: chroms, mlac, qual as two doubles (qual = qual + qual_lo; NaN where no item takes part), the rows that a
 comparison leaves out — mlac where the two largest phi_k y_k lie within a relative 1e-9 of each other, the script's text where 100 SVQ lies within
 1e-6 of a half-integer — and a digest of the inputs.  Refuses a case whose left-out share exceeds the cap (pick another seed).  No device takes
-part: this runs on the CPU, minutes on a few cores (het_2048: two rows of 2 048 steps over up to 4 097 entries each).
+part: this runs on the CPU, minutes on a few cores (het_2048: two rows of 2 048 steps over up to 4 097 entries each; the 18 cases of
+cohort_qual_cases.SHAPE_CASES together: 15 s on eight cores, shallow_poly_512's two rows of 512 steps at ploidy 8 being the longest).
 
     python tests/golden/make_cohort_qual.py [case ...]
 """
@@ -55,7 +56,7 @@ if __name__ == "__main__":
     jobs = []
     for name in names:
         _, S, R, _, _ = next(c for c in QC.CASES + QC.EXTRA if c[0] == name)
-        step = 1 if S > 500 else 25                                 # the large rows one by one: the pool stays busy
+        step = 1 if S > 500 else 5 if S > 100 else 25               # the large rows one by one: the pool stays busy
         jobs += [(name, list(range(lo, min(R, lo + step)))) for lo in range(0, R, step)]
     jobs.sort(key=lambda j: -next(c[1] for c in QC.CASES + QC.EXTRA if c[0] == j[0]))
     parts = {name: [] for name in names}

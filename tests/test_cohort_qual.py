@@ -98,10 +98,14 @@ def test_constants_and_cadence():
     assert 0 < k["abs"] < 1e-9 and 0 < k["rel"] < 1e-12
     assert 0.05 * M.harmonic(4096) < 1                                  # phi_0 > 0 for every accepted call
     # between two rescalings the maximum cannot fall below 2^-512: one step shrinks it by at most 1 / C(M, P)
-    for m_max, P in ((1, 1), (2, 2), (128, 2), (130, 2), (136, 8), (1200, 2), (4096, 2), (4096, 8), (4095, 5)):
+    pairs = [(1, 1), (2, 2), (128, 2), (130, 2), (136, 8), (1200, 2), (4096, 2), (4096, 8), (4095, 5)]
+    pairs += [(c[1] * QC.MAX_PLOIDY[c[3]], QC.MAX_PLOIDY[c[3]]) for c in QC.SHAPE_CASES]
+    assert {(63, 1), (64, 1), (66, 2), (258, 2), (60, 3), (140, 7), (1024, 8), (600, 2), (600, 1), (512, 8)} <= set(pairs)
+    for m_max, P in pairs:
         n = sim.every(m_max, P)
         assert n >= 1 and (n == 1 or n * math.log2(math.comb(m_max, min(P, m_max))) <= 512)
     assert math.log2(math.comb(4096, 8)) < 82
+    assert sim.every(1024, 8) == 5 and sim.every(4096, 8) == 4 and sim.every(512, 8) == 6      # mixed_128, shallow_poly_512, steep_64
 
 
 def test_item_is_prior_item_with_d0_beside_it():
@@ -156,7 +160,9 @@ def test_harness_against_the_model(name):
         if every == 0:
             worst = [max(worst[0], a), max(worst[1], r)]
     print("%s: max |qual - model| = %.3e absolute (model < 1), %.3e relative (model >= 1)" % (name, worst[0], worst[1]))
-    assert worst[0] <= 1.044e-14 and worst[1] <= 1.994e-15           # what svjg_geno.h says the harness measured (the asserted bound is 8 x the DEVICE's maxima)
+    # what svjg_geno.h says the harness measured (the asserted bound is 8 x the DEVICE's maxima): 1.044e-14 and 1.994e-15 over the first 16 cases;
+    # the relative one is now shallow_hap_600's, on a row whose model value is 3.4 (0.35 of the bound there)
+    assert worst[0] <= 1.044e-14 and worst[1] <= 8.558e-15
     QC.check_planted(c, done, raw, *got)
 
 
@@ -167,13 +173,84 @@ def test_stored_answers_are_the_models(name):
     want = QC.load_golden(name, c)
     done, raw = QC.gate(c)
     R = len(c["t"])
-    rows = sorted(set(c["planted"].values()) | set(np.random.default_rng(5).permutation(R)[:6].tolist())) if c["S"] <= 100 else [R - 1] if c["S"] <= 600 else []
+    if c["S"] <= 100:
+        rows = sorted(set(c["planted"].values()) | set(np.random.default_rng(5).permutation(R)[:6].tolist()))
+    else:                                                            # the last row with a quality, unless a row takes seconds (M = 4 096)
+        rows = [int(np.flatnonzero(~np.isnan(want["qual"]))[-1])] if c["S"] * c["max_ploidy"] <= 1200 else []
     m = M.run(c["t"], raw, done, c["ploidy"], QC.ERR, QC.THETA, rows=rows)
     for r in rows:
         assert m["chroms"][r] == want["chroms"][r] and m["mlac"][r] == want["mlac"][r]
         assert (np.isnan(m["qual"][r]) and np.isnan(want["qual"][r])) or (m["qual"][r] == want["qual"][r] and np.float32(m["qual_lo"][r]) == np.float32(want["qual_lo"][r]))
         if not np.isnan(m["qual"][r]):
             assert bool(m["gap"][r] < QC.TOP_GAP) == bool(want["mlac_out"][r]) and bool(m["half"][r] < QC.HALF_BAND) == bool(want["text_out"][r])
+
+
+def test_what_each_shape_case_is_for():
+    """on the model's arrays alone: the shapes the new cases were made for are in them"""
+    got = {}
+    for name in QC.NEW:
+        c = QC.inputs(name)
+        want = QC.load_golden(name, c)
+        assert want["mlac_out"].mean() <= QC.CAP and want["text_out"].mean() <= QC.CAP
+        got[name] = (c, want, ~np.isnan(want["qual"]))
+    for S in QC.HAP_SIZES:                                          # M + 1 = 64, 65, 66 and 130: a lane's last entry of one, two and three trips
+        c, want, has = got["hap_%d" % S]
+        assert int(c["ploidy"].max()) == c["max_ploidy"] == 1 and (c["ploidy"] == 0).any()
+        assert (want["chroms"][:50] + 1 == S + 1).sum() >= 20 and (want["chroms"] <= S).all() and (want["chroms"][has] < S).any()
+    for S in QC.SEX_SIZES:
+        c, want, has = got["sex_%d" % S]
+        assert int(c["ploidy"].max()) == c["max_ploidy"] == 2
+        pl = c["ploidy"]
+        classes = ((pl == 2).all(axis=1), (pl == 2).any(axis=1) & (pl == 1).any(axis=1), (pl == 0).any(axis=1) & (pl == 1).any(axis=1))
+        assert all((k & has).sum() >= 20 for k in classes) and (classes[0] | classes[1] | classes[2]).all()
+        assert (want["chroms"][classes[1] & has] % 2 == 1).any() and (want["chroms"][classes[2] & has] % 2 == 1).any()
+    for name in ("mixed_128", "shallow_mixed_128"):                 # k >= 448: a lane's eighth trip
+        c, want, has = got[name]
+        assert c["max_ploidy"] == 8 and (want["chroms"] >= 448).sum() > len(has) // 2
+    c, want, has = got["shallow_poly_512"]
+    assert (want["chroms"] == 4096).all() and c["max_ploidy"] == 8 and 16 * 4097 + 720 > 65536
+    for P in QC.MIXED_UPTO:
+        c, want, has = got["mixed_m%d_20" % P]
+        done, raw = QC.gate(c)
+        part = (done != 0) & (raw.sum(axis=2) > 0)
+        assert int(c["ploidy"].max()) == c["max_ploidy"] == P and set(np.unique(c["ploidy"])) == set(range(P + 1))
+        assert (part & (c["ploidy"] == P)).any() and all((part & (c["ploidy"] == g)).any() for g in range(1, P + 1))
+    for name in QC.NEW:                                             # where QUAL_ABS is what is tested
+        c, want, has = got[name]
+        if name.startswith("shallow_"):
+            assert has.all() and (want["qual"] < 100).sum() * 3 >= len(has) and (want["qual"] < 1).any()
+    c, want, has = got["steep_64"]                                   # the model does not know the samples' order
+    assert (want["chroms"] == 512).all() and want["mlac"][0] == want["mlac"][1] == 256 and want["qual"].min() > 5e4
+    assert abs((want["qual"][0] - want["qual"][1]) + (want["qual_lo"][0] - want["qual_lo"][1])) < 1e-30 * want["qual"][0]
+
+
+UNDER = [c[0] for c in QC.SHAPE_CASES if QC.MAX_PLOIDY[c[3]] < 8] + ["mixed_3"]
+
+
+def max_ploidies_of(c):
+    """the max_ploidy values a case's array may be called with: its own to 8, as far as S max_ploidy stays a call (QUAL_MAX_CHROMS)"""
+    return [mp for mp in range(c["max_ploidy"], 9) if c["S"] * mp <= 4096]
+
+
+@pytest.mark.parametrize("name", UNDER)
+def test_one_array_under_every_max_ploidy(name):
+    """One ploidy array called at every max_ploidy from the array's largest value to 8, in the kernel's order of the sums.  max_ploidy sizes the
+    row and sets the rescaling's cadence and nothing else: every answer is within the bound of the model, and all are EQUAL byte for byte, qual
+    and mlac both — a rescaling multiplies the whole row by an exact power of two and adds the exponent to an integer, so when it happens changes
+    no bit until an entry underflows between two of them, and at these depths none does (the deep pattern, where weights underflow by design, is
+    not among the cases)."""
+    c = QC.inputs(name)
+    assert c["ploidy"] is not None and (c["max_ploidy"] < 8 or name == "mixed_3")
+    want = QC.load_golden(name, c)
+    done, raw = QC.gate(c)
+    first = None
+    for mp in max_ploidies_of(c):
+        got = sim.rows(c["t"], raw, done, c["ploidy"], mp, QC.ERR, QC.THETA, wave=True)
+        _compare("%s at max_ploidy %d" % (name, mp), want, got)
+        if first is None:
+            first = got
+        assert all(x.tobytes() == y.tobytes() for x, y in zip(first, got)), (name, mp)
+    assert first is not None
 
 
 def _plain_convolution(items_a, theta):

@@ -1,7 +1,10 @@
 """The cohort site quality on the GPU (svjg_cohort_qual, k_cohort_qual) against the 60-digit model of tests/cohort_qual_model.py, whose answers
 for the cases of tests/cohort_qual_cases.py are stored under tests/golden/cohort_qual/: 300 rows x S diploid samples with M + 1 on both sides of
 64 and 128, 300 rows x S at ploidies 0..8 mixed within rows, deep counts, 20 rows x 600 shallow samples, 2 rows x 2 048 samples (M = the call's
-limit); chunked calls, calls of more rows than one trip of the grid, the rows that only the cohort decides, the argument errors, the script.
+limit); the shapes that max_ploidy and the ploidy array decide (the chrX / chrY pattern under max_ploidy 2, haploid under max_ploidy 1, ploidies
+0..P under max_ploidy P = 3..7, 128 samples at 0..8, the shallow regime at mixed ploidy, haploid and at 512 samples of ploidy 8, the steepest
+shrink per step), one array under every max_ploidy; chunked calls, calls of more rows than one trip of the grid, the rows that only the cohort
+decides, the argument errors, the script.
 Needs an MI355X: run with -m gpu.
 
 What may be left out of a comparison is decided by the model alone, before any device ran (tests/golden/make_cohort_qual.py): mlac on rows whose
@@ -82,21 +85,50 @@ def test_case_against_the_model(ctx, name):
         assert (got[2] == sim.constants()["max_chroms"]).all() and np.array_equal(got[1], got[2] // 2)
     if name == "shallow_600":
         assert (got[1][:10] == 0).all() and (got[0][:10] < 0.1).all()
+    if name == "shallow_poly_512":                                 # the call's limit at max_ploidy 8: the request beyond 64 KiB of LDS, with every entry in use
+        assert (got[2] == 4096).all() and c["S"] * c["max_ploidy"] == sim.constants()["max_chroms"]
+    if name == "steep_64":                                         # row 1 is row 0 in reverse sample order: the model does not know the order
+        k = sim.constants()
+        assert got[1][0] == got[1][1] == 256 and abs(got[0][0] - got[0][1]) <= k["abs"] + k["rel"] * want["qual"][0]
+
+
+@pytest.mark.parametrize("name", ["sex_65", "hap_65", "mixed_m3_20", "mixed_m5_20", "shallow_sex_300"])
+def test_one_array_under_every_max_ploidy(ctx, name):
+    """tests/test_cohort_qual.py's test of the same name, on the device: one ploidy array called at every max_ploidy from the array's largest value
+    to 8.  max_ploidy sizes the two rows in LDS, the harmonic table and the launch, and sets the rescaling's cadence; every call is within the
+    bound of the model, and has the bytes of the call at the case's own max_ploidy (a rescaling multiplies by an exact power of two, so when it
+    happens changes no bit until something underflows; the host harness has equal bytes on every one of these cases)"""
+    from tests.test_cohort_qual import UNDER, max_ploidies_of
+    assert name in UNDER                                           # equal bytes are asserted there
+    c = QC.inputs(name)
+    want = QC.load_golden(name, c)
+    _load_matrix(ctx, c["n_slots"], c["counts"], c["present"])
+    own = _qual(ctx, c)
+    _check_against_model(name, want, own)
+    wider = max_ploidies_of(c)[1:]
+    assert wider[-1] == 8 and len(wider) == 8 - c["max_ploidy"]
+    for mp in wider:
+        got = _qual(ctx, dict(c, max_ploidy=mp))
+        _check_against_model("%s at max_ploidy %d" % (name, mp), want, got)
+        assert all(x.tobytes() == y.tobytes() for x, y in zip(own, got)), (name, mp)
 
 
 def test_chunks_equal_one_call(ctx):
     from svjg import genotype
-    for name in ("null_33", "mixed_9", "null_65"):
+    for name in ("null_33", "mixed_9", "null_65", "sex_65", "hap_129", "mixed_m3_20"):
         c = QC.inputs(name)
         _load_matrix(ctx, c["n_slots"], c["counts"], c["present"])
         rows = types.SimpleNamespace(sv_type=c["t"], slot=c["slot"], ok=c["ok"])
-        one = genotype.cohort_qual_rows(ctx, rows, c["S"], c["ploidy"], QC.ERR)
-        parts = genotype.cohort_qual_rows(ctx, rows, c["S"], c["ploidy"], QC.ERR, step=97)
+        seen = []                                                   # the max_ploidy of every call: the array's largest value (2, 1 and 3 for the last three)
+        spy = types.SimpleNamespace(cohort_qual=lambda t, slot, ok, ploidy, mp, *rest: seen.append(mp) or ctx.cohort_qual(t, slot, ok, ploidy, mp, *rest))
+        one = genotype.cohort_qual_rows(spy, rows, c["S"], c["ploidy"], QC.ERR)
+        parts = genotype.cohort_qual_rows(spy, rows, c["S"], c["ploidy"], QC.ERR, step=97)
+        assert len(seen) == 1 + -(-len(c["t"]) // 97) and set(seen) == {c["max_ploidy"]}
         assert len(one) == 3 and all(x.tobytes() == y.tobytes() and x.shape == y.shape for x, y in zip(one, parts))
         assert all(x.tobytes() == y.tobytes() for x, y in zip(one, _qual(ctx, c)))
 
 
-@pytest.mark.parametrize("name", ["null_33", "mixed_9", "shallow_600"])
+@pytest.mark.parametrize("name", ["null_33", "mixed_9", "shallow_600", "sex_65", "hap_129", "mixed_m3_20"])
 def test_more_rows_than_one_trip_of_the_grid(ctx, name):
     """The launch is capped at what a compute unit holds of one-wave blocks (16 by registers, fewer where the rows' LDS decides): a case's rows,
     repeated until the call has more rows than that plus a partial last trip, so that blocks take the grid-stride loop a second time and set up y,
@@ -258,12 +290,77 @@ def _without_quality(line):
     return "\t".join(f)
 
 
-@pytest.mark.parametrize("prior", [False, True])
+PLOIDY_LINES = [("S1", "2\t1"), ("S2", "2\t1"), ("S3", "1\t30000\t40000\t0"), ("S4", "1\t3"), ("*", "2\t2")]   # tests/test_cohort_ploidy_gpu.py's mixed file
+
+
+def _ploidy_of_lines(co):
+    """the ploidy matrix that PLOIDY_LINES say, by hand: a sample's own lines and the `*` lines in file order, the first that matches the row's
+    CHROM (and POS, for a region line) wins, 2 without one"""
+    out = np.full((len(co.rows.chrom), len(co.names)), 2, np.uint8)
+    for s, name in enumerate(co.names):
+        for r, (chrom, pos) in enumerate(zip(co.rows.chrom, co.rows.pos)):
+            for who, rest in PLOIDY_LINES:
+                f = rest.split("\t")
+                if who in (name, "*") and f[0] == chrom and (len(f) == 2 or int(f[1]) <= int(pos) <= int(f[2])):
+                    out[r, s] = int(f[-1])
+                    break
+    return out
+
+
+def _quality_tags(line):
+    return [x for x in line.split("\t")[7].split(";") if x.split("=", 1)[0] in ("SVQ", "MLAC", "MLAF")]
+
+
+def _script_with_a_ploidy_file(co, tmp_path):
+    """--cohort LIST --cohort-ploidy FILE --cohort-qual: the three tags of every row are what the writer prints from the model's answer on the
+    file's ploidy matrix (S1 and S2 haploid on contig 2, S3 at ploidy 0 on 1:30000-40000, S4 triploid on contig 1); every other byte is the run
+    without --cohort-qual; --cohort-theta changes the three tags only"""
+    from svjg import genotype
+    ploidy = _ploidy_of_lines(co)
+    assert sorted(np.unique(ploidy).tolist()) == [0, 1, 2, 3] and (ploidy[:, 2] == 0).sum() == 6 and ploidy.max() == 3
+    done, raw = _presence(co)
+    done = done & (ploidy != 0)
+    raw = np.where(done[:, :, None] != 0, raw, 0).astype(np.uint32)
+    f = tmp_path / "mixed.tsv"
+    f.write_text("# SAMPLE CHROM [FROM TO] PLOIDY\n" + "".join("%s\t%s\n" % x for x in PLOIDY_LINES))
+    base = ["--cohort", co.list, "--cohort-ploidy", str(f)]
+    lines = {}
+    for tag, theta in (("qual", 1e-3), ("theta", 0.05)):
+        m = M.run(co.rows.sv_type, raw, done, ploidy, 5e-5, theta)
+        has = ~np.isnan(m["qual"])
+        band = has & (m["half"] < QC.HALF_BAND)                      # the model alone decides what is left out
+        assert has.sum() >= 5 and band.mean() <= QC.CAP
+        assert (m["chroms"][has] != 2 * ((done != 0) & (raw.sum(axis=2) > 0)).sum(axis=1)[has]).any()        # the ploidies are in the answer
+        p, out = _run(tmp_path, tag, *base, "--cohort-qual", *(["--cohort-theta", "0.05"] if tag == "theta" else []), "-v", co.vcf)
+        assert p.returncode == 0, p.stderr
+        a = lines[tag] = _lines(out)
+        data = [ln for ln in a if ln and not ln.startswith("#")]
+        assert len(data) == len(has)
+        for v, ln in enumerate(data):
+            want = _quality_tags("\t" * 7 + genotype.cohort_info(".", 0, 0, qual=(m["qual"][v], m["mlac"][v], m["chroms"][v])))
+            got = _quality_tags(ln)
+            if band[v]:
+                want, got = ([x for x in tags if not x.startswith("SVQ=")] for tags in (want, got))
+            info = ln.split("\t")[7].split(";")
+            assert got == want and info[len(info) - len(got):] == got, (tag, v, got, want)
+        assert sum("SVQ=" in ln for ln in data) == int(has.sum()) and sum("MLAC=" in ln for ln in data) == int((m["chroms"] > 0).sum())
+    q, plain = _run(tmp_path, "plain", *base, "-v", co.vcf)
+    assert q.returncode == 0, q.stderr
+    for tag in lines:
+        assert [_without_quality(x) for x in lines[tag] if not x.startswith("##INFO=<ID=SVQ") and not x.startswith("##INFO=<ID=MLA")] == _lines(plain)
+        assert genotype.COHORT_QUAL_INFO_LINES in "\n".join(lines[tag])
+    assert lines["qual"] != lines["theta"] and p.stdout == q.stdout
+
+
+@pytest.mark.parametrize("prior", [False, True, "ploidy"])
 def test_script(golden, tmp_path, prior):
-    """--cohort LIST --cohort-qual, alone and with --cohort-prior: the file the writer makes from the model's arrays; every sample column and every
-    other INFO tag as in the run without the flag; and that run is byte for byte what it was before the flag existed"""
+    """--cohort LIST --cohort-qual, alone, with --cohort-prior and with --cohort-ploidy FILE: the file the writer makes from the model's arrays;
+    every sample column and every other INFO tag as in the run without the flag; and that run is byte for byte what it was before the flag
+    existed (with the ploidy file: _script_with_a_ploidy_file)"""
     from svjg import genotype
     co = CM.Cohort(golden, "plain")
+    if prior == "ploidy":
+        return _script_with_a_ploidy_file(co, tmp_path)
     done, raw = _presence(co)
     m = M.run(co.rows.sv_type, raw, done, None, 5e-5, 1e-3)
     has = ~np.isnan(m["qual"])
