@@ -380,6 +380,26 @@ int svjg_genotype_cohort_sites(svjg_ctx *ctx, const uint32_t *slots /* [n_sites]
                                uint32_t *raw /* [n_sites][n_samples][7] */, uint8_t *members, uint8_t *boundary,
                                uint32_t *site /* [n_sites][SVJG_MAX_SITE_ALTS][2] = NS_j, AC_j */);
 
+/* svjg_genotype_cohort_sites_prior: svjg_genotype_cohort_sites, and behind it in the same call the samples of a SITE inform each other
+ * (--cohort --joint-ins --joint-prior): the frequencies p_0..p_C of the site's alleles (0 the reference, j candidate j) are estimated by EM under
+ * Hardy-Weinberg over the items that have a site (K' >= 2) and a read, from p_j = 1 / (C + 1), until max_j |p_j' - p_j| <= 1e-9 or 128 steps; each
+ * item is then called at the maximum of likelihood x prior over the genotypes on the reference and ITS OWN members (the model, the fixed-point
+ * caveat for samples with a subset of the candidates, and how the kernel divides the work: svjg_geno.h).  gt, pl, raw, members,
+ * boundary and site are bit for bit what svjg_genotype_cohort_sites returns.  Added: sgt[2] = the posterior call in the item's member numbering (gt's
+ * convention), 0xFF, 0xFF: no call (a tie, below min_support, no site or no read); sgq = min(99, int(-10 log10(sum of the other posteriors))), 0xFF
+ * beside a no-call; af[k*7 + j] = p_j (0 beyond C; all NaN where no item took part); em_steps[k]: the steps taken, bit 31 set: not converged;
+ * psite[k*12 + j*2..] = NS_j, AC_j of the posterior calls.  No atomics: equal bytes from run to run.  A block of its own: it neither reads nor
+ * changes another call's block or views.  Checks and errors as svjg_genotype_cohort_sites (the added arrays must not be null), all before any
+ * launch; 259 bytes per item and 180 per site.  svjg_last_kernel_ms reports both kernels together as genotype_ms.
+ * Measured once, with the change that added it (one MI355X, 2026-10-21, ROCm 7.2.0, tools/cohort_sites_prior_timing.py: 10 000 sites, K mixed 2..6,
+ * presence 0.9, counts 0..60, e = 5e-5, median of 30 calls behind 5, the legs alternated twice in one process): 0.614 / 0.615 ms for both kernels at 64
+ * samples against 0.129 / 0.128 ms of svjg_genotype_cohort_sites alone (6.49 steps a site, at most 13), 2.560 / 2.559 against 0.540 / 0.540 ms at 256
+ * (6.06 steps, at most 9).  Nothing else about this kernel has been measured. */
+int svjg_genotype_cohort_sites_prior(svjg_ctx *ctx, const uint32_t *slots /* [n_sites][SVJG_MAX_SITE_ALTS] */, uint64_t n_sites, uint32_t min_support,
+                                     double err, uint8_t *gt, int64_t *pl, uint32_t *raw, uint8_t *members, uint8_t *boundary, uint32_t *site,
+                                     uint8_t *sgt /* [n_sites][n_samples][2] */, uint8_t *sgq /* [n_sites][n_samples] */, double *af /* [n_sites][7] */,
+                                     uint32_t *em_steps /* [n_sites] */, uint32_t *psite /* [n_sites][SVJG_MAX_SITE_ALTS][2] */);
+
 /* svjg_cohort_qual: the site quality of every row of a cohort (--cohort-qual): how sure are we that at least one alt copy exists in the cohort.
  *   The exact allele-count posterior (the "exact model" of Li 2011): the samples' genotype likelihoods folded in one by one into y_k, the
  *   likelihood of k alt copies among the M chromosomes folded in so far, in its normalised form, rescaled by exact powers of two;

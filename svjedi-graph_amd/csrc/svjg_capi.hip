@@ -82,7 +82,7 @@ constexpr uint64_t STAGE_PIECE = 8ull << 20;
 // hands out pointers into BLOCK_ROWS' twin and svjg_genotype_boundary reads it later, and both must survive calls of the other six.
 // A fused pass's slot holds the same pair (RunSlot).
 struct LegBlock { DevBuf<uint8_t> d;  PinBuf h; };
-enum { BLOCK_ROWS, BLOCK_PLOIDY, BLOCK_SITES, BLOCK_COHORT, BLOCK_COHORT_PLOIDY, BLOCK_COHORT_PRIOR, BLOCK_COHORT_SITES, BLOCK_COHORT_QUAL, LEG_BLOCKS };   // rows_layout, ploidy_layout, sites_layout, cohort_layout for the three cohort blocks, sites_layout again, qual_layout (svjg_geno.h)
+enum { BLOCK_ROWS, BLOCK_PLOIDY, BLOCK_SITES, BLOCK_COHORT, BLOCK_COHORT_PLOIDY, BLOCK_COHORT_PRIOR, BLOCK_COHORT_SITES, BLOCK_COHORT_QUAL, BLOCK_COHORT_SITES_PRIOR, LEG_BLOCKS };   // rows_layout, ploidy_layout, sites_layout, cohort_layout for the three cohort blocks, sites_layout again, qual_layout, sites_layout with its prior switch (svjg_geno.h)
 
 // slots the passes of svjg_run_begin rotate through: two may be in flight, and the one the NEXT pass will use is zeroed while the newest computes
 constexpr int RUN_SLOTS = 3;
@@ -1138,7 +1138,8 @@ extern "C" int svjg_genotype_ploidy(svjg_ctx *c, const uint8_t *sv_type, const u
 
 // Insertions that share a position, genotyped together (svjg.h), through genotype_leg by ONE leg, sites_call: svjg_genotype_sites in BLOCK_SITES
 // (k_genotype_sites on the count vector) and svjg_genotype_cohort_sites in BLOCK_COHORT_SITES (k_genotype_cohort_sites on the cohort matrix; it reads
-// nothing else of the context).  launch_sites: all items with the table at hand.  The cohort's site words lie right in front of the max_n pair
+// nothing else of the context), and svjg_genotype_cohort_sites_prior in BLOCK_COHORT_SITES_PRIOR (the same kernel with k_cohort_sites_prior enqueued
+// behind it: launch_sites_prior).  launch_sites: all items with the table at hand.  The cohort's site words lie right in front of the max_n pair
 // (sites_layout): ONE memset zeroes both in front of EVERY launch, as launch_cohort's.  Blocks: capped_grid(n_sites) for the single-sample kernel;
 // the cohort kernel takes 104 VGPRs (the compiler's resource remark), so a SIMD holds 512 / 104 = four of its waves and a unit four
 // blocks of four waves; the rest in strides of the grid.
@@ -1154,6 +1155,16 @@ static int launch_sites(svjg_ctx *c, GenoCohortSitesArgs &p, bool cohort) {
         HIPCHK(c, hipMemsetAsync(a.max_n, 0, 8, c->stream));
         hipLaunchKernelGGL(k_genotype_sites, dim3(capped_grid(a.n_sites)), dim3(TPB), 0, c->stream, a);
     }
+    HIPCHK(c, hipGetLastError());
+    return 0;
+}
+
+// k_cohort_sites_prior on what the cohort sites kernel left in the block.  Blocks of SITES_PRIOR_TPB = two waves, a wave holds 64 / width sites
+// (prior_segment_width); a block's 57 472 bytes of LDS let two blocks share a unit's 160 KiB; the rest in strides of the grid.
+static int launch_sites_prior(svjg_ctx *c, CohortSitesPriorArgs &p) {
+    const uint64_t per_wave = 64u / prior_segment_width(p.n_samples), waves = (p.n_sites + per_wave - 1) / per_wave;
+    const uint64_t blocks = (waves * 64 + SITES_PRIOR_TPB - 1) / SITES_PRIOR_TPB, cap = (uint64_t)c->n_cu * 2;
+    hipLaunchKernelGGL(k_cohort_sites_prior, dim3((uint32_t)(blocks < cap ? blocks : cap)), dim3(SITES_PRIOR_TPB), 0, c->stream, p);
     HIPCHK(c, hipGetLastError());
     return 0;
 }
@@ -1177,19 +1188,20 @@ static int check_sites(svjg_ctx *c, const uint32_t *slots, uint64_t n_sites, uin
 
 // The host leg of both: the checks of the call's kind (all of them before any launch), the call's logarithms by the host's libm and the sites' slots in, the kernel of the call's kind, the copy out.  members, site: the cohort's only.
 static int sites_call(svjg_ctx *c, int block, const uint32_t *slots, uint64_t n_sites, uint32_t min_support, double err,
-                      uint8_t *gt, int64_t *pl, uint32_t *raw, uint8_t *members, uint8_t *boundary, uint32_t *site) {
+                      uint8_t *gt, int64_t *pl, uint32_t *raw, uint8_t *members, uint8_t *boundary, uint32_t *site,
+                      uint8_t *sgt = nullptr, uint8_t *sgq = nullptr, double *af = nullptr, uint32_t *em_steps = nullptr, uint32_t *psite = nullptr) {
     static_assert(SVJG_MAX_SITE_ALTS == MAX_SITE_ALTS && SVJG_SITE_GENOTYPES == SITE_GENOTYPES, "svjg.h and svjg_geno.h disagree");
-    const bool cohort = block == BLOCK_COHORT_SITES;
+    const bool prior = block == BLOCK_COHORT_SITES_PRIOR, cohort = prior || block == BLOCK_COHORT_SITES;   // (prior: k_cohort_sites_prior behind the cohort kernel, in a block of its own)
     if (!c || (!cohort && !c->have_counts)) return SVJG_E_ARG;
     if (cohort && !c->d_cm) { c->err = "no cohort matrix"; return SVJG_E_ARG; }
     if (n_sites == 0) return 0;
-    if (!slots || !gt || !pl || !raw || !boundary || (cohort && (!members || !site))) { if (cohort) c->err = "a null array"; return SVJG_E_ARG; }
+    if (!slots || !gt || !pl || !raw || !boundary || (cohort && (!members || !site)) || (prior && (!sgt || !sgq || !af || !em_steps || !psite))) { if (cohort) c->err = "a null array"; return SVJG_E_ARG; }
     const uint64_t S = cohort ? c->cohort_samples : 1;
     if (cohort && n_sites > (1ull << 40) / S) { c->err = "too many items for one call: genotype the sites in chunks"; return SVJG_E_ARG; }
     if (const int rc0 = check_sites(c, slots, n_sites, cohort ? c->cohort_slots : c->n_slots)) return rc0;
     HIPCHK(c, hipSetDevice(c->device));
     if (!cohort) { const int rc0 = fetch_slot_counts(c); if (rc0) return rc0; }
-    const SitesLayout L = sites_layout(n_sites, S, cohort);
+    const SitesLayout L = sites_layout(n_sites, S, cohort, prior);
     const int rc = genotype_leg(c, c->leg[block], L,
         [&](uint8_t *hb) { site_log_table(err, (double *)(hb + L.logs)); memcpy(hb + L.slots, slots, n_sites * MAX_SITE_ALTS * 4); },
         [&](uint8_t *base) {
@@ -1200,7 +1212,11 @@ static int sites_call(svjg_ctx *c, int block, const uint32_t *slots, uint64_t n_
             a.pl = (int64_t *)(base + L.pl); a.raw = (uint32_t *)(base + L.raw); a.gt = base + L.gt; a.boundary = base + L.boundary;
             a.max_n = (unsigned int *)(base + L.maxn);
             p.present = c->d_cpresent; p.n_samples = (uint32_t)S; p.members = base + L.members; p.site = (unsigned long long *)(base + L.site);
-            return launch_sites(c, p, cohort);
+            if (const int rc1 = launch_sites(c, p, cohort)) return rc1;
+            if (!prior) return 0;
+            CohortSitesPriorArgs q{a.raw, p.members, a.slots, a.logs, n_sites, (uint32_t)S, min_support,
+                                   base + L.sgt, base + L.sgq, (double *)(base + L.af), (uint32_t *)(base + L.steps), (uint32_t *)(base + L.psite)};
+            return launch_sites_prior(c, q);
         });
     if (rc) return rc;
     const uint8_t *hb = c->leg[block].h;
@@ -1208,6 +1224,10 @@ static int sites_call(svjg_ctx *c, int block, const uint32_t *slots, uint64_t n_
     memcpy(pl, hb + L.pl, n * SITE_GENOTYPES * sizeof *pl); memcpy(raw, hb + L.raw, n * (MAX_SITE_ALTS + 1) * sizeof *raw);
     memcpy(gt, hb + L.gt, n * 2); memcpy(boundary, hb + L.boundary, n);
     if (cohort) { memcpy(members, hb + L.members, n); memcpy(site, hb + L.site, n_sites * MAX_SITE_ALTS * 8); }   // (NS_j, AC_j: the two halves of the kernel's one word a candidate)
+    if (prior) {
+        memcpy(sgt, hb + L.sgt, n * 2); memcpy(sgq, hb + L.sgq, n); memcpy(af, hb + L.af, n_sites * SITE_ALLELES * sizeof *af);
+        memcpy(em_steps, hb + L.steps, n_sites * sizeof *em_steps); memcpy(psite, hb + L.psite, n_sites * MAX_SITE_ALTS * 2 * sizeof *psite);
+    }
     return 0;
 }
 
@@ -1219,6 +1239,12 @@ extern "C" int svjg_genotype_sites(svjg_ctx *c, const uint32_t *slots, uint64_t 
 extern "C" int svjg_genotype_cohort_sites(svjg_ctx *c, const uint32_t *slots, uint64_t n_sites, uint32_t min_support, double err,
                                           uint8_t *gt, int64_t *pl, uint32_t *raw, uint8_t *members, uint8_t *boundary, uint32_t *site) {
     return sites_call(c, BLOCK_COHORT_SITES, slots, n_sites, min_support, err, gt, pl, raw, members, boundary, site);
+}
+
+extern "C" int svjg_genotype_cohort_sites_prior(svjg_ctx *c, const uint32_t *slots, uint64_t n_sites, uint32_t min_support, double err,
+                                                uint8_t *gt, int64_t *pl, uint32_t *raw, uint8_t *members, uint8_t *boundary, uint32_t *site,
+                                                uint8_t *sgt, uint8_t *sgq, double *af, uint32_t *em_steps, uint32_t *psite) {
+    return sites_call(c, BLOCK_COHORT_SITES_PRIOR, slots, n_sites, min_support, err, gt, pl, raw, members, boundary, site, sgt, sgq, af, em_steps, psite);
 }
 
 // ---- cohort: many samples' counts against one row set (svjg.h) -------------------------------------------------------------

@@ -285,6 +285,18 @@ inline void site_log_table(double err, double *tab) {
     }
 }
 
+// lik_ab of a site as every caller compares it (geno_site, and site_prior_load below): the exact sum of the two ROUNDED products.  c: the site's
+// normalised counts, indexed by the caller's unrolled constants, N their sum.  (its own pragma: the caller's does not reach into an inlined callee)
+SVJG_HD dd site_lik(const double *c, double N, uint32_t a, uint32_t b, double l_ok, double l_x, double l_he) {
+#ifdef __clang__
+#pragma clang fp contract(off)                           // the products are rounded to doubles before the exact sum
+#endif
+    const double own = a == b ? c[a] : c[a] + c[b];
+    const double rest = a == b ? N - c[a] : N - c[a] - c[b];
+    const double p1 = own * (a == b ? l_ok : l_he), p2 = rest * l_x;
+    return two_sum(p1, p2);
+}
+
 struct GenoSite {
     uint8_t a, b;    // the call, a <= b; SITE_NO_CALL, SITE_NO_CALL: a tie or below min_support
     bool near;       // one of the site's values lies within SITE_PL_GUARD of an integer, or the site is beyond the table's cap: the host recomputes it
@@ -339,10 +351,7 @@ SVJG_HD uint32_t geno_site(uint32_t K, uint32_t ref, const uint32_t *alt, uint32
         for (uint32_t a = 0; a <= b; ++a) {
             const uint32_t at = b * (b + 1) / 2 + a;
             if (b > K) { pl[at] = 0; continue; }
-            const double own = a == b ? c[a] : c[a] + c[b];
-            const double rest = a == b ? N - c[a] : N - c[a] - c[b];
-            const double p1 = own * (a == b ? l_ok : l_he), p2 = rest * l_x;
-            const dd l = two_sum(p1, p2);
+            const dd l = site_lik(c, N, a, b, l_ok, l_x, l_he);
             const int cmp = at ? dd_cmp(l, best) : 1;
             if (cmp > 0) { best = l; best_a = (uint8_t)a; best_b = (uint8_t)b; tie = false; } else if (cmp == 0) tie = true;
             bool inside;
@@ -663,6 +672,199 @@ SVJG_HD uint32_t prior_segment_width(uint64_t S) {
     return w;
 }
 
+// ---- cohort sites with an allele-frequency prior (k_cohort_sites_prior behind k_genotype_cohort_sites) ----
+// The samples of a SITE inform each other: the frequencies p = (p_0..p_C) of the site's alleles are estimated by EM under Hardy-Weinberg, each item
+// is then called at the maximum of likelihood x prior.  Alleles: a site has C = 2..MAX_SITE_ALTS candidates (its named slots); allele 0 is the
+// reference, allele j candidate j, the same numbering for every sample of the site.  An item (k, s) takes part iff the first kernel gave it a site
+// (K' >= 2 members present: `members` and the raw counts as site_item left them) and it has a read, N = sum c_j > 0; support gates calls, not
+// likelihoods.  Weights: l_AB = site_lik on the item's own members with its own K' (logs[K'], logs[8 + K']) — with the counts expanded to
+// candidate order (0 for an absent candidate) these are bit for bit the values geno_site compares in member numbering —, d_AB = l_AB - max l
+// subtracted in double-double and collapsed to one double, w_AB = 10^d_AB (the chain term T is the same for every genotype and cancels).  The
+// item keeps its SITE_GENOTYPES weights in CANDIDATE order, slot B (B + 1) / 2 + A for A <= B over 0..6; a genotype that names a candidate absent
+// for this sample, or one beyond C, has weight 0: K' does not occur behind site_prior_load.  Prior pi_AB(p) = p_A^2 (A = B), 2 p_A p_B (A < B);
+// t_AB = pi_AB w_AB, z = sum t, posterior q_AB = t_AB / z over the genotypes on {0} + the sample's members, one-hot at the item's first largest w
+// where z is 0.  Expected copies x_j = (sum_AB copies_j(A, B) t_AB) / z for j = 0..C, numerator and z summed in increasing slot order.  Step:
+// p_j <- sum_s x_(s,j) / (2 n), n the number of items taking part (an integer, reduced once); start p_j = 1 / (C + 1); the site stops after the
+// first step with max_j |p_j' - p_j| <= EM_TOL or after EM_MAX_IT steps (bit 31 of the step word: not converged, as prior_step); n = 0: all p NaN,
+// 0 steps.  p_j beyond C is 0 wherever there is an estimate.  Calls under the final p: argmax q, an exact tie or N < min_support is a no-call;
+// SGQ = min(99, int(-10 log10(sum of the other q, in increasing slot order))), 99 where that sum is 0.
+// This is a stated fixed-point iteration: a sample with a proper subset of the candidates conditions on that subset.  It is not claimed to be the
+// maximum-likelihood estimate of a model in which an absent candidate counts as zero alt reads.
+// Compiled without fused multiply-adds, so the host harness (tests/site_prior_sim) and the kernel differ in exp10 and log10 only.
+constexpr uint32_t SITE_ALLELES = MAX_SITE_ALTS + 1;    // 7: the reference and the candidates
+// max_j |p_j(device) - p_j(model)|, the model being tests/site_prior_model.py at 60 digits, is measured, not assumed (2026-10-21, one MI355X, ROCm
+// 7.2.0, tests/test_cohort_site_prior_gpu.py: 46 cases of 200 sites (one of 77) x 1..130 samples, the 37 of them with an estimate): at most
+// 2.322e-16 absolute (rare_3: one carrier among 3 samples) and 8.230e-16 relative among the p_j > 1e-6 (mixed_3_odd).  The host harness in the
+// kernel's order of the sums, glibc's pow and log10 in place of the device's exp10 and log10, measures the same two figures in the same two cases
+// (tests/test_cohort_site_prior.py): the constant is the DEVICE reading, which the CPU tests assert as well.
+// The tests assert 8 x the absolute maximum: the margin is for other seeds, not for other arithmetic.
+constexpr double SITE_EM_P_BOUND = 8 * 2.322e-16;
+
+// what an item keeps beside its weights: members (bit j = candidate j present), top = the slot of its first largest w, N, and whether it takes part
+struct SitePriorMeta { uint32_t members, top; double N; bool part; };
+
+SVJG_HD bool site_prior_valid(uint32_t members, uint32_t A, uint32_t B) {
+    return (A == 0 || ((members >> (A - 1)) & 1u)) && (B == 0 || ((members >> (B - 1)) & 1u));
+}
+
+// One item from what the first kernel left: raw[1 + MAX_SITE_ALTS] = the ref maximum and the MEMBERS' alt counts (compacted), members.  The counts
+// are expanded to candidate order ONCE, by unrolled selects under constant indices (site_compact's reverse); the weights go to w[slot * stride]
+// (the kernel: slot-major in LDS, stride = the block's lanes; the harness: stride 1).  An item that takes no part: zeros.
+SVJG_HD void site_prior_load(const uint32_t *raw, uint32_t members, const double *logs, double *w, uint32_t stride, SitePriorMeta &m) {
+#ifdef __clang__
+#pragma clang fp contract(off)
+#endif
+    uint32_t v[SITE_ALLELES];
+    SVJG_UNROLL
+    for (uint32_t t = 0; t < SITE_ALLELES; ++t) v[t] = raw[t];
+    members &= (1u << MAX_SITE_ALTS) - 1u;
+    const uint32_t K = (uint32_t)__builtin_popcount(members);
+    double c[SITE_ALLELES];
+    c[0] = (double)v[0];
+    double N = c[0];
+    SVJG_UNROLL
+    for (uint32_t j = 0; j < MAX_SITE_ALTS; ++j) {
+        const bool in = (members >> j) & 1u;
+        const uint32_t at = (uint32_t)__builtin_popcount(members & ((1u << j) - 1u));       // the members in front of candidate j: its place in raw
+        uint32_t a = 0;
+        SVJG_UNROLL
+        for (uint32_t t = 0; t <= j; ++t) a = in && t == at ? v[1 + t] : a;
+        c[1 + j] = (double)a * 0.5;                      // the INS normalisation, exact for halves (0 stays 0)
+        N += c[1 + j];                                   // (halves below 2^36: exact in any order)
+    }
+    m.members = members; m.top = 0; m.N = N; m.part = K >= 2 && N > 0.0;
+    const uint32_t Kc = K < 2 ? 2u : K;                  // (an item that takes no part reads two logarithms it does not use)
+    const double l_ok = logs[0], l_x = logs[Kc], l_he = logs[8 + Kc];
+    dd best{0.0, 0.0};
+    SVJG_UNROLL
+    for (uint32_t B = 0; B <= MAX_SITE_ALTS; ++B) {
+        SVJG_UNROLL
+        for (uint32_t A = 0; A <= B; ++A) {
+            const uint32_t at = B * (B + 1) / 2 + A;
+            const dd l = site_lik(c, N, A, B, l_ok, l_x, l_he);
+            if (site_prior_valid(members, A, B) && (at == 0 || dd_cmp(l, best) > 0)) { best = l; m.top = at; }
+        }
+    }
+    SVJG_UNROLL
+    for (uint32_t B = 0; B <= MAX_SITE_ALTS; ++B) {
+        SVJG_UNROLL
+        for (uint32_t A = 0; A <= B; ++A) {
+            const uint32_t at = B * (B + 1) / 2 + A;
+            const dd d = dd_add(site_lik(c, N, A, B, l_ok, l_x, l_he), dd_neg(best));
+            w[at * stride] = m.part && site_prior_valid(members, A, B) ? prior_exp10(d.hi + d.lo) : 0.0;
+        }
+    }
+}
+
+// t_AB = pi_AB(p) w_AB of one slot (A, B: the callers' unrolled constants)
+SVJG_HD double site_prior_term(const double *w, uint32_t stride, const double *p, uint32_t A, uint32_t B) {
+#ifdef __clang__
+#pragma clang fp contract(off)
+#endif
+    const double pi = A == B ? p[A] * p[A] : (2.0 * p[A]) * p[B];
+    return pi * w[(B * (B + 1) / 2 + A) * stride];
+}
+
+// x[j] += the item's expected copies of allele j under p, j = 0..6 (nothing for an item that takes no part)
+SVJG_HD void site_prior_expected(const double *w, uint32_t stride, const SitePriorMeta &m, const double *p, double *x) {
+#ifdef __clang__
+#pragma clang fp contract(off)
+#endif
+    double z = 0.0, u[SITE_ALLELES];
+    SVJG_UNROLL
+    for (uint32_t j = 0; j < SITE_ALLELES; ++j) u[j] = 0.0;
+    SVJG_UNROLL
+    for (uint32_t B = 0; B <= MAX_SITE_ALTS; ++B) {
+        SVJG_UNROLL
+        for (uint32_t A = 0; A <= B; ++A) {
+            const double t = site_prior_term(w, stride, p, A, B);
+            z += t;
+            if (A == B) u[A] += 2.0 * t; else { u[A] += t; u[B] += t; }
+        }
+    }
+    if (!m.part) return;
+    SVJG_UNROLL
+    for (uint32_t B = 0; B <= MAX_SITE_ALTS; ++B) {
+        SVJG_UNROLL
+        for (uint32_t A = 0; A <= B; ++A) {
+            const uint32_t at = B * (B + 1) / 2 + A;
+            if (!(z > 0.0) && at == m.top) { u[A] = u[A] + 1.0; u[B] = u[B] + 1.0; }     // one-hot at the first largest w (every u is 0 here)
+        }
+    }
+    SVJG_UNROLL
+    for (uint32_t j = 0; j < SITE_ALLELES; ++j) x[j] += z > 0.0 ? u[j] / z : u[j];
+}
+
+// The call of one item under the site's final p, in the ITEM's member numbering (gt's convention: project_cohort_sites serves both): a <= b, 0 the
+// reference, t the t-th present candidate; SITE_NO_CALL twice and gq = 0xFF: a tie at the maximum, below min_support, or the item takes no part.
+struct SitePriorCall { uint8_t a, b, gq; };
+SVJG_HD SitePriorCall site_prior_call(const double *w, uint32_t stride, const SitePriorMeta &m, const double *p, uint32_t min_support) {
+#ifdef __clang__
+#pragma clang fp contract(off)
+#endif
+    double z = 0.0, top = 0.0; uint32_t best = 0; bool tie = false;
+    SVJG_UNROLL
+    for (uint32_t B = 0; B <= MAX_SITE_ALTS; ++B) {
+        SVJG_UNROLL
+        for (uint32_t A = 0; A <= B; ++A) {
+            const uint32_t at = B * (B + 1) / 2 + A;
+            const double t = site_prior_term(w, stride, p, A, B);
+            z += t;
+            if (at == 0 || t > top) { top = t; best = at; tie = false; } else if (t == top) tie = true;
+        }
+    }
+    if (!m.part) return SitePriorCall{SITE_NO_CALL, SITE_NO_CALL, 0xFF};
+    if (!(z > 0.0)) { best = m.top; tie = false; }
+    double rest = 0.0; uint32_t bA = 0, bB = 0;
+    SVJG_UNROLL
+    for (uint32_t B = 0; B <= MAX_SITE_ALTS; ++B) {
+        SVJG_UNROLL
+        for (uint32_t A = 0; A <= B; ++A) {
+            const uint32_t at = B * (B + 1) / 2 + A;
+            if (at != best) rest += site_prior_term(w, stride, p, A, B); else { bA = A; bB = B; }     // (formed again, the same bits: 28 terms are not kept in registers)
+        }
+    }
+    rest = z > 0.0 ? rest / z : 0.0;
+    if (tie || !(m.N >= (double)min_support)) return SitePriorCall{SITE_NO_CALL, SITE_NO_CALL, 0xFF};
+    double v = rest > 0.0 ? -10.0 * log10(rest) : 99.0;
+    if (!(v < 99.0)) v = 99.0;
+    const uint32_t a = bA ? 1u + (uint32_t)__builtin_popcount(m.members & ((1u << (bA - 1)) - 1u)) : 0u;
+    const uint32_t b = bB ? 1u + (uint32_t)__builtin_popcount(m.members & ((1u << (bB - 1)) - 1u)) : 0u;
+    return SitePriorCall{(uint8_t)a, (uint8_t)b, (uint8_t)(v > 0.0 ? (uint32_t)v : 0u)};
+}
+
+// A site across its EM steps.  C: its candidates (the named slots of its MAX_SITE_ALTS), n: its items that take part.
+struct SitePriorSite { double p[SITE_ALLELES]; uint32_t steps; bool done; };
+SVJG_HD uint32_t site_candidates(const uint32_t *slots) {
+    uint32_t C = 0;
+    SVJG_UNROLL
+    for (uint32_t j = 0; j < MAX_SITE_ALTS; ++j) C += slots[j] != SITE_NO_SLOT;
+    return C;
+}
+SVJG_HD SitePriorSite site_prior_start(uint32_t C, uint32_t n) {
+    SitePriorSite s;
+    const double p0 = 1.0 / (double)(C + 1u);
+    SVJG_UNROLL
+    for (uint32_t j = 0; j < SITE_ALLELES; ++j) s.p[j] = n ? (j <= C ? p0 : 0.0) : NAN;
+    s.steps = 0; s.done = n == 0;
+    return s;
+}
+// one step's outcome: the sums x[0..6] over the site's items against the p they were computed under
+SVJG_HD void site_prior_step(SitePriorSite &s, const double *x, uint32_t n) {
+    if (s.done) return;                                  // a stopped site keeps its p while its wave goes on
+    const double den = 2.0 * (double)n;
+    double far = 0.0;
+    SVJG_UNROLL
+    for (uint32_t j = 0; j < SITE_ALLELES; ++j) {
+        const double pn = x[j] / den, d = fabs(pn - s.p[j]);
+        far = d > far ? d : far;
+        s.p[j] = pn;
+    }
+    ++s.steps;
+    if (far <= EM_TOL) s.done = true;
+    else if (s.steps == EM_MAX_IT) { s.done = true; s.steps |= EM_NOT_CONVERGED; }
+}
+
 // ---- cohort site quality: the exact allele-count posterior (k_cohort_qual) ----
 // "Is there at least one alt copy in this cohort": the exact model of Li 2011 (the QUAL of samtools / bcftools), at any ploidy.  An item (r, s)
 // takes part under the rule of the EM above: cohort_gate passes (ok & 1, a slot, presence), its ploidy P is in 1..max_ploidy (2 everywhere
@@ -878,14 +1080,19 @@ inline PloidyLayout ploidy_layout(uint64_t n) {
 // svjg_genotype_sites (S = 1, not cohort): [ pl 224 | raw 28 | gt 2 | boundary 1 ] x n_sites.  svjg_genotype_cohort_sites (cohort): [ pl 224 | raw 28 |
 // gt 2 | members 1 | boundary 1 ] x (n_sites * S items, site-major: 256 bytes an item), then the site words, 8-aligned, as the LAST output:
 // MAX_SITE_ALTS words a site, NS_j | AC_j << 32; the max_n pair lies right behind them, and ONE memset zeroes both in front of every launch (as
-// cohort_layout).  in, both: the call's logarithms (site_log_table) and the sites' slots.  A field the call does not have is 0.
-struct SitesLayout : LegSpan { uint64_t pl, raw, gt, members, boundary, site, logs, slots; };
-inline SitesLayout sites_layout(uint64_t n_sites, uint64_t S = 1, bool cohort = false) {
+// cohort_layout).  svjg_genotype_cohort_sites_prior (cohort and prior): k_cohort_sites_prior's own outputs [ sgt 2 | sgq 1 ] x items behind the
+// boundary bytes and, 8-aligned, [ af 56 | psite 48 (NS_j, AC_j) | steps 4 ] x sites in front of the first kernel's site words, which stay the
+// LAST output.  in, all: the call's logarithms (site_log_table) and the sites' slots.  A field the call does not have is 0.
+struct SitesLayout : LegSpan { uint64_t pl, raw, gt, members, boundary, site, logs, slots, sgt, sgq, af, psite, steps; };
+inline SitesLayout sites_layout(uint64_t n_sites, uint64_t S = 1, bool cohort = false, bool prior = false) {
     SitesLayout L{}; uint64_t o = 0; const uint64_t n = n_sites * S;
     L.pl = o; o += n * 8 * SITE_GENOTYPES; L.raw = o; o += n * 4 * (MAX_SITE_ALTS + 1); L.gt = o; o += n * 2;
     if (cohort) { L.members = o; o += n; }
     L.boundary = o; o += n;
-    if (cohort) { o = (o + 7) & ~7ull; L.site = o; o += n_sites * 8 * MAX_SITE_ALTS; }
+    if (cohort && prior) { L.sgt = o; o += n * 2; L.sgq = o; o += n; }
+    if (cohort) o = (o + 7) & ~7ull;
+    if (cohort && prior) { L.af = o; o += n_sites * 8 * SITE_ALLELES; L.psite = o; o += n_sites * 8 * MAX_SITE_ALTS; L.steps = o; o += n_sites * 4; o = (o + 7) & ~7ull; }
+    if (cohort) { L.site = o; o += n_sites * 8 * MAX_SITE_ALTS; }
     leg_span(L, o, SITE_LOGS * 8 + n_sites * 4 * MAX_SITE_ALTS);
     L.logs = L.in_at; L.slots = L.logs + SITE_LOGS * 8;
     return L;

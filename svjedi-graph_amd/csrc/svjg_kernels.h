@@ -15,6 +15,7 @@
 //   k_genotype_cohort one (row, sample) item per lane over a slot-major count matrix, k_genotype's arithmetic; NS / AC per row by wave ballots
 //   k_genotype_cohort_ploidy  the same division of work at a ploidy per item, k_genotype_ploidy's arithmetic; NS / AN / AC per row by wave ballots
 //   k_genotype_cohort_sites   one (site, sample) item per lane: the candidates present for the sample, k_genotype_sites' arithmetic; NS / AC per candidate by wave ballots
+//   k_cohort_sites_prior      behind k_genotype_cohort_sites: a site per wave segment, its allele frequencies by EM over its samples, posterior site call and SGQ per item
 //   k_cohort_prior    behind either cohort kernel: a row per wave segment, its allele frequency by EM over its samples, posterior GT and GQ per item
 //   k_cohort_qual     a row per wave over the cohort matrix: the exact allele-count posterior folded in sample by sample in LDS, site quality and MLAC per row
 //   k_cohort_store / k_cohort_load  one sample's column of that matrix from / to a dense count vector
@@ -2476,6 +2477,104 @@ __global__ __launch_bounds__(TPB) void k_genotype_cohort_sites(GenoCohortSitesAr
             const CohortSums t = cohort_site_member_sums(b, j, seg.mask);
             if (t.ns) atomicAdd(p.site + k * MAX_SITE_ALTS + j, (unsigned long long)cohort_site_word(t));
         }
+    }
+  }
+}
+
+// ---- cohort sites with an allele-frequency prior (svjg_genotype_cohort_sites_prior; the model: svjg_geno.h) ----
+// Enqueued behind k_genotype_cohort_sites on the same stream: it reads what that kernel left in the call's block (raw, members) and the call's
+// inputs (the sites' slots, for C; the logarithms), and writes only its own outputs: sgt, sgq per item, p[7], the step word and NS_j / AC_j of the
+// posterior calls per site.  Everything is written, nothing added to: a second launch behind a grown table rewrites it.
+struct CohortSitesPriorArgs {
+    const uint32_t *raw; const uint8_t *members; const uint32_t *slots;
+    const double *logs;                // site_log_table of the call's err
+    uint64_t n_sites; uint32_t n_samples, min_support;
+    uint8_t *sgt, *sgq; double *af; uint32_t *steps, *psite;
+};
+constexpr uint32_t SITES_PRIOR_TPB = 128;                                      // two planes of 28 weights a lane: 2 x 28 x 128 x 8 = 57 344 bytes of LDS
+
+// The division of the work is k_cohort_prior's: a site takes a segment of W = prior_segment_width(S) lanes, 64 / W sites share a wave, a site never
+// spans two waves; lane j of a segment holds sample j and, for S > 64, strides over j + 64, j + 128, ...; lanes at or beyond S idle.  The loop's
+// bound is the WAVE's first site and every shuffle and ballot is executed by all 64 lanes on every trip: stopped sites, sites without an item and
+// lanes beyond the last site (n = 0: done from the start) alike.  n is reduced once, in integers; the seven sums of a step go through the xor
+// butterfly (prior_segment_sum), so every lane of the segment holds the same bits; NS_j / AC_j are butterfly sums of integers — no atomics, equal
+// bytes from run to run.  The 28 weights of a lane's FIRST item live in LDS across the steps, slot-major across the block's lanes
+// (w[slot * 128 + lane of the block]: neighbouring lanes read neighbouring 8-byte words, a ds_read_b64 of 32 lanes covers the 64 banks once), indexed
+// by constants only; a lane reads only what it wrote itself: no barrier.  A lane's further items (S > 64) are recomputed at every step into the
+// second plane (28 exp10 each).  Not staged, by a measurement (2026-10-21, one MI355X, ROCm 7.2.0, tools/cohort_sites_prior_timing.py, 10 000 sites, 6.5
+// and 6.1 steps a site, both kernels of the call, median of 30 calls behind 5, alternated twice, measured once): 0.614 / 0.615 ms at 64 samples (the
+// first kernel alone 0.129 / 0.128: the second adds 0.486) and 2.560 / 2.559 ms at 256 (0.540 / 0.540: it adds 2.020) — four times the items in 4.15
+// times the time, although three of a lane's four items are built again at every step: what staging them could save is the 0.08 ms above 4 x 0.486.
+// Compile remarks (ROCm 7.2.0, gfx950): 256 VGPRs and 66 AGPRs (the allocator's overflow registers), 106 SGPRs (68 of them spilled to VGPR lanes), 0 bytes
+// of scratch, 1 wave a SIMD, 57 472 bytes of LDS a block (2 planes x 28 x 128 x 8 and the 128 of the logarithms): two blocks a unit.  No register array
+// is indexed by a variable: w lives in LDS under constant offsets, p, x, ns and ac are unrolled.
+__global__ __launch_bounds__(SITES_PRIOR_TPB) void k_cohort_sites_prior(CohortSitesPriorArgs p) {
+  __shared__ double logs[SITE_LOGS];
+  __shared__ double planes[2 * SITE_GENOTYPES * SITES_PRIOR_TPB];
+  stage_site_logs(logs, p.logs);
+  double *w0 = planes + threadIdx.x, *w1 = planes + SITE_GENOTYPES * SITES_PRIOR_TPB + threadIdx.x;
+  const uint64_t S = p.n_samples;
+  const uint32_t lane = threadIdx.x & 63u, W = prior_segment_width(S), per_wave = 64u / W, j = lane & (W - 1), sub = lane / W;
+  const uint64_t n_waves = (p.n_sites + per_wave - 1) / per_wave;
+  for (uint64_t wv = ((uint64_t)blockIdx.x * blockDim.x + threadIdx.x) >> 6; wv < n_waves; wv += ((uint64_t)gridDim.x * blockDim.x) >> 6) {
+    const uint64_t k = wv * per_wave + sub;
+    const bool mine = k < p.n_sites && j < S;                                  // the lane holds items of a site
+    SitePriorMeta m0{0u, 0u, 0.0, false};
+    uint32_t n = 0, C = 0;
+    if (k < p.n_sites) C = site_candidates(p.slots + k * MAX_SITE_ALTS);     // (every lane of the segment, idle ones too: the site's state is the same in all of them)
+    if (mine) {
+        const uint64_t i = k * S + j;
+        site_prior_load(p.raw + i * SITE_ALLELES, p.members[i], logs, w0, SITES_PRIOR_TPB, m0);
+        n = m0.part;
+        for (uint64_t s = (uint64_t)j + 64; s < S; s += 64) {
+            SitePriorMeta o;
+            site_prior_load(p.raw + (k * S + s) * SITE_ALLELES, p.members[k * S + s], logs, w1, SITES_PRIOR_TPB, o);
+            n += o.part;
+        }
+    }
+    n = prior_segment_sum(n, W);
+    SitePriorSite st = site_prior_start(C, n);
+    while (__ballot(!st.done)) {
+        double x[SITE_ALLELES];
+#pragma unroll
+        for (uint32_t a = 0; a < SITE_ALLELES; ++a) x[a] = 0.0;
+        if (mine && !st.done) {
+            site_prior_expected(w0, SITES_PRIOR_TPB, m0, st.p, x);
+            for (uint64_t s = (uint64_t)j + 64; s < S; s += 64) {
+                SitePriorMeta o;
+                site_prior_load(p.raw + (k * S + s) * SITE_ALLELES, p.members[k * S + s], logs, w1, SITES_PRIOR_TPB, o);
+                site_prior_expected(w1, SITES_PRIOR_TPB, o, st.p, x);
+            }
+        }
+#pragma unroll
+        for (uint32_t a = 0; a < SITE_ALLELES; ++a) x[a] = prior_segment_sum(x[a], W);
+        site_prior_step(st, x, n);
+    }
+    uint32_t ns[MAX_SITE_ALTS], ac[MAX_SITE_ALTS];
+#pragma unroll
+    for (uint32_t c = 0; c < MAX_SITE_ALTS; ++c) ns[c] = ac[c] = 0;
+    if (mine) {
+        for (uint64_t s = j; s < S; s += 64) {
+            const uint64_t i = k * S + s;
+            SitePriorMeta o = m0; const double *w = w0;
+            if (s != j) { site_prior_load(p.raw + i * SITE_ALLELES, p.members[i], logs, w1, SITES_PRIOR_TPB, o); w = w1; }
+            const SitePriorCall call = site_prior_call(w, SITES_PRIOR_TPB, o, st.p, p.min_support);
+            p.sgt[i * 2] = call.a; p.sgt[i * 2 + 1] = call.b; p.sgq[i] = call.gq;
+#pragma unroll
+            for (uint32_t c = 0; c < MAX_SITE_ALTS; ++c) {
+                const uint32_t copies = site_candidate_copies(o.members, call.a, call.b, c);
+                if (copies != SITE_NO_CALL) { ++ns[c]; ac[c] += copies; }
+            }
+        }
+    }
+#pragma unroll
+    for (uint32_t c = 0; c < MAX_SITE_ALTS; ++c) { ns[c] = prior_segment_sum(ns[c], W); ac[c] = prior_segment_sum(ac[c], W); }
+    if (mine && j == 0) {
+#pragma unroll
+        for (uint32_t a = 0; a < SITE_ALLELES; ++a) p.af[k * SITE_ALLELES + a] = st.p[a];
+        p.steps[k] = st.steps;
+#pragma unroll
+        for (uint32_t c = 0; c < MAX_SITE_ALTS; ++c) { p.psite[(k * MAX_SITE_ALTS + c) * 2] = ns[c]; p.psite[(k * MAX_SITE_ALTS + c) * 2 + 1] = ac[c]; }
     }
   }
 }

@@ -6,6 +6,7 @@
     predict-genotype.py --cohort LIST --cohort-ploidy FILE -v VCF ...                       (extension: a ploidy per sample and contig or region)
     predict-genotype.py --cohort LIST --cohort-prior [--cohort-ploidy FILE] -v VCF ...      (extension: calls under the cohort's allele frequency, with GQ)
     predict-genotype.py --cohort LIST --joint-ins -v VCF ...                                (extension: insertions that share a position, together per sample)
+    predict-genotype.py --cohort LIST --joint-ins --joint-prior -v VCF ...                  (extension: the samples of such a site inform each other, with SGQ)
     predict-genotype.py --cohort LIST --cohort-qual [--cohort-theta X] -v VCF ...           (extension: SVQ / MLAC / MLAF, the cohort's exact allele-count posterior)
 """
 import argparse
@@ -32,6 +33,10 @@ def main():
                     help="genotype insertions that share a CHROM and POS together, 2..6 per site, diploid only (extension).  With --cohort: per "
                          "sample, over the rows that sample has counts for; a position with more than six such rows in the VCF is skipped for "
                          "every sample (a single-sample run forms a site there when at most six of them are present in that sample)")
+    ap.add_argument("--joint-prior", action="store_true",
+                    help="with --cohort --joint-ins: estimate the frequencies of a site's alleles from all samples by EM under Hardy-Weinberg and call "
+                         "every sample's site at the maximum of likelihood x prior; member rows gain SGQ, INFO gains EMAF and EMNC, DP / AD / PL stay "
+                         "as without it (extension)")
     ap.add_argument("--cohort", metavar="<samplelist>",
                     help="many samples, one multi-sample VCF with NS / AN / AC / AF in INFO: lines `NAME<TAB>PATH_TO_informative_aln.json` "
                          "(extension; takes the place of -d; diploid, row by row, unless --cohort-ploidy is given; --joint-ins genotypes "
@@ -62,6 +67,10 @@ def main():
         ap.error("--joint-ins is diploid only: it cannot be combined with --ploidy or --ploidy-file")
     if args.joint_ins and (args.cohort_ploidy is not None or args.cohort_prior):
         ap.error("--joint-ins is diploid only: with --cohort it cannot be combined with --cohort-ploidy or --cohort-prior")
+    if args.joint_prior and args.cohort is None:
+        ap.error("--joint-prior needs --cohort")
+    if args.joint_prior and not args.joint_ins:
+        ap.error("--joint-prior needs --joint-ins")
     if args.cohort_qual and args.cohort is None:
         ap.error("--cohort-qual needs --cohort")
     if args.cohort_theta is not None and not args.cohort_qual:
@@ -75,7 +84,7 @@ def main():
     from svjg import genotype
     if args.cohort is not None:
         genotype.run_cohort(args.cohort, args.vcf, out, args.minsupport, err, ploidy_file=args.cohort_ploidy, prior=args.cohort_prior, joint_ins=args.joint_ins,
-                            qual=args.cohort_qual, theta=0.001 if args.cohort_theta is None else args.cohort_theta)
+                            qual=args.cohort_qual, theta=0.001 if args.cohort_theta is None else args.cohort_theta, joint_prior=args.joint_prior)
         return
     genotype.run(args.aln[0], args.vcf, out, args.minsupport, err, ploidy=args.ploidy, ploidy_file=args.ploidy_file, joint_ins=args.joint_ins)
 

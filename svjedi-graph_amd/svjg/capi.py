@@ -93,6 +93,7 @@ _SIGS = {
     "svjg_genotype_cohort_ploidy": (ctypes.c_int, [ctypes.c_void_p] * 5 + [ctypes.c_uint32, ctypes.c_uint64, ctypes.c_uint32, ctypes.c_double] + [ctypes.c_void_p] * 6),
     "svjg_genotype_cohort_prior": (ctypes.c_int, [ctypes.c_void_p] * 5 + [ctypes.c_uint32, ctypes.c_uint64, ctypes.c_uint32, ctypes.c_double] + [ctypes.c_void_p] * 9),
     "svjg_genotype_cohort_sites": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_uint32, ctypes.c_double] + [ctypes.c_void_p] * 6),
+    "svjg_genotype_cohort_sites_prior": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_uint32, ctypes.c_double] + [ctypes.c_void_p] * 11),
     "svjg_cohort_qual": (ctypes.c_int, [ctypes.c_void_p] * 5 + [ctypes.c_uint32, ctypes.c_uint64, ctypes.c_double, ctypes.c_double] + [ctypes.c_void_p] * 3),
     "svjg_set_rows": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64]),
     "svjg_run_resident": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_uint64, ctypes.c_uint32, ctypes.c_double] + [ctypes.POINTER(ctypes.c_void_p)] * 5),
@@ -516,17 +517,21 @@ class Context:
         return self._sites_call("svjg_genotype_sites", slots, min_support, err)
 
     def _sites_call(self, name, slots, min_support, err):
-        """The two site calls: the slot matrix's check, the output arrays (per site, or per (site, sample) item with members and the site words
-        for svjg_genotype_cohort_sites) and the call of library function `name`"""
+        """The three site calls: the slot matrix's check, the output arrays (per site, or per (site, sample) item with members and the site words
+        for svjg_genotype_cohort_sites, and the posterior's five behind them for svjg_genotype_cohort_sites_prior) and the call of library function `name`"""
         slots = np.ascontiguousarray(slots, dtype=np.uint32)
         if slots.ndim != 2 or slots.shape[1] != MAX_SITE_ALTS:
             raise SvjgError("slots: %d per site" % MAX_SITE_ALTS)
         n = len(slots)
-        cohort = name == "svjg_genotype_cohort_sites"
+        prior = name == "svjg_genotype_cohort_sites_prior"
+        cohort = prior or name == "svjg_genotype_cohort_sites"
         at = (n, getattr(self, "_cohort", (0, 0))[0]) if cohort else (n,)
         out = (np.empty(at + (2,), np.uint8), np.empty(at + (SITE_GENOTYPES,), np.int64), np.empty(at + (MAX_SITE_ALTS + 1,), np.uint32), np.empty(at, np.uint8))
         if cohort:
             out = out[:3] + (np.empty(at, np.uint8), out[3], np.empty((n, MAX_SITE_ALTS, 2), np.uint32))
+        if prior:
+            out += (np.empty(at + (2,), np.uint8), np.empty(at, np.uint8), np.empty((n, MAX_SITE_ALTS + 1), np.float64), np.empty(n, np.uint32),
+                    np.empty((n, MAX_SITE_ALTS, 2), np.uint32))
         self._chk(getattr(self.lib, name)(self.h, slots.ctypes.data, n, min_support, float(err), *(a.ctypes.data for a in out)))
         return out
 
@@ -626,6 +631,13 @@ class Context:
         raw[n, S, 7], members[n, S] = bit j: candidate j took part (fewer than two: no site call), boundary[n, S] = the items to recompute with
         svjg.genotype.exact_pl_site, site[n, 6, 2] = NS_j and AC_j of every candidate over the items with a site call)"""
         return self._sites_call("svjg_genotype_cohort_sites", slots, min_support, err)
+
+    def genotype_cohort_sites_prior(self, slots, min_support, err):
+        """genotype_cohort_sites with an allele-frequency prior over the samples of a site (svjg_genotype_cohort_sites_prior).  -> the six arrays of
+        genotype_cohort_sites, bit for bit, and (sgt[n, S, 2] = the POSTERIOR call in the item's member numbering or 0xFF, 0xFF, sgq[n, S] (0xFF:
+        none), af[n, 7] = the frequencies of the reference and the six candidates (NaN: no estimate), em_steps[n] (bit 31: not converged),
+        psite[n, 6, 2] = NS_j and AC_j of the posterior calls)"""
+        return self._sites_call("svjg_genotype_cohort_sites_prior", slots, min_support, err)
 
     def set_rows(self, sv_type, slot, ok):
         """the VCF rows' input arrays of genotype(), left on the device for run_resident()"""

@@ -614,40 +614,48 @@ def cohort_info(info, ns, ac, an=None, em=None, qual=None):
 def _joint_columns(rows, raw, plain, joint):
     """columns(v) of a --cohort --joint-ins run from the plain cohort's: a row of `joint` (row -> (covered[S], g[S], pl3[S, 3], a[S], b[S], sal[S]),
     cohort_joint_sites) prints GT:DP:AD:PL:SGT:SAL — a covered sample what write_vcf_joint prints (the projection of its site call; DP and AD stay
-    the row's own), every other sample its independent column and `:.:.` —; every other row is the plain one"""
+    the row's own), every other sample its independent column and `:.:.` —; every other row is the plain one.  --joint-prior: a seventh array,
+    sgq[S], behind the six (g, a and b are then the POSTERIOR site call's): GT:DP:AD:PL:SGT:SAL:SGQ, SGQ `.` beside `./.`, and `:.:.:.` behind a
+    sample without a site"""
     raw = np.asarray(raw)
 
     def columns(v):
         cols = plain(v)
         if v not in joint:
             return cols
-        covered, g, p3, a, b, sal = (x.tolist() for x in joint[v])
+        covered, g, p3, a, b, sal, *more = (x.tolist() for x in joint[v])
         t = int(rows.sv_type[v])
-        return ["GT:DP:AD:PL:SGT:SAL"] + [_member_column(t, g[s], p3[s], int(raw[v, s, 0]), int(raw[v, s, 1]), _sgt_text(a[s], b[s]), sal[s]) if covered[s]
-                                          else col + ":.:." for s, col in enumerate(cols[1:])]
+        out = [_member_column(t, g[s], p3[s], int(raw[v, s, 0]), int(raw[v, s, 1]), _sgt_text(a[s], b[s]), sal[s]) if covered[s]
+               else col + ":.:." for s, col in enumerate(cols[1:])]
+        if not more:
+            return ["GT:DP:AD:PL:SGT:SAL"] + out
+        sgq = more[0]
+        return ["GT:DP:AD:PL:SGT:SAL:SGQ"] + [col + (":." if not covered[s] or a[s] == NO_CALL else ":%d" % sgq[s]) for s, col in enumerate(out)]
     return columns
 
 
-def write_vcf_cohort(out_path, rows, names, gt, pl, raw, done, site, ploidy=None, gq=None, af=None, em_steps=None, joint=None, qual=None):
+def write_vcf_cohort(out_path, rows, names, gt, pl, raw, done, site, ploidy=None, gq=None, af=None, em_steps=None, joint=None, qual=None, joint_em=None):
     """The one cohort writer: write_vcf with one column per sample (gt, done: [n, S]; pl: [n, S, >= 3]; raw: [n, S, 2]), the site tags' INFO lines
     in front of the header and the tags in INFO; site: [n, 2] = NS, AC or [n, 3] = NS, AN, AC.  ploidy ([n, S]; None: diploid arrays, `Number=3`):
     every item in write_vcf_ploidy's forms (pl: [n, S, >= P + 1]) and `Number=G` in the PL header line.  --cohort-prior: gq[n, S], one more
     FORMAT field, GQ; af[n] and em_steps[n], EMAF / EMNC in INFO.  joint (--joint-ins; cohort_joint_sites): the rows that are members of a site
     for at least one sample, printed by _joint_columns, and SITE_FORMAT_LINES behind the PL line.  qual (--cohort-qual; cohort_qual_rows): (svq[n],
     mlac[n], chroms[n]), SVQ / MLAC / MLAF behind the other tags in INFO and their three header lines; the QUAL column stays the input's.
+    joint_em (--joint-prior; cohort_joint_sites with prior): row -> (p_j, not_converged) of the site's EM for the member rows, EMAF / EMNC in their
+    INFO under the --cohort-prior header lines, and SITE_PRIOR_FORMAT_LINE behind SAL's.
     -> the number of genotyped rows of every sample"""
     columns, n_done = _item_columns(rows, ploidy, gt, pl, raw, done, gq)
     header = FORMAT_HEADER if ploidy is None else FORMAT_HEADER.replace(_PL_3, _PL_G)
     if joint is not None:
         columns = _joint_columns(rows, raw, columns, joint)
-        header = header.replace(_PL_LINE, _PL_LINE + SITE_FORMAT_LINES)
+        header = header.replace(_PL_LINE, _PL_LINE + SITE_FORMAT_LINES + (SITE_PRIOR_FORMAT_LINE if joint_em is not None else ""))
     if gq is not None:
         header = header.replace("#CHROM\t", _GQ_LINE + "#CHROM\t")
-    header = COHORT_INFO_LINES + (COHORT_PRIOR_INFO_LINES if af is not None else "") + (COHORT_QUAL_INFO_LINES if qual is not None else "") + header.replace("\tFORMAT\tSAMPLE\n", "\tFORMAT\t" + "\t".join(names) + "\n")
+    header = COHORT_INFO_LINES + (COHORT_PRIOR_INFO_LINES if af is not None or joint_em is not None else "") + (COHORT_QUAL_INFO_LINES if qual is not None else "") + header.replace("\tFORMAT\tSAMPLE\n", "\tFORMAT\t" + "\t".join(names) + "\n")
     an = np.shape(site)[1] == 3
     _write_rows(out_path, rows, header, columns,
                 lambda v, info: cohort_info(info, int(site[v, 0]), int(site[v, -1]), int(site[v, 1]) if an else None,
-                                            None if af is None else (float(af[v]), bool(int(em_steps[v]) & EM_NOT_CONVERGED)),
+                                            (float(af[v]), bool(int(em_steps[v]) & EM_NOT_CONVERGED)) if af is not None else joint_em.get(v) if joint_em is not None else None,
                                             None if qual is None else (float(qual[0][v]), int(qual[1][v]), int(qual[2][v]))))
     return n_done
 
@@ -811,16 +819,22 @@ def cohort_qual_rows(ctx, rows, n_samples, ploidy, err, theta=COHORT_QUAL_THETA,
     return tuple(np.concatenate([p[k] for p in parts]) for k in range(3))
 
 
-# ---- cohort calls for insertions that share a position (--cohort LIST --joint-ins): svjg_genotype_cohort_sites behind the plain cohort call ----
+# ---- cohort calls for insertions that share a position (--cohort LIST --joint-ins [--joint-prior]): svjg_genotype_cohort_sites (svjg_genotype_cohort_sites_prior) behind the plain cohort call ----
 
 JOINT_INS_COHORT = "--joint-ins is diploid only: with --cohort it cannot be combined with --cohort-ploidy or --cohort-prior"
 COHORT_SITES_ITEM_BYTES = 256      # svjg.h: what one (site, sample) item takes in a svjg_genotype_cohort_sites call,
 COHORT_SITES_SITE_BYTES = 72       # and one site
+JOINT_PRIOR_NEEDS = "--joint-prior needs --cohort and --joint-ins: it is the allele-frequency prior over the samples of a multi-allelic site"
+COHORT_SITES_PRIOR_ITEM_BYTES = 259      # svjg.h: svjg_genotype_cohort_sites_prior adds sgt and sgq to an item,
+COHORT_SITES_PRIOR_SITE_BYTES = 180      # and p[7], the step word and the posterior's NS_j, AC_j to a site
+SITE_PRIOR_FORMAT_LINE = '##FORMAT=<ID=SGQ,Number=1,Type=Integer,Description="Quality of SGT under the site\'s allele frequencies: -10 log10 of the posterior probability that the joint call is wrong, at most 99">\n'
 
 
-def cohort_sites_chunk(n_samples):
-    """sites per svjg_genotype_cohort_sites call, so that it stays under 1 GiB"""
-    return max(1, COHORT_CALL_BYTES // (COHORT_SITES_ITEM_BYTES * max(1, int(n_samples)) + COHORT_SITES_SITE_BYTES))
+def cohort_sites_chunk(n_samples, prior=False):
+    """sites per svjg_genotype_cohort_sites call (prior: svjg_genotype_cohort_sites_prior), so that it stays under 1 GiB"""
+    item, site = (COHORT_SITES_PRIOR_ITEM_BYTES, COHORT_SITES_PRIOR_SITE_BYTES) if prior else (COHORT_SITES_ITEM_BYTES, COHORT_SITES_SITE_BYTES)
+    fixed = 256 if prior else 0          # the pair, the logarithms, the spare bytes and the alignments of the block (the plain call's chunks stay what they were)
+    return max(1, (COHORT_CALL_BYTES - fixed) // (item * max(1, int(n_samples)) + site))
 
 
 def project_cohort_sites(s_gt, s_pl, members):
@@ -850,24 +864,30 @@ def project_cohort_sites(s_gt, s_pl, members):
     return covered, g, pl3, sal
 
 
-def cohort_joint_sites(ctx, rows, gt, site, min_support, err, step=None):
+def cohort_joint_sites(ctx, rows, gt, site, min_support, err, step=None, prior=False):
     """Behind the plain cohort call (gt[n, S], site[n, 2] = NS, AC): the candidate sites at the VCF level — the INS rows with ok & 1 and a slot
     that share CHROM and POS text, 2..6 of them in file order (form_sites; more than six: skipped for every sample, one stderr line) —, ONE
     svjg_genotype_cohort_sites call over them (chunks of `step` sites, None: what fits 1 GiB), the flagged items recomputed with their own K'
     (exact_pl_site), the projection.  -> (site with the candidate rows' NS and AC replaced: the kernel's sums over the covered samples plus the
-    independent calls of the others; joint: row -> (covered[S], g[S], pl3[S, 3], a[S], b[S], sal[S]) for the rows covered in at least one sample)"""
+    independent calls of the others; joint: row -> (covered[S], g[S], pl3[S, 3], a[S], b[S], sal[S]) for the rows covered in at least one sample).
+    prior (--joint-prior): svjg_genotype_cohort_sites_prior instead — the PLs, and so the flagged items' recomputation, are the same; g, a, b and the
+    sums are the POSTERIOR calls', joint's tuples end with sgq[S], and a third value comes back: row -> (p_j, not_converged) for the rows of joint
+    (p_j: the EM's frequency of that row's allele, NaN where no item of the site took part)"""
     min_support, call_err, _ = _call_args(min_support, err)
     sites, skipped = form_sites(rows, ((rows.ok & 1) != 0) & (rows.slot != NONE))
     _report_skipped(skipped)
-    site, joint = np.array(site), {}
+    site, joint, em = np.array(site), {}, {}
     if not sites:
-        return site, joint
+        return (site, joint, em) if prior else (site, joint)
     slots = _site_slots(rows, sites)
     if step is None:
-        step = cohort_sites_chunk(np.shape(gt)[1])
-    parts = [ctx.genotype_cohort_sites(slots[at:at + step], min_support, call_err) for at in range(0, len(sites), int(step))]
-    s_gt, s_pl, s_raw, members, boundary, s_site = (np.concatenate([p[k] for p in parts]) for k in range(6))
+        step = cohort_sites_chunk(np.shape(gt)[1], prior)
+    call = ctx.genotype_cohort_sites_prior if prior else ctx.genotype_cohort_sites
+    parts = [call(slots[at:at + step], min_support, call_err) for at in range(0, len(sites), int(step))]
+    s_gt, s_pl, s_raw, members, boundary, s_site, *post = (np.concatenate([p[k] for p in parts]) for k in range(len(parts[0])))
     recompute_flagged_sites(s_pl, s_raw, boundary, ((members[..., None] >> np.arange(MAX_SITE_ALTS, dtype=np.uint8)) & 1).sum(axis=-1), err)
+    if prior:
+        s_gt, sgq, af, em_steps, s_site = post                   # (the EM never reads PLs: the posterior calls stand as the kernel gave them)
     covered, g, pl3, sal = project_cohort_sites(s_gt, s_pl, members)
     k_of = np.repeat(np.arange(len(sites)), [len(m) for m in sites])
     j_of = np.concatenate([np.arange(len(m)) for m in sites])
@@ -879,12 +899,14 @@ def cohort_joint_sites(ctx, rows, gt, site, min_support, err, step=None):
     site[r_of, 1] = s_site[k_of, j_of, 1] + np.where(alone, own, 0).sum(axis=1)
     for c in np.flatnonzero(cov.any(axis=1)).tolist():
         k, j = k_of[c], j_of[c]
-        joint[int(r_of[c])] = (cov[c], g[k, :, j], pl3[k, :, j], s_gt[k, :, 0], s_gt[k, :, 1], sal[k, :, j])
-    return site, joint
+        joint[int(r_of[c])] = (cov[c], g[k, :, j], pl3[k, :, j], s_gt[k, :, 0], s_gt[k, :, 1], sal[k, :, j]) + ((sgq[k],) if prior else ())
+        if prior:
+            em[int(r_of[c])] = (float(af[k, 1 + j]), bool(int(em_steps[k]) & EM_NOT_CONVERGED))
+    return (site, joint, em) if prior else (site, joint)
 
 
 def run_cohort(list_path, vcf_path, out_path, min_support=3, err=0.00005, device=0, ploidy_file=None, prior=False, joint_ins=False, qual=False,
-               theta=COHORT_QUAL_THETA):
+               theta=COHORT_QUAL_THETA, joint_prior=False):
     """predict-genotype.py --cohort: the samples of a cohort list (load_cohort_list), one multi-sample VCF.  Sample column s is what the
     reference writes as SAMPLE for sample s alone; INFO gains NS, AN, AC and AF.  ploidy_file (--cohort-ploidy, load_cohort_ploidy_file): a
     ploidy per sample and contig or region; column s is then what --ploidy-file with the sample's lines writes for sample s alone, and AN is
@@ -894,8 +916,13 @@ def run_cohort(list_path, vcf_path, out_path, min_support=3, err=0.00005, device
     column s is then what --joint-ins writes for sample s alone, but for `:.:.` behind a sample that has no site on a row another sample has one
     on, and for a position with more than six candidate rows, which is skipped for EVERY sample.  qual (--cohort-qual, theta: --cohort-theta; with
     any of the above but joint_ins): INFO gains SVQ, MLAC and MLAF of the row's exact allele-count posterior (svjg_cohort_qual); every other byte
-    of the file stays what it is without it.  -> the number of genotyped rows of every sample"""
+    of the file stays what it is without it.  joint_prior (--joint-prior, with joint_ins only): the samples of a site inform each other — the
+    frequencies of the site's alleles by EM (svjg_genotype_cohort_sites_prior); a member row prints GT:DP:AD:PL:SGT:SAL:SGQ with GT the projection of the
+    POSTERIOR site call and SGT that call, NS / AC / AN / AF come from the posterior calls, EMAF and EMNC follow them; every non-member row stays the
+    plain cohort row.  -> the number of genotyped rows of every sample"""
     from . import capi, filter as flt
+    if joint_prior and not joint_ins:
+        raise ValueError(JOINT_PRIOR_NEEDS)                      # (before anything is read, asked of the device or written)
     if joint_ins and (ploidy_file is not None or prior):
         raise ValueError(JOINT_INS_COHORT)                       # (before anything is read, asked of the device or written)
     if joint_ins and qual:
@@ -918,13 +945,14 @@ def run_cohort(list_path, vcf_path, out_path, min_support=3, err=0.00005, device
         for s, (slots, counts) in enumerate(per):
             ctx.cohort_set_counts(s, slots, counts)
         gt, pl, raw, done, site, *em = genotype_cohort_rows(ctx, rows, len(samples), min_support, err, ploidy, prior)   # (em: gq, af, em_steps with the prior)
-        joint = None
+        joint = joint_em = None
         if joint_ins:
-            site, joint = cohort_joint_sites(ctx, rows, gt, site, min_support, err)
+            site, joint, *post = cohort_joint_sites(ctx, rows, gt, site, min_support, err, prior=joint_prior)
+            joint_em = post[0] if joint_prior else None
         site_qual = cohort_qual_rows(ctx, rows, len(samples), ploidy, err, theta) if qual else None
     finally:
         ctx.close()
-    n_done = write_vcf_cohort(out_path, rows, names, gt, pl, raw, done, site, ploidy, *em, joint=joint, qual=site_qual)
+    n_done = write_vcf_cohort(out_path, rows, names, gt, pl, raw, done, site, ploidy, *em, joint=joint, qual=site_qual, joint_em=joint_em)
     for name, n in zip(names, n_done):
         print("Genotyped svs (%s): %d" % (name, n))
     return n_done
