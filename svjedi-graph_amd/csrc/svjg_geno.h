@@ -690,7 +690,7 @@ SVJG_HD uint32_t prior_segment_width(uint64_t S) {
 // SGQ = min(99, int(-10 log10(sum of the other q, in increasing slot order))), 99 where that sum is 0.
 // This is a stated fixed-point iteration: a sample with a proper subset of the candidates conditions on that subset.  It is not claimed to be the
 // maximum-likelihood estimate of a model in which an absent candidate counts as zero alt reads.
-// Compiled without fused multiply-adds, so the host harness (tests/site_prior_sim) and the kernel differ in exp10 and log10 only.
+// Compiled without fused multiply-adds, so the host harness (tests/geno_sim, topic site_prior) and the kernel differ in exp10 and log10 only.
 constexpr uint32_t SITE_ALLELES = MAX_SITE_ALTS + 1;    // 7: the reference and the candidates
 // max_j |p_j(device) - p_j(model)|, the model being tests/site_prior_model.py at 60 digits, is measured, not assumed (2026-10-21, one MI355X, ROCm
 // 7.2.0, tests/test_cohort_site_prior_gpu.py: 46 cases of 200 sites (one of 77) x 1..130 samples, the 37 of them with an estimate): at most

@@ -10,29 +10,14 @@ static void row_em(bool wave, uint32_t sv_type, const uint32_t *raw, const uint8
     double tab[2 * PLOIDY_TAB];
     ploidy_log_table(err, tab);
     const uint8_t t8 = (uint8_t)sv_type, *type = &t8;
-    const uint32_t W = prior_segment_width(S);
     uint32_t sum_p = 0;
     for (uint64_t s = 0; s < S; ++s) { PriorItem it; double c; prior_load(type, raw, done, ploidy, s, tab, c, it); sum_p += it.P; }
     PriorRow row = prior_row_start(sum_p);
     while (!row.done) {
         double x = 0.0;
-        if (wave) {
-            double v[64], u[64];
-            for (uint32_t j = 0; j < W; ++j) {                                        // lane j: its items j, j + 64, j + 128, ... from the first one on
-                v[j] = 0.0;
-                for (uint64_t s = j; s < S; s += 64) {
-                    PriorItem it; double c;
-                    prior_load(type, raw, done, ploidy, s, tab, c, it);
-                    const double e = prior_expected(it, row.f);
-                    v[j] = s == j ? e : v[j] + e;
-                }
-            }
-            for (uint32_t m = 1; m < W; m <<= 1) {                                    // the butterfly: every lane adds its partner's value of the level before
-                for (uint32_t j = 0; j < W; ++j) u[j] = v[j] + v[j ^ m];
-                for (uint32_t j = 0; j < W; ++j) v[j] = u[j];
-            }
-            x = v[0];
-        } else
+        if (wave)
+            wave_sum<1>(S, [&](uint64_t s, double *v) { PriorItem it; double c; prior_load(type, raw, done, ploidy, s, tab, c, it); *v += prior_expected(it, row.f); }, &x);
+        else
             for (uint64_t s = 0; s < S; ++s) { PriorItem it; double c; prior_load(type, raw, done, ploidy, s, tab, c, it); x += prior_expected(it, row.f); }
         prior_step(row, x, sum_p);
     }
@@ -52,9 +37,7 @@ extern "C" void genosim_prior_row(uint32_t sv_type, const uint32_t *raw, const u
     row_em(false, sv_type, raw, done, ploidy, S, err, min_support, f, steps, gt, gq, site);
 }
 
-// The same row with every step's sum in the kernel's order: lane j of W = prior_segment_width(S) lanes adds its items j, j + 64, j + 128, ... in
-// that order, starting from the first; then the levels m = 1, 2, ..., W / 2 of the xor butterfly; lanes at or beyond S hold 0.0.  The kernel
-// differs from this in exp10 and log10 only.
+// The same row with every step's sum in the kernel's order (geno_sim.cpp: wave_sum).  The kernel differs from this in exp10 and log10 only.
 extern "C" void genosim_prior_row_wave(uint32_t sv_type, const uint32_t *raw, const uint8_t *done, const uint8_t *ploidy, uint64_t S, double err, uint32_t min_support,
                                        double *f, uint32_t *steps, uint8_t *gt, uint8_t *gq, uint32_t *site) {
     row_em(true, sv_type, raw, done, ploidy, S, err, min_support, f, steps, gt, gq, site);
@@ -73,7 +56,10 @@ extern "C" uint32_t genosim_prior_item(uint32_t sv_type, uint32_t ref, uint32_t 
 }
 
 extern "C" uint32_t genosim_prior_width(uint64_t S) { return prior_segment_width(S); }
-extern "C" void genosim_prior_constants(double *tol, uint32_t *max_it, uint32_t *flag_bit, double *f_bound) { *tol = EM_TOL; *max_it = EM_MAX_IT; *flag_bit = EM_NOT_CONVERGED; *f_bound = EM_F_BOUND; }
+// the EM's constants, those of the site prior (site_prior.inc) among them
+extern "C" void genosim_prior_constants(double *tol, uint32_t *max_it, uint32_t *flag_bit, double *f_bound, double *p_bound) {
+    *tol = EM_TOL; *max_it = EM_MAX_IT; *flag_bit = EM_NOT_CONVERGED; *f_bound = EM_F_BOUND; *p_bound = SITE_EM_P_BOUND;
+}
 
 #ifdef GENO_SIM_MAIN
 static int main_prior() {

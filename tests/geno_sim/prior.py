@@ -32,12 +32,12 @@ def width(S):
     return call("genosim_prior_width", U32, [U64], int(S))
 
 
-def constants():
-    """-> (EM_TOL, EM_MAX_IT, EM_NOT_CONVERGED, EM_F_BOUND)"""
-    tol, bound = np.zeros(1), np.zeros(1)
+def constants(site=False):
+    """-> (EM_TOL, EM_MAX_IT, EM_NOT_CONVERGED, EM_F_BOUND, or with site SITE_EM_P_BOUND)"""
+    tol, f_bound, p_bound = np.zeros(1), np.zeros(1), np.zeros(1)
     it, bit = np.zeros(1, np.uint32), np.zeros(1, np.uint32)
-    call("genosim_prior_constants", None, [PTR] * 4, tol, it, bit, bound)
-    return float(tol[0]), int(it[0]), int(bit[0]), float(bound[0])
+    call("genosim_prior_constants", None, [PTR] * 5, tol, it, bit, f_bound, p_bound)
+    return float(tol[0]), int(it[0]), int(bit[0]), float((p_bound if site else f_bound)[0])
 
 
 def layout(n_rows, S, max_ploidy, per_item):

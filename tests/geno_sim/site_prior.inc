@@ -1,23 +1,14 @@
-// TEST HARNESS ONLY (never shipped, never loaded by the product): the routines of svjg_geno.h behind k_cohort_sites_prior (site_prior_load,
-// site_prior_expected, site_prior_step, site_prior_call), compiled with g++ and driven from numpy (tests/site_prior_sim/__init__.py).  A site's EM
-// runs sequentially over its samples (wave = 0) or with every step's sums in the kernel's order (wave = 1: lanes, strides, butterfly).  With
-// -DSITE_PRIOR_SIM_MAIN it is a stand-alone program (for -fsanitize=address,undefined) that runs seeded sites with every array at exactly its size.
-#define SVJG_HD inline
-#include "../../svjedi-graph_amd/csrc/svjg_geno.h"
-#include <math.h>
-#include <stdio.h>
-#include <string.h>
-#include <vector>
-
-using namespace svjg;
+// The routines of svjg_geno.h behind k_cohort_sites_prior (site_prior_load, site_prior_expected, site_prior_step, site_prior_call).  A site's EM
+// runs sequentially over its samples (wave = 0) or with every step's sums in the kernel's order (wave = 1: geno_sim.cpp: wave_sum).  Topic
+// `site_prior` of the stand-alone program runs seeded sites with every array at exactly its size.
 
 // One site of S samples: raw[S][7], members[S] as the first kernel left them, slots[6] (only which are named matters) -> p[7] (NaN: no estimate),
 // *steps (the kernel's word), sgt[S][2] (member numbering), sgq[S], psite[6][2] = NS_j, AC_j.
-extern "C" void sitepriorsim_site(int wave, const uint32_t *raw, const uint8_t *members, const uint32_t *slots, uint64_t S, double err, uint32_t min_support,
-                                  double *p, uint32_t *steps, uint8_t *sgt, uint8_t *sgq, uint32_t *psite) {
+extern "C" void genosim_site_prior_site(int wave, const uint32_t *raw, const uint8_t *members, const uint32_t *slots, uint64_t S, double err, uint32_t min_support,
+                                        double *p, uint32_t *steps, uint8_t *sgt, uint8_t *sgq, uint32_t *psite) {
     double logs[SITE_LOGS];
     site_log_table(err, logs);
-    const uint32_t W = prior_segment_width(S), C = site_candidates(slots);
+    const uint32_t C = site_candidates(slots);
     std::vector<double> w(S * SITE_GENOTYPES);
     std::vector<SitePriorMeta> meta(S);
     uint32_t n = 0;
@@ -28,18 +19,9 @@ extern "C" void sitepriorsim_site(int wave, const uint32_t *raw, const uint8_t *
     SitePriorSite st = site_prior_start(C, n);
     while (!st.done) {
         double x[SITE_ALLELES];
-        if (wave) {
-            double v[64][SITE_ALLELES], u[64][SITE_ALLELES];
-            for (uint32_t j = 0; j < W; ++j) {                                        // lane j: its items j, j + 64, j + 128, ... added to zeros in that order
-                for (uint32_t a = 0; a < SITE_ALLELES; ++a) v[j][a] = 0.0;
-                for (uint64_t s = j; s < S; s += 64) site_prior_expected(w.data() + s * SITE_GENOTYPES, 1, meta[s], st.p, v[j]);
-            }
-            for (uint32_t m = 1; m < W; m <<= 1) {                                    // the butterfly: every lane adds its partner's value of the level before
-                for (uint32_t j = 0; j < W; ++j) for (uint32_t a = 0; a < SITE_ALLELES; ++a) u[j][a] = v[j][a] + v[j ^ m][a];
-                memcpy(v, u, sizeof v);
-            }
-            for (uint32_t a = 0; a < SITE_ALLELES; ++a) x[a] = v[0][a];
-        } else {
+        if (wave)
+            wave_sum<SITE_ALLELES>(S, [&](uint64_t s, double *v) { site_prior_expected(w.data() + s * SITE_GENOTYPES, 1, meta[s], st.p, v); }, x);
+        else {
             for (uint32_t a = 0; a < SITE_ALLELES; ++a) x[a] = 0.0;
             for (uint64_t s = 0; s < S; ++s) site_prior_expected(w.data() + s * SITE_GENOTYPES, 1, meta[s], st.p, x);
         }
@@ -59,15 +41,15 @@ extern "C" void sitepriorsim_site(int wave, const uint32_t *raw, const uint8_t *
 }
 
 // n sites of S samples each, back to back
-extern "C" void sitepriorsim_sites(int wave, const uint32_t *raw, const uint8_t *members, const uint32_t *slots, uint64_t n, uint64_t S, double err, uint32_t min_support,
-                                   double *p, uint32_t *steps, uint8_t *sgt, uint8_t *sgq, uint32_t *psite) {
+extern "C" void genosim_site_prior_sites(int wave, const uint32_t *raw, const uint8_t *members, const uint32_t *slots, uint64_t n, uint64_t S, double err, uint32_t min_support,
+                                         double *p, uint32_t *steps, uint8_t *sgt, uint8_t *sgq, uint32_t *psite) {
     for (uint64_t k = 0; k < n; ++k)
-        sitepriorsim_site(wave, raw + k * S * SITE_ALLELES, members + k * S, slots + k * MAX_SITE_ALTS, S, err, min_support,
-                          p + k * SITE_ALLELES, steps + k, sgt + k * S * 2, sgq + k * S, psite + k * 2 * MAX_SITE_ALTS);
+        genosim_site_prior_site(wave, raw + k * S * SITE_ALLELES, members + k * S, slots + k * MAX_SITE_ALTS, S, err, min_support,
+                                p + k * SITE_ALLELES, steps + k, sgt + k * S * 2, sgq + k * S, psite + k * 2 * MAX_SITE_ALTS);
 }
 
 // the weights of one item in candidate order: w[28] at the given stride (a test may hand in a strided array), -> takes part; *top, *N
-extern "C" uint32_t sitepriorsim_item(const uint32_t *raw, uint32_t members, double err, double *w, uint32_t stride, uint32_t *top, double *N) {
+extern "C" uint32_t genosim_site_prior_item(const uint32_t *raw, uint32_t members, double err, double *w, uint32_t stride, uint32_t *top, double *N) {
     double logs[SITE_LOGS];
     site_log_table(err, logs);
     SitePriorMeta m;
@@ -77,7 +59,7 @@ extern "C" uint32_t sitepriorsim_item(const uint32_t *raw, uint32_t members, dou
 }
 
 // geno_site's likelihoods in member numbering (what the factored site_lik returns for a site of K members): hi[28], lo[28], 0 beyond the site's
-extern "C" void sitepriorsim_lik(uint32_t K, uint32_t ref, const uint32_t *alt, double err, double *hi, double *lo) {
+extern "C" void genosim_site_prior_lik(uint32_t K, uint32_t ref, const uint32_t *alt, double err, double *hi, double *lo) {
     double logs[SITE_LOGS], c[SITE_ALLELES];
     site_log_table(err, logs);
     c[0] = (double)ref; double N = c[0];
@@ -89,18 +71,8 @@ extern "C" void sitepriorsim_lik(uint32_t K, uint32_t ref, const uint32_t *alt, 
         }
 }
 
-// sites_layout with both switches -> the offsets in the order of the names below (site_prior_sim/__init__.py: LAYOUT_FIELDS)
-extern "C" void sitepriorsim_layout(uint64_t n, uint64_t S, int cohort, int prior, uint64_t *at) {
-    const SitesLayout L = sites_layout(n, S, cohort != 0, prior != 0);
-    const uint64_t v[] = {L.pl, L.raw, L.gt, L.members, L.boundary, L.sgt, L.sgq, L.af, L.psite, L.steps, L.site, L.maxn, L.in_at, L.logs, L.slots, L.in_bytes, L.total};
-    memcpy(at, v, sizeof v);
-}
-
-extern "C" uint32_t sitepriorsim_width(uint64_t S) { return prior_segment_width(S); }
-extern "C" void sitepriorsim_constants(double *tol, uint32_t *max_it, uint32_t *flag_bit, double *p_bound) { *tol = EM_TOL; *max_it = EM_MAX_IT; *flag_bit = EM_NOT_CONVERGED; *p_bound = SITE_EM_P_BOUND; }
-
-#ifdef SITE_PRIOR_SIM_MAIN
-int main() {
+#ifdef GENO_SIM_MAIN
+static int main_site_prior() {
     const uint64_t sizes[] = {1, 2, 3, 8, 9, 63, 64, 65, 130};
     uint64_t sites = 0, bad = 0, x = 88172645463325252ull;
     auto next = [&] { x ^= x << 13; x ^= x >> 7; x ^= x << 17; return x; };
@@ -120,8 +92,8 @@ int main() {
                 }
                 double p[SITE_ALLELES], p2[SITE_ALLELES]; uint32_t steps, steps2, ps[2 * MAX_SITE_ALTS], ps2[2 * MAX_SITE_ALTS];
                 const uint32_t ms = k & 1 ? 3 : 0;
-                sitepriorsim_site(0, raw.data(), members.data(), slots.data(), S, 5e-5, ms, p, &steps, sgt.data(), sgq.data(), ps);
-                sitepriorsim_site(1, raw.data(), members.data(), slots.data(), S, 5e-5, ms, p2, &steps2, sgt2.data(), sgq2.data(), ps2);
+                genosim_site_prior_site(0, raw.data(), members.data(), slots.data(), S, 5e-5, ms, p, &steps, sgt.data(), sgq.data(), ps);
+                genosim_site_prior_site(1, raw.data(), members.data(), slots.data(), S, 5e-5, ms, p2, &steps2, sgt2.data(), sgq2.data(), ps2);
                 ++sites;
                 uint32_t part = 0, ns[MAX_SITE_ALTS] = {0}, ac[MAX_SITE_ALTS] = {0};
                 for (uint64_t s = 0; s < S; ++s) {
@@ -145,7 +117,7 @@ int main() {
             }
     for (uint64_t n : {1, 7, 1000}) for (uint64_t S : {1, 3, 64, 65}) {
         uint64_t a[17], b[17];
-        sitepriorsim_layout(n, S, 1, 1, a); sitepriorsim_layout(n, S, 1, 0, b);
+        layout_at(LAYOUT_SITES, n, S, 0, 1 | 4, a); layout_at(LAYOUT_SITES, n, S, 0, 1 | 8, b);
         if (a[7] % 8 || a[8] % 8 || a[10] % 8 || a[11] != a[10] + n * 48 || a[5] != b[4] + n * S || b[5] || b[7] || a[12] != a[11] + 8) ++bad;
     }
     printf("site_prior_sim %s: %llu sites, %llu checks failed\n", bad ? "FAILED" : "ok", (unsigned long long)sites, (unsigned long long)bad);

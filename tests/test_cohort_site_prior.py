@@ -1,6 +1,6 @@
 """Joint insertion calls in a cohort under an allele-frequency prior (--cohort LIST --joint-ins --joint-prior), on the CPU: the 60-digit model
 (tests/site_prior_model.py) against a brute-force EM; the routines of svjg_geno.h behind k_cohort_sites_prior, compiled with g++
-(tests/site_prior_sim), against the model's stored answers in sequential order and in the kernel's order of the sums; the weights' expansion to
+(tests/geno_sim, topic site_prior), against the model's stored answers in sequential order and in the kernel's order of the sums; the weights' expansion to
 candidate order; site_lik behind the factoring; the layout; the harness under the sanitizers; the option's refusals; the writer on a hand-made
 cohort against the model's calls; the run without the option against the parent's bytes."""
 import json
@@ -17,7 +17,7 @@ import pytest
 from tests import cohort_site_prior_cases as CS
 from tests import site_model as SM
 from tests import site_prior_model as M
-from tests import site_prior_sim as H
+from tests.geno_sim import site_prior as H
 from tests.geno_sim import site as geno_site_sim
 from tests.test_cohort_joint_ins import CohortModelCtx, _sample_counts, _NoGpu
 from tests.test_joint_ins import _ROWS, VCF_TEXT
@@ -234,7 +234,7 @@ def test_layout_with_the_prior_switch(n, S):
 
 def test_harness_under_the_sanitizers():
     """the seeded checks as a stand-alone program with its own main under -fsanitize=address,undefined, every array at exactly its size"""
-    p = subprocess.run([H.build_main()], capture_output=True, text=True)
+    p = subprocess.run([H.build_main(), "site_prior"], capture_output=True, text=True)
     assert p.returncode == 0 and p.stdout.startswith("site_prior_sim ok") and not p.stderr, (p.stdout, p.stderr)
 
 

@@ -13,7 +13,7 @@ import pytest
 from tests import cohort_site_prior_cases as CS
 from tests import products_items as PI
 from tests import site_prior_model as M
-from tests import site_prior_sim as H
+from tests.geno_sim import site_prior as H
 
 pytestmark = pytest.mark.gpu
 

@@ -1,6 +1,6 @@
-"""The seven step-by-step genotype calls share one host leg (svjg_capi.hip: genotype_leg; the three cohort calls one more, cohort_call, the two
-site calls another, sites_call) and keep a block each (svjg_ctx::leg[]): run on ONE context in either order, every call returns the bytes it
-returns on a context of its own, whichever calls ran in between, and a view of the diploid call's pinned block outlives the other six.  Needs an MI355X: run with -m gpu."""
+"""The eight step-by-step genotype calls share one host leg (svjg_capi.hip: genotype_leg; the three cohort calls one more, cohort_call, the three
+site calls another, sites_call) and keep a block each (svjg_ctx::leg[]): run on ONE context in any of four orders, every call returns the bytes it
+returns on a context of its own, whichever calls ran in between, and a view of the diploid call's pinned block outlives the other seven.  Needs an MI355X: run with -m gpu."""
 import numpy as np
 import pytest
 
@@ -9,7 +9,7 @@ pytestmark = pytest.mark.gpu
 NONE = 0xFFFFFFFF
 R, S, N_SLOTS = 65, 3, 90              # two waves of rows with a ragged end; three samples; the sites' members lie behind the rows' slots
 MS, ERR = 3, 5e-5
-CALLS = ("rows", "ploidy", "sites", "cohort", "cohort_ploidy", "cohort_prior", "cohort_sites")
+CALLS = ("rows", "ploidy", "sites", "cohort", "cohort_ploidy", "cohort_prior", "cohort_sites", "cohort_sites_prior")
 
 
 def _case():
@@ -63,6 +63,8 @@ def _call(ctx, c, which, view=False):
         return ctx.genotype_sites(c["sites"], MS, ERR)
     if which == "cohort_sites":
         return ctx.genotype_cohort_sites(c["sites"], MS, ERR)              # (the same five sites, as candidates in the matrix)
+    if which == "cohort_sites_prior":
+        return ctx.genotype_cohort_sites_prior(c["sites"], MS, ERR)        # (its first six arrays are the call's without the prior)
     if which == "cohort_ploidy":
         return ctx.genotype_cohort_ploidy(c["t"], c["slot"], c["ok"], c["item_ploidy"], 8, MS, ERR)
     if which == "cohort_prior":
@@ -98,11 +100,15 @@ def alone(case):
     assert done[item] == 1 and raw[2 * item: 2 * item + 2].tolist() == [40_000, 40_000] and pl[3 * item: 3 * item + 3].any()
     assert any(want["rows"][0]) and any(want["ploidy"][1]) and any(want["sites"][1]) and any(want["cohort_ploidy"][1]) and any(want["cohort_prior"][1])
     assert any(want["cohort_sites"][1]) and any(want["cohort_sites"][5])      # PLs and site words
+    assert all(any(want["cohort_sites_prior"][i]) for i in (1, 6, 8))         # PLs, posterior calls, frequencies
     return want
 
 
 @pytest.mark.parametrize("order", [("rows", "ploidy", "sites", "cohort", "cohort_sites", "cohort_ploidy", "cohort_prior", "rows"),
-                                   ("rows", "cohort_sites", "cohort_prior", "cohort", "sites", "cohort_ploidy", "ploidy", "rows")])
+                                   ("rows", "cohort_sites", "cohort_prior", "cohort", "sites", "cohort_ploidy", "ploidy", "rows"),
+                                   ("rows", "cohort_sites", "cohort_sites_prior", "cohort_prior", "sites", "cohort_sites_prior", "cohort", "ploidy", "rows"),
+                                   ("rows", "cohort_sites_prior", "cohort", "cohort_sites", "cohort_sites_prior", "cohort_ploidy", "cohort_prior",
+                                    "cohort_sites_prior", "rows")])
 def test_every_call_in_a_block_of_its_own(case, alone, order):
     from svjg import capi
     ctx = capi.Context(0)
@@ -111,7 +117,9 @@ def test_every_call_in_a_block_of_its_own(case, alone, order):
         view = _call(ctx, case, order[0], view=True)[:4]             # gt, pl, raw, genotyped: pointers into the pinned block
         assert _bytes(view) == alone["rows"][:4] and ctx.logfact_entries() == 65536
         for which in order[1:-1]:
-            assert _bytes(_call(ctx, case, which)) == alone[which], which
+            got = _bytes(_call(ctx, case, which))
+            assert got == alone[which], which
+            assert which != "cohort_sites_prior" or got[:6] == alone["cohort_sites"]
             assert _bytes(view) == alone["rows"][:4], f"the view after {which}"
             assert ctx.boundary_flags(R).tobytes() == alone["rows"][4], f"the boundary bytes after {which}"
         assert ctx.logfact_entries() > 65536                         # the table grew inside a leg that was not the first
