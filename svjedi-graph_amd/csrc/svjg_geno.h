@@ -1097,9 +1097,6 @@ inline SitesLayout sites_layout(uint64_t n_sites, uint64_t S = 1, bool cohort = 
     L.logs = L.in_at; L.slots = L.logs + SITE_LOGS * 8;
     return L;
 }
-// (the parent's cohort entry point, kept like cohort_ploidy_layout above: the harness of earlier tests, tests/cohort_sites_sim as it stood, compiles against it)
-using CohortSitesLayout = SitesLayout;
-inline SitesLayout cohort_sites_layout(uint64_t n_sites, uint64_t S) { return sites_layout(n_sites, S, true); }
 
 // svjg_genotype_cohort (max_ploidy 2, neither switch), _cohort_ploidy (per_item) and _cohort_prior (prior; per_item iff it has a ploidy array):
 // [ pl 8 (max_ploidy + 1) | raw 8 | gt 1 | flags 1 | boundary 1 ] x (n_rows * S items, row-major) — the PL stride is the CALL's, not MAX_PLOIDY + 1:
@@ -1120,13 +1117,6 @@ inline CohortLayout cohort_layout(uint64_t n_rows, uint64_t S, uint32_t max_ploi
     L.logtab = logs ? L.in_at : 0; L.in = rows_in(n_rows, L.in_at + logs); L.ploidy = L.in.slot + L.in.bytes;
     return L;
 }
-// The parent's three layout entry points: cohort_layout(n_rows, S) through the defaults above, and these.  Nothing in this tree calls them; the host
-// harnesses of the tests written before the one layout (one directory a feature then; since merged into tests/geno_sim) compile against them, and
-// those tests are held against every later build.
-using CohortPloidyLayout = CohortLayout;
-using CohortPriorLayout = CohortLayout;
-inline CohortLayout cohort_ploidy_layout(uint64_t n_rows, uint64_t S, uint32_t max_ploidy) { return cohort_layout(n_rows, S, max_ploidy, true, false); }
-inline CohortLayout cohort_prior_layout(uint64_t n_rows, uint64_t S, uint32_t max_ploidy, bool per_item) { return cohort_layout(n_rows, S, max_ploidy, per_item, true); }
 
 // svjg_cohort_qual: [ qual 8 | mlac 4 | chroms 4 ] x n_rows of output; in: the call's logarithms (ploidy_log_table), H_0..H_m_max
 // (qual_harmonic), rows_in(n_rows) and, per_item, the n_rows * S ploidy bytes

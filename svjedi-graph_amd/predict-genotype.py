@@ -59,34 +59,31 @@ def main():
     if args.cohort is not None and (args.ploidy is not None or args.ploidy_file is not None):
         ap.error("--cohort is diploid, row by row: it cannot be combined with --ploidy or --ploidy-file "
                  "(per-sample ploidy in a cohort: --cohort-ploidy)")
-    if args.cohort_ploidy is not None and args.cohort is None:
-        ap.error("--cohort-ploidy needs --cohort")
-    if args.cohort_prior and args.cohort is None:
-        ap.error("--cohort-prior needs --cohort")
-    if args.joint_ins and (args.ploidy is not None or args.ploidy_file is not None):
-        ap.error("--joint-ins is diploid only: it cannot be combined with --ploidy or --ploidy-file")
-    if args.joint_ins and (args.cohort_ploidy is not None or args.cohort_prior):
-        ap.error("--joint-ins is diploid only: with --cohort it cannot be combined with --cohort-ploidy or --cohort-prior")
-    if args.joint_prior and args.cohort is None:
-        ap.error("--joint-prior needs --cohort")
-    if args.joint_prior and not args.joint_ins:
-        ap.error("--joint-prior needs --joint-ins")
-    if args.cohort_qual and args.cohort is None:
-        ap.error("--cohort-qual needs --cohort")
+    from svjg import genotype
+    single = dict(ploidy=args.ploidy, ploidy_file=args.ploidy_file, joint_ins=args.joint_ins)
+    cohort = dict(ploidy_file=args.cohort_ploidy, prior=args.cohort_prior, joint_ins=args.joint_ins, joint_prior=args.joint_prior, qual=args.cohort_qual,
+                  theta=genotype.COHORT_QUAL_THETA if args.cohort_theta is None else args.cohort_theta)
+    try:                                                         # the rules between the options themselves are the library's: one text each
+        if args.cohort is None:
+            for flag, given in (("--cohort-ploidy", args.cohort_ploidy is not None), ("--cohort-prior", args.cohort_prior)):
+                if given:
+                    ap.error(flag + " needs --cohort")
+            genotype.check_single_options(**single)
+            for flag, given in (("--joint-prior", args.joint_prior), ("--cohort-qual", args.cohort_qual)):
+                if given:
+                    ap.error(flag + " needs --cohort")
+        else:
+            genotype.check_cohort_options(**cohort)
+    except ValueError as e:
+        ap.error(str(e))
     if args.cohort_theta is not None and not args.cohort_qual:
         ap.error("--cohort-theta needs --cohort-qual")
-    if args.cohort_theta is not None and not 0.0 < args.cohort_theta <= 0.05:
-        ap.error("--cohort-theta: a value in (0, 0.05]")
-    if args.joint_ins and args.cohort_qual:
-        ap.error("--joint-ins cannot be combined with --cohort-qual: the site model there is multi-allelic")
     out = "genotype_results.txt" if args.output is None else args.output[0]
     err = args.err[0] if args.err is not None else 0.00005
-    from svjg import genotype
     if args.cohort is not None:
-        genotype.run_cohort(args.cohort, args.vcf, out, args.minsupport, err, ploidy_file=args.cohort_ploidy, prior=args.cohort_prior, joint_ins=args.joint_ins,
-                            qual=args.cohort_qual, theta=0.001 if args.cohort_theta is None else args.cohort_theta, joint_prior=args.joint_prior)
+        genotype.run_cohort(args.cohort, args.vcf, out, args.minsupport, err, **cohort)
         return
-    genotype.run(args.aln[0], args.vcf, out, args.minsupport, err, ploidy=args.ploidy, ploidy_file=args.ploidy_file, joint_ins=args.joint_ins)
+    genotype.run(args.aln[0], args.vcf, out, args.minsupport, err, **single)
 
 
 if __name__ == "__main__":

@@ -325,6 +325,28 @@ def _row_inputs(sv_type, slot, ok):
     return np.ascontiguousarray(sv_type, dtype=np.uint8), np.ascontiguousarray(slot, dtype=np.uint32), np.ascontiguousarray(ok, dtype=np.uint8)
 
 
+def _view(ptr, count, dtype):
+    """`count` elements at the library's pointer as a read-only array: no copy"""
+    a = np.frombuffer((ctypes.c_char * (count * np.dtype(dtype).itemsize)).from_address(ptr.value), dtype=dtype)
+    a.flags.writeable = False
+    return a
+
+
+def _max_ploidy(max_ploidy):
+    """a cohort call's max_ploidy as the library takes it (a value out of 1..MAX_PLOIDY is the library's to refuse: nothing is written then)"""
+    if not 0 <= int(max_ploidy) <= 0xFFFFFFFF:
+        raise SvjgError("max_ploidy: 1..%d" % MAX_PLOIDY)
+    return int(max_ploidy)
+
+
+def _ploidy_matrix(ploidy, n, S):
+    """a cohort call's ploidy[n, S] in the element type the library reads"""
+    ploidy = np.asarray(ploidy)
+    if ploidy.shape != (n, S) or (ploidy.size and (int(ploidy.min()) < 0 or int(ploidy.max()) > 255)):
+        raise SvjgError("ploidy: one value in 0..max_ploidy per (row, sample)")
+    return np.ascontiguousarray(ploidy, dtype=np.uint8)
+
+
 class Context:
     """One GPU.  Thin, stateful wrapper over the C ABI."""
 
@@ -337,6 +359,7 @@ class Context:
             raise SvjgError(f"svjg_init failed ({rc}): {msg.decode() if msg else ''}")
         self.h = h
         self.graph = None
+        self._cohort = (0, 0)                                   # (n_samples, n_slots) of the cohort matrix (cohort_alloc)
 
     def close(self):
         if getattr(self, "h", None):
@@ -476,12 +499,7 @@ class Context:
             p = [ctypes.c_void_p() for _ in range(4)]
             self._chk(self.lib.svjg_genotype_view(self.h, sv_type.ctypes.data, slot.ctypes.data, ok.ctypes.data, n, min_support,
                                                   float(err), *[ctypes.byref(x) for x in p]))
-
-            def view(ptr, count, dt):
-                a = np.frombuffer((ctypes.c_char * (count * np.dtype(dt).itemsize)).from_address(ptr.value), dtype=dt)
-                a.flags.writeable = False
-                return a
-            return view(p[0], n, np.uint8), view(p[1], n * 3, np.int64).reshape(n, 3), view(p[2], n * 2, np.uint32).reshape(n, 2), view(p[3], n, np.uint8)
+            return _view(p[0], n, np.uint8), _view(p[1], n * 3, np.int64).reshape(n, 3), _view(p[2], n * 2, np.uint32).reshape(n, 2), _view(p[3], n, np.uint8)
         gt = np.empty(n, dtype=np.uint8)
         pl = np.empty((n, 3), dtype=np.int64)
         raw = np.empty((n, 2), dtype=np.uint32)
@@ -514,25 +532,23 @@ class Context:
         """Insertions that share a position, genotyped together (svjg_genotype_sites).  slots[n, 6]: the members' count slots first, 0xFFFFFFFF
         behind them.  -> (gt[n, 2] = the pair (a, b) or 0xFF, 0xFF, pl[n, 28] in VCF order then zeros, raw[n, 7] = ref maximum and alt_1..alt_6,
         boundary = the sites to recompute with svjg.genotype.exact_pl_site)"""
-        return self._sites_call("svjg_genotype_sites", slots, min_support, err)
+        return self._sites_call(self.lib.svjg_genotype_sites, slots, min_support, err)
 
-    def _sites_call(self, name, slots, min_support, err):
-        """The three site calls: the slot matrix's check, the output arrays (per site, or per (site, sample) item with members and the site words
-        for svjg_genotype_cohort_sites, and the posterior's five behind them for svjg_genotype_cohort_sites_prior) and the call of library function `name`"""
+    def _sites_call(self, fn, slots, min_support, err, cohort=False, prior=False):
+        """The three site calls: the slot matrix's check, the output arrays (per site; cohort: per (site, sample) item, with members and the site
+        words; prior: the posterior's five behind those) and the call of library function `fn`"""
         slots = np.ascontiguousarray(slots, dtype=np.uint32)
         if slots.ndim != 2 or slots.shape[1] != MAX_SITE_ALTS:
             raise SvjgError("slots: %d per site" % MAX_SITE_ALTS)
         n = len(slots)
-        prior = name == "svjg_genotype_cohort_sites_prior"
-        cohort = prior or name == "svjg_genotype_cohort_sites"
-        at = (n, getattr(self, "_cohort", (0, 0))[0]) if cohort else (n,)
+        at = (n, self._cohort[0]) if cohort else (n,)
         out = (np.empty(at + (2,), np.uint8), np.empty(at + (SITE_GENOTYPES,), np.int64), np.empty(at + (MAX_SITE_ALTS + 1,), np.uint32), np.empty(at, np.uint8))
         if cohort:
             out = out[:3] + (np.empty(at, np.uint8), out[3], np.empty((n, MAX_SITE_ALTS, 2), np.uint32))
         if prior:
             out += (np.empty(at + (2,), np.uint8), np.empty(at, np.uint8), np.empty((n, MAX_SITE_ALTS + 1), np.float64), np.empty(n, np.uint32),
                     np.empty((n, MAX_SITE_ALTS, 2), np.uint32))
-        self._chk(getattr(self.lib, name)(self.h, slots.ctypes.data, n, min_support, float(err), *(a.ctypes.data for a in out)))
+        self._chk(fn(self.h, slots.ctypes.data, n, min_support, float(err), *(a.ctypes.data for a in out)))
         return out
 
     def cohort_alloc(self, n_samples, n_slots):
@@ -555,71 +571,58 @@ class Context:
 
     def cohort_get_counts(self, sample):
         """-> (counts[n_slots, 2], present[n_slots]) of one sample (svjg_cohort_get_counts)"""
-        n_slots = getattr(self, "_cohort", (0, 0))[1]
+        n_slots = self._cohort[1]
         out = np.zeros((n_slots, 2), dtype=np.uint32)
         present = np.zeros(n_slots, dtype=np.uint8)
         self._chk(self.lib.svjg_cohort_get_counts(self.h, int(sample), out.ctypes.data, present.ctypes.data, n_slots))
         return out, present
 
-    def _cohort_call(self, name, sv_type, slot, ok, ploidy, max_ploidy, min_support, err):
-        """The three cohort calls: the checks, the output arrays and the call of library function `name`.  -> (gt[n, S], pl[n, S, max_ploidy + 1],
-        raw[n, S, 2], genotyped[n, S], boundary[n, S], site[n, 2 or 3]) and, from svjg_genotype_cohort_prior, (gq[n, S], af[n], em_steps[n])"""
-        plain, prior = name == "svjg_genotype_cohort", name == "svjg_genotype_cohort_prior"
-        n = len(sv_type)
-        S = getattr(self, "_cohort", (0, 0))[0]
-        max_ploidy = int(max_ploidy)
-        if not 0 <= max_ploidy <= 0xFFFFFFFF:
-            raise SvjgError("max_ploidy: 1..%d" % MAX_PLOIDY)
-        width = min(max_ploidy, MAX_PLOIDY) + 1                  # (a max_ploidy out of range is the library's to refuse: nothing is written then)
+    def _cohort_call(self, fn, sv_type, slot, ok, ploidy, max_ploidy, min_support, err, ploidy_pair=True, need_ploidy=False, prior=False):
+        """The three cohort calls: the checks, the output arrays and the call of library function `fn`.  ploidy_pair: fn takes (ploidy, max_ploidy)
+        and gives site[n, 3], else site[n, 2]; need_ploidy: ploidy may not be None; prior: fn gives (gq[n, S], af[n], em_steps[n]) as well.
+        -> (gt[n, S], pl[n, S, max_ploidy + 1], raw[n, S, 2], genotyped[n, S], boundary[n, S], site) and the prior's three"""
+        n, S = len(sv_type), self._cohort[0]
+        max_ploidy = _max_ploidy(max_ploidy)
+        width = min(max_ploidy, MAX_PLOIDY) + 1
         sv_type, slot, ok = _row_inputs(sv_type, slot, ok)
-        if ploidy is not None or not (plain or prior):
-            ploidy = np.asarray(ploidy)
-            if ploidy.shape != (n, S) or (ploidy.size and (int(ploidy.min()) < 0 or int(ploidy.max()) > 255)):
-                raise SvjgError("ploidy: one value in 0..max_ploidy per (row, sample)")
-            ploidy = np.ascontiguousarray(ploidy, dtype=np.uint8)
+        if ploidy is not None or need_ploidy:
+            ploidy = _ploidy_matrix(ploidy, n, S)
         out = (np.empty((n, S), np.uint8), np.empty((n, S, width), np.int64), np.empty((n, S, 2), np.uint32), np.empty((n, S), np.uint8),
-               np.empty((n, S), np.uint8), np.empty((n, 2 if plain else 3), np.uint32))
+               np.empty((n, S), np.uint8), np.empty((n, 3 if ploidy_pair else 2), np.uint32))
         if prior:
             out += (np.empty((n, S), np.uint8), np.empty(n, np.float64), np.empty(n, np.uint32))
-        kind = () if plain else (None if ploidy is None else ploidy.ctypes.data, max_ploidy)
-        self._chk(getattr(self.lib, name)(self.h, sv_type.ctypes.data, slot.ctypes.data, ok.ctypes.data, *kind, n, min_support, float(err),
-                                          *(a.ctypes.data for a in out)))
+        kind = (None if ploidy is None else ploidy.ctypes.data, max_ploidy) if ploidy_pair else ()
+        self._chk(fn(self.h, sv_type.ctypes.data, slot.ctypes.data, ok.ctypes.data, *kind, n, min_support, float(err), *(a.ctypes.data for a in out)))
         return out
 
     def genotype_cohort(self, sv_type, slot, ok, min_support, err):
         """Every row against every sample of the cohort matrix (svjg_genotype_cohort; ok bit 1 is ignored: the presence bytes decide).
         -> (gt[n, S], pl[n, S, 3], raw[n, S, 2], genotyped[n, S], boundary[n, S] = the items to recompute with svjg.genotype.exact_pl,
         site[n, 2] = NS and AC of each row)"""
-        return self._cohort_call("svjg_genotype_cohort", sv_type, slot, ok, None, 2, min_support, err)
+        return self._cohort_call(self.lib.svjg_genotype_cohort, sv_type, slot, ok, None, 2, min_support, err, ploidy_pair=False)
 
     def genotype_cohort_ploidy(self, sv_type, slot, ok, ploidy, max_ploidy, min_support, err):
         """Every row against every sample of the cohort matrix at a ploidy per item (svjg_genotype_cohort_ploidy): ploidy[n, S] in 0..max_ploidy,
         0 = the item is never genotyped.  -> (gt[n, S] = alt copies or 0xFF, pl[n, S, max_ploidy + 1] = PL_0..PL_P then zeros, raw[n, S, 2],
         genotyped[n, S], boundary[n, S] = the items to recompute with svjg.genotype.exact_pl_ploidy, site[n, 3] = NS, AN and AC of each row)"""
-        return self._cohort_call("svjg_genotype_cohort_ploidy", sv_type, slot, ok, ploidy, max_ploidy, min_support, err)
+        return self._cohort_call(self.lib.svjg_genotype_cohort_ploidy, sv_type, slot, ok, ploidy, max_ploidy, min_support, err, need_ploidy=True)
 
     def genotype_cohort_prior(self, sv_type, slot, ok, ploidy, max_ploidy, min_support, err):
         """The cohort call with an allele-frequency prior (svjg_genotype_cohort_prior).  ploidy: [n, S] in 0..max_ploidy, or None = every item
         diploid (max_ploidy must then be 2).  -> (gt[n, S] = alt copies of the POSTERIOR call or 0xFF, pl[n, S, max_ploidy + 1], raw[n, S, 2],
         genotyped[n, S], boundary[n, S] — pl, raw, genotyped and boundary as genotype_cohort / genotype_cohort_ploidy give them —, site[n, 3] =
         NS, AN, AC of the posterior calls, gq[n, S] (0xFF: none), af[n] (NaN: no estimate), em_steps[n] (bit 31: not converged))"""
-        return self._cohort_call("svjg_genotype_cohort_prior", sv_type, slot, ok, ploidy, max_ploidy, min_support, err)
+        return self._cohort_call(self.lib.svjg_genotype_cohort_prior, sv_type, slot, ok, ploidy, max_ploidy, min_support, err, prior=True)
 
     def cohort_qual(self, sv_type, slot, ok, ploidy, max_ploidy, err, theta=QUAL_THETA):
         """The site quality of every row against the cohort matrix: the exact allele-count posterior (svjg_cohort_qual).  ploidy: [n, S] in
         0..max_ploidy, or None = every item diploid (max_ploidy must then be 2).  -> (qual[n] = -10 log10 of the posterior of "no alt copy in the
         cohort", NaN where no item took part; mlac[n] = the allele count at the posterior's maximum; chroms[n] = the chromosomes that took part)"""
         n = len(sv_type)
-        S = getattr(self, "_cohort", (0, 0))[0]
-        max_ploidy = int(max_ploidy)
-        if not 0 <= max_ploidy <= 0xFFFFFFFF:
-            raise SvjgError("max_ploidy: 1..%d" % MAX_PLOIDY)
+        max_ploidy = _max_ploidy(max_ploidy)
         sv_type, slot, ok = _row_inputs(sv_type, slot, ok)
         if ploidy is not None:
-            ploidy = np.asarray(ploidy)
-            if ploidy.shape != (n, S) or (ploidy.size and (int(ploidy.min()) < 0 or int(ploidy.max()) > 255)):
-                raise SvjgError("ploidy: one value in 0..max_ploidy per (row, sample)")
-            ploidy = np.ascontiguousarray(ploidy, dtype=np.uint8)
+            ploidy = _ploidy_matrix(ploidy, n, self._cohort[0])
         out = (np.empty(n, np.float64), np.empty(n, np.uint32), np.empty(n, np.uint32))
         self._chk(self.lib.svjg_cohort_qual(self.h, sv_type.ctypes.data, slot.ctypes.data, ok.ctypes.data, None if ploidy is None else ploidy.ctypes.data,
                                             max_ploidy, n, float(err), float(theta), *(a.ctypes.data for a in out)))
@@ -630,20 +633,18 @@ class Context:
         site first, 0xFFFFFFFF behind them; sample s's site = the candidates present for s.  -> (gt[n, S, 2] = the pair or 0xFF, 0xFF, pl[n, S, 28],
         raw[n, S, 7], members[n, S] = bit j: candidate j took part (fewer than two: no site call), boundary[n, S] = the items to recompute with
         svjg.genotype.exact_pl_site, site[n, 6, 2] = NS_j and AC_j of every candidate over the items with a site call)"""
-        return self._sites_call("svjg_genotype_cohort_sites", slots, min_support, err)
+        return self._sites_call(self.lib.svjg_genotype_cohort_sites, slots, min_support, err, cohort=True)
 
     def genotype_cohort_sites_prior(self, slots, min_support, err):
         """genotype_cohort_sites with an allele-frequency prior over the samples of a site (svjg_genotype_cohort_sites_prior).  -> the six arrays of
         genotype_cohort_sites, bit for bit, and (sgt[n, S, 2] = the POSTERIOR call in the item's member numbering or 0xFF, 0xFF, sgq[n, S] (0xFF:
         none), af[n, 7] = the frequencies of the reference and the six candidates (NaN: no estimate), em_steps[n] (bit 31: not converged),
         psite[n, 6, 2] = NS_j and AC_j of the posterior calls)"""
-        return self._sites_call("svjg_genotype_cohort_sites_prior", slots, min_support, err)
+        return self._sites_call(self.lib.svjg_genotype_cohort_sites_prior, slots, min_support, err, cohort=True, prior=True)
 
     def set_rows(self, sv_type, slot, ok):
         """the VCF rows' input arrays of genotype(), left on the device for run_resident()"""
-        sv_type = np.ascontiguousarray(sv_type, dtype=np.uint8)
-        slot = np.ascontiguousarray(slot, dtype=np.uint32)
-        ok = np.ascontiguousarray(ok, dtype=np.uint8)
+        sv_type, slot, ok = _row_inputs(sv_type, slot, ok)
         self._n_rows = len(sv_type)
         self._chk(self.lib.svjg_set_rows(self.h, sv_type.ctypes.data, slot.ctypes.data, ok.ctypes.data, self._n_rows))
 
@@ -652,13 +653,8 @@ class Context:
         if not n:
             self.last_boundary = np.zeros(0, np.uint8)
             return np.zeros(0, np.uint8), np.zeros((0, 3), np.int32), np.zeros((0, 2), np.uint32), np.zeros(0, np.uint8)
-
-        def view(ptr, count, dt):
-            a = np.frombuffer((ctypes.c_char * (count * np.dtype(dt).itemsize)).from_address(ptr.value), dtype=dt)
-            a.flags.writeable = False
-            return a
-        self.last_boundary = view(p[4], n, np.uint8)
-        return view(p[0], n, np.uint8), view(p[1], n * 3, np.int32).reshape(n, 3), view(p[2], n * 2, np.uint32).reshape(n, 2), view(p[3], n, np.uint8)
+        self.last_boundary = _view(p[4], n, np.uint8)
+        return _view(p[0], n, np.uint8), _view(p[1], n * 3, np.int32).reshape(n, 3), _view(p[2], n * 2, np.uint32).reshape(n, 2), _view(p[3], n, np.uint8)
 
     def run_resident(self, min_support, err, base_offset=0):
         """One whole pass with one host wait (svjg_run_resident): zero the counts, classify the uploaded text, all-reduce the

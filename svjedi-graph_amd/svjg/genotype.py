@@ -4,6 +4,7 @@ Mirrors predict-genotype.py's decision_vcf (:89-279) for everything that is file
 (:281-338) and the presence gate (:216) run on the GPU.
 """
 import functools
+from typing import NamedTuple
 
 import numpy as np
 
@@ -359,23 +360,27 @@ def write_vcf_ploidy(out_path, rows, ploidy, gt, pl, raw, done):
     return n_done[0]
 
 
-def apply_boundary_guard_ploidy(rows, ploidy, pl, raw, done, boundary, err):
-    """-> pl with the flagged rows recomputed, number of flagged rows"""
-    return pl, recompute_flagged(rows.sv_type, pl, raw, done, boundary, err, ploidy)
+def _open_call(vcf_path, slot_of, slot_is_presence, min_support, err, native=False):
+    """The opening of every single-sample driver: the rows (open_rows; native False: the Python rows) and _call_args -> (rows, min_support, the err
+    to call with, check); check(genotyped) after the call: "math domain error" if err lies outside (0, 1) and any row was genotyped
+    (predict-genotype.py:295-297: the reference dies at the first genotyped row)"""
+    rows = open_rows(vcf_path, slot_of, slot_is_presence, native)
+    min_support, call_err, bad_err = _call_args(min_support, err)
+
+    def check(done):
+        if bad_err and np.asarray(done).any():
+            raise ValueError("math domain error")
+    return rows, min_support, call_err, check
 
 
 def genotype_with_counts_ploidy(ctx, vcf_path, slot_of, out_path, min_support, err, slot_is_presence, ploidy, ploidy_file):
     """genotype_with_counts with --ploidy and / or --ploidy-file: the Python rows, svjg_genotype_ploidy, the writer above"""
     regions = load_ploidy_file(ploidy_file) if ploidy_file is not None else ()       # (raises before any output exists)
-    if not isinstance(slot_of, dict):
-        slot_of = {k: i for i, k in enumerate(slot_of)}
-    rows = VcfRows(vcf_path, slot_of, slot_is_presence)
+    rows, min_support, call_err, check = _open_call(vcf_path, slot_of, slot_is_presence, min_support, err)
     pld = rows_ploidy(rows, ploidy, regions)
-    min_support, call_err, bad_err = _call_args(min_support, err)
     gt, pl, raw, done, boundary = ctx.genotype_ploidy(rows.sv_type, rows.slot, rows.ok, pld, min_support, call_err)
-    if bad_err and done.any():
-        raise ValueError("math domain error")
-    pl, _ = apply_boundary_guard_ploidy(rows, pld, pl, raw, done, boundary, err)
+    check(done)
+    recompute_flagged(rows.sv_type, pl, raw, done, boundary, err, pld)
     return write_vcf_ploidy(out_path, rows, pld, gt, pl, raw, done)
 
 
@@ -388,6 +393,12 @@ SITE_FORMAT_LINES = (
     '##FORMAT=<ID=SGT,Number=1,Type=String,Description="Joint genotype of the insertions sharing this position: allele 0 is the reference, allele i the insertion with SAL=i">\n'
     '##FORMAT=<ID=SAL,Number=1,Type=Integer,Description="Allele number of this insertion in SGT">\n'
 )
+
+
+def check_single_options(ploidy=None, ploidy_file=None, joint_ins=False):
+    """The rules between the options of a single-sample run (run, genotype_with_counts, predict-genotype.py): ValueError with the rule's text"""
+    if joint_ins and (ploidy is not None or ploidy_file is not None):
+        raise ValueError(JOINT_INS_PLOIDY)
 
 
 def site_genotypes(K):
@@ -490,7 +501,8 @@ def write_vcf_joint(out_path, rows, gt, pl, raw, done, member):
     def columns(v):
         if not (done[v] and v in member):
             return plain(v)
-        return ["GT:DP:AD:PL:SGT:SAL", _member_column(int(rows.sv_type[v]), *member[v][:2], int(raw[v, 0]), int(raw[v, 1]), *member[v][2:])]
+        g, pl3, sgt, sal = member[v]
+        return ["GT:DP:AD:PL:SGT:SAL", _member_column(int(rows.sv_type[v]), g, pl3, int(raw[v, 0]), int(raw[v, 1]), sgt, sal)]
     _write_rows(out_path, rows, FORMAT_HEADER.replace(_PL_LINE, _PL_LINE + SITE_FORMAT_LINES), columns)
     return n_done[0]
 
@@ -498,13 +510,9 @@ def write_vcf_joint(out_path, rows, gt, pl, raw, done, member):
 def genotype_with_counts_joint(ctx, vcf_path, slot_of, out_path, min_support, err, slot_is_presence):
     """genotype_with_counts with --joint-ins: the Python rows, the ordinary diploid call on all of them, then ONE svjg_genotype_sites call
     over the sites of form_sites; the members' GT and PL become the site call's projection (project_cohort_sites at S = 1), DP and AD stay the row's own"""
-    if not isinstance(slot_of, dict):
-        slot_of = {k: i for i, k in enumerate(slot_of)}
-    rows = VcfRows(vcf_path, slot_of, slot_is_presence)
-    min_support, call_err, bad_err = _call_args(min_support, err)
+    rows, min_support, call_err, check = _open_call(vcf_path, slot_of, slot_is_presence, min_support, err)
     gt, pl, raw, done = ctx.genotype(rows.sv_type, rows.slot, rows.ok, min_support, call_err)
-    if bad_err and np.asarray(done).any():
-        raise ValueError("math domain error")
+    check(done)
     pl, _ = apply_boundary_guard(ctx, rows, pl, raw, done, err)
     sites, skipped = form_sites(rows, done)
     _report_skipped(skipped)
@@ -611,63 +619,78 @@ def cohort_info(info, ns, ac, an=None, em=None, qual=None):
     return ";".join(keep)
 
 
+class CohortCalls(NamedTuple):
+    """What a cohort call gives over all rows (genotype_cohort_rows): gt, done: [n, S]; pl: [n, S, >= 3]; raw: [n, S, 2]; site: [n, 2] = NS, AC or
+    [n, 3] = NS, AN, AC.  With the prior (--cohort-prior) gt and site are the posterior calls', and gq[n, S], af[n], em_steps[n] are there"""
+    gt: np.ndarray; pl: np.ndarray; raw: np.ndarray; done: np.ndarray; site: np.ndarray
+    gq: np.ndarray = None; af: np.ndarray = None; em_steps: np.ndarray = None
+
+
+class JointMember(NamedTuple):
+    """A row that is a member of a site for at least one sample (cohort_joint_sites), one entry per sample: covered[S]; g[S] and pl3[S, 3], the
+    projection of the sample's site call; a[S], b[S], that call; sal[S], the row's allele number in it.  With --joint-prior g, a and b are the
+    POSTERIOR site call's and sgq[S] is there"""
+    covered: np.ndarray; g: np.ndarray; pl3: np.ndarray; a: np.ndarray; b: np.ndarray; sal: np.ndarray
+    sgq: np.ndarray = None
+
+
+class JointSites(NamedTuple):
+    """cohort_joint_sites' answer: site, the plain call's with the candidate rows' NS and AC replaced; joint: row -> JointMember; em (--joint-prior):
+    row -> (p_j, not_converged) of the site's EM for the rows of joint"""
+    site: np.ndarray; joint: dict
+    em: dict = None
+
+
 def _joint_columns(rows, raw, plain, joint):
-    """columns(v) of a --cohort --joint-ins run from the plain cohort's: a row of `joint` (row -> (covered[S], g[S], pl3[S, 3], a[S], b[S], sal[S]),
-    cohort_joint_sites) prints GT:DP:AD:PL:SGT:SAL — a covered sample what write_vcf_joint prints (the projection of its site call; DP and AD stay
-    the row's own), every other sample its independent column and `:.:.` —; every other row is the plain one.  --joint-prior: a seventh array,
-    sgq[S], behind the six (g, a and b are then the POSTERIOR site call's): GT:DP:AD:PL:SGT:SAL:SGQ, SGQ `.` beside `./.`, and `:.:.:.` behind a
-    sample without a site"""
+    """columns(v) of a --cohort --joint-ins run from the plain cohort's: a row of `joint` (row -> JointMember) prints GT:DP:AD:PL:SGT:SAL — a
+    covered sample what write_vcf_joint prints (DP and AD stay the row's own), every other sample its independent column and `:.:.` —; every other
+    row is the plain one.  With sgq (--joint-prior): GT:DP:AD:PL:SGT:SAL:SGQ, SGQ `.` beside `./.`, and `:.:.:.` behind a sample without a site"""
     raw = np.asarray(raw)
 
     def columns(v):
         cols = plain(v)
         if v not in joint:
             return cols
-        covered, g, p3, a, b, sal, *more = (x.tolist() for x in joint[v])
+        m = joint[v]
+        covered, g, p3, a, b, sal = (x.tolist() for x in m[:6])
         t = int(rows.sv_type[v])
         out = [_member_column(t, g[s], p3[s], int(raw[v, s, 0]), int(raw[v, s, 1]), _sgt_text(a[s], b[s]), sal[s]) if covered[s]
                else col + ":.:." for s, col in enumerate(cols[1:])]
-        if not more:
+        if m.sgq is None:
             return ["GT:DP:AD:PL:SGT:SAL"] + out
-        sgq = more[0]
+        sgq = m.sgq.tolist()
         return ["GT:DP:AD:PL:SGT:SAL:SGQ"] + [col + (":." if not covered[s] or a[s] == NO_CALL else ":%d" % sgq[s]) for s, col in enumerate(out)]
     return columns
 
 
-def write_vcf_cohort(out_path, rows, names, gt, pl, raw, done, site, ploidy=None, gq=None, af=None, em_steps=None, joint=None, qual=None, joint_em=None):
-    """The one cohort writer: write_vcf with one column per sample (gt, done: [n, S]; pl: [n, S, >= 3]; raw: [n, S, 2]), the site tags' INFO lines
-    in front of the header and the tags in INFO; site: [n, 2] = NS, AC or [n, 3] = NS, AN, AC.  ploidy ([n, S]; None: diploid arrays, `Number=3`):
-    every item in write_vcf_ploidy's forms (pl: [n, S, >= P + 1]) and `Number=G` in the PL header line.  --cohort-prior: gq[n, S], one more
-    FORMAT field, GQ; af[n] and em_steps[n], EMAF / EMNC in INFO.  joint (--joint-ins; cohort_joint_sites): the rows that are members of a site
-    for at least one sample, printed by _joint_columns, and SITE_FORMAT_LINES behind the PL line.  qual (--cohort-qual; cohort_qual_rows): (svq[n],
-    mlac[n], chroms[n]), SVQ / MLAC / MLAF behind the other tags in INFO and their three header lines; the QUAL column stays the input's.
-    joint_em (--joint-prior; cohort_joint_sites with prior): row -> (p_j, not_converged) of the site's EM for the member rows, EMAF / EMNC in their
-    INFO under the --cohort-prior header lines, and SITE_PRIOR_FORMAT_LINE behind SAL's.
-    -> the number of genotyped rows of every sample"""
-    columns, n_done = _item_columns(rows, ploidy, gt, pl, raw, done, gq)
+def write_vcf_cohort(out_path, rows, names, calls, ploidy=None, joint=None, qual=None):
+    """The one cohort writer: write_vcf with one column per sample of `calls` (CohortCalls), the site tags' INFO lines in front of the header and
+    the tags in INFO.  ploidy ([n, S]; None: diploid arrays, `Number=3`): every item in write_vcf_ploidy's forms and `Number=G` in the PL header
+    line.  calls.gq: one more FORMAT field, GQ; calls.af and em_steps: EMAF / EMNC in INFO.  joint (JointSites): its site words stand for the
+    calls', the member rows are printed by _joint_columns under SITE_FORMAT_LINES; joint.em: EMAF / EMNC in the member rows' INFO, and
+    SITE_PRIOR_FORMAT_LINE behind SAL's.  qual (cohort_qual_rows): (svq[n], mlac[n], chroms[n]), SVQ / MLAC / MLAF behind the other tags in INFO
+    and their header lines; the QUAL column stays the input's.  -> the number of genotyped rows of every sample"""
+    columns, n_done = _item_columns(rows, ploidy, calls.gt, calls.pl, calls.raw, calls.done, calls.gq)
     header = FORMAT_HEADER if ploidy is None else FORMAT_HEADER.replace(_PL_3, _PL_G)
+    site, em = calls.site, None                                  # em: row -> (frequency, not_converged) for the rows that have an EM
     if joint is not None:
-        columns = _joint_columns(rows, raw, columns, joint)
-        header = header.replace(_PL_LINE, _PL_LINE + SITE_FORMAT_LINES + (SITE_PRIOR_FORMAT_LINE if joint_em is not None else ""))
-    if gq is not None:
+        site, em = joint.site, joint.em
+        columns = _joint_columns(rows, calls.raw, columns, joint.joint)
+        header = header.replace(_PL_LINE, _PL_LINE + SITE_FORMAT_LINES + (SITE_PRIOR_FORMAT_LINE if em is not None else ""))
+    if calls.gq is not None:
         header = header.replace("#CHROM\t", _GQ_LINE + "#CHROM\t")
-    header = COHORT_INFO_LINES + (COHORT_PRIOR_INFO_LINES if af is not None or joint_em is not None else "") + (COHORT_QUAL_INFO_LINES if qual is not None else "") + header.replace("\tFORMAT\tSAMPLE\n", "\tFORMAT\t" + "\t".join(names) + "\n")
-    an = np.shape(site)[1] == 3
-    _write_rows(out_path, rows, header, columns,
-                lambda v, info: cohort_info(info, int(site[v, 0]), int(site[v, -1]), int(site[v, 1]) if an else None,
-                                            (float(af[v]), bool(int(em_steps[v]) & EM_NOT_CONVERGED)) if af is not None else joint_em.get(v) if joint_em is not None else None,
-                                            None if qual is None else (float(qual[0][v]), int(qual[1][v]), int(qual[2][v]))))
+    if calls.af is not None:
+        not_converged = (np.asarray(calls.em_steps).astype(np.int64) & EM_NOT_CONVERGED) != 0
+        em = dict(enumerate(zip(np.asarray(calls.af, dtype=np.float64).tolist(), not_converged.tolist())))
+    info_lines = COHORT_INFO_LINES + (COHORT_PRIOR_INFO_LINES if em is not None else "") + (COHORT_QUAL_INFO_LINES if qual is not None else "")
+    header = info_lines + header.replace("\tFORMAT\tSAMPLE\n", "\tFORMAT\t" + "\t".join(names) + "\n")
+    has_an = np.shape(site)[1] == 3
+
+    def info(v, text):
+        return cohort_info(text, int(site[v, 0]), int(site[v, -1]), int(site[v, 1]) if has_an else None, None if em is None else em.get(v),
+                           None if qual is None else (float(qual[0][v]), int(qual[1][v]), int(qual[2][v])))
+    _write_rows(out_path, rows, header, columns, info)
     return n_done
-
-
-def write_vcf_cohort_ploidy(out_path, rows, names, ploidy, gt, pl, raw, done, site):
-    """write_vcf_cohort at per-sample ploidy, in the argument order of its earlier writer"""
-    return write_vcf_cohort(out_path, rows, names, gt, pl, raw, done, site, ploidy)
-
-
-def write_vcf_cohort_prior(out_path, rows, names, ploidy, gt, pl, raw, done, site, gq, af, em_steps):
-    """write_vcf_cohort with the posterior calls, in the argument order of its earlier writer"""
-    return write_vcf_cohort(out_path, rows, names, gt, pl, raw, done, site, ploidy, gq, af, em_steps)
 
 
 def cohort_chunk_rows(n_samples, max_ploidy=None, prior=False):
@@ -677,39 +700,32 @@ def cohort_chunk_rows(n_samples, max_ploidy=None, prior=False):
     return max(1, COHORT_CALL_BYTES // (item * max(1, int(n_samples)) + (46 if prior else 0)))
 
 
-def cohort_ploidy_chunk_rows(n_samples, max_ploidy):
-    """rows per svjg_genotype_cohort_ploidy call"""
-    return cohort_chunk_rows(n_samples, max_ploidy)
-
-
-def cohort_prior_chunk_rows(n_samples, max_ploidy):
-    """rows per svjg_genotype_cohort_prior call"""
-    return cohort_chunk_rows(n_samples, max_ploidy, True)
+def _join_chunks(parts):
+    """the tuples of the chunks of one call -> one list of arrays over all rows, field by field (a field that is None stays None)"""
+    return [None if parts[0][k] is None else np.concatenate([p[k] for p in parts]) for k in range(len(parts[0]))]
 
 
 def _cohort_rows(call, rows, step, empty, min_support, err, ploidy=None):
-    """The one cohort driver: the rows of a VcfRows against the context's cohort matrix in chunks of `step` rows, call(lo, hi, min_support,
-    err) -> (gt, pl, raw, done, boundary, site) per chunk -> (gt, pl, raw, done, site) over all rows (empty: the same for no row at all), the
-    flagged items recomputed (the GT does not depend on the PL integers: the site words stay as the kernel gave them).  Whatever a call
-    returns behind site (--cohort-prior: gq, af, em_steps) is joined over the chunks and returned behind site as well"""
+    """The one cohort driver: the rows of a VcfRows against the context's cohort matrix in chunks of `step` rows, call(lo, hi, min_support, err) ->
+    the context's tuple (gt, pl, raw, done, boundary, site[, gq, af, em_steps]) per chunk -> CohortCalls over all rows (empty: the same for no row
+    at all), the flagged items recomputed (the GT does not depend on the PL integers: the site words stay as the kernel gave them)"""
     min_support, call_err, bad_err = _call_args(min_support, err)
     parts = []
     for at in range(0, len(rows.sv_type), step):
-        gt, pl, raw, done, boundary, site, *more = call(at, at + step, min_support, call_err)
+        got = call(at, at + step, min_support, call_err)
+        gt, pl, raw, done, boundary, site = got[:6]
         if bad_err and done.any():
             raise ValueError("math domain error")               # (as genotype_with_counts)
         recompute_flagged(rows.sv_type[at:at + step], pl, raw, done, boundary, err, None if ploidy is None else ploidy[at:at + step])
-        parts.append((gt, pl, raw, done, site, *more))
-    if not parts:
-        return empty
-    return tuple(np.concatenate([p[k] for p in parts]) for k in range(len(parts[0])))
+        parts.append(CohortCalls(gt, pl, raw, done, site, *got[6:]))
+    return CohortCalls(*_join_chunks(parts)) if parts else empty
 
 
 def genotype_cohort_rows(ctx, rows, n_samples, min_support, err, ploidy=None, prior=False, step=None):
-    """The cohort call over all rows.  ploidy None and no prior: svjg_genotype_cohort -> (gt (3: no call), pl[n, S, 3], raw, done, site[n, 2] = NS,
-    AC).  ploidy[n, S]: svjg_genotype_cohort_ploidy -> (gt (0xFF: no call), pl[n, S, max_ploidy + 1], raw, done, site[n, 3] = NS, AN, AC);
-    max_ploidy = the matrix's maximum, at least 1.  prior: svjg_genotype_cohort_prior, ploidy[n, S] or None (diploid) -> gt = the posterior calls
-    (0xFF: none), site of them, and behind site gq[n, S], af[n], em_steps[n].  step: rows per call (None: what fits 1 GiB)"""
+    """The cohort call over all rows -> CohortCalls.  ploidy None and no prior: svjg_genotype_cohort, gt (3: no call), pl[n, S, 3], site[n, 2] = NS,
+    AC.  ploidy[n, S]: svjg_genotype_cohort_ploidy, gt (0xFF: no call), pl[n, S, max_ploidy + 1], site[n, 3] = NS, AN, AC; max_ploidy = the
+    matrix's maximum, at least 1.  prior: svjg_genotype_cohort_prior, ploidy[n, S] or None (diploid), gt = the posterior calls (0xFF: none), site
+    of them, and gq[n, S], af[n], em_steps[n].  step: rows per call (None: what fits 1 GiB)"""
     S = int(n_samples)
     if ploidy is not None:
         ploidy = np.ascontiguousarray(ploidy, dtype=np.uint8)
@@ -721,18 +737,11 @@ def genotype_cohort_rows(ctx, rows, n_samples, min_support, err, ploidy=None, pr
             return ctx.genotype_cohort(rows.sv_type[lo:hi], rows.slot[lo:hi], rows.ok[lo:hi], ms, e)
         fn = ctx.genotype_cohort_prior if prior else ctx.genotype_cohort_ploidy
         return fn(rows.sv_type[lo:hi], rows.slot[lo:hi], rows.ok[lo:hi], None if ploidy is None else ploidy[lo:hi], max_ploidy, ms, e)
-    empty = (np.zeros((0, S), np.uint8), np.zeros((0, S, max_ploidy + 1), np.int64), np.zeros((0, S, 2), np.uint32), np.zeros((0, S), np.uint8),
-             np.zeros((0, 2 if plain else 3), np.uint32))
-    if prior:
-        empty += (np.zeros((0, S), np.uint8), np.zeros(0, np.float64), np.zeros(0, np.uint32))
+    empty = CohortCalls(np.zeros((0, S), np.uint8), np.zeros((0, S, max_ploidy + 1), np.int64), np.zeros((0, S, 2), np.uint32), np.zeros((0, S), np.uint8),
+                        np.zeros((0, 2 if plain else 3), np.uint32), *((np.zeros((0, S), np.uint8), np.zeros(0, np.float64), np.zeros(0, np.uint32)) if prior else ()))
     if step is None:
         step = cohort_chunk_rows(S, None if plain else max_ploidy, prior)
     return _cohort_rows(call, rows, int(step), empty, min_support, err, ploidy)
-
-
-def genotype_cohort_prior_rows(ctx, rows, n_samples, ploidy, min_support, err, step=None):
-    """genotype_cohort_rows with the prior"""
-    return genotype_cohort_rows(ctx, rows, n_samples, min_support, err, ploidy, True, step)
 
 
 # ---- cohort at per-sample ploidy (--cohort LIST --cohort-ploidy FILE): the file and the ploidy matrix of svjg_genotype_cohort_ploidy ----
@@ -800,6 +809,7 @@ COHORT_QUAL_INFO_LINES = (
 )
 COHORT_QUAL_THETA = 1e-3           # the default of --cohort-theta
 COHORT_QUAL_THETA_MAX = 0.05       # svjg.h: theta of svjg_cohort_qual lies in (0, 0.05]
+COHORT_THETA_RANGE = "--cohort-theta: a value in (0, %g]" % COHORT_QUAL_THETA_MAX
 JOINT_INS_QUAL = "--joint-ins cannot be combined with --cohort-qual: the site model there is multi-allelic"
 
 
@@ -816,7 +826,7 @@ def cohort_qual_rows(ctx, rows, n_samples, ploidy, err, theta=COHORT_QUAL_THETA,
                              max_ploidy, call_err, theta) for at in range(0, len(rows.sv_type), int(step))]
     if not parts:
         return np.zeros(0, np.float64), np.zeros(0, np.uint32), np.zeros(0, np.uint32)
-    return tuple(np.concatenate([p[k] for p in parts]) for k in range(3))
+    return tuple(_join_chunks(parts))
 
 
 # ---- cohort calls for insertions that share a position (--cohort LIST --joint-ins [--joint-prior]): svjg_genotype_cohort_sites (svjg_genotype_cohort_sites_prior) behind the plain cohort call ----
@@ -868,26 +878,26 @@ def cohort_joint_sites(ctx, rows, gt, site, min_support, err, step=None, prior=F
     """Behind the plain cohort call (gt[n, S], site[n, 2] = NS, AC): the candidate sites at the VCF level — the INS rows with ok & 1 and a slot
     that share CHROM and POS text, 2..6 of them in file order (form_sites; more than six: skipped for every sample, one stderr line) —, ONE
     svjg_genotype_cohort_sites call over them (chunks of `step` sites, None: what fits 1 GiB), the flagged items recomputed with their own K'
-    (exact_pl_site), the projection.  -> (site with the candidate rows' NS and AC replaced: the kernel's sums over the covered samples plus the
-    independent calls of the others; joint: row -> (covered[S], g[S], pl3[S, 3], a[S], b[S], sal[S]) for the rows covered in at least one sample).
-    prior (--joint-prior): svjg_genotype_cohort_sites_prior instead — the PLs, and so the flagged items' recomputation, are the same; g, a, b and the
-    sums are the POSTERIOR calls', joint's tuples end with sgq[S], and a third value comes back: row -> (p_j, not_converged) for the rows of joint
-    (p_j: the EM's frequency of that row's allele, NaN where no item of the site took part)"""
+    (exact_pl_site), the projection.  -> JointSites: site with the candidate rows' NS and AC replaced (the kernel's sums over the covered samples
+    plus the independent calls of the others) and joint, the rows covered in at least one sample.  prior (--joint-prior): svjg_genotype_cohort_sites_prior
+    instead — the PLs, and so the flagged items' recomputation, are the same; g, a, b and the sums are the POSTERIOR calls', the members carry
+    sgq[S], and em is there (p_j: the EM's frequency of that row's allele, NaN where no item of the site took part)"""
     min_support, call_err, _ = _call_args(min_support, err)
     sites, skipped = form_sites(rows, ((rows.ok & 1) != 0) & (rows.slot != NONE))
     _report_skipped(skipped)
-    site, joint, em = np.array(site), {}, {}
+    site, joint, em = np.array(site), {}, {} if prior else None
     if not sites:
-        return (site, joint, em) if prior else (site, joint)
+        return JointSites(site, joint, em)
     slots = _site_slots(rows, sites)
     if step is None:
         step = cohort_sites_chunk(np.shape(gt)[1], prior)
     call = ctx.genotype_cohort_sites_prior if prior else ctx.genotype_cohort_sites
-    parts = [call(slots[at:at + step], min_support, call_err) for at in range(0, len(sites), int(step))]
-    s_gt, s_pl, s_raw, members, boundary, s_site, *post = (np.concatenate([p[k] for p in parts]) for k in range(len(parts[0])))
+    got = _join_chunks([call(slots[at:at + step], min_support, call_err) for at in range(0, len(sites), int(step))])
+    s_gt, s_pl, s_raw, members, boundary, s_site = got[:6]
     recompute_flagged_sites(s_pl, s_raw, boundary, ((members[..., None] >> np.arange(MAX_SITE_ALTS, dtype=np.uint8)) & 1).sum(axis=-1), err)
+    sgq = None
     if prior:
-        s_gt, sgq, af, em_steps, s_site = post                   # (the EM never reads PLs: the posterior calls stand as the kernel gave them)
+        s_gt, sgq, af, em_steps, s_site = got[6:]                # (the EM never reads PLs: the posterior calls stand as the kernel gave them)
     covered, g, pl3, sal = project_cohort_sites(s_gt, s_pl, members)
     k_of = np.repeat(np.arange(len(sites)), [len(m) for m in sites])
     j_of = np.concatenate([np.arange(len(m)) for m in sites])
@@ -899,10 +909,22 @@ def cohort_joint_sites(ctx, rows, gt, site, min_support, err, step=None, prior=F
     site[r_of, 1] = s_site[k_of, j_of, 1] + np.where(alone, own, 0).sum(axis=1)
     for c in np.flatnonzero(cov.any(axis=1)).tolist():
         k, j = k_of[c], j_of[c]
-        joint[int(r_of[c])] = (cov[c], g[k, :, j], pl3[k, :, j], s_gt[k, :, 0], s_gt[k, :, 1], sal[k, :, j]) + ((sgq[k],) if prior else ())
+        joint[int(r_of[c])] = JointMember(cov[c], g[k, :, j], pl3[k, :, j], s_gt[k, :, 0], s_gt[k, :, 1], sal[k, :, j], sgq[k] if prior else None)
         if prior:
             em[int(r_of[c])] = (float(af[k, 1 + j]), bool(int(em_steps[k]) & EM_NOT_CONVERGED))
-    return (site, joint, em) if prior else (site, joint)
+    return JointSites(site, joint, em)
+
+
+def check_cohort_options(ploidy_file=None, prior=False, joint_ins=False, joint_prior=False, qual=False, theta=COHORT_QUAL_THETA):
+    """The rules between the options of a cohort run (run_cohort, predict-genotype.py --cohort): ValueError with the first broken rule's text"""
+    if joint_ins and (ploidy_file is not None or prior):
+        raise ValueError(JOINT_INS_COHORT)
+    if joint_prior and not joint_ins:
+        raise ValueError(JOINT_PRIOR_NEEDS)
+    if qual and not 0.0 < theta <= COHORT_QUAL_THETA_MAX:
+        raise ValueError(COHORT_THETA_RANGE)
+    if joint_ins and qual:
+        raise ValueError(JOINT_INS_QUAL)
 
 
 def run_cohort(list_path, vcf_path, out_path, min_support=3, err=0.00005, device=0, ploidy_file=None, prior=False, joint_ins=False, qual=False,
@@ -921,15 +943,8 @@ def run_cohort(list_path, vcf_path, out_path, min_support=3, err=0.00005, device
     POSTERIOR site call and SGT that call, NS / AC / AN / AF come from the posterior calls, EMAF and EMNC follow them; every non-member row stays the
     plain cohort row.  -> the number of genotyped rows of every sample"""
     from . import capi, filter as flt
-    if joint_prior and not joint_ins:
-        raise ValueError(JOINT_PRIOR_NEEDS)                      # (before anything is read, asked of the device or written)
-    if joint_ins and (ploidy_file is not None or prior):
-        raise ValueError(JOINT_INS_COHORT)                       # (before anything is read, asked of the device or written)
-    if joint_ins and qual:
-        raise ValueError(JOINT_INS_QUAL)
-    if qual and not 0.0 < theta <= COHORT_QUAL_THETA_MAX:
-        raise ValueError("theta: a value in (0, %g]" % COHORT_QUAL_THETA_MAX)
-    samples = load_cohort_list(list_path)                        # (raises before any output exists)
+    check_cohort_options(ploidy_file, prior, joint_ins, joint_prior, qual, theta)     # (before anything is read, asked of the device or written)
+    samples = load_cohort_list(list_path)                       # (raises before any output exists)
     names = [name for name, _ in samples]
     regions = load_cohort_ploidy_file(ploidy_file, names) if ploidy_file is not None else None   # (so does this)
     loaded = []
@@ -937,22 +952,19 @@ def run_cohort(list_path, vcf_path, out_path, min_support=3, err=0.00005, device
         got = flt.read_handoff(path)                             # left by our filter-alignments.py for exactly this file, else None
         loaded.append(got if got is not None else capi.count_informative_json(path))
     keys, per = cohort_union(loaded)
-    rows = VcfRows(vcf_path, {k: i for i, k in enumerate(keys)})
+    rows = open_rows(vcf_path, keys, native=False)
     ploidy = cohort_ploidy_matrix(rows, regions) if regions is not None else None
     ctx = capi.Context(device)
     try:
         ctx.cohort_alloc(len(samples), len(keys))
         for s, (slots, counts) in enumerate(per):
             ctx.cohort_set_counts(s, slots, counts)
-        gt, pl, raw, done, site, *em = genotype_cohort_rows(ctx, rows, len(samples), min_support, err, ploidy, prior)   # (em: gq, af, em_steps with the prior)
-        joint = joint_em = None
-        if joint_ins:
-            site, joint, *post = cohort_joint_sites(ctx, rows, gt, site, min_support, err, prior=joint_prior)
-            joint_em = post[0] if joint_prior else None
+        calls = genotype_cohort_rows(ctx, rows, len(samples), min_support, err, ploidy, prior)
+        joint = cohort_joint_sites(ctx, rows, calls.gt, calls.site, min_support, err, prior=joint_prior) if joint_ins else None
         site_qual = cohort_qual_rows(ctx, rows, len(samples), ploidy, err, theta) if qual else None
     finally:
         ctx.close()
-    n_done = write_vcf_cohort(out_path, rows, names, gt, pl, raw, done, site, ploidy, *em, joint=joint, qual=site_qual, joint_em=joint_em)
+    n_done = write_vcf_cohort(out_path, rows, names, calls, ploidy, joint, site_qual)
     for name, n in zip(names, n_done):
         print("Genotyped svs (%s): %d" % (name, n))
     return n_done
@@ -964,18 +976,16 @@ def write_vcf(out_path, rows, gt, pl, raw, done):
     return n_done[0]
 
 
-def open_rows(vcf_path, slot_of, slot_is_presence=False):
+def open_rows(vcf_path, slot_of, slot_is_presence=False, native=True):
     """The rows of the VCF with their count slots: the native reader (libsvjg_host, svjg_vcf_load) for ordinary files, the
     Python rows above (the semantics, and what raises the reference's exceptions) for everything it declines.
     slot_of: dict key -> slot, or a list of keys (slot = index; a repeated key: the last one wins, like json.load).
-    SVJG_PY_VCF=1 forces the Python rows."""
+    SVJG_PY_VCF=1, or native False, forces the Python rows."""
     import os
     from . import capi
-    if not os.environ.get("SVJG_PY_VCF"):
-        if isinstance(slot_of, dict):
-            rows = capi.vcf_load_native(vcf_path, slot_of.keys(), np.fromiter(slot_of.values(), dtype=np.uint32, count=len(slot_of)), slot_is_presence)
-        else:
-            rows = capi.vcf_load_native(vcf_path, slot_of, None, slot_is_presence)
+    if native and not os.environ.get("SVJG_PY_VCF"):
+        slots = np.fromiter(slot_of.values(), dtype=np.uint32, count=len(slot_of)) if isinstance(slot_of, dict) else None
+        rows = capi.vcf_load_native(vcf_path, slot_of, slots, slot_is_presence)      # (a dict gives its keys)
         if rows is not None:
             return rows
     if not isinstance(slot_of, dict):
@@ -988,17 +998,14 @@ def genotype_with_counts(ctx, vcf_path, slot_of, out_path, min_support=3, err=0.
     """Counts already live in the context (fused path, or set_counts): parse, run the kernel, write.  ploidy (1..8, every row) and / or
     ploidy_file (per contig or region, load_ploidy_file): genotype_with_counts_ploidy; joint_ins (insertions that share a position are
     genotyped together, diploid only): genotype_with_counts_joint; with none of them, the diploid path below."""
-    if joint_ins and (ploidy is not None or ploidy_file is not None):
-        raise ValueError(JOINT_INS_PLOIDY)                       # (before anything is asked of the device or written)
+    check_single_options(ploidy, ploidy_file, joint_ins)         # (before anything is asked of the device or written)
     if joint_ins:
         return genotype_with_counts_joint(ctx, vcf_path, slot_of, out_path, min_support, err, slot_is_presence)
     if ploidy is not None or ploidy_file is not None:
         return genotype_with_counts_ploidy(ctx, vcf_path, slot_of, out_path, min_support, err, slot_is_presence, ploidy, ploidy_file)
-    rows = open_rows(vcf_path, slot_of, slot_is_presence)
-    min_support, call_err, bad_err = _call_args(min_support, err)
+    rows, min_support, call_err, check = _open_call(vcf_path, slot_of, slot_is_presence, min_support, err, native=True)
     gt, pl, raw, done = ctx.genotype(rows.sv_type, rows.slot, rows.ok, min_support, call_err, reuse_outputs=True)   # views: written out right away
-    if bad_err and np.asarray(done).any():
-        raise ValueError("math domain error")                   # (predict-genotype.py:295-297: the reference dies at the first genotyped row)
+    check(done)
     pl, _ = apply_boundary_guard(ctx, rows, pl, raw, done, err)
     if isinstance(rows, VcfRows):
         return write_vcf(out_path, rows, gt, pl, raw, done)
@@ -1011,8 +1018,7 @@ def genotype_with_counts(ctx, vcf_path, slot_of, out_path, min_support=3, err=0.
 def run(json_path, vcf_path, out_path, min_support=3, err=0.00005, device=0, ploidy=None, ploidy_file=None, joint_ins=False):
     """predict-genotype.py main(): counts come from the informative-alignment JSON."""
     from . import capi, filter as flt
-    if joint_ins and (ploidy is not None or ploidy_file is not None):
-        raise ValueError(JOINT_INS_PLOIDY)
+    check_single_options(ploidy, ploidy_file, joint_ins)
     got = flt.read_handoff(json_path)                            # left by our filter-alignments.py for exactly this file, else None
     if got is None:
         got = capi.count_informative_json(json_path)             # len() of the two lists of every key (:219-226)

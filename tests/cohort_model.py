@@ -46,4 +46,4 @@ class Cohort:
     def assemble(self, out_path):
         """the merged file from the reference's columns -> the per-sample numbers of genotyped rows"""
         from svjg import genotype
-        return genotype.write_vcf_cohort(out_path, self.rows, self.names, self.gt, self.pl, self.raw, self.done, self.site)
+        return genotype.write_vcf_cohort(out_path, self.rows, self.names, genotype.CohortCalls(self.gt, self.pl, self.raw, self.done, self.site))

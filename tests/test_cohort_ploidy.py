@@ -145,7 +145,7 @@ def test_chunk_rows_keep_a_call_under_one_gib():
     for mp in (1, 2, 8):
         item = 8 * (mp + 1) + 12
         for S in (1, 2, 64, 3000, 10**7, 10**9):
-            n = genotype.cohort_ploidy_chunk_rows(S, mp)
+            n = genotype.cohort_chunk_rows(S, mp)
             assert n >= 1 and (n * S * item <= 1 << 30 or n == 1) and (n + 1) * S * item > 1 << 30
 
 
@@ -168,7 +168,7 @@ def test_writer_text_of_a_mixed_row(tmp_path):
     pl[0, 5] = (90, 30, 0, 40)
     site = np.array([[3, 6, 4]], np.uint32)                       # NS, AN = 1 + 2 + 3, AC = 1 + 1 + 2
     out = tmp_path / "out.vcf"
-    assert genotype.write_vcf_cohort_ploidy(str(out), rows, names, ploidy, gt, pl, raw, done, site) == [0, 1, 1, 1, 0, 1]
+    assert genotype.write_vcf_cohort(str(out), rows, names, genotype.CohortCalls(gt, pl, raw, done, site), ploidy) == [0, 1, 1, 1, 0, 1]
     lines = out.read_text().split("\n")
     assert lines[-1] == "" and lines[0] == "##fileformat=VCFv4.2"
     assert [ln.split(",")[0] for ln in lines[1:5]] == ["##INFO=<ID=NS", "##INFO=<ID=AN", "##INFO=<ID=AC", "##INFO=<ID=AF"]

@@ -195,9 +195,10 @@ def test_driver_joins_what_a_call_returns_behind_site():
     assert len(out) == 8 and out[0].shape == (n, S) and out[4][:, 0].tolist() == [0] * 4 + [4] * 4 + [8] * 2
     assert (out[5] == 7).all() and out[6].tolist() == list(range(n)) and out[7].tolist() == [0] * 4 + [4] * 4 + [8] * 2
     five = genotype._cohort_rows(lambda lo, hi, ms, e: call(lo, hi, ms, e)[:6], rows, 4, None, 3, 5e-5)
-    assert len(five) == 5                                          # the calls without a prior: as before
-    assert genotype.cohort_prior_chunk_rows(64, 2) * (64 * 37 + 46) <= 1 << 30 < (genotype.cohort_prior_chunk_rows(64, 2) + 1) * (64 * 37 + 46)
-    assert genotype.cohort_prior_chunk_rows(10**9, 8) == 1
+    assert five.site.shape == (n, 3) and five.gq is None and five.af is None and five.em_steps is None      # the calls without a prior: nothing behind site
+    assert all(np.array_equal(x, y) for x, y in zip(five[:5], out[:5]))
+    assert genotype.cohort_chunk_rows(64, 2, True) * (64 * 37 + 46) <= 1 << 30 < (genotype.cohort_chunk_rows(64, 2, True) + 1) * (64 * 37 + 46)
+    assert genotype.cohort_chunk_rows(10**9, 8, True) == 1
 
 
 # ---- the writer ----
@@ -235,7 +236,7 @@ def test_writer_over_the_reference_made_fixtures(golden, tmp_path, which):
     assert len(has) >= 3
     steps[has[1]] |= FLAG                                          # (no row of these fixtures reaches the cap: one is marked by hand)
     out = str(tmp_path / "out.vcf")
-    n_done = genotype.write_vcf_cohort_prior(out, co.rows, co.names, ploidy, m["gt"], co.pl, co.raw, co.done, M.site_of(m["gt"], ploidy), m["gq"], m["f_hi"], steps)
+    n_done = genotype.write_vcf_cohort(out, co.rows, co.names, genotype.CohortCalls(m["gt"], co.pl, co.raw, co.done, M.site_of(m["gt"], ploidy), m["gq"], m["f_hi"], steps), ploidy)
     assert n_done == co.genotyped
     lines = open(out).read().split("\n")
     head = [ln for ln in lines if ln.startswith("##")]
@@ -271,8 +272,8 @@ def test_writer_drops_the_inputs_tags(tmp_path):
     rows = genotype.VcfRows(str(f), {})
     one = np.ones((1, 1), np.uint8)
     out = tmp_path / "out.vcf"
-    genotype.write_vcf_cohort_prior(str(out), rows, ["s"], None, one, np.array([[[10, 0, 20]]], np.int64), np.array([[[4, 4]]], np.uint32), one, np.array([[1, 2, 1]], np.uint32),
-                                    one * 33, np.array([0.5]), np.array([3], np.uint32))
+    genotype.write_vcf_cohort(str(out), rows, ["s"], genotype.CohortCalls(one, np.array([[[10, 0, 20]]], np.int64), np.array([[[4, 4]]], np.uint32), one, np.array([[1, 2, 1]], np.uint32),
+                                                                           one * 33, np.array([0.5]), np.array([3], np.uint32)))
     assert out.read_text().split("\n")[-2] == "chr1\t100\td1\tN\t<DEL>\t.\tPASS\tSVTYPE=DEL;END=400;NS=1;AN=2;AC=1;AF=0.5;EMAF=0.5\tGT:DP:AD:PL:GQ\t0/1:6.0:2.0,4:10,0,20:33"
 
 

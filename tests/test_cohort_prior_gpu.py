@@ -165,8 +165,8 @@ def test_chunks_equal_one_call(ctx):
         c = CC.inputs(name)
         _load_matrix(ctx, c["n_slots"], c["counts"], c["present"])
         rows = types.SimpleNamespace(sv_type=c["t"], slot=c["slot"], ok=c["ok"])
-        one = genotype.genotype_cohort_prior_rows(ctx, rows, c["S"], c["ploidy"], 3, CC.ERR)
-        parts = genotype.genotype_cohort_prior_rows(ctx, rows, c["S"], c["ploidy"], 3, CC.ERR, step=97)
+        one = genotype.genotype_cohort_rows(ctx, rows, c["S"], 3, CC.ERR, c["ploidy"], True)
+        parts = genotype.genotype_cohort_rows(ctx, rows, c["S"], 3, CC.ERR, c["ploidy"], True, step=97)
         assert len(one) == 8 and all(x.tobytes() == y.tobytes() and x.shape == y.shape for x, y in zip(one, parts))
 
 
@@ -309,7 +309,7 @@ def test_script(golden, tmp_path, which):
     assert (m["gq_margin"][part] > 1e-3).all() and (m["gap"][part] > 1e-6).all()    # nothing of these fixtures sits near a decision
     want = str(tmp_path / "want.vcf")
     steps = m["steps"] | np.where(m["flag"], np.uint32(FLAG), np.uint32(0))
-    genotype.write_vcf_cohort_prior(want, co.rows, co.names, ploidy, m["gt"], co.pl, co.raw, co.done, M.site_of(m["gt"], ploidy), m["gq"], m["f_hi"], steps)
+    genotype.write_vcf_cohort(want, co.rows, co.names, genotype.CohortCalls(m["gt"], co.pl, co.raw, co.done, M.site_of(m["gt"], ploidy), m["gq"], m["f_hi"], steps), ploidy)
     p, out = _run(tmp_path, which, "--cohort", co.list, "--cohort-prior", *extra, "-v", co.vcf)
     assert p.returncode == 0, p.stderr
     assert open(out).read() == open(want).read()

@@ -329,8 +329,9 @@ def test_writer(tmp_path, golden):
     n = len(co.rows.slot)
     qual = (np.where(np.arange(n) % 3 == 0, np.nan, np.arange(n) * 1.005), (np.arange(n) % 5).astype(np.uint32), np.where(np.arange(n) % 3 == 0, 0, 8).astype(np.uint32))
     plain, with_q = str(tmp_path / "plain.vcf"), str(tmp_path / "qual.vcf")
-    genotype.write_vcf_cohort(plain, co.rows, co.names, co.gt, co.pl, co.raw, co.done, co.site)
-    assert genotype.write_vcf_cohort(with_q, co.rows, co.names, co.gt, co.pl, co.raw, co.done, co.site, qual=qual) == co.genotyped
+    calls = genotype.CohortCalls(co.gt, co.pl, co.raw, co.done, co.site)
+    genotype.write_vcf_cohort(plain, co.rows, co.names, calls)
+    assert genotype.write_vcf_cohort(with_q, co.rows, co.names, calls, qual=qual) == co.genotyped
     a, b = open(plain).read().split("\n"), open(with_q).read().split("\n")
     extra = [ln for ln in b if ln not in a and ln.startswith("##")]
     assert [ln.split(",")[0] for ln in extra] == ["##INFO=<ID=SVQ", "##INFO=<ID=MLAC", "##INFO=<ID=MLAF"]

@@ -373,10 +373,10 @@ def test_script(golden, tmp_path, prior):
     if prior:
         pm = PM.run(co.rows.sv_type, co.raw, co.done, None, 5e-5, 3)
         steps = pm["steps"] | np.where(pm["flag"], np.uint32(1 << 31), np.uint32(0))
-        genotype.write_vcf_cohort(want, co.rows, co.names, pm["gt"], co.pl, co.raw, co.done, PM.site_of(pm["gt"], None), None, pm["gq"], pm["f_hi"], steps, qual=qual)
+        genotype.write_vcf_cohort(want, co.rows, co.names, genotype.CohortCalls(pm["gt"], co.pl, co.raw, co.done, PM.site_of(pm["gt"], None), pm["gq"], pm["f_hi"], steps), qual=qual)
         extra = ["--cohort-prior"]
     else:
-        genotype.write_vcf_cohort(want, co.rows, co.names, co.gt, co.pl, co.raw, co.done, co.site, qual=qual)
+        genotype.write_vcf_cohort(want, co.rows, co.names, genotype.CohortCalls(co.gt, co.pl, co.raw, co.done, co.site), qual=qual)
     p, out = _run(tmp_path, "qual", "--cohort", co.list, "--cohort-qual", *extra, "-v", co.vcf)
     assert p.returncode == 0, p.stderr
     a, b = _lines(out), _lines(want)
@@ -398,7 +398,7 @@ def test_script(golden, tmp_path, prior):
     assert [_without_quality(x) for x in a if not x.startswith("##INFO=<ID=SVQ") and not x.startswith("##INFO=<ID=MLA")] == c
     before = str(tmp_path / "before.vcf")
     if prior:
-        genotype.write_vcf_cohort_prior(before, co.rows, co.names, None, pm["gt"], co.pl, co.raw, co.done, PM.site_of(pm["gt"], None), pm["gq"], pm["f_hi"], steps)
+        genotype.write_vcf_cohort(before, co.rows, co.names, genotype.CohortCalls(pm["gt"], co.pl, co.raw, co.done, PM.site_of(pm["gt"], None), pm["gq"], pm["f_hi"], steps))
     else:
         co.assemble(before)
     assert c == _lines(before)
