@@ -425,6 +425,36 @@ int svjg_cohort_qual(svjg_ctx *ctx, const uint8_t *sv_type, const uint32_t *slot
                      const uint8_t *ploidy /* [n_rows][n_samples], or NULL */, uint32_t max_ploidy, uint64_t n_rows, double err, double theta,
                      double *qual, uint32_t *mlac, uint32_t *chroms);
 
+/* svjg_cohort_qc: the samples of a cohort, from the calls a cohort run has made (--cohort-qc): six sums per sample and five per pair of samples,
+ * the counts of the KING-robust kinship estimator (Manichaikul et al. 2010).  Integers only.  gt[n_rows][n_samples] = the calls, ploidy the same
+ * shape or NULL (2 everywhere); with g the call and P the ploidy of an item: eligible P >= 1; called: eligible and g <= P (both no-call codes of
+ * the library, 3 and 0xFF, are "g > P"); carrier: called and g >= 1; dip: called and P = 2; het: dip and g = 1; homalt: dip and g = 2; homref: dip
+ * and g = 0.  Outputs, uint32 sums over the rows:
+ *   sample [n_samples][6]                     eligible, called, carrier, dip, het, homalt
+ *   pair   [n_samples (n_samples - 1) / 2][5] for i < j at k = i n_samples - i (i + 1) / 2 + (j - i - 1): both = sum dip_i dip_j, het1 = sum het_i dip_j,
+ *                                             het2 = sum dip_i het_j, hethet = sum het_i het_j, ibs0 = sum (homref_i homalt_j + homalt_i homref_j)
+ * Only diploid items enter a pair.  The kinship is the host's: with m = min(het1, het2), phi = 0.5 - (4 ibs0 + (het1 - hethet) + (het2 - hethet)) / (4 m),
+ * no estimate where m = 0 (svjedi-graph_amd/svjg/genotype.py: kinship).  A first kernel turns the bytes into bit planes of 64 rows a word and sums
+ * the samples' counts (integer atomics), a second one takes the pairs tile by tile with ANDs and popcounts and writes every pair once: no float,
+ * equal bytes from run to run, and sums over row chunks add up to the sums of one call.  The call neither needs nor reads the cohort matrix, the
+ * count vector or the log10(i!) table's values, and works in a block of its own: it neither reads nor changes any other call's block or views.
+ * The caller bounds memory by calling with row chunks: 1 byte per item (2 with a ploidy array) on the device and the host, 3 bits per item of
+ * planes on the device, 20 bytes per pair and 24 per sample.  n_rows = 0 returns 0 with zeroed outputs; n_samples = 1 is valid and writes no pair
+ * (pair may be NULL).  SVJG_E_ARG with a message in svjg_last_error, all found before any launch: a null gt or sample, a null pair with
+ * n_samples >= 2, n_samples = 0 or above SVJG_QC_MAX_SAMPLES (the pair array is then at most 42 MB; the sample count svjg_cohort_qual admits for
+ * diploids), n_rows x n_samples beyond 2^40, n_rows >= 2^32 (a sum must fit 32 bits).  svjg_last_kernel_ms reports both kernels together as
+ * genotype_ms.
+ * Measured once, with the change that added it (one MI355X, 2026-10-21, ROCm 7.2.0, tools/cohort_qc_timing.py: 10 000 rows, calls 0 / 1 / 2 / none at
+ * 0.45 / 0.3 / 0.15 / 0.1, no ploidy array, median of 10 calls behind 3, run twice in one process; genotype_ms, the memset and both kernels):
+ * 64 samples (2 016 pairs) 0.215 / 0.217 ms, 256 samples (32 640 pairs) 0.230 / 0.230 ms, 2 048 samples (2 096 128 pairs) 0.538 / 0.538 ms; a call
+ * from Python took 0.32 / 0.32, 0.43 / 0.43 and 7.4 / 7.3 ms (42 MB of pairs to the host), the numpy model of tests/cohort_qc_model.py (float64 matrix
+ * products on the same machine's CPUs) 12, 36 and 608 ms, and every call's outputs equalled it.  With 8 words instead of 2 to a lane of the first
+ * kernel the three shapes took 0.306, 0.353 and 0.657 ms (20 waves at 64 samples).  A first reading: nothing is compared against it, and nothing
+ * else has been measured. */
+#define SVJG_QC_MAX_SAMPLES 2048
+int svjg_cohort_qc(svjg_ctx *ctx, const uint8_t *gt /* [n_rows][n_samples] */, const uint8_t *ploidy /* [n_rows][n_samples], or NULL */,
+                   uint64_t n_rows, uint32_t n_samples, uint32_t *sample /* [n_samples][6] */, uint32_t *pair /* [n_samples (n_samples - 1) / 2][5] */);
+
 /* ---- the whole pass in one call (what a fused svjedi-graph run and bench.py do per batch) -----------------------------------
  * svjg_set_rows copies the three per-row input arrays of svjg_genotype to the device once (they stay until the next
  * svjg_set_rows / svjg_destroy).  svjg_run_resident then does, for the resident text of svjg_gaf_upload and those rows:

@@ -82,7 +82,7 @@ constexpr uint64_t STAGE_PIECE = 8ull << 20;
 // hands out pointers into BLOCK_ROWS' twin and svjg_genotype_boundary reads it later, and both must survive calls of the other six.
 // A fused pass's slot holds the same pair (RunSlot).
 struct LegBlock { DevBuf<uint8_t> d;  PinBuf h; };
-enum { BLOCK_ROWS, BLOCK_PLOIDY, BLOCK_SITES, BLOCK_COHORT, BLOCK_COHORT_PLOIDY, BLOCK_COHORT_PRIOR, BLOCK_COHORT_SITES, BLOCK_COHORT_QUAL, BLOCK_COHORT_SITES_PRIOR, LEG_BLOCKS };   // rows_layout, ploidy_layout, sites_layout, cohort_layout for the three cohort blocks, sites_layout again, qual_layout, sites_layout with its prior switch (svjg_geno.h)
+enum { BLOCK_ROWS, BLOCK_PLOIDY, BLOCK_SITES, BLOCK_COHORT, BLOCK_COHORT_PLOIDY, BLOCK_COHORT_PRIOR, BLOCK_COHORT_SITES, BLOCK_COHORT_QUAL, BLOCK_COHORT_SITES_PRIOR, BLOCK_COHORT_QC, LEG_BLOCKS };   // rows_layout, ploidy_layout, sites_layout, cohort_layout for the three cohort blocks, sites_layout again, qual_layout, sites_layout with its prior switch, qc_layout (svjg_geno.h)
 
 // slots the passes of svjg_run_begin rotate through: two may be in flight, and the one the NEXT pass will use is zeroed while the newest computes
 constexpr int RUN_SLOTS = 3;
@@ -986,7 +986,7 @@ static int build_logfact(svjg_ctx *c, uint32_t upto) {
     return 0;
 }
 
-// ---- one genotype leg, for the seven step-by-step calls (genotype_leg) and the fused pass alike ----
+// ---- one genotype leg, for the step-by-step calls (genotype_leg) and the fused pass alike ----
 // k_genotype's arguments but where the results go (the callers' layouts, svjg_geno.h); p: device block with the rows' inputs at I
 static GenoArgs geno_args(const svjg_ctx *c, const unsigned long long *counts, const uint8_t *p, const RowsIn &I, uint64_t n_rows, uint32_t min_support, double err) {
     GenoArgs a{};
@@ -1493,6 +1493,59 @@ extern "C" int svjg_cohort_qual(svjg_ctx *c, const uint8_t *sv_type, const uint3
     if (rc) return rc;
     const uint8_t *hb = c->leg[BLOCK_COHORT_QUAL].h;
     memcpy(qual, hb + L.qual, n_rows * sizeof *qual); memcpy(mlac, hb + L.mlac, n_rows * sizeof *mlac); memcpy(chroms, hb + L.chroms, n_rows * sizeof *chroms);
+    return 0;
+}
+
+// ---- cohort sample QC (svjg.h: svjg_cohort_qc; the model, the planes and the tiles: svjg_geno.h) ----
+// Through genotype_leg in BLOCK_COHORT_QC, a block of its own: the call bytes (and the ploidy bytes) go in; ONE memset zeroes sample[] and the max_n
+// pair behind it; k_qc_planes over the units, k_qc_pairs over the tiles (S >= 2), both in strides of a grid of at most QC_BLOCKS_PER_CU blocks a
+// unit (the pair kernel's 36 864 bytes of LDS and 4 waves a block admit that many); pair[] and sample[] come out.  Neither kernel reads the
+// log10(i!) table, the cohort matrix or the count vector, and the max_n pair stays zero: the leg never runs them twice.
+constexpr uint32_t QC_BLOCKS_PER_CU = 4;
+static int launch_cohort_qc(svjg_ctx *c, const QcArgs &p) {
+    HIPCHK(c, hipMemsetAsync(p.sample, 0, (uint64_t)p.S * 4 * QC_CLASSES + 8, c->stream));      // (the max_n pair lies right behind sample[]: qc_layout)
+    const uint64_t cap = (uint64_t)c->n_cu * QC_BLOCKS_PER_CU, blocks = (qc_plane_units(p.n_words, p.S) + TPB - 1) / TPB;
+    hipLaunchKernelGGL(k_qc_planes, dim3((uint32_t)(blocks < cap ? blocks : cap)), dim3(TPB), 0, c->stream, p);
+    HIPCHK(c, hipGetLastError());
+    const uint64_t tiles = qc_tiles(p.S);
+    if (tiles) {
+        hipLaunchKernelGGL(k_qc_pairs, dim3((uint32_t)(tiles < cap ? tiles : cap)), dim3(TPB), 0, c->stream, p);
+        HIPCHK(c, hipGetLastError());
+    }
+    return 0;
+}
+
+extern "C" int svjg_cohort_qc(svjg_ctx *c, const uint8_t *gt, const uint8_t *ploidy, uint64_t n_rows, uint32_t n_samples, uint32_t *sample, uint32_t *pair) {
+    if (!c) return SVJG_E_ARG;
+    static_assert(SVJG_QC_MAX_SAMPLES == QC_MAX_SAMPLES, "svjg.h and svjg_geno.h disagree");
+    const uint64_t S = n_samples;
+    if (S == 0) { c->err = "no sample"; return SVJG_E_ARG; }
+    if (S > QC_MAX_SAMPLES) { c->err = "too many samples for the pair table: n_samples is above SVJG_QC_MAX_SAMPLES = 2048"; return SVJG_E_ARG; }
+    if (!gt || !sample || (!pair && S >= 2)) { c->err = "a null array"; return SVJG_E_ARG; }
+    if (n_rows >= (1ull << 32)) { c->err = "too many rows for 32-bit sums: take the rows in chunks"; return SVJG_E_ARG; }
+    if (n_rows > (1ull << 40) / S) { c->err = "too many items for one call: take the rows in chunks"; return SVJG_E_ARG; }
+    const uint64_t n = n_rows * S, n_pairs = qc_pairs(S);
+    if (n_rows == 0) {
+        memset(sample, 0, S * QC_CLASSES * sizeof *sample);
+        if (n_pairs) memset(pair, 0, n_pairs * QC_PAIR_COUNTS * sizeof *pair);
+        return 0;
+    }
+    HIPCHK(c, hipSetDevice(c->device));
+    const QcLayout L = qc_layout(n_rows, S, ploidy != nullptr);
+    const int rc = genotype_leg(c, c->leg[BLOCK_COHORT_QC], L,
+        [&](uint8_t *hb) {
+            memcpy(hb + L.gt, gt, n);
+            if (ploidy) memcpy(hb + L.ploidy, ploidy, n);
+        },
+        [&](uint8_t *base) {
+            const QcArgs p{base + L.gt, ploidy ? base + L.ploidy : nullptr, n_rows, qc_words(n_rows), n_samples, (uint64_t *)(base + L.planes),
+                           (uint32_t *)(base + L.sample), (uint32_t *)(base + L.pair)};
+            return launch_cohort_qc(c, p);
+        });
+    if (rc) return rc;
+    const uint8_t *hb = c->leg[BLOCK_COHORT_QC].h;
+    memcpy(sample, hb + L.sample, S * QC_CLASSES * sizeof *sample);
+    if (n_pairs) memcpy(pair, hb + L.pair, n_pairs * QC_PAIR_COUNTS * sizeof *pair);
     return 0;
 }
 

@@ -1033,6 +1033,94 @@ SVJG_HD double qual_finish(double phi0, dd D0, double T, int64_t E) {
     return q > 0.0 ? q : 0.0;                                                  // (never -0.0)
 }
 
+// ---- cohort sample QC: per-sample sums and pairwise kinship counts (k_qc_planes, k_qc_pairs) ----
+// Integers only.  Item (r, s) has the call g = gt[r][s] and the ploidy P = ploidy[r][s] (2 without an array); both no-call codes of the library are
+// "g > P" (3 in the diploid calls, 0xFF elsewhere).  Six predicates an item, one bit each (QC_*): eligible P >= 1; called: eligible and g <= P;
+// carrier: called and g >= 1; dip: called and P = 2; het: dip and g = 1; homalt: dip and g = 2 (homref = dip & ~het & ~homalt).  Per sample the six
+// sums over the rows; per pair i < j, at k = i S - i (i + 1) / 2 + (j - i - 1), five sums over the rows: both = dip_i dip_j, het1 = het_i dip_j,
+// het2 = dip_i het_j, hethet = het_i het_j, ibs0 = homref_i homalt_j + homalt_i homref_j.  A sample's predicates over 64 consecutive rows are one
+// 64-bit word a predicate (row 64 w + b is bit b of word w; the bits behind the call's last row are 0), a pair's sums popcounts of ANDs of them.
+enum : uint32_t { QC_ELIGIBLE, QC_CALLED, QC_CARRIER, QC_DIP, QC_HET, QC_HOMALT, QC_CLASSES };       // the order of sample[s][6]
+constexpr uint32_t QC_PAIR_COUNTS = 5;                   // both, het1, het2, hethet, ibs0: the order of pair[k][5]
+constexpr uint32_t QC_MAX_SAMPLES = 2048;                // 2 096 128 pairs, 42 MB of them
+SVJG_HD uint32_t qc_class(uint32_t g, uint32_t P) {      // -> bit QC_x set: the predicate holds
+    const uint32_t eligible = P >= 1, called = eligible & (g <= P), carrier = called & (g >= 1), dip = called & (P == 2);
+    return eligible << QC_ELIGIBLE | called << QC_CALLED | carrier << QC_CARRIER | dip << QC_DIP | (dip & (g == 1)) << QC_HET | (dip & (g == 2)) << QC_HOMALT;
+}
+constexpr uint64_t qc_words(uint64_t n_rows) { return (n_rows + 63) / 64; }
+constexpr uint64_t qc_pairs(uint64_t S) { return S * (S - 1) / 2; }
+SVJG_HD uint32_t qc_pair_at(uint32_t i, uint32_t j, uint32_t S) { return i * S - i * (i + 1) / 2 + (j - i - 1); }      // i < j < S <= QC_MAX_SAMPLES: below 2^21
+
+// the six words of sample s over the rows 64 w .. 64 w + 63 of a call of n_rows rows x S samples (k_qc_planes: one lane a sample, so a wave reads
+// consecutive bytes of a row); word[] is indexed by unrolled constants only
+SVJG_HD void qc_plane_words(const uint8_t *gt, const uint8_t *ploidy, uint64_t n_rows, uint64_t S, uint64_t w, uint64_t s, uint64_t *word) {
+    SVJG_UNROLL
+    for (uint32_t q = 0; q < QC_CLASSES; ++q) word[q] = 0;
+    const uint64_t r0 = w * 64, left = n_rows - r0;
+    const uint32_t n = left < 64 ? (uint32_t)left : 64u;
+    for (uint32_t b = 0; b < n; ++b) {
+        const uint64_t at = (r0 + b) * S + s;
+        const uint32_t c = qc_class(gt[at], ploidy ? ploidy[at] : 2u);
+        SVJG_UNROLL
+        for (uint32_t q = 0; q < QC_CLASSES; ++q) word[q] |= (uint64_t)((c >> q) & 1u) << b;
+    }
+}
+
+// one 64-row word of a pair: the five counts added to c[] (di / hi / ai: dip, het and homalt of sample i)
+SVJG_HD void qc_pair_word(uint64_t di, uint64_t hi, uint64_t ai, uint64_t dj, uint64_t hj, uint64_t aj, uint32_t *c) {
+    const uint64_t ri = di & ~hi & ~ai, rj = dj & ~hj & ~aj;
+    c[0] += (uint32_t)__builtin_popcountll(di & dj);
+    c[1] += (uint32_t)__builtin_popcountll(hi & dj);
+    c[2] += (uint32_t)__builtin_popcountll(di & hj);
+    c[3] += (uint32_t)__builtin_popcountll(hi & hj);
+    c[4] += (uint32_t)__builtin_popcountll((ri & aj) | (ai & rj));
+}
+
+// k_qc_planes keeps the three planes k_qc_pairs reads (dip, het, homalt; plane p of QC_DIP + p), word-major: planes[(p * n_words + w) * S + s], so
+// that the lanes of a wave (consecutive samples) write, and the pair kernel's staging reads, consecutive words.
+constexpr uint32_t QC_PLANES = 3;
+SVJG_HD uint64_t qc_plane_at(uint32_t p, uint64_t w, uint64_t s, uint64_t n_words, uint64_t S) { return ((uint64_t)p * n_words + w) * S + s; }
+// a lane of k_qc_planes takes QC_PLANE_WORDS consecutive words of one sample (a "unit": unit u = chunk u / S, sample u % S) and adds its six
+// popcounts to sample[] once per unit
+constexpr uint32_t QC_PLANE_WORDS = 2;
+constexpr uint64_t qc_plane_units(uint64_t n_words, uint64_t S) { return (n_words + QC_PLANE_WORDS - 1) / QC_PLANE_WORDS * S; }
+
+// k_qc_pairs: a block of four waves takes a tile of QC_TI x QC_TJ samples (i x j) of the upper triangle.  Lane l of wave v owns the QC_RI pairs
+// (i0 + v QC_RI + a, j0 + l), a = 0..QC_RI - 1: a register tile of QC_RI x 5 counters.  The row words go through LDS QC_STAGE_WORDS at a time, as
+// uint64 slot e of [ i-side: plane p, word w, sample x of QC_TI | j-side: the same of QC_TJ ], sample fastest: a wave's 64-bit reads of the j-side
+// are 64 consecutive slots (banks 2 l, 2 l + 1 within a 32-lane group: no conflict), its reads of the i-side one slot (a broadcast).
+constexpr uint32_t QC_TI = 32, QC_TJ = 64, QC_WAVES = 4, QC_RI = QC_TI / QC_WAVES, QC_STAGE_WORDS = 16;
+constexpr uint32_t QC_LDS_I = QC_PLANES * QC_STAGE_WORDS * QC_TI, QC_LDS_SLOTS = QC_LDS_I + QC_PLANES * QC_STAGE_WORDS * QC_TJ;    // 36 864 bytes
+SVJG_HD uint32_t qc_lds_i(uint32_t p, uint32_t w, uint32_t x) { return (p * QC_STAGE_WORDS + w) * QC_TI + x; }
+SVJG_HD uint32_t qc_lds_j(uint32_t p, uint32_t w, uint32_t x) { return QC_LDS_I + (p * QC_STAGE_WORDS + w) * QC_TJ + x; }
+// what slot e holds in the stage that begins at word w0 of the tile at samples i0, j0: 0 for a sample at or beyond S or a word at or beyond n_words
+SVJG_HD uint64_t qc_stage_word(const uint64_t *planes, uint32_t e, uint32_t i0, uint32_t j0, uint64_t w0, uint64_t n_words, uint32_t S) {
+    const bool jside = e >= QC_LDS_I;
+    const uint32_t f = jside ? e - QC_LDS_I : e, width = jside ? QC_TJ : QC_TI;
+    const uint32_t x = f % width, pw = f / width, w = pw % QC_STAGE_WORDS, p = pw / QC_STAGE_WORDS;
+    const uint32_t s = (jside ? j0 : i0) + x;
+    return s < S && w0 + w < n_words ? planes[qc_plane_at(p, w0 + w, s, n_words, S)] : 0ull;
+}
+// The tiles of the upper triangle, i-tile by i-tile: i runs over 0..S - 2, so there are ceil((S - 1) / QC_TI) i-tiles, and the i-tile at i0 needs the
+// j-tiles that hold a j > i0: from (i0 + 1) / QC_TJ on.  Tile t -> (ti, tj) by walking the i-tiles (at most 64 steps: bounded by S alone).
+SVJG_HD uint32_t qc_tiles_i(uint32_t S) { return S < 2 ? 0u : (S - 1 + QC_TI - 1) / QC_TI; }
+SVJG_HD uint32_t qc_tiles_j(uint32_t S) { return (S + QC_TJ - 1) / QC_TJ; }
+SVJG_HD uint32_t qc_tile_first_j(uint32_t ti) { return (ti * QC_TI + 1) / QC_TJ; }
+SVJG_HD uint32_t qc_tiles(uint32_t S) {
+    uint32_t n = 0;
+    for (uint32_t ti = 0; ti < qc_tiles_i(S); ++ti) n += qc_tiles_j(S) - qc_tile_first_j(ti);
+    return n;
+}
+SVJG_HD void qc_tile_at(uint32_t t, uint32_t S, uint32_t &ti, uint32_t &tj) {         // t < qc_tiles(S)
+    const uint32_t ni = qc_tiles_i(S), nj = qc_tiles_j(S);
+    for (ti = 0; ti + 1 < ni; ++ti) {
+        const uint32_t n = nj - qc_tile_first_j(ti);
+        if (t < n) break;
+        t -= n;
+    }
+    tj = qc_tile_first_j(ti) + t;
+}
+
 // ---- host side of a k_genotype launch: the table's size and where a call's rows lie, in plain integers (pinned without a GPU: tests/test_rows_layout.py) ----
 
 // entries of the log10(i!) table: the first one built; the one that holds max_n (the largest n the kernel met beyond the table, < LOGFACT_CAP) with room to spare
@@ -1048,7 +1136,7 @@ constexpr uint32_t logfact_reserve_to(uint32_t have, uint32_t entries) { return 
 struct RowsIn { uint64_t slot, type, ok, bytes; };
 inline RowsIn rows_in(uint64_t n, uint64_t at = 0) { return RowsIn{at, at + n * 4, at + n * 5, n * 6}; }
 
-// The eight step-by-step calls (svjg_genotype / _view, _ploidy, _sites, _cohort, _cohort_ploidy, _cohort_prior, _cohort_sites, svjg_cohort_qual) each own one device block and its pinned host twin, all of ONE
+// The nine step-by-step calls (svjg_genotype / _view, _ploidy, _sites, _cohort, _cohort_ploidy, _cohort_prior, _cohort_sites, svjg_cohort_qual, svjg_cohort_qc) each own one device block and its pinned host twin, all of ONE
 // shape: the outputs (they end at out_end), the max_n pair 8-aligned, ONE contiguous input region right behind the pair, 64 spare bytes -> ONE copy
 // in (in_bytes from in_at), ONE copy out (maxn + 8 bytes from 0).  A layout below IS a LegSpan and adds only what is its own: its outputs and where its inputs lie.
 struct LegSpan { uint64_t maxn, in_at, in_bytes, total; };
@@ -1126,6 +1214,22 @@ inline QualLayout qual_layout(uint64_t n_rows, uint64_t S, uint32_t m_max, bool 
     L.qual = o; o += n_rows * 8; L.mlac = o; o += n_rows * 4; L.chroms = o; o += n_rows * 4;
     leg_span(L, o, logs + harm + n_rows * 6 + (per_item ? n_rows * S : 0));
     L.logtab = L.in_at; L.harm = L.logtab + logs; L.in = rows_in(n_rows, L.harm + harm); L.ploidy = L.in.slot + L.in.bytes;
+    return L;
+}
+
+// svjg_cohort_qc: [ pair 20 ] x S (S - 1) / 2 of output, then, 8-aligned, [ sample 24 ] x S as the LAST output: the max_n pair lies right behind
+// it (a multiple of 8: leg_span pads nothing), and ONE memset zeroes both in front of every launch (k_qc_planes adds to sample[]; the pair is never
+// written: the call reads no table and names no slot).  in: the n_rows * S call bytes and, per_item, as many ploidy bytes.  Behind the inputs,
+// 8-aligned and never copied: the QC_PLANES planes of qc_words(n_rows) * S words, written by k_qc_planes and read by k_qc_pairs.
+struct QcLayout : LegSpan { uint64_t pair, sample, gt, ploidy, planes; };
+inline QcLayout qc_layout(uint64_t n_rows, uint64_t S, bool per_item) {
+    QcLayout L{}; uint64_t o = 0; const uint64_t n = n_rows * S;
+    L.pair = o; o += qc_pairs(S) * 4 * QC_PAIR_COUNTS; o = (o + 7) & ~7ull;
+    L.sample = o; o += S * 4 * QC_CLASSES;
+    leg_span(L, o, n * (per_item ? 2 : 1));
+    L.gt = L.in_at; L.ploidy = per_item ? L.gt + n : 0;
+    L.planes = (L.in_at + L.in_bytes + 7) & ~7ull;
+    L.total = L.planes + QC_PLANES * qc_words(n_rows) * S * 8 + 64;
     return L;
 }
 

@@ -2579,4 +2579,87 @@ __global__ __launch_bounds__(SITES_PRIOR_TPB) void k_cohort_sites_prior(CohortSi
   }
 }
 
+// ---- cohort sample QC (svjg.h: svjg_cohort_qc; the model, the planes and the tiles: svjg_geno.h) ----
+struct QcArgs {
+    const uint8_t *gt, *ploidy;          // [n_rows][S]; ploidy nullptr: 2 everywhere
+    uint64_t n_rows, n_words;            // n_words = qc_words(n_rows)
+    uint32_t S;
+    uint64_t *planes;                    // qc_plane_at
+    uint32_t *sample, *pair;             // [S][6] (zeroed in front of the launch), [qc_pairs(S)][5]
+};
+
+// One lane a unit (QC_PLANE_WORDS words of one sample), neighbouring lanes neighbouring samples: the six words of every 64 rows row by row in
+// registers (no ballot), the three planes the pair kernel reads stored, the six popcounts summed over the unit and added to sample[] by one integer
+// atomic a count and unit: integer sums, equal from run to run.  Strides of the grid over the units; every loop is bounded by the arguments.
+__global__ __launch_bounds__(TPB) void k_qc_planes(QcArgs p) {
+    const uint64_t units = qc_plane_units(p.n_words, p.S);
+    for (uint64_t u = (uint64_t)blockIdx.x * TPB + threadIdx.x; u < units; u += (uint64_t)gridDim.x * TPB) {
+        const uint64_t chunk = u / p.S, s = u % p.S;
+        const uint64_t w_begin = chunk * QC_PLANE_WORDS, w_end = w_begin + QC_PLANE_WORDS < p.n_words ? w_begin + QC_PLANE_WORDS : p.n_words;
+        uint32_t n[QC_CLASSES];
+#pragma unroll
+        for (uint32_t q = 0; q < QC_CLASSES; ++q) n[q] = 0;
+        for (uint64_t w = w_begin; w < w_end; ++w) {
+            uint64_t word[QC_CLASSES];
+            qc_plane_words(p.gt, p.ploidy, p.n_rows, p.S, w, s, word);
+#pragma unroll
+            for (uint32_t q = 0; q < QC_CLASSES; ++q) n[q] += (uint32_t)__builtin_popcountll(word[q]);
+#pragma unroll
+            for (uint32_t k = 0; k < QC_PLANES; ++k) p.planes[qc_plane_at(k, w, s, p.n_words, p.S)] = word[QC_DIP + k];
+        }
+#pragma unroll
+        for (uint32_t q = 0; q < QC_CLASSES; ++q) if (n[q]) atomicAdd(p.sample + s * QC_CLASSES + q, n[q]);
+    }
+}
+
+// One block a tile of the upper triangle, strides of the grid over the tiles.  Per stage of QC_STAGE_WORDS row words: the block copies the three
+// planes of the tile's QC_TI + QC_TJ samples into LDS (slot e = qc_stage_word: consecutive lanes read consecutive words of a plane row), then every
+// lane adds the stage's words to its QC_RI pairs' five counters: three 64-bit reads of its own j (conflict-free), three a pair of the wave's i
+// (one address a wave: a broadcast), ANDs and popcounts (qc_pair_word).  A wave whose every i is at or beyond the tile's last j has no pair and only
+// keeps the barriers.  At the end every pair i < j < S is written once: no float, no atomic, equal bytes from run to run.  Every loop is bounded by
+// the arguments; no wave waits for another but at the block's barriers.
+__global__ __launch_bounds__(TPB) void k_qc_pairs(QcArgs p) {
+    static_assert(TPB == QC_WAVES * 64 && QC_TJ == 64, "a wave's lanes are the tile's j");
+    __shared__ uint64_t lds[QC_LDS_SLOTS];
+    const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6, n_tiles = qc_tiles(p.S);
+    for (uint32_t t = blockIdx.x; t < n_tiles; t += gridDim.x) {
+        uint32_t ti, tj;
+        qc_tile_at(t, p.S, ti, tj);
+        const uint32_t i0 = ti * QC_TI, j0 = tj * QC_TJ, iw = i0 + wave * QC_RI, j = j0 + lane;
+        const bool work = iw < j0 + QC_TJ - 1;           // (the wave's smallest i against the tile's largest j)
+        uint32_t acc[QC_RI][QC_PAIR_COUNTS];
+#pragma unroll
+        for (uint32_t a = 0; a < QC_RI; ++a)
+#pragma unroll
+            for (uint32_t k = 0; k < QC_PAIR_COUNTS; ++k) acc[a][k] = 0;
+        for (uint64_t w0 = 0; w0 < p.n_words; w0 += QC_STAGE_WORDS) {
+            __syncthreads();                             // the stage before has been read
+            for (uint32_t e = threadIdx.x; e < QC_LDS_SLOTS; e += TPB) lds[e] = qc_stage_word(p.planes, e, i0, j0, w0, p.n_words, p.S);
+            __syncthreads();
+            if (work) {
+                const uint32_t nw = p.n_words - w0 < QC_STAGE_WORDS ? (uint32_t)(p.n_words - w0) : QC_STAGE_WORDS;
+                for (uint32_t w = 0; w < nw; ++w) {
+                    const uint64_t dj = lds[qc_lds_j(0, w, lane)], hj = lds[qc_lds_j(1, w, lane)], aj = lds[qc_lds_j(2, w, lane)];
+#pragma unroll
+                    for (uint32_t a = 0; a < QC_RI; ++a) {
+                        const uint32_t x = wave * QC_RI + a;
+                        qc_pair_word(lds[qc_lds_i(0, w, x)], lds[qc_lds_i(1, w, x)], lds[qc_lds_i(2, w, x)], dj, hj, aj, acc[a]);
+                    }
+                }
+            }
+        }
+        if (j < p.S) {
+#pragma unroll
+            for (uint32_t a = 0; a < QC_RI; ++a) {
+                const uint32_t i = iw + a;
+                if (i < j) {                             // (i < j < S: the pair exists, and no other lane of any tile owns it)
+                    uint32_t *out = p.pair + (uint64_t)qc_pair_at(i, j, p.S) * QC_PAIR_COUNTS;
+#pragma unroll
+                    for (uint32_t k = 0; k < QC_PAIR_COUNTS; ++k) out[k] = acc[a][k];
+                }
+            }
+        }
+    }
+}
+
 }  // namespace svjg

@@ -8,6 +8,7 @@
     predict-genotype.py --cohort LIST --joint-ins -v VCF ...                                (extension: insertions that share a position, together per sample)
     predict-genotype.py --cohort LIST --joint-ins --joint-prior -v VCF ...                  (extension: the samples of such a site inform each other, with SGQ)
     predict-genotype.py --cohort LIST --cohort-qual [--cohort-theta X] -v VCF ...           (extension: SVQ / MLAC / MLAF, the cohort's exact allele-count posterior)
+    predict-genotype.py --cohort LIST --cohort-qc PREFIX -v VCF ...                         (extension: PREFIX.samples.tsv and PREFIX.pairs.tsv, per-sample sums and pairwise kinship)
 """
 import argparse
 import os
@@ -53,6 +54,10 @@ def main():
                          "the QUAL column and everything else stay as without it; not with --joint-ins (extension)")
     ap.add_argument("--cohort-theta", metavar="<theta>", type=float,
                     help="with --cohort-qual: the prior of k alt copies in the cohort is theta / k, a value in (0, 0.05] (default: 0.001)")
+    ap.add_argument("--cohort-qc", metavar="<prefix>",
+                    help="with --cohort, beside any other cohort option: write <prefix>.samples.tsv (per sample: eligible, called, carrier, diploid, het and "
+                         "hom-alt rows, call rate, het / hom-alt) and <prefix>.pairs.tsv (per pair of samples: the KING-robust kinship over the rows both "
+                         "are diploid on, and DUP / 1ST / 2ND / 3RD / UN) from the run's calls; the VCF stays byte for byte what it is without it (extension)")
     args = ap.parse_args()
     if args.cohort is not None and args.aln is not None:
         ap.error("exactly one of -d and --cohort")
@@ -62,7 +67,7 @@ def main():
     from svjg import genotype
     single = dict(ploidy=args.ploidy, ploidy_file=args.ploidy_file, joint_ins=args.joint_ins)
     cohort = dict(ploidy_file=args.cohort_ploidy, prior=args.cohort_prior, joint_ins=args.joint_ins, joint_prior=args.joint_prior, qual=args.cohort_qual,
-                  theta=genotype.COHORT_QUAL_THETA if args.cohort_theta is None else args.cohort_theta)
+                  theta=genotype.COHORT_QUAL_THETA if args.cohort_theta is None else args.cohort_theta, qc=args.cohort_qc)
     try:                                                         # the rules between the options themselves are the library's: one text each
         if args.cohort is None:
             for flag, given in (("--cohort-ploidy", args.cohort_ploidy is not None), ("--cohort-prior", args.cohort_prior)):
@@ -72,6 +77,8 @@ def main():
             for flag, given in (("--joint-prior", args.joint_prior), ("--cohort-qual", args.cohort_qual)):
                 if given:
                     ap.error(flag + " needs --cohort")
+            if args.cohort_qc is not None:
+                ap.error(genotype.COHORT_QC_NEEDS)
         else:
             genotype.check_cohort_options(**cohort)
     except ValueError as e:

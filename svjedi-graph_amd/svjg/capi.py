@@ -95,6 +95,7 @@ _SIGS = {
     "svjg_genotype_cohort_sites": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_uint32, ctypes.c_double] + [ctypes.c_void_p] * 6),
     "svjg_genotype_cohort_sites_prior": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_uint32, ctypes.c_double] + [ctypes.c_void_p] * 11),
     "svjg_cohort_qual": (ctypes.c_int, [ctypes.c_void_p] * 5 + [ctypes.c_uint32, ctypes.c_uint64, ctypes.c_double, ctypes.c_double] + [ctypes.c_void_p] * 3),
+    "svjg_cohort_qc": (ctypes.c_int, [ctypes.c_void_p] * 3 + [ctypes.c_uint64, ctypes.c_uint32] + [ctypes.c_void_p] * 2),
     "svjg_set_rows": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64]),
     "svjg_run_resident": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_uint64, ctypes.c_uint32, ctypes.c_double] + [ctypes.POINTER(ctypes.c_void_p)] * 5),
     "svjg_run_begin": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_uint64, ctypes.c_uint32, ctypes.c_double]),
@@ -117,6 +118,7 @@ EXPORTS = tuple(_SIGS) + ("svjg_write_informative_json", "svjg_count_informative
 MAX_PLOIDY = 8                      # svjg.h: SVJG_MAX_PLOIDY
 MAX_SITE_ALTS = 6                   # svjg.h: SVJG_MAX_SITE_ALTS
 SITE_GENOTYPES = 28                 # svjg.h: SVJG_SITE_GENOTYPES
+QC_MAX_SAMPLES = 2048               # svjg.h: SVJG_QC_MAX_SAMPLES
 QUAL_THETA = 1e-3                   # the default theta of the site quality (svjg_cohort_qual; the library takes a value in (0, 0.05])
 _lib = None
 _host_lib = None
@@ -627,6 +629,24 @@ class Context:
         self._chk(self.lib.svjg_cohort_qual(self.h, sv_type.ctypes.data, slot.ctypes.data, ok.ctypes.data, None if ploidy is None else ploidy.ctypes.data,
                                             max_ploidy, n, float(err), float(theta), *(a.ctypes.data for a in out)))
         return out
+
+    def cohort_qc(self, gt, ploidy=None):
+        """The samples of a cohort from its calls (svjg_cohort_qc): gt[n, S] = alt copies, ploidy[n, S] or None (2 everywhere); an item with
+        gt > ploidy (3, 0xFF) is not called, one with ploidy 0 not eligible.  It reads nothing of the context's matrix or counts.
+        -> (sample[S, 6] = eligible, called, carrier, diploid, het, homalt; pair[S (S - 1) / 2, 5] = both, het1, het2, hethet, ibs0 of the pairs
+        i < j at k = i S - i (i + 1) / 2 + (j - i - 1), over the items both diploid), uint32 sums over the rows"""
+        gt = np.ascontiguousarray(gt, dtype=np.uint8)
+        if gt.ndim != 2:
+            raise ValueError("gt must be [n_rows, n_samples]")
+        n, S = gt.shape
+        if ploidy is not None:
+            ploidy = np.ascontiguousarray(ploidy, dtype=np.uint8)
+            if ploidy.shape != gt.shape:
+                raise ValueError("ploidy must have gt's shape")
+        sample, pair = np.empty((S, 6), np.uint32), np.empty((S * (S - 1) // 2 if S else 0, 5), np.uint32)
+        self._chk(self.lib.svjg_cohort_qc(self.h, gt.ctypes.data, None if ploidy is None else ploidy.ctypes.data, n, S, sample.ctypes.data,
+                                          pair.ctypes.data if len(pair) else None))
+        return sample, pair
 
     def genotype_cohort_sites(self, slots, min_support, err):
         """genotype_sites for every sample of the cohort matrix in one launch (svjg_genotype_cohort_sites).  slots[n, 6]: the CANDIDATE slots of each

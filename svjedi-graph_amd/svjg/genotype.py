@@ -915,7 +915,107 @@ def cohort_joint_sites(ctx, rows, gt, site, min_support, err, step=None, prior=F
     return JointSites(site, joint, em)
 
 
-def check_cohort_options(ploidy_file=None, prior=False, joint_ins=False, joint_prior=False, qual=False, theta=COHORT_QUAL_THETA):
+# ---- cohort sample QC (--cohort LIST --cohort-qc PREFIX): svjg_cohort_qc on the calls the run has made, PREFIX.samples.tsv and PREFIX.pairs.tsv ----
+
+COHORT_QC_NEEDS = "--cohort-qc needs --cohort: it summarises the samples of a cohort run"
+COHORT_QC_PREFIX = "--cohort-qc: the prefix of PREFIX.samples.tsv and PREFIX.pairs.tsv must not be empty"
+QC_SAMPLES_HEADER = "#SAMPLE\tN_ELIGIBLE\tN_CALLED\tCALL_RATE\tN_CARRIER\tN_DIPLOID\tN_HET\tN_HOMALT\tHET_HOMALT\n"
+QC_PAIRS_HEADER = "#SAMPLE1\tSAMPLE2\tN_BOTH\tHET1\tHET2\tHETHET\tIBS0\tKINSHIP\tRELATION\n"
+KINSHIP_BOUNDS = ((2.0 ** -1.5, "DUP"), (2.0 ** -2.5, "1ST"), (2.0 ** -3.5, "2ND"), (2.0 ** -4.5, "3RD"))
+
+
+def kinship(het1, het2, hethet, ibs0):
+    """KING-robust (Manichaikul et al. 2010) on svjg_cohort_qc's counts of a pair, in Python integers and ONE true division:
+    0.5 - (4 ibs0 + (het1 - hethet) + (het2 - hethet)) / (4 min(het1, het2)); None where that minimum is 0 (no estimate).  Equal columns: exactly 0.5"""
+    het1, het2, hethet, ibs0 = int(het1), int(het2), int(hethet), int(ibs0)
+    m = min(het1, het2)
+    if m == 0:
+        return None
+    return 0.5 - (4 * ibs0 + (het1 - hethet) + (het2 - hethet)) / (4 * m)
+
+
+def relation(phi):
+    """the degree a kinship says, decided on the double: above 2^-1.5 DUP, 2^-2.5 1ST, 2^-3.5 2ND, 2^-4.5 3RD, else UN"""
+    for bound, name in KINSHIP_BOUNDS:
+        if phi > bound:
+            return name
+    return "UN"
+
+
+def kinship_text(phi):
+    """"%.4f", and 0.0000 for a value that would print -0.0000"""
+    text = "%.4f" % phi
+    return "0.0000" if text == "-0.0000" else text
+
+
+def _ratio_text(a, b):
+    return "%.6g" % (a / b) if b else "."
+
+
+def cohort_qc_chunk_rows(n_samples, per_item=False):
+    """rows per svjg_cohort_qc call, so that it stays under 1 GiB (svjg.h: 1 byte an item, 2 with a ploidy array, 3 bits of planes, 20 bytes a pair,
+    24 a sample) and under the call's 2^32 rows"""
+    S = max(1, int(n_samples))
+    fixed = 20 * (S * (S - 1) // 2) + 24 * S + 24 * S + 256          # (the pairs, the samples, the planes' last word begun, the block's own bytes)
+    return max(1, min((1 << 32) - 1, (COHORT_CALL_BYTES - fixed) // (S * (2 if per_item else 1) + (3 * S + 7) // 8)))
+
+
+def cohort_qc_rows(ctx, gt, done, ploidy, step=None):
+    """svjg_cohort_qc over all rows of a cohort run's calls: gt[n, S] and done[n, S] as CohortCalls has them — an item with done == 0 goes in as
+    0xFF, not called whatever its ploidy —, ploidy[n, S] or None (diploid).  Rows in chunks of `step` (None: cohort_qc_chunk_rows); the chunks'
+    integer outputs are summed in int64, so any chunking gives the same numbers.  -> (sample[S, 6], pair[S (S - 1) / 2, 5]) int64"""
+    gt = np.where(np.asarray(done) != 0, np.asarray(gt, dtype=np.uint8), np.uint8(NO_CALL)).astype(np.uint8)
+    n, S = gt.shape
+    if ploidy is not None:
+        ploidy = np.ascontiguousarray(ploidy, dtype=np.uint8)
+    if step is None:
+        step = cohort_qc_chunk_rows(S, ploidy is not None)
+    sample, pair = np.zeros((S, 6), np.int64), np.zeros((S * (S - 1) // 2, 5), np.int64)
+    for at in range(0, n, int(step)):
+        s, p = ctx.cohort_qc(gt[at:at + step], None if ploidy is None else ploidy[at:at + step])
+        sample += s
+        pair += np.asarray(p).reshape(-1, 5)
+    return sample, pair
+
+
+def printed_gt(calls, joint=None):
+    """gt[n, S] as the cohort writer prints it: calls.gt, and on a row of joint.joint (--joint-ins) the projection of the site call for the samples
+    the site covers (3: the site has no call), the row-by-row call for the others"""
+    gt = np.array(calls.gt, dtype=np.uint8)
+    if joint is not None:
+        for v, m in joint.joint.items():
+            gt[v] = np.where(m.covered, m.g, gt[v])
+    return gt
+
+
+def write_qc_samples(path, names, sample):
+    """PREFIX.samples.tsv: a line per sample of the cohort list, in its order; CALL_RATE = called / eligible and HET_HOMALT = het / homalt as
+    "%.6g", `.` where the denominator is 0"""
+    with open(path, "w") as fh:
+        fh.write(QC_SAMPLES_HEADER)
+        for name, row in zip(names, np.asarray(sample).tolist()):
+            eligible, called, carrier, dip, het, homalt = row
+            fh.write("%s\t%d\t%d\t%s\t%d\t%d\t%d\t%d\t%s\n" % (name, eligible, called, _ratio_text(called, eligible), carrier, dip, het, homalt,
+                                                                _ratio_text(het, homalt)))
+
+
+def write_qc_pairs(path, names, pair):
+    """PREFIX.pairs.tsv: a line per pair i < j in the order of svjg_cohort_qc's k; KINSHIP as kinship_text and RELATION from the double, both `.`
+    where there is no estimate"""
+    rows = np.asarray(pair).tolist()
+    with open(path, "w") as fh:
+        fh.write(QC_PAIRS_HEADER)
+        k = 0
+        for i in range(len(names)):
+            for j in range(i + 1, len(names)):
+                both, het1, het2, hethet, ibs0 = rows[k]
+                k += 1
+                phi = kinship(het1, het2, hethet, ibs0)
+                fh.write("%s\t%s\t%d\t%d\t%d\t%d\t%d\t%s\t%s\n" % (names[i], names[j], both, het1, het2, hethet, ibs0,
+                                                                    "." if phi is None else kinship_text(phi), "." if phi is None else relation(phi)))
+
+
+def check_cohort_options(ploidy_file=None, prior=False, joint_ins=False, joint_prior=False, qual=False, theta=COHORT_QUAL_THETA, qc=None):
     """The rules between the options of a cohort run (run_cohort, predict-genotype.py --cohort): ValueError with the first broken rule's text"""
     if joint_ins and (ploidy_file is not None or prior):
         raise ValueError(JOINT_INS_COHORT)
@@ -925,10 +1025,12 @@ def check_cohort_options(ploidy_file=None, prior=False, joint_ins=False, joint_p
         raise ValueError(COHORT_THETA_RANGE)
     if joint_ins and qual:
         raise ValueError(JOINT_INS_QUAL)
+    if qc is not None and not qc:
+        raise ValueError(COHORT_QC_PREFIX)
 
 
 def run_cohort(list_path, vcf_path, out_path, min_support=3, err=0.00005, device=0, ploidy_file=None, prior=False, joint_ins=False, qual=False,
-               theta=COHORT_QUAL_THETA, joint_prior=False):
+               theta=COHORT_QUAL_THETA, joint_prior=False, qc=None):
     """predict-genotype.py --cohort: the samples of a cohort list (load_cohort_list), one multi-sample VCF.  Sample column s is what the
     reference writes as SAMPLE for sample s alone; INFO gains NS, AN, AC and AF.  ploidy_file (--cohort-ploidy, load_cohort_ploidy_file): a
     ploidy per sample and contig or region; column s is then what --ploidy-file with the sample's lines writes for sample s alone, and AN is
@@ -941,9 +1043,11 @@ def run_cohort(list_path, vcf_path, out_path, min_support=3, err=0.00005, device
     of the file stays what it is without it.  joint_prior (--joint-prior, with joint_ins only): the samples of a site inform each other — the
     frequencies of the site's alleles by EM (svjg_genotype_cohort_sites_prior); a member row prints GT:DP:AD:PL:SGT:SAL:SGQ with GT the projection of the
     POSTERIOR site call and SGT that call, NS / AC / AN / AF come from the posterior calls, EMAF and EMNC follow them; every non-member row stays the
-    plain cohort row.  -> the number of genotyped rows of every sample"""
+    plain cohort row.  qc (--cohort-qc PREFIX, with any of the above): svjg_cohort_qc on the calls the file prints (printed_gt, calls.done) — with prior the
+    posterior calls, with joint_ins a member row's projected site calls — and, once the VCF has been written, PREFIX.samples.tsv (write_qc_samples) and PREFIX.pairs.tsv
+    (write_qc_pairs); no byte of the VCF changes.  -> the number of genotyped rows of every sample"""
     from . import capi, filter as flt
-    check_cohort_options(ploidy_file, prior, joint_ins, joint_prior, qual, theta)     # (before anything is read, asked of the device or written)
+    check_cohort_options(ploidy_file, prior, joint_ins, joint_prior, qual, theta, qc)     # (before anything is read, asked of the device or written)
     samples = load_cohort_list(list_path)                       # (raises before any output exists)
     names = [name for name, _ in samples]
     regions = load_cohort_ploidy_file(ploidy_file, names) if ploidy_file is not None else None   # (so does this)
@@ -962,9 +1066,13 @@ def run_cohort(list_path, vcf_path, out_path, min_support=3, err=0.00005, device
         calls = genotype_cohort_rows(ctx, rows, len(samples), min_support, err, ploidy, prior)
         joint = cohort_joint_sites(ctx, rows, calls.gt, calls.site, min_support, err, prior=joint_prior) if joint_ins else None
         site_qual = cohort_qual_rows(ctx, rows, len(samples), ploidy, err, theta) if qual else None
+        qc_counts = cohort_qc_rows(ctx, printed_gt(calls, joint), calls.done, ploidy) if qc is not None else None
     finally:
         ctx.close()
     n_done = write_vcf_cohort(out_path, rows, names, calls, ploidy, joint, site_qual)
+    if qc is not None:
+        write_qc_samples(qc + ".samples.tsv", names, qc_counts[0])
+        write_qc_pairs(qc + ".pairs.tsv", names, qc_counts[1])
     for name, n in zip(names, n_done):
         print("Genotyped svs (%s): %d" % (name, n))
     return n_done
