@@ -455,6 +455,34 @@ int svjg_cohort_qual(svjg_ctx *ctx, const uint8_t *sv_type, const uint32_t *slot
 int svjg_cohort_qc(svjg_ctx *ctx, const uint8_t *gt /* [n_rows][n_samples] */, const uint8_t *ploidy /* [n_rows][n_samples], or NULL */,
                    uint64_t n_rows, uint32_t n_samples, uint32_t *sample /* [n_samples][6] */, uint32_t *pair /* [n_samples (n_samples - 1) / 2][5] */);
 
+/* svjg_cohort_hwe: the sites of a cohort, from the calls a cohort run has made (--cohort-hwe): do a row's genotypes fit Hardy-Weinberg
+ * proportions?  gt[n_rows][n_samples] = the calls, ploidy the same shape or NULL (2 everywhere).  An item enters iff it is a called diploid item,
+ * the dip predicate of svjg_cohort_qc: P = 2 and g <= 2 (haploid, polyploid and ploidy-0 items and both no-call codes drop out).  Per row:
+ * counts[r][3] = n_ref, n_het, n_alt, the entering items with g = 0, 1, 2; n their sum, nA = 2 n_alt + n_het, nB = 2 n_ref + n_het, m = min(nA, nB).
+ * For every h of m's parity in 0..m, with a = (m - h) / 2 and b = (2 n - m - h) / 2, the weight is w(h) = 2^h n! / (a! h! b!), the number of ways to
+ * have h heterozygotes among n diploids with m minor alleles (Wigginton et al. 2005).  p[r][0] = HWE, the two-sided exact test: the sum of w(h)
+ * over the h with w(h) 10^7 <= w(n_het) (10^7 + 1) — the 1e-7 slack is the tie rule of R's fisher.test: exact ties occur — over the sum of all
+ * w(h); p[r][1] = EXCHET, the one-sided test for excess heterozygotes: the sum over h >= n_het over the same total.  m = 0: both exactly 1.0;
+ * n = 0: both NaN.  The model in Python integers is tests/cohort_hwe_model.py; the device forms log10 w(h) in double-double from the log10(i!)
+ * table, every term relative to the h next to the mean nA nB / (2 n - 1), and sums doubles in a fixed order: within 1e-9 relative of the model
+ * wherever the model is at least 1e-280 and no weight lies within 1e-8 of the tie rule's edge (asserted; the observed maximum is in DESIGN 4.3),
+ * below that a value of at most 1e-279, possibly 0.  One kernel, one row a wave segment, no atomics: equal bytes from run to run, and a row's bytes
+ * do not depend on the rows around it or on how the caller chunks the rows.  The call reads the log10(i!) table — it reserves 2 n_samples + 1
+ * entries through svjg_logfact_reserve's path before it launches — and neither needs nor reads the cohort matrix or the count vector; it works
+ * in a block of its own: it neither reads nor changes any other call's block or views.  The caller bounds memory by calling with row chunks:
+ * 1 byte per item (2 with a ploidy array) and 28 bytes per row, on the device and the host.  n_rows = 0 returns 0 and writes nothing.
+ * SVJG_E_ARG with a message in svjg_last_error, all found before any launch: a null gt, counts or p, n_samples = 0 or above
+ * SVJG_HWE_MAX_SAMPLES, n_rows x n_samples beyond 2^40, n_rows >= 2^32.  svjg_last_kernel_ms reports the kernel as genotype_ms.
+ * Measured once, with the change that added it (one MI355X, 2026-10-21, ROCm 7.2.0, tools/cohort_hwe_timing.py: genotypes in Hardy-Weinberg
+ * proportions at a frequency per row in 0.01 .. 0.5, no ploidy array, median of 10 calls behind 3, run twice in one process; genotype_ms, the
+ * kernel): 100 000 rows x 64 samples 0.163 / 0.159 ms, 10 000 rows x 2 048 samples 0.087 / 0.087 ms; a call from Python took 0.55 / 0.55 and
+ * 0.79 / 0.79 ms, the host harness (tests/hwe_sim, the same routines with g++ -O2, one thread) 305 and 218 ms for the same call, and the device's
+ * p-values lay within 2.1e-15 and 5.6e-15 relative of the harness's.  A first reading: nothing is compared against it, and nothing else has
+ * been measured. */
+#define SVJG_HWE_MAX_SAMPLES 65536
+int svjg_cohort_hwe(svjg_ctx *ctx, const uint8_t *gt /* [n_rows][n_samples] */, const uint8_t *ploidy /* [n_rows][n_samples], or NULL */,
+                    uint64_t n_rows, uint32_t n_samples, uint32_t *counts /* [n_rows][3]: n_ref, n_het, n_alt */, double *p /* [n_rows][2]: HWE, EXCHET */);
+
 /* ---- the whole pass in one call (what a fused svjedi-graph run and bench.py do per batch) -----------------------------------
  * svjg_set_rows copies the three per-row input arrays of svjg_genotype to the device once (they stay until the next
  * svjg_set_rows / svjg_destroy).  svjg_run_resident then does, for the resident text of svjg_gaf_upload and those rows:

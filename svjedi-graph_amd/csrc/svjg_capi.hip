@@ -82,7 +82,7 @@ constexpr uint64_t STAGE_PIECE = 8ull << 20;
 // hands out pointers into BLOCK_ROWS' twin and svjg_genotype_boundary reads it later, and both must survive calls of the other six.
 // A fused pass's slot holds the same pair (RunSlot).
 struct LegBlock { DevBuf<uint8_t> d;  PinBuf h; };
-enum { BLOCK_ROWS, BLOCK_PLOIDY, BLOCK_SITES, BLOCK_COHORT, BLOCK_COHORT_PLOIDY, BLOCK_COHORT_PRIOR, BLOCK_COHORT_SITES, BLOCK_COHORT_QUAL, BLOCK_COHORT_SITES_PRIOR, BLOCK_COHORT_QC, LEG_BLOCKS };   // rows_layout, ploidy_layout, sites_layout, cohort_layout for the three cohort blocks, sites_layout again, qual_layout, sites_layout with its prior switch, qc_layout (svjg_geno.h)
+enum { BLOCK_ROWS, BLOCK_PLOIDY, BLOCK_SITES, BLOCK_COHORT, BLOCK_COHORT_PLOIDY, BLOCK_COHORT_PRIOR, BLOCK_COHORT_SITES, BLOCK_COHORT_QUAL, BLOCK_COHORT_SITES_PRIOR, BLOCK_COHORT_QC, BLOCK_COHORT_HWE, LEG_BLOCKS };   // rows_layout, ploidy_layout, sites_layout, cohort_layout for the three cohort blocks, sites_layout again, qual_layout, sites_layout with its prior switch, qc_layout, hwe_layout (svjg_geno.h)
 
 // slots the passes of svjg_run_begin rotate through: two may be in flight, and the one the NEXT pass will use is zeroed while the newest computes
 constexpr int RUN_SLOTS = 3;
@@ -1546,6 +1546,52 @@ extern "C" int svjg_cohort_qc(svjg_ctx *c, const uint8_t *gt, const uint8_t *plo
     const uint8_t *hb = c->leg[BLOCK_COHORT_QC].h;
     memcpy(sample, hb + L.sample, S * QC_CLASSES * sizeof *sample);
     if (n_pairs) memcpy(pair, hb + L.pair, n_pairs * QC_PAIR_COUNTS * sizeof *pair);
+    return 0;
+}
+
+// ---- cohort site test for Hardy-Weinberg equilibrium (svjg.h: svjg_cohort_hwe; the model and the routines: svjg_geno.h) ----
+// Through genotype_leg in BLOCK_COHORT_HWE, a block of its own: the call bytes (and the ploidy bytes) go in, k_cohort_hwe over the rows — a wave
+// holds 64 / width rows (prior_segment_width), a block four waves, eight blocks a unit at the most, the rest in strides of the grid —, p[] and
+// counts[] come out.  The table's 2 S + 1 entries are reserved in front of the leg (svjg_logfact_reserve: the growth path of every caller), so the
+// kernel meets no n beyond it and the max_n pair, zeroed here, stays zero: the leg never runs the kernel twice.
+static int launch_cohort_hwe(svjg_ctx *c, HweArgs &p, unsigned int *max_n) {
+    p.logfact = c->d_logfact;
+    HIPCHK(c, hipMemsetAsync(max_n, 0, 8, c->stream));
+    const uint64_t rows_per_wave = 64u / prior_segment_width(p.S), waves = (p.n_rows + rows_per_wave - 1) / rows_per_wave;
+    const uint64_t blocks = (waves * 64 + TPB - 1) / TPB, cap = (uint64_t)c->n_cu * 8;
+    hipLaunchKernelGGL(k_cohort_hwe, dim3((uint32_t)(blocks < cap ? blocks : cap)), dim3(TPB), 0, c->stream, p);
+    HIPCHK(c, hipGetLastError());
+    return 0;
+}
+
+extern "C" int svjg_cohort_hwe(svjg_ctx *c, const uint8_t *gt, const uint8_t *ploidy, uint64_t n_rows, uint32_t n_samples, uint32_t *counts, double *p) {
+    if (!c) return SVJG_E_ARG;
+    static_assert(SVJG_HWE_MAX_SAMPLES == HWE_MAX_SAMPLES, "svjg.h and svjg_geno.h disagree");
+    const uint64_t S = n_samples;
+    if (S == 0) { c->err = "no sample"; return SVJG_E_ARG; }
+    if (S > HWE_MAX_SAMPLES) { c->err = "too many samples: n_samples is above SVJG_HWE_MAX_SAMPLES = 65536"; return SVJG_E_ARG; }
+    if (!gt || !counts || !p) { c->err = "a null array"; return SVJG_E_ARG; }
+    if (n_rows >= (1ull << 32)) { c->err = "too many rows for one call: take the rows in chunks"; return SVJG_E_ARG; }
+    if (n_rows > (1ull << 40) / S) { c->err = "too many items for one call: take the rows in chunks"; return SVJG_E_ARG; }
+    if (n_rows == 0) return 0;
+    HIPCHK(c, hipSetDevice(c->device));
+    const uint32_t entries = 2 * n_samples + 1;          // (a context without a table gets the first one of every leg, never a smaller one)
+    if (const int rc = svjg_logfact_reserve(c, entries > logfact_first() ? entries : logfact_first())) return rc;
+    const uint64_t n = n_rows * S;
+    const HweLayout L = hwe_layout(n_rows, S, ploidy != nullptr);
+    const int rc = genotype_leg(c, c->leg[BLOCK_COHORT_HWE], L,
+        [&](uint8_t *hb) {
+            memcpy(hb + L.gt, gt, n);
+            if (ploidy) memcpy(hb + L.ploidy, ploidy, n);
+        },
+        [&](uint8_t *base) {
+            HweArgs a{base + L.gt, ploidy ? base + L.ploidy : nullptr, n_rows, n_samples, nullptr, (uint32_t *)(base + L.counts), (double *)(base + L.p)};
+            return launch_cohort_hwe(c, a, (unsigned int *)(base + L.maxn));
+        });
+    if (rc) return rc;
+    const uint8_t *hb = c->leg[BLOCK_COHORT_HWE].h;
+    memcpy(counts, hb + L.counts, n_rows * 3 * sizeof *counts);
+    memcpy(p, hb + L.p, n_rows * 2 * sizeof *p);
     return 0;
 }
 

@@ -1121,6 +1121,75 @@ SVJG_HD void qc_tile_at(uint32_t t, uint32_t S, uint32_t &ti, uint32_t &tj) {   
     tj = qc_tile_first_j(ti) + t;
 }
 
+// ---- cohort site test for Hardy-Weinberg equilibrium (k_cohort_hwe) ----
+// Item (r, s) enters iff it is a called diploid item (the dip predicate of qc_class).  Per row n_ref, n_het, n_alt = the entering items with g = 0,
+// 1, 2 and n their sum; nA = 2 n_alt + n_het, nB = 2 n_ref + n_het, m = min(nA, nB).  For every h = m mod 2, + 2, .., m with a = (m - h) / 2 and
+// b = (2 n - m - h) / 2 the weight is w(h) = 2^h n! / (a! h! b!) (Wigginton et al. 2005).  HWE = sum of w(h) over the h with
+// w(h) <= (1 + 1e-7) w(n_het), over the sum of all; EXCHET = the same with h >= n_het.  m = 0: both 1.0; n = 0: both NaN.  On the device
+// u(h) = log10 w(h) - log10 n! = h log10 2 - log10 a! - log10 h! - log10 b! in double-double from the log10(i!) table (entries 0..n), every term is
+// 10^(u(h) - u(h0)) with h0 = the h of right parity next to nA nB / (2 n - 1), the mean of h: near the mode, so one pass is enough and a term that
+// underflows against it is 0, rightly.  The tie rule is decided on the double-double u(h) - u(n_het) against log10(1 + 1e-7).  Compiled without
+// fused multiply-adds, so the host harness (tests/hwe_sim) and the kernel differ in exp10 and in the table's log10 only.
+constexpr uint32_t HWE_MAX_SAMPLES = 65536;
+// log10 2 = HWE_L2_0 + HWE_L2_1 + HWE_L2_2, the first two of 30 and 29 significant bits: h times either is exact for every h <= 2^17
+constexpr double HWE_L2_0 = 0x1.34413508p-2, HWE_L2_1 = 0x1.f79fef3p-34, HWE_L2_2 = 0x1.1f12b35816f92p-66;
+constexpr double HWE_TIE_HI = 0x1.750e5c9d09872p-25, HWE_TIE_LO = 0x1.ea2bc03de8dp-80;       // log10(1 + 1e-7)
+
+// the three counts of an item added to a lane's (integer registers)
+SVJG_HD void hwe_count(uint32_t g, uint32_t P, uint32_t &n_ref, uint32_t &n_het, uint32_t &n_alt) {
+    const uint32_t c = qc_class(g, P), dip = (c >> QC_DIP) & 1u, het = (c >> QC_HET) & 1u, alt = (c >> QC_HOMALT) & 1u;
+    n_het += het; n_alt += alt; n_ref += dip - het - alt;
+}
+
+// what the test of a row needs of its counts: terms = the number of h (0: no test, n = 0 or m = 0), h = par + 2 t for t < terms
+struct HweRow { uint32_t n, m, par, het, h0, terms; };
+SVJG_HD HweRow hwe_row(uint32_t n_ref, uint32_t n_het, uint32_t n_alt) {
+    HweRow r{};
+    r.n = n_ref + n_het + n_alt; r.het = n_het;
+    const uint32_t nA = 2 * n_alt + n_het, nB = 2 * n_ref + n_het;
+    r.m = nA < nB ? nA : nB; r.par = r.m & 1u;
+    if (r.m == 0) return r;                              // (n = 0 too)
+    uint32_t h0 = (uint32_t)((uint64_t)nA * nB / (2ull * r.n - 1));      // <= m, as max(nA, nB) <= 2 n - 1 where m >= 1
+    if ((h0 ^ r.m) & 1u) ++h0;                           // (h0 = m has m's parity: never beyond m)
+    r.h0 = h0; r.terms = (r.m - r.par) / 2 + 1;
+    return r;
+}
+
+SVJG_HD dd hwe_h_log2(uint32_t h) {                      // h log10 2, h <= 2^17
+#ifdef __clang__
+#pragma clang fp contract(off)                           // the two exact products are rounded (not at all) before the exact sum
+#endif
+    const double x = (double)h, p0 = x * HWE_L2_0, p1 = x * HWE_L2_1, p2 = x * HWE_L2_2;
+    dd s = two_sum(p0, p1);
+    s.lo += p2;
+    return two_sum(s.hi, s.lo);
+}
+// u(h) of a row; h has m's parity and h <= m: a, h, b <= n index the table
+SVJG_HD dd hwe_log_weight(const dd *logfact, uint32_t n, uint32_t m, uint32_t h) {
+    const uint32_t a = (m - h) / 2, b = n - h - a;
+    return dd_add(hwe_h_log2(h), dd_neg(dd_add(dd_add(logfact[a], logfact[h]), logfact[b])));
+}
+// term t of a row added to a lane's three sums: all, selected by the tie rule, h >= n_het; u0 = u(h0), uhet = u(n_het)
+struct HweSums { double all, sel, exc; };
+SVJG_HD void hwe_term(const dd *logfact, const HweRow &r, dd u0, dd uhet, uint32_t t, HweSums &s) {
+#ifdef __clang__
+#pragma clang fp contract(off)
+#endif
+    const uint32_t h = r.par + 2 * t;
+    const dd u = hwe_log_weight(logfact, r.n, r.m, h), d = dd_add(u, dd_neg(u0));
+    const double x = prior_exp10(d.hi + d.lo);
+    s.all += x;
+    if (dd_cmp(dd_add(u, dd_neg(uhet)), dd{HWE_TIE_HI, HWE_TIE_LO}) <= 0) s.sel += x;
+    if (h >= r.het) s.exc += x;
+}
+// a row's HWE or EXCHET from its reduced sums: min(1, part / all) (all >= 1: the term of h0 is 10^0); 1.0 where m = 0, NaN where n = 0
+SVJG_HD double hwe_p(const HweRow &r, double part, double all) {
+    if (r.n == 0) return NAN;
+    if (r.m == 0) return 1.0;
+    const double p = part / all;
+    return p < 1.0 ? p : 1.0;
+}
+
 // ---- host side of a k_genotype launch: the table's size and where a call's rows lie, in plain integers (pinned without a GPU: tests/test_rows_layout.py) ----
 
 // entries of the log10(i!) table: the first one built; the one that holds max_n (the largest n the kernel met beyond the table, < LOGFACT_CAP) with room to spare
@@ -1136,7 +1205,7 @@ constexpr uint32_t logfact_reserve_to(uint32_t have, uint32_t entries) { return 
 struct RowsIn { uint64_t slot, type, ok, bytes; };
 inline RowsIn rows_in(uint64_t n, uint64_t at = 0) { return RowsIn{at, at + n * 4, at + n * 5, n * 6}; }
 
-// The nine step-by-step calls (svjg_genotype / _view, _ploidy, _sites, _cohort, _cohort_ploidy, _cohort_prior, _cohort_sites, svjg_cohort_qual, svjg_cohort_qc) each own one device block and its pinned host twin, all of ONE
+// The ten step-by-step calls (svjg_genotype / _view, _ploidy, _sites, _cohort, _cohort_ploidy, _cohort_prior, _cohort_sites, svjg_cohort_qual, svjg_cohort_qc, svjg_cohort_hwe) each own one device block and its pinned host twin, all of ONE
 // shape: the outputs (they end at out_end), the max_n pair 8-aligned, ONE contiguous input region right behind the pair, 64 spare bytes -> ONE copy
 // in (in_bytes from in_at), ONE copy out (maxn + 8 bytes from 0).  A layout below IS a LegSpan and adds only what is its own: its outputs and where its inputs lie.
 struct LegSpan { uint64_t maxn, in_at, in_bytes, total; };
@@ -1230,6 +1299,18 @@ inline QcLayout qc_layout(uint64_t n_rows, uint64_t S, bool per_item) {
     L.gt = L.in_at; L.ploidy = per_item ? L.gt + n : 0;
     L.planes = (L.in_at + L.in_bytes + 7) & ~7ull;
     L.total = L.planes + QC_PLANES * qc_words(n_rows) * S * 8 + 64;
+    return L;
+}
+
+// svjg_cohort_hwe: [ p 16 ] x n_rows (HWE, EXCHET), then [ counts 12 ] x n_rows (n_ref, n_het, n_alt) of output; the max_n pair is zeroed in front
+// of every launch and never written (the call reserves the table entries it reads before it launches).  in: the n_rows * S call bytes and,
+// per_item, as many ploidy bytes.
+struct HweLayout : LegSpan { uint64_t p, counts, gt, ploidy; };
+inline HweLayout hwe_layout(uint64_t n_rows, uint64_t S, bool per_item) {
+    HweLayout L{}; const uint64_t n = n_rows * S;
+    L.p = 0; L.counts = n_rows * 16;
+    leg_span(L, L.counts + n_rows * 12, n * (per_item ? 2 : 1));
+    L.gt = L.in_at; L.ploidy = per_item ? L.gt + n : 0;
     return L;
 }
 

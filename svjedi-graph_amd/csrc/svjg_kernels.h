@@ -2662,4 +2662,45 @@ __global__ __launch_bounds__(TPB) void k_qc_pairs(QcArgs p) {
     }
 }
 
+// ---- cohort site test for Hardy-Weinberg equilibrium (svjg.h: svjg_cohort_hwe; the model and the routines: svjg_geno.h) ----
+struct HweArgs {
+    const uint8_t *gt, *ploidy;          // [n_rows][S]; ploidy nullptr: 2 everywhere
+    uint64_t n_rows; uint32_t S;
+    const dd *logfact;                   // at least S + 1 entries (the host reserves 2 S + 1 before the launch)
+    uint32_t *counts; double *p;         // [n_rows][3], [n_rows][2]
+};
+
+// The division of the work is k_cohort_prior's: a row takes a segment of W = prior_segment_width(S) lanes, 64 / W rows share a wave, a row never
+// spans two; the waves stride over the rows.  Phase 1: lane j of a segment strides over the row's consecutive bytes j, j + W, .. (W = 64 wherever a
+// lane has a second item; neighbouring segments hold neighbouring rows: a wave's loads are consecutive bytes), counts its called diploid items by
+// call in three integer registers (hwe_count), and the xor butterfly leaves the row's three counts in every lane of the segment.  Phase 2: the
+// lanes stride over the terms t = j, j + W, .. < terms (hwe_term: three table entries, the double-double difference against u(h0), one exp10, three
+// lane sums in increasing t); the three sums go through the same butterfly, lane 0 of the segment stores the counts and the two ratios.  No shuffle
+// stands inside a loop whose length differs between the rows of a wave: all 64 lanes execute every one of them.  No atomics, no LDS, no scratch;
+// a row's bytes depend on its own items and on S alone — not on the grid, the chunk or its neighbours — and are equal from run to run.
+__global__ __launch_bounds__(TPB) void k_cohort_hwe(HweArgs p) {
+  const uint64_t S = p.S;
+  const uint32_t lane = threadIdx.x & 63u, W = prior_segment_width(S), rows_per_wave = 64u / W, j = lane & (W - 1), sub = lane / W;
+  const uint64_t n_waves = (p.n_rows + rows_per_wave - 1) / rows_per_wave;
+  for (uint64_t wv = ((uint64_t)blockIdx.x * blockDim.x + threadIdx.x) >> 6; wv < n_waves; wv += ((uint64_t)gridDim.x * blockDim.x) >> 6) {
+    const uint64_t r = wv * rows_per_wave + sub;
+    const bool mine = r < p.n_rows;
+    uint32_t n_ref = 0, n_het = 0, n_alt = 0;
+    if (mine)
+        for (uint64_t s = j; s < S; s += W) hwe_count(p.gt[r * S + s], p.ploidy ? p.ploidy[r * S + s] : 2u, n_ref, n_het, n_alt);
+    n_ref = prior_segment_sum(n_ref, W); n_het = prior_segment_sum(n_het, W); n_alt = prior_segment_sum(n_alt, W);
+    const HweRow row = hwe_row(n_ref, n_het, n_alt);
+    HweSums sum{0.0, 0.0, 0.0};
+    if (row.terms) {                                     // (0 for a row behind the last one)
+        const dd u0 = hwe_log_weight(p.logfact, row.n, row.m, row.h0), uhet = hwe_log_weight(p.logfact, row.n, row.m, row.het);
+        for (uint32_t t = j; t < row.terms; t += W) hwe_term(p.logfact, row, u0, uhet, t, sum);
+    }
+    sum.all = prior_segment_sum(sum.all, W); sum.sel = prior_segment_sum(sum.sel, W); sum.exc = prior_segment_sum(sum.exc, W);
+    if (mine && j == 0) {
+        p.counts[r * 3] = n_ref; p.counts[r * 3 + 1] = n_het; p.counts[r * 3 + 2] = n_alt;
+        p.p[r * 2] = hwe_p(row, sum.sel, sum.all); p.p[r * 2 + 1] = hwe_p(row, sum.exc, sum.all);
+    }
+  }
+}
+
 }  // namespace svjg

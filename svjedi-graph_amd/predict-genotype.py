@@ -9,6 +9,7 @@
     predict-genotype.py --cohort LIST --joint-ins --joint-prior -v VCF ...                  (extension: the samples of such a site inform each other, with SGQ)
     predict-genotype.py --cohort LIST --cohort-qual [--cohort-theta X] -v VCF ...           (extension: SVQ / MLAC / MLAF, the cohort's exact allele-count posterior)
     predict-genotype.py --cohort LIST --cohort-qc PREFIX -v VCF ...                         (extension: PREFIX.samples.tsv and PREFIX.pairs.tsv, per-sample sums and pairwise kinship)
+    predict-genotype.py --cohort LIST --cohort-hwe -v VCF ...                               (extension: DGC / HWE / EXCHET / FIS, the exact test of Hardy-Weinberg equilibrium per site)
 """
 import argparse
 import os
@@ -58,6 +59,10 @@ def main():
                     help="with --cohort, beside any other cohort option: write <prefix>.samples.tsv (per sample: eligible, called, carrier, diploid, het and "
                          "hom-alt rows, call rate, het / hom-alt) and <prefix>.pairs.tsv (per pair of samples: the KING-robust kinship over the rows both "
                          "are diploid on, and DUP / 1ST / 2ND / 3RD / UN) from the run's calls; the VCF stays byte for byte what it is without it (extension)")
+    ap.add_argument("--cohort-hwe", action="store_true",
+                    help="with --cohort, beside any other cohort option: INFO gains DGC (hom-ref, het and hom-alt calls), HWE (the exact two-sided test "
+                         "of Hardy-Weinberg equilibrium), EXCHET (the one-sided test for an excess of heterozygotes) and FIS, over the called diploid "
+                         "samples of each row, from the calls the file prints; everything else stays as without it (extension)")
     args = ap.parse_args()
     if args.cohort is not None and args.aln is not None:
         ap.error("exactly one of -d and --cohort")
@@ -67,14 +72,14 @@ def main():
     from svjg import genotype
     single = dict(ploidy=args.ploidy, ploidy_file=args.ploidy_file, joint_ins=args.joint_ins)
     cohort = dict(ploidy_file=args.cohort_ploidy, prior=args.cohort_prior, joint_ins=args.joint_ins, joint_prior=args.joint_prior, qual=args.cohort_qual,
-                  theta=genotype.COHORT_QUAL_THETA if args.cohort_theta is None else args.cohort_theta, qc=args.cohort_qc)
+                  theta=genotype.COHORT_QUAL_THETA if args.cohort_theta is None else args.cohort_theta, qc=args.cohort_qc, hwe=args.cohort_hwe)
     try:                                                         # the rules between the options themselves are the library's: one text each
         if args.cohort is None:
             for flag, given in (("--cohort-ploidy", args.cohort_ploidy is not None), ("--cohort-prior", args.cohort_prior)):
                 if given:
                     ap.error(flag + " needs --cohort")
             genotype.check_single_options(**single)
-            for flag, given in (("--joint-prior", args.joint_prior), ("--cohort-qual", args.cohort_qual)):
+            for flag, given in (("--joint-prior", args.joint_prior), ("--cohort-qual", args.cohort_qual), ("--cohort-hwe", args.cohort_hwe)):
                 if given:
                     ap.error(flag + " needs --cohort")
             if args.cohort_qc is not None:

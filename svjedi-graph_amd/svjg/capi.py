@@ -96,6 +96,7 @@ _SIGS = {
     "svjg_genotype_cohort_sites_prior": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_uint32, ctypes.c_double] + [ctypes.c_void_p] * 11),
     "svjg_cohort_qual": (ctypes.c_int, [ctypes.c_void_p] * 5 + [ctypes.c_uint32, ctypes.c_uint64, ctypes.c_double, ctypes.c_double] + [ctypes.c_void_p] * 3),
     "svjg_cohort_qc": (ctypes.c_int, [ctypes.c_void_p] * 3 + [ctypes.c_uint64, ctypes.c_uint32] + [ctypes.c_void_p] * 2),
+    "svjg_cohort_hwe": (ctypes.c_int, [ctypes.c_void_p] * 3 + [ctypes.c_uint64, ctypes.c_uint32] + [ctypes.c_void_p] * 2),
     "svjg_set_rows": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64]),
     "svjg_run_resident": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_uint64, ctypes.c_uint32, ctypes.c_double] + [ctypes.POINTER(ctypes.c_void_p)] * 5),
     "svjg_run_begin": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_uint64, ctypes.c_uint32, ctypes.c_double]),
@@ -119,6 +120,7 @@ MAX_PLOIDY = 8                      # svjg.h: SVJG_MAX_PLOIDY
 MAX_SITE_ALTS = 6                   # svjg.h: SVJG_MAX_SITE_ALTS
 SITE_GENOTYPES = 28                 # svjg.h: SVJG_SITE_GENOTYPES
 QC_MAX_SAMPLES = 2048               # svjg.h: SVJG_QC_MAX_SAMPLES
+HWE_MAX_SAMPLES = 65536             # svjg.h: SVJG_HWE_MAX_SAMPLES
 QUAL_THETA = 1e-3                   # the default theta of the site quality (svjg_cohort_qual; the library takes a value in (0, 0.05])
 _lib = None
 _host_lib = None
@@ -647,6 +649,24 @@ class Context:
         self._chk(self.lib.svjg_cohort_qc(self.h, gt.ctypes.data, None if ploidy is None else ploidy.ctypes.data, n, S, sample.ctypes.data,
                                           pair.ctypes.data if len(pair) else None))
         return sample, pair
+
+    def cohort_hwe(self, gt, ploidy=None):
+        """The sites of a cohort from its calls (svjg_cohort_hwe): gt[n, S] = alt copies, ploidy[n, S] or None (2 everywhere); only the called
+        diploid items of a row enter (ploidy 2 and gt <= 2).  It reads nothing of the context's matrix or counts.
+        -> (counts[n, 3] = n_ref, n_het, n_alt, uint32; p[n, 2] = HWE, the two-sided exact test, and EXCHET, the one-sided one for excess
+        heterozygotes, float64: 1.0 for a row without a minor allele, NaN for a row without an item)"""
+        gt = np.ascontiguousarray(gt, dtype=np.uint8)
+        if gt.ndim != 2:
+            raise ValueError("gt must be [n_rows, n_samples]")
+        n, S = gt.shape
+        if ploidy is not None:
+            ploidy = np.ascontiguousarray(ploidy, dtype=np.uint8)
+            if ploidy.shape != gt.shape:
+                raise ValueError("ploidy must have gt's shape")
+        counts, p = np.empty((n, 3), np.uint32), np.empty((n, 2), np.float64)
+        self._chk(self.lib.svjg_cohort_hwe(self.h, gt.ctypes.data, None if ploidy is None else ploidy.ctypes.data, n, S, counts.ctypes.data,
+                                           p.ctypes.data))
+        return counts, p
 
     def genotype_cohort_sites(self, slots, min_support, err):
         """genotype_sites for every sample of the cohort matrix in one launch (svjg_genotype_cohort_sites).  slots[n, 6]: the CANDIDATE slots of each

@@ -584,18 +584,23 @@ def cohort_union(samples):
     return list(slot_of), per
 
 
-def cohort_info(info, ns, ac, an=None, em=None, qual=None):
+def cohort_info(info, ns, ac, an=None, em=None, qual=None, hwe=None):
     """the INFO column of a cohort row: the input's without any NS= / AN= / AC= / AF= field (whole fields, exact key), a lone `.` replaced,
     then NS, AN (2 NS unless given: the called samples' ploidies summed, --cohort-ploidy), AC and, when AN > 0, AF = "%.6g" % (AC / AN).
     em (--cohort-prior): (f, not_converged) of the row's EM — the input's EMAF= and EMNC fields are dropped too, EMAF = "%.6g" % f follows
     unless f is NaN (no estimate), and the flag EMNC when the step cap was reached.  qual (--cohort-qual): (svq, mlac, chroms) of the row's
     allele-count posterior — the input's SVQ= / MLAC= / MLAF= fields are dropped too; behind everything else SVQ = "%.2f" % svq unless it is NaN
-    (a value that prints as -0.00 prints 0.00) and, where chroms > 0, MLAC and MLAF = "%.6g" % (mlac / chroms)"""
+    (a value that prints as -0.00 prints 0.00) and, where chroms > 0, MLAC and MLAF = "%.6g" % (mlac / chroms).  hwe (--cohort-hwe):
+    ((n_ref, n_het, n_alt), p_hwe, p_exchet) of the row's called diploid samples — the input's DGC= / HWE= / EXCHET= / FIS= fields are dropped too;
+    behind everything else DGC always, HWE and EXCHET = "%.6g" where there is an item (n > 0), FIS = "%.6g" % hwe_fis where there is a minor
+    allele (a text of -0 prints 0)"""
     keep = [f for f in info.split(";") if not f.startswith(_SITE_TAGS)]
     if em is not None:
         keep = [f for f in keep if f.split("=", 1)[0] not in _EM_KEYS]
     if qual is not None:
         keep = [f for f in keep if f.split("=", 1)[0] not in _QUAL_KEYS]
+    if hwe is not None:
+        keep = [f for f in keep if f.split("=", 1)[0] not in _HWE_KEYS]
     if keep == ["."]:
         keep = []
     if an is None:
@@ -616,6 +621,15 @@ def cohort_info(info, ns, ac, an=None, em=None, qual=None):
             keep.append("SVQ=%s" % ("0.00" if text == "-0.00" else text))
         if chroms > 0:
             keep += ["MLAC=%d" % mlac, "MLAF=%s" % ("%.6g" % (mlac / chroms))]
+    if hwe is not None:
+        dgc, p_hwe, p_exc = hwe
+        keep.append("DGC=%d,%d,%d" % tuple(dgc))
+        if sum(dgc) > 0:
+            keep += ["HWE=%s" % ("%.6g" % p_hwe), "EXCHET=%s" % ("%.6g" % p_exc)]
+        fis = hwe_fis(*dgc)
+        if fis is not None:
+            text = "%.6g" % fis
+            keep.append("FIS=%s" % ("0" if text == "-0" else text))
     return ";".join(keep)
 
 
@@ -663,13 +677,14 @@ def _joint_columns(rows, raw, plain, joint):
     return columns
 
 
-def write_vcf_cohort(out_path, rows, names, calls, ploidy=None, joint=None, qual=None):
+def write_vcf_cohort(out_path, rows, names, calls, ploidy=None, joint=None, qual=None, hwe=None):
     """The one cohort writer: write_vcf with one column per sample of `calls` (CohortCalls), the site tags' INFO lines in front of the header and
     the tags in INFO.  ploidy ([n, S]; None: diploid arrays, `Number=3`): every item in write_vcf_ploidy's forms and `Number=G` in the PL header
     line.  calls.gq: one more FORMAT field, GQ; calls.af and em_steps: EMAF / EMNC in INFO.  joint (JointSites): its site words stand for the
     calls', the member rows are printed by _joint_columns under SITE_FORMAT_LINES; joint.em: EMAF / EMNC in the member rows' INFO, and
     SITE_PRIOR_FORMAT_LINE behind SAL's.  qual (cohort_qual_rows): (svq[n], mlac[n], chroms[n]), SVQ / MLAC / MLAF behind the other tags in INFO
-    and their header lines; the QUAL column stays the input's.  -> the number of genotyped rows of every sample"""
+    and their header lines; the QUAL column stays the input's.  hwe (cohort_hwe_rows): (counts[n, 3], p[n, 2]), DGC / HWE / EXCHET / FIS behind all
+    of them and their header lines behind all other INFO lines.  -> the number of genotyped rows of every sample"""
     columns, n_done = _item_columns(rows, ploidy, calls.gt, calls.pl, calls.raw, calls.done, calls.gq)
     header = FORMAT_HEADER if ploidy is None else FORMAT_HEADER.replace(_PL_3, _PL_G)
     site, em = calls.site, None                                  # em: row -> (frequency, not_converged) for the rows that have an EM
@@ -682,13 +697,15 @@ def write_vcf_cohort(out_path, rows, names, calls, ploidy=None, joint=None, qual
     if calls.af is not None:
         not_converged = (np.asarray(calls.em_steps).astype(np.int64) & EM_NOT_CONVERGED) != 0
         em = dict(enumerate(zip(np.asarray(calls.af, dtype=np.float64).tolist(), not_converged.tolist())))
-    info_lines = COHORT_INFO_LINES + (COHORT_PRIOR_INFO_LINES if em is not None else "") + (COHORT_QUAL_INFO_LINES if qual is not None else "")
+    info_lines = COHORT_INFO_LINES + (COHORT_PRIOR_INFO_LINES if em is not None else "") + (COHORT_QUAL_INFO_LINES if qual is not None else "") + (
+        COHORT_HWE_INFO_LINES if hwe is not None else "")
     header = info_lines + header.replace("\tFORMAT\tSAMPLE\n", "\tFORMAT\t" + "\t".join(names) + "\n")
     has_an = np.shape(site)[1] == 3
 
     def info(v, text):
         return cohort_info(text, int(site[v, 0]), int(site[v, -1]), int(site[v, 1]) if has_an else None, None if em is None else em.get(v),
-                           None if qual is None else (float(qual[0][v]), int(qual[1][v]), int(qual[2][v])))
+                           None if qual is None else (float(qual[0][v]), int(qual[1][v]), int(qual[2][v])),
+                           None if hwe is None else (tuple(int(x) for x in hwe[0][v]), float(hwe[1][v][0]), float(hwe[1][v][1])))
     _write_rows(out_path, rows, header, columns, info)
     return n_done
 
@@ -1015,8 +1032,55 @@ def write_qc_pairs(path, names, pair):
                                                                     "." if phi is None else kinship_text(phi), "." if phi is None else relation(phi)))
 
 
-def check_cohort_options(ploidy_file=None, prior=False, joint_ins=False, joint_prior=False, qual=False, theta=COHORT_QUAL_THETA, qc=None):
-    """The rules between the options of a cohort run (run_cohort, predict-genotype.py --cohort): ValueError with the first broken rule's text"""
+# ---- cohort site test for Hardy-Weinberg equilibrium (--cohort LIST --cohort-hwe): svjg_cohort_hwe on the calls the run has made, DGC / HWE / EXCHET / FIS in INFO ----
+
+COHORT_HWE_INFO_LINES = (
+    '##INFO=<ID=DGC,Number=3,Type=Integer,Description="Genotype counts hom-ref, het, hom-alt, called diploid samples only">\n'
+    '##INFO=<ID=HWE,Number=1,Type=Float,Description="Exact two-sided test of Hardy-Weinberg equilibrium (Wigginton et al. 2005), called diploid samples only">\n'
+    '##INFO=<ID=EXCHET,Number=1,Type=Float,Description="Exact one-sided test for an excess of heterozygotes, called diploid samples only">\n'
+    '##INFO=<ID=FIS,Number=1,Type=Float,Description="Inbreeding coefficient 1 - observed / expected heterozygotes, called diploid samples only">\n'
+)
+_HWE_KEYS = ("DGC", "HWE", "EXCHET", "FIS")
+
+
+def hwe_fis(n_ref, n_het, n_alt):
+    """the inbreeding coefficient of a row from svjg_cohort_hwe's counts, in Python integers and ONE true division: 1 - n_het 2 n / (nA nB) with
+    nA = 2 n_alt + n_het, nB = 2 n_ref + n_het; None where min(nA, nB) = 0 (no minor allele: no estimate)"""
+    n_ref, n_het, n_alt = int(n_ref), int(n_het), int(n_alt)
+    nA, nB = 2 * n_alt + n_het, 2 * n_ref + n_het
+    if min(nA, nB) == 0:
+        return None
+    return 1 - n_het * 2 * (n_ref + n_het + n_alt) / (nA * nB)
+
+
+def cohort_hwe_chunk_rows(n_samples, per_item=False):
+    """rows per svjg_cohort_hwe call, so that it stays under 1 GiB (svjg.h: 1 byte an item, 2 with a ploidy array, 28 bytes a row) and under the
+    call's 2^32 rows"""
+    S = max(1, int(n_samples))
+    return max(1, min((1 << 32) - 1, (COHORT_CALL_BYTES - 256) // (S * (2 if per_item else 1) + 28)))
+
+
+def cohort_hwe_rows(ctx, gt, done, ploidy, step=None):
+    """svjg_cohort_hwe over all rows of a cohort run's calls: gt[n, S] and done[n, S] as CohortCalls has them — an item with done == 0 goes in as
+    0xFF, not called whatever its ploidy, as in cohort_qc_rows —, ploidy[n, S] or None (diploid).  Rows in chunks of `step` (None:
+    cohort_hwe_chunk_rows), concatenated: a row's numbers do not depend on its chunk.  -> (counts[n, 3] uint32, p[n, 2] float64)"""
+    gt = np.where(np.asarray(done) != 0, np.asarray(gt, dtype=np.uint8), np.uint8(NO_CALL)).astype(np.uint8)
+    n, S = gt.shape
+    if ploidy is not None:
+        ploidy = np.ascontiguousarray(ploidy, dtype=np.uint8)
+    if step is None:
+        step = cohort_hwe_chunk_rows(S, ploidy is not None)
+    counts, p = [np.zeros((0, 3), np.uint32)], [np.zeros((0, 2), np.float64)]
+    for at in range(0, n, int(step)):
+        c, q = ctx.cohort_hwe(gt[at:at + step], None if ploidy is None else ploidy[at:at + step])
+        counts.append(np.asarray(c, dtype=np.uint32).reshape(-1, 3))
+        p.append(np.asarray(q, dtype=np.float64).reshape(-1, 2))
+    return np.concatenate(counts), np.concatenate(p)
+
+
+def check_cohort_options(ploidy_file=None, prior=False, joint_ins=False, joint_prior=False, qual=False, theta=COHORT_QUAL_THETA, qc=None, hwe=False):
+    """The rules between the options of a cohort run (run_cohort, predict-genotype.py --cohort): ValueError with the first broken rule's text
+    (hwe, --cohort-hwe, stands beside every other option: no rule names it)"""
     if joint_ins and (ploidy_file is not None or prior):
         raise ValueError(JOINT_INS_COHORT)
     if joint_prior and not joint_ins:
@@ -1030,7 +1094,7 @@ def check_cohort_options(ploidy_file=None, prior=False, joint_ins=False, joint_p
 
 
 def run_cohort(list_path, vcf_path, out_path, min_support=3, err=0.00005, device=0, ploidy_file=None, prior=False, joint_ins=False, qual=False,
-               theta=COHORT_QUAL_THETA, joint_prior=False, qc=None):
+               theta=COHORT_QUAL_THETA, joint_prior=False, qc=None, hwe=False):
     """predict-genotype.py --cohort: the samples of a cohort list (load_cohort_list), one multi-sample VCF.  Sample column s is what the
     reference writes as SAMPLE for sample s alone; INFO gains NS, AN, AC and AF.  ploidy_file (--cohort-ploidy, load_cohort_ploidy_file): a
     ploidy per sample and contig or region; column s is then what --ploidy-file with the sample's lines writes for sample s alone, and AN is
@@ -1045,9 +1109,11 @@ def run_cohort(list_path, vcf_path, out_path, min_support=3, err=0.00005, device
     POSTERIOR site call and SGT that call, NS / AC / AN / AF come from the posterior calls, EMAF and EMNC follow them; every non-member row stays the
     plain cohort row.  qc (--cohort-qc PREFIX, with any of the above): svjg_cohort_qc on the calls the file prints (printed_gt, calls.done) — with prior the
     posterior calls, with joint_ins a member row's projected site calls — and, once the VCF has been written, PREFIX.samples.tsv (write_qc_samples) and PREFIX.pairs.tsv
-    (write_qc_pairs); no byte of the VCF changes.  -> the number of genotyped rows of every sample"""
+    (write_qc_pairs); no byte of the VCF changes.  hwe (--cohort-hwe, with any of the above): svjg_cohort_hwe on the same printed calls; INFO gains DGC, HWE,
+    EXCHET and FIS behind every other tag (cohort_info), the header their four lines; every other byte stays what it is without it.
+    -> the number of genotyped rows of every sample"""
     from . import capi, filter as flt
-    check_cohort_options(ploidy_file, prior, joint_ins, joint_prior, qual, theta, qc)     # (before anything is read, asked of the device or written)
+    check_cohort_options(ploidy_file, prior, joint_ins, joint_prior, qual, theta, qc, hwe)     # (before anything is read, asked of the device or written)
     samples = load_cohort_list(list_path)                       # (raises before any output exists)
     names = [name for name, _ in samples]
     regions = load_cohort_ploidy_file(ploidy_file, names) if ploidy_file is not None else None   # (so does this)
@@ -1067,9 +1133,10 @@ def run_cohort(list_path, vcf_path, out_path, min_support=3, err=0.00005, device
         joint = cohort_joint_sites(ctx, rows, calls.gt, calls.site, min_support, err, prior=joint_prior) if joint_ins else None
         site_qual = cohort_qual_rows(ctx, rows, len(samples), ploidy, err, theta) if qual else None
         qc_counts = cohort_qc_rows(ctx, printed_gt(calls, joint), calls.done, ploidy) if qc is not None else None
+        site_hwe = cohort_hwe_rows(ctx, printed_gt(calls, joint), calls.done, ploidy) if hwe else None
     finally:
         ctx.close()
-    n_done = write_vcf_cohort(out_path, rows, names, calls, ploidy, joint, site_qual)
+    n_done = write_vcf_cohort(out_path, rows, names, calls, ploidy, joint, site_qual, site_hwe)
     if qc is not None:
         write_qc_samples(qc + ".samples.tsv", names, qc_counts[0])
         write_qc_pairs(qc + ".pairs.tsv", names, qc_counts[1])
