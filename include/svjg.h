@@ -476,7 +476,7 @@ int svjg_cohort_qc(svjg_ctx *ctx, const uint8_t *gt /* [n_rows][n_samples] */, c
  * Measured once, with the change that added it (one MI355X, 2026-10-21, ROCm 7.2.0, tools/cohort_hwe_timing.py: genotypes in Hardy-Weinberg
  * proportions at a frequency per row in 0.01 .. 0.5, no ploidy array, median of 10 calls behind 3, run twice in one process; genotype_ms, the
  * kernel): 100 000 rows x 64 samples 0.163 / 0.159 ms, 10 000 rows x 2 048 samples 0.087 / 0.087 ms; a call from Python took 0.55 / 0.55 and
- * 0.79 / 0.79 ms, the host harness (tests/hwe_sim, the same routines with g++ -O2, one thread) 305 and 218 ms for the same call, and the device's
+ * 0.79 / 0.79 ms, the host harness (tests/geno_sim, the same routines with g++ -O2, one thread) 305 and 218 ms for the same call, and the device's
  * p-values lay within 2.1e-15 and 5.6e-15 relative of the harness's.  A first reading: nothing is compared against it, and nothing else has
  * been measured. */
 #define SVJG_HWE_MAX_SAMPLES 65536

@@ -1159,12 +1159,11 @@ static int launch_sites(svjg_ctx *c, GenoCohortSitesArgs &p, bool cohort) {
     return 0;
 }
 
-// k_cohort_sites_prior on what the cohort sites kernel left in the block.  Blocks of SITES_PRIOR_TPB = two waves, a wave holds 64 / width sites
-// (prior_segment_width); a block's 57 472 bytes of LDS let two blocks share a unit's 160 KiB; the rest in strides of the grid.
+// k_cohort_sites_prior on what the cohort sites kernel left in the block.  Blocks of SITES_PRIOR_TPB = two waves, a site a segment of a wave
+// (svjg_geno.h: segment_grid).
 static int launch_sites_prior(svjg_ctx *c, CohortSitesPriorArgs &p) {
-    const uint64_t per_wave = 64u / prior_segment_width(p.n_samples), waves = (p.n_sites + per_wave - 1) / per_wave;
-    const uint64_t blocks = (waves * 64 + SITES_PRIOR_TPB - 1) / SITES_PRIOR_TPB, cap = (uint64_t)c->n_cu * 2;
-    hipLaunchKernelGGL(k_cohort_sites_prior, dim3((uint32_t)(blocks < cap ? blocks : cap)), dim3(SITES_PRIOR_TPB), 0, c->stream, p);
+    const uint32_t grid = segment_grid(p.n_sites, p.n_samples, SITES_PRIOR_TPB, (uint32_t)c->n_cu, SITES_PRIOR_BLOCKS_PER_CU);
+    hipLaunchKernelGGL(k_cohort_sites_prior, dim3(grid), dim3(SITES_PRIOR_TPB), 0, c->stream, p);
     HIPCHK(c, hipGetLastError());
     return 0;
 }
@@ -1345,8 +1344,7 @@ static int launch_cohort(svjg_ctx *c, GenoCohortArgs &p, bool per_item) {
     return 0;
 }
 
-// k_cohort_prior on what the cohort kernel left in the block.  Blocks: a wave holds 64 / width rows (prior_segment_width), a block four waves, eight
-// blocks a unit at the most; the rest in strides of the grid.
+// k_cohort_prior on what the cohort kernel left in the block.  Blocks of four waves, a row a segment of a wave (svjg_geno.h: segment_grid).
 constexpr bool PRIOR_STAGE_DEFAULT = true;                          // measured: see k_cohort_prior
 static int launch_cohort_prior(svjg_ctx *c, CohortPriorArgs &p) {
     const char *e = getenv("SVJG_PRIOR_STAGE");                   // "lds" / "recompute": the other way for the items beyond a lane's first (tools/cohort_prior_timing.py)
@@ -1354,9 +1352,8 @@ static int launch_cohort_prior(svjg_ctx *c, CohortPriorArgs &p) {
     p.staged = PRIOR_STAGE_DEFAULT ? (uint32_t)(further < PRIOR_STAGE_MAX ? further : PRIOR_STAGE_MAX) : 0u;
     if (e && !strcmp(e, "recompute")) p.staged = 0;
     if (e && !strcmp(e, "lds")) p.staged = (uint32_t)(further < PRIOR_STAGE_MAX ? further : PRIOR_STAGE_MAX);
-    const uint64_t rows_per_wave = 64u / prior_segment_width(p.n_samples), waves = (p.n_rows + rows_per_wave - 1) / rows_per_wave;
-    const uint64_t blocks = (waves * 64 + TPB - 1) / TPB, cap = (uint64_t)c->n_cu * 8;
-    hipLaunchKernelGGL(k_cohort_prior, dim3((uint32_t)(blocks < cap ? blocks : cap)), dim3(TPB), prior_stage_bytes(p.staged, TPB), c->stream, p);
+    const uint32_t grid = segment_grid(p.n_rows, p.n_samples, TPB, (uint32_t)c->n_cu, PRIOR_BLOCKS_PER_CU);
+    hipLaunchKernelGGL(k_cohort_prior, dim3(grid), dim3(TPB), prior_stage_bytes(p.staged, TPB), c->stream, p);
     HIPCHK(c, hipGetLastError());
     return 0;
 }
@@ -1499,9 +1496,8 @@ extern "C" int svjg_cohort_qual(svjg_ctx *c, const uint8_t *sv_type, const uint3
 // ---- cohort sample QC (svjg.h: svjg_cohort_qc; the model, the planes and the tiles: svjg_geno.h) ----
 // Through genotype_leg in BLOCK_COHORT_QC, a block of its own: the call bytes (and the ploidy bytes) go in; ONE memset zeroes sample[] and the max_n
 // pair behind it; k_qc_planes over the units, k_qc_pairs over the tiles (S >= 2), both in strides of a grid of at most QC_BLOCKS_PER_CU blocks a
-// unit (the pair kernel's 36 864 bytes of LDS and 4 waves a block admit that many); pair[] and sample[] come out.  Neither kernel reads the
-// log10(i!) table, the cohort matrix or the count vector, and the max_n pair stays zero: the leg never runs them twice.
-constexpr uint32_t QC_BLOCKS_PER_CU = 4;
+// unit (svjg_geno.h); pair[] and sample[] come out.  Neither kernel reads the log10(i!) table, the cohort matrix or the count vector, and the
+// max_n pair stays zero: the leg never runs them twice.
 static int launch_cohort_qc(svjg_ctx *c, const QcArgs &p) {
     HIPCHK(c, hipMemsetAsync(p.sample, 0, (uint64_t)p.S * 4 * QC_CLASSES + 8, c->stream));      // (the max_n pair lies right behind sample[]: qc_layout)
     const uint64_t cap = (uint64_t)c->n_cu * QC_BLOCKS_PER_CU, blocks = (qc_plane_units(p.n_words, p.S) + TPB - 1) / TPB;
@@ -1550,16 +1546,14 @@ extern "C" int svjg_cohort_qc(svjg_ctx *c, const uint8_t *gt, const uint8_t *plo
 }
 
 // ---- cohort site test for Hardy-Weinberg equilibrium (svjg.h: svjg_cohort_hwe; the model and the routines: svjg_geno.h) ----
-// Through genotype_leg in BLOCK_COHORT_HWE, a block of its own: the call bytes (and the ploidy bytes) go in, k_cohort_hwe over the rows — a wave
-// holds 64 / width rows (prior_segment_width), a block four waves, eight blocks a unit at the most, the rest in strides of the grid —, p[] and
-// counts[] come out.  The table's 2 S + 1 entries are reserved in front of the leg (svjg_logfact_reserve: the growth path of every caller), so the
-// kernel meets no n beyond it and the max_n pair, zeroed here, stays zero: the leg never runs the kernel twice.
+// Through genotype_leg in BLOCK_COHORT_HWE, a block of its own: the call bytes (and the ploidy bytes) go in, k_cohort_hwe over the rows — blocks
+// of four waves, a row a segment of a wave (svjg_geno.h: segment_grid) —, p[] and counts[] come out.  The table's 2 S + 1 entries are reserved in
+// front of the leg (svjg_logfact_reserve: the growth path of every caller), so the kernel meets no n beyond it and the max_n pair, zeroed here,
+// stays zero: the leg never runs the kernel twice.
 static int launch_cohort_hwe(svjg_ctx *c, HweArgs &p, unsigned int *max_n) {
     p.logfact = c->d_logfact;
     HIPCHK(c, hipMemsetAsync(max_n, 0, 8, c->stream));
-    const uint64_t rows_per_wave = 64u / prior_segment_width(p.S), waves = (p.n_rows + rows_per_wave - 1) / rows_per_wave;
-    const uint64_t blocks = (waves * 64 + TPB - 1) / TPB, cap = (uint64_t)c->n_cu * 8;
-    hipLaunchKernelGGL(k_cohort_hwe, dim3((uint32_t)(blocks < cap ? blocks : cap)), dim3(TPB), 0, c->stream, p);
+    hipLaunchKernelGGL(k_cohort_hwe, dim3(segment_grid(p.n_rows, p.S, TPB, (uint32_t)c->n_cu, HWE_BLOCKS_PER_CU)), dim3(TPB), 0, c->stream, p);
     HIPCHK(c, hipGetLastError());
     return 0;
 }

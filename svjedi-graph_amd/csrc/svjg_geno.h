@@ -671,6 +671,18 @@ SVJG_HD uint32_t prior_segment_width(uint64_t S) {
     while (w < m) w <<= 1;
     return w;
 }
+// The grid of a kernel that gives every row such a segment (k_cohort_prior, k_cohort_sites_prior, k_cohort_hwe), in blocks of tpb lanes: as many as
+// hold the waves of n_rows rows, at most blocks_per_cu on each of n_cu units; the kernel takes the rest in strides of the grid.
+SVJG_HD uint32_t segment_grid(uint64_t n_rows, uint64_t S, uint32_t tpb, uint32_t n_cu, uint32_t blocks_per_cu) {
+    const uint64_t rows_per_wave = 64u / prior_segment_width(S), waves = (n_rows + rows_per_wave - 1) / rows_per_wave;
+    const uint64_t blocks = (waves * 64 + tpb - 1) / tpb, cap = (uint64_t)n_cu * blocks_per_cu;
+    return (uint32_t)(blocks < cap ? blocks : cap);
+}
+// the blocks a unit gets at the most, by launch
+constexpr uint32_t PRIOR_BLOCKS_PER_CU = 8;              // k_cohort_prior: blocks of four waves
+constexpr uint32_t SITES_PRIOR_BLOCKS_PER_CU = 2;        // k_cohort_sites_prior: a block's 57 472 bytes of LDS let two share a unit's 160 KiB
+constexpr uint32_t HWE_BLOCKS_PER_CU = 8;                // k_cohort_hwe: blocks of four waves
+constexpr uint32_t QC_BLOCKS_PER_CU = 4;                 // k_qc_planes, k_qc_pairs: the pair kernel's 36 864 bytes of LDS and 4 waves a block admit that many
 
 // ---- cohort sites with an allele-frequency prior (k_cohort_sites_prior behind k_genotype_cohort_sites) ----
 // The samples of a SITE inform each other: the frequencies p = (p_0..p_C) of the site's alleles are estimated by EM under Hardy-Weinberg, each item
@@ -1129,7 +1141,7 @@ SVJG_HD void qc_tile_at(uint32_t t, uint32_t S, uint32_t &ti, uint32_t &tj) {   
 // u(h) = log10 w(h) - log10 n! = h log10 2 - log10 a! - log10 h! - log10 b! in double-double from the log10(i!) table (entries 0..n), every term is
 // 10^(u(h) - u(h0)) with h0 = the h of right parity next to nA nB / (2 n - 1), the mean of h: near the mode, so one pass is enough and a term that
 // underflows against it is 0, rightly.  The tie rule is decided on the double-double u(h) - u(n_het) against log10(1 + 1e-7).  Compiled without
-// fused multiply-adds, so the host harness (tests/hwe_sim) and the kernel differ in exp10 and in the table's log10 only.
+// fused multiply-adds, so the host harness (tests/geno_sim, topic hwe) and the kernel differ in exp10 and in the table's log10 only.
 constexpr uint32_t HWE_MAX_SAMPLES = 65536;
 // log10 2 = HWE_L2_0 + HWE_L2_1 + HWE_L2_2, the first two of 30 and 29 significant bits: h times either is exact for every h <= 2^17
 constexpr double HWE_L2_0 = 0x1.34413508p-2, HWE_L2_1 = 0x1.f79fef3p-34, HWE_L2_2 = 0x1.1f12b35816f92p-66;

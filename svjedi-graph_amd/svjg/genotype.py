@@ -977,14 +977,21 @@ def cohort_qc_chunk_rows(n_samples, per_item=False):
     return max(1, min((1 << 32) - 1, (COHORT_CALL_BYTES - fixed) // (S * (2 if per_item else 1) + (3 * S + 7) // 8)))
 
 
-def cohort_qc_rows(ctx, gt, done, ploidy, step=None):
-    """svjg_cohort_qc over all rows of a cohort run's calls: gt[n, S] and done[n, S] as CohortCalls has them — an item with done == 0 goes in as
-    0xFF, not called whatever its ploidy —, ploidy[n, S] or None (diploid).  Rows in chunks of `step` (None: cohort_qc_chunk_rows); the chunks'
-    integer outputs are summed in int64, so any chunking gives the same numbers.  -> (sample[S, 6], pair[S (S - 1) / 2, 5]) int64"""
+def _masked_calls(gt, done, ploidy):
+    """what cohort_qc_rows and cohort_hwe_rows hand to the device: gt with NO_CALL where done == 0, its shape, ploidy contiguous or None
+    -> (gt, n, S, ploidy)"""
     gt = np.where(np.asarray(done) != 0, np.asarray(gt, dtype=np.uint8), np.uint8(NO_CALL)).astype(np.uint8)
     n, S = gt.shape
     if ploidy is not None:
         ploidy = np.ascontiguousarray(ploidy, dtype=np.uint8)
+    return gt, n, S, ploidy
+
+
+def cohort_qc_rows(ctx, gt, done, ploidy, step=None):
+    """svjg_cohort_qc over all rows of a cohort run's calls: gt[n, S] and done[n, S] as CohortCalls has them — an item with done == 0 goes in as
+    0xFF, not called whatever its ploidy —, ploidy[n, S] or None (diploid).  Rows in chunks of `step` (None: cohort_qc_chunk_rows); the chunks'
+    integer outputs are summed in int64, so any chunking gives the same numbers.  -> (sample[S, 6], pair[S (S - 1) / 2, 5]) int64"""
+    gt, n, S, ploidy = _masked_calls(gt, done, ploidy)
     if step is None:
         step = cohort_qc_chunk_rows(S, ploidy is not None)
     sample, pair = np.zeros((S, 6), np.int64), np.zeros((S * (S - 1) // 2, 5), np.int64)
@@ -1064,10 +1071,7 @@ def cohort_hwe_rows(ctx, gt, done, ploidy, step=None):
     """svjg_cohort_hwe over all rows of a cohort run's calls: gt[n, S] and done[n, S] as CohortCalls has them — an item with done == 0 goes in as
     0xFF, not called whatever its ploidy, as in cohort_qc_rows —, ploidy[n, S] or None (diploid).  Rows in chunks of `step` (None:
     cohort_hwe_chunk_rows), concatenated: a row's numbers do not depend on its chunk.  -> (counts[n, 3] uint32, p[n, 2] float64)"""
-    gt = np.where(np.asarray(done) != 0, np.asarray(gt, dtype=np.uint8), np.uint8(NO_CALL)).astype(np.uint8)
-    n, S = gt.shape
-    if ploidy is not None:
-        ploidy = np.ascontiguousarray(ploidy, dtype=np.uint8)
+    gt, n, S, ploidy = _masked_calls(gt, done, ploidy)
     if step is None:
         step = cohort_hwe_chunk_rows(S, ploidy is not None)
     counts, p = [np.zeros((0, 3), np.uint32)], [np.zeros((0, 2), np.float64)]

@@ -1,6 +1,6 @@
 """The host harness of svjg_geno.h (tests only): ONE library (geno_sim.cpp and the topic files it includes) and ONE stand-alone sanitizer program,
-built by tests/sim_build.py.  ploidy.py, site.py, cohort.py, prior.py, qual.py and site_prior.py hold the numpy-facing functions of a topic each; what they share
-is here."""
+built by tests/sim_build.py.  ploidy.py, site.py, cohort.py, prior.py, qual.py, site_prior.py, qc.py and hwe.py hold the numpy-facing functions of a topic
+each; what they share is here."""
 import ctypes
 import os
 
@@ -12,10 +12,10 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 SRC = os.path.join(HERE, "geno_sim.cpp")
 CSRC = os.path.join(HERE, "..", "..", "svjedi-graph_amd", "csrc")
 # exactly the files geno_sim.cpp includes; svjg_pass.h through svjg_geno.h (run_layout's DevStatus and GUARD_WORDS)
-DEPS = [os.path.join(HERE, t + ".inc") for t in ("ploidy", "site", "cohort", "prior", "qual", "site_prior")] + [
+DEPS = [os.path.join(HERE, t + ".inc") for t in ("ploidy", "site", "cohort", "prior", "qual", "site_prior", "qc", "hwe")] + [
     os.path.join(HERE, "..", "host_logfact.h"), os.path.join(CSRC, "svjg_geno.h"), os.path.join(CSRC, "svjg_pass.h")]
 PTR, U32, U64, INT, F64 = ctypes.c_void_p, ctypes.c_uint32, ctypes.c_uint64, ctypes.c_int, ctypes.c_double
-ROWS, PLOIDY, SITES, COHORT, QUAL = range(5)            # geno_sim.cpp: LAYOUT_*
+ROWS, PLOIDY, SITES, COHORT, QUAL, QC, HWE = range(7)           # geno_sim.cpp: LAYOUT_*
 
 
 def call(name, restype, argtypes, *args):

@@ -1,54 +1,24 @@
-// TEST HARNESS ONLY (never shipped, never loaded by the product): the cohort site test for Hardy-Weinberg equilibrium of svjg_geno.h compiled with
-// g++ — hwe_count, hwe_row, hwe_log_weight, hwe_term, hwe_p, prior_segment_width and hwe_layout are the kernel's own code; what is restated here in
-// plain C++ is k_cohort_hwe's loops over blocks, waves, segments and lanes (svjg_kernels.h), the lane order of the xor butterfly included, inside a
-// block laid out by hwe_layout, with the log10(i!) table of the host's libm (tests/host_logfact.h).  Driven from numpy (tests/hwe_sim/__init__.py).
-// With -DHWE_SIM_MAIN it is a stand-alone program (for -fsanitize=address,undefined) that runs seeded random calls against a brute-force count and
-// a recurrence in long double.
-#define SVJG_HD inline
-#include "../../svjedi-graph_amd/csrc/svjg_geno.h"
-#include "../host_logfact.h"
-#include <stdio.h>
-#include <stdlib.h>
-#include <string.h>
-#include <vector>
+// The cohort site test for Hardy-Weinberg equilibrium (svjg_geno.h: hwe_count, hwe_row, hwe_log_weight, hwe_term, hwe_p are the kernel's own code)
+// inside a plain C++ restatement of k_cohort_hwe's loops over blocks, waves, segments and lanes (svjg_kernels.h), the lane order of the xor
+// butterfly included (geno_sim.cpp: butterfly), in a block laid out by hwe_layout, with the log10(i!) table of the host's libm.  Topic `hwe` of the
+// stand-alone program runs seeded random calls against a brute-force count and a recurrence in long double.
 
-using namespace svjg;
-
-constexpr uint32_t SIM_TPB = 256;                        // svjg_kernels.h: TPB
-constexpr uint32_t SIM_BLOCKS_PER_CU = 8;                // svjg_capi.hip: launch_cohort_hwe
-
-extern "C" void hwesim_constants(uint32_t *out) {
-    const uint32_t v[3] = {HWE_MAX_SAMPLES, SIM_TPB, SIM_BLOCKS_PER_CU};
+extern "C" void genosim_hwe_constants(uint32_t *out) {
+    const uint32_t v[3] = {HWE_MAX_SAMPLES, SIM_TPB, HWE_BLOCKS_PER_CU};
     memcpy(out, v, sizeof v);
 }
-extern "C" uint32_t hwesim_segment_width(uint64_t S) { return prior_segment_width(S); }
-extern "C" void hwesim_layout(uint64_t n_rows, uint64_t S, int per_item, uint64_t *out) {
-    const HweLayout L = hwe_layout(n_rows, S, per_item != 0);
-    const uint64_t v[8] = {L.p, L.counts, L.maxn, L.in_at, L.in_bytes, L.gt, L.ploidy, L.total};
-    memcpy(out, v, sizeof v);
-}
-extern "C" void hwesim_row(uint32_t n_ref, uint32_t n_het, uint32_t n_alt, uint32_t *out) {
+extern "C" void genosim_hwe_row(uint32_t n_ref, uint32_t n_het, uint32_t n_alt, uint32_t *out) {
     const HweRow r = hwe_row(n_ref, n_het, n_alt);
     const uint32_t v[6] = {r.n, r.m, r.par, r.het, r.h0, r.terms};
     memcpy(out, v, sizeof v);
 }
 
-// the butterfly of prior_segment_sum over the 64 lanes of a wave: at every level a lane adds its partner's value of the level before
-template <class T>
-static void segment_sum(T *v, uint32_t width) {
-    for (uint32_t m = 1; m < width; m <<= 1) {
-        T old[64];
-        memcpy(old, v, sizeof old);
-        for (uint32_t l = 0; l < 64; ++l) v[l] = old[l] + old[l ^ m];
-    }
-}
-
 // The kernel over a call with a grid of `grid` blocks (0: what launch_cohort_hwe takes on n_cu units).  -> 0, or a code: 1 a store outside its
 // field, 2 an output word written twice or never, 3 a table entry read beyond the reserved ones, 4 the lanes of a segment disagree.
-extern "C" int hwesim_run(const uint8_t *gt, const uint8_t *ploidy, uint64_t n_rows, uint32_t S32, uint32_t grid, uint32_t n_cu, uint32_t *counts, double *p) {
+extern "C" int genosim_hwe_run(const uint8_t *gt, const uint8_t *ploidy, uint64_t n_rows, uint32_t S32, uint32_t grid, uint32_t n_cu, uint32_t *counts, double *p) {
     const uint64_t S = S32, n = n_rows * S;
     const HweLayout L = hwe_layout(n_rows, S, ploidy != nullptr);
-    std::vector<uint64_t> block((L.total + 7) / 8, 0xA5A5A5A5A5A5A5A5ull);
+    std::vector<uint64_t> block = poisoned_block(L.total);
     uint8_t *base = (uint8_t *)block.data();
     memcpy(base + L.gt, gt, n);
     if (ploidy) memcpy(base + L.ploidy, ploidy, n);
@@ -64,10 +34,7 @@ extern "C" int hwesim_run(const uint8_t *gt, const uint8_t *ploidy, uint64_t n_r
 
     const uint32_t W = prior_segment_width(S), rows_per_wave = 64u / W;
     const uint64_t n_waves = (n_rows + rows_per_wave - 1) / rows_per_wave;
-    uint64_t blocks = (n_waves * 64 + SIM_TPB - 1) / SIM_TPB;
-    const uint64_t cap = (uint64_t)(n_cu ? n_cu : 256) * SIM_BLOCKS_PER_CU;
-    if (blocks > cap) blocks = cap;
-    if (grid) blocks = grid;
+    const uint64_t blocks = grid ? grid : segment_grid(n_rows, S, SIM_TPB, n_cu ? n_cu : 256, HWE_BLOCKS_PER_CU);
     const uint64_t grid_waves = blocks * SIM_TPB / 64;
     for (uint64_t first = 0; first < grid_waves; ++first)
         for (uint64_t wv = first; wv < n_waves; wv += grid_waves) {
@@ -79,7 +46,7 @@ extern "C" int hwesim_run(const uint8_t *gt, const uint8_t *ploidy, uint64_t n_r
                 if (r < n_rows)
                     for (uint64_t at = j; at < S; at += W) hwe_count(d_gt[r * S + at], d_ploidy ? d_ploidy[r * S + at] : 2u, c[0][lane], c[1][lane], c[2][lane]);
             }
-            for (auto &x : c) segment_sum(x, W);
+            for (auto &x : c) butterfly<1>(x, 64, W);
             for (uint32_t lane = 0; lane < 64; ++lane) {
                 const uint32_t j = lane & (W - 1);
                 row[lane] = hwe_row(c[0][lane], c[1][lane], c[2][lane]);
@@ -91,7 +58,7 @@ extern "C" int hwesim_run(const uint8_t *gt, const uint8_t *ploidy, uint64_t n_r
                 }
                 s[0][lane] = sum.all; s[1][lane] = sum.sel; s[2][lane] = sum.exc;
             }
-            for (auto &x : s) segment_sum(x, W);
+            for (auto &x : s) butterfly<1>(x, 64, W);
             for (uint32_t lane = 0; lane < 64; ++lane) {
                 const uint32_t j = lane & (W - 1), sub = lane / W, l0 = lane - j;
                 const uint64_t r = wv * rows_per_wave + sub;
@@ -103,18 +70,15 @@ extern "C" int hwesim_run(const uint8_t *gt, const uint8_t *ploidy, uint64_t n_r
             }
         }
     for (uint8_t w : written) if (w != 1) return 2;
-    if (((const uint32_t *)(base + L.maxn))[0] || ((const uint32_t *)(base + L.maxn))[1]) return 1;
+    if (!maxn_stayed_zero(base, L.maxn)) return 1;
     memcpy(counts, d_counts, n_rows * 12);
     memcpy(p, d_p, n_rows * 16);
     return 0;
 }
 
-#ifdef HWE_SIM_MAIN
-static uint64_t rng_state = 0x9E3779B97F4A7C15ull;
-static uint32_t rnd() { rng_state ^= rng_state << 13; rng_state ^= rng_state >> 7; rng_state ^= rng_state << 17; return (uint32_t)(rng_state >> 32); }
-
+#ifdef GENO_SIM_MAIN
 // the definitions item by item, and the weights by their recurrence in long double from the largest one down and up (Wigginton's own order)
-static int brute(const std::vector<uint8_t> &gt, const uint8_t *ploidy, uint64_t R, uint32_t S, const std::vector<uint32_t> &counts, const std::vector<double> &p) {
+static int hwe_brute(const std::vector<uint8_t> &gt, const uint8_t *ploidy, uint64_t R, uint32_t S, const std::vector<uint32_t> &counts, const std::vector<double> &p) {
     for (uint64_t r = 0; r < R; ++r) {
         uint32_t want[3] = {};
         for (uint32_t s = 0; s < S; ++s) {
@@ -154,7 +118,7 @@ static int brute(const std::vector<uint8_t> &gt, const uint8_t *ploidy, uint64_t
     return 0;
 }
 
-int main() {
+static int main_hwe() {
     const uint32_t sizes[] = {1, 2, 3, 5, 31, 32, 33, 63, 64, 65, 130, 193, 400};
     const uint64_t rows[] = {1, 3, 65, 130};
     int cases = 0;
@@ -173,9 +137,9 @@ int main() {
                 std::vector<uint32_t> counts(R * 3);
                 std::vector<double> p(R * 2);
                 const uint8_t *ploidy = mode ? pl.data() : nullptr;
-                const int rc = hwesim_run(gt.data(), ploidy, R, S, cases % 2 ? 1 : 0, 256, counts.data(), p.data());
+                const int rc = genosim_hwe_run(gt.data(), ploidy, R, S, cases % 2 ? 1 : 0, 256, counts.data(), p.data());
                 if (rc) { fprintf(stderr, "hwe_sim: code %d at S %u rows %llu mode %d\n", rc, S, (unsigned long long)R, mode); return 1; }
-                const int bad = brute(gt, ploidy, R, S, counts, p);
+                const int bad = hwe_brute(gt, ploidy, R, S, counts, p);
                 if (bad) { fprintf(stderr, "hwe_sim: %s at S %u rows %llu mode %d\n", bad == 1 ? "counts differ" : bad == 2 ? "a row without a test is wrong" : "p differs", S, (unsigned long long)R, mode); return 1; }
                 ++cases;
             }

@@ -56,6 +56,7 @@ extern "C" uint32_t genosim_prior_item(uint32_t sv_type, uint32_t ref, uint32_t 
 }
 
 extern "C" uint32_t genosim_prior_width(uint64_t S) { return prior_segment_width(S); }
+extern "C" uint32_t genosim_segment_grid(uint64_t n_rows, uint64_t S, uint32_t tpb, uint32_t n_cu, uint32_t blocks_per_cu) { return segment_grid(n_rows, S, tpb, n_cu, blocks_per_cu); }
 // the EM's constants, those of the site prior (site_prior.inc) among them
 extern "C" void genosim_prior_constants(double *tol, uint32_t *max_it, uint32_t *flag_bit, double *f_bound, double *p_bound) {
     *tol = EM_TOL; *max_it = EM_MAX_IT; *flag_bit = EM_NOT_CONVERGED; *f_bound = EM_F_BOUND; *p_bound = SITE_EM_P_BOUND;

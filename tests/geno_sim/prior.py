@@ -32,6 +32,11 @@ def width(S):
     return call("genosim_prior_width", U32, [U64], int(S))
 
 
+def segment_grid(n_rows, S, tpb, n_cu, blocks_per_cu):
+    """the blocks of a launch that gives every row a segment of width(S) lanes (k_cohort_prior, k_cohort_sites_prior, k_cohort_hwe)"""
+    return call("genosim_segment_grid", U32, [U64, U64, U32, U32, U32], int(n_rows), int(S), int(tpb), int(n_cu), int(blocks_per_cu))
+
+
 def constants(site=False):
     """-> (EM_TOL, EM_MAX_IT, EM_NOT_CONVERGED, EM_F_BOUND, or with site SITE_EM_P_BOUND)"""
     tol, f_bound, p_bound = np.zeros(1), np.zeros(1), np.zeros(1)

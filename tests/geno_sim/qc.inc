@@ -1,40 +1,23 @@
-// TEST HARNESS ONLY (never shipped, never loaded by the product): the cohort sample QC of svjg_geno.h compiled with g++ — qc_class, qc_plane_words,
-// qc_pair_word, the stage slots, the tiles and qc_layout are the kernels' own code; what is restated here in plain C++ is the two kernels' loops
-// over blocks, waves and lanes (k_qc_planes, k_qc_pairs of svjg_kernels.h) inside a block laid out by qc_layout.  Driven from numpy
-// (tests/qc_sim/__init__.py).  With -DQC_SIM_MAIN it is a stand-alone program (for -fsanitize=address,undefined) that runs seeded random calls
-// against a brute-force count.
-#define SVJG_HD inline
-#include "../../svjedi-graph_amd/csrc/svjg_geno.h"
-#include <stdio.h>
-#include <stdlib.h>
-#include <string.h>
-#include <vector>
+// The cohort sample QC (svjg_geno.h: qc_class, qc_plane_words, qc_pair_word, the stage slots and the tiles are the kernels' own code) inside a plain
+// C++ restatement of the two kernels' loops over blocks, waves and lanes (k_qc_planes, k_qc_pairs of svjg_kernels.h), in a block laid out by
+// qc_layout.  Topic `qc` of the stand-alone program runs seeded random calls against a brute-force count.
 
-using namespace svjg;
-
-constexpr uint32_t SIM_TPB = 256;                        // svjg_kernels.h: TPB
-
-extern "C" void qcsim_constants(uint32_t *out) {
-    const uint32_t v[8] = {QC_TI, QC_TJ, QC_STAGE_WORDS, QC_MAX_SAMPLES, QC_RI, QC_PLANE_WORDS, QC_WAVES, QC_LDS_SLOTS};
+extern "C" void genosim_qc_constants(uint32_t *out) {
+    const uint32_t v[9] = {QC_TI, QC_TJ, QC_STAGE_WORDS, QC_MAX_SAMPLES, QC_RI, QC_PLANE_WORDS, QC_WAVES, QC_LDS_SLOTS, QC_BLOCKS_PER_CU};
     memcpy(out, v, sizeof v);
 }
-extern "C" uint32_t qcsim_class(uint32_t g, uint32_t P) { return qc_class(g, P); }
-extern "C" uint32_t qcsim_tiles(uint32_t S) { return qc_tiles(S); }
-extern "C" void qcsim_tile_at(uint32_t t, uint32_t S, uint32_t *ij) { qc_tile_at(t, S, ij[0], ij[1]); }
-extern "C" void qcsim_layout(uint64_t n_rows, uint64_t S, int per_item, uint64_t *out) {
-    const QcLayout L = qc_layout(n_rows, S, per_item != 0);
-    const uint64_t v[9] = {L.pair, L.sample, L.maxn, L.in_at, L.in_bytes, L.gt, L.ploidy, L.planes, L.total};
-    memcpy(out, v, sizeof v);
-}
-extern "C" void qcsim_pair_word(const uint64_t *i3, const uint64_t *j3, uint32_t *c) { qc_pair_word(i3[0], i3[1], i3[2], j3[0], j3[1], j3[2], c); }
+extern "C" uint32_t genosim_qc_class(uint32_t g, uint32_t P) { return qc_class(g, P); }
+extern "C" uint32_t genosim_qc_tiles(uint32_t S) { return qc_tiles(S); }
+extern "C" void genosim_qc_tile_at(uint32_t t, uint32_t S, uint32_t *ij) { qc_tile_at(t, S, ij[0], ij[1]); }
+extern "C" void genosim_qc_pair_word(const uint64_t *i3, const uint64_t *j3, uint32_t *c) { qc_pair_word(i3[0], i3[1], i3[2], j3[0], j3[1], j3[2], c); }
 
 // Both kernels over a call, with grids of grid_planes / grid_pairs blocks (0: one block a unit of work, the uncapped launch).  -> 0, or a code:
 // 1 a store outside the block's field, 2 a pair written twice or never, 3 a plane word never written, 4 a bit set behind the last row.
-extern "C" int qcsim_run(const uint8_t *gt, const uint8_t *ploidy, uint64_t n_rows, uint32_t S, uint32_t grid_planes, uint32_t grid_pairs,
+extern "C" int genosim_qc_run(const uint8_t *gt, const uint8_t *ploidy, uint64_t n_rows, uint32_t S, uint32_t grid_planes, uint32_t grid_pairs,
                          uint32_t *sample, uint32_t *pair) {
     const QcLayout L = qc_layout(n_rows, S, ploidy != nullptr);
     const uint64_t n = n_rows * S, n_words = qc_words(n_rows), n_pairs = qc_pairs(S), n_plane_words = QC_PLANES * n_words * S;
-    std::vector<uint64_t> block((L.total + 7) / 8, 0xA5A5A5A5A5A5A5A5ull);                  // (planes never written would show)
+    std::vector<uint64_t> block = poisoned_block(L.total);
     uint8_t *base = (uint8_t *)block.data();
     memcpy(base + L.gt, gt, n);
     if (ploidy) memcpy(base + L.ploidy, ploidy, n);
@@ -111,18 +94,15 @@ extern "C" int qcsim_run(const uint8_t *gt, const uint8_t *ploidy, uint64_t n_ro
             }
         }
     for (uint8_t w : pair_written) if (w != 1) return 2;
-    if (((const uint32_t *)(base + L.maxn))[0] || ((const uint32_t *)(base + L.maxn))[1]) return 1;
+    if (!maxn_stayed_zero(base, L.maxn)) return 1;
     memcpy(sample, d_sample, (uint64_t)S * 24);
     if (n_pairs) memcpy(pair, d_pair, n_pairs * 20);
     return 0;
 }
 
-#ifdef QC_SIM_MAIN
-static uint64_t rng_state = 0x9E3779B97F4A7C15ull;
-static uint32_t rnd() { rng_state ^= rng_state << 13; rng_state ^= rng_state >> 7; rng_state ^= rng_state << 17; return (uint32_t)(rng_state >> 32); }
-
+#ifdef GENO_SIM_MAIN
 // the definitions item by item and pair by pair
-static int brute(const std::vector<uint8_t> &gt, const uint8_t *ploidy, uint64_t R, uint32_t S, const std::vector<uint32_t> &sample, const std::vector<uint32_t> &pair) {
+static int qc_brute(const std::vector<uint8_t> &gt, const uint8_t *ploidy, uint64_t R, uint32_t S, const std::vector<uint32_t> &sample, const std::vector<uint32_t> &pair) {
     for (uint32_t s = 0; s < S; ++s) {
         uint32_t want[6] = {};
         for (uint64_t r = 0; r < R; ++r) {
@@ -147,7 +127,7 @@ static int brute(const std::vector<uint8_t> &gt, const uint8_t *ploidy, uint64_t
     return 0;
 }
 
-int main() {
+static int main_qc() {
     const uint32_t sizes[] = {1, 2, 3, QC_TJ - 1, QC_TJ, QC_TJ + 1, 2 * QC_TJ + 2};
     const uint64_t rows[] = {1, 63, 64, 65, 64 * QC_STAGE_WORDS - 1, 64 * QC_STAGE_WORDS + 1};
     int cases = 0;
@@ -160,9 +140,9 @@ int main() {
                 if (mode != 2) for (auto &g : gt) if (g != 0xFF && rnd() % 4) g %= 4;      // mostly 0..3 where every item is diploid
                 std::vector<uint32_t> sample(S * 6), pair(qc_pairs(S) * 5 + 1);
                 const uint8_t *ploidy = mode ? pl.data() : nullptr;
-                const int rc = qcsim_run(gt.data(), ploidy, R, S, cases % 2 ? 3 : 0, cases % 3 ? 2 : 0, sample.data(), pair.data());
+                const int rc = genosim_qc_run(gt.data(), ploidy, R, S, cases % 2 ? 3 : 0, cases % 3 ? 2 : 0, sample.data(), pair.data());
                 if (rc) { fprintf(stderr, "qc_sim: code %d at S %u rows %llu mode %d\n", rc, S, (unsigned long long)R, mode); return 1; }
-                if (brute(gt, ploidy, R, S, sample, pair)) { fprintf(stderr, "qc_sim: counts differ at S %u rows %llu mode %d\n", S, (unsigned long long)R, mode); return 1; }
+                if (qc_brute(gt, ploidy, R, S, sample, pair)) { fprintf(stderr, "qc_sim: counts differ at S %u rows %llu mode %d\n", S, (unsigned long long)R, mode); return 1; }
                 ++cases;
             }
     printf("qc_sim ok: %d cases\n", cases);

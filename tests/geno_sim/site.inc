@@ -105,9 +105,6 @@ extern "C" void genosim_site_items_by_steps(uint64_t n_items, const uint8_t *bit
 }
 
 #ifdef GENO_SIM_MAIN
-static uint64_t rng_state = 88172645463325252ull;
-static uint64_t rnd() { uint64_t &x = rng_state; x ^= x << 13; x ^= x >> 7; x ^= x << 17; return x; }
-
 // The gather and the item at S samples (S = 1 also with present == nullptr) over arrays of EXACTLY n_slots * S entries: a read through a slot
 // behind a hole or at or beyond n_slots would be a read beyond the allocation.  Every eighth site is bad in one of four ways.  -> what differs
 static uint64_t beyond = 0;

@@ -1,5 +1,5 @@
 """Cohort site test for Hardy-Weinberg equilibrium (--cohort LIST --cohort-hwe) on the CPU: the integer model's self-checks
-(tests/cohort_hwe_model.py); the fixtures under tests/golden/cohort_hwe; the host harness (tests/hwe_sim: svjg_geno.h's own routines inside a
+(tests/cohort_hwe_model.py); the fixtures under tests/golden/cohort_hwe; the host harness (tests/geno_sim, topic hwe: svjg_geno.h's own routines inside a
 restatement of k_cohort_hwe's loops) against the model within the derived bound; layout, chunking, INFO text and writer; run_cohort(hwe=True) with
 stand-in contexts that answer cohort_hwe from the harness."""
 import math
@@ -12,7 +12,7 @@ import numpy as np
 import pytest
 
 from tests import cohort_hwe_model as M
-from tests import hwe_sim
+from tests.geno_sim import hwe as hwe_sim
 
 AMD = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "svjedi-graph_amd")
 GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "cohort_hwe")
@@ -180,7 +180,7 @@ def test_a_row_does_not_depend_on_its_neighbours_or_the_grid():
 
 def test_harness_under_the_sanitizers():
     """the same code as a stand-alone program with its own main under -fsanitize=address,undefined (nothing is loaded into Python)"""
-    p = subprocess.run([hwe_sim.build_main()], capture_output=True, text=True)
+    p = subprocess.run([hwe_sim.build_main(), "hwe"], capture_output=True, text=True)
     assert p.returncode == 0 and p.stdout.startswith("hwe_sim ok") and not p.stderr, (p.stdout, p.stderr)
 
 

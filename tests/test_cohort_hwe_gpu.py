@@ -2,7 +2,7 @@
 of tests/test_cohort_hwe.py; every segment width and one, two and three items a lane in both phases; the fixtures; the growth of the log10(i!)
 table; more rows than one trip of the grid; equal bytes from call to call and from chunk to chunk; the call's own block; the argument errors; and
 predict-genotype.py --cohort --cohort-hwe on the golden cohort beside every other cohort option.  The device's bytes are also compared with the host
-harness's (tests/hwe_sim): the two differ in exp10 and in the table's log10 only, so the last bits of p may differ — the share of rows that do is
+harness's (tests/geno_sim, topic hwe): the two differ in exp10 and in the table's log10 only, so the last bits of p may differ — the share of rows that do is
 printed, and only the model bound binds.  Needs an MI355X: run with -m gpu."""
 import os
 import subprocess
@@ -13,7 +13,7 @@ import pytest
 
 from tests import cohort_hwe_model as M
 from tests import cohort_model as CM
-from tests import hwe_sim
+from tests.geno_sim import hwe as hwe_sim
 from tests.test_cohort_hwe import AMD, FAMILIES, check_tags, draw, held, load
 
 pytestmark = pytest.mark.gpu

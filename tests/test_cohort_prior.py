@@ -37,6 +37,18 @@ def test_segment_width(S, W):
     assert sim.width(S) == W and 64 % W == 0
 
 
+def test_segment_grid():
+    """svjg_geno.h: segment_grid on 256 units, worked by hand: W = width(S), 64 / W rows a wave, ceil(n_rows / that) waves, ceil(waves * 64 / tpb)
+    blocks, at most 256 * per_cu"""
+    for (n_rows, S, tpb, per_cu), blocks in {(1, 1, 256, 8): 1,                       # one wave of 64 rows, one block
+                                             (1000, 5, 256, 8): 32,                   # W 8: 125 waves, 31.25 blocks
+                                             (1000, 5, 128, 2): 63,                   # 125 waves, 62.5 blocks of two waves
+                                             (65, 33, 256, 8): 17,                    # W 64: 65 waves, 16.25 blocks
+                                             (100000, 64, 256, 8): 2048,              # 25 000 blocks: the cap
+                                             (10000, 2048, 256, 8): 2048}.items():    # 2 500 blocks: the cap
+        assert sim.segment_grid(n_rows, S, tpb, 256, per_cu) == blocks, (n_rows, S, tpb, per_cu)
+
+
 def test_item_weights_against_the_model():
     from decimal import localcontext
     rng = np.random.default_rng(3)

@@ -1,4 +1,4 @@
-"""Cohort sample QC (--cohort LIST --cohort-qc PREFIX) on the CPU: the host harness (tests/qc_sim: svjg_geno.h's own routines inside a restatement of
+"""Cohort sample QC (--cohort LIST --cohort-qc PREFIX) on the CPU: the host harness (tests/geno_sim, topic qc: svjg_geno.h's own routines inside a restatement of
 both kernels' loops) against the numpy model (tests/cohort_qc_model.py) bit for bit; planted pairs; the kinship, its thresholds and its text; both
 writers; the chunked host flow; the script's refusal; run_cohort(qc=...) on the golden cohort with a stand-in context that answers from the models."""
 import math
@@ -10,8 +10,8 @@ import numpy as np
 import pytest
 
 from tests import cohort_qc_model as M
-from tests import qc_sim
 from tests import standin_capi
+from tests.geno_sim import qc as qc_sim
 from tests.test_cohort_joint_ins import CohortModelCtx
 
 AMD = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "svjedi-graph_amd")
@@ -100,7 +100,7 @@ def test_qc_layout(n_rows, S, per_item):
 
 def test_harness_under_the_sanitizers():
     """the same code as a stand-alone program with its own main under -fsanitize=address,undefined (nothing is loaded into Python)"""
-    p = subprocess.run([qc_sim.build_main()], capture_output=True, text=True)
+    p = subprocess.run([qc_sim.build_main(), "qc"], capture_output=True, text=True)
     assert p.returncode == 0 and p.stdout.startswith("qc_sim ok") and not p.stderr, (p.stdout, p.stderr)
 
 

@@ -1,5 +1,5 @@
 """svjg_cohort_qc on the device against the numpy model (tests/cohort_qc_model.py), all bytes: the shapes at which k_qc_planes and k_qc_pairs take
-another path (tests/qc_sim: constants), the largest triangle, chunked calls, the call's own block, the argument errors, and predict-genotype.py
+another path (tests/geno_sim/qc.py: constants), the largest triangle, chunked calls, the call's own block, the argument errors, and predict-genotype.py
 --cohort --cohort-qc on the golden cohort.  Needs an MI355X: run with -m gpu."""
 import os
 import subprocess
@@ -10,7 +10,7 @@ import pytest
 
 from tests import cohort_model as CM
 from tests import cohort_qc_model as M
-from tests import qc_sim
+from tests.geno_sim import qc as qc_sim
 from tests.test_cohort_qc import AMD, ROWS, SIZES, model_tsvs, random_call, vcf_gt
 
 pytestmark = pytest.mark.gpu

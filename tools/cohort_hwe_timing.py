@@ -3,7 +3,7 @@
 allele frequency per row between 0.01 and 0.5, every item diploid (ploidy NULL).
 
 Median of `--calls` calls behind `--warmup`, genotype_ms of svjg_last_kernel_ms (the event pair around the kernel), every shape run twice in one
-process; beside it the wall time of a call from Python and, once per shape, the single-thread wall time of the host harness (tests/hwe_sim: the
+process; beside it the wall time of a call from Python and, once per shape, the single-thread wall time of the host harness (tests/geno_sim, topic hwe: the
 kernel's own routines and loops compiled with g++ -O2) for the same call, with which the call's counts are compared bit for bit and its p-values
 to 1e-9 relative.  One JSON line per reading.  A first reading: nothing is compared against the times.
 
@@ -30,7 +30,7 @@ def main():
     ap.add_argument("--warmup", type=int, default=3)
     args = ap.parse_args()
     from svjg import capi
-    from tests import hwe_sim
+    from tests.geno_sim import hwe as hwe_sim
     ctx = capi.Context(0)
     hwe_sim.constants()                                          # (the harness library is built here, not inside a timed call)
     for shape in args.shapes:
