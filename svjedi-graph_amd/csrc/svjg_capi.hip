@@ -79,10 +79,10 @@ constexpr int STAGE_THREADS = 4;
 constexpr uint64_t STAGE_PIECE = 8ull << 20;
 
 // The device block of a step-by-step genotype call and its pinned host twin (genotype_leg).  Every call has a block of its own: svjg_genotype_view
-// hands out pointers into BLOCK_ROWS' twin and svjg_genotype_boundary reads it later, and both must survive calls of the other six.
+// hands out pointers into BLOCK_ROWS' twin and svjg_genotype_boundary reads it later, and both must survive calls of the other ten.
 // A fused pass's slot holds the same pair (RunSlot).
 struct LegBlock { DevBuf<uint8_t> d;  PinBuf h; };
-enum { BLOCK_ROWS, BLOCK_PLOIDY, BLOCK_SITES, BLOCK_COHORT, BLOCK_COHORT_PLOIDY, BLOCK_COHORT_PRIOR, BLOCK_COHORT_SITES, BLOCK_COHORT_QUAL, BLOCK_COHORT_SITES_PRIOR, BLOCK_COHORT_QC, BLOCK_COHORT_HWE, LEG_BLOCKS };   // rows_layout, ploidy_layout, sites_layout, cohort_layout for the three cohort blocks, sites_layout again, qual_layout, sites_layout with its prior switch, qc_layout, hwe_layout (svjg_geno.h)
+enum { BLOCK_ROWS, BLOCK_PLOIDY, BLOCK_SITES, BLOCK_COHORT, BLOCK_COHORT_PLOIDY, BLOCK_COHORT_PRIOR, BLOCK_COHORT_SITES, BLOCK_COHORT_QUAL, BLOCK_COHORT_SITES_PRIOR, BLOCK_COHORT_QC, BLOCK_COHORT_HWE, LEG_BLOCKS };   // eleven, a call each (svjg_geno.h: LegSpan): rows_layout, ploidy_layout, sites_layout, cohort_layout for the three cohort blocks, sites_layout again, qual_layout, sites_layout with its prior switch, qc_layout, hwe_layout
 
 // slots the passes of svjg_run_begin rotate through: two may be in flight, and the one the NEXT pass will use is zeroed while the newest computes
 constexpr int RUN_SLOTS = 3;
@@ -1358,6 +1358,18 @@ static int launch_cohort_prior(svjg_ctx *c, CohortPriorArgs &p) {
     return 0;
 }
 
+// max_ploidy of a cohort call (cohort_call, svjg_cohort_qual): in range, and 2 where no array says otherwise; no item's ploidy above it
+static int check_max_ploidy(svjg_ctx *c, const uint8_t *ploidy, uint32_t max_ploidy) {
+    if (max_ploidy < 1 || max_ploidy > MAX_PLOIDY) { c->err = "max_ploidy is not in 1..SVJG_MAX_PLOIDY"; return SVJG_E_ARG; }
+    if (!ploidy && max_ploidy != 2) { c->err = "without a ploidy array every item is diploid: max_ploidy must be 2"; return SVJG_E_ARG; }
+    return 0;
+}
+static int check_item_ploidy(svjg_ctx *c, const uint8_t *ploidy, uint64_t n, uint32_t max_ploidy) {
+    for (uint64_t i = 0; ploidy && i < n; ++i)
+        if (ploidy[i] > max_ploidy) { c->err = "ploidy above max_ploidy"; return SVJG_E_ARG; }
+    return 0;
+}
+
 // The host leg of svjg_genotype_cohort (block BLOCK_COHORT: ploidy NULL, max_ploidy 2), svjg_genotype_cohort_ploidy (BLOCK_COHORT_PLOIDY: a
 // ploidy per item) and svjg_genotype_cohort_prior (BLOCK_COHORT_PRIOR: ploidy or NULL, gq / af / em_steps): the checks, the call's logarithms
 // (by the host's libm, as geno_args' three) and ploidy bytes in with the three input arrays, the cohort kernel of the call's kind — the table's
@@ -1371,15 +1383,12 @@ static int cohort_call(svjg_ctx *c, int block, const uint8_t *sv_type, const uin
     if (n_rows == 0) return 0;
     if (!sv_type || !slot || !ok || (!ploidy && block == BLOCK_COHORT_PLOIDY) || !gt || !pl || !raw || !genotyped || !boundary || !site ||
         (prior && (!gq || !af || !em_steps))) { c->err = "a null array"; return SVJG_E_ARG; }
-    if (max_ploidy < 1 || max_ploidy > MAX_PLOIDY) { c->err = "max_ploidy is not in 1..SVJG_MAX_PLOIDY"; return SVJG_E_ARG; }
-    if (!ploidy && max_ploidy != 2) { c->err = "without a ploidy array every item is diploid: max_ploidy must be 2"; return SVJG_E_ARG; }
+    if (const int rc0 = check_max_ploidy(c, ploidy, max_ploidy)) return rc0;
     const uint64_t S = c->cohort_samples;
     if (block != BLOCK_COHORT && S >= (1ull << 28)) { c->err = "too many samples: AN would not fit 32 bits"; return SVJG_E_ARG; }
     if (n_rows > (1ull << 40) / S) { c->err = "too many items for one call: genotype the rows in chunks"; return SVJG_E_ARG; }
     const uint64_t n = n_rows * S;
-    if (ploidy)
-        for (uint64_t i = 0; i < n; ++i)
-            if (ploidy[i] > max_ploidy) { c->err = "ploidy above max_ploidy"; return SVJG_E_ARG; }
+    if (const int rc0 = check_item_ploidy(c, ploidy, n, max_ploidy)) return rc0;
     HIPCHK(c, hipSetDevice(c->device));
     const CohortLayout L = cohort_layout(n_rows, S, max_ploidy, per_item, prior);
     const int rc = genotype_leg(c, c->leg[block], L,
@@ -1458,17 +1467,14 @@ extern "C" int svjg_cohort_qual(svjg_ctx *c, const uint8_t *sv_type, const uint3
     if (!c->d_cm) { c->err = "no cohort matrix"; return SVJG_E_ARG; }
     if (n_rows == 0) return 0;
     if (!sv_type || !slot || !ok || !qual || !mlac || !chroms) { c->err = "a null array"; return SVJG_E_ARG; }
-    if (max_ploidy < 1 || max_ploidy > MAX_PLOIDY) { c->err = "max_ploidy is not in 1..SVJG_MAX_PLOIDY"; return SVJG_E_ARG; }
-    if (!ploidy && max_ploidy != 2) { c->err = "without a ploidy array every item is diploid: max_ploidy must be 2"; return SVJG_E_ARG; }
+    if (const int rc0 = check_max_ploidy(c, ploidy, max_ploidy)) return rc0;
     const uint64_t S = c->cohort_samples;
     static_assert(SVJG_QUAL_MAX_CHROMS == QUAL_MAX_CHROMS, "svjg.h and svjg_geno.h disagree");
     if (S * max_ploidy > QUAL_MAX_CHROMS) { c->err = "too many chromosomes for the site quality: n_samples * max_ploidy is above SVJG_QUAL_MAX_CHROMS = 4096"; return SVJG_E_ARG; }
     if (!(theta > 0.0 && theta <= QUAL_THETA_MAX)) { c->err = "theta is not in (0, 0.05]"; return SVJG_E_ARG; }
     if (n_rows > (1ull << 40) / S) { c->err = "too many items for one call: take the rows in chunks"; return SVJG_E_ARG; }
     const uint64_t n = n_rows * S;
-    if (ploidy)
-        for (uint64_t i = 0; i < n; ++i)
-            if (ploidy[i] > max_ploidy) { c->err = "ploidy above max_ploidy"; return SVJG_E_ARG; }
+    if (const int rc0 = check_item_ploidy(c, ploidy, n, max_ploidy)) return rc0;
     HIPCHK(c, hipSetDevice(c->device));
     const uint32_t m_max = (uint32_t)(S * max_ploidy);
     const QualLayout L = qual_layout(n_rows, S, m_max, ploidy != nullptr);
@@ -1493,11 +1499,28 @@ extern "C" int svjg_cohort_qual(svjg_ctx *c, const uint8_t *sv_type, const uint3
     return 0;
 }
 
+// ---- the calls that take the run's calls, gt[n_rows, S] and ploidy[n_rows, S] or NULL (svjg_cohort_qc, svjg_cohort_hwe) ----
+// They read neither the cohort matrix nor the count vector, and their max_n pair stays zero: the leg never runs their kernels twice.  check_calls: their checks, in this order
+// (max_samples with limit_err, and rows_err: the call's own; arrays: gt and the call's outputs are there).  calls_leg: genotype_leg in the call's own block, laid out by L
+// (a CallsIn: calls_in); the n = n_rows * S call bytes (and the ploidy bytes) go in.
+static int check_calls(svjg_ctx *c, uint64_t S, uint64_t max_samples, const char *limit_err, bool arrays, uint64_t n_rows, const char *rows_err) {
+    if (S == 0) { c->err = "no sample"; return SVJG_E_ARG; }
+    if (S > max_samples) { c->err = limit_err; return SVJG_E_ARG; }
+    if (!arrays) { c->err = "a null array"; return SVJG_E_ARG; }
+    if (n_rows >= (1ull << 32)) { c->err = rows_err; return SVJG_E_ARG; }
+    if (n_rows > (1ull << 40) / S) { c->err = "too many items for one call: take the rows in chunks"; return SVJG_E_ARG; }
+    return 0;
+}
+template <class Layout, class Launch>
+static int calls_leg(svjg_ctx *c, int block, const Layout &L, const uint8_t *gt, const uint8_t *ploidy, uint64_t n, Launch launch) {
+    HIPCHK(c, hipSetDevice(c->device));
+    return genotype_leg(c, c->leg[block], L, [&](uint8_t *hb) { stage_calls(hb, L, gt, ploidy, n); }, launch);
+}
+
 // ---- cohort sample QC (svjg.h: svjg_cohort_qc; the model, the planes and the tiles: svjg_geno.h) ----
-// Through genotype_leg in BLOCK_COHORT_QC, a block of its own: the call bytes (and the ploidy bytes) go in; ONE memset zeroes sample[] and the max_n
-// pair behind it; k_qc_planes over the units, k_qc_pairs over the tiles (S >= 2), both in strides of a grid of at most QC_BLOCKS_PER_CU blocks a
-// unit (svjg_geno.h); pair[] and sample[] come out.  Neither kernel reads the log10(i!) table, the cohort matrix or the count vector, and the
-// max_n pair stays zero: the leg never runs them twice.
+// Through calls_leg in BLOCK_COHORT_QC: ONE memset zeroes sample[] and the max_n pair behind it; k_qc_planes over the units, k_qc_pairs over the
+// tiles (S >= 2), both in strides of a grid of at most QC_BLOCKS_PER_CU blocks a unit (svjg_geno.h); pair[] and sample[] come out.  Neither
+// kernel reads the log10(i!) table.
 static int launch_cohort_qc(svjg_ctx *c, const QcArgs &p) {
     HIPCHK(c, hipMemsetAsync(p.sample, 0, (uint64_t)p.S * 4 * QC_CLASSES + 8, c->stream));      // (the max_n pair lies right behind sample[]: qc_layout)
     const uint64_t cap = (uint64_t)c->n_cu * QC_BLOCKS_PER_CU, blocks = (qc_plane_units(p.n_words, p.S) + TPB - 1) / TPB;
@@ -1514,25 +1537,16 @@ static int launch_cohort_qc(svjg_ctx *c, const QcArgs &p) {
 extern "C" int svjg_cohort_qc(svjg_ctx *c, const uint8_t *gt, const uint8_t *ploidy, uint64_t n_rows, uint32_t n_samples, uint32_t *sample, uint32_t *pair) {
     if (!c) return SVJG_E_ARG;
     static_assert(SVJG_QC_MAX_SAMPLES == QC_MAX_SAMPLES, "svjg.h and svjg_geno.h disagree");
-    const uint64_t S = n_samples;
-    if (S == 0) { c->err = "no sample"; return SVJG_E_ARG; }
-    if (S > QC_MAX_SAMPLES) { c->err = "too many samples for the pair table: n_samples is above SVJG_QC_MAX_SAMPLES = 2048"; return SVJG_E_ARG; }
-    if (!gt || !sample || (!pair && S >= 2)) { c->err = "a null array"; return SVJG_E_ARG; }
-    if (n_rows >= (1ull << 32)) { c->err = "too many rows for 32-bit sums: take the rows in chunks"; return SVJG_E_ARG; }
-    if (n_rows > (1ull << 40) / S) { c->err = "too many items for one call: take the rows in chunks"; return SVJG_E_ARG; }
-    const uint64_t n = n_rows * S, n_pairs = qc_pairs(S);
+    const uint64_t S = n_samples, n_pairs = qc_pairs(S);
+    if (const int rc0 = check_calls(c, S, QC_MAX_SAMPLES, "too many samples for the pair table: n_samples is above SVJG_QC_MAX_SAMPLES = 2048", gt && sample && (pair || S < 2),
+                                    n_rows, "too many rows for 32-bit sums: take the rows in chunks")) return rc0;
     if (n_rows == 0) {
         memset(sample, 0, S * QC_CLASSES * sizeof *sample);
         if (n_pairs) memset(pair, 0, n_pairs * QC_PAIR_COUNTS * sizeof *pair);
         return 0;
     }
-    HIPCHK(c, hipSetDevice(c->device));
     const QcLayout L = qc_layout(n_rows, S, ploidy != nullptr);
-    const int rc = genotype_leg(c, c->leg[BLOCK_COHORT_QC], L,
-        [&](uint8_t *hb) {
-            memcpy(hb + L.gt, gt, n);
-            if (ploidy) memcpy(hb + L.ploidy, ploidy, n);
-        },
+    const int rc = calls_leg(c, BLOCK_COHORT_QC, L, gt, ploidy, n_rows * S,
         [&](uint8_t *base) {
             const QcArgs p{base + L.gt, ploidy ? base + L.ploidy : nullptr, n_rows, qc_words(n_rows), n_samples, (uint64_t *)(base + L.planes),
                            (uint32_t *)(base + L.sample), (uint32_t *)(base + L.pair)};
@@ -1546,10 +1560,9 @@ extern "C" int svjg_cohort_qc(svjg_ctx *c, const uint8_t *gt, const uint8_t *plo
 }
 
 // ---- cohort site test for Hardy-Weinberg equilibrium (svjg.h: svjg_cohort_hwe; the model and the routines: svjg_geno.h) ----
-// Through genotype_leg in BLOCK_COHORT_HWE, a block of its own: the call bytes (and the ploidy bytes) go in, k_cohort_hwe over the rows — blocks
-// of four waves, a row a segment of a wave (svjg_geno.h: segment_grid) —, p[] and counts[] come out.  The table's 2 S + 1 entries are reserved in
-// front of the leg (svjg_logfact_reserve: the growth path of every caller), so the kernel meets no n beyond it and the max_n pair, zeroed here,
-// stays zero: the leg never runs the kernel twice.
+// Through calls_leg in BLOCK_COHORT_HWE: k_cohort_hwe over the rows — blocks of four waves, a row a segment of a wave (svjg_geno.h: segment_grid)
+// —, p[] and counts[] come out.  The table's 2 S + 1 entries are reserved in front of the leg (svjg_logfact_reserve: the growth path of every
+// caller), so the kernel meets no n beyond it and the max_n pair, zeroed here, stays zero.
 static int launch_cohort_hwe(svjg_ctx *c, HweArgs &p, unsigned int *max_n) {
     p.logfact = c->d_logfact;
     HIPCHK(c, hipMemsetAsync(max_n, 0, 8, c->stream));
@@ -1562,30 +1575,20 @@ extern "C" int svjg_cohort_hwe(svjg_ctx *c, const uint8_t *gt, const uint8_t *pl
     if (!c) return SVJG_E_ARG;
     static_assert(SVJG_HWE_MAX_SAMPLES == HWE_MAX_SAMPLES, "svjg.h and svjg_geno.h disagree");
     const uint64_t S = n_samples;
-    if (S == 0) { c->err = "no sample"; return SVJG_E_ARG; }
-    if (S > HWE_MAX_SAMPLES) { c->err = "too many samples: n_samples is above SVJG_HWE_MAX_SAMPLES = 65536"; return SVJG_E_ARG; }
-    if (!gt || !counts || !p) { c->err = "a null array"; return SVJG_E_ARG; }
-    if (n_rows >= (1ull << 32)) { c->err = "too many rows for one call: take the rows in chunks"; return SVJG_E_ARG; }
-    if (n_rows > (1ull << 40) / S) { c->err = "too many items for one call: take the rows in chunks"; return SVJG_E_ARG; }
+    if (const int rc0 = check_calls(c, S, HWE_MAX_SAMPLES, "too many samples: n_samples is above SVJG_HWE_MAX_SAMPLES = 65536", gt && counts && p,
+                                    n_rows, "too many rows for one call: take the rows in chunks")) return rc0;
     if (n_rows == 0) return 0;
-    HIPCHK(c, hipSetDevice(c->device));
     const uint32_t entries = 2 * n_samples + 1;          // (a context without a table gets the first one of every leg, never a smaller one)
     if (const int rc = svjg_logfact_reserve(c, entries > logfact_first() ? entries : logfact_first())) return rc;
-    const uint64_t n = n_rows * S;
     const HweLayout L = hwe_layout(n_rows, S, ploidy != nullptr);
-    const int rc = genotype_leg(c, c->leg[BLOCK_COHORT_HWE], L,
-        [&](uint8_t *hb) {
-            memcpy(hb + L.gt, gt, n);
-            if (ploidy) memcpy(hb + L.ploidy, ploidy, n);
-        },
+    const int rc = calls_leg(c, BLOCK_COHORT_HWE, L, gt, ploidy, n_rows * S,
         [&](uint8_t *base) {
             HweArgs a{base + L.gt, ploidy ? base + L.ploidy : nullptr, n_rows, n_samples, nullptr, (uint32_t *)(base + L.counts), (double *)(base + L.p)};
             return launch_cohort_hwe(c, a, (unsigned int *)(base + L.maxn));
         });
     if (rc) return rc;
     const uint8_t *hb = c->leg[BLOCK_COHORT_HWE].h;
-    memcpy(counts, hb + L.counts, n_rows * 3 * sizeof *counts);
-    memcpy(p, hb + L.p, n_rows * 2 * sizeof *p);
+    memcpy(counts, hb + L.counts, n_rows * 3 * sizeof *counts); memcpy(p, hb + L.p, n_rows * 2 * sizeof *p);
     return 0;
 }
 

@@ -4,6 +4,7 @@
 #pragma once
 #include <math.h>
 #include <stdint.h>
+#include <string.h>
 #include "svjg_pass.h"
 
 #ifndef SVJG_HD
@@ -1216,8 +1217,13 @@ constexpr uint32_t logfact_reserve_to(uint32_t have, uint32_t entries) { return 
 // the three input arrays of n rows, back to back from byte `at` of a block: [ slot 4 | type 1 | ok 1 ] x n
 struct RowsIn { uint64_t slot, type, ok, bytes; };
 inline RowsIn rows_in(uint64_t n, uint64_t at = 0) { return RowsIn{at, at + n * 4, at + n * 5, n * 6}; }
+// the input arrays of a call that takes the run's calls (svjg_cohort_qc, svjg_cohort_hwe), back to back from byte `at` of a block: [ gt 1 ] x n_rows * S and, per_item, as many
+// ploidy bytes (ploidy 0: no array); such a call's layout IS a CallsIn as it is a LegSpan.  stage_calls: the call's arrays, n bytes each, into the block (host; tests/geno_sim too)
+struct CallsIn { uint64_t gt, ploidy, bytes; };
+inline CallsIn calls_in(uint64_t n_rows, uint64_t S, bool per_item, uint64_t at = 0) { const uint64_t n = n_rows * S; return CallsIn{at, per_item ? at + n : 0, per_item ? 2 * n : n}; }
+inline void stage_calls(uint8_t *hb, const CallsIn &I, const uint8_t *gt, const uint8_t *ploidy, uint64_t n) { memcpy(hb + I.gt, gt, n); if (ploidy) memcpy(hb + I.ploidy, ploidy, n); }
 
-// The ten step-by-step calls (svjg_genotype / _view, _ploidy, _sites, _cohort, _cohort_ploidy, _cohort_prior, _cohort_sites, svjg_cohort_qual, svjg_cohort_qc, svjg_cohort_hwe) each own one device block and its pinned host twin, all of ONE
+// The eleven step-by-step calls (svjg_genotype / _view, _ploidy, _sites, _cohort, _cohort_ploidy, _cohort_prior, _cohort_sites, _cohort_sites_prior, svjg_cohort_qual, svjg_cohort_qc, svjg_cohort_hwe) each own one device block and its pinned host twin, all of ONE
 // shape: the outputs (they end at out_end), the max_n pair 8-aligned, ONE contiguous input region right behind the pair, 64 spare bytes -> ONE copy
 // in (in_bytes from in_at), ONE copy out (maxn + 8 bytes from 0).  A layout below IS a LegSpan and adds only what is its own: its outputs and where its inputs lie.
 struct LegSpan { uint64_t maxn, in_at, in_bytes, total; };
@@ -1300,29 +1306,25 @@ inline QualLayout qual_layout(uint64_t n_rows, uint64_t S, uint32_t m_max, bool 
 
 // svjg_cohort_qc: [ pair 20 ] x S (S - 1) / 2 of output, then, 8-aligned, [ sample 24 ] x S as the LAST output: the max_n pair lies right behind
 // it (a multiple of 8: leg_span pads nothing), and ONE memset zeroes both in front of every launch (k_qc_planes adds to sample[]; the pair is never
-// written: the call reads no table and names no slot).  in: the n_rows * S call bytes and, per_item, as many ploidy bytes.  Behind the inputs,
+// written: the call reads no table and names no slot).  in: calls_in(n_rows, S, per_item).  Behind the inputs,
 // 8-aligned and never copied: the QC_PLANES planes of qc_words(n_rows) * S words, written by k_qc_planes and read by k_qc_pairs.
-struct QcLayout : LegSpan { uint64_t pair, sample, gt, ploidy, planes; };
+struct QcLayout : LegSpan, CallsIn { uint64_t pair, sample, planes; };
 inline QcLayout qc_layout(uint64_t n_rows, uint64_t S, bool per_item) {
-    QcLayout L{}; uint64_t o = 0; const uint64_t n = n_rows * S;
+    QcLayout L{}; uint64_t o = 0;
     L.pair = o; o += qc_pairs(S) * 4 * QC_PAIR_COUNTS; o = (o + 7) & ~7ull;
     L.sample = o; o += S * 4 * QC_CLASSES;
-    leg_span(L, o, n * (per_item ? 2 : 1));
-    L.gt = L.in_at; L.ploidy = per_item ? L.gt + n : 0;
+    leg_span(L, o, calls_in(n_rows, S, per_item).bytes); static_cast<CallsIn &>(L) = calls_in(n_rows, S, per_item, L.in_at);
     L.planes = (L.in_at + L.in_bytes + 7) & ~7ull;
     L.total = L.planes + QC_PLANES * qc_words(n_rows) * S * 8 + 64;
     return L;
 }
 
 // svjg_cohort_hwe: [ p 16 ] x n_rows (HWE, EXCHET), then [ counts 12 ] x n_rows (n_ref, n_het, n_alt) of output; the max_n pair is zeroed in front
-// of every launch and never written (the call reserves the table entries it reads before it launches).  in: the n_rows * S call bytes and,
-// per_item, as many ploidy bytes.
-struct HweLayout : LegSpan { uint64_t p, counts, gt, ploidy; };
+// of every launch and never written (the call reserves the table entries it reads before it launches).  in: calls_in(n_rows, S, per_item).
+struct HweLayout : LegSpan, CallsIn { uint64_t p, counts; };
 inline HweLayout hwe_layout(uint64_t n_rows, uint64_t S, bool per_item) {
-    HweLayout L{}; const uint64_t n = n_rows * S;
-    L.p = 0; L.counts = n_rows * 16;
-    leg_span(L, L.counts + n_rows * 12, n * (per_item ? 2 : 1));
-    L.gt = L.in_at; L.ploidy = per_item ? L.gt + n : 0;
+    HweLayout L{}; L.p = 0; L.counts = n_rows * 16;
+    leg_span(L, L.counts + n_rows * 12, calls_in(n_rows, S, per_item).bytes); static_cast<CallsIn &>(L) = calls_in(n_rows, S, per_item, L.in_at);
     return L;
 }
 

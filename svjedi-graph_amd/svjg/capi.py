@@ -351,6 +351,18 @@ def _ploidy_matrix(ploidy, n, S):
     return np.ascontiguousarray(ploidy, dtype=np.uint8)
 
 
+def _calls_in(gt, ploidy):
+    """a run's calls as cohort_qc and cohort_hwe take them -> (gt[n, S] uint8, ploidy the same or None, n, S)"""
+    gt = np.ascontiguousarray(gt, dtype=np.uint8)
+    if gt.ndim != 2:
+        raise ValueError("gt must be [n_rows, n_samples]")
+    if ploidy is not None:
+        ploidy = np.ascontiguousarray(ploidy, dtype=np.uint8)
+        if ploidy.shape != gt.shape:
+            raise ValueError("ploidy must have gt's shape")
+    return (gt, ploidy) + gt.shape
+
+
 class Context:
     """One GPU.  Thin, stateful wrapper over the C ABI."""
 
@@ -637,14 +649,7 @@ class Context:
         gt > ploidy (3, 0xFF) is not called, one with ploidy 0 not eligible.  It reads nothing of the context's matrix or counts.
         -> (sample[S, 6] = eligible, called, carrier, diploid, het, homalt; pair[S (S - 1) / 2, 5] = both, het1, het2, hethet, ibs0 of the pairs
         i < j at k = i S - i (i + 1) / 2 + (j - i - 1), over the items both diploid), uint32 sums over the rows"""
-        gt = np.ascontiguousarray(gt, dtype=np.uint8)
-        if gt.ndim != 2:
-            raise ValueError("gt must be [n_rows, n_samples]")
-        n, S = gt.shape
-        if ploidy is not None:
-            ploidy = np.ascontiguousarray(ploidy, dtype=np.uint8)
-            if ploidy.shape != gt.shape:
-                raise ValueError("ploidy must have gt's shape")
+        gt, ploidy, n, S = _calls_in(gt, ploidy)
         sample, pair = np.empty((S, 6), np.uint32), np.empty((S * (S - 1) // 2 if S else 0, 5), np.uint32)
         self._chk(self.lib.svjg_cohort_qc(self.h, gt.ctypes.data, None if ploidy is None else ploidy.ctypes.data, n, S, sample.ctypes.data,
                                           pair.ctypes.data if len(pair) else None))
@@ -655,14 +660,7 @@ class Context:
         diploid items of a row enter (ploidy 2 and gt <= 2).  It reads nothing of the context's matrix or counts.
         -> (counts[n, 3] = n_ref, n_het, n_alt, uint32; p[n, 2] = HWE, the two-sided exact test, and EXCHET, the one-sided one for excess
         heterozygotes, float64: 1.0 for a row without a minor allele, NaN for a row without an item)"""
-        gt = np.ascontiguousarray(gt, dtype=np.uint8)
-        if gt.ndim != 2:
-            raise ValueError("gt must be [n_rows, n_samples]")
-        n, S = gt.shape
-        if ploidy is not None:
-            ploidy = np.ascontiguousarray(ploidy, dtype=np.uint8)
-            if ploidy.shape != gt.shape:
-                raise ValueError("ploidy must have gt's shape")
+        gt, ploidy, n, S = _calls_in(gt, ploidy)
         counts, p = np.empty((n, 3), np.uint32), np.empty((n, 2), np.float64)
         self._chk(self.lib.svjg_cohort_hwe(self.h, gt.ctypes.data, None if ploidy is None else ploidy.ctypes.data, n, S, counts.ctypes.data,
                                            p.ctypes.data))

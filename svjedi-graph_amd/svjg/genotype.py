@@ -738,16 +738,20 @@ def _cohort_rows(call, rows, step, empty, min_support, err, ploidy=None):
     return CohortCalls(*_join_chunks(parts)) if parts else empty
 
 
+def _matrix_max_ploidy(ploidy):
+    """a cohort call's ploidy matrix or None -> (the matrix as the library reads it or None, max_ploidy: 2 without a matrix, else its maximum, at least 1)"""
+    ploidy = None if ploidy is None else np.ascontiguousarray(ploidy, dtype=np.uint8)
+    return ploidy, 2 if ploidy is None else max(1, int(ploidy.max())) if ploidy.size else 1
+
+
 def genotype_cohort_rows(ctx, rows, n_samples, min_support, err, ploidy=None, prior=False, step=None):
     """The cohort call over all rows -> CohortCalls.  ploidy None and no prior: svjg_genotype_cohort, gt (3: no call), pl[n, S, 3], site[n, 2] = NS,
     AC.  ploidy[n, S]: svjg_genotype_cohort_ploidy, gt (0xFF: no call), pl[n, S, max_ploidy + 1], site[n, 3] = NS, AN, AC; max_ploidy = the
     matrix's maximum, at least 1.  prior: svjg_genotype_cohort_prior, ploidy[n, S] or None (diploid), gt = the posterior calls (0xFF: none), site
     of them, and gq[n, S], af[n], em_steps[n].  step: rows per call (None: what fits 1 GiB)"""
     S = int(n_samples)
-    if ploidy is not None:
-        ploidy = np.ascontiguousarray(ploidy, dtype=np.uint8)
+    ploidy, max_ploidy = _matrix_max_ploidy(ploidy)
     plain = ploidy is None and not prior
-    max_ploidy = 2 if ploidy is None else max(1, int(ploidy.max())) if ploidy.size else 1
 
     def call(lo, hi, ms, e):
         if plain:
@@ -834,9 +838,7 @@ def cohort_qual_rows(ctx, rows, n_samples, ploidy, err, theta=COHORT_QUAL_THETA,
     """svjg_cohort_qual over all rows, in the row chunks of the cohort call (step: rows per call, None: cohort_chunk_rows of the plain call — a row's
     answer depends on no other row, so any chunking gives the same bytes).  ploidy[n, S] or None (diploid) -> (qual[n], mlac[n], chroms[n])"""
     _, call_err, _ = _call_args(0, err)
-    if ploidy is not None:
-        ploidy = np.ascontiguousarray(ploidy, dtype=np.uint8)
-    max_ploidy = 2 if ploidy is None else max(1, int(ploidy.max())) if ploidy.size else 1
+    ploidy, max_ploidy = _matrix_max_ploidy(ploidy)
     if step is None:
         step = cohort_chunk_rows(n_samples, None if ploidy is None else max_ploidy)
     parts = [ctx.cohort_qual(rows.sv_type[at:at + step], rows.slot[at:at + step], rows.ok[at:at + step], None if ploidy is None else ploidy[at:at + step],
@@ -969,34 +971,35 @@ def _ratio_text(a, b):
     return "%.6g" % (a / b) if b else "."
 
 
+def _calls_chunk_rows(n_samples, per_item, row_bytes, fixed):
+    """rows per call of a statistic over the run's calls (svjg_cohort_qc, svjg_cohort_hwe), so that it stays under 1 GiB and under the call's 2^32
+    rows: 1 byte an item, 2 with a ploidy array, row_bytes a row beside them, `fixed` a call whatever its rows, and the block's own 256"""
+    return max(1, min((1 << 32) - 1, (COHORT_CALL_BYTES - fixed - 256) // (max(1, int(n_samples)) * (2 if per_item else 1) + row_bytes)))
+
+
 def cohort_qc_chunk_rows(n_samples, per_item=False):
-    """rows per svjg_cohort_qc call, so that it stays under 1 GiB (svjg.h: 1 byte an item, 2 with a ploidy array, 3 bits of planes, 20 bytes a pair,
-    24 a sample) and under the call's 2^32 rows"""
+    """rows per svjg_cohort_qc call (svjg.h: 3 bits of planes an item; 20 bytes a pair, 24 a sample, and 24 a sample for the planes' last word begun)"""
     S = max(1, int(n_samples))
-    fixed = 20 * (S * (S - 1) // 2) + 24 * S + 24 * S + 256          # (the pairs, the samples, the planes' last word begun, the block's own bytes)
-    return max(1, min((1 << 32) - 1, (COHORT_CALL_BYTES - fixed) // (S * (2 if per_item else 1) + (3 * S + 7) // 8)))
+    return _calls_chunk_rows(S, per_item, (3 * S + 7) // 8, 20 * (S * (S - 1) // 2) + 24 * S + 24 * S)
 
 
-def _masked_calls(gt, done, ploidy):
-    """what cohort_qc_rows and cohort_hwe_rows hand to the device: gt with NO_CALL where done == 0, its shape, ploidy contiguous or None
-    -> (gt, n, S, ploidy)"""
+def _calls_chunks(call, chunk_rows, gt, done, ploidy, step):
+    """The one walk of cohort_qc_rows and cohort_hwe_rows: gt with NO_CALL where done == 0 and ploidy (contiguous, or None) go to call(gt, ploidy)
+    in chunks of `step` rows (None: chunk_rows(S, per_item)) -> the list of its answers, a chunk each (no row: empty)"""
     gt = np.where(np.asarray(done) != 0, np.asarray(gt, dtype=np.uint8), np.uint8(NO_CALL)).astype(np.uint8)
     n, S = gt.shape
-    if ploidy is not None:
-        ploidy = np.ascontiguousarray(ploidy, dtype=np.uint8)
-    return gt, n, S, ploidy
+    ploidy = None if ploidy is None else np.ascontiguousarray(ploidy, dtype=np.uint8)
+    step = chunk_rows(S, ploidy is not None) if step is None else int(step)
+    return [call(gt[at:at + step], None if ploidy is None else ploidy[at:at + step]) for at in range(0, n, step)]
 
 
 def cohort_qc_rows(ctx, gt, done, ploidy, step=None):
     """svjg_cohort_qc over all rows of a cohort run's calls: gt[n, S] and done[n, S] as CohortCalls has them — an item with done == 0 goes in as
     0xFF, not called whatever its ploidy —, ploidy[n, S] or None (diploid).  Rows in chunks of `step` (None: cohort_qc_chunk_rows); the chunks'
     integer outputs are summed in int64, so any chunking gives the same numbers.  -> (sample[S, 6], pair[S (S - 1) / 2, 5]) int64"""
-    gt, n, S, ploidy = _masked_calls(gt, done, ploidy)
-    if step is None:
-        step = cohort_qc_chunk_rows(S, ploidy is not None)
+    S = np.shape(gt)[1]
     sample, pair = np.zeros((S, 6), np.int64), np.zeros((S * (S - 1) // 2, 5), np.int64)
-    for at in range(0, n, int(step)):
-        s, p = ctx.cohort_qc(gt[at:at + step], None if ploidy is None else ploidy[at:at + step])
+    for s, p in _calls_chunks(ctx.cohort_qc, cohort_qc_chunk_rows, gt, done, ploidy, step):
         sample += s
         pair += np.asarray(p).reshape(-1, 5)
     return sample, pair
@@ -1061,25 +1064,17 @@ def hwe_fis(n_ref, n_het, n_alt):
 
 
 def cohort_hwe_chunk_rows(n_samples, per_item=False):
-    """rows per svjg_cohort_hwe call, so that it stays under 1 GiB (svjg.h: 1 byte an item, 2 with a ploidy array, 28 bytes a row) and under the
-    call's 2^32 rows"""
-    S = max(1, int(n_samples))
-    return max(1, min((1 << 32) - 1, (COHORT_CALL_BYTES - 256) // (S * (2 if per_item else 1) + 28)))
+    """rows per svjg_cohort_hwe call (svjg.h: 28 bytes a row)"""
+    return _calls_chunk_rows(n_samples, per_item, 28, 0)
 
 
 def cohort_hwe_rows(ctx, gt, done, ploidy, step=None):
     """svjg_cohort_hwe over all rows of a cohort run's calls: gt[n, S] and done[n, S] as CohortCalls has them — an item with done == 0 goes in as
     0xFF, not called whatever its ploidy, as in cohort_qc_rows —, ploidy[n, S] or None (diploid).  Rows in chunks of `step` (None:
     cohort_hwe_chunk_rows), concatenated: a row's numbers do not depend on its chunk.  -> (counts[n, 3] uint32, p[n, 2] float64)"""
-    gt, n, S, ploidy = _masked_calls(gt, done, ploidy)
-    if step is None:
-        step = cohort_hwe_chunk_rows(S, ploidy is not None)
-    counts, p = [np.zeros((0, 3), np.uint32)], [np.zeros((0, 2), np.float64)]
-    for at in range(0, n, int(step)):
-        c, q = ctx.cohort_hwe(gt[at:at + step], None if ploidy is None else ploidy[at:at + step])
-        counts.append(np.asarray(c, dtype=np.uint32).reshape(-1, 3))
-        p.append(np.asarray(q, dtype=np.float64).reshape(-1, 2))
-    return np.concatenate(counts), np.concatenate(p)
+    parts = _calls_chunks(ctx.cohort_hwe, cohort_hwe_chunk_rows, gt, done, ploidy, step)
+    return (np.concatenate([np.zeros((0, 3), np.uint32)] + [np.asarray(c, dtype=np.uint32).reshape(-1, 3) for c, _ in parts]),
+            np.concatenate([np.zeros((0, 2), np.float64)] + [np.asarray(q, dtype=np.float64).reshape(-1, 2) for _, q in parts]))
 
 
 def check_cohort_options(ploidy_file=None, prior=False, joint_ins=False, joint_prior=False, qual=False, theta=COHORT_QUAL_THETA, qc=None, hwe=False):
@@ -1136,8 +1131,9 @@ def run_cohort(list_path, vcf_path, out_path, min_support=3, err=0.00005, device
         calls = genotype_cohort_rows(ctx, rows, len(samples), min_support, err, ploidy, prior)
         joint = cohort_joint_sites(ctx, rows, calls.gt, calls.site, min_support, err, prior=joint_prior) if joint_ins else None
         site_qual = cohort_qual_rows(ctx, rows, len(samples), ploidy, err, theta) if qual else None
-        qc_counts = cohort_qc_rows(ctx, printed_gt(calls, joint), calls.done, ploidy) if qc is not None else None
-        site_hwe = cohort_hwe_rows(ctx, printed_gt(calls, joint), calls.done, ploidy) if hwe else None
+        printed = printed_gt(calls, joint) if qc is not None or hwe else None
+        qc_counts = cohort_qc_rows(ctx, printed, calls.done, ploidy) if qc is not None else None
+        site_hwe = cohort_hwe_rows(ctx, printed, calls.done, ploidy) if hwe else None
     finally:
         ctx.close()
     n_done = write_vcf_cohort(out_path, rows, names, calls, ploidy, joint, site_qual, site_hwe)

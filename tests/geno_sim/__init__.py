@@ -39,6 +39,15 @@ def f64(x):
     return np.ascontiguousarray(x, np.float64)
 
 
+def calls(gt, ploidy):
+    """a run's calls as the harness takes them -> (gt[n, S] uint8, ploidy the same or None, n, S)"""
+    gt = u8(gt)
+    if ploidy is not None:
+        ploidy = u8(ploidy)
+        assert ploidy.shape == gt.shape
+    return (gt, ploidy) + gt.shape
+
+
 def logfact_table(n):
     """log10(i!) for i < n in double-double (float64[n, 2]), with the host libm's log10"""
     tab = np.zeros((n, 2), np.float64)

@@ -20,8 +20,7 @@ extern "C" int genosim_hwe_run(const uint8_t *gt, const uint8_t *ploidy, uint64_
     const HweLayout L = hwe_layout(n_rows, S, ploidy != nullptr);
     std::vector<uint64_t> block = poisoned_block(L.total);
     uint8_t *base = (uint8_t *)block.data();
-    memcpy(base + L.gt, gt, n);
-    if (ploidy) memcpy(base + L.ploidy, ploidy, n);
+    stage_calls(base, L, gt, ploidy, n);
     memset(base + L.maxn, 0, 8);                                               // the launch's memset
     const uint8_t *d_gt = base + L.gt, *d_ploidy = ploidy ? base + L.ploidy : nullptr;
     uint32_t *d_counts = (uint32_t *)(base + L.counts);

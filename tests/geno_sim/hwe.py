@@ -2,7 +2,7 @@
 host harness (tests only)."""
 import numpy as np
 
-from tests.geno_sim import HWE, PTR, U32, U64, INT, u8, call, layout as _layout
+from tests.geno_sim import HWE, PTR, U32, U64, INT, calls, call, layout as _layout
 from tests.geno_sim import build_main                                                  # noqa: F401
 from tests.geno_sim.prior import width as segment_width                                # noqa: F401  (prior_segment_width: the lanes a row takes)
 
@@ -31,11 +31,7 @@ def row(n_ref, n_het, n_alt):
 
 def run(gt, ploidy=None, grid=0, n_cu=256):
     """the kernel's loops over a call (a grid of that many blocks; 0: the launch's own on n_cu units) -> (counts[n, 3] uint32, p[n, 2] float64)"""
-    gt = u8(gt)
-    n, S = gt.shape
-    if ploidy is not None:
-        ploidy = u8(ploidy)
-        assert ploidy.shape == gt.shape
+    gt, ploidy, n, S = calls(gt, ploidy)
     counts, p = np.zeros((n, 3), np.uint32), np.zeros((n, 2), np.float64)
     rc = call("genosim_hwe_run", INT, [PTR, PTR, U64, U32, U32, U32, PTR, PTR], gt, ploidy, n, S, int(grid), int(n_cu), counts, p)
     assert rc == 0, RUN_CODES.get(rc, rc)

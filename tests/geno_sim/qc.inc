@@ -19,8 +19,7 @@ extern "C" int genosim_qc_run(const uint8_t *gt, const uint8_t *ploidy, uint64_t
     const uint64_t n = n_rows * S, n_words = qc_words(n_rows), n_pairs = qc_pairs(S), n_plane_words = QC_PLANES * n_words * S;
     std::vector<uint64_t> block = poisoned_block(L.total);
     uint8_t *base = (uint8_t *)block.data();
-    memcpy(base + L.gt, gt, n);
-    if (ploidy) memcpy(base + L.ploidy, ploidy, n);
+    stage_calls(base, L, gt, ploidy, n);
     const uint8_t *d_gt = base + L.gt, *d_ploidy = ploidy ? base + L.ploidy : nullptr;
     uint64_t *planes = (uint64_t *)(base + L.planes);
     uint32_t *d_sample = (uint32_t *)(base + L.sample), *d_pair = (uint32_t *)(base + L.pair);

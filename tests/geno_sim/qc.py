@@ -1,7 +1,7 @@
 """The cohort sample QC (svjg_geno.h's QC routines inside a restatement of the loops of k_qc_planes and k_qc_pairs) through the host harness (tests only)."""
 import numpy as np
 
-from tests.geno_sim import QC, PTR, U32, U64, INT, u8, call, layout as _layout
+from tests.geno_sim import QC, PTR, U32, U64, INT, calls, call, layout as _layout
 from tests.geno_sim import build_main                                                  # noqa: F401
 
 RUN_CODES = {1: "a store outside its field", 2: "a pair written twice or never", 3: "a plane word never written", 4: "a bit set behind the last row"}
@@ -44,11 +44,7 @@ def pair_word(i3, j3):
 
 def run(gt, ploidy=None, grid_planes=0, grid_pairs=0):
     """both kernels' loops over a call (grids of that many blocks, 0: a block per unit of work) -> (sample[S, 6], pair[S (S - 1) / 2, 5]) uint32"""
-    gt = u8(gt)
-    n, S = gt.shape
-    if ploidy is not None:
-        ploidy = u8(ploidy)
-        assert ploidy.shape == gt.shape
+    gt, ploidy, n, S = calls(gt, ploidy)
     sample, pair = np.zeros((S, 6), np.uint32), np.zeros((S * (S - 1) // 2 + 1, 5), np.uint32)
     rc = call("genosim_qc_run", INT, [PTR, PTR, U64, U32, U32, U32, PTR, PTR], gt, ploidy, n, S, int(grid_planes), int(grid_pairs), sample, pair)
     assert rc == 0, RUN_CODES.get(rc, rc)

@@ -1,6 +1,6 @@
 """svjg_cohort_hwe on the device against the integer model (tests/cohort_hwe_model.py): counts bit for bit, HWE and EXCHET within the derived bound
 of tests/test_cohort_hwe.py; every segment width and one, two and three items a lane in both phases; the fixtures; the growth of the log10(i!)
-table; more rows than one trip of the grid; equal bytes from call to call and from chunk to chunk; the call's own block; the argument errors; and
+table; more rows than one trip of the grid; equal bytes from call to call and from chunk to chunk; the argument errors; and
 predict-genotype.py --cohort --cohort-hwe on the golden cohort beside every other cohort option.  The device's bytes are also compared with the host
 harness's (tests/geno_sim, topic hwe): the two differ in exp10 and in the table's log10 only, so the last bits of p may differ — the share of rows that do is
 printed, and only the model bound binds.  Needs an MI355X: run with -m gpu."""
@@ -115,50 +115,6 @@ def test_chunks_give_the_bytes_of_one_call(ctx, mode):
     for step in (1, 64, 65, n - 1):
         counts, p = genotype.cohort_hwe_rows(ctx, gt, done, ploidy, step)
         assert counts.tobytes() == one[0].tobytes() and p.tobytes() == one[1].tobytes(), step
-
-
-def test_a_block_of_its_own(ctx):
-    """a svjg_cohort_hwe call between a call and a reading of that call's outputs changes nothing of them: the diploid call's pinned views and
-    boundary bytes survive it, every other call returns what it returns on a context of its own with hwe calls in between, and the hwe call's own
-    bytes stay what they were"""
-    from svjg import capi
-    from tests.test_leg_blocks_gpu import CALLS, R, _bytes, _call, _case, _load
-    case = _case()
-    rng = np.random.default_rng(9)
-    gt, ploidy = draw(rng, 130, 70, "mixed")
-    want = check(ctx, gt, ploidy, "alone")
-    want = (want[0].tobytes(), want[1].tobytes())
-
-    def hwe(c):
-        got = c.cohort_hwe(gt, ploidy)
-        return (got[0].tobytes(), got[1].tobytes())
-    alone = {}
-    for which in CALLS:
-        c = capi.Context(0)
-        try:
-            _load(c, case)
-            alone[which] = _bytes(_call(c, case, which))
-        finally:
-            c.close()
-    c = capi.Context(0)
-    try:
-        _load(c, case)
-        assert hwe(c) == want and c.logfact_entries() > 0                     # (before any other call: the first table is the call's)
-        view = _call(c, case, "rows", view=True)[:4]
-        assert _bytes(view) == alone["rows"][:4]
-        assert hwe(c) == want
-        assert _bytes(view) == alone["rows"][:4] and c.boundary_flags(R).tobytes() == alone["rows"][4]
-        for which in CALLS[1:]:
-            got = _bytes(_call(c, case, which))
-            assert hwe(c) == want, which
-            assert got == alone[which], which
-            assert _bytes(view) == alone["rows"][:4] and c.boundary_flags(R).tobytes() == alone["rows"][4], which
-        qc = c.cohort_qc(gt, ploidy)
-        assert hwe(c) == want
-        again = c.cohort_qc(gt, ploidy)
-        assert qc[0].tobytes() == again[0].tobytes() and qc[1].tobytes() == again[1].tobytes()
-    finally:
-        c.close()
 
 
 def test_argument_errors_launch_nothing(ctx):

@@ -1,5 +1,5 @@
 """svjg_cohort_qc on the device against the numpy model (tests/cohort_qc_model.py), all bytes: the shapes at which k_qc_planes and k_qc_pairs take
-another path (tests/geno_sim/qc.py: constants), the largest triangle, chunked calls, the call's own block, the argument errors, and predict-genotype.py
+another path (tests/geno_sim/qc.py: constants), the largest triangle, chunked calls, the argument errors, and predict-genotype.py
 --cohort --cohort-qc on the golden cohort.  Needs an MI355X: run with -m gpu."""
 import os
 import subprocess
@@ -68,40 +68,6 @@ def test_one_call_equals_the_sum_of_its_chunks(ctx, mode):
     for step in (1, 64, 65, n - 1):
         sample, pair = genotype.cohort_qc_rows(ctx, gt, done, ploidy, step)
         assert sample.dtype == pair.dtype == np.int64 and np.array_equal(sample, one[0]) and np.array_equal(pair, one[1]), step
-
-
-def test_a_block_of_its_own(ctx):
-    """a svjg_cohort_qc call between a call and a reading of that call's outputs changes nothing of them: the diploid call's pinned views and
-    boundary bytes survive it, and every other call returns what it returns on a context of its own with qc calls in between"""
-    from svjg import capi
-    from tests.test_leg_blocks_gpu import CALLS, R, _bytes, _call, _case, _load
-    case = _case()
-    rng = np.random.default_rng(9)
-    gt, ploidy = random_call(rng, 130, 70, "mixed")
-    want_qc = M.qc(gt, ploidy)
-    alone = {}
-    for which in CALLS:
-        c = capi.Context(0)
-        try:
-            _load(c, case)
-            alone[which] = _bytes(_call(c, case, which))
-        finally:
-            c.close()
-    c = capi.Context(0)
-    try:
-        _load(c, case)
-        assert _equal(c.cohort_qc(gt, ploidy), want_qc) and c.logfact_entries() > 0     # (before any other call: the leg builds the first table)
-        view = _call(c, case, "rows", view=True)[:4]
-        assert _bytes(view) == alone["rows"][:4]
-        assert _equal(c.cohort_qc(gt, ploidy), want_qc)
-        assert _bytes(view) == alone["rows"][:4] and c.boundary_flags(R).tobytes() == alone["rows"][4]
-        for which in CALLS[1:]:
-            got = _bytes(_call(c, case, which))
-            assert _equal(c.cohort_qc(gt, ploidy), want_qc), which
-            assert got == alone[which], which
-            assert _bytes(view) == alone["rows"][:4] and c.boundary_flags(R).tobytes() == alone["rows"][4], which
-    finally:
-        c.close()
 
 
 def test_argument_errors_launch_nothing(ctx):

@@ -1,6 +1,8 @@
-"""The eight step-by-step genotype calls share one host leg (svjg_capi.hip: genotype_leg; the three cohort calls one more, cohort_call, the three
-site calls another, sites_call) and keep a block each (svjg_ctx::leg[]): run on ONE context in any of four orders, every call returns the bytes it
-returns on a context of its own, whichever calls ran in between, and a view of the diploid call's pinned block outlives the other seven.  Needs an MI355X: run with -m gpu."""
+"""The eleven step-by-step calls share one host leg (svjg_capi.hip: genotype_leg; the three cohort calls one more, cohort_call, the three site
+calls another, sites_call, the two statistics over a run's calls a fourth, calls_leg) and keep a block each (svjg_ctx::leg[]).  The eight genotype
+calls (CALLS) run on ONE context in any of four orders: every call returns the bytes it returns on a context of its own, whichever calls ran in
+between, and a view of the diploid call's pinned block outlives the other seven.  The three statistics (STATS: svjg_cohort_qc, svjg_cohort_hwe,
+svjg_cohort_qual) run between the eight, one statistic a test: nothing of the eleven disturbs another.  Needs an MI355X: run with -m gpu."""
 import numpy as np
 import pytest
 
@@ -10,6 +12,7 @@ NONE = 0xFFFFFFFF
 R, S, N_SLOTS = 65, 3, 90              # two waves of rows with a ragged end; three samples; the sites' members lie behind the rows' slots
 MS, ERR = 3, 5e-5
 CALLS = ("rows", "ploidy", "sites", "cohort", "cohort_ploidy", "cohort_prior", "cohort_sites", "cohort_sites_prior")
+STATS = ("cohort_qc", "cohort_hwe", "cohort_qual")
 
 
 def _case():
@@ -124,5 +127,74 @@ def test_every_call_in_a_block_of_its_own(case, alone, order):
             assert ctx.boundary_flags(R).tobytes() == alone["rows"][4], f"the boundary bytes after {which}"
         assert ctx.logfact_entries() > 65536                         # the table grew inside a leg that was not the first
         assert _bytes(_call(ctx, case, order[-1])) == alone["rows"]
+    finally:
+        ctx.close()
+
+
+def _statistic(case, stat):
+    """-> (the arguments of Context method `stat`, first(ctx) -> its arrays, held to the statistic's expected answer).  cohort_qc and cohort_hwe: 130
+    rows x 70 samples at mixed ploidy, against tests/cohort_qc_model.py and by tests/test_cohort_hwe_gpu.py's check.  cohort_qual: the case's own rows
+    and samples, the smallest shape with two waves of rows, a ragged end and every ploidy class; a quality on at least one row."""
+    if stat == "cohort_qual":
+        args = (case["t"], case["slot"], case["ok"], case["item_ploidy"], 8, ERR)
+
+        def first(ctx):
+            out = ctx.cohort_qual(*args)
+            assert np.isfinite(out[0]).any()
+            return out
+    elif stat == "cohort_qc":
+        from tests import cohort_qc_model
+        from tests.test_cohort_qc import random_call
+        from tests.test_cohort_qc_gpu import _equal
+        args = random_call(np.random.default_rng(9), 130, 70, "mixed")
+
+        def first(ctx):
+            out = ctx.cohort_qc(*args)
+            assert _equal(out, cohort_qc_model.qc(*args))
+            return out
+    else:
+        from tests.test_cohort_hwe import draw
+        from tests.test_cohort_hwe_gpu import check
+        args = draw(np.random.default_rng(9), 130, 70, "mixed")
+
+        def first(ctx):
+            return check(ctx, *args, "alone")
+    return args, first
+
+
+@pytest.mark.parametrize("stat", STATS)
+def test_a_statistic_in_a_block_of_its_own(case, alone, stat):
+    """a statistic's call between a call and a reading of that call's outputs changes nothing of them: the diploid call's pinned views and boundary
+    bytes survive it, every other call returns what it returns on a context of its own with the statistic's calls in between, and the statistic's
+    own bytes stay what they are on a fresh context"""
+    from svjg import capi
+    args, first = _statistic(case, stat)
+
+    def again(ctx):
+        return _bytes(getattr(ctx, stat)(*args))
+
+    def rows_intact(ctx, view):
+        return _bytes(view) == alone["rows"][:4] and ctx.boundary_flags(R).tobytes() == alone["rows"][4]
+    ctx = capi.Context(0)
+    try:
+        _load(ctx, case)
+        want = _bytes(first(ctx))
+    finally:
+        ctx.close()
+    ctx = capi.Context(0)
+    try:
+        _load(ctx, case)
+        assert _bytes(first(ctx)) == want and ctx.logfact_entries() > 0      # (before any other call: the first table is the call's leg's)
+        view = _call(ctx, case, "rows", view=True)[:4]
+        assert _bytes(view) == alone["rows"][:4]
+        assert again(ctx) == want and rows_intact(ctx, view)
+        for which in CALLS[1:]:
+            got = _bytes(_call(ctx, case, which))
+            assert again(ctx) == want, which
+            assert got == alone[which], which
+            assert rows_intact(ctx, view), which
+        if stat == "cohort_hwe":                                             # the two that stage through calls_leg, one behind the other
+            qc = _bytes(ctx.cohort_qc(*args))
+            assert again(ctx) == want and _bytes(ctx.cohort_qc(*args)) == qc
     finally:
         ctx.close()
